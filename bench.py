@@ -67,7 +67,25 @@ def parse():
                          "'auto' (direct when every rank can set it up and it passes its cross-check against RCCL, else RCCL)")
     ap.add_argument("--no-profile-events", action="store_true",
                     help="do not record per-kernel HIP events in the timed region")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the last timed step returned as DIR/<name>.npy (float64): pose, stats, "
+                         "n_corr_hist — for comparing two builds output for output (the inputs are seeded)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(d, pose, st):
+    """What the caller of the timed entry receives (sageicp_register_frame_resident): the pose and the
+    statistics that describe the computation — the wall-clock fields of the statistics are left out."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "pose.npy"), np.asarray(pose, dtype=np.float64))        # qx qy qz qw tx ty tz
+    np.save(os.path.join(d, "stats.npy"), np.array(
+        [st.iterations, st.converged, st.n_queries, st.n_corr_first, st.n_corr_last, st.last_step_norm],
+        dtype=np.float64))
+    np.save(os.path.join(d, "n_corr_hist.npy"), np.array(st.n_corr_hist[:], dtype=np.float64))
 
 
 def self_launch(args):
@@ -568,6 +586,9 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pose, stats[-1])
 
     # the host-buffer entry the C++ shim calls (frame uploaded inside the call), not the headline
     host_entry_ms = None

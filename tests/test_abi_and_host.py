@@ -263,7 +263,10 @@ def test_multi_device_map_replicates_mutations_on_the_host(sage):
     pts = rng.uniform(-20, 20, size=(4000, 4))
     pts[:, 3] = rng.choice([0, 40, 70], size=len(pts))
     a = sage.VoxelHashMap(1.0, 15.0)
-    a.set_devices([0, 1, 2])
+    # three copies on ordinals that exist where a device is visible (the library refuses the others there; a
+    # device may hold more than one copy), 0 1 2 where none is
+    n = sage.device_count()
+    a.set_devices([k % n if n else k for k in range(3)])
     assert a.num_devices() == 3
     a.AddPoints(pts)
     b = sage.VoxelHashMap(1.0, 15.0)
@@ -329,3 +332,14 @@ def test_roofline_frac_is_null_without_counters_of_this_build():
     other = bench.apply_counters(fresh(), entry, h, False, 23.3e6, 127.7e6)          # counters of k_loop, the run went through k_icp
     assert other["frac"] is None and not other["counters_fresh"] and "k_loop" in other["frac_basis"]
     assert bench.apply_counters(fresh(), None, h, True, 1.0, 1.0)["frac"] is None
+
+
+def test_bench_refuses_fewer_than_one_timed_step():
+    """bench.py --steps sets the number of timed steps; ms_per_step is undefined without one, so 0 is an argument
+    error (before any device is touched)"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr

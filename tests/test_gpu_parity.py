@@ -950,6 +950,35 @@ def test_direct_exchange_timeout_is_reported_not_hung(gpu_sage):
     assert "did not arrive in time" in run.stderr and "no RCCL side to fall back to" in run.stderr
 
 
+def test_bench_dump_outputs_are_what_the_timed_path_returns(gpu_sage, tmp_path):
+    """bench.py --dump-outputs DIR: the pose and statistics of the last timed step, float64, the same as the resident
+    entry returns for the same seeded frame in this process; `steps` and `ms_per_step` describe the timed region"""
+    import json
+    import subprocess
+    import sys
+    from sage_icp_amd import synthetic as syn
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "out"
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--scale", "0.05", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                         capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stderr[-3000:]
+    line = json.loads(run.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    pose, stats, hist = (np.load(d / (n + ".npy")) for n in ("pose", "stats", "n_corr_hist"))
+    assert pose.dtype == stats.dtype == hist.dtype == np.float64
+    assert pose.shape == (7,) and stats.shape == (6,) and hist.shape == (64,)
+    assert stats[0] == line["config"]["iterations_per_frame"] and stats[2] == line["config"]["scan_points"]
+    assert list(stats[3:5]) == line["config"]["correspondences_first_last"]
+    p = syn.PARAMS["cold"]
+    w = syn.make_workload("c2", lambda: gpu_sage.VoxelHashMap(1.0, 100.0), scale=0.05)
+    f = gpu_sage.Frame(w["map"], w["scan"])
+    ref, st = gpu_sage.register_frame(f, w["map"], gpu_sage.IDENTITY, p["max_dist"], p["kernel"], p["sem_th"],
+                                      return_stats=True)
+    assert stats[0] == st.iterations and stats[3] == st.n_corr_first and stats[4] == st.n_corr_last
+    assert np.allclose(pose, ref, rtol=0, atol=1e-12)
+
+
 def test_profiling_stats(gpu_sage, oracle, monkeypatch):
     monkeypatch.setenv("SAGEICP_LOOP", "0")       # per-kernel times of the launch-per-iteration loop (k_loop: tests/test_loop_kernel.py)
     w, om = _workload(gpu_sage, oracle, "c2", 0.05)
