@@ -6,7 +6,6 @@ usage: python profiles/collect.py <tag> [workload] [params]"""
 import collections
 import csv
 import glob
-import gzip
 import json
 import os
 import shutil
@@ -48,8 +47,8 @@ for sub in ("pmc_fetch", "pmc_tcc", "pmc_sq", "pmc_sq2", "pmc_mem"):
     p = os.path.join(src, sub, "pmc_counter_collection.csv")
     if not os.path.exists(p):
         continue
-    with open(p, "rb") as f, gzip.open(os.path.join(dst, sub + ".csv.gz"), "wb") as g:
-        g.write(f.read())
+    # (the per-dispatch CSV itself stays out of the repository — megabytes per pass; summary.md keeps the
+    # per-counter means, and the entry below the means per iteration)
     acc = collections.defaultdict(list)
     dur = []
     for r in csv.DictReader(open(p)):
@@ -81,7 +80,7 @@ entry = {
     "workload": key,
     "iterations_per_launch": int(per),
     "source_sha256": device_source_hash(),
-    "counters_source": "profiles/%s/%s/pmc_*.csv.gz (rocprofv3 --pmc, separate passes, means per iteration "
+    "counters_source": "profiles/%s/%s/summary.md (rocprofv3 --pmc, separate passes, means per iteration "
                        "over %d launches%s)"
                        % (tag, key, int(mean.get("_launches_SQ_INSTS_VALU", mean.get("_launches_FETCH_SIZE", 0))),
                           "; k_loop: counters of the counter-collection twin of the library (solving wave inside the grid: "

@@ -1,4 +1,4 @@
-"""Where the solving wave's ~3 us go (-DSAGE_LOOP_TIMING build): assemble + LDL^T | SE3 exp | composition + rotation matrix | norm | rest.
+"""Where the solving wave's time goes (-DSAGE_LOOP_TIMING build): solve | SE3 exp (+ the step norm's sqrt) | composition + rotation matrix | norm test | rest.
     python profiles/solve_split.py [workload c1]"""
 import ctypes as C
 import os
@@ -31,9 +31,10 @@ n = min(IT, st.iterations) - 1
 r = slice(3, n)
 print("%s: mean over iterations 3..%d, us:" % (name, n - 1))
 print("   counts complete -> sums in fp64          %.2f" % (sv[r, 1] - sv[r, 0]).mean())
-print("   assemble + pivoted LDL^T + substitutions %.2f" % (s2[r, 0] - sv[r, 1]).mean())
-print("   SE3 exp (sqrt, sincos, divisions)        %.2f" % (s2[r, 1] - s2[r, 0]).mean())
+print("   solve (structured; 6x6 LDL^T if refused) %.2f" % (s2[r, 0] - sv[r, 1]).mean())
+print("   SE3 exp + sqrt of the step norm          %.2f" % (s2[r, 1] - s2[r, 0]).mean())
 print("   composition (2 lanes) + rotation matrix  %.2f" % (s2[r, 2] - s2[r, 1]).mean())
-print("   norm of the step (sqrt)                  %.2f" % (s2[r, 3] - s2[r, 2]).mean())
+print("   test of the step norm                    %.2f" % (s2[r, 3] - s2[r, 2]).mean())
 print("   state, LDS hand-over                     %.2f" % (sv[r, 2] - s2[r, 3]).mean())
 print("   publish                                  %.2f" % (sv[r, 3] - sv[r, 2]).mean())
+print("   counts complete -> published, in all     %.2f" % (sv[r, 3] - sv[r, 0]).mean())

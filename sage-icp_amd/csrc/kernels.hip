@@ -1456,13 +1456,22 @@ struct WaveLanes {
         s0 = readlane_f64(sv, 0); c0 = readlane_f64(cv, 0);
         s1 = readlane_f64(sv, 1); c1 = readlane_f64(cv, 1);
     }
+    static __device__ __forceinline__ void sqrt2(double a0, double a1, double &r0, double &r1) {
+        const int lane = static_cast<int>(threadIdx.x & 63u);
+        const double v = sqrt(lane == 1 ? a1 : a0);
+        r0 = readlane_f64(v, 0);
+        r1 = readlane_f64(v, 1);
+    }
+    // (the operands are uniform, so is b: taken as the wave's, a scalar branch)
+    static __device__ __forceinline__ bool uniform(bool b) { return __all(b); }
 };
 
 // ------------------------------------------------------------------------------ finish_iteration
 // Executed by ONE workgroup of 1024 threads once per ICP iteration (k_fin): fixed-order reduction
-// of the workgroup partials of k_icp (bit-reproducible), then the first wave assembles the 6x6
-// normal equations from the 16 closed-form sums, solves them (register-resident pivoted LDL^T),
-// applies SE3 exp, composes the pose and tests convergence (Registration.cpp:92-93,135-137).
+// of the workgroup partials of k_icp (bit-reproducible), then the first wave solves the normal
+// equations from the 16 closed-form sums (se3_math.h solve_normal_equations_t: the block-structured
+// solve, the register-resident pivoted 6x6 LDL^T where its guard refuses), applies SE3 exp, composes
+// the pose and tests convergence (Registration.cpp:92-93,135-137).
 #ifdef SAGE_GN_TIMING
 __device__ unsigned long long g_gn_phase[16];
 #define FIN_STAMP(i) do { if (threadIdx.x == 0) fin_t[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -1610,13 +1619,10 @@ __device__ __forceinline__ void solve_and_publish(IcpState *st, const double *S,
 #endif
     FIN_STAMP(1);
     const int lane = static_cast<int>(threadIdx.x);
-    double JTJ[36], JTr[6], neg[6], x[6], est[7];
-    assemble_normal_equations(S, JTJ, JTr);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) neg[i] = -JTr[i];
-    ldlt_solve6_t<WaveLanes>(JTJ, neg, x);
+    double x[6], est[7], nrm;
+    solve_normal_equations_t<WaveLanes>(S, x);
     FIN_STAMP(2);
-    se3_exp_t<WaveLanes>(x, est);
+    se3_exp_sqrt_t<WaveLanes>(x, est, SAGE_SQNORM6(x), nrm);        // nrm = |x|, beside the exponential's sqrt
     FIN_STAMP(3);
 
     // the two compositions (Registration.cpp:135 and the cumulative pose) on lanes 0 and 1
@@ -1635,7 +1641,6 @@ __device__ __forceinline__ void solve_and_publish(IcpState *st, const double *S,
     // round trip on one serial lane — except where those ulps could matter: a step within 1e-12
     // (relative 1e-8; the two differ by ~1e-19 there) of the stop threshold, or |omega| >= 3,
     // goes through the exact log so that the stop iteration is the reference's in every case.
-    double nrm = sqrt(SAGE_SQNORM6(x));
     if (!(x[3] * x[3] + x[4] * x[4] + x[5] * x[5] < 9.0) ||
         fabs(nrm - kEstimationThreshold) < 1e-12) {
         double lg[6];
@@ -1791,7 +1796,7 @@ constexpr int kLoopTimedIters = 32, kLoopTimedWgs = 2048;
 __device__ unsigned long long g_loop_wg[kLoopTimedIters][kLoopTimedWgs][4];     // counted in | pose held | a wave took a unit beyond one per wave | ... finished it
 __device__ unsigned g_loop_wginfo[kLoopTimedIters][kLoopTimedWgs][4];     // HW_ID | max points of a query | stale queries | points
 __device__ unsigned long long g_loop_solver[kLoopTimedIters][4];
-__device__ unsigned long long g_loop_solver2[kLoopTimedIters][4];      // inside the solve: after the LDL^T | the exponential | the composition | the norm
+__device__ unsigned long long g_loop_solver2[kLoopTimedIters][4];      // inside the solve: after the solve | the exponential (and the sqrt of the step norm) | the composition | the norm test
 __device__ unsigned long long g_loop_wave[kLoopTimedIters][kLoopTimedWgs][8][2];      // per wave: its FIRST unit of the iteration: end stamp | start stamp (low 32) << 32 ... see LOOP_STAMP_WAVE
 __device__ unsigned long long g_loop_phase[16];     // [0..7] cycles per body phase, [8] wait for the pose, [9] closing a workgroup, [10] group passes
 #define LOOP_STAMP_SOLVER(it, k) do { if ((it) < kLoopTimedIters && (threadIdx.x & 63u) == 0u) g_loop_solver[it][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -1998,13 +2003,10 @@ __device__ __forceinline__ unsigned loop_finish_iteration(const LoopParams &L, c
     }
 
     // 3. solve, compose, test (Registration.cpp:92-93,135-137) — as k_fin's solve_and_publish
-    double JTJ[36], JTr[6], neg[6], x[6], est[7];
-    assemble_normal_equations(S, JTJ, JTr);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) neg[i] = -JTr[i];
-    ldlt_solve6_t<WaveLanes>(JTJ, neg, x);
+    double x[6], est[7], nrm;
+    solve_normal_equations_t<WaveLanes>(S, x);
     LOOP_STAMP_SOLVER2(it, 0);
-    se3_exp_t<WaveLanes>(x, est);
+    se3_exp_sqrt_t<WaveLanes>(x, est, SAGE_SQNORM6(x), nrm);        // nrm = |x|, beside the exponential's sqrt
     LOOP_STAMP_SOLVER2(it, 1);
     double rhs[7], Tn[7];
     {
@@ -2022,7 +2024,6 @@ __device__ __forceinline__ unsigned loop_finish_iteration(const LoopParams &L, c
     double Rn[9];
     quat_to_mat(Tn, Rn);
     LOOP_STAMP_SOLVER2(it, 2);
-    double nrm = sqrt(SAGE_SQNORM6(x));
     if (!(x[3] * x[3] + x[4] * x[4] + x[5] * x[5] < 9.0) || fabs(nrm - kEstimationThreshold) < 1e-12) {
         double lg[6];                                      // see solve_and_publish
         se3_log(est, lg);

@@ -2,7 +2,7 @@
 // Pose layout: T[7] = {qx, qy, qz, qw, tx, ty, tz} == Sophus::SE3d::data().
 //
 // These replace the third-party arithmetic at the reference's call sites
-//   Registration.cpp:92  JTJ.ldlt().solve(-JTr)      -> ldlt_solve6
+//   Registration.cpp:92  JTJ.ldlt().solve(-JTr)      -> solve_normal_equations (ldlt_solve6 where it must)
 //   Registration.cpp:93  Sophus::SE3d::exp(x)        -> se3_exp
 //   Registration.cpp:135 estimation * T_icp          -> se3_mul
 //   Registration.cpp:137 estimation.log().norm()     -> se3_log
@@ -73,14 +73,18 @@ struct SerialLanes {
         s0 = sin(a0); c0 = cos(a0);
         s1 = sin(a1); c1 = cos(a1);
     }
+    static SAGE_HD void sqrt2(double a0, double a1, double &r0, double &r1) {
+        r0 = sqrt(a0);
+        r1 = sqrt(a1);
+    }
+    // a decision every lane of the caller takes the same way (the wave policy takes it once, for the wave)
+    static SAGE_HD bool uniform(bool b) { return b; }
 };
 
-// exp: tangent a = (upsilon, omega), translation first.
+// exp: tangent a = (upsilon, omega), translation first; th2 = |omega|^2 as se3_exp_t forms it, th its sqrt.
 template <class Lanes>
-SAGE_HD inline void se3_exp_t(const double a[6], double T[7]) {
+SAGE_HD inline void se3_exp_core_t(const double a[6], const double th2, const double th, double T[7]) {
     const double wx = a[3], wy = a[4], wz = a[5];
-    const double th2 = wx * wx + wy * wy + wz * wz;
-    const double th = sqrt(th2);
     double imag, real, A, B;   // q = (imag*w, real); V = I + A*W + B*W^2
     if (th < 1e-10) {
         const double th4 = th2 * th2;
@@ -109,6 +113,20 @@ SAGE_HD inline void se3_exp_t(const double a[6], double T[7]) {
     T[4] = ux + A * cx + B * ccx;
     T[5] = uy + A * cy + B * ccy;
     T[6] = uz + A * cz + B * ccz;
+}
+template <class Lanes>
+SAGE_HD inline void se3_exp_t(const double a[6], double T[7]) {
+    const double th2 = a[3] * a[3] + a[4] * a[4] + a[5] * a[5];
+    se3_exp_core_t<Lanes>(a, th2, sqrt(th2), T);
+}
+// exp, and r = sqrt(n2) on the side: a caller's square root (the step norm of the ICP iteration) taken
+// beside the exponential's own instead of after it (Lanes::sqrt2 — the same two square roots, bit for bit).
+template <class Lanes>
+SAGE_HD inline void se3_exp_sqrt_t(const double a[6], double T[7], const double n2, double &r) {
+    const double th2 = a[3] * a[3] + a[4] * a[4] + a[5] * a[5];
+    double th;
+    Lanes::sqrt2(th2, n2, th, r);
+    se3_exp_core_t<Lanes>(a, th2, th, T);
 }
 SAGE_HD inline void se3_exp(const double a[6], double T[7]) { se3_exp_t<SerialLanes>(a, T); }
 
@@ -287,5 +305,89 @@ SAGE_HD inline void assemble_normal_equations(const double *S, double *JTJ, doub
     JTr[0] = S[kWrx]; JTr[1] = S[kWry]; JTr[2] = S[kWrz];
     JTr[3] = S[kWcx]; JTr[4] = S[kWcy]; JTr[5] = S[kWcz];
 }
+
+// The step of an ICP iteration, JTJ x = -JTr (Registration.cpp:92), from the 16 sums, by the block
+// structure assemble_normal_equations gives JTJ (a = Sws, M = Sw(|s|^2 I - s s^T), w = Sw):
+//     JTJ = [ w I      hat(a)^T ]        x = [t; omega],  -JTr = [g_t; g_w]
+//           [ hat(a)   M        ]
+// The translation block is eliminated in closed form.  With c = a / w:
+//     S omega = g_w - c x g_t,   S = M - (|a|^2 I - a a^T) / w  (the inertia about the weighted centroid)
+//     t       = g_t / w + c x omega
+// S omega = r is solved by cofactors: adj(S) r on every lane, then one division per component on three
+// lanes.  The chain is two divisions and a few dozen products, against the generic pivoted 6x6 LDL^T's
+// five rounds of divisions and its run-time pivot selects.
+//
+// Guard.  The structured step is taken only where it is a well-posed solve of the same system; everywhere
+// else the caller's answer is ldlt_solve6_t's, bit for bit (its pseudo-inverse of zero pivots is what the
+// degenerate sets — no pairs, one pair, collinear pairs — rely on).  It is refused when
+//   - w is not positive (no pairs: ldlt_solve6 returns x = 0);
+//   - some S_ii < 2^-16 M_ii: forming S_ii cancels log2(M_ii / S_ii) bits of M_ii — a frame far from the
+//     origin (|centroid| >> spread: UTM coordinates).  Rounding then perturbs S_ii by a few ulps of M_ii,
+//     at most ~2^-50 M_ii, so within the bound S_ii keeps a relative error under ~2^-34 (6e-11): a system
+//     as well posed as the frame's geometry, with room below the 1e-10 the two solves agree to;
+//   - a pivot of the LDL^T of S in the order 0, 1, 2 (S_00, C_22 / S_00, det / C_22) falls below 2^-16 of
+//     its diagonal entry, or is not positive: S (nearly) singular — collinear pairs, or one pair, where the
+//     rotation about the line is left to the rank-deficient rule of the 6x6 solve;
+//   - the result is not finite.
+// Each bound is 2^-16: a tighter pivot bound would only raise the condition number accepted; the looser
+// (2^-20 .. 2^-24) already fails the 1e-10 agreement on frames at 10 km (tests/test_structured_solve.py).
+// Every lane of the caller takes the same branch (Lanes::uniform).  Every array index is a compile-time
+// constant (see ldlt_solve6_t).
+constexpr double kStructuredSolveBound = 1.0 / 65536.0;
+
+template <class Lanes>
+SAGE_HD inline bool structured_solve_t(const double *S, double *x) {
+    const double w = S[kW], ax = S[kWsx], ay = S[kWsy], az = S[kWsz];
+    const double xx = S[kWxx], xy = S[kWxy], xz = S[kWxz], yy = S[kWyy], yz = S[kWyz], zz = S[kWzz];
+    const double gtx = -S[kWrx], gty = -S[kWry], gtz = -S[kWrz];
+    const double gwx = -S[kWcx], gwy = -S[kWcy], gwz = -S[kWcz];
+    const double iw = 1.0 / w;
+    const double cx = ax * iw, cy = ay * iw, cz = az * iw;
+    const double m00 = yy + zz, m11 = xx + zz, m22 = xx + yy;          // the diagonal of M, as assembled
+    const double s00 = m00 - (ay * cy + az * cz);
+    const double s11 = m11 - (ax * cx + az * cz);
+    const double s22 = m22 - (ax * cx + ay * cy);
+    const double s01 = ax * cy - xy, s02 = ax * cz - xz, s12 = ay * cz - yz;
+    const double r0 = gwx - (cy * gtz - cz * gty);
+    const double r1 = gwy - (cz * gtx - cx * gtz);
+    const double r2 = gwz - (cx * gty - cy * gtx);
+    // cofactors (S and adj(S) symmetric)
+    const double c00 = s11 * s22 - s12 * s12, c11 = s00 * s22 - s02 * s02, c22 = s00 * s11 - s01 * s01;
+    const double c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s11 * s02, c12 = s01 * s02 - s00 * s12;
+    const double det = s00 * c00 + s01 * c01 + s02 * c02;
+    const double k = kStructuredSolveBound;
+    bool ok = w > 0.0 && w <= 1.7976931348623157e308 && s00 > 0.0 && s11 > 0.0 && s22 > 0.0 &&
+              s00 >= k * m00 && s11 >= k * m11 && s22 >= k * m22 &&
+              c22 >= k * (s00 * s11) && det >= k * (s22 * c22);
+    double num[6], den[6], om[6];
+    num[0] = c00 * r0 + c01 * r1 + c02 * r2;
+    num[1] = c01 * r0 + c11 * r1 + c12 * r2;
+    num[2] = c02 * r0 + c12 * r1 + c22 * r2;
+    num[3] = 0.0; num[4] = 0.0; num[5] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) den[i] = i < 3 ? det : 1.0;
+    Lanes::divide6(num, den, om);
+    x[3] = om[0]; x[4] = om[1]; x[5] = om[2];
+    x[0] = gtx * iw + (cy * om[2] - cz * om[1]);
+    x[1] = gty * iw + (cz * om[0] - cx * om[2]);
+    x[2] = gtz * iw + (cx * om[1] - cy * om[0]);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) ok = ok && fabs(x[i]) <= 1.7976931348623157e308;       // (false for NaN)
+    return Lanes::uniform(ok);
+}
+
+// JTJ x = -JTr from the 16 sums: the structured solve where its guard accepts, else ldlt_solve6_t.  The
+// solve of every device path (k_fin, the one-launch loops) — one solve, so that they agree bit for bit.
+template <class Lanes>
+SAGE_HD inline void solve_normal_equations_t(const double *S, double *x) {
+    if (structured_solve_t<Lanes>(S, x)) return;
+    double JTJ[36], JTr[6], neg[6];
+    assemble_normal_equations(S, JTJ, JTr);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) neg[i] = -JTr[i];
+    ldlt_solve6_t<Lanes>(JTJ, neg, x);
+}
+SAGE_HD inline bool structured_solve(const double *S, double *x) { return structured_solve_t<SerialLanes>(S, x); }
+SAGE_HD inline void solve_normal_equations(const double *S, double *x) { solve_normal_equations_t<SerialLanes>(S, x); }
 
 }  // namespace sageicp
