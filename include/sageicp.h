@@ -57,7 +57,10 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * sageicp_comm_describe, sageicp_map_pointcloud served from the HBM copy, sageicp_map_point_slots
  * (size-classed voxel storage).   3: sageicp_stats names its loop form (single_launch in the slot of
  * reserved0), sageicp_pipeline_prefetch_wait, non-finite input refused (SAGEICP_ERR_INVALID) at every entry
- * that would cast it.   4: sageicp_map_loop_status, sageicp_reload_env (additions only). */
+ * that would cast it.   4: sageicp_map_loop_status, sageicp_reload_env; then the dynamic vehicle filter —
+ * sageicp_preprocess_dynamic, sageicp_cluster_emission_order, sageicp_dynfilter_info and the pipeline's
+ * sageicp_pipeline_set_dynamic_vehicle_filter / sageicp_pipeline_dynamic_filter_info (additions only: no
+ * existing struct or entry changed). */
 #define SAGEICP_ABI_VERSION 4
 
 /* Filled by sageicp_register_frame*.  Times are microseconds. */
@@ -307,14 +310,43 @@ int sageicp_voxel_downsample(const double *frame_xyzl, uint64_t n, int n_groups,
                              const double *group_voxel_size, double vox_scale, double *out_xyzl,
                              uint64_t *n_out, int device);
 
+/* Preprocess() with dynamic_vehicle_filter == true: core/Preprocessing.cpp:95-172, on the device (dyn_filter.hip).
+ * The crop is the filter-off branch's.  A kept point whose label (static_cast<uint32_t>, after zeroing beyond
+ * label_max_range) is in dynamic_labels is a vehicle point; the vehicle points are clustered like PCL's
+ * EuclideanClusterExtraction (fp32 copies, connected under squared distance < 0.25f, at least 5 points) and a
+ * cluster is kept iff its points have more than static_cast<int>(dy_th * size) neighbours within 0.5 m whose label
+ * is in landmark_labels.  out (capacity n*4 doubles): the other kept points in frame order, then the kept clusters
+ * in PCL's order (sageicp_cluster_emission_order), each in frame order.  Without vehicle points the result is
+ * sageicp_preprocess's.  A non-finite label of a kept point refuses the call (SAGEICP_ERR_INVALID).
+ * info (optional): what the filter saw.  Assumptions about PCL / FLANN: DESIGN.md, D7. */
+typedef struct sageicp_dynfilter_info {
+    uint64_t vehicle_points;    /* kept points with a dynamic label */
+    uint64_t landmark_points;   /* kept points with a landmark label */
+    uint64_t clusters;          /* connected components of >= 5 vehicle points (PCL's clusters) */
+    uint64_t clusters_kept;     /* ... that passed the static test (parked vehicles) */
+    uint64_t points_removed;    /* vehicle points dropped: moving clusters and components of < 5 points */
+    double us_wall;             /* host wall time of the filter, both host round trips included */
+    double us_host;             /* of which the host step: waiting for the cluster table, the order replay, the test */
+    double us_device;           /* device time of the filter's launches (HIP events; 0 unless sageicp_set_profiling) */
+} sageicp_dynfilter_info;
+int sageicp_preprocess_dynamic(const double *frame_xyzl, uint64_t n, double max_range, double min_range,
+                               double label_max_range, double dy_th, const int *dynamic_labels, int n_dynamic,
+                               const int *landmark_labels, int n_landmark, double *out_xyzl, uint64_t *n_out,
+                               sageicp_dynfilter_info *info /* optional */, int device);
+/* The cluster order replay itself (host code, no device needed): PCL finds the clusters in order of their smallest
+ * index, then sorts them with std::sort(rbegin, rend, by size) — largest first, not stable beyond 16 clusters.
+ * sizes[k]: size of the k-th cluster found; order_out[j] = k of the j-th cluster emitted (libstdc++'s std::sort). */
+int sageicp_cluster_emission_order(const uint32_t *sizes, uint64_t n, uint32_t *order_out);
+
 /* ---- per-frame pipeline counterpart: sage_icp::pipeline::sageICP (pipeline/sageICP.{hpp,cpp}) --
  * Host-side orchestration around the hot path for a stream of scans:
  * range crop + label zeroing (core/Preprocessing.cpp:173-187), two-level semantic voxel
  * down-sampling (core/Preprocessing.cpp:44-84, pipeline/sageICP.cpp:97-101), adaptive threshold
  * (core/Threshold.cpp:29-50), constant-velocity guess (pipeline/sageICP.cpp:110-115), RegisterFrame,
  * map update.  The reference's own pipeline compiles unchanged against the header shims; this
- * entry exists so that streams can be driven through the C ABI (tests, bench).  The PCL dynamic
- * vehicle filter and deskewing are not reproduced (both off in the pre-labelled configurations). */
+ * entry exists so that streams can be driven through the C ABI (tests, bench).  The dynamic vehicle
+ * filter (Preprocessing.cpp:95-172) is off by default and switched on with
+ * sageicp_pipeline_set_dynamic_vehicle_filter; deskewing is not reproduced (off in every launch file). */
 typedef struct sageicp_pipeline sageicp_pipeline;
 typedef struct sageicp_pipeline_config {   /* sageConfig, pipeline/sageICP.hpp:39-65 */
     double voxel_size_map, max_range, min_range, label_max_range, local_map_range;
@@ -360,6 +392,16 @@ int sageicp_pipeline_prefetch_wait(sageicp_pipeline *p);
 /* Drop an announcement / a prepared frame and wait for the helper thread: afterwards nothing
  * reads any announced buffer. */
 int sageicp_pipeline_prefetch_cancel(sageicp_pipeline *p);
+/* sageConfig's dynamic_vehicle_filter, dynamic_vehicle_filter_th, dynamic_vehicle_voxid, dynamic_remove_lankmark
+ * (pipeline/sageICP.hpp:39-65; used at pipeline/sageICP.cpp:58-65): with enable != 0 every frame goes through
+ * sageicp_preprocess_dynamic's filter with dynamic_labels = the config's label group dynamic_vehicle_voxid before it
+ * is down-sampled.  Off by default.  An out-of-range voxid is SAGEICP_ERR_INVALID.  A frame prepared by
+ * sageicp_pipeline_prefetch under the old setting is dropped (an announcement is kept and prepared under the new). */
+int sageicp_pipeline_set_dynamic_vehicle_filter(sageicp_pipeline *p, int enable, double dy_th,
+                                                int dynamic_vehicle_voxid, const int *landmark_labels,
+                                                int n_landmark);
+/* What the filter did to the last frame registered (all zero when it was off). */
+int sageicp_pipeline_dynamic_filter_info(const sageicp_pipeline *p, sageicp_dynfilter_info *info);
 int sageicp_pipeline_reinitialize(sageicp_pipeline *p);          /* pipeline/sageICP.hpp:94-99 */
 uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p);  /* poses().size() */
 int sageicp_pipeline_pose(const sageicp_pipeline *p, uint64_t index, double pose_out[7]);

@@ -96,6 +96,16 @@ class PipelineConfig(C.Structure):
     ]
 
 
+class DynFilterInfo(C.Structure):
+    """sageicp_dynfilter_info: what Preprocess()'s dynamic vehicle filter did to a frame"""
+    _fields_ = [("vehicle_points", C.c_uint64), ("landmark_points", C.c_uint64), ("clusters", C.c_uint64),
+                ("clusters_kept", C.c_uint64), ("points_removed", C.c_uint64), ("us_wall", C.c_double),
+                ("us_host", C.c_double), ("us_device", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # the SemanticKITTI parameter sets of ros/launch/odometry*.launch.py
 KITTI_VOXEL_LABELS = [[40, 44, 48, 49], [50, 51, 52], [70, 72], [60, 71, 80, 81, 99], [0],
                       [10, 11, 13, 15, 16, 18, 20]]
@@ -106,8 +116,12 @@ def make_pipeline_config(voxel_size_map=0.8, max_range=100.0, min_range=5.0, lab
                          local_map_range=100.0, basic=20, critical=20,
                          basic_parts_labels=(40, 44, 48, 49, 50, 70, 72), min_motion_th=0.1,
                          initial_threshold=2.0, sem_th=0.05, voxel_labels=None, voxel_size=None,
-                         device=0, map_update_on_device=True):
-    """defaults: ros/launch/odometry_gt.launch.py (pre-labelled scans, dynamic filter off)"""
+                         device=0, map_update_on_device=True, dynamic_vehicle_filter=False,
+                         dynamic_vehicle_filter_th=0.5, dynamic_vehicle_voxid=5, dynamic_remove_lankmark=(44, 48)):
+    """defaults: ros/launch/odometry_gt.launch.py (pre-labelled scans, dynamic filter off); odometry.launch.py sets
+    dynamic_vehicle_filter=True.  The four dynamic_* settings (sageConfig's names) are kept on the returned object
+    only — the C struct has no room for them — and SageICP() applies them through
+    sageicp_pipeline_set_dynamic_vehicle_filter."""
     voxel_labels = KITTI_VOXEL_LABELS if voxel_labels is None else voxel_labels
     voxel_size = KITTI_VOXEL_SIZE if voxel_size is None else voxel_size
     assert len(voxel_labels) == len(voxel_size)
@@ -122,6 +136,8 @@ def make_pipeline_config(voxel_size_map=0.8, max_range=100.0, min_range=5.0, lab
                          initial_threshold, sem_th, len(voxel_labels), keep["counts"],
                          keep["labels"], keep["sizes"], device, 1 if map_update_on_device else 0)
     cfg._keep = keep          # the arrays must outlive the struct
+    cfg._dynamic = dict(enable=bool(dynamic_vehicle_filter), dy_th=float(dynamic_vehicle_filter_th),
+                        voxid=int(dynamic_vehicle_voxid), landmarks=tuple(dynamic_remove_lankmark))
     return cfg
 
 
@@ -184,6 +200,13 @@ _SIGNATURES = [
     ("sageicp_voxel_downsample", C.c_int,
      [_dp, C.c_uint64, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
       C.c_double, _dp, _u64p, C.c_int]),
+    ("sageicp_preprocess_dynamic", C.c_int,
+     [_dp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int), C.c_int,
+      C.POINTER(C.c_int), C.c_int, _dp, _u64p, C.POINTER(DynFilterInfo), C.c_int]),
+    ("sageicp_cluster_emission_order", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("sageicp_pipeline_set_dynamic_vehicle_filter", C.c_int,
+     [C.c_void_p, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    ("sageicp_pipeline_dynamic_filter_info", C.c_int, [C.c_void_p, C.POINTER(DynFilterInfo)]),
     ("sageicp_pipeline_create", C.c_void_p, [C.POINTER(PipelineConfig)]),
     ("sageicp_pipeline_destroy", None, [C.c_void_p]),
     ("sageicp_pipeline_register_frame", C.c_int,
@@ -543,6 +566,22 @@ class SageICP:
         self._h = lib().sageicp_pipeline_create(C.byref(self.config))
         if not self._h:
             raise SageIcpError(ERR_INVALID, (lib().sageicp_last_error() or b"").decode())
+        dyn = getattr(self.config, "_dynamic", None)
+        if dyn and dyn["enable"]:
+            self.set_dynamic_vehicle_filter(True, dyn["dy_th"], dyn["voxid"], dyn["landmarks"])
+
+    def set_dynamic_vehicle_filter(self, enable=True, dy_th=0.5, voxid=5, landmark_labels=(44, 48)):
+        """Preprocess()'s dynamic vehicle filter for every frame (sageicp_pipeline_set_dynamic_vehicle_filter):
+        dynamic labels = the config's label group `voxid`"""
+        lm = (C.c_int * max(len(landmark_labels), 1))(*landmark_labels)
+        _check(lib().sageicp_pipeline_set_dynamic_vehicle_filter(self._h, 1 if enable else 0, dy_th, voxid, lm,
+                                                                 len(landmark_labels)))
+
+    def dynamic_filter_info(self):
+        """dict: what the filter did to the last frame registered (zeros when it was off)"""
+        info = DynFilterInfo()
+        _check(lib().sageicp_pipeline_dynamic_filter_info(self._h, C.byref(info)))
+        return info.as_dict()
 
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:       # (None: interpreter shutdown)
@@ -598,15 +637,35 @@ class SageICP:
         return out
 
 
-def preprocess(frame, max_range, min_range, label_max_range, device=0):
-    """sage_icp::Preprocess with dynamic_vehicle_filter off (core/Preprocessing.cpp:173-187)"""
+def preprocess(frame, max_range, min_range, label_max_range, device=0, dynamic_vehicle_filter=False, dy_th=0.5,
+               dynamic_labels=(), landmark_labels=(44, 48), return_info=False):
+    """sage_icp::Preprocess (core/Preprocessing.cpp:86-187); with dynamic_vehicle_filter the PCL clustering branch
+    (:95-172, sageicp_preprocess_dynamic).  return_info: also the filter's DynFilterInfo as a dict."""
     pts, pp = _d(frame)
     n = pts.reshape(-1, 4).shape[0]
     out = np.empty((n, 4))
     k = C.c_uint64(0)
-    _check(lib().sageicp_preprocess(pp, n, max_range, min_range, label_max_range,
-                                    out.ctypes.data_as(_dp), C.byref(k), device))
-    return out[:k.value].copy()
+    info = DynFilterInfo()
+    if dynamic_vehicle_filter:
+        dl = (C.c_int * max(len(dynamic_labels), 1))(*dynamic_labels)
+        ll = (C.c_int * max(len(landmark_labels), 1))(*landmark_labels)
+        _check(lib().sageicp_preprocess_dynamic(pp, n, max_range, min_range, label_max_range, dy_th, dl,
+                                                len(dynamic_labels), ll, len(landmark_labels),
+                                                out.ctypes.data_as(_dp), C.byref(k), C.byref(info), device))
+    else:
+        _check(lib().sageicp_preprocess(pp, n, max_range, min_range, label_max_range,
+                                        out.ctypes.data_as(_dp), C.byref(k), device))
+    res = out[:k.value].copy()
+    return (res, info.as_dict()) if return_info else res
+
+
+def cluster_emission_order(sizes):
+    """sageicp_cluster_emission_order: PCL's cluster order (std::sort(rbegin, rend) by size) for clusters found with
+    these sizes; element j = index of the j-th cluster emitted"""
+    s = np.ascontiguousarray(sizes, dtype=np.uint32)
+    out = np.zeros(max(len(s), 1), dtype=np.uint32)
+    _check(lib().sageicp_cluster_emission_order(s.ctypes.data_as(C.c_void_p), len(s), out.ctypes.data_as(C.c_void_p)))
+    return out[:len(s)].copy()
 
 
 def voxel_downsample(frame, voxel_labels, voxel_size, vox_scale, device=0):

@@ -899,6 +899,42 @@ int sageicp_voxel_downsample(const double *frame, uint64_t n, int n_groups,
     return SAGEICP_OK;
 }
 
+int sageicp_preprocess_dynamic(const double *frame, uint64_t n, double max_range, double min_range,
+                               double label_max_range, double dy_th, const int *dynamic_labels, int n_dynamic,
+                               const int *landmark_labels, int n_landmark, double *out, uint64_t *n_out,
+                               sageicp_dynfilter_info *info, int device) {
+    if (!n_out || (n && (!frame || !out)) || n_dynamic < 0 || n_landmark < 0 || (n_dynamic && !dynamic_labels) ||
+        (n_landmark && !landmark_labels) || !std::isfinite(dy_th))
+        return fail(SAGEICP_ERR_INVALID, "bad argument");
+    if (info) *info = sageicp_dynfilter_info{};
+    DynFilterConfig cfg;
+    cfg.dy_th = dy_th;
+    cfg.dynamic_labels.assign(dynamic_labels, dynamic_labels + n_dynamic);
+    cfg.landmark_labels.assign(landmark_labels, landmark_labels + n_landmark);
+    Prep pr;
+    int rc = pr.init(device);
+    if (rc) return rc;
+    std::vector<std::vector<double>> res;
+    const int crop = 0;
+    const double scale = 0.0;       // one pass-through level: the filtered cloud, downloaded
+    rc = pr.run(frame, n, max_range, min_range, label_max_range, 0, nullptr, nullptr, nullptr, &crop, &scale, 1, res,
+                true, &cfg);
+    const sageicp_dynfilter_info got = pr.dyn.info;
+    pr.destroy();
+    if (rc) return rc;
+    *n_out = res[0].size() / 4;
+    if (!res[0].empty()) std::memcpy(out, res[0].data(), res[0].size() * sizeof(double));
+    if (info) *info = got;
+    return SAGEICP_OK;
+}
+
+int sageicp_cluster_emission_order(const uint32_t *sizes, uint64_t n, uint32_t *order_out) {
+    if (n && (!sizes || !order_out)) return fail(SAGEICP_ERR_INVALID, "null argument");
+    if (n >= (1ull << 32)) return fail(SAGEICP_ERR_INVALID, "too many clusters");
+    cluster_emission_order(sizes, static_cast<size_t>(n), order_out);
+    return SAGEICP_OK;
+}
+
 // ---- pipeline counterpart -----------------------------------------------------------------------
 struct sageicp_pipeline {
     sageicp::Pipeline impl;
@@ -934,6 +970,9 @@ struct sageicp_pipeline {
     }
     int pf_rc = 0;
     std::string pf_err;
+    // Preprocess()'s dynamic vehicle filter (sageicp_pipeline_set_dynamic_vehicle_filter): off by default
+    bool dyn_on = false;
+    sageicp::DynFilterConfig dyn_cfg;
     explicit sageicp_pipeline(const sageicp_pipeline_config &c) : impl(c), device(c.device) {}
     ~sageicp_pipeline() {
         if (worker.joinable()) worker.join();
@@ -954,7 +993,7 @@ struct sageicp_pipeline {
         pr.arrival_order_levels = env_int("SAGEICP_SOURCE_REFERENCE_ORDER", 0) ? 0u : 2u;
         return pr.run(f, m, impl.max_range_(), impl.min_range_(), impl.label_max_range_(),
                       static_cast<int>(counts.size()), counts.data(), labels.data(), vs.data(),
-                      crop, scales, 2, res, false);
+                      crop, scales, 2, res, false, dyn_on ? &dyn_cfg : nullptr);
     }
 };
 
@@ -1059,6 +1098,31 @@ int sageicp_pipeline_prefetch_cancel(sageicp_pipeline *p) {
     if (p->worker.joinable()) p->worker.join();     // nothing reads an announced buffer after this
     p->announced = false;
     p->ready = false;
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_set_dynamic_vehicle_filter(sageicp_pipeline *p, int enable, double dy_th,
+                                                int voxid, const int *landmark_labels, int n_landmark) {
+    if (!p || n_landmark < 0 || (n_landmark && !landmark_labels) || !std::isfinite(dy_th))
+        return fail(SAGEICP_ERR_INVALID, "bad argument");
+    std::vector<int> counts, labels;
+    std::vector<double> vs;
+    p->impl.group_tables(counts, labels, vs);
+    if (voxid < 0 || voxid >= static_cast<int>(counts.size()))
+        return fail(SAGEICP_ERR_INVALID, "dynamic_vehicle_voxid is not a label group of the config");
+    if (p->worker.joinable()) p->worker.join();     // a frame prepared under the old setting is dropped
+    p->ready = false;
+    int off = 0;
+    for (int g = 0; g < voxid; ++g) off += counts[g];
+    p->dyn_on = enable != 0;
+    p->dyn_cfg.dy_th = dy_th;
+    p->dyn_cfg.dynamic_labels.assign(labels.begin() + off, labels.begin() + off + counts[voxid]);
+    p->dyn_cfg.landmark_labels.assign(landmark_labels, landmark_labels + n_landmark);
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_dynamic_filter_info(const sageicp_pipeline *p, sageicp_dynfilter_info *info) {
+    if (!p || !info) return fail(SAGEICP_ERR_INVALID, "null argument");
+    const sageicp::Prep &pr = p->prep[p->cur];
+    *info = pr.dyn_ran ? pr.dyn.info : sageicp_dynfilter_info{};
     return SAGEICP_OK;
 }
 int sageicp_pipeline_reinitialize(sageicp_pipeline *p) {

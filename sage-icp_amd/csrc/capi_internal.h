@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -402,6 +403,57 @@ private:
     bool stop_ = false;
 };
 
+// ---- dynamic vehicle filter (dyn_filter.hip; core/Preprocessing.cpp:95-172) -----------------------
+// PCL's cluster order: EuclideanClusterExtraction finds the clusters in order of their smallest index, then
+// std::sort(clusters.rbegin(), clusters.rend(), comparePointClusters) orders them by size, largest first — not stably.
+// std::sort permutes by comparisons only, so the same call on (size, index) records with the same comparator gives
+// PCL's permutation under the same standard library (libstdc++).  order[j] = index of the j-th cluster emitted.
+inline void cluster_emission_order(const uint32_t *sizes, size_t n, uint32_t *order) {
+    struct Rec {
+        uint32_t size, index;
+    };
+    std::vector<Rec> v(n);
+    for (size_t k = 0; k < n; ++k) v[k] = Rec{sizes[k], static_cast<uint32_t>(k)};
+    std::sort(v.rbegin(), v.rend(), [](const Rec &a, const Rec &b) { return a.size < b.size; });
+    for (size_t k = 0; k < n; ++k) order[k] = v[k].index;
+}
+// Preprocessing.cpp:141-158: a cluster is static iff the running count of its landmark neighbours ever exceeds
+// static_cast<int>(dy_th * size) — i.e. count >= 1 and count > that threshold (the count only grows)
+inline bool cluster_is_static(uint64_t count, uint32_t size, double dy_th) {
+    return count >= 1 && static_cast<double>(count) > std::trunc(dy_th * static_cast<double>(size));
+}
+
+struct DynFilterConfig {
+    double dy_th = 0.5;
+    std::vector<uint32_t> dynamic_labels;      // the reference's std::vector<int>, compared as uint32_t
+    std::vector<uint32_t> landmark_labels;
+};
+
+// buffers of one Prep; run() filters a frame already on the device (n points at `in`) into `out` (may be `in`),
+// passing the cropped points through `tmp` (n points)
+struct DynFilter {
+    size_t cap = 0, labels_cap = 0, temp_bytes = 0;
+    uint32_t *d_labels = nullptr, *d_ctr = nullptr, *h_ctr = nullptr;   // h_ctr pinned: [0..3] counters, [4] flags
+    unsigned long long *d_cnt = nullptr, *d_pos = nullptr, *d_vkey = nullptr, *d_lkey = nullptr, *d_count = nullptr;
+    float4 *d_vp = nullptr, *d_vs = nullptr, *d_lp = nullptr, *d_ls = nullptr;
+    uint32_t *d_vval = nullptr, *d_lval = nullptr, *d_vframe = nullptr, *d_parent = nullptr, *d_root = nullptr,
+             *d_size = nullptr, *d_rec_of_root = nullptr, *d_start = nullptr, *d_rkv = nullptr, *d_off = nullptr;
+    uint4 *d_rec = nullptr;
+    void *d_temp = nullptr;
+    void *h_rec = nullptr;                     // pinned: the component table
+    uint32_t *h_off = nullptr;                 // pinned: output offset per component (~0: dropped)
+    hipEvent_t ev[6] = {};                     // device time of the three launch batches (sageicp_set_profiling)
+    hipEvent_t ev_table = nullptr;
+    std::vector<uint32_t> order_scratch, size_scratch;
+    sageicp_dynfilter_info info{};             // of the last run
+
+    int reserve(size_t n, size_t nlabels);
+    void free_points();
+    void destroy();
+    int run(const Point4 *in, uint64_t n, double max_range, double min_range, double label_max_range,
+            const DynFilterConfig &cfg, Point4 *tmp, Point4 *out, int *d_ovf, uint64_t &n_out, hipStream_t s);
+};
+
 // ---- device preprocessing (preprocess.hip): buffers of one pipeline ------------------------------
 struct Prep {
     int device = -1;
@@ -432,6 +484,8 @@ struct Prep {
     void *h_pin = nullptr;              // pinned staging for the raw frame and the results
     size_t pin_bytes = 0;
     uint32_t kept_levels[2] = {0, 0};   // points the last run left in d_fd / d_src
+    DynFilter dyn;                      // the dynamic vehicle filter's buffers (allocated with its first use)
+    bool dyn_ran = false;               // the last run filtered (dyn.info describes its frame)
 
     int init(int dev) {
         if (stream) return SAGEICP_OK;
@@ -511,6 +565,7 @@ struct Prep {
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(stream);
         free_points();
+        dyn.destroy();
         if (d_nkept) (void)hipFree(d_nkept);
         if (d_overflow) (void)hipFree(d_overflow);
         if (d_gcounts) (void)hipFree(d_gcounts);
@@ -521,12 +576,17 @@ struct Prep {
 
     // levels: each {do_crop, scale}; a scale <= 0 means "crop only" (no voxel test).  Runs the
     // levels in sequence on the device, each feeding the next, and returns every level's cloud.
+    // With `dyn_cfg` the frame first goes through Preprocess()'s dynamic vehicle filter (dyn_filter.hip), which
+    // crops it itself: the levels then start from the filtered cloud with the crop off.
     int run(const double *frame, uint64_t n, double max_range, double min_range,
             double label_max_range, int n_groups, const int *gcounts, const int *glabels,
             const double *gvs, const int *crop, const double *scales, int n_levels,
-            std::vector<std::vector<double>> &out, bool download = true) {
+            std::vector<std::vector<double>> &out, bool download = true,
+            const DynFilterConfig *dyn_cfg = nullptr) {
         kept_levels[0] = kept_levels[1] = 0;
         us_order = 0;
+        dyn_ran = dyn_cfg != nullptr;
+        dyn.info = sageicp_dynfilter_info{};
         if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
         if (n_groups > 8) return fail(SAGEICP_ERR_INVALID, "at most 8 label groups");
         size_t nlabels = 0;
@@ -546,9 +606,14 @@ struct Prep {
         const Point4 *in = d_in;
         Point4 *outs[2] = {d_fd, d_src};
         uint64_t cur = n;
+        if (dyn_cfg) {      // the filtered cloud replaces the frame in d_in (the filter has read it by then)
+            int r = dyn.run(d_in, n, max_range, min_range, label_max_range, *dyn_cfg, d_tmp, d_in, d_overflow, cur,
+                            stream);
+            if (r) return r;
+        }
         for (int l = 0; l < n_levels; ++l) {
             VdsParams P{};
-            P.in = in; P.n = static_cast<int>(cur); P.do_crop = crop[l];
+            P.in = in; P.n = static_cast<int>(cur); P.do_crop = dyn_cfg ? 0 : crop[l];
             P.max_range = max_range; P.min_range = min_range; P.label_max_range = label_max_range;
             P.n_groups = scales[l] > 0.0 ? n_groups : -1;
             P.group_counts = d_gcounts; P.group_labels = d_glabels;

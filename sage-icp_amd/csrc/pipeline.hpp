@@ -10,9 +10,9 @@
 //   core/Threshold.cpp:29-50       AdaptiveThreshold::ComputeThreshold, ComputeModelError
 //   core/Preprocessing.cpp:44-84   VoxelDownsample (first point per voxel, per label group)
 //   core/Preprocessing.cpp:173-187 Preprocess, dynamic_vehicle_filter == false branch
-// Not reproduced: the PCL Euclidean-clustering "dynamic vehicle filter" (Preprocessing.cpp:95-172;
-// PCL is not available and every pre-labelled configuration runs with it off) and deskewing
-// (off in every launch file).  The down-sampled clouds come from the backend in the reference's
+// The PCL Euclidean-clustering "dynamic vehicle filter" (Preprocessing.cpp:95-172) runs on the device
+// (dyn_filter.hip) when sageicp_pipeline_set_dynamic_vehicle_filter switched it on, before the
+// down-sampling.  Not reproduced: deskewing (off in every launch file).  The down-sampled clouds come from the backend in the reference's
 // emission order (the bucket order of its tsl::robin_map, Preprocessing.cpp:76-82, replayed by
 // csrc/robin_order.hpp) unless sageicp_set_downsample_order(0) selected arrival order per label
 // group.

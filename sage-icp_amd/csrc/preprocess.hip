@@ -3,7 +3,8 @@
 // denser one that goes into the map and the sparser one that is registered.
 //
 // Reference (cpp/sage_icp/):
-//   core/Preprocessing.cpp:173-187  Preprocess, dynamic_vehicle_filter == false branch
+//   core/Preprocessing.cpp:173-187  Preprocess, dynamic_vehicle_filter == false branch (the == true branch,
+//                                   :95-172, is dyn_filter.hip; its output enters here with the crop off)
 //   core/Preprocessing.cpp:44-84    VoxelDownsample: one hash grid per label group, the FIRST point
 //                                   that falls into a voxel is kept
 //   pipeline/sageICP.cpp:97-101     Voxelize(): scale 0.5 -> frame_downsample, then 1.5 -> source
