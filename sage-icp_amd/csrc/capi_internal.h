@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/sageicp.h"
+#include "dyn_rules.h"
 #include "host_map.hpp"
 #include "kernels.h"
 #include "map_update.h"
@@ -417,11 +418,7 @@ inline void cluster_emission_order(const uint32_t *sizes, size_t n, uint32_t *or
     std::sort(v.rbegin(), v.rend(), [](const Rec &a, const Rec &b) { return a.size < b.size; });
     for (size_t k = 0; k < n; ++k) order[k] = v[k].index;
 }
-// Preprocessing.cpp:141-158: a cluster is static iff the running count of its landmark neighbours ever exceeds
-// static_cast<int>(dy_th * size) — i.e. count >= 1 and count > that threshold (the count only grows)
-inline bool cluster_is_static(uint64_t count, uint32_t size, double dy_th) {
-    return count >= 1 && static_cast<double>(count) > std::trunc(dy_th * static_cast<double>(size));
-}
+// cluster_is_static (Preprocessing.cpp:141-158): dyn_rules.h
 
 struct DynFilterConfig {
     double dy_th = 0.5;

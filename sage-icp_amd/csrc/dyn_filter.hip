@@ -14,7 +14,7 @@
 //   radix sorts      V and L by packed cell: a neighbour within 0.5 m lies in one of the 27 surrounding cells
 //   k_dyn_link       union-find over V: every pair (i < j) with d2 < 0.25f hooks the larger root under the smaller
 //                    (atomicCAS), so each root ends as its component's smallest vehicle index — the labelling does
-//                    not depend on the schedule
+//                    not depend on the schedule, and the walks have bounds that hold under any schedule (find_root)
 //   k_dyn_count      compress; per point the L neighbours within radius; size and count per root (integer atomics)
 //   k_dyn_records    the components of >= 5 points, in ascending root order = the order PCL finds them
 //   -- round trip 2: the per-component table (root, size, count); the host replays PCL's std::sort of the clusters
@@ -56,7 +56,7 @@ struct DynParams {
     unsigned long long *lkey;
     uint32_t *lval;
     uint32_t *ctr;                     // [0] inliers [1] |V| [2] |L| [3] components of >= 5
-    int *ovf;                          // 1: cell index out of range, 2: non-finite label, 4: union-find gave up
+    int *ovf;                          // 1: cell index out of range, 2: non-finite label, 4: union-find invariant broken
 };
 
 __device__ __forceinline__ bool cell_of(float x, float y, float z, long long c[3]) {
@@ -101,8 +101,9 @@ __global__ __launch_bounds__(256) void k_dyn_classify(DynParams P) {
         }
         unsigned long long c = 0;
         if (kept) {
-            // :107-111 — static_cast<uint32_t> of the zeroed label; the int lists compare as unsigned
-            const uint32_t lab = static_cast<uint32_t>(static_cast<long long>(p.l));
+            // :107-111 — static_cast<uint32_t> of the zeroed label as x86 converts it (dyn_rules.h); the int lists
+            // compare as unsigned
+            const uint32_t lab = label_code(p.l);
             c = has_label(P.labels, P.n_dyn, lab) ? (1ull << 32) : 1ull;
             lm = has_label(P.labels + P.n_dyn, P.n_lm, lab);
             P.tmp[i] = p;
@@ -184,11 +185,14 @@ __device__ __forceinline__ uint32_t ld(const uint32_t *a) {
 }
 
 // root of x with path halving (a parent only ever moves to an ancestor, so the plain halving stores are safe next to
-// the CAS on roots); `budget` bounds the walk — a tree is never deeper than |V|
-__device__ __forceinline__ uint32_t find_root(uint32_t *parent, uint32_t x, int &budget) {
-    for (;;) {
+// the CAS on roots).  Every parent is smaller than its child: a root is hooked only under a smaller root, and a halving
+// store writes an ancestor.  So each step lowers x, and a walk from x < nv ends within nv - 1 steps whatever the other
+// threads do; more steps mean the invariant is broken, and the walk stops with `broken` set.
+__device__ __forceinline__ uint32_t find_root(uint32_t *parent, uint32_t x, uint32_t nv, bool &broken) {
+    for (uint32_t steps = 0;; ++steps) {
         const uint32_t p = ld(parent + x);
-        if (p == x || --budget < 0) return p;
+        if (p == x) return p;
+        if (steps >= nv) { broken = true; return p; }
         const uint32_t g = ld(parent + p);
         if (g != p) __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         x = g;
@@ -230,26 +234,25 @@ __global__ __launch_bounds__(256) void k_dyn_link(const float4 *vs, const unsign
     const uint32_t i = vidx[p];
     long long c[3];
     cell_of(a.x, a.y, a.z, c);
-    bool gave_up = false;
+    bool broken = false;
     for_neighbour_cells(vkey_s, nv, c, [&](uint32_t q) {
         const uint32_t j = vidx[q];
-        if (j <= i || gave_up || !(dist2(a, vs[q]) < 0.25f)) return;
-        // unite(i, j): hook the larger root under the smaller; a failed CAS means that root was just hooked
-        // elsewhere — every retry follows some other union's success, so |V| retries bound it
-        int budget = static_cast<int>(nv) + 64;
-        uint32_t ra = find_root(parent, i, budget), rb = find_root(parent, j, budget);
-        for (;;) {
-            if (budget < 0) { gave_up = true; return; }
+        if (j <= i || broken || !(dist2(a, vs[q]) < 0.25f)) return;
+        // unite(i, j): hook the larger root under the smaller.  A failed CAS means that root was just hooked elsewhere
+        // and is never a root again, so the retries of one unite fail on distinct roots: fewer than nv of them, as a
+        // frame has at most nv - 1 hooks.  Neither bound depends on the schedule; they only catch a broken invariant.
+        uint32_t ra = find_root(parent, i, nv, broken), rb = find_root(parent, j, nv, broken);
+        for (uint32_t failed = 0; !broken; ++failed) {
             if (ra == rb) return;
             if (ra > rb) { const uint32_t t = ra; ra = rb; rb = t; }
             const uint32_t old = atomicCAS(parent + rb, rb, ra);
             if (old == rb) return;
-            --budget;
-            rb = find_root(parent, old, budget);
-            ra = find_root(parent, ra, budget);
+            if (failed + 1 >= nv) { broken = true; return; }
+            rb = find_root(parent, old, nv, broken);
+            ra = find_root(parent, ra, nv, broken);
         }
     });
-    if (gave_up) atomicOr(ovf, 4);
+    if (broken) atomicOr(ovf, 4);
 }
 
 __global__ __launch_bounds__(256) void k_dyn_count(const float4 *vs, const uint32_t *vidx, uint32_t nv,
@@ -259,9 +262,9 @@ __global__ __launch_bounds__(256) void k_dyn_count(const float4 *vs, const uint3
     const uint32_t p = blockIdx.x * 256 + threadIdx.x;
     if (p >= nv) return;
     const uint32_t i = vidx[p];
-    int budget = static_cast<int>(nv) + 64;
-    const uint32_t r = find_root(parent, i, budget);
-    if (budget < 0) atomicOr(ovf, 4);
+    bool broken = false;
+    const uint32_t r = find_root(parent, i, nv, broken);
+    if (broken) atomicOr(ovf, 4);
     root[i] = r;
     // Preprocessing.cpp:139-158: the landmark points of map_all within radius of this vehicle point
     const float4 a = vs[p];
@@ -487,7 +490,7 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
     if (prof) HIPCHK(hipEventRecord(ev[3], s));
     const double th0 = now_us();
     HIPCHK(hipEventSynchronize(ev_table));
-    if (h_ctr[4] & 4) return fail(SAGEICP_ERR_HIP, "dynamic vehicle filter: the union-find did not converge");
+    if (h_ctr[4] & 4) return fail(SAGEICP_ERR_HIP, "dynamic vehicle filter: union-find invariant broken");
     const uint32_t ncl = h_ctr[3];
     if (ncl > max_rec) return fail(SAGEICP_ERR_HIP, "dynamic vehicle filter: inconsistent component table");
 

@@ -1,6 +1,7 @@
 """Host-side tests of Preprocess()'s dynamic vehicle filter (core/Preprocessing.cpp:95-172): the independent CPU
 restatement (tests/dynfilter_ref.cpp) against hand-derived answers, the library's replay of PCL's cluster order
-against the restatement's, and the C ABI additions where no device is needed."""
+against the restatement's, the C ABI additions where no device is needed, and csrc/dyn_rules.h (the label cast and the
+static test) compiled for the host against the reference's expressions."""
 import ctypes
 import os
 import subprocess
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 
 import dynref
+import dynscenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -126,3 +128,79 @@ def test_dynfilter_info_layout_matches_header(sage):
     assert got[0] == ctypes.sizeof(sage.DynFilterInfo) == 64
     assert got[1:-1] == [getattr(sage.DynFilterInfo, f).offset for f, _ in sage.DynFilterInfo._fields_]
     assert got[-1] == 4 == sage.ABI_VERSION
+
+
+# ---- the label and threshold edges (tests/dynscenes.py), and dyn_rules.h against the reference's expressions ------
+@pytest.mark.parametrize("name", sorted(dynscenes.label_kat_scenes()))
+def test_restatement_label_known_answers(name):
+    frame, kw, expected = dynscenes.label_kat_scenes()[name]
+    out, _ = dynref.preprocess(frame, **kw, **dynref.KAT_RANGES)
+    assert np.array_equal(out, expected)
+
+
+@pytest.mark.parametrize("name", sorted(dynscenes.threshold_kat_scenes()))
+def test_restatement_threshold_known_answers(name):
+    frame, kw, expected = dynscenes.threshold_kat_scenes()[name]
+    out, info = dynref.preprocess(frame, **kw, **dynref.KAT_RANGES)
+    assert np.array_equal(out, expected)
+    assert info["clusters"] == 3 and info["vehicle_points"] == 24
+
+
+RULES_SRC = r'''
+#include "dyn_rules.h"
+extern "C" int dr_static(unsigned long long count, unsigned size, double dy_th) {
+    return sageicp::cluster_is_static(count, size, dy_th) ? 1 : 0;
+}
+extern "C" unsigned dr_label(double l) { return sageicp::label_code(l); }
+// the reference's expressions (Preprocessing.cpp:107-111, 141-158), as tests/dynfilter_ref.cpp states them
+extern "C" int ref_static(int count, int size, double dy_th) {
+    int count_size = 0;
+    for (int k = 0; k < count; ++k) {
+        ++count_size;
+        if (count_size > static_cast<int>(dy_th * static_cast<double>(size))) return 1;
+    }
+    return 0;
+}
+extern "C" unsigned ref_label(double l) { return static_cast<uint32_t>(static_cast<long long>(l)); }
+'''
+
+
+@pytest.fixture(scope="module")
+def rules(tmp_path_factory):
+    d = tmp_path_factory.mktemp("dyn_rules")
+    src, so = d / "rules.cpp", d / "librules.so"
+    src.write_text(RULES_SRC)
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wextra",
+                           "-Werror", "-I", os.path.join(ROOT, "sage-icp_amd", "csrc"), str(src), "-o", str(so)])
+    L = ctypes.CDLL(str(so))
+    L.dr_static.argtypes = [ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_double]
+    L.ref_static.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double]
+    L.dr_label.argtypes = L.ref_label.argtypes = [ctypes.c_double]
+    L.dr_label.restype = L.ref_label.restype = ctypes.c_uint
+    return L
+
+
+def test_cluster_is_static_follows_the_reference_expression(rules):
+    counts = (0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 99, 100, 101, 1000)
+    sizes = (5, 6, 7, 8, 10, 100, 1000, 65537)
+    ths = [-1e300, -1e10, -2.0 ** 31, -1.0, -0.5, 0.0, 0.1, 0.5, 0.75, 1.0, 2.0, 10.0, 1e10, 1e300, float("nan")]
+    for s in sizes:        # either side of the int range of dy_th * size
+        for edge in (2.0 ** 31 / s, -(2.0 ** 31) / s, (2.0 ** 31 + 1) / s):
+            ths += [float(np.nextafter(edge, -np.inf)), edge, float(np.nextafter(edge, np.inf))]
+    for s in sizes:
+        for th in ths:
+            for c in counts:
+                assert rules.dr_static(c, s, th) == rules.ref_static(c, s, th), (c, s, th)
+    # the overflow: static_cast<int> gives INT_MIN, so one landmark neighbour keeps any cluster
+    assert rules.ref_static(1, 10, 1e10) == 1 and rules.dr_static(1, 10, 1e10) == 1
+    assert rules.dr_static(1 << 40, 10, 2.0 ** 31 / 10 * 0.999) == 1 and rules.dr_static(0, 10, 1e10) == 0
+    assert rules.dr_static(2 ** 31 - 1, 8, float(np.nextafter(2.0 ** 28, 0))) == 0
+
+
+def test_label_code_follows_the_reference_cast(rules):
+    ls = [0.0, -0.0, 0.5, -0.5, 10.9, -1.0, -1.5, 4294967295.0, 4294967296.0, 4294967306.0, 2.0 ** 53, -(2.0 ** 53),
+          2.0 ** 63 - 1024, -(2.0 ** 63), float(np.nextafter(-(2.0 ** 63), -np.inf)), 2.0 ** 63, 1e19, -1e19, 1e300,
+          -1e300, 2.0 ** 64 + 2.0 ** 33]
+    for l in ls:
+        assert rules.dr_label(l) == rules.ref_label(l), l
+    assert [rules.dr_label(l) for l in (10.9, -0.5, -1.0, 4294967306.0, 1e19, -1e19)] == [10, 0, 0xFFFFFFFF, 10, 0, 0]
