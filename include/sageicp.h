@@ -338,6 +338,16 @@ int sageicp_preprocess_dynamic(const double *frame_xyzl, uint64_t n, double max_
  * sizes[k]: size of the k-th cluster found; order_out[j] = k of the j-th cluster emitted (libstdc++'s std::sort). */
 int sageicp_cluster_emission_order(const uint32_t *sizes, uint64_t n, uint32_t *order_out);
 
+/* core/Deskew.cpp:36-50 DeSkewScan: out may equal frame_xyzl.  delta = (start.inverse() * finish).log() is formed once
+ * on the host; every point i becomes exp((timestamps[i] - 0.5) * delta) * xyz on the device (deskew.hip), with the
+ * exponential and point action the ICP update uses (se3_math.h).  The label and the row order are kept.  Poses are
+ * {qx, qy, qz, qw, tx, ty, tz} (Sophus::SE3d::data()).  Refused (SAGEICP_ERR_INVALID, nothing written): a NULL pose,
+ * a NULL frame / timestamps / out with n > 0, n > 2^26 - 4, and any pose entry, timestamp or point coordinate or label
+ * that is not finite.  n == 0 needs no device. */
+int sageicp_deskew_scan(const double *frame_xyzl, const double *timestamps, uint64_t n,
+                        const double start_pose[7], const double finish_pose[7],
+                        double *out_xyzl, int device);
+
 /* ---- per-frame pipeline counterpart: sage_icp::pipeline::sageICP (pipeline/sageICP.{hpp,cpp}) --
  * Host-side orchestration around the hot path for a stream of scans:
  * range crop + label zeroing (core/Preprocessing.cpp:173-187), two-level semantic voxel
@@ -346,7 +356,8 @@ int sageicp_cluster_emission_order(const uint32_t *sizes, uint64_t n, uint32_t *
  * map update.  The reference's own pipeline compiles unchanged against the header shims; this
  * entry exists so that streams can be driven through the C ABI (tests, bench).  The dynamic vehicle
  * filter (Preprocessing.cpp:95-172) is off by default and switched on with
- * sageicp_pipeline_set_dynamic_vehicle_filter; deskewing is not reproduced (off in every launch file). */
+ * sageicp_pipeline_set_dynamic_vehicle_filter.  Deskewing (pipeline/sageICP.cpp:36-52, core/Deskew.cpp) is off by
+ * default, switched on with sageicp_pipeline_set_deskew and applied by sageicp_pipeline_register_frame_timestamps. */
 typedef struct sageicp_pipeline sageicp_pipeline;
 typedef struct sageicp_pipeline_config {   /* sageConfig, pipeline/sageICP.hpp:39-65 */
     double voxel_size_map, max_range, min_range, label_max_range, local_map_range;
@@ -383,7 +394,9 @@ int sageicp_pipeline_register_frame(sageicp_pipeline *p, const double *frame_xyz
  * must stay valid and unchanged, also when the announced frame ends up not being registered.
  * A frame is recognised by pointer, size AND a fingerprint of its content taken here (64 rows spread
  * over the frame and the last one: best effort — it tells a buffer refilled with another scan from
- * the scan that was announced, not a buffer edited in a few places; do not edit announced buffers). */
+ * the scan that was announced, not a buffer edited in a few places; do not edit announced buffers).
+ * With deskew on (sageicp_pipeline_set_deskew) a frame's Preprocess() reads the deskewed frame, which depends on the
+ * pose of the frame registered before it: nothing can be prepared ahead, and this call is SAGEICP_ERR_INVALID. */
 int sageicp_pipeline_prefetch(sageicp_pipeline *p, const double *next_frame_xyzl, uint64_t n);
 /* Wait for the helper thread without dropping what it prepared: afterwards nothing reads the
  * announced buffer any more (it may be released or refilled), and the prepared clouds are still
@@ -402,6 +415,22 @@ int sageicp_pipeline_set_dynamic_vehicle_filter(sageicp_pipeline *p, int enable,
                                                 int n_landmark);
 /* What the filter did to the last frame registered (all zero when it was off). */
 int sageicp_pipeline_dynamic_filter_info(const sageicp_pipeline *p, sageicp_dynfilter_info *info);
+/* sageConfig::deskew (pipeline/sageICP.hpp:59).  Off by default.  Drops a prepared or announced frame, and while it is
+ * on sageicp_pipeline_prefetch is refused (see there).  The one-argument sageicp_pipeline_register_frame never
+ * deskews, whatever the setting. */
+int sageicp_pipeline_set_deskew(sageicp_pipeline *p, int enable);
+/* sageICP::RegisterFrame(frame, timestamps), pipeline/sageICP.cpp:36-52.  Deskew off: timestamps is not read and the
+ * call is sageicp_pipeline_register_frame's, bit for bit.  Deskew on: timestamps (n of them) must be non-NULL and
+ * finite — checked on every frame, also before the third pose, so a bad stream fails on its first frame
+ * (SAGEICP_ERR_INVALID, no pose pushed; the reference does not check).  With three poses or more the
+ * frame is deskewed on the device (sageicp_deskew_scan's kernel) with poses N-2 and N-1 before Preprocess(); with
+ * fewer it passes through unchanged.  The reference's callers normalise integer stamps first (ros/ros2/Utils.hpp). */
+int sageicp_pipeline_register_frame_timestamps(sageicp_pipeline *p, const double *frame_xyzl,
+                                               const double *timestamps, uint64_t n, double pose_out[7],
+                                               double *icp_seconds, double *total_seconds, uint64_t *n_source,
+                                               sageicp_stats *stats /* optional */);
+/* Whether the last frame registered was deskewed, and the delta tangent it used (zeros if not). */
+int sageicp_pipeline_deskew_info(const sageicp_pipeline *p, int *applied, double delta_out[6]);
 int sageicp_pipeline_reinitialize(sageicp_pipeline *p);          /* pipeline/sageICP.hpp:94-99 */
 uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p);  /* poses().size() */
 int sageicp_pipeline_pose(const sageicp_pipeline *p, uint64_t index, double pose_out[7]);

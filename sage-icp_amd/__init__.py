@@ -117,11 +117,13 @@ def make_pipeline_config(voxel_size_map=0.8, max_range=100.0, min_range=5.0, lab
                          basic_parts_labels=(40, 44, 48, 49, 50, 70, 72), min_motion_th=0.1,
                          initial_threshold=2.0, sem_th=0.05, voxel_labels=None, voxel_size=None,
                          device=0, map_update_on_device=True, dynamic_vehicle_filter=False,
-                         dynamic_vehicle_filter_th=0.5, dynamic_vehicle_voxid=5, dynamic_remove_lankmark=(44, 48)):
+                         dynamic_vehicle_filter_th=0.5, dynamic_vehicle_voxid=5, dynamic_remove_lankmark=(44, 48),
+                         deskew=False):
     """defaults: ros/launch/odometry_gt.launch.py (pre-labelled scans, dynamic filter off); odometry.launch.py sets
     dynamic_vehicle_filter=True.  The four dynamic_* settings (sageConfig's names) are kept on the returned object
     only — the C struct has no room for them — and SageICP() applies them through
-    sageicp_pipeline_set_dynamic_vehicle_filter."""
+    sageicp_pipeline_set_dynamic_vehicle_filter; likewise `deskew` (sageConfig::deskew, off in every launch file),
+    applied through sageicp_pipeline_set_deskew."""
     voxel_labels = KITTI_VOXEL_LABELS if voxel_labels is None else voxel_labels
     voxel_size = KITTI_VOXEL_SIZE if voxel_size is None else voxel_size
     assert len(voxel_labels) == len(voxel_size)
@@ -138,6 +140,7 @@ def make_pipeline_config(voxel_size_map=0.8, max_range=100.0, min_range=5.0, lab
     cfg._keep = keep          # the arrays must outlive the struct
     cfg._dynamic = dict(enable=bool(dynamic_vehicle_filter), dy_th=float(dynamic_vehicle_filter_th),
                         voxid=int(dynamic_vehicle_voxid), landmarks=tuple(dynamic_remove_lankmark))
+    cfg._deskew = bool(deskew)
     return cfg
 
 
@@ -207,6 +210,11 @@ _SIGNATURES = [
     ("sageicp_pipeline_set_dynamic_vehicle_filter", C.c_int,
      [C.c_void_p, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int), C.c_int]),
     ("sageicp_pipeline_dynamic_filter_info", C.c_int, [C.c_void_p, C.POINTER(DynFilterInfo)]),
+    ("sageicp_deskew_scan", C.c_int, [_dp, _dp, C.c_uint64, _dp, _dp, _dp, C.c_int]),
+    ("sageicp_pipeline_set_deskew", C.c_int, [C.c_void_p, C.c_int]),
+    ("sageicp_pipeline_register_frame_timestamps", C.c_int,
+     [C.c_void_p, _dp, _dp, C.c_uint64, _dp, _dp, _dp, _u64p, C.POINTER(Stats)]),
+    ("sageicp_pipeline_deskew_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int), _dp]),
     ("sageicp_pipeline_create", C.c_void_p, [C.POINTER(PipelineConfig)]),
     ("sageicp_pipeline_destroy", None, [C.c_void_p]),
     ("sageicp_pipeline_register_frame", C.c_int,
@@ -569,6 +577,22 @@ class SageICP:
         dyn = getattr(self.config, "_dynamic", None)
         if dyn and dyn["enable"]:
             self.set_dynamic_vehicle_filter(True, dyn["dy_th"], dyn["voxid"], dyn["landmarks"])
+        if getattr(self.config, "_deskew", False):
+            self.set_deskew(True)
+
+    def set_deskew(self, enable=True):
+        """sageConfig::deskew (sageicp_pipeline_set_deskew): RegisterFrame(frame, timestamps) deskews from the third
+        pose on.  Drops a prepared or announced frame; prefetch() is refused while it is on."""
+        _check(lib().sageicp_pipeline_set_deskew(self._h, 1 if enable else 0))
+        if enable:
+            self._announced = ()
+
+    def deskew_info(self):
+        """(applied, delta[6]): whether the last frame registered was deskewed, and the tangent it used (zeros if not)"""
+        applied = C.c_int(0)
+        delta = np.zeros(6)
+        _check(lib().sageicp_pipeline_deskew_info(self._h, C.byref(applied), delta.ctypes.data_as(_dp)))
+        return bool(applied.value), delta
 
     def set_dynamic_vehicle_filter(self, enable=True, dy_th=0.5, voxid=5, landmark_labels=(44, 48)):
         """Preprocess()'s dynamic vehicle filter for every frame (sageicp_pipeline_set_dynamic_vehicle_filter):
@@ -588,15 +612,25 @@ class SageICP:
             lib().sageicp_pipeline_destroy(self._h)
             self._h = None
 
-    def RegisterFrame(self, frame):
-        """returns (pose[7], icp_seconds, total_seconds, n_source, stats)"""
+    def RegisterFrame(self, frame, timestamps=None):
+        """returns (pose[7], icp_seconds, total_seconds, n_source, stats).  With `timestamps` (one per point, in [0, 1)
+        for a scan — see normalize_timestamps) this is RegisterFrame(frame, timestamps), which deskews when deskew is
+        on; without, the one-argument RegisterFrame(frame), which never does."""
         pts, pp = _d(frame)
+        n = pts.reshape(-1, 4).shape[0]
         out = np.empty(7)
         icp, tot, ns = C.c_double(0), C.c_double(0), C.c_uint64(0)
         st = Stats()
-        _check(lib().sageicp_pipeline_register_frame(self._h, pp, pts.reshape(-1, 4).shape[0],
-                                                     out.ctypes.data_as(_dp), C.byref(icp),
-                                                     C.byref(tot), C.byref(ns), C.byref(st)))
+        if timestamps is None:
+            _check(lib().sageicp_pipeline_register_frame(self._h, pp, n, out.ctypes.data_as(_dp), C.byref(icp),
+                                                         C.byref(tot), C.byref(ns), C.byref(st)))
+        else:
+            ts, tp = _d(timestamps)
+            if ts.size != n:
+                raise ValueError("%d timestamps for %d points" % (ts.size, n))
+            _check(lib().sageicp_pipeline_register_frame_timestamps(self._h, pp, tp, n, out.ctypes.data_as(_dp),
+                                                                    C.byref(icp), C.byref(tot), C.byref(ns),
+                                                                    C.byref(st)))
         return out, icp.value, tot.value, ns.value, st
 
     def prefetch(self, next_frame):
@@ -657,6 +691,33 @@ def preprocess(frame, max_range, min_range, label_max_range, device=0, dynamic_v
                                         out.ctypes.data_as(_dp), C.byref(k), device))
     res = out[:k.value].copy()
     return (res, info.as_dict()) if return_info else res
+
+
+def deskew_scan(frame, timestamps, start_pose, finish_pose, device=0):
+    """sage_icp::DeSkewScan (core/Deskew.cpp:31-50) on the device: every point moved by exp((t - 0.5) * delta),
+    delta = (start.inverse() * finish).log(); labels and row order kept"""
+    pts, pp = _d(frame)
+    n = pts.reshape(-1, 4).shape[0]
+    ts, tp = _d(timestamps)
+    if ts.size != n:
+        raise ValueError("%d timestamps for %d points" % (ts.size, n))
+    a, ap = _d(start_pose)
+    b, bp = _d(finish_pose)
+    if a.size != 7 or b.size != 7:
+        raise ValueError("poses are (qx, qy, qz, qw, tx, ty, tz)")
+    out = np.empty((n, 4))
+    _check(lib().sageicp_deskew_scan(pp, tp, n, ap, bp, out.ctypes.data_as(_dp), device))
+    return out
+
+
+def normalize_timestamps(timestamps):
+    """NormalizeTimestamps (ros/ros2/Utils.hpp:68-77): the stamps unchanged if their maximum is below 1, else divided
+    by it — for integer per-point stamps (the reference's node does this before RegisterFrame(frame, timestamps))"""
+    t = np.asarray(timestamps, dtype=np.float64)
+    if t.size == 0:
+        return t.copy()
+    m = t.max()
+    return t.copy() if m < 1.0 else t / m
 
 
 def cluster_emission_order(sizes):

@@ -935,12 +935,62 @@ int sageicp_cluster_emission_order(const uint32_t *sizes, uint64_t n, uint32_t *
     return SAGEICP_OK;
 }
 
+// ---- DeSkewScan on the device (deskew.hip) -----------------------------------------------------------
+static bool finite_n(const double *v, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+int sageicp_deskew_scan(const double *frame, const double *timestamps, uint64_t n, const double start_pose[7],
+                        const double finish_pose[7], double *out, int device) {
+    if (!start_pose || !finish_pose || (n && (!frame || !timestamps || !out)))
+        return fail(SAGEICP_ERR_INVALID, "null argument");
+    if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
+    if (!finite_n(start_pose, 7) || !finite_n(finish_pose, 7)) return fail(SAGEICP_ERR_INVALID, "a pose is not finite");
+    if (!finite_n(timestamps, n)) return fail(SAGEICP_ERR_INVALID, "a timestamp is not finite (NaN / Inf)");
+    if (!finite_n(frame, 4 * n)) return fail(SAGEICP_ERR_INVALID, "a point is not finite (NaN / Inf)");
+    // Deskew.cpp:36: delta_pose = (start_pose.inverse() * finish_pose).log(), once per frame on the host
+    double inv[7], rel[7];
+    DeskewTangent delta;
+    se3_inv(start_pose, inv);
+    se3_mul(inv, finish_pose, rel);
+    se3_log(rel, delta.v);
+    if (n == 0) return SAGEICP_OK;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
+    if (device < 0 || device >= count) return fail(SAGEICP_ERR_INVALID, "device ordinal out of range");
+    Point4 *d_p = nullptr;
+    double *d_t = nullptr;
+    hipStream_t s = nullptr;
+    auto body = [&]() -> int {
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        HIPCHK(hipMalloc(&d_p, n * sizeof(Point4)));
+        HIPCHK(hipMalloc(&d_t, n * sizeof(double)));
+        HIPCHK(hipMemcpyAsync(d_p, frame, n * sizeof(Point4), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_t, timestamps, n * sizeof(double), hipMemcpyHostToDevice, s));
+        launch_deskew(d_p, d_p, d_t, static_cast<int>(n), delta, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, d_p, n * sizeof(Point4), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return SAGEICP_OK;
+    };
+    const int rc = body();
+    if (s) (void)hipStreamSynchronize(s);
+    if (d_p) (void)hipFree(d_p);
+    if (d_t) (void)hipFree(d_t);
+    if (s) (void)hipStreamDestroy(s);
+    return rc;
+}
+
 // ---- pipeline counterpart -----------------------------------------------------------------------
 struct sageicp_pipeline {
     sageicp::Pipeline impl;
     // Preprocess() + Voxelize() depend on the raw frame only (not on the pose, not on the map), so
     // the next frame's can run while this one registers (sageicp_pipeline_prefetch): two sets of
-    // buffers and streams, `cur` the one the frame being registered lives in.
+    // buffers and streams, `cur` the one the frame being registered lives in.  (Not with deskew on: a
+    // deskewed frame depends on the poses of the two frames before it, so prefetch is refused then.)
     sageicp::Prep prep[2];
     int cur = 0;
     int device;
@@ -973,13 +1023,15 @@ struct sageicp_pipeline {
     // Preprocess()'s dynamic vehicle filter (sageicp_pipeline_set_dynamic_vehicle_filter): off by default
     bool dyn_on = false;
     sageicp::DynFilterConfig dyn_cfg;
+    // sageConfig::deskew (sageicp_pipeline_set_deskew): off by default; read by the timestamped entry only
+    bool deskew_on = false;
     explicit sageicp_pipeline(const sageicp_pipeline_config &c) : impl(c), device(c.device) {}
     ~sageicp_pipeline() {
         if (worker.joinable()) worker.join();
         prep[0].destroy();
         prep[1].destroy();
     }
-    int voxelize_into(sageicp::Prep &pr, const double *f, uint64_t m) {
+    int voxelize_into(sageicp::Prep &pr, const double *f, uint64_t m, const sageicp::DeskewArgs *deskew = nullptr) {
         int rc = pr.init(device);
         if (rc) return rc;
         std::vector<int> counts, labels;
@@ -993,7 +1045,7 @@ struct sageicp_pipeline {
         pr.arrival_order_levels = env_int("SAGEICP_SOURCE_REFERENCE_ORDER", 0) ? 0u : 2u;
         return pr.run(f, m, impl.max_range_(), impl.min_range_(), impl.label_max_range_(),
                       static_cast<int>(counts.size()), counts.data(), labels.data(), vs.data(),
-                      crop, scales, 2, res, false, dyn_on ? &dyn_cfg : nullptr);
+                      crop, scales, 2, res, false, dyn_on ? &dyn_cfg : nullptr, deskew);
     }
 };
 
@@ -1010,20 +1062,27 @@ sageicp_pipeline *sageicp_pipeline_create(const sageicp_pipeline_config *c) {
     return p;
 }
 void sageicp_pipeline_destroy(sageicp_pipeline *p) { delete p; }
-int sageicp_pipeline_register_frame(sageicp_pipeline *p, const double *frame, uint64_t n,
-                                    double pose_out[7], double *icp_s, double *total_s,
-                                    uint64_t *n_source, sageicp_stats *stats) {
-    if (!p || !pose_out || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
-    // Preprocess + Voxelize on the device (preprocess.hip): crop + scale 0.5, then scale 1.5.
+// timestamps: the frame's (deskew on, all finite) or nullptr (the one-argument RegisterFrame)
+static int pipeline_register(sageicp_pipeline *p, const double *frame, const double *timestamps, uint64_t n,
+                             double pose_out[7], double *icp_s, double *total_s, uint64_t *n_source,
+                             sageicp_stats *stats) {
+    // Deskew (deskew.hip) on the uploaded frame when the pipeline decides so, then Preprocess + Voxelize on the
+    // device (preprocess.hip): crop + scale 0.5, then scale 1.5.
     // Neither cloud comes back to the host: the source is registered and the down-sampled frame
     // inserted into the map from where the kernels left them (only a host-side map update
     // downloads its points).
     struct Backend {
         sageicp_pipeline *p;
-        int voxelize(const double *f, uint64_t m, uint64_t &n_src) {
+        const double *ts;
+        int voxelize(const double *f, uint64_t m, uint64_t &n_src, const double *delta) {
             if (p->worker.joinable()) p->worker.join();
             int r;
-            if (p->ready && p->pf_frame == f && p->pf_n == m &&
+            if (delta) {                         // deskewed: depends on the last two poses, never prepared ahead
+                sageicp::DeskewArgs da{ts, {}};
+                for (int k = 0; k < 6; ++k) da.delta.v[k] = delta[k];
+                p->ready = false;
+                r = p->voxelize_into(p->prep[p->cur], f, m, &da);
+            } else if (p->ready && p->pf_frame == f && p->pf_n == m &&
                 p->pf_print == sageicp_pipeline::fingerprint(f, m)) {   // prepared while the last frame registered
                 r = p->pf_rc ? fail(p->pf_rc, p->pf_err) : SAGEICP_OK;
                 p->cur ^= 1;
@@ -1076,12 +1135,49 @@ int sageicp_pipeline_register_frame(sageicp_pipeline *p, const double *frame, ui
             return sageicp_map_update_pose(p->impl.map, fd.data(), n_fd, pose);
         }
     };
-    const int rc = p->impl.register_frame(frame, n, pose_out, icp_s, total_s, n_source, stats, Backend{p});
+    const int rc = p->impl.register_frame(frame, n, timestamps != nullptr, pose_out, icp_s, total_s, n_source, stats,
+                                          Backend{p, timestamps});
     p->announced = false;       // an announcement is consumed by this call, also when it failed or the frame was empty
     return rc;
 }
+int sageicp_pipeline_register_frame(sageicp_pipeline *p, const double *frame, uint64_t n,
+                                    double pose_out[7], double *icp_s, double *total_s,
+                                    uint64_t *n_source, sageicp_stats *stats) {
+    if (!p || !pose_out || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
+    return pipeline_register(p, frame, nullptr, n, pose_out, icp_s, total_s, n_source, stats);
+}
+int sageicp_pipeline_register_frame_timestamps(sageicp_pipeline *p, const double *frame, const double *timestamps,
+                                               uint64_t n, double pose_out[7], double *icp_s, double *total_s,
+                                               uint64_t *n_source, sageicp_stats *stats) {
+    if (!p || !pose_out || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
+    if (!p->deskew_on)          // config_.deskew false: the frame passes through, the timestamps are not read
+        return pipeline_register(p, frame, nullptr, n, pose_out, icp_s, total_s, n_source, stats);
+    // checked on every frame, also before the third pose exists, so that a bad stream fails on its first frame
+    if (n && !timestamps) return fail(SAGEICP_ERR_INVALID, "deskew is on and timestamps is NULL");
+    for (uint64_t i = 0; i < n; ++i)
+        if (!std::isfinite(timestamps[i])) return fail(SAGEICP_ERR_INVALID, "deskew is on and a timestamp is not finite");
+    static const double kNone = 0.0;       // (n == 0: a non-null marker that deskew is asked for)
+    return pipeline_register(p, frame, timestamps ? timestamps : &kNone, n, pose_out, icp_s, total_s, n_source, stats);
+}
+int sageicp_pipeline_set_deskew(sageicp_pipeline *p, int enable) {
+    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
+    if (p->worker.joinable()) p->worker.join();     // an announced or prepared frame is dropped
+    p->announced = false;
+    p->ready = false;
+    p->deskew_on = enable != 0;
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_deskew_info(const sageicp_pipeline *p, int *applied, double delta_out[6]) {
+    if (!p || !applied || !delta_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    *applied = p->impl.deskew_applied ? 1 : 0;
+    for (int k = 0; k < 6; ++k) delta_out[k] = p->impl.deskew_delta[k];
+    return SAGEICP_OK;
+}
 int sageicp_pipeline_prefetch(sageicp_pipeline *p, const double *frame, uint64_t n) {
     if (!p || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
+    if (p->deskew_on)
+        return fail(SAGEICP_ERR_INVALID, "sageicp_pipeline_prefetch: deskew is on: a deskewed frame's Preprocess() needs "
+                                         "the pose of the frame registered before it, so it cannot be prepared ahead");
     p->announced = true;
     p->an_frame = frame;
     p->an_n = n;

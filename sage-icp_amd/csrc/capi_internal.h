@@ -451,6 +451,12 @@ struct DynFilter {
             const DynFilterConfig &cfg, Point4 *tmp, Point4 *out, int *d_ovf, uint64_t &n_out, hipStream_t s);
 };
 
+// ---- deskew of a frame before it is preprocessed (deskew.hip; core/Deskew.cpp:36-50) ---------------------------
+struct DeskewArgs {
+    const double *timestamps;           // host, one per point, all finite (checked by the caller)
+    DeskewTangent delta;                // (start.inverse() * finish).log()
+};
+
 // ---- device preprocessing (preprocess.hip): buffers of one pipeline ------------------------------
 struct Prep {
     int device = -1;
@@ -483,6 +489,9 @@ struct Prep {
     uint32_t kept_levels[2] = {0, 0};   // points the last run left in d_fd / d_src
     DynFilter dyn;                      // the dynamic vehicle filter's buffers (allocated with its first use)
     bool dyn_ran = false;               // the last run filtered (dyn.info describes its frame)
+    // the timestamps of a frame that is deskewed (allocated with the first such frame): pinned staging, device copy
+    double *h_ts = nullptr, *d_ts = nullptr;
+    size_t ts_cap = 0;
 
     int init(int dev) {
         if (stream) return SAGEICP_OK;
@@ -534,6 +543,21 @@ struct Prep {
         cap = c;
         return SAGEICP_OK;
     }
+    int reserve_timestamps(size_t n) {
+        if (n <= ts_cap) return SAGEICP_OK;
+        free_timestamps();
+        const size_t c = n + n / 4 + 1024;
+        HIPCHK(hipMalloc(&d_ts, c * sizeof(double)));
+        HIPCHK(hipHostMalloc(&h_ts, c * sizeof(double), hipHostMallocDefault));
+        ts_cap = c;
+        return SAGEICP_OK;
+    }
+    void free_timestamps() {
+        if (d_ts) (void)hipFree(d_ts);
+        if (h_ts) (void)hipHostFree(h_ts);
+        d_ts = h_ts = nullptr;
+        ts_cap = 0;
+    }
     void free_points() {
         if (d_in) (void)hipFree(d_in);
         if (d_tmp) (void)hipFree(d_tmp);
@@ -562,6 +586,7 @@ struct Prep {
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(stream);
         free_points();
+        free_timestamps();
         dyn.destroy();
         if (d_nkept) (void)hipFree(d_nkept);
         if (d_overflow) (void)hipFree(d_overflow);
@@ -575,11 +600,13 @@ struct Prep {
     // levels in sequence on the device, each feeding the next, and returns every level's cloud.
     // With `dyn_cfg` the frame first goes through Preprocess()'s dynamic vehicle filter (dyn_filter.hip), which
     // crops it itself: the levels then start from the filtered cloud with the crop off.
+    // With `deskew` the uploaded frame is deskewed in place before anything else reads it (the reference's order:
+    // DeSkewScan, then Preprocess, then Voxelize; pipeline/sageICP.cpp:36-52).
     int run(const double *frame, uint64_t n, double max_range, double min_range,
             double label_max_range, int n_groups, const int *gcounts, const int *glabels,
             const double *gvs, const int *crop, const double *scales, int n_levels,
             std::vector<std::vector<double>> &out, bool download = true,
-            const DynFilterConfig *dyn_cfg = nullptr) {
+            const DynFilterConfig *dyn_cfg = nullptr, const DeskewArgs *deskew = nullptr) {
         kept_levels[0] = kept_levels[1] = 0;
         us_order = 0;
         dyn_ran = dyn_cfg != nullptr;
@@ -590,6 +617,10 @@ struct Prep {
         for (int g = 0; g < n_groups; ++g) nlabels += static_cast<size_t>(gcounts[g]);
         int rc = reserve(n, nlabels);
         if (rc) return rc;
+        if (deskew) {
+            rc = reserve_timestamps(n);
+            if (rc) return rc;
+        }
         HIPCHK(hipSetDevice(device));
         out.assign(n_levels, std::vector<double>());
         if (n == 0) return SAGEICP_OK;
@@ -600,6 +631,12 @@ struct Prep {
         HIPCHK(hipMemsetAsync(d_overflow, 0, sizeof(int), stream));
         std::memcpy(h_pin, frame, n * sizeof(Point4));
         HIPCHK(hipMemcpyAsync(d_in, h_pin, n * sizeof(Point4), hipMemcpyHostToDevice, stream));
+        if (deskew) {
+            std::memcpy(h_ts, deskew->timestamps, n * sizeof(double));
+            HIPCHK(hipMemcpyAsync(d_ts, h_ts, n * sizeof(double), hipMemcpyHostToDevice, stream));
+            launch_deskew(d_in, d_in, d_ts, static_cast<int>(n), deskew->delta, stream);
+            HIPCHK(hipGetLastError());
+        }
         const Point4 *in = d_in;
         Point4 *outs[2] = {d_fd, d_src};
         uint64_t cur = n;

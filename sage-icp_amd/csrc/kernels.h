@@ -268,6 +268,12 @@ void launch_vds_permute(const Point4 *in, const uint32_t *perm, uint32_t n, Poin
 hipError_t voxel_downsample_device(const VdsParams &P, void *sort_temp, size_t sort_temp_bytes,
                                    uint32_t *d_n_kept, Point4 *out, hipStream_t s);
 
+// deskew.hip: DeSkewScan (core/Deskew.cpp:36-50) of n points, in place when out == in; ts: [n] device fp64 timestamps
+struct DeskewTangent {
+    double v[6];                       // (start.inverse() * finish).log(): translation first
+};
+void launch_deskew(const Point4 *in, Point4 *out, const double *ts, int n, const DeskewTangent &d, hipStream_t s);
+
 // sort.hip: re-ordering of a frame along the Morton curve of its map-frame voxels
 size_t sort_temp_bytes(int n);
 // ... and the dispatch order of k_icp's stripes: `order` = the stripes by `work`, heaviest first (stable); `work` is zeroed

@@ -5,6 +5,7 @@
 // shims use.
 //
 // Reference (cpp/sage_icp/):
+//   pipeline/sageICP.cpp:36-52     sageICP::RegisterFrame(frame, timestamps): the deskew decision and its delta
 //   pipeline/sageICP.cpp:54-95     sageICP::RegisterFrame           -> Pipeline::register_frame
 //   pipeline/sageICP.cpp:97-121    Voxelize / GetAdaptiveThreshold / GetPredictionModel / HasMoved
 //   core/Threshold.cpp:29-50       AdaptiveThreshold::ComputeThreshold, ComputeModelError
@@ -12,7 +13,8 @@
 //   core/Preprocessing.cpp:173-187 Preprocess, dynamic_vehicle_filter == false branch
 // The PCL Euclidean-clustering "dynamic vehicle filter" (Preprocessing.cpp:95-172) runs on the device
 // (dyn_filter.hip) when sageicp_pipeline_set_dynamic_vehicle_filter switched it on, before the
-// down-sampling.  Not reproduced: deskewing (off in every launch file).  The down-sampled clouds come from the backend in the reference's
+// down-sampling.  Deskewing (core/Deskew.cpp) runs on the device (deskew.hip) on the raw frame before anything else
+// when the caller passes timestamps, and three poses or more exist.  The down-sampled clouds come from the backend in the reference's
 // emission order (the bucket order of its tsl::robin_map, Preprocessing.cpp:76-82, replayed by
 // csrc/robin_order.hpp) unless sageicp_set_downsample_order(0) selected arrival order per label
 // group.
@@ -65,19 +67,32 @@ public:
         sageicp_map_clear(map);
     }
 
-    // pipeline/sageICP.cpp:54-95.  The three device stages are supplied by the caller (capi.hip):
-    //   be.voxelize(frame, n, n_source)      Preprocess() + Voxelize() (preprocess.hip;
+    // pipeline/sageICP.cpp:36-95.  The three device stages are supplied by the caller (capi.hip):
+    //   be.voxelize(frame, n, n_source, delta)  DeSkewScan() if delta != nullptr (deskew.hip; core/Deskew.cpp:36-50),
+    //                                        then Preprocess() + Voxelize() (preprocess.hip;
     //                                        core/Preprocessing.cpp:173-187,44-84,
     //                                        pipeline/sageICP.cpp:57-67,97-101); both clouds stay
     //                                        on the device
     //   be.register_source(guess, max_corr, kernel, sem_th, pose, stats)    RegisterFrame(source, ...)
     //   be.update_map(pose)                  local_map_.Update(frame_downsample, pose)
+    // deskew: RegisterFrame(frame, timestamps) with config_.deskew (the caller has the timestamps); false: the
+    // one-argument RegisterFrame(frame), which never deskews.
     template <typename Backend>
-    int register_frame(const double *frame, uint64_t n, double pose_out[7], double *icp_s,
+    int register_frame(const double *frame, uint64_t n, bool deskew, double pose_out[7], double *icp_s,
                        double *total_s, uint64_t *n_source, sageicp_stats *stats, Backend &&be) {
         const auto t_pre = std::chrono::steady_clock::now();
+        deskew_applied = false;
+        for (double &d : deskew_delta) d = 0.0;
+        if (deskew && poses.size() > 2) {                    // sageICP.cpp:42-48: N <= 2 passes the frame through
+            const size_t N = poses.size();
+            Pose7 inv, rel;
+            se3_inv(poses[N - 2].v, inv.v);
+            se3_mul(inv.v, poses[N - 1].v, rel.v);
+            se3_log(rel.v, deskew_delta);                   // Deskew.cpp:36
+            deskew_applied = true;
+        }
         uint64_t n_src = 0;
-        int rc = be.voxelize(frame, n, n_src);
+        int rc = be.voxelize(frame, n, n_src, deskew_applied ? deskew_delta : nullptr);
         if (rc) return rc;
         const double sigma = adaptive_threshold();
         Pose7 prediction;                                     // GetPredictionModel()
@@ -112,6 +127,9 @@ public:
 
     std::vector<Pose7> poses;
     sageicp_map *map = nullptr;
+    // the last register_frame: whether it deskewed its frame, and with which tangent (zeros if not)
+    bool deskew_applied = false;
+    double deskew_delta[6] = {0, 0, 0, 0, 0, 0};
 
     // label groups as flat tables for the device kernels
     void group_tables(std::vector<int> &counts, std::vector<int> &labels, std::vector<double> &vs) const {
