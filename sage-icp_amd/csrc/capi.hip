@@ -181,26 +181,6 @@ void sageicp_map_destroy(sageicp_map *m) {
     if (m->sc.stream) {
         (void)hipSetDevice(m->device);
         (void)hipStreamSynchronize(m->sc.stream);
-        if (m->d_table) (void)hipFree(m->d_table);
-        if (m->d_pts) (void)hipFree(m->d_pts);
-        if (m->d_cand) (void)hipFree(m->d_cand);
-        if (m->d_cand_flags) (void)hipFree(m->d_cand_flags);
-        if (m->d_stage) (void)hipFree(m->d_stage);
-        if (m->h_stage) (void)hipHostFree(m->h_stage);
-        for (int k = 0; k < kMaxClasses; ++k)
-            if (m->d_free_units[k]) (void)hipFree(m->d_free_units[k]);
-        if (m->d_regions) (void)hipFree(m->d_regions);
-        if (m->d_freed) (void)hipFree(m->d_freed);
-        if (m->d_block_of) (void)hipFree(m->d_block_of);
-        void *aux[] = {m->d_zeros, m->d_slot_of, m->d_free, m->d_ctr, m->up.raw, m->up.w, m->up.keys,
-                       m->up.keys_alt, m->up.idx, m->up.idx_alt, m->up.head_slot, m->up.flag, m->up.rank, m->up.want,
-                       m->up.far_flag, m->up.far_sel, m->up.n_sel, m->up.temp};
-        for (void *q : aux)
-            if (q) (void)hipFree(q);
-        if (m->h_ctr) (void)hipHostFree(m->h_ctr);
-        if (m->h_ctr_aux) (void)hipHostFree(m->h_ctr_aux);
-        if (m->h_lists) (void)hipHostFree(m->h_lists);
-        if (m->d_pc) (void)hipFree(m->d_pc);
     }
     m->sc.destroy();
     delete m;
@@ -222,34 +202,33 @@ static int clone_on_device(const sageicp_map *src, sageicp_map *m) {
     HIPCHK(hipSetDevice(m->device));
     hipStream_t s = m->sc.stream;
     HIPCHK(hipStreamSynchronize(src->sc.stream));
-    HIPCHK(hipMalloc(&m->d_table, src->d_table_cap * sizeof(Slot)));
-    m->d_table_cap = src->d_table_cap;
-    HIPCHK(hipMemcpyAsync(m->d_table, src->d_table, src->d_table_cap * sizeof(Slot),
+    HIPCHK(m->d_table.reserve(src->d_table.capacity()));
+    HIPCHK(hipMemcpyAsync(m->d_table.data(), src->d_table.data(), src->d_table.capacity() * sizeof(Slot),
                           hipMemcpyDeviceToDevice, s));
     m->ctr = src->ctr;
-    if ((rc = grow_device_blocks(m, src->d_blocks_cap, 0))) return rc;
-    if ((rc = reserve_device_points(m, src->d_units_cap, 0))) return rc;
+    if ((rc = grow_device_blocks(m, src->blocks_cap(), 0))) return rc;
+    if ((rc = reserve_device_points(m, src->units_cap(), 0))) return rc;
     m->on_device = false;       // (reserve_unit_stacks: nothing of this map's to keep yet)
     if ((rc = reserve_unit_stacks(m, 0))) return rc;
-    HIPCHK(hipMemcpyAsync(m->d_pts, src->d_pts, static_cast<size_t>(m->ctr.units_hi) * kUnitPoints * sizeof(Point4),
+    HIPCHK(hipMemcpyAsync(m->d_pts.data(), src->d_pts.data(), static_cast<size_t>(m->ctr.units_hi) * kUnitPoints * sizeof(Point4),
                           hipMemcpyDeviceToDevice, s));
     for (int k = 0; k < h.n_classes; ++k)
         if (m->ctr.free_units_count[k] > 0)
-            HIPCHK(hipMemcpyAsync(m->d_free_units[k], src->d_free_units[k],
+            HIPCHK(hipMemcpyAsync(m->d_free_units[k].data(), src->d_free_units[k].data(),
                                   static_cast<size_t>(m->ctr.free_units_count[k]) * sizeof(uint32_t),
                                   hipMemcpyDeviceToDevice, s));
     if (m->ctr.units_hi)
-        HIPCHK(hipMemcpyAsync(m->d_block_of, src->d_block_of, static_cast<size_t>(m->ctr.units_hi) * sizeof(uint32_t),
+        HIPCHK(hipMemcpyAsync(m->d_block_of.data(), src->d_block_of.data(), static_cast<size_t>(m->ctr.units_hi) * sizeof(uint32_t),
                               hipMemcpyDeviceToDevice, s));
     if (m->ctr.blocks_hi) {
-        HIPCHK(hipMemcpyAsync(m->d_regions, src->d_regions, m->ctr.blocks_hi * sizeof(uint32_t),
+        HIPCHK(hipMemcpyAsync(m->d_regions.data(), src->d_regions.data(), m->ctr.blocks_hi * sizeof(uint32_t),
                               hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(m->d_zeros, src->d_zeros, m->ctr.blocks_hi, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(m->d_slot_of, src->d_slot_of, m->ctr.blocks_hi * sizeof(uint32_t),
+        HIPCHK(hipMemcpyAsync(m->d_zeros.data(), src->d_zeros.data(), m->ctr.blocks_hi, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(m->d_slot_of.data(), src->d_slot_of.data(), m->ctr.blocks_hi * sizeof(uint32_t),
                               hipMemcpyDeviceToDevice, s));
     }
     if (m->ctr.free_count)
-        HIPCHK(hipMemcpyAsync(m->d_free, src->d_free, m->ctr.free_count * sizeof(uint32_t),
+        HIPCHK(hipMemcpyAsync(m->d_free.data(), src->d_free.data(), m->ctr.free_count * sizeof(uint32_t),
                               hipMemcpyDeviceToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     m->on_device = true;
@@ -441,13 +420,7 @@ static int pointcloud_from_device(const sageicp_map *m, double *out, uint64_t ca
     if (!want) return SAGEICP_OK;
     int rc = reserve_update_scratch(m, 0, static_cast<size_t>(m->ctr.blocks_hi) + 1);
     if (rc) return rc;
-    if (total > m->d_pc_cap) {
-        if (m->d_pc) HIPCHK(hipFree(m->d_pc));
-        m->d_pc = nullptr; m->d_pc_cap = 0;
-        const size_t c = total + total / 4 + 1024;
-        HIPCHK(hipMalloc(&m->d_pc, c * sizeof(Point4)));
-        m->d_pc_cap = c;
-    }
+    if (total > m->d_pc.capacity()) HIPCHK(m->d_pc.reserve(total + total / 4 + 1024));
     const DevMap dm = dev_map(m);
     if (m->host.track_order) {
         // reference-order mode: the voxels in the bucket order of the host's array (VoxelHashMap.cpp:132-142), their points
@@ -456,14 +429,14 @@ static int pointcloud_from_device(const sageicp_map *m, double *out, uint64_t ca
         list.reserve(m->host.order.size());
         m->host.order.for_each([&](uint32_t b) { list.push_back(b); });
         if ((rc = reserve_update_scratch(m, 0, list.size() + 1))) return rc;
-        uint32_t *d_list = reinterpret_cast<uint32_t *>(m->up.far_list);        // ([nb] uint2: room for the list)
+        uint32_t *d_list = reinterpret_cast<uint32_t *>(m->up.far_list.data());        // ([nb] uint2: room for the list)
         if (!list.empty()) HIPCHK(hipMemcpyAsync(d_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIPCHK(map_pointcloud_listed(dm, d_list, static_cast<uint32_t>(list.size()), m->up.far_flag, m->up.far_sel, m->up.temp,
-                                     m->up.temp_bytes, m->d_pc, s));
+        HIPCHK(map_pointcloud_listed(dm, d_list, static_cast<uint32_t>(list.size()), m->up.far_flag.data(), m->up.far_sel.data(), m->up.temp.data(),
+                                     m->up.temp.capacity(), m->d_pc.data(), s));
         HIPCHK(hipStreamSynchronize(s));                                         // (`list` is pageable and leaves scope)
     } else {
-        HIPCHK(map_pointcloud_device(dm, m->ctr.blocks_hi, m->up.far_flag, m->up.far_sel, m->up.temp,
-                                     m->up.temp_bytes, m->d_pc, s));
+        HIPCHK(map_pointcloud_device(dm, m->ctr.blocks_hi, m->up.far_flag.data(), m->up.far_sel.data(), m->up.temp.data(),
+                                     m->up.temp.capacity(), m->d_pc.data(), s));
     }
     // The destination is the caller's pageable buffer, and under the reference's interface a FRESH
     // one every call (`std::vector<Eigen::Vector4d> Pointcloud()` returns by value: tens of MB
@@ -472,7 +445,7 @@ static int pointcloud_from_device(const sageicp_map *m, double *out, uint64_t ca
     // by one inside the copy (profiles/pointcloud_probe.py).  So the pages are made to exist first, by a
     // few parked host threads side by side, while the device packs the points.
     pretouch(out, want * sizeof(Point4));
-    HIPCHK(hipMemcpyAsync(out, m->d_pc, want * sizeof(Point4), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(out, m->d_pc.data(), want * sizeof(Point4), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return SAGEICP_OK;
 }
@@ -522,26 +495,26 @@ int sageicp_get_correspondences(const sageicp_map *m, const double *q, uint64_t 
     if ((rc = sc.reserve_nn(n))) return rc;
     if ((rc = sc.reserve_sort(n))) return rc;
     hipStream_t s = sc.stream;
-    HIPCHK(hipMemcpyAsync(sc.d_frame, q, n * sizeof(Point4), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.d_frame.data(), q, n * sizeof(Point4), hipMemcpyHostToDevice, s));
     double I[7];
     identity_pose(I);
-    fill_state(sc.h_state, I);
-    HIPCHK(hipMemcpyAsync(sc.d_state, sc.h_state, sizeof(IcpState), hipMemcpyHostToDevice, s));
+    fill_state(sc.h_state.data(), I);
+    HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
     // same pipeline as the ICP loop, pose = identity: sort, rows, search; results are mapped
     // back to the caller's query order through the sort permutation
-    HIPCHK(sort_frame(sc.d_frame, sc.d_sorted, static_cast<int>(n), sc.d_state, false, false,
-                      m->host.voxel_size, sc.d_keys, sc.d_vals, sc.d_sort_temp, sc.sort_temp_bytes_,
+    HIPCHK(sort_frame(sc.d_frame.data(), sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), false, false,
+                      m->host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(), sc.d_sort_temp.capacity(),
                       s));
     const int lw = icp_lw(n, sparse_voxels(m));
     if ((rc = ensure_cand(m, wants_filter(m, n, sem_th)))) return rc;
-    const IcpParams ip = icp_params(m, sc.d_sorted, n, sem_th, lw);     // identity pose, no loop state
+    const IcpParams ip = icp_params(m, sc.d_sorted.data(), n, sem_th, lw);     // identity pose, no loop state
     launch_rows(ip, s);
     launch_icp(ip, lw, false, s);
     HIPCHK(hipGetLastError());
     std::vector<int32_t> idx(n);
     std::vector<uint32_t> perm(n);
-    HIPCHK(hipMemcpyAsync(idx.data(), sc.d_nn, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(perm.data(), sc.d_vals + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
+    HIPCHK(hipMemcpyAsync(idx.data(), sc.d_nn.data(), n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(perm.data(), sc.d_vals.data() + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost,
                           s));
     HIPCHK(hipStreamSynchronize(s));
     std::vector<int32_t> by_query(n);
@@ -577,30 +550,30 @@ int sageicp_align_clouds(const double *src, const double *tgt, uint64_t n, doubl
         if ((r = sc.reserve_tgt(n))) return r;
         hipStream_t s = sc.stream;
         if (n) {
-            HIPCHK(hipMemcpyAsync(sc.d_frame, src, n * sizeof(Point4), hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(sc.d_tgt, tgt, n * sizeof(Point4), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(sc.d_frame.data(), src, n * sizeof(Point4), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(sc.d_tgt.data(), tgt, n * sizeof(Point4), hipMemcpyHostToDevice, s));
         }
         double I[7];
         identity_pose(I);
-        fill_state(sc.h_state, I);
-        HIPCHK(hipMemcpyAsync(sc.d_state, sc.h_state, sizeof(IcpState), hipMemcpyHostToDevice, s));
+        fill_state(sc.h_state.data(), I);
+        HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
         if ((r = sc.reserve_partials(128))) return r;
-        GnParams gp{sc.d_frame, sc.d_tgt, static_cast<int>(n), kernel, sc.d_partials};
+        GnParams gp{sc.d_frame.data(), sc.d_tgt.data(), static_cast<int>(n), kernel, sc.d_partials.data()};
         FinParams fp{};
-        fp.st = sc.d_state;
-        fp.partials = sc.d_partials;
+        fp.st = sc.d_state.data();
+        fp.partials = sc.d_partials.data();
         fp.nparts = launch_gn(gp, s);
         fp.mode = 0;
         fp.standalone = 1;
         launch_fin(fp, s);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(sc.h_state, sc.d_state, sizeof(IcpState), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         // one step from identity: T_icp == est
-        for (int i = 0; i < 7; ++i) pose_out[i] = sc.h_state->T_icp[i];
+        for (int i = 0; i < 7; ++i) pose_out[i] = sc.h_state.data()->T_icp[i];
         if (JTJ_out || JTr_out) {
             double JTJ[36], JTr[6];
-            assemble_normal_equations(sc.h_state->sums, JTJ, JTr);
+            assemble_normal_equations(sc.h_state.data()->sums, JTJ, JTr);
             if (JTJ_out) std::memcpy(JTJ_out, JTJ, sizeof(JTJ));
             if (JTr_out) std::memcpy(JTr_out, JTr, sizeof(JTr));
         }
@@ -623,13 +596,13 @@ int sageicp_transform_points(const double pose[7], double *xyzl, uint64_t n, int
         int r;
         if ((r = sc.reserve_frame(n))) return r;
         hipStream_t s = sc.stream;
-        fill_state(sc.h_state, pose);
-        HIPCHK(hipMemcpyAsync(sc.d_state, sc.h_state, sizeof(IcpState), hipMemcpyHostToDevice, s));
+        fill_state(sc.h_state.data(), pose);
+        HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
         if (n) {
-            HIPCHK(hipMemcpyAsync(sc.d_frame, xyzl, n * sizeof(Point4), hipMemcpyHostToDevice, s));
-            launch_tf(sc.d_frame, static_cast<int>(n), sc.d_state, s);
+            HIPCHK(hipMemcpyAsync(sc.d_frame.data(), xyzl, n * sizeof(Point4), hipMemcpyHostToDevice, s));
+            launch_tf(sc.d_frame.data(), static_cast<int>(n), sc.d_state.data(), s);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(xyzl, sc.d_frame, n * sizeof(Point4), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(xyzl, sc.d_frame.data(), n * sizeof(Point4), hipMemcpyDeviceToHost, s));
         }
         HIPCHK(hipStreamSynchronize(s));
         return SAGEICP_OK;
@@ -656,10 +629,10 @@ int sageicp_register_frame(const sageicp_map *m, const double *frame, uint64_t n
     if (rc) return rc;
     Scratch &sc = m->sc;
     if ((rc = sc.reserve_frame(n))) return rc;
-    if (n) HIPCHK(hipMemcpyAsync(sc.d_frame, frame, n * sizeof(Point4), hipMemcpyHostToDevice,
+    if (n) HIPCHK(hipMemcpyAsync(sc.d_frame.data(), frame, n * sizeof(Point4), hipMemcpyHostToDevice,
                                  sc.stream));
     const double us_upload = now_us() - t0;
-    return run_icp(m, sc.d_frame, n, init, max_dist, kernel, sem_th, nullptr, pose_out, stats,
+    return run_icp(m, sc.d_frame.data(), n, init, max_dist, kernel, sem_th, nullptr, pose_out, stats,
                    us_upload, t0);
 }
 
@@ -683,14 +656,13 @@ sageicp_frame *sageicp_frame_upload(const sageicp_map *m, const double *frame, u
     sageicp_frame *f = new sageicp_frame;
     f->device = m->device;
     f->n = n;
-    if (hipMalloc(&f->d, std::max<uint64_t>(n, 1) * sizeof(Point4)) != hipSuccess) {
+    if (f->d.reserve(std::max<uint64_t>(n, 1)) != hipSuccess) {
         fail(SAGEICP_ERR_HIP, "hipMalloc(frame)");
         delete f;
         return nullptr;
     }
-    if (n && hipMemcpy(f->d, frame, n * sizeof(Point4), hipMemcpyHostToDevice) != hipSuccess) {
+    if (n && hipMemcpy(f->d.data(), frame, n * sizeof(Point4), hipMemcpyHostToDevice) != hipSuccess) {
         fail(SAGEICP_ERR_HIP, "hipMemcpy(frame)");
-        (void)hipFree(f->d);
         delete f;
         return nullptr;
     }
@@ -700,32 +672,38 @@ sageicp_frame *sageicp_frame_upload(const sageicp_map *m, const double *frame, u
 void sageicp_frame_destroy(sageicp_frame *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
-    if (f->d) (void)hipFree(f->d);
     delete f;
+}
+
+// RegisterFrame of n points already on `device` (an uploaded frame, or the pipeline's source cloud)
+static int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
+                             double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
+                             sageicp_stats *stats) {
+    if (!m || !init || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    if (device != m->device) return fail(SAGEICP_ERR_INVALID, "frame and map live on different devices");
+    if (comm && comm->device != m->device) return fail(SAGEICP_ERR_INVALID, "comm and map live on different devices");
+    const double t0 = now_us();
+    if (map_is_empty(m)) {
+        std::memcpy(pose_out, init, 56);
+        if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->n_queries = n; }
+        return SAGEICP_OK;
+    }
+    if (!m->replicas.empty()) {
+        if (comm) return fail(SAGEICP_ERR_INVALID, "a map that spans several devices shards the frame itself");
+        return register_sharded(m, nullptr, d_frame, n, init, max_dist, kernel, sem_th, pose_out, stats, t0);
+    }
+    int rc = sync_mirror(m);
+    if (rc) return rc;
+    const double us_upload = now_us() - t0;
+    return run_icp(m, d_frame, n, init, max_dist, kernel, sem_th, comm, pose_out, stats, us_upload, t0);
 }
 
 int sageicp_register_frame_resident(const sageicp_map *m, const sageicp_frame *f,
                                     const double init[7], double max_dist, double kernel,
                                     double sem_th, sageicp_comm *comm, double pose_out[7],
                                     sageicp_stats *stats) {
-    if (!m || !f || !init || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    if (f->device != m->device) return fail(SAGEICP_ERR_INVALID, "frame and map live on different devices");
-    if (comm && comm->device != m->device) return fail(SAGEICP_ERR_INVALID, "comm and map live on different devices");
-    const double t0 = now_us();
-    if (map_is_empty(m)) {
-        std::memcpy(pose_out, init, 56);
-        if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->n_queries = f->n; }
-        return SAGEICP_OK;
-    }
-    if (!m->replicas.empty()) {
-        if (comm) return fail(SAGEICP_ERR_INVALID, "a map that spans several devices shards the frame itself");
-        return register_sharded(m, nullptr, f->d, f->n, init, max_dist, kernel, sem_th, pose_out, stats, t0);
-    }
-    int rc = sync_mirror(m);
-    if (rc) return rc;
-    const double us_upload = now_us() - t0;
-    return run_icp(m, f->d, f->n, init, max_dist, kernel, sem_th, comm, pose_out, stats, us_upload,
-                   t0);
+    if (!f) return fail(SAGEICP_ERR_INVALID, "null argument");
+    return register_resident(m, f->d.data(), f->n, f->device, init, max_dist, kernel, sem_th, comm, pose_out, stats);
 }
 
 // ---- RCCL communicator ------------------------------------------------------------------------
@@ -783,8 +761,8 @@ int sageicp_comm_p2p_export(sageicp_comm *c, uint8_t handle_out[SAGEICP_P2P_HAND
         HIPCHK(hipExtMallocWithFlags(reinterpret_cast<void **>(&c->my_block), sizeof(P2pBlock),
                                      hipDeviceMallocFinegrained));
         HIPCHK(hipMemset(c->my_block, 0, sizeof(P2pBlock)));
-        HIPCHK(hipMalloc(&c->d_exchanges, sizeof(unsigned long long)));
-        HIPCHK(hipMemset(c->d_exchanges, 0, sizeof(unsigned long long)));
+        HIPCHK(c->d_exchanges.reserve(1));
+        HIPCHK(hipMemset(c->d_exchanges.data(), 0, sizeof(unsigned long long)));
         HIPCHK(hipDeviceSynchronize());
     }
     hipIpcMemHandle_t h;
@@ -854,7 +832,6 @@ void sageicp_comm_destroy(sageicp_comm *c) {
     for (int r = 0; r < c->nranks && r < kMaxRanks; ++r)
         if (r != c->rank && c->blocks[r] && !c->peer_mapped) (void)hipIpcCloseMemHandle(c->blocks[r]);
     if (c->my_block) (void)hipFree(c->my_block);
-    if (c->d_exchanges) (void)hipFree(c->d_exchanges);
     if (c->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(c->comm);
     delete c;
 }
@@ -960,26 +937,24 @@ int sageicp_deskew_scan(const double *frame, const double *timestamps, uint64_t 
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
         return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
     if (device < 0 || device >= count) return fail(SAGEICP_ERR_INVALID, "device ordinal out of range");
-    Point4 *d_p = nullptr;
-    double *d_t = nullptr;
+    DevBuf<Point4> d_p;
+    DevBuf<double> d_t;
     hipStream_t s = nullptr;
     auto body = [&]() -> int {
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIPCHK(hipMalloc(&d_p, n * sizeof(Point4)));
-        HIPCHK(hipMalloc(&d_t, n * sizeof(double)));
-        HIPCHK(hipMemcpyAsync(d_p, frame, n * sizeof(Point4), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_t, timestamps, n * sizeof(double), hipMemcpyHostToDevice, s));
-        launch_deskew(d_p, d_p, d_t, static_cast<int>(n), delta, s);
+        HIPCHK(d_p.reserve(n));
+        HIPCHK(d_t.reserve(n));
+        HIPCHK(hipMemcpyAsync(d_p.data(), frame, n * sizeof(Point4), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_t.data(), timestamps, n * sizeof(double), hipMemcpyHostToDevice, s));
+        launch_deskew(d_p.data(), d_p.data(), d_t.data(), static_cast<int>(n), delta, s);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out, d_p, n * sizeof(Point4), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out, d_p.data(), n * sizeof(Point4), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return SAGEICP_OK;
     };
     const int rc = body();
     if (s) (void)hipStreamSynchronize(s);
-    if (d_p) (void)hipFree(d_p);
-    if (d_t) (void)hipFree(d_t);
     if (s) (void)hipStreamDestroy(s);
     return rc;
 }
@@ -1115,22 +1090,19 @@ static int pipeline_register(sageicp_pipeline *p, const double *frame, const dou
         }
         int register_source(const double guess[7], double max_dist, double kernel, double sem_th,
                             double pose[7], sageicp_stats *stats) {
-            sageicp_frame view;                 // non-owning: the source cloud in the Prep buffers
-            view.device = p->device;
-            view.d = p->prep[p->cur].d_src;
-            view.n = p->prep[p->cur].kept_levels[1];
-            return sageicp_register_frame_resident(p->impl.map, &view, guess, max_dist, kernel, sem_th,
-                                                   nullptr, pose, stats);
+            // the source cloud in the Prep buffers
+            return register_resident(p->impl.map, p->prep[p->cur].d_src.data(), p->prep[p->cur].kept_levels[1],
+                                     p->device, guess, max_dist, kernel, sem_th, nullptr, pose, stats);
         }
         int update_map(const double pose[7]) {
             const sageicp::Prep &pr = p->prep[p->cur];
             const uint64_t n_fd = pr.kept_levels[0];
             if (p->impl.map_update_on_device_())
-                return device_update_all(p->impl.map, nullptr, n_fd, pose, pr.d_fd);
+                return device_update_all(p->impl.map, nullptr, n_fd, pose, pr.d_fd.data());
             std::vector<double> fd(4 * n_fd);
             if (n_fd) {
                 HIPCHK(hipSetDevice(p->device));
-                HIPCHK(hipMemcpy(fd.data(), pr.d_fd, n_fd * sizeof(Point4), hipMemcpyDeviceToHost));
+                HIPCHK(hipMemcpy(fd.data(), pr.d_fd.data(), n_fd * sizeof(Point4), hipMemcpyDeviceToHost));
             }
             return sageicp_map_update_pose(p->impl.map, fd.data(), n_fd, pose);
         }
@@ -1262,8 +1234,8 @@ int sageicp_metrics_absolute_trajectory_error(const double *poses_gt, const doub
 // probes: the loop state the last RegisterFrame of this map left on the host (pose T[7], T_icp[7], the last
 // reduced sums [20], iterations, last step)
 extern "C" int sageicp_debug_last_state(const sageicp_map *m, double *out36) {
-    if (!m || !m->sc.h_state) return SAGEICP_ERR_INVALID;
-    const sageicp::IcpState &st = *m->sc.h_state;
+    if (!m || !m->sc.h_state.data()) return SAGEICP_ERR_INVALID;
+    const sageicp::IcpState &st = *m->sc.h_state.data();
     for (int i = 0; i < 7; ++i) out36[i] = st.T[i];
     for (int i = 0; i < 7; ++i) out36[7 + i] = st.T_icp[i];
     for (int i = 0; i < sageicp::kNumSums; ++i) out36[14 + i] = st.sums[i];
@@ -1275,7 +1247,7 @@ extern "C" int sageicp_debug_last_state(const sageicp_map *m, double *out36) {
 #ifdef SAGE_NN_TIMING
 // probe: map points handed to every query in the last iteration (sorted order)
 extern "C" int sageicp_debug_work(const sageicp_map *m, uint32_t *out, size_t n) {
-    if (!m || !m->sc.d_work) return SAGEICP_ERR_INVALID;
-    return hipMemcpy(out, m->sc.d_work, n * 4, hipMemcpyDeviceToHost) == hipSuccess ? SAGEICP_OK : SAGEICP_ERR_HIP;
+    if (!m || !m->sc.d_work.data()) return SAGEICP_ERR_INVALID;
+    return hipMemcpy(out, m->sc.d_work.data(), n * 4, hipMemcpyDeviceToHost) == hipSuccess ? SAGEICP_OK : SAGEICP_ERR_HIP;
 }
 #endif

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/sageicp.h"
+#include "dev_buffer.h"
 #include "dyn_rules.h"
 #include "host_map.hpp"
 #include "kernels.h"
@@ -125,19 +126,20 @@ constexpr int kChunkMax = 16;
 struct Scratch {
     int device = -1;
     hipStream_t stream = nullptr;
-    Point4 *d_frame = nullptr; size_t frame_cap = 0;
-    Point4 *d_tgt = nullptr; size_t tgt_cap = 0;
-    int32_t *d_nn = nullptr; size_t nn_cap = 0;
+    DevBuf<Point4> d_frame, d_tgt;
+    DevBuf<int32_t> d_nn;
     // Morton re-ordering of the frame (sort.hip)
-    Point4 *d_sorted = nullptr; uint32_t *d_keys = nullptr; uint32_t *d_vals = nullptr;
-    void *d_sort_temp = nullptr; size_t sort_cap = 0; size_t sort_temp_bytes_ = 0;
+    DevBuf<Point4> d_sorted;
+    DevBuf<uint32_t> d_keys, d_vals;
+    DevBuf<unsigned char> d_sort_temp;
+    size_t sort_cap = 0;           // points the buffers of reserve_sort hold (all of them: 0 after a failed reserve)
     // per-call work buffers: the queries' cached neighbourhood rows, the workgroup partials
-    uint32_t *d_rows = nullptr;
-    uint2 *d_prev = nullptr;       // every query's record of the previous iteration (kernels.h)
-    uint32_t *d_work = nullptr;    // instrumented builds: points handed to each query
-    double *d_partials = nullptr; size_t partials_cap = 0;
-    long long *d_acc = nullptr;    // fixed-point accumulators of the Gauss-Newton sums (kernels.h, kAcc*)
-    LoopShared *d_loop = nullptr;  // what the workgroups of k_loop share inside its launch (kernels.h)
+    DevBuf<uint32_t> d_rows;
+    DevBuf<uint2> d_prev;          // every query's record of the previous iteration (kernels.h)
+    DevBuf<uint32_t> d_work;       // instrumented builds: points handed to each query
+    DevBuf<double> d_partials;
+    DevBuf<long long> d_acc;       // fixed-point accumulators of the Gauss-Newton sums (kernels.h, kAcc*)
+    DevBuf<LoopShared> d_loop;     // what the workgroups of k_loop share inside its launch (kernels.h)
     unsigned long long go_word = 0; // (host source of a `go` word sent by a copy: run_icp)
     hipStream_t stream2 = nullptr; // the solving wave of the one-launch loop runs here, beside the grid on `stream`
                                    // (created with the first such launch: a process has few hardware queues, and
@@ -154,10 +156,10 @@ struct Scratch {
     uint64_t calls_single_launch = 0, calls_per_iteration = 0, calls_chained = 0;
     uint32_t loop_timeouts = 0;
     int last_fallback = 0;
-    unsigned long long *d_cand = nullptr;      // per-wave counters of k_icp [2 x sort_cap]
-    IcpState *d_state = nullptr;
-    IcpState *h_state = nullptr;   // pinned
-    IcpProgress *h_prog = nullptr; // pinned + host-mapped: written by the device every iteration
+    DevBuf<unsigned long long> d_cand;         // per-wave counters of k_icp [2 x sort_cap]
+    DevBuf<IcpState> d_state;
+    PinnedBuf<IcpState> h_state;
+    PinnedBuf<IcpProgress, hipHostMallocMapped | hipHostMallocCoherent> h_prog;   // written by the device every iteration
     IcpProgress *d_prog = nullptr; // its device address
     std::vector<hipEvent_t> events;  // 5 per profiled iteration
 
@@ -196,14 +198,14 @@ struct Scratch {
             cu_share_k = 1;
             HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         }
-        HIPCHK(hipMalloc(&d_state, sizeof(IcpState)));
-        HIPCHK(hipMalloc(&d_acc, sizeof(long long) * kAccReplicas * kAccWords));
-        HIPCHK(hipMalloc(&d_loop, sizeof(LoopShared)));
-        HIPCHK(hipMemset(d_loop, 0, sizeof(LoopShared)));
+        HIPCHK(d_state.reserve(1));
+        HIPCHK(d_acc.reserve(kAccReplicas * kAccWords));
+        HIPCHK(d_loop.reserve(1));
+        HIPCHK(hipMemset(d_loop.data(), 0, sizeof(LoopShared)));
 
-        HIPCHK(hipHostMalloc(&h_state, sizeof(IcpState), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(&h_prog, sizeof(IcpProgress), hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&d_prog), h_prog, 0));
+        HIPCHK(h_state.reserve(1));
+        HIPCHK(h_prog.reserve(1));
+        HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&d_prog), h_prog.data(), 0));
         return SAGEICP_OK;
     }
     int loop_streams() {
@@ -225,68 +227,36 @@ struct Scratch {
         return SAGEICP_OK;
     }
     int reserve_frame(size_t n) {
-        if (n <= frame_cap) return SAGEICP_OK;
-        if (d_frame) HIPCHK(hipFree(d_frame));
-        d_frame = nullptr; frame_cap = 0;
-        const size_t cap = n + n / 4 + 1024;
-        HIPCHK(hipMalloc(&d_frame, cap * sizeof(Point4)));
-        frame_cap = cap;
+        if (n > d_frame.capacity()) HIPCHK(d_frame.reserve(n + n / 4 + 1024));
         return SAGEICP_OK;
     }
     int reserve_tgt(size_t n) {
-        if (n <= tgt_cap) return SAGEICP_OK;
-        if (d_tgt) HIPCHK(hipFree(d_tgt));
-        d_tgt = nullptr; tgt_cap = 0;
-        const size_t cap = n + n / 4 + 1024;
-        HIPCHK(hipMalloc(&d_tgt, cap * sizeof(Point4)));
-        tgt_cap = cap;
+        if (n > d_tgt.capacity()) HIPCHK(d_tgt.reserve(n + n / 4 + 1024));
         return SAGEICP_OK;
     }
     int reserve_nn(size_t n) {
-        if (n <= nn_cap) return SAGEICP_OK;
-        if (d_nn) HIPCHK(hipFree(d_nn));
-        d_nn = nullptr; nn_cap = 0;
-        const size_t cap = n + n / 4 + 1024;
-        HIPCHK(hipMalloc(&d_nn, cap * sizeof(int32_t)));
-        nn_cap = cap;
+        if (n > d_nn.capacity()) HIPCHK(d_nn.reserve(n + n / 4 + 1024));
         return SAGEICP_OK;
     }
     int reserve_sort(size_t n) {
         if (n <= sort_cap) return SAGEICP_OK;
-        if (d_sorted) HIPCHK(hipFree(d_sorted));
-        if (d_keys) HIPCHK(hipFree(d_keys));
-        if (d_vals) HIPCHK(hipFree(d_vals));
-        if (d_sort_temp) HIPCHK(hipFree(d_sort_temp));
-        if (d_rows) HIPCHK(hipFree(d_rows));
-        if (d_prev) HIPCHK(hipFree(d_prev));
-        d_rows = nullptr; d_prev = nullptr;
-        d_sorted = nullptr; d_keys = d_vals = nullptr; d_sort_temp = nullptr; sort_cap = 0;
+        sort_cap = 0;
         const size_t cap = n + n / 4 + 1024;
-        HIPCHK(hipMalloc(&d_sorted, cap * sizeof(Point4)));
-        HIPCHK(hipMalloc(&d_rows, cap * kRowWords * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&d_prev, cap * sizeof(uint2)));
+        HIPCHK(d_sorted.reserve(cap));
+        HIPCHK(d_rows.reserve(cap * kRowWords));
+        HIPCHK(d_prev.reserve(cap));
 #ifdef SAGE_NN_TIMING
-        if (d_work) HIPCHK(hipFree(d_work));
-        d_work = nullptr;
-        HIPCHK(hipMalloc(&d_work, cap * sizeof(uint32_t)));
+        HIPCHK(d_work.reserve(cap));
 #endif
-        if (d_cand) HIPCHK(hipFree(d_cand));
-        d_cand = nullptr;
-        HIPCHK(hipMalloc(&d_cand, 2 * cap * sizeof(unsigned long long)));
-        HIPCHK(hipMalloc(&d_keys, 2 * cap * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&d_vals, 2 * cap * sizeof(uint32_t)));
-        sort_temp_bytes_ = sort_temp_bytes(static_cast<int>(cap));
-        HIPCHK(hipMalloc(&d_sort_temp, sort_temp_bytes_));
+        HIPCHK(d_cand.reserve(2 * cap));
+        HIPCHK(d_keys.reserve(2 * cap));
+        HIPCHK(d_vals.reserve(2 * cap));
+        HIPCHK(d_sort_temp.reserve(sort_temp_bytes(static_cast<int>(cap))));
         sort_cap = cap;
         return SAGEICP_OK;
     }
     int reserve_partials(size_t blocks) {
-        if (blocks <= partials_cap) return SAGEICP_OK;
-        if (d_partials) HIPCHK(hipFree(d_partials));
-        d_partials = nullptr; partials_cap = 0;
-        const size_t cap = blocks + blocks / 4 + 256;
-        HIPCHK(hipMalloc(&d_partials, cap * kNumSums * sizeof(double)));
-        partials_cap = cap;
+        if (blocks > d_partials.capacity() / kNumSums) HIPCHK(d_partials.reserve((blocks + blocks / 4 + 256) * kNumSums));
         return SAGEICP_OK;
     }
     int reserve_events(size_t iterations) {
@@ -306,25 +276,9 @@ struct Scratch {
         if (stream2) (void)hipStreamDestroy(stream2);
         for (auto &e : events) (void)hipEventDestroy(e);
         events.clear();
-        if (d_frame) (void)hipFree(d_frame);
-        if (d_tgt) (void)hipFree(d_tgt);
-        if (d_nn) (void)hipFree(d_nn);
-        if (d_sorted) (void)hipFree(d_sorted);
-        if (d_keys) (void)hipFree(d_keys);
-        if (d_vals) (void)hipFree(d_vals);
-        if (d_sort_temp) (void)hipFree(d_sort_temp);
-        if (d_rows) (void)hipFree(d_rows);
-        if (d_prev) (void)hipFree(d_prev);
-        if (d_work) (void)hipFree(d_work);
-        if (d_partials) (void)hipFree(d_partials);
-        if (d_state) (void)hipFree(d_state);
-        if (d_acc) (void)hipFree(d_acc);
-        if (d_loop) (void)hipFree(d_loop);
-        if (d_cand) (void)hipFree(d_cand);
-        if (h_state) (void)hipHostFree(h_state);
-        if (h_prog) (void)hipHostFree(h_prog);
-        (void)hipStreamDestroy(stream);
-        *this = Scratch();
+        const hipStream_t s = stream;
+        *this = Scratch();              // (releases the buffers: nothing runs on the streams any more)
+        (void)hipStreamDestroy(s);
     }
 };
 
@@ -429,23 +383,22 @@ struct DynFilterConfig {
 // buffers of one Prep; run() filters a frame already on the device (n points at `in`) into `out` (may be `in`),
 // passing the cropped points through `tmp` (n points)
 struct DynFilter {
-    size_t cap = 0, labels_cap = 0, temp_bytes = 0;
-    uint32_t *d_labels = nullptr, *d_ctr = nullptr, *h_ctr = nullptr;   // h_ctr pinned: [0..3] counters, [4] flags
-    unsigned long long *d_cnt = nullptr, *d_pos = nullptr, *d_vkey = nullptr, *d_lkey = nullptr, *d_count = nullptr;
-    float4 *d_vp = nullptr, *d_vs = nullptr, *d_lp = nullptr, *d_ls = nullptr;
-    uint32_t *d_vval = nullptr, *d_lval = nullptr, *d_vframe = nullptr, *d_parent = nullptr, *d_root = nullptr,
-             *d_size = nullptr, *d_rec_of_root = nullptr, *d_start = nullptr, *d_rkv = nullptr, *d_off = nullptr;
-    uint4 *d_rec = nullptr;
-    void *d_temp = nullptr;
-    void *h_rec = nullptr;                     // pinned: the component table
-    uint32_t *h_off = nullptr;                 // pinned: output offset per component (~0: dropped)
+    size_t cap = 0;                            // points the buffers of reserve() hold (all of them: 0 after a failed reserve)
+    DevBuf<uint32_t> d_labels, d_ctr;
+    PinnedBuf<uint32_t> h_ctr;                 // [0..3] counters, [4] flags
+    DevBuf<unsigned long long> d_cnt, d_pos, d_vkey, d_lkey, d_count;
+    DevBuf<float4> d_vp, d_vs, d_lp, d_ls;
+    DevBuf<uint32_t> d_vval, d_lval, d_vframe, d_parent, d_root, d_size, d_rec_of_root, d_start, d_rkv, d_off;
+    DevBuf<uint4> d_rec;
+    DevBuf<unsigned char> d_temp;
+    PinnedBuf<uint4> h_rec;                    // the component table
+    PinnedBuf<uint32_t> h_off;                 // output offset per component (~0: dropped)
     hipEvent_t ev[6] = {};                     // device time of the three launch batches (sageicp_set_profiling)
     hipEvent_t ev_table = nullptr;
     std::vector<uint32_t> order_scratch, size_scratch;
     sageicp_dynfilter_info info{};             // of the last run
 
     int reserve(size_t n, size_t nlabels);
-    void free_points();
     void destroy();
     int run(const Point4 *in, uint64_t n, double max_range, double min_range, double label_max_range,
             const DynFilterConfig &cfg, Point4 *tmp, Point4 *out, int *d_ovf, uint64_t &n_out, hipStream_t s);
@@ -461,17 +414,15 @@ struct DeskewArgs {
 struct Prep {
     int device = -1;
     hipStream_t stream = nullptr;
-    size_t cap = 0;                     // points
-    Point4 *d_in = nullptr, *d_tmp = nullptr, *d_fd = nullptr, *d_src = nullptr;
-    uint32_t *d_slot = nullptr, *d_skey = nullptr, *d_sval = nullptr, *d_winner = nullptr;
-    unsigned long long *d_keys = nullptr;
-    uint32_t table_cap = 0;
-    void *d_sort_temp = nullptr;
-    size_t sort_bytes = 0;
-    unsigned long long *d_okeys = nullptr;   // survivors' voxel keys (reference-order emission)
-    uint32_t *d_perm = nullptr;
-    unsigned long long *h_keys = nullptr;    // pinned
-    uint32_t *h_perm = nullptr;              // pinned
+    size_t cap = 0;                     // points the buffers of reserve() hold (all of them: 0 after a failed reserve)
+    DevBuf<Point4> d_in, d_tmp, d_fd, d_src;
+    DevBuf<uint32_t> d_slot, d_skey, d_sval, d_winner;
+    DevBuf<unsigned long long> d_keys;
+    DevBuf<unsigned char> d_sort_temp;
+    DevBuf<unsigned long long> d_okeys;      // survivors' voxel keys (reference-order emission)
+    DevBuf<uint32_t> d_perm;
+    PinnedBuf<unsigned long long> h_keys;
+    PinnedBuf<uint32_t> h_perm;
     std::vector<uint32_t> h_hash;
     RobinScratch rscratch[8];                // bucket arrays of the order replay, one pair per label group
     std::unique_ptr<ReplayPool> pool;        // parked helper threads of the order replays
@@ -480,18 +431,16 @@ struct Prep {
     // pipeline's second level — its cloud is only registered, and registration sorts its frame
     // spatially first, so its emission order reaches nothing but the order of fp64 summation
     unsigned arrival_order_levels = 0;
-    uint32_t *d_nkept = nullptr;        // [2]
-    int *d_overflow = nullptr;
-    int *d_gcounts = nullptr, *d_glabels = nullptr;
-    size_t glabels_cap = 0;
-    void *h_pin = nullptr;              // pinned staging for the raw frame and the results
-    size_t pin_bytes = 0;
+    DevBuf<uint32_t> d_nkept;           // [2]
+    DevBuf<int> d_overflow;
+    DevBuf<int> d_gcounts, d_glabels;
+    PinnedBuf<Point4> h_pin;            // staging for the raw frame and the results
     uint32_t kept_levels[2] = {0, 0};   // points the last run left in d_fd / d_src
     DynFilter dyn;                      // the dynamic vehicle filter's buffers (allocated with its first use)
     bool dyn_ran = false;               // the last run filtered (dyn.info describes its frame)
     // the timestamps of a frame that is deskewed (allocated with the first such frame): pinned staging, device copy
-    double *h_ts = nullptr, *d_ts = nullptr;
-    size_t ts_cap = 0;
+    PinnedBuf<double> h_ts;
+    DevBuf<double> d_ts;
 
     int init(int dev) {
         if (stream) return SAGEICP_OK;
@@ -502,98 +451,53 @@ struct Prep {
         device = dev;
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        HIPCHK(hipMalloc(&d_nkept, 2 * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&d_overflow, sizeof(int)));
-        HIPCHK(hipMalloc(&d_gcounts, 8 * sizeof(int)));
+        HIPCHK(d_nkept.reserve(2));
+        HIPCHK(d_overflow.reserve(1));
+        HIPCHK(d_gcounts.reserve(8));
         return SAGEICP_OK;
     }
     int reserve(size_t n, size_t nlabels) {
-        if (nlabels > glabels_cap) {
-            if (d_glabels) HIPCHK(hipFree(d_glabels));
-            d_glabels = nullptr;
-            HIPCHK(hipMalloc(&d_glabels, (nlabels + 16) * sizeof(int)));
-            glabels_cap = nlabels + 16;
-        }
+        if (nlabels > d_glabels.capacity()) HIPCHK(d_glabels.reserve(nlabels + 16));
         if (n <= cap) return SAGEICP_OK;
-        free_points();
+        cap = 0;
         const size_t c = n + n / 4 + 1024;
         uint32_t t = 1024;
         while (t < 2 * c) t <<= 1;
-        HIPCHK(hipMalloc(&d_in, c * sizeof(Point4)));
-        HIPCHK(hipMalloc(&d_tmp, c * sizeof(Point4)));
-        HIPCHK(hipMalloc(&d_fd, c * sizeof(Point4)));
-        HIPCHK(hipMalloc(&d_src, c * sizeof(Point4)));
-        HIPCHK(hipMalloc(&d_slot, c * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&d_skey, 2 * c * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&d_sval, 2 * c * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&d_keys, static_cast<size_t>(t) * sizeof(unsigned long long)));
-        HIPCHK(hipMalloc(&d_winner, static_cast<size_t>(t) * sizeof(uint32_t)));
-        HIPCHK(hipMalloc(&d_okeys, c * sizeof(unsigned long long)));
-        HIPCHK(hipMalloc(&d_perm, c * sizeof(uint32_t)));
-        if (h_keys) (void)hipHostFree(h_keys);
-        if (h_perm) (void)hipHostFree(h_perm);
-        h_keys = nullptr; h_perm = nullptr;
-        HIPCHK(hipHostMalloc(&h_keys, c * sizeof(unsigned long long), hipHostMallocDefault));
-        HIPCHK(hipHostMalloc(&h_perm, c * sizeof(uint32_t), hipHostMallocDefault));
-        table_cap = t;
-        sort_bytes = vds_sort_temp_bytes(static_cast<int>(c));
-        HIPCHK(hipMalloc(&d_sort_temp, sort_bytes));
-        HIPCHK(hipHostMalloc(&h_pin, 3 * c * sizeof(Point4), hipHostMallocDefault));
-        pin_bytes = 3 * c * sizeof(Point4);
+        HIPCHK(d_in.reserve(c));
+        HIPCHK(d_tmp.reserve(c));
+        HIPCHK(d_fd.reserve(c));
+        HIPCHK(d_src.reserve(c));
+        HIPCHK(d_slot.reserve(c));
+        HIPCHK(d_skey.reserve(2 * c));
+        HIPCHK(d_sval.reserve(2 * c));
+        HIPCHK(d_keys.reserve(t));
+        HIPCHK(d_winner.reserve(t));
+        HIPCHK(d_okeys.reserve(c));
+        HIPCHK(d_perm.reserve(c));
+        HIPCHK(h_keys.reserve(c));
+        HIPCHK(h_perm.reserve(c));
+        HIPCHK(d_sort_temp.reserve(vds_sort_temp_bytes(static_cast<int>(c))));
+        HIPCHK(h_pin.reserve(3 * c));
         cap = c;
         return SAGEICP_OK;
     }
+    // (the staging copy goes first and comes back last: after a failed reserve it is empty)
     int reserve_timestamps(size_t n) {
-        if (n <= ts_cap) return SAGEICP_OK;
-        free_timestamps();
+        if (n <= h_ts.capacity()) return SAGEICP_OK;
         const size_t c = n + n / 4 + 1024;
-        HIPCHK(hipMalloc(&d_ts, c * sizeof(double)));
-        HIPCHK(hipHostMalloc(&h_ts, c * sizeof(double), hipHostMallocDefault));
-        ts_cap = c;
+        h_ts.reset();
+        HIPCHK(d_ts.reserve(c));
+        HIPCHK(h_ts.reserve(c));
         return SAGEICP_OK;
-    }
-    void free_timestamps() {
-        if (d_ts) (void)hipFree(d_ts);
-        if (h_ts) (void)hipHostFree(h_ts);
-        d_ts = h_ts = nullptr;
-        ts_cap = 0;
-    }
-    void free_points() {
-        if (d_in) (void)hipFree(d_in);
-        if (d_tmp) (void)hipFree(d_tmp);
-        if (d_fd) (void)hipFree(d_fd);
-        if (d_src) (void)hipFree(d_src);
-        if (d_slot) (void)hipFree(d_slot);
-        if (d_skey) (void)hipFree(d_skey);
-        if (d_sval) (void)hipFree(d_sval);
-        if (d_keys) (void)hipFree(d_keys);
-        if (d_winner) (void)hipFree(d_winner);
-        if (d_okeys) (void)hipFree(d_okeys);
-        if (d_perm) (void)hipFree(d_perm);
-        if (h_keys) (void)hipHostFree(h_keys);
-        if (h_perm) (void)hipHostFree(h_perm);
-        h_keys = nullptr; h_perm = nullptr;
-        d_okeys = nullptr; d_perm = nullptr;
-        if (d_sort_temp) (void)hipFree(d_sort_temp);
-        if (h_pin) (void)hipHostFree(h_pin);
-        d_in = d_tmp = d_fd = d_src = nullptr;
-        d_slot = d_skey = d_sval = d_winner = nullptr;
-        d_keys = nullptr; d_sort_temp = nullptr; h_pin = nullptr;
-        cap = 0;
     }
     void destroy() {
         if (!stream) return;
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(stream);
-        free_points();
-        free_timestamps();
         dyn.destroy();
-        if (d_nkept) (void)hipFree(d_nkept);
-        if (d_overflow) (void)hipFree(d_overflow);
-        if (d_gcounts) (void)hipFree(d_gcounts);
-        if (d_glabels) (void)hipFree(d_glabels);
-        (void)hipStreamDestroy(stream);
-        *this = Prep();
+        const hipStream_t s = stream;
+        *this = Prep();                 // (releases the buffers: nothing runs on the stream any more)
+        (void)hipStreamDestroy(s);
     }
 
     // levels: each {do_crop, scale}; a scale <= 0 means "crop only" (no voxel test).  Runs the
@@ -625,23 +529,23 @@ struct Prep {
         out.assign(n_levels, std::vector<double>());
         if (n == 0) return SAGEICP_OK;
         if (n_groups > 0) {
-            HIPCHK(hipMemcpyAsync(d_gcounts, gcounts, n_groups * sizeof(int), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemcpyAsync(d_glabels, glabels, nlabels * sizeof(int), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(d_gcounts.data(), gcounts, n_groups * sizeof(int), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(d_glabels.data(), glabels, nlabels * sizeof(int), hipMemcpyHostToDevice, stream));
         }
-        HIPCHK(hipMemsetAsync(d_overflow, 0, sizeof(int), stream));
-        std::memcpy(h_pin, frame, n * sizeof(Point4));
-        HIPCHK(hipMemcpyAsync(d_in, h_pin, n * sizeof(Point4), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemsetAsync(d_overflow.data(), 0, sizeof(int), stream));
+        std::memcpy(h_pin.data(), frame, n * sizeof(Point4));
+        HIPCHK(hipMemcpyAsync(d_in.data(), h_pin.data(), n * sizeof(Point4), hipMemcpyHostToDevice, stream));
         if (deskew) {
-            std::memcpy(h_ts, deskew->timestamps, n * sizeof(double));
-            HIPCHK(hipMemcpyAsync(d_ts, h_ts, n * sizeof(double), hipMemcpyHostToDevice, stream));
-            launch_deskew(d_in, d_in, d_ts, static_cast<int>(n), deskew->delta, stream);
+            std::memcpy(h_ts.data(), deskew->timestamps, n * sizeof(double));
+            HIPCHK(hipMemcpyAsync(d_ts.data(), h_ts.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
+            launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream);
             HIPCHK(hipGetLastError());
         }
-        const Point4 *in = d_in;
-        Point4 *outs[2] = {d_fd, d_src};
+        const Point4 *in = d_in.data();
+        Point4 *outs[2] = {d_fd.data(), d_src.data()};
         uint64_t cur = n;
         if (dyn_cfg) {      // the filtered cloud replaces the frame in d_in (the filter has read it by then)
-            int r = dyn.run(d_in, n, max_range, min_range, label_max_range, *dyn_cfg, d_tmp, d_in, d_overflow, cur,
+            int r = dyn.run(d_in.data(), n, max_range, min_range, label_max_range, *dyn_cfg, d_tmp.data(), d_in.data(), d_overflow.data(), cur,
                             stream);
             if (r) return r;
         }
@@ -650,25 +554,25 @@ struct Prep {
             P.in = in; P.n = static_cast<int>(cur); P.do_crop = dyn_cfg ? 0 : crop[l];
             P.max_range = max_range; P.min_range = min_range; P.label_max_range = label_max_range;
             P.n_groups = scales[l] > 0.0 ? n_groups : -1;
-            P.group_counts = d_gcounts; P.group_labels = d_glabels;
+            P.group_counts = d_gcounts.data(); P.group_labels = d_glabels.data();
             for (int g = 0; g < n_groups; ++g) P.group_vs[g] = gvs[g];
             P.scale = scales[l];
-            P.keys = d_keys; P.winner = d_winner; P.mask = table_cap - 1;
-            P.tmp = d_tmp; P.slot_of = d_slot; P.sort_key = d_skey; P.sort_val = d_sval;
-            P.overflow = d_overflow;
+            P.keys = d_keys.data(); P.winner = d_winner.data(); P.mask = static_cast<uint32_t>(d_keys.capacity() - 1);
+            P.tmp = d_tmp.data(); P.slot_of = d_slot.data(); P.sort_key = d_skey.data(); P.sort_val = d_sval.data();
+            P.overflow = d_overflow.data();
             const bool reorder = g_reference_order && P.n_groups > 0 && !((arrival_order_levels >> l) & 1u);
-            P.out_keys = reorder ? d_okeys : nullptr;
+            P.out_keys = reorder ? d_okeys.data() : nullptr;
             Point4 *dst = outs[l & 1];
-            HIPCHK(voxel_downsample_device(P, d_sort_temp, sort_bytes, d_nkept + (l & 1), dst, stream));
+            HIPCHK(voxel_downsample_device(P, d_sort_temp.data(), d_sort_temp.capacity(), d_nkept.data() + (l & 1), dst, stream));
             uint32_t kept = 0;
-            HIPCHK(hipMemcpyAsync(&kept, d_nkept + (l & 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(&kept, d_nkept.data() + (l & 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
             HIPCHK(hipStreamSynchronize(stream));
             kept_levels[l & 1] = kept;
             if (reorder && kept) {
                 // the reference's emission order (Preprocessing.cpp:76-82): replay, group by
                 // group, the insertions into its robin_map and permute the survivors
                 const double t0 = now_us();
-                HIPCHK(hipMemcpyAsync(h_keys, d_okeys, kept * sizeof(unsigned long long),
+                HIPCHK(hipMemcpyAsync(h_keys.data(), d_okeys.data(), kept * sizeof(unsigned long long),
                                       hipMemcpyDeviceToHost, stream));
                 HIPCHK(hipStreamSynchronize(stream));
                 const double t1 = now_us();
@@ -678,18 +582,18 @@ struct Prep {
                 // permutation in place
                 std::vector<std::pair<uint32_t, uint32_t>> runs;
                 for (uint32_t a = 0; a < kept;) {
-                    const unsigned long long g = h_keys[a] >> 60;
+                    const unsigned long long g = h_keys.data()[a] >> 60;
                     uint32_t lo = a, hi = kept;            // first index of another group (binary search: the runs are long)
                     while (hi - lo > 1) {
                         const uint32_t mid = lo + (hi - lo) / 2;
-                        if ((h_keys[mid] >> 60) == g) lo = mid; else hi = mid;
+                        if ((h_keys.data()[mid] >> 60) == g) lo = mid; else hi = mid;
                     }
                     runs.emplace_back(a, hi);
                     a = hi;
                 }
                 auto replay = [&](size_t r) {
                     const uint32_t a = runs[r].first, b = runs[r].second;
-                    for (uint32_t i = a; i < b; ++i) h_hash[i] = static_cast<uint32_t>(h_keys[i] & 0xFFFFFu);   // hashed on the device
+                    for (uint32_t i = a; i < b; ++i) h_hash[i] = static_cast<uint32_t>(h_keys.data()[i] & 0xFFFFFu);   // hashed on the device
                     std::vector<uint32_t> part;
                     part.reserve(b - a);
                     if (!RobinOrderReplay::iteration_order(h_hash.data() + a, b - a, a, part, &rscratch[r & 7])) {
@@ -704,7 +608,7 @@ struct Prep {
                         part.resize(b - a);
                         for (uint32_t i = a; i < b; ++i) part[i - a] = i;
                     }
-                    std::memcpy(h_perm + a, part.data(), (b - a) * sizeof(uint32_t));
+                    std::memcpy(h_perm.data() + a, part.data(), (b - a) * sizeof(uint32_t));
                 };
                 // The groups' replays are independent and the largest (half of the survivors on street
                 // scenes) is the critical path: every group gets its own thread — parked helpers of
@@ -724,9 +628,9 @@ struct Prep {
                     for (size_t r = 0; r < runs.size(); ++r) replay(r);
                 }
                 const double t2 = now_us();
-                HIPCHK(hipMemcpyAsync(d_perm, h_perm, kept * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                launch_vds_permute(dst, d_perm, kept, d_tmp, stream);
-                HIPCHK(hipMemcpyAsync(dst, d_tmp, kept * sizeof(Point4), hipMemcpyDeviceToDevice, stream));
+                HIPCHK(hipMemcpyAsync(d_perm.data(), h_perm.data(), kept * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+                launch_vds_permute(dst, d_perm.data(), kept, d_tmp.data(), stream);
+                HIPCHK(hipMemcpyAsync(dst, d_tmp.data(), kept * sizeof(Point4), hipMemcpyDeviceToDevice, stream));
                 us_order += now_us() - t0;
                 if (env_int("SAGEICP_DEBUG_ORDER", 0)) {
                     std::string rs;
@@ -736,7 +640,7 @@ struct Prep {
                 }
             }
             if (download) {       // otherwise the level's cloud stays in d_fd / d_src for the caller
-                char *hp = static_cast<char *>(h_pin) + static_cast<size_t>(1 + (l & 1)) * cap * sizeof(Point4);
+                Point4 *hp = h_pin.data() + static_cast<size_t>(1 + (l & 1)) * cap;
                 if (kept) HIPCHK(hipMemcpyAsync(hp, dst, kept * sizeof(Point4), hipMemcpyDeviceToHost, stream));
                 HIPCHK(hipStreamSynchronize(stream));
                 out[l].resize(4 * static_cast<size_t>(kept));
@@ -746,7 +650,7 @@ struct Prep {
             cur = kept;
         }
         int ovf = 0;
-        HIPCHK(hipMemcpy(&ovf, d_overflow, sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&ovf, d_overflow.data(), sizeof(int), hipMemcpyDeviceToHost));
         if (ovf & 2) return fail(SAGEICP_ERR_INVALID, "a label (or, without the range crop, a coordinate) is not finite (NaN / Inf)");
         if (ovf) return fail(SAGEICP_ERR_CAPACITY, "voxel index beyond +-2^19 in VoxelDownsample");
         return SAGEICP_OK;
@@ -763,62 +667,78 @@ struct sageicp_map {
     int device = 0;
     // device mirror + scratch: logically a cache of `host`, refreshed lazily by const searches
     mutable Scratch sc;
-    mutable Slot *d_table = nullptr;
-    mutable size_t d_table_cap = 0;      // slots
-    mutable Point4 *d_pts = nullptr;
-    mutable size_t d_units_cap = 0;      // units (4 points) the point array holds
-    mutable size_t d_blocks_cap = 0;     // blocks the per-block arrays (d_regions, and the update's aux arrays) hold
-    mutable uint32_t *d_regions = nullptr;              // per block: (class << 28) | first unit of its region
-    mutable size_t d_regions_cap = 0;
-    mutable uint32_t *d_free_units[kMaxClasses] = {};   // device-side update: per-class stacks of free regions
-    mutable size_t d_free_units_cap[kMaxClasses] = {};
-    mutable uint32_t *d_freed = nullptr;                // regions released by one insertion pass
-    mutable size_t d_freed_cap = 0;
-    mutable uint32_t *d_block_of = nullptr;             // device-side update: unit -> block (slot words carry units)
-    mutable size_t d_block_of_cap = 0;
+    mutable DevBuf<Slot> d_table;
+    mutable DevBuf<Point4> d_pts;                // units of 4 points, + one NaN point after them (reserve_device_points)
+    mutable DevBuf<uint32_t> d_regions;          // per block: (class << 28) | first unit of its region
+    mutable DevBuf<uint32_t> d_free_units[kMaxClasses];   // device-side update: per-class stacks of free regions
+    mutable DevBuf<uint32_t> d_freed;            // regions released by one insertion pass
+    mutable DevBuf<uint32_t> d_block_of;         // device-side update: unit -> block (slot words carry units)
     mutable bool mirror_stale_all = true;
     // compact copy of d_pts for k_icp's scan (fp32 x, y, z, label), derived on the device whenever
-    // the HBM copy of the map has changed since the last search
-    mutable uint4 *d_cand = nullptr;
-    mutable size_t d_cand_slots = 0;     // point slots it holds
-    mutable uint32_t *d_cand_flags = nullptr;
+    // the HBM copy of the map has changed since the last search: a record per point slot, one more, and
+    // kCandSlack records nothing reads (k_icp loads a record's neighbour at a constant offset that the
+    // buffer load's range check does not cover)
+    static constexpr size_t kCandSlack = 64;
+    mutable DevBuf<uint4> d_cand;
+    mutable DevBuf<uint32_t> d_cand_flags;
     mutable bool cand_stale = true;
     // pinned staging + device landing buffers for the scattered refresh of changed records
-    mutable void *h_stage = nullptr;
-    mutable void *d_stage = nullptr;
-    mutable size_t stage_bytes = 0;
+    mutable PinnedBuf<char> h_stage;
+    mutable DevBuf<char> d_stage;
+    mutable size_t stage_bytes = 0;              // what both hold (0 after a failed reserve)
     // Device-side Update() (map_update.hip).  After one the HBM copy is the authority
     // (`on_device`) and `host` is stale until ensure_host() downloads it; `ctr` is the host's
     // shadow of the device counters.  The auxiliary arrays are valid for the host generation
     // they were uploaded at.
     mutable bool on_device = false;
-    mutable uint8_t *d_zeros = nullptr;
-    mutable uint32_t *d_slot_of = nullptr;
-    mutable uint32_t *d_free = nullptr;
-    mutable MapCounters *d_ctr = nullptr;
-    mutable MapCounters *h_ctr = nullptr;       // pinned
-    mutable uint32_t *h_ctr_aux = nullptr;      // pinned, 16 words: what else a device update hands back (far voxels found)
+    // the update's per-block arrays: as many blocks as d_zeros holds (d_regions holds at least as many)
+    mutable DevBuf<uint8_t> d_zeros;
+    mutable DevBuf<uint32_t> d_slot_of;
+    mutable DevBuf<uint32_t> d_free;
+    mutable DevBuf<MapCounters> d_ctr;
+    mutable PinnedBuf<MapCounters> h_ctr;
+    mutable PinnedBuf<uint32_t> h_ctr_aux;       // 16 words: what else a device update hands back (far voxels found)
     // reference-order maps: the lists a device update exchanges with the host's bucket array (pinned)
-    mutable uint2 *h_lists = nullptr;
-    mutable size_t h_lists_cap = 0;
+    mutable PinnedBuf<uint2> h_lists;
     int reserve_lists(size_t n) const {
-        if (n + 2 <= h_lists_cap) return SAGEICP_OK;
-        if (h_lists) HIPCHK(hipHostFree(h_lists));
-        h_lists = nullptr; h_lists_cap = 0;
-        const size_t c = n + n / 2 + 4096;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&h_lists), c * sizeof(uint2), hipHostMallocDefault));
-        h_lists_cap = c;
+        if (n + 2 > h_lists.capacity()) HIPCHK(h_lists.reserve(n + n / 2 + 4096));
         return SAGEICP_OK;
     }
-    mutable size_t d_aux_cap = 0;               // blocks the auxiliary arrays hold
     mutable bool aux_valid = false;
     mutable uint64_t aux_generation = 0;
     mutable MapCounters ctr{};
-    mutable UpdateScratch up{};
-    mutable size_t up_n = 0, up_nb = 0;
+    // the update's scratch (reserve_update_scratch); map_update.hip gets the view
+    struct UpdateBuffers {
+        DevBuf<Point4> raw, w;
+        DevBuf<unsigned long long> keys, keys_alt;
+        DevBuf<uint32_t> idx, idx_alt, head_slot;
+        DevBuf<UpdateEvents> flag, rank;
+        DevBuf<int8_t> want;
+        DevBuf<uint2> new_list;
+        size_t n = 0;                            // points the buffers above hold (0 after a failed reserve)
+        DevBuf<uint32_t> far_flag, far_sel;
+        DevBuf<uint2> far_list;
+        size_t nb = 0;                           // blocks the three above hold (0 after a failed reserve)
+        DevBuf<uint32_t> n_sel;
+        DevBuf<unsigned char> temp;
+        UpdateScratch view() const {
+            UpdateScratch v{};
+            v.raw = raw.data(); v.w = w.data();
+            v.keys = keys.data(); v.keys_alt = keys_alt.data();
+            v.idx = idx.data(); v.idx_alt = idx_alt.data(); v.head_slot = head_slot.data();
+            v.flag = flag.data(); v.rank = rank.data(); v.want = want.data();
+            v.far_flag = far_flag.data(); v.far_sel = far_sel.data(); v.n_sel = n_sel.data();
+            v.new_list = new_list.data(); v.far_list = far_list.data();
+            v.temp = temp.data(); v.temp_bytes = temp.capacity();
+            return v;
+        }
+    };
+    mutable UpdateBuffers up;
     // Pointcloud() served from the HBM copy: the packed points before they cross PCIe
-    mutable Point4 *d_pc = nullptr;
-    mutable size_t d_pc_cap = 0;
+    mutable DevBuf<Point4> d_pc;
+    size_t units_cap() const { return d_pts.capacity() / kUnitPoints; }       // units the point array holds
+    size_t blocks_cap() const { return d_zeros.capacity(); }
+    size_t cand_slots() const { return d_cand.capacity() ? d_cand.capacity() - 1 - kCandSlack : 0; }
     // Single-process multi-GPU mode (SAGEICP_DEVICES / sageicp_map_set_devices): one more complete
     // copy of the map per extra device.  Every mutation is applied to all of them, RegisterFrame
     // shards the frame over them (one host thread and one stream per device) and the ranks'
@@ -833,7 +753,7 @@ struct sageicp_map {
 
 struct sageicp_frame {
     int device = 0;
-    Point4 *d = nullptr;
+    DevBuf<Point4> d;
     uint64_t n = 0;
 };
 
@@ -846,7 +766,7 @@ struct sageicp_comm {
                                          // differ, so the blocks must not be used again
     P2pBlock *my_block = nullptr;        // fine-grained device memory, exported through HIP IPC
     P2pBlock *blocks[kMaxRanks] = {};    // every rank's block as mapped here (blocks[rank] == my_block)
-    unsigned long long *d_exchanges = nullptr;
+    DevBuf<unsigned long long> d_exchanges;
     bool peer_mapped = false;            // blocks[] are plain peer pointers of this process (no IPC handles to close)
     bool device_shared = false;          // several ranks of ONE process run on this device (tests on a 1-GPU box): their
                                          // streams share the process's few hardware queues, where a solving wave that

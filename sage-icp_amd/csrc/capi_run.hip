@@ -103,20 +103,20 @@ IcpParams icp_params(const sageicp_map *m, const Point4 *d_queries, uint64_t n, 
     IcpParams ip{};
     ip.frame = d_queries;
     ip.n = static_cast<int>(n);
-    ip.st = sc.d_state;
+    ip.st = sc.d_state.data();
     ip.check_done = 0;
     ip.apply_pose = 0;
     ip.voxel_size = m->host.voxel_size;
     ip.inv_voxel_size = env_int("SAGEICP_EXACT_DIVIDE", 0) ? 0.0 : 1.0 / m->host.voxel_size;
-    ip.rows = sc.d_rows;
-    ip.table = m->d_table;
-    ip.mask = static_cast<uint32_t>(m->d_table_cap - 1);
-    ip.pts = m->d_pts;
-    const uint64_t pts_bytes = (static_cast<uint64_t>(m->d_units_cap) * kUnitPoints + 1) * sizeof(Point4);
+    ip.rows = sc.d_rows.data();
+    ip.table = m->d_table.data();
+    ip.mask = static_cast<uint32_t>(m->d_table.capacity() - 1);
+    ip.pts = m->d_pts.data();
+    const uint64_t pts_bytes = (static_cast<uint64_t>(m->units_cap()) * kUnitPoints + 1) * sizeof(Point4);
     ip.pts_bytes = static_cast<uint32_t>(pts_bytes);        // (< 4 GiB: kMaxUnits units of 128 B)
-    ip.cand = m->d_cand;
-    ip.cand_bytes = m->d_cand_slots >= m->d_units_cap * kUnitPoints ? static_cast<uint32_t>(pts_bytes / 2) : 0u;
-    ip.cand_flags = m->d_cand_flags;
+    ip.cand = m->d_cand.data();
+    ip.cand_bytes = m->cand_slots() >= m->units_cap() * kUnitPoints ? static_cast<uint32_t>(pts_bytes / 2) : 0u;
+    ip.cand_flags = m->d_cand_flags.data();
     // fp32 thresholds of the scan's filter (kernels.hip): off (infinite) for a negative or NaN
     // sem_th, where a larger distance can scale to a smaller one
     {
@@ -136,11 +136,11 @@ IcpParams icp_params(const sageicp_map *m, const Point4 *d_queries, uint64_t n, 
     const bool prune = sem_th >= 0.0 && env_int("SAGEICP_NO_PRUNE", 0) == 0;
     ip.prune_scale = prune ? std::min(sem_th, 1.0) * (1.0 - 1e-9) : 0.0;
     ip.keep_all = prune ? 0u : 0x7FFFFFFu;
-    ip.nn_idx = sc.d_nn;
+    ip.nn_idx = sc.d_nn.data();
     ip.kernel = 0.0;
     ip.accept_r2 = -1.0;
-    ip.nn_prev = sc.d_prev;
-    ip.work = sc.d_work;
+    ip.nn_prev = sc.d_prev.data();
+    ip.work = sc.d_work.data();
     ip.acc_scale = std::ldexp(1.0, -24 * std::max(g_acc_shift, std::min(2, std::max(0, env_int("SAGEICP_ACC_SHIFT", 0)))));
     {
         // k_fin adds the accumulator copies in 64-bit integers: blocks x limit < 2^62 (kernels.hip, kDigitLimitCounted)
@@ -329,12 +329,12 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
     // (probes only: SAGEICP_MAX_ITER stops either loop early — the launch-per-iteration loop then simply runs out of launches)
     const int max_it = std::min(kMaxIterations, std::max(1, env_int("SAGEICP_MAX_ITER", kMaxIterations)));
 
-    fill_state(sc.h_state, init);
+    fill_state(sc.h_state.data(), init);
     if (polled) {
-        std::memset(sc.h_prog, 0, sizeof(IcpProgress));
-        sc.h_state->progress = sc.d_prog;
+        std::memset(sc.h_prog.data(), 0, sizeof(IcpProgress));
+        sc.h_state.data()->progress = sc.d_prog;
     }
-    HIPCHK(hipMemcpyAsync(sc.d_state, sc.h_state, sizeof(IcpState), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
 
     // Lanes per query are decided in ONE place, whichever loop then runs: a frame that fits the one-launch
     // loop takes that loop's choice also when the launch-per-iteration loop registers it (a launch that timed
@@ -358,7 +358,7 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
     const unsigned loop_waves = use_loop ? static_cast<unsigned>((n + (64u >> plan.lw) - 1) / (64u >> plan.lw)) : 0u;
     if ((rc = ensure_cand(m, wants_filter(m, n, sem_th)))) return rc;
     if ((rc = sc.reserve_sort(n))) return rc;
-    IcpParams ip = icp_params(m, sc.d_sorted, n, sem_th, lw);
+    IcpParams ip = icp_params(m, sc.d_sorted.data(), n, sem_th, lw);
     ip.check_done = 1;
     ip.apply_pose = 1;
     ip.kernel = kernel;
@@ -366,8 +366,8 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
     // (the counters behind sum_candidates / pairs_evaluated cost ~45 vector instructions per pass, a memset and a
     // launch per frame: a caller that wants the other statistics only — bench.py's timed region — switches them off)
     const bool counting = stats && g_counting != 0;
-    ip.counters = counting ? sc.d_cand : nullptr;
-    if (counting) HIPCHK(hipMemsetAsync(sc.d_cand, 0, sizeof(unsigned long long) * 2 * (std::max(ip.nwaves, loop_waves) + 1), s));
+    ip.counters = counting ? sc.d_cand.data() : nullptr;
+    if (counting) HIPCHK(hipMemsetAsync(sc.d_cand.data(), 0, sizeof(unsigned long long) * 2 * (std::max(ip.nwaves, loop_waves) + 1), s));
 
     // direct exchange of the sums with the peer GPUs (k_fin mode 3, or the solving wave of the one-launch loop)
     P2pParams xp{};
@@ -376,7 +376,7 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
         xp.nranks = comm->nranks;
         xp.rank = comm->rank;
         for (int r = 0; r < comm->nranks; ++r) xp.block[r] = comm->blocks[r];
-        xp.exchanges = comm->d_exchanges;
+        xp.exchanges = comm->d_exchanges.data();
         // a peer's sums normally arrive within microseconds, but its FIRST launches of a process (code
         // object loading) or a GPU shared with other work can take a second: five seconds of in-kernel
         // waiting is a failure (SAGEICP_P2P_TIMEOUT_S overrides, e.g. under a debugger)
@@ -395,7 +395,7 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
         ~SolverGuard() {
             if (!sc) return;
             const unsigned long long word = epoch | 0x8000000000000000ull;
-            (void)hipMemcpyAsync(&sc->d_loop->go[0], &word, sizeof(word), hipMemcpyHostToDevice, sc->stream);
+            (void)hipMemcpyAsync(&sc->d_loop.data()->go[0], &word, sizeof(word), hipMemcpyHostToDevice, sc->stream);
             (void)hipStreamSynchronize(sc->stream);
             (void)hipStreamSynchronize(sc->stream2);
         }
@@ -415,8 +415,8 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
                        chain_grid / kChainReplicas <= 255 && !g_no_chain && !prof2 && env_int("SAGEICP_CHAIN", 1) != 0;
     if ((use_loop || chain) && (rc = sc.loop_streams())) return rc;
     if (chain) {
-        L.sh = sc.d_loop;
-        L.st = sc.d_state;
+        L.sh = sc.d_loop.data();
+        L.st = sc.d_state.data();
         L.wgs = chain_grid;                       // every workgroup of a launch sends its sums, also the ones past the frame's end
         L.copies = kChainReplicas;
         L.progress = sc.d_prog;
@@ -448,8 +448,8 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
     if (use_loop) {
         // ---- the whole loop in one launch (kernels.hip, k_loop): first its solving wave, on its own stream —
         // it has to hold its registers before the grid fills the machine; it waits for the grid's go
-        L.sh = sc.d_loop;
-        L.st = sc.d_state;
+        L.sh = sc.d_loop.data();
+        L.st = sc.d_state.data();
         L.nw = plan.nw;
         L.gpw = plan.gpw;
         L.wgs = plan.wgs;
@@ -502,11 +502,11 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
     // c2 cold start, profiles/README.md.)
     // ... from kSortFrameFrom points on (kernels.h); SAGEICP_SORT_FROM overrides the size (0: always sorted)
     if (n > 0 && n < static_cast<uint64_t>(std::max(0, env_int("SAGEICP_SORT_FROM", kSortFrameFrom))))
-        HIPCHK(check_copy_frame(d_frame, sc.d_sorted, static_cast<int>(n), sc.d_state, comm == nullptr, s));
+        HIPCHK(check_copy_frame(d_frame, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), comm == nullptr, s));
     else if (n > 0)
-        HIPCHK(sort_frame(d_frame, sc.d_sorted, static_cast<int>(n), sc.d_state, true, comm == nullptr,
-                          m->host.voxel_size, sc.d_keys, sc.d_vals, sc.d_sort_temp,
-                          sc.sort_temp_bytes_, s));
+        HIPCHK(sort_frame(d_frame, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), true, comm == nullptr,
+                          m->host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(),
+                          sc.d_sort_temp.capacity(), s));
 
     double us_nn = 0, us_fin = 0;
     uint32_t nn_launches = 0;
@@ -517,7 +517,7 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
         IcpParams lp = ip;
         lp.filter = plan.filter ? ip.filter : 0;
         lp.nwaves = loop_waves;
-        HIPCHK(hipMemsetAsync(sc.d_loop, 0, offsetof(LoopShared, acc32), s));      // (the chained launches' copies are not this loop's)
+        HIPCHK(hipMemsetAsync(sc.d_loop.data(), 0, offsetof(LoopShared, acc32), s));      // (the chained launches' copies are not this loop's)
         if (prof) HIPCHK(hipEventRecord(sc.events[1], s));
         launch_loop(lp, L, plan.lw, s);
         if (hipPeekAtLastError() == hipSuccess) solver_guard.sc = nullptr;      // the grid is on its way: it will say go
@@ -525,19 +525,19 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
 #ifndef SAGE_LOOP_INGRID
         HIPCHK(hipStreamWaitEvent(s, sc.ev_solve, 0));             // the solving wave writes the final state
 #endif
-        if (counting) launch_sum_counters(sc.d_cand, static_cast<int>(lp.nwaves), sc.d_state, s);
+        if (counting) launch_sum_counters(sc.d_cand.data(), static_cast<int>(lp.nwaves), sc.d_state.data(), s);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(sc.h_state, sc.d_state, sizeof(IcpState), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (sc.h_state->bad_input && !comm) {
+        if (sc.h_state.data()->bad_input && !comm) {
             looped = true;                     // (reported below)
-        } else if (sc.h_state->exchange_failed) {
+        } else if (sc.h_state.data()->exchange_failed) {
             looped = true;                     // (reported below)
-        } else if (sc.h_state->loop_aborted || !sc.h_state->done) {
+        } else if (sc.h_state.data()->loop_aborted || !sc.h_state.data()->done) {
             // a wait inside the launch timed out (the grid was not resident as a whole: another stream
             // or process held CUs): the launch-per-iteration loop below registers the frame instead,
             // with the same lanes per query
-            if (sc.h_state->peer_aborted) {
+            if (sc.h_state.data()->peer_aborted) {
                 // not this rank's grid: a peer lost its one-launch loop and every rank left the same exchange with it
                 // (sageicp_types.h, P2pBlock::abort_tag) — this frame goes through the other form on every rank, in step; no cool-down here
                 sc.last_fallback = SAGEICP_LOOP_FALLBACK_PEER;
@@ -558,13 +558,13 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
             }
             // (under a communicator the solving wave told the peers through the exchange it was about to make: they left
             // it with this rank, the exchange counts as made on every rank, and all of them register the frame again below)
-            fill_state(sc.h_state, init);
+            fill_state(sc.h_state.data(), init);
             if (polled) {
-                std::memset(sc.h_prog, 0, sizeof(IcpProgress));
-                sc.h_state->progress = sc.d_prog;
+                std::memset(sc.h_prog.data(), 0, sizeof(IcpProgress));
+                sc.h_state.data()->progress = sc.d_prog;
             }
-            HIPCHK(hipMemcpyAsync(sc.d_state, sc.h_state, sizeof(IcpState), hipMemcpyHostToDevice, s));
-            if (counting) HIPCHK(hipMemsetAsync(sc.d_cand, 0, sizeof(unsigned long long) * 2 * (ip.nwaves + 1), s));
+            HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
+            if (counting) HIPCHK(hipMemsetAsync(sc.d_cand.data(), 0, sizeof(unsigned long long) * 2 * (ip.nwaves + 1), s));
             use_loop = false;
         } else {
             looped = true;
@@ -572,30 +572,30 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
                 float a = 0;
                 (void)hipEventElapsedTime(&a, sc.events[1], sc.events[2]);
                 us_nn = 1e3 * a;
-                nn_launches = static_cast<uint32_t>(std::max(1, sc.h_state->iter));   // per iteration
+                nn_launches = static_cast<uint32_t>(std::max(1, sc.h_state.data()->iter));   // per iteration
             }
         }
     }
     if (n > 0 && !looped) {
         launch_rows(ip, s);
-        HIPCHK(hipMemsetAsync(sc.d_prev, 0xFF, n * sizeof(uint2), s));     // no previous answers yet
+        HIPCHK(hipMemsetAsync(sc.d_prev.data(), 0xFF, n * sizeof(uint2), s));     // no previous answers yet
     }
 
     // The workgroups of k_icp add their sums into fixed-point accumulators (kernels.h) that k_fin
     // reads in one round trip.
-    HIPCHK(hipMemsetAsync(sc.d_acc, 0, sizeof(long long) * kAccReplicas * kAccWords, s));
-    ip.acc = sc.d_acc;
+    HIPCHK(hipMemsetAsync(sc.d_acc.data(), 0, sizeof(long long) * kAccReplicas * kAccWords, s));
+    ip.acc = sc.d_acc.data();
     if (chain) {
         // ... or, chained, into the counted accumulators of the shared block the solving wave reads (zeroed first: the
         // solving wave starts on launch 0's go)
-        HIPCHK(hipMemsetAsync(sc.d_loop, 0, sizeof(LoopShared), s));
-        ip.chain = sc.d_loop;
+        HIPCHK(hipMemsetAsync(sc.d_loop.data(), 0, sizeof(LoopShared), s));
+        ip.chain = sc.d_loop.data();
         ip.chain_timeout = L.timeout_ticks;
         ip.chain_epoch = L.epoch;
         ip.digit_limit = std::min(ip.digit_limit, std::ldexp(1.0, 40));       // (counted words: kernels.hip, kDigitLimitCounted)
     }
     FinParams fp{};
-    fp.st = sc.d_state;
+    fp.st = sc.d_state.data();
     fp.partials = nullptr;
     fp.acc = ip.acc;
     fp.acc_unscale = 1.0 / ip.acc_scale;
@@ -614,9 +614,9 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
     // regions stay the heavy regions).  The sort's buffers are the frame sort's, free once the frame is in order.
     const unsigned stripes = (n > 0 && !looped) ? static_cast<unsigned>(icp_stripes_for(static_cast<int>(n), lw)) : 0u;
     // (three small sorts per frame: worth it from ~40k points on — c1 through this loop: +4.5 % with them)
-    const bool lpt = stripes >= 16 && stripes <= sc.sort_cap && stripe_sort_temp_bytes(stripes) <= sc.sort_temp_bytes_ &&
+    const bool lpt = stripes >= 16 && stripes <= sc.sort_cap && stripe_sort_temp_bytes(stripes) <= sc.d_sort_temp.capacity() &&
                      env_int("SAGEICP_LPT", n >= 40000 ? 1 : 0) != 0;
-    uint32_t *st_work = sc.d_keys, *st_sorted = sc.d_keys + stripes, *st_iota = sc.d_vals, *st_order = sc.d_vals + stripes;
+    uint32_t *st_work = sc.d_keys.data(), *st_sorted = sc.d_keys.data() + stripes, *st_iota = sc.d_vals.data(), *st_order = sc.d_vals.data() + stripes;
     if (lpt) stripe_order_init(st_work, st_iota, stripes, s);
     auto measures = [&](int iteration) { return lpt && (iteration == 0 || iteration == 3 || iteration == 15); };
     auto enqueue_iteration = [&](int slot, int iteration) -> int {
@@ -627,14 +627,14 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
         launch_icp(ip, lw, true, s);
         if (chain && iteration == 0 && hipPeekAtLastError() == hipSuccess) solver_guard.sc = nullptr;      // launch 0 will say go
         if (measures(iteration)) {
-            HIPCHK(stripe_order_sort(st_work, st_sorted, st_iota, st_order, stripes, sc.d_sort_temp, sc.sort_temp_bytes_, s));
+            HIPCHK(stripe_order_sort(st_work, st_sorted, st_iota, st_order, stripes, sc.d_sort_temp.data(), sc.d_sort_temp.capacity(), s));
             ip.stripe_order = st_order;
         }
         if (ev) HIPCHK(hipEventRecord(sc.events[5 * slot + 2], s));
         if (chain) return SAGEICP_OK;                  // (the solving wave is already waiting for this launch's sums)
         launch_fin(fp, s);
         if (comm && !p2p) {     // k_fin left the local sums in state->sums
-            ncclResult_t r = g_rccl.AllReduce(sc.d_state->sums, sc.d_state->sums, kNumSums,
+            ncclResult_t r = g_rccl.AllReduce(sc.d_state.data()->sums, sc.d_state.data()->sums, kNumSums,
                                               ncclDouble, ncclSum, comm->comm, s);
             if (r != ncclSuccess)
                 return fail(SAGEICP_ERR_RCCL, std::string("ncclAllReduce: ") +
@@ -659,7 +659,7 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
         // (the one-launch loop has run; the state is on the host)
     } else if (polled) {
         const int depth = std::min(8, std::max(1, env_int("SAGEICP_DEPTH", 4)));
-        volatile unsigned long long *word = &sc.h_prog->word;
+        volatile unsigned long long *word = &sc.h_prog.data()->word;
         int enq = 0;
         unsigned spins = 0;
         unsigned long long idle_word = ~0ull;       // (chained: the progress word at the last look that found the stream idle)
@@ -695,15 +695,15 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
             // no launch was enqueued at all (the sort refused the frame — a non-finite point — before the host got to
             // iteration 0): nobody will tell the solving wave to start, so it is sent home here, not when this call returns
             sc.go_word = solver_guard.epoch | 0x8000000000000000ull;
-            HIPCHK(hipMemcpyAsync(&sc.d_loop->go[0], &sc.go_word, sizeof(sc.go_word), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(&sc.d_loop.data()->go[0], &sc.go_word, sizeof(sc.go_word), hipMemcpyHostToDevice, s));
             solver_guard.sc = nullptr;
         }
         if (chain) HIPCHK(hipStreamWaitEvent(s, sc.ev_solve, 0));      // the solving wave writes the final state
-        if (counting) launch_sum_counters(sc.d_cand, static_cast<int>(ip.nwaves), sc.d_state, s);
+        if (counting) launch_sum_counters(sc.d_cand.data(), static_cast<int>(ip.nwaves), sc.d_state.data(), s);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(sc.h_state, sc.d_state, sizeof(IcpState), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (chain && (sc.h_state->loop_aborted || !sc.h_state->done) && !sc.h_state->bad_input) {
+        if (chain && (sc.h_state.data()->loop_aborted || !sc.h_state.data()->done) && !sc.h_state.data()->bad_input) {
             // a wait timed out (the solving wave was not resident beside the launches, or a launch took longer than its
             // patience): the frame again with k_fin between the launches — same lanes per query, same bits
             static std::atomic<int> told{0};
@@ -716,7 +716,7 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
             return rc2;
         }
         if (prof)
-            for (int k = 0; k < sc.h_state->iter && k < enq; ++k)      // the rest were no-ops
+            for (int k = 0; k < sc.h_state.data()->iter && k < enq; ++k)      // the rest were no-ops
                 if (sampled(k)) harvest(k);
     } else {
         int launched = 0;
@@ -725,21 +725,21 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
             const int todo = std::min(chunk, kMaxIterations - launched);
             for (int k = 0; k < todo; ++k)
                 if ((rc = enqueue_iteration(k, launched + k))) return rc;
-            if (counting) launch_sum_counters(sc.d_cand, static_cast<int>(ip.nwaves), sc.d_state, s);
+            if (counting) launch_sum_counters(sc.d_cand.data(), static_cast<int>(ip.nwaves), sc.d_state.data(), s);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(sc.h_state, sc.d_state, sizeof(IcpState), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             if (prof) {
-                const int executed = std::min(todo, sc.h_state->iter - launched);   // the rest were no-ops
+                const int executed = std::min(todo, sc.h_state.data()->iter - launched);   // the rest were no-ops
                 for (int k = 0; k < executed; ++k)
                     if (sampled(launched + k)) harvest(k);
             }
             launched += todo;
-            if (sc.h_state->done || launched >= kMaxIterations) break;
+            if (sc.h_state.data()->done || launched >= kMaxIterations) break;
             chunk = std::min(kChunkMax, chunk * 2);   // 4, 8, 16, 16, ... : few syncs, bounded no-op tail
         }
     }
-    const IcpState &st = *sc.h_state;
+    const IcpState &st = *sc.h_state.data();
     if (st.peer_aborted && !looped && comm && g_restarts < 4) {
         // a peer gave up its one-launch loop at an exchange this rank made from k_fin: every rank starts the frame again
         // (this one in the form it already had)
@@ -867,8 +867,8 @@ int create_ranks(const sageicp_map *m) {
             hipExtMallocWithFlags(reinterpret_cast<void **>(&c->my_block), sizeof(P2pBlock),
                                   hipDeviceMallocFinegrained) != hipSuccess ||
             hipMemset(c->my_block, 0, sizeof(P2pBlock)) != hipSuccess ||
-            hipMalloc(&c->d_exchanges, sizeof(unsigned long long)) != hipSuccess ||
-            hipMemset(c->d_exchanges, 0, sizeof(unsigned long long)) != hipSuccess ||
+            c->d_exchanges.reserve(1) != hipSuccess ||
+            hipMemset(c->d_exchanges.data(), 0, sizeof(unsigned long long)) != hipSuccess ||
             hipDeviceSynchronize() != hipSuccess) {
             undo();
             return fail(SAGEICP_ERR_HIP, "allocating the exchange blocks failed");
@@ -921,15 +921,15 @@ int register_sharded(const sageicp_map *m, const double *h_frame, const Point4 *
             if ((r = sc.reserve_frame(cnt))) return r;
             if ((r = ensure_cand(mk, wants_filter(mk, cnt, sem_th)))) return r;
             if ((r = sc.reserve_sort(cnt))) return r;
-            mine = sc.d_frame;
+            mine = sc.d_frame.data();
             if (cnt) {
                 if (h_frame)
-                    HIPCHK(hipMemcpyAsync(sc.d_frame, h_frame + 4 * lo, cnt * sizeof(Point4),
+                    HIPCHK(hipMemcpyAsync(sc.d_frame.data(), h_frame + 4 * lo, cnt * sizeof(Point4),
                                           hipMemcpyHostToDevice, sc.stream));
                 else if (k == 0)
                     mine = d_frame + lo;
                 else
-                    HIPCHK(hipMemcpyPeerAsync(sc.d_frame, mk->device, d_frame + lo, m->device,
+                    HIPCHK(hipMemcpyPeerAsync(sc.d_frame.data(), mk->device, d_frame + lo, m->device,
                                               cnt * sizeof(Point4), sc.stream));
                 HIPCHK(hipStreamSynchronize(sc.stream));     // the shard has arrived (or the copy failed: here, not in the loop)
             }

@@ -321,42 +321,37 @@ inline unsigned grid_of(uint64_t n) { return static_cast<unsigned>((n + 255) / 2
 }  // namespace
 
 int DynFilter::reserve(size_t n, size_t nlabels) {
-    if (nlabels > labels_cap) {
-        if (d_labels) HIPCHK(hipFree(d_labels));
-        d_labels = nullptr;
-        HIPCHK(hipMalloc(&d_labels, (nlabels + 16) * sizeof(uint32_t)));
-        labels_cap = nlabels + 16;
-    }
-    if (!d_ctr) {
-        HIPCHK(hipMalloc(&d_ctr, 4 * sizeof(uint32_t)));
-        HIPCHK(hipHostMalloc(&h_ctr, 8 * sizeof(uint32_t), hipHostMallocDefault));
+    if (nlabels > d_labels.capacity()) HIPCHK(d_labels.reserve(nlabels + 16));
+    if (!h_ctr) {
+        HIPCHK(d_ctr.reserve(4));
+        HIPCHK(h_ctr.reserve(8));
     }
     if (n <= cap) return SAGEICP_OK;
-    free_points();
+    cap = 0;
     const size_t c = n + n / 4 + 1024;
     const size_t nrec = c / 5 + 2;
-    HIPCHK(hipMalloc(&d_cnt, c * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&d_pos, c * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&d_vp, c * sizeof(float4)));
-    HIPCHK(hipMalloc(&d_vs, c * sizeof(float4)));
-    HIPCHK(hipMalloc(&d_lp, c * sizeof(float4)));
-    HIPCHK(hipMalloc(&d_ls, c * sizeof(float4)));
-    HIPCHK(hipMalloc(&d_vkey, 2 * c * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&d_lkey, 2 * c * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&d_vval, 2 * c * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_lval, 2 * c * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_vframe, c * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_parent, c * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_root, c * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_size, c * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_count, c * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&d_rec_of_root, c * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_start, c * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_rkv, 2 * c * sizeof(uint32_t)));
-    HIPCHK(hipMalloc(&d_rec, nrec * sizeof(uint4)));
-    HIPCHK(hipMalloc(&d_off, nrec * sizeof(uint32_t)));
-    HIPCHK(hipHostMalloc(&h_rec, nrec * sizeof(uint4), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(&h_off, nrec * sizeof(uint32_t), hipHostMallocDefault));
+    HIPCHK(d_cnt.reserve(c));
+    HIPCHK(d_pos.reserve(c));
+    HIPCHK(d_vp.reserve(c));
+    HIPCHK(d_vs.reserve(c));
+    HIPCHK(d_lp.reserve(c));
+    HIPCHK(d_ls.reserve(c));
+    HIPCHK(d_vkey.reserve(2 * c));
+    HIPCHK(d_lkey.reserve(2 * c));
+    HIPCHK(d_vval.reserve(2 * c));
+    HIPCHK(d_lval.reserve(2 * c));
+    HIPCHK(d_vframe.reserve(c));
+    HIPCHK(d_parent.reserve(c));
+    HIPCHK(d_root.reserve(c));
+    HIPCHK(d_size.reserve(c));
+    HIPCHK(d_count.reserve(c));
+    HIPCHK(d_rec_of_root.reserve(c));
+    HIPCHK(d_start.reserve(c));
+    HIPCHK(d_rkv.reserve(2 * c));
+    HIPCHK(d_rec.reserve(nrec));
+    HIPCHK(d_off.reserve(nrec));
+    HIPCHK(h_rec.reserve(nrec));
+    HIPCHK(h_off.reserve(nrec));
     size_t b = 0, t = 0;
     unsigned long long *k64 = nullptr;
     uint32_t *k32 = nullptr;
@@ -366,37 +361,12 @@ int DynFilter::reserve(size_t n, size_t nlabels) {
     b = std::max(b, t);
     HIPCHK(rocprim::radix_sort_pairs(nullptr, t, k32, k32, k32, k32, c, 0, 32));
     b = std::max(b, t);
-    HIPCHK(hipMalloc(&d_temp, b));
-    temp_bytes = b;
+    HIPCHK(d_temp.reserve(b));
     cap = c;
     return SAGEICP_OK;
 }
 
-void DynFilter::free_points() {
-    void *dev[] = {d_cnt, d_pos, d_vp, d_vs, d_lp, d_ls, d_vkey, d_lkey, d_vval, d_lval, d_vframe, d_parent, d_root,
-                   d_size, d_count, d_rec_of_root, d_start, d_rkv, d_rec, d_off, d_temp};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (h_rec) (void)hipHostFree(h_rec);
-    if (h_off) (void)hipHostFree(h_off);
-    d_cnt = d_pos = nullptr;
-    d_vp = d_vs = d_lp = d_ls = nullptr;
-    d_vkey = d_lkey = nullptr;
-    d_vval = d_lval = d_vframe = d_parent = d_root = d_size = d_rec_of_root = d_start = d_rkv = d_off = nullptr;
-    d_count = nullptr;
-    d_rec = nullptr;
-    d_temp = nullptr;
-    h_rec = nullptr;
-    h_off = nullptr;
-    temp_bytes = 0;
-    cap = 0;
-}
-
 void DynFilter::destroy() {
-    free_points();
-    if (d_labels) (void)hipFree(d_labels);
-    if (d_ctr) (void)hipFree(d_ctr);
-    if (h_ctr) (void)hipHostFree(h_ctr);
     for (auto &e : ev)
         if (e) (void)hipEventDestroy(e);
     if (ev_table) (void)hipEventDestroy(ev_table);
@@ -412,6 +382,7 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
     int rc = reserve(n, nlab);
     if (rc) return rc;
     if (n == 0) return SAGEICP_OK;
+    size_t temp_bytes = d_temp.capacity();     // (rocprim takes the size by reference)
     const bool prof = g_profiling != 0;
     if (prof && !ev[0])
         for (auto &e : ev) HIPCHK(hipEventCreate(&e));
@@ -421,29 +392,29 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
     DynParams P{};
     P.in = in; P.n = static_cast<int>(n);
     P.max_range = max_range; P.min_range = min_range; P.label_max_range = label_max_range;
-    P.labels = d_labels; P.n_dyn = static_cast<int>(cfg.dynamic_labels.size()); P.n_lm = static_cast<int>(cfg.landmark_labels.size());
-    P.tmp = tmp; P.cnt = d_cnt; P.pos = d_pos; P.out = out;
-    P.vp = d_vp; P.vframe = d_vframe; P.vkey = d_vkey; P.vval = d_vval;
-    P.lp = d_lp; P.lkey = d_lkey; P.lval = d_lval;
-    P.ctr = d_ctr; P.ovf = d_ovf;
+    P.labels = d_labels.data(); P.n_dyn = static_cast<int>(cfg.dynamic_labels.size()); P.n_lm = static_cast<int>(cfg.landmark_labels.size());
+    P.tmp = tmp; P.cnt = d_cnt.data(); P.pos = d_pos.data(); P.out = out;
+    P.vp = d_vp.data(); P.vframe = d_vframe.data(); P.vkey = d_vkey.data(); P.vval = d_vval.data();
+    P.lp = d_lp.data(); P.lkey = d_lkey.data(); P.lval = d_lval.data();
+    P.ctr = d_ctr.data(); P.ovf = d_ovf;
 
     // ---- classify, compact -------------------------------------------------------------------------------------
     if (prof) HIPCHK(hipEventRecord(ev[0], s));
-    if (!lab.empty()) HIPCHK(hipMemcpyAsync(d_labels, lab.data(), lab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(d_ctr, 0, 4 * sizeof(uint32_t), s));
+    if (!lab.empty()) HIPCHK(hipMemcpyAsync(d_labels.data(), lab.data(), lab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(d_ctr.data(), 0, 4 * sizeof(uint32_t), s));
     hipLaunchKernelGGL(k_dyn_classify, dim3(grid_of(n)), dim3(256), 0, s, P);
-    HIPCHK(rocprim::exclusive_scan(d_temp, temp_bytes, d_cnt, d_pos, 0ull, static_cast<size_t>(n),
+    HIPCHK(rocprim::exclusive_scan(d_temp.data(), temp_bytes, d_cnt.data(), d_pos.data(), 0ull, static_cast<size_t>(n),
                                    rocprim::plus<unsigned long long>(), s));
     hipLaunchKernelGGL(k_dyn_compact, dim3(grid_of(n)), dim3(256), 0, s, P);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h_ctr + 4, d_ovf, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_ctr.data(), d_ctr.data(), 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_ctr.data() + 4, d_ovf, sizeof(int), hipMemcpyDeviceToHost, s));
     if (prof) HIPCHK(hipEventRecord(ev[1], s));
     HIPCHK(hipStreamSynchronize(s));
-    const int ovf1 = static_cast<int>(h_ctr[4]);
+    const int ovf1 = static_cast<int>(h_ctr.data()[4]);
     if (ovf1 & 2) return fail(SAGEICP_ERR_INVALID, "a label is not finite (NaN / Inf)");
     if (ovf1 & 1) return fail(SAGEICP_ERR_CAPACITY, "dynamic vehicle filter: a point lies beyond +-2^19 m");
-    const uint32_t n_in = h_ctr[0], nv = h_ctr[1], nl = h_ctr[2];
+    const uint32_t n_in = h_ctr.data()[0], nv = h_ctr.data()[1], nl = h_ctr.data()[2];
     info.vehicle_points = nv;
     info.landmark_points = nl;
     n_out = n_in;
@@ -459,55 +430,55 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
 
     // ---- grids, components, counts, the component table ------------------------------------------------------------
     if (prof) HIPCHK(hipEventRecord(ev[2], s));
-    unsigned long long *vkey_s = d_vkey + cap, *lkey_s = d_lkey + cap;
-    uint32_t *vidx = d_vval + cap, *lidx = d_lval + cap;
-    HIPCHK(rocprim::radix_sort_pairs(d_temp, temp_bytes, d_vkey, vkey_s, d_vval, vidx, nv, 0, 3 * kCellBits, s));
-    if (nl) HIPCHK(rocprim::radix_sort_pairs(d_temp, temp_bytes, d_lkey, lkey_s, d_lval, lidx, nl, 0, 3 * kCellBits, s));
-    hipLaunchKernelGGL(k_dyn_gather, dim3(grid_of(std::max(nv, nl))), dim3(256), 0, s, d_vp, vidx, nv, d_vs, d_lp, lidx,
-                       nl, d_ls, d_parent, d_size, d_count, d_rec_of_root);
-    hipLaunchKernelGGL(k_dyn_link, dim3(grid_of(nv)), dim3(256), 0, s, d_vs, vkey_s, vidx, nv, d_parent, d_ovf);
-    hipLaunchKernelGGL(k_dyn_count, dim3(grid_of(nv)), dim3(256), 0, s, d_vs, vidx, nv, d_ls, lkey_s, nl, d_parent,
-                       d_root, d_size, d_count, d_ovf);
-    hipLaunchKernelGGL(k_dyn_root_flags, dim3(grid_of(nv)), dim3(256), 0, s, d_root, d_size, nv, d_cnt);
-    HIPCHK(rocprim::exclusive_scan(d_temp, temp_bytes, d_cnt, d_pos, 0ull, static_cast<size_t>(nv),
+    unsigned long long *vkey_s = d_vkey.data() + cap, *lkey_s = d_lkey.data() + cap;
+    uint32_t *vidx = d_vval.data() + cap, *lidx = d_lval.data() + cap;
+    HIPCHK(rocprim::radix_sort_pairs(d_temp.data(), temp_bytes, d_vkey.data(), vkey_s, d_vval.data(), vidx, nv, 0, 3 * kCellBits, s));
+    if (nl) HIPCHK(rocprim::radix_sort_pairs(d_temp.data(), temp_bytes, d_lkey.data(), lkey_s, d_lval.data(), lidx, nl, 0, 3 * kCellBits, s));
+    hipLaunchKernelGGL(k_dyn_gather, dim3(grid_of(std::max(nv, nl))), dim3(256), 0, s, d_vp.data(), vidx, nv, d_vs.data(), d_lp.data(), lidx,
+                       nl, d_ls.data(), d_parent.data(), d_size.data(), d_count.data(), d_rec_of_root.data());
+    hipLaunchKernelGGL(k_dyn_link, dim3(grid_of(nv)), dim3(256), 0, s, d_vs.data(), vkey_s, vidx, nv, d_parent.data(), d_ovf);
+    hipLaunchKernelGGL(k_dyn_count, dim3(grid_of(nv)), dim3(256), 0, s, d_vs.data(), vidx, nv, d_ls.data(), lkey_s, nl, d_parent.data(),
+                       d_root.data(), d_size.data(), d_count.data(), d_ovf);
+    hipLaunchKernelGGL(k_dyn_root_flags, dim3(grid_of(nv)), dim3(256), 0, s, d_root.data(), d_size.data(), nv, d_cnt.data());
+    HIPCHK(rocprim::exclusive_scan(d_temp.data(), temp_bytes, d_cnt.data(), d_pos.data(), 0ull, static_cast<size_t>(nv),
                                    rocprim::plus<unsigned long long>(), s));
-    hipLaunchKernelGGL(k_dyn_records, dim3(grid_of(nv)), dim3(256), 0, s, d_cnt, d_pos, nv, d_size, d_count, d_rec,
-                       d_rec_of_root, d_ctr);
+    hipLaunchKernelGGL(k_dyn_records, dim3(grid_of(nv)), dim3(256), 0, s, d_cnt.data(), d_pos.data(), nv, d_size.data(), d_count.data(), d_rec.data(),
+                       d_rec_of_root.data(), d_ctr.data());
     HIPCHK(hipGetLastError());
     const size_t max_rec = nv / 5;             // components of >= 5 points
-    HIPCHK(hipMemcpyAsync(h_ctr, d_ctr, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h_ctr + 4, d_ovf, sizeof(int), hipMemcpyDeviceToHost, s));
-    if (max_rec) HIPCHK(hipMemcpyAsync(h_rec, d_rec, max_rec * sizeof(uint4), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_ctr.data(), d_ctr.data(), 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_ctr.data() + 4, d_ovf, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (max_rec) HIPCHK(hipMemcpyAsync(h_rec.data(), d_rec.data(), max_rec * sizeof(uint4), hipMemcpyDeviceToHost, s));
     if (!ev_table) HIPCHK(hipEventCreateWithFlags(&ev_table, hipEventDisableTiming));
     HIPCHK(hipEventRecord(ev_table, s));
     // grouping of the points by component runs while the host works on the table
-    uint32_t *rkey = d_rkv, *rval = d_rkv + cap;
+    uint32_t *rkey = d_rkv.data(), *rval = d_rkv.data() + cap;
     unsigned bits = 1;
     while (bits < 32 && (1ull << bits) < nv) ++bits;
-    HIPCHK(rocprim::radix_sort_pairs(d_temp, temp_bytes, d_root, rkey, d_vval, rval, nv, 0, bits, s));
-    hipLaunchKernelGGL(k_dyn_starts, dim3(grid_of(nv)), dim3(256), 0, s, rkey, nv, d_start);
+    HIPCHK(rocprim::radix_sort_pairs(d_temp.data(), temp_bytes, d_root.data(), rkey, d_vval.data(), rval, nv, 0, bits, s));
+    hipLaunchKernelGGL(k_dyn_starts, dim3(grid_of(nv)), dim3(256), 0, s, rkey, nv, d_start.data());
     HIPCHK(hipGetLastError());
     if (prof) HIPCHK(hipEventRecord(ev[3], s));
     const double th0 = now_us();
     HIPCHK(hipEventSynchronize(ev_table));
-    if (h_ctr[4] & 4) return fail(SAGEICP_ERR_HIP, "dynamic vehicle filter: union-find invariant broken");
-    const uint32_t ncl = h_ctr[3];
+    if (h_ctr.data()[4] & 4) return fail(SAGEICP_ERR_HIP, "dynamic vehicle filter: union-find invariant broken");
+    const uint32_t ncl = h_ctr.data()[3];
     if (ncl > max_rec) return fail(SAGEICP_ERR_HIP, "dynamic vehicle filter: inconsistent component table");
 
     // ---- host: PCL's cluster order and the static test (Preprocessing.cpp:130-170) --------------------------------
-    const uint4 *rec = static_cast<const uint4 *>(h_rec);
+    const uint4 *rec = h_rec.data();
     order_scratch.resize(ncl);
     size_scratch.resize(ncl);
     for (uint32_t k = 0; k < ncl; ++k) size_scratch[k] = rec[k].y;
     cluster_emission_order(size_scratch.data(), ncl, order_scratch.data());
     uint64_t at = n_in, kept = 0, kept_pts = 0;
-    for (uint32_t k = 0; k < ncl; ++k) h_off[k] = kNone;
+    for (uint32_t k = 0; k < ncl; ++k) h_off.data()[k] = kNone;
     for (uint32_t e = 0; e < ncl; ++e) {
         const uint32_t k = order_scratch[e];
         const uint32_t sz = rec[k].y;
         const uint64_t count = static_cast<uint64_t>(rec[k].z) | (static_cast<uint64_t>(rec[k].w) << 32);
         if (cluster_is_static(count, sz, cfg.dy_th)) {
-            h_off[k] = static_cast<uint32_t>(at);
+            h_off.data()[k] = static_cast<uint32_t>(at);
             at += sz;
             ++kept;
             kept_pts += sz;
@@ -522,9 +493,9 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
     // ---- scatter ---------------------------------------------------------------------------------------------------
     if (kept) {
         if (prof) HIPCHK(hipEventRecord(ev[4], s));
-        HIPCHK(hipMemcpyAsync(d_off, h_off, ncl * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_dyn_scatter, dim3(grid_of(nv)), dim3(256), 0, s, rkey, rval, nv, d_start, d_rec_of_root,
-                           d_off, d_vframe, tmp, out);
+        HIPCHK(hipMemcpyAsync(d_off.data(), h_off.data(), ncl * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_dyn_scatter, dim3(grid_of(nv)), dim3(256), 0, s, rkey, rval, nv, d_start.data(), d_rec_of_root.data(),
+                           d_off.data(), d_vframe.data(), tmp, out);
         HIPCHK(hipGetLastError());
         if (prof) HIPCHK(hipEventRecord(ev[5], s));
     }
