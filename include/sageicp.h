@@ -59,8 +59,9 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * reserved0), sageicp_pipeline_prefetch_wait, non-finite input refused (SAGEICP_ERR_INVALID) at every entry
  * that would cast it.   4: sageicp_map_loop_status, sageicp_reload_env; then the dynamic vehicle filter —
  * sageicp_preprocess_dynamic, sageicp_cluster_emission_order, sageicp_dynfilter_info and the pipeline's
- * sageicp_pipeline_set_dynamic_vehicle_filter / sageicp_pipeline_dynamic_filter_info (additions only: no
- * existing struct or entry changed). */
+ * sageicp_pipeline_set_dynamic_vehicle_filter / sageicp_pipeline_dynamic_filter_info; then frames in device memory —
+ * sageicp_device_frame, SAGEICP_DTYPE_*, sageicp_pipeline_register_frame_device, sageicp_frame_from_device (additions
+ * only: no existing struct or entry changed). */
 #define SAGEICP_ABI_VERSION 4
 
 /* Filled by sageicp_register_frame*.  Times are microseconds. */
@@ -431,6 +432,51 @@ int sageicp_pipeline_register_frame_timestamps(sageicp_pipeline *p, const double
                                                sageicp_stats *stats /* optional */);
 /* Whether the last frame registered was deskewed, and the delta tangent it used (zeros if not). */
 int sageicp_pipeline_deskew_info(const sageicp_pipeline *p, int *applied, double delta_out[6]);
+
+/* ---- frames already in device memory (a segmentation network's tensors) --------------------------
+ * A raw frame in the caller's device memory, read in place by the ingest kernel (ingest.hip), which writes the
+ * library's double[n][4] rows on the device: every value converted with a plain (double) cast (round to nearest, as
+ * numpy's astype(float64) or torch's .double()), nothing else — no mask, no label table.  Non-finite values pass
+ * through and meet the same checks as host input (the whole call refused, SAGEICP_ERR_INVALID).
+ *   xyz    row i starts at xyz + i * xyz_stride bytes; x, y, z are its first three elements (FLOAT32 or FLOAT64).
+ *          xyz_stride: a multiple of the element size, at least 3 elements (4 when the label is column 3).
+ *   label  NULL: column 3 of the same rows, of xyz_dtype (label_dtype and label_stride are not read);
+ *          else element i at label + i * label_stride bytes, UINT8 / INT32 / INT64, stride a multiple of its size.
+ * Every extent must be device memory on the handle's device (checked with hipPointerGetAttributes on its first and
+ * last byte, before anything is enqueued): host, pinned or managed memory is refused, not copied.
+ * Stream: the work that wrote the buffers is ordered before the ingest through an event on `stream` (a hipStream_t
+ * of the handle's device; NULL: the null stream).  Lifetime: the calls are synchronous — once one returns, nothing
+ * reads the caller's buffers any more (they may be overwritten or freed).  A process must hold ONE HIP runtime:
+ * pointers and streams of another runtime loaded beside this library's mean nothing to it. */
+#define SAGEICP_DTYPE_FLOAT32 1
+#define SAGEICP_DTYPE_FLOAT64 2
+#define SAGEICP_DTYPE_UINT8 3
+#define SAGEICP_DTYPE_INT32 4
+#define SAGEICP_DTYPE_INT64 5
+typedef struct sageicp_device_frame {
+    const void *xyz;            /* device memory, n rows */
+    uint64_t xyz_stride;        /* bytes between rows */
+    int32_t xyz_dtype;          /* SAGEICP_DTYPE_FLOAT32 / _FLOAT64 */
+    int32_t label_dtype;        /* SAGEICP_DTYPE_UINT8 / _INT32 / _INT64 (label != NULL only) */
+    const void *label;          /* device memory, n labels; NULL: column 3 of the rows */
+    uint64_t label_stride;      /* bytes between labels (label != NULL only) */
+    uint64_t n;                 /* points (at most 2^26 - 4) */
+} sageicp_device_frame;
+/* sageicp_pipeline_register_frame of a device frame.  timestamps == NULL: sageicp_pipeline_register_frame, bit for
+ * bit against the same values given as host rows.  timestamps != NULL (n fp64, contiguous, device memory):
+ * sageicp_pipeline_register_frame_timestamps — with deskew off they are not read; with deskew on they are checked on
+ * every frame, and a non-finite one is SAGEICP_ERR_INVALID with no pose pushed.  The frame is never one prepared by
+ * sageicp_pipeline_prefetch (which takes host frames only); an announcement is consumed by this call as by the host
+ * entries. */
+int sageicp_pipeline_register_frame_device(sageicp_pipeline *p, const sageicp_device_frame *frame,
+                                           const double *timestamps /* device or NULL */,
+                                           void *stream /* hipStream_t; NULL = null stream */, double pose_out[7],
+                                           double *icp_seconds, double *total_seconds, uint64_t *n_source,
+                                           sageicp_stats *stats /* optional */);
+/* sageicp_frame_upload of a device frame: the rows are built on the map's device; the result feeds
+ * sageicp_register_frame_resident (sharded too) and is released with sageicp_frame_destroy.  NULL on error. */
+sageicp_frame *sageicp_frame_from_device(const sageicp_map *map, const sageicp_device_frame *frame,
+                                         void *stream /* hipStream_t; NULL = null stream */);
 int sageicp_pipeline_reinitialize(sageicp_pipeline *p);          /* pipeline/sageICP.hpp:94-99 */
 uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p);  /* poses().size() */
 int sageicp_pipeline_pose(const sageicp_pipeline *p, uint64_t index, double pose_out[7]);

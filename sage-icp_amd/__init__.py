@@ -16,6 +16,7 @@ The directory is named `sage-icp_amd`; import it as `sage_icp_amd` through the l
 """
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -42,6 +43,7 @@ UNIQUE_ID_BYTES = 128
 P2P_HANDLE_BYTES = 64
 
 IDENTITY = np.array([0, 0, 0, 1, 0, 0, 0], dtype=np.float64)
+DTYPE_FLOAT32, DTYPE_FLOAT64, DTYPE_UINT8, DTYPE_INT32, DTYPE_INT64 = 1, 2, 3, 4, 5     # SAGEICP_DTYPE_*
 
 
 class SageIcpError(RuntimeError):
@@ -104,6 +106,12 @@ class DynFilterInfo(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class DeviceFrame(C.Structure):
+    """sageicp_device_frame: a raw frame in device memory (xyz rows, labels in column 3 or apart)"""
+    _fields_ = [("xyz", C.c_void_p), ("xyz_stride", C.c_uint64), ("xyz_dtype", C.c_int32), ("label_dtype", C.c_int32),
+                ("label", C.c_void_p), ("label_stride", C.c_uint64), ("n", C.c_uint64)]
 
 
 # the SemanticKITTI parameter sets of ros/launch/odometry*.launch.py
@@ -215,6 +223,9 @@ _SIGNATURES = [
     ("sageicp_pipeline_register_frame_timestamps", C.c_int,
      [C.c_void_p, _dp, _dp, C.c_uint64, _dp, _dp, _dp, _u64p, C.POINTER(Stats)]),
     ("sageicp_pipeline_deskew_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int), _dp]),
+    ("sageicp_pipeline_register_frame_device", C.c_int,
+     [C.c_void_p, C.POINTER(DeviceFrame), C.c_void_p, C.c_void_p, _dp, _dp, _dp, _u64p, C.POINTER(Stats)]),
+    ("sageicp_frame_from_device", C.c_void_p, [C.c_void_p, C.POINTER(DeviceFrame), C.c_void_p]),
     ("sageicp_pipeline_create", C.c_void_p, [C.POINTER(PipelineConfig)]),
     ("sageicp_pipeline_destroy", None, [C.c_void_p]),
     ("sageicp_pipeline_register_frame", C.c_int,
@@ -299,6 +310,79 @@ def device_count():
     return int(lib().sageicp_device_count())
 
 
+# ---- frames that are torch tensors on a GPU (sageicp_device_frame) ------------------------------------------------------
+# torch is never imported here: a tensor can only exist once its caller has imported it.
+_XYZ_DTYPES = {"torch.float32": DTYPE_FLOAT32, "torch.float64": DTYPE_FLOAT64}
+_LABEL_DTYPES = {"torch.uint8": DTYPE_UINT8, "torch.int32": DTYPE_INT32, "torch.int64": DTYPE_INT64}
+
+
+def _is_tensor(x):
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(x, torch.Tensor)
+
+
+def _is_device_tensor(x):
+    """a torch tensor that is not in host memory: it takes the device path (a CPU tensor keeps the host path)"""
+    return _is_tensor(x) and x.device.type != "cpu"
+
+
+_one_runtime = [False]
+
+
+def _hip_runtimes():
+    """the distinct libamdhip64 files mapped into this process: {(device, inode): path}"""
+    found = {}
+    with open("/proc/self/maps") as f:
+        for line in f:
+            parts = line.split(None, 5)
+            if len(parts) == 6 and os.path.basename(parts[5].strip()).startswith("libamdhip64"):
+                found.setdefault((parts[3], parts[4]), parts[5].strip())
+    return found
+
+
+def _check_one_hip_runtime():
+    """Pointers and streams of a tensor mean something to this library only if torch and the library share one HIP
+    runtime.  Some torch wheels bundle their own libamdhip64 with the ROCm one's soname: imported first, torch's is
+    the one the library binds to; loaded after the library, it is a second runtime beside it."""
+    if _one_runtime[0]:
+        return
+    paths = sorted(set(_hip_runtimes().values()))
+    if len(paths) > 1:
+        raise SageIcpError(ERR_INVALID, "two HIP runtimes are loaded in this process (%s): a torch tensor's memory and "
+                                        "stream mean nothing to the library's; import torch before the first "
+                                        "sage_icp_amd call" % " and ".join(paths))
+    _one_runtime[0] = True       # (torch loads its runtime when it is imported, before any tensor exists)
+
+
+def _device_frame(pts, labels, device):
+    """(DeviceFrame, stream) for a torch tensor on a GPU; everything that can be wrong with the arguments raises
+    ValueError here, before any call into the library"""
+    if pts.dim() != 2 or pts.shape[1] < (3 if labels is not None else 4) or pts.stride(1) != 1:
+        raise ValueError("a device frame is a 2-D tensor with stride(1) == 1 and at least %d columns, not shape %s "
+                         "strides %s" % (3 if labels is not None else 4, tuple(pts.shape), tuple(pts.stride())))
+    xd = _XYZ_DTYPES.get(str(pts.dtype))
+    if xd is None:
+        raise ValueError("a device frame is float32 or float64, not %s" % pts.dtype)
+    if labels is not None:
+        if not _is_device_tensor(labels):
+            raise ValueError("labels of a device frame are a tensor on the same device")
+        if labels.dim() != 1 or labels.shape[0] != pts.shape[0]:
+            raise ValueError("labels: a 1-D tensor of %d elements, not shape %s" % (pts.shape[0], tuple(labels.shape)))
+        if str(labels.dtype) not in _LABEL_DTYPES:
+            raise ValueError("labels are uint8, int32 or int64, not %s" % labels.dtype)
+        if labels.device != pts.device:
+            raise ValueError("labels on %s, points on %s" % (labels.device, pts.device))
+    if pts.device.type != "cuda" or pts.device.index != device:
+        raise ValueError("the frame is on %s, the pipeline / map on GPU %d" % (pts.device, device))
+    _check_one_hip_runtime()
+    f = DeviceFrame(pts.data_ptr() or None, pts.stride(0) * pts.element_size(), xd, 0, None, 0, pts.shape[0])
+    if labels is not None:
+        f.label, f.label_stride = labels.data_ptr() or None, labels.stride(0) * labels.element_size()
+        f.label_dtype = _LABEL_DTYPES[str(labels.dtype)]
+    stream = sys.modules["torch"].cuda.current_stream(pts.device).cuda_stream
+    return f, stream
+
+
 def robin_sweep(vox, far, listed):
     """sageicp_robin_sweep: (erased voxels in erasure order, iteration order of the rest)"""
     v = np.ascontiguousarray(vox, dtype=np.int32).reshape(-1, 3)
@@ -329,9 +413,20 @@ def set_counting(on):
 
 
 class Frame:
-    """A scan resident in HBM (sageicp_frame)."""
+    """A scan resident in HBM (sageicp_frame).  `pts`: (n,4) host rows, or a torch tensor on the map's GPU (float32 /
+    float64, x y z in its first three columns; the label in column 3 or, given, `labels`: 1-D uint8 / int32 / int64 on
+    the same device), built on the device in the current torch stream's order."""
 
-    def __init__(self, vmap, pts):
+    def __init__(self, vmap, pts, labels=None):
+        if _is_device_tensor(pts):
+            f, stream = _device_frame(pts, labels, vmap.device)
+            self.n = int(f.n)
+            self._h = lib().sageicp_frame_from_device(vmap._h, C.byref(f), stream)
+            if not self._h:
+                raise SageIcpError(ERR_INVALID, (lib().sageicp_last_error() or b"").decode())
+            return
+        if labels is not None:
+            raise ValueError("labels= is for a frame that is a torch tensor on a GPU")
         pts, pp = _d(pts)
         self.n = pts.reshape(-1, 4).shape[0]
         self._h = lib().sageicp_frame_upload(vmap._h, pp, self.n)
@@ -612,10 +707,18 @@ class SageICP:
             lib().sageicp_pipeline_destroy(self._h)
             self._h = None
 
-    def RegisterFrame(self, frame, timestamps=None):
+    def RegisterFrame(self, frame, timestamps=None, labels=None):
         """returns (pose[7], icp_seconds, total_seconds, n_source, stats).  With `timestamps` (one per point, in [0, 1)
         for a scan — see normalize_timestamps) this is RegisterFrame(frame, timestamps), which deskews when deskew is
-        on; without, the one-argument RegisterFrame(frame), which never does."""
+        on; without, the one-argument RegisterFrame(frame), which never does.
+        `frame` may be a torch tensor on the pipeline's GPU (float32 / float64, stride(1) == 1, x y z in columns 0-2 and
+        the label in column 3, or `labels`: a 1-D uint8 / int32 / int64 tensor on the same device, column 3 then
+        ignored); `timestamps` are then a tensor on that device too.  The frame is read in the order of the device's
+        current torch stream, and not any more once the call has returned."""
+        if _is_device_tensor(frame):
+            return self._register_device(frame, timestamps, labels)
+        if labels is not None:
+            raise ValueError("labels= is for a frame that is a torch tensor on a GPU")
         pts, pp = _d(frame)
         n = pts.reshape(-1, 4).shape[0]
         out = np.empty(7)
@@ -631,6 +734,22 @@ class SageICP:
             _check(lib().sageicp_pipeline_register_frame_timestamps(self._h, pp, tp, n, out.ctypes.data_as(_dp),
                                                                     C.byref(icp), C.byref(tot), C.byref(ns),
                                                                     C.byref(st)))
+        return out, icp.value, tot.value, ns.value, st
+
+    def _register_device(self, frame, timestamps, labels):
+        if timestamps is not None:
+            if not _is_device_tensor(timestamps) or timestamps.device != frame.device:
+                raise ValueError("timestamps of a device frame are a tensor on the same device")
+            if str(timestamps.dtype) != "torch.float64" or timestamps.dim() != 1 or \
+                    timestamps.shape[0] != frame.shape[0] or timestamps.stride(0) != 1:
+                raise ValueError("timestamps: a contiguous 1-D float64 tensor of %d elements" % frame.shape[0])
+        f, stream = _device_frame(frame, labels, self.config.device)
+        out = np.empty(7)
+        icp, tot, ns = C.c_double(0), C.c_double(0), C.c_uint64(0)
+        st = Stats()
+        tp = (timestamps.data_ptr() or None) if timestamps is not None else None
+        _check(lib().sageicp_pipeline_register_frame_device(self._h, C.byref(f), tp, stream, out.ctypes.data_as(_dp),
+                                                            C.byref(icp), C.byref(tot), C.byref(ns), C.byref(st)))
         return out, icp.value, tot.value, ns.value, st
 
     def prefetch(self, next_frame):

@@ -675,6 +675,103 @@ void sageicp_frame_destroy(sageicp_frame *f) {
     delete f;
 }
 
+// ---- frames in the caller's device memory (ingest.hip) ------------------------------------------------------------
+static size_t dtype_bytes(int32_t t) {
+    switch (t) {
+    case SAGEICP_DTYPE_FLOAT32: return 4;
+    case SAGEICP_DTYPE_FLOAT64: return 8;
+    case SAGEICP_DTYPE_UINT8: return 1;
+    case SAGEICP_DTYPE_INT32: return 4;
+    case SAGEICP_DTYPE_INT64: return 8;
+    default: return 0;
+    }
+}
+
+// the first and the last byte of an extent must be device memory of `device` (this library's runtime's view of it:
+// a pointer of another HIP runtime loaded into the process is unknown here, and refused like host memory)
+static int check_extent(const void *p, uint64_t bytes, int device, const char *what) {
+    const char *ends[2] = {static_cast<const char *>(p), static_cast<const char *>(p) + bytes - 1};
+    for (const char *q : ends) {
+        hipPointerAttribute_t at{};
+        const hipError_t e = hipPointerGetAttributes(&at, q);
+        (void)hipGetLastError();        // an unknown pointer leaves an error behind that the next call must not see
+        if (e != hipSuccess || at.type != hipMemoryTypeDevice)
+            return fail(SAGEICP_ERR_INVALID, std::string(what) + " is not device memory of this process's HIP runtime "
+                                             "(host, pinned and managed memory are refused, not copied)");
+        if (at.device != device)
+            return fail(SAGEICP_ERR_INVALID, std::string(what) + " lives on device " + std::to_string(at.device) +
+                                             ", the handle on device " + std::to_string(device));
+    }
+    return SAGEICP_OK;
+}
+
+// Everything about a device frame that can be known before the stream is touched or anything launched: the layout
+// first (no device needed), then the size, then where the memory lives.  ts: the n timestamps that will be read, or
+// nullptr.
+static int check_device_frame(const sageicp_device_frame *f, const double *ts, void *stream, int device) {
+    if (!f) return fail(SAGEICP_ERR_INVALID, "null device frame");
+    if (f->n && !f->xyz) return fail(SAGEICP_ERR_INVALID, "device frame: xyz is NULL");
+    const size_t ex = f->xyz_dtype == SAGEICP_DTYPE_FLOAT32 || f->xyz_dtype == SAGEICP_DTYPE_FLOAT64 ? dtype_bytes(f->xyz_dtype) : 0;
+    if (!ex) return fail(SAGEICP_ERR_INVALID, "device frame: xyz_dtype must be SAGEICP_DTYPE_FLOAT32 or _FLOAT64");
+    const uint64_t cols = f->label ? 3 : 4;
+    if (f->xyz_stride < cols * ex || f->xyz_stride % ex)
+        return fail(SAGEICP_ERR_INVALID, f->label ? "device frame: xyz_stride must be a multiple of the element size and "
+                                                    "at least 3 elements"
+                                                  : "device frame: xyz_stride must be a multiple of the element size and "
+                                                    "at least 4 elements (the label is column 3)");
+    size_t el = 0;
+    if (f->label) {
+        el = f->label_dtype == SAGEICP_DTYPE_UINT8 || f->label_dtype == SAGEICP_DTYPE_INT32 ||
+             f->label_dtype == SAGEICP_DTYPE_INT64 ? dtype_bytes(f->label_dtype) : 0;
+        if (!el) return fail(SAGEICP_ERR_INVALID, "device frame: label_dtype must be SAGEICP_DTYPE_UINT8, _INT32 or _INT64");
+        if (f->label_stride < el || f->label_stride % el)
+            return fail(SAGEICP_ERR_INVALID, "device frame: label_stride must be a positive multiple of the label's size");
+    }
+    if (f->n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
+    if (!f->n) return SAGEICP_OK;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
+    int rc = check_extent(f->xyz, (f->n - 1) * f->xyz_stride + cols * ex, device, "device frame: xyz");
+    if (!rc && f->label) rc = check_extent(f->label, (f->n - 1) * f->label_stride + el, device, "device frame: label");
+    if (!rc && ts) rc = check_extent(ts, f->n * sizeof(double), device, "timestamps");
+    if (rc) return rc;
+    if (stream) {
+        int sd = -1;
+        const hipError_t e = hipStreamGetDevice(static_cast<hipStream_t>(stream), &sd);
+        (void)hipGetLastError();
+        if (e != hipSuccess || sd != device)
+            return fail(SAGEICP_ERR_INVALID, "stream is not a stream of the handle's device");
+    }
+    return SAGEICP_OK;
+}
+
+sageicp_frame *sageicp_frame_from_device(const sageicp_map *m, const sageicp_device_frame *fr, void *stream) {
+    if (!m) { fail(SAGEICP_ERR_INVALID, "null argument"); return nullptr; }
+    if (check_device_frame(fr, nullptr, stream, m->device)) return nullptr;
+    if (m->sc.init(m->device)) return nullptr;
+    if (hipSetDevice(m->device) != hipSuccess) { fail(SAGEICP_ERR_HIP, "hipSetDevice"); return nullptr; }
+    sageicp_frame *f = new sageicp_frame;
+    f->device = m->device;
+    f->n = fr->n;
+    if (f->d.reserve(std::max<uint64_t>(fr->n, 1)) != hipSuccess) {
+        fail(SAGEICP_ERR_HIP, "hipMalloc(frame)");
+        delete f;
+        return nullptr;
+    }
+    // on the caller's stream, behind the work that wrote the buffers; synchronous: afterwards nothing reads them
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    launch_ingest(ingest_args(*fr), f->d.data(), s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        fail(SAGEICP_ERR_HIP, std::string("ingest of a device frame: ") + hipGetErrorString(e));
+        delete f;
+        return nullptr;
+    }
+    return f;
+}
+
 // RegisterFrame of n points already on `device` (an uploaded frame, or the pipeline's source cloud)
 static int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
                              double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
@@ -1006,7 +1103,8 @@ struct sageicp_pipeline {
         prep[0].destroy();
         prep[1].destroy();
     }
-    int voxelize_into(sageicp::Prep &pr, const double *f, uint64_t m, const sageicp::DeskewArgs *deskew = nullptr) {
+    int voxelize_into(sageicp::Prep &pr, const double *f, uint64_t m, const sageicp::DeskewArgs *deskew = nullptr,
+                      const sageicp::DeviceSource *dev = nullptr) {
         int rc = pr.init(device);
         if (rc) return rc;
         std::vector<int> counts, labels;
@@ -1020,7 +1118,7 @@ struct sageicp_pipeline {
         pr.arrival_order_levels = env_int("SAGEICP_SOURCE_REFERENCE_ORDER", 0) ? 0u : 2u;
         return pr.run(f, m, impl.max_range_(), impl.min_range_(), impl.label_max_range_(),
                       static_cast<int>(counts.size()), counts.data(), labels.data(), vs.data(),
-                      crop, scales, 2, res, false, dyn_on ? &dyn_cfg : nullptr, deskew);
+                      crop, scales, 2, res, false, dyn_on ? &dyn_cfg : nullptr, deskew, dev);
     }
 };
 
@@ -1037,10 +1135,11 @@ sageicp_pipeline *sageicp_pipeline_create(const sageicp_pipeline_config *c) {
     return p;
 }
 void sageicp_pipeline_destroy(sageicp_pipeline *p) { delete p; }
-// timestamps: the frame's (deskew on, all finite) or nullptr (the one-argument RegisterFrame)
+// timestamps: the frame's (deskew on, all finite) or nullptr (the one-argument RegisterFrame).  dev: the frame is in the
+// caller's device memory (`frame` is not read; a non-null `timestamps` only marks deskew on, they are dev's)
 static int pipeline_register(sageicp_pipeline *p, const double *frame, const double *timestamps, uint64_t n,
                              double pose_out[7], double *icp_s, double *total_s, uint64_t *n_source,
-                             sageicp_stats *stats) {
+                             sageicp_stats *stats, const sageicp::DeviceSource *dev = nullptr) {
     // Deskew (deskew.hip) on the uploaded frame when the pipeline decides so, then Preprocess + Voxelize on the
     // device (preprocess.hip): crop + scale 0.5, then scale 1.5.
     // Neither cloud comes back to the host: the source is registered and the down-sampled frame
@@ -1049,20 +1148,21 @@ static int pipeline_register(sageicp_pipeline *p, const double *frame, const dou
     struct Backend {
         sageicp_pipeline *p;
         const double *ts;
+        const sageicp::DeviceSource *dev;
         int voxelize(const double *f, uint64_t m, uint64_t &n_src, const double *delta) {
             if (p->worker.joinable()) p->worker.join();
             int r;
             if (delta) {                         // deskewed: depends on the last two poses, never prepared ahead
-                sageicp::DeskewArgs da{ts, {}};
+                sageicp::DeskewArgs da{dev ? nullptr : ts, {}};
                 for (int k = 0; k < 6; ++k) da.delta.v[k] = delta[k];
                 p->ready = false;
-                r = p->voxelize_into(p->prep[p->cur], f, m, &da);
-            } else if (p->ready && p->pf_frame == f && p->pf_n == m &&
+                r = p->voxelize_into(p->prep[p->cur], f, m, &da, dev);
+            } else if (!dev && p->ready && p->pf_frame == f && p->pf_n == m &&
                 p->pf_print == sageicp_pipeline::fingerprint(f, m)) {   // prepared while the last frame registered
                 r = p->pf_rc ? fail(p->pf_rc, p->pf_err) : SAGEICP_OK;
                 p->cur ^= 1;
-            } else {                                                 // none, or another frame: dropped
-                r = p->voxelize_into(p->prep[p->cur], f, m);
+            } else {                                                 // none, another frame or a device frame: dropped
+                r = p->voxelize_into(p->prep[p->cur], f, m, nullptr, dev);
             }
             p->ready = false;
             n_src = p->prep[p->cur].kept_levels[1];
@@ -1108,7 +1208,7 @@ static int pipeline_register(sageicp_pipeline *p, const double *frame, const dou
         }
     };
     const int rc = p->impl.register_frame(frame, n, timestamps != nullptr, pose_out, icp_s, total_s, n_source, stats,
-                                          Backend{p, timestamps});
+                                          Backend{p, timestamps, dev});
     p->announced = false;       // an announcement is consumed by this call, also when it failed or the frame was empty
     return rc;
 }
@@ -1130,6 +1230,18 @@ int sageicp_pipeline_register_frame_timestamps(sageicp_pipeline *p, const double
         if (!std::isfinite(timestamps[i])) return fail(SAGEICP_ERR_INVALID, "deskew is on and a timestamp is not finite");
     static const double kNone = 0.0;       // (n == 0: a non-null marker that deskew is asked for)
     return pipeline_register(p, frame, timestamps ? timestamps : &kNone, n, pose_out, icp_s, total_s, n_source, stats);
+}
+int sageicp_pipeline_register_frame_device(sageicp_pipeline *p, const sageicp_device_frame *frame,
+                                           const double *timestamps, void *stream, double pose_out[7], double *icp_s,
+                                           double *total_s, uint64_t *n_source, sageicp_stats *stats) {
+    if (!p || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    // without timestamps the one-argument RegisterFrame (never deskews); with deskew off they are not read (not even
+    // checked), as in sageicp_pipeline_register_frame_timestamps
+    const double *ts = p->deskew_on ? timestamps : nullptr;
+    int rc = check_device_frame(frame, ts, stream, p->device);
+    if (rc) return rc;
+    const sageicp::DeviceSource dev{frame, ts, static_cast<hipStream_t>(stream)};
+    return pipeline_register(p, nullptr, ts, frame->n, pose_out, icp_s, total_s, n_source, stats, &dev);
 }
 int sageicp_pipeline_set_deskew(sageicp_pipeline *p, int enable) {
     if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");

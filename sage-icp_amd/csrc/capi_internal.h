@@ -406,9 +406,30 @@ struct DynFilter {
 
 // ---- deskew of a frame before it is preprocessed (deskew.hip; core/Deskew.cpp:36-50) ---------------------------
 struct DeskewArgs {
-    const double *timestamps;           // host, one per point, all finite (checked by the caller)
+    const double *timestamps;           // host, one per point, all finite (checked by the caller); a device frame's are in
+                                        // its DeviceSource
     DeskewTangent delta;                // (start.inverse() * finish).log()
 };
+
+// A raw frame in the caller's device memory (sageicp_device_frame, validated by capi.hip): the ingest kernel reads it
+// into d_in on Prep::stream once that stream has waited for the caller's.  timestamps: device, n of them, or nullptr
+// (not asked for); they are copied to d_ts and checked in the same pass.
+struct DeviceSource {
+    const sageicp_device_frame *frame;
+    const double *timestamps;
+    hipStream_t stream;
+};
+inline IngestArgs ingest_args(const sageicp_device_frame &f) {
+    IngestArgs a{};
+    a.xyz = static_cast<const unsigned char *>(f.xyz);
+    a.xyz_stride = f.xyz_stride;
+    a.xyz_dtype = f.xyz_dtype;
+    a.label = static_cast<const unsigned char *>(f.label);
+    a.label_stride = f.label_stride;
+    a.label_dtype = f.label_dtype;
+    a.n = static_cast<int>(f.n);
+    return a;
+}
 
 // ---- device preprocessing (preprocess.hip): buffers of one pipeline ------------------------------
 struct Prep {
@@ -441,6 +462,7 @@ struct Prep {
     // the timestamps of a frame that is deskewed (allocated with the first such frame): pinned staging, device copy
     PinnedBuf<double> h_ts;
     DevBuf<double> d_ts;
+    hipEvent_t ev_caller = nullptr;     // a device frame: orders the caller's stream before `stream` (created with the first)
 
     int init(int dev) {
         if (stream) return SAGEICP_OK;
@@ -495,9 +517,34 @@ struct Prep {
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(stream);
         dyn.destroy();
+        if (ev_caller) (void)hipEventDestroy(ev_caller);
         const hipStream_t s = stream;
         *this = Prep();                 // (releases the buffers: nothing runs on the stream any more)
         (void)hipStreamDestroy(s);
+    }
+
+    // The raw frame of a device source into d_in (and its timestamps into d_ts), after the work the caller enqueued on
+    // its stream.  Timestamps are checked here, before anything reads them: a non-finite one refuses the frame (the
+    // host entry's check, sageicp_pipeline_register_frame_timestamps).  The caller's buffers are last read by this
+    // launch, which the first level's synchronisation waits for: run() returns with them released.
+    int ingest(const DeviceSource &src, uint64_t n) {
+        if (!ev_caller) HIPCHK(hipEventCreateWithFlags(&ev_caller, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(ev_caller, src.stream));
+        HIPCHK(hipStreamWaitEvent(stream, ev_caller, 0));
+        IngestArgs a = ingest_args(*src.frame);
+        a.n = static_cast<int>(n);
+        a.ts = src.timestamps;
+        a.ts_out = src.timestamps ? d_ts.data() : nullptr;
+        a.flags = d_overflow.data();
+        launch_ingest(a, d_in.data(), stream);
+        HIPCHK(hipGetLastError());
+        if (src.timestamps) {
+            int flags = 0;
+            HIPCHK(hipMemcpyAsync(&flags, d_overflow.data(), sizeof(int), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            if (flags & kIngestBadTimestamp) return fail(SAGEICP_ERR_INVALID, "deskew is on and a timestamp is not finite");
+        }
+        return SAGEICP_OK;
     }
 
     // levels: each {do_crop, scale}; a scale <= 0 means "crop only" (no voxel test).  Runs the
@@ -506,11 +553,14 @@ struct Prep {
     // crops it itself: the levels then start from the filtered cloud with the crop off.
     // With `deskew` the uploaded frame is deskewed in place before anything else reads it (the reference's order:
     // DeSkewScan, then Preprocess, then Voxelize; pipeline/sageICP.cpp:36-52).
+    // With `dev` the raw frame comes from the caller's device memory instead of `frame` (ingest()); everything after
+    // it reaches d_in is the same.
     int run(const double *frame, uint64_t n, double max_range, double min_range,
             double label_max_range, int n_groups, const int *gcounts, const int *glabels,
             const double *gvs, const int *crop, const double *scales, int n_levels,
             std::vector<std::vector<double>> &out, bool download = true,
-            const DynFilterConfig *dyn_cfg = nullptr, const DeskewArgs *deskew = nullptr) {
+            const DynFilterConfig *dyn_cfg = nullptr, const DeskewArgs *deskew = nullptr,
+            const DeviceSource *dev = nullptr) {
         kept_levels[0] = kept_levels[1] = 0;
         us_order = 0;
         dyn_ran = dyn_cfg != nullptr;
@@ -521,7 +571,7 @@ struct Prep {
         for (int g = 0; g < n_groups; ++g) nlabels += static_cast<size_t>(gcounts[g]);
         int rc = reserve(n, nlabels);
         if (rc) return rc;
-        if (deskew) {
+        if (deskew || (dev && dev->timestamps)) {
             rc = reserve_timestamps(n);
             if (rc) return rc;
         }
@@ -533,13 +583,22 @@ struct Prep {
             HIPCHK(hipMemcpyAsync(d_glabels.data(), glabels, nlabels * sizeof(int), hipMemcpyHostToDevice, stream));
         }
         HIPCHK(hipMemsetAsync(d_overflow.data(), 0, sizeof(int), stream));
-        std::memcpy(h_pin.data(), frame, n * sizeof(Point4));
-        HIPCHK(hipMemcpyAsync(d_in.data(), h_pin.data(), n * sizeof(Point4), hipMemcpyHostToDevice, stream));
-        if (deskew) {
-            std::memcpy(h_ts.data(), deskew->timestamps, n * sizeof(double));
-            HIPCHK(hipMemcpyAsync(d_ts.data(), h_ts.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
-            launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream);
-            HIPCHK(hipGetLastError());
+        if (dev) {
+            rc = ingest(*dev, n);
+            if (rc) return rc;
+            if (deskew) {
+                launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream);
+                HIPCHK(hipGetLastError());
+            }
+        } else {
+            std::memcpy(h_pin.data(), frame, n * sizeof(Point4));
+            HIPCHK(hipMemcpyAsync(d_in.data(), h_pin.data(), n * sizeof(Point4), hipMemcpyHostToDevice, stream));
+            if (deskew) {
+                std::memcpy(h_ts.data(), deskew->timestamps, n * sizeof(double));
+                HIPCHK(hipMemcpyAsync(d_ts.data(), h_ts.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
+                launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream);
+                HIPCHK(hipGetLastError());
+            }
         }
         const Point4 *in = d_in.data();
         Point4 *outs[2] = {d_fd.data(), d_src.data()};

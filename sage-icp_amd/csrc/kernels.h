@@ -274,6 +274,22 @@ struct DeskewTangent {
 };
 void launch_deskew(const Point4 *in, Point4 *out, const double *ts, int n, const DeskewTangent &d, hipStream_t s);
 
+// ingest.hip: a frame in a caller's device memory (include/sageicp.h, sageicp_device_frame) into n Point4 rows, every
+// value a plain (double) conversion; optionally the frame's fp64 timestamps copied alongside, a non-finite one raising
+// kIngestBadTimestamp in *flags.  The layout has been validated by the caller (capi.hip).
+constexpr int kIngestBadTimestamp = 8;      // (Prep::d_overflow: 1, 2 are preprocess.hip's, 4 dyn_filter.hip's)
+struct IngestArgs {
+    const unsigned char *xyz;           // row i at xyz + i * xyz_stride
+    const unsigned char *label;         // nullptr: column 3 of the rows
+    unsigned long long xyz_stride, label_stride;     // bytes
+    int xyz_dtype, label_dtype;         // SAGEICP_DTYPE_*
+    int n;
+    const double *ts;                   // optional: [n] timestamps, copied to ts_out
+    double *ts_out;
+    int *flags;
+};
+void launch_ingest(const IngestArgs &a, Point4 *out, hipStream_t s);
+
 // sort.hip: re-ordering of a frame along the Morton curve of its map-frame voxels
 size_t sort_temp_bytes(int n);
 // ... and the dispatch order of k_icp's stripes: `order` = the stripes by `work`, heaviest first (stable); `work` is zeroed
