@@ -60,8 +60,9 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * that would cast it.   4: sageicp_map_loop_status, sageicp_reload_env; then the dynamic vehicle filter —
  * sageicp_preprocess_dynamic, sageicp_cluster_emission_order, sageicp_dynfilter_info and the pipeline's
  * sageicp_pipeline_set_dynamic_vehicle_filter / sageicp_pipeline_dynamic_filter_info; then frames in device memory —
- * sageicp_device_frame, SAGEICP_DTYPE_*, sageicp_pipeline_register_frame_device, sageicp_frame_from_device (additions
- * only: no existing struct or entry changed). */
+ * sageicp_device_frame, SAGEICP_DTYPE_*, sageicp_pipeline_register_frame_device, sageicp_frame_from_device; then outputs
+ * in device memory — sageicp_device_points, sageicp_pipeline_source, sageicp_pipeline_source_device,
+ * sageicp_map_pointcloud_device (additions only: no existing struct or entry changed). */
 #define SAGEICP_ABI_VERSION 4
 
 /* Filled by sageicp_register_frame*.  Times are microseconds. */
@@ -477,6 +478,52 @@ int sageicp_pipeline_register_frame_device(sageicp_pipeline *p, const sageicp_de
  * sageicp_register_frame_resident (sharded too) and is released with sageicp_frame_destroy.  NULL on error. */
 sageicp_frame *sageicp_frame_from_device(const sageicp_map *map, const sageicp_device_frame *frame,
                                          void *stream /* hipStream_t; NULL = null stream */);
+
+/* ---- outputs into the caller's device memory (egress.hip): the mirror of sageicp_device_frame ---------------------
+ * A destination of `cap` rows in the caller's device memory, written in place by the egress kernels.
+ *   xyz    row i at xyz + i * xyz_stride bytes; x, y, z are its first three elements (FLOAT32 or FLOAT64).
+ *          xyz_stride: a multiple of the element size, at least 3 elements (4 when the label is column 3).
+ *          May be NULL only when cap == 0.
+ *   label  NULL: column 3 of the same rows, of xyz_dtype (label_dtype and label_stride are not read);
+ *          else element i at label + i * label_stride bytes, UINT8 / INT32 / INT64 / FLOAT32 / FLOAT64, the stride a
+ *          positive multiple of its size.
+ * Which rows: *n_out is the number of rows available, n; the first min(cap, n) of them are written (as
+ * sageicp_map_pointcloud does) and the rest of the destination is not touched.
+ * Conversions: float64 coordinates are written bit for bit, float32 ones through a plain (float) cast (round to
+ * nearest, as numpy's astype(float32)); a float label is a plain cast; an integer label is static_cast<int64_t>(label)
+ * (the reference's cast) and must then fit the label's type — one that does not (259 into UINT8, say) makes the call
+ * SAGEICP_ERR_INVALID, and the destination's contents are then unspecified.
+ * Checks, before anything is enqueued: the layout above; every extent of `cap` rows must be device memory on the
+ * handle's device (hipPointerGetAttributes on its first and last byte): host, pinned or managed memory is refused,
+ * not copied.
+ * Stream: the caller's earlier work on `stream` (a hipStream_t of the handle's device; NULL: the null stream) is
+ * ordered before the write through an event — a caching allocator hands out blocks that earlier kernels on that
+ * stream may still be using.  Lifetime: the calls are synchronous — once one returns, the rows are in place and
+ * nothing of the library touches the destination any more. */
+typedef struct sageicp_device_points {
+    void *xyz;                  /* device memory, cap rows */
+    uint64_t xyz_stride;        /* bytes between rows */
+    int32_t xyz_dtype;          /* SAGEICP_DTYPE_FLOAT32 / _FLOAT64 */
+    int32_t label_dtype;        /* SAGEICP_DTYPE_UINT8 / _INT32 / _INT64 / _FLOAT32 / _FLOAT64 (label != NULL only) */
+    void *label;                /* device memory, cap labels; NULL: column 3 of the rows */
+    uint64_t label_stride;      /* bytes between labels (label != NULL only) */
+    uint64_t cap;               /* rows the destination holds */
+} sageicp_device_points;
+/* The source cloud of the last frame registered (RegisterFrame's `source`, pipeline/sageICP.cpp:94): the n_source rows
+ * that were registered, through any entry (host rows, timestamps, device frame; with or without prefetch, deskew or
+ * the dynamic filter), as double[n][4] host rows.  out_xyzl may be NULL only when cap == 0 (*n_out then tells n).
+ * Order: the pipeline's own — arrival order within each label group by default, a permutation of the reference's
+ * `source`; the reference's bucket order under SAGEICP_SOURCE_REFERENCE_ORDER=1.  0 rows before the first frame,
+ * after a register call that failed and after sageicp_pipeline_reinitialize.  Valid until the next register call. */
+int sageicp_pipeline_source(const sageicp_pipeline *p, double *out_xyzl, uint64_t cap, uint64_t *n_out);
+/* the same rows into the caller's device memory */
+int sageicp_pipeline_source_device(const sageicp_pipeline *p, const sageicp_device_points *dst,
+                                   void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
+/* sageicp_map_pointcloud's rows, in its order (the bucket order in reference-order mode), into the caller's device
+ * memory; packed on the device straight into the destination while the HBM copy is the authority, staged from the
+ * host copy while it is not */
+int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_points *dst,
+                                  void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
 int sageicp_pipeline_reinitialize(sageicp_pipeline *p);          /* pipeline/sageICP.hpp:94-99 */
 uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p);  /* poses().size() */
 int sageicp_pipeline_pose(const sageicp_pipeline *p, uint64_t index, double pose_out[7]);

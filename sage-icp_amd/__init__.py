@@ -114,6 +114,12 @@ class DeviceFrame(C.Structure):
                 ("label", C.c_void_p), ("label_stride", C.c_uint64), ("n", C.c_uint64)]
 
 
+class DevicePoints(C.Structure):
+    """sageicp_device_points: a destination in device memory (xyz rows, labels in column 3 or apart), cap rows"""
+    _fields_ = [("xyz", C.c_void_p), ("xyz_stride", C.c_uint64), ("xyz_dtype", C.c_int32), ("label_dtype", C.c_int32),
+                ("label", C.c_void_p), ("label_stride", C.c_uint64), ("cap", C.c_uint64)]
+
+
 # the SemanticKITTI parameter sets of ros/launch/odometry*.launch.py
 KITTI_VOXEL_LABELS = [[40, 44, 48, 49], [50, 51, 52], [70, 72], [60, 71, 80, 81, 99], [0],
                       [10, 11, 13, 15, 16, 18, 20]]
@@ -226,6 +232,9 @@ _SIGNATURES = [
     ("sageicp_pipeline_register_frame_device", C.c_int,
      [C.c_void_p, C.POINTER(DeviceFrame), C.c_void_p, C.c_void_p, _dp, _dp, _dp, _u64p, C.POINTER(Stats)]),
     ("sageicp_frame_from_device", C.c_void_p, [C.c_void_p, C.POINTER(DeviceFrame), C.c_void_p]),
+    ("sageicp_pipeline_source", C.c_int, [C.c_void_p, _dp, C.c_uint64, _u64p]),
+    ("sageicp_pipeline_source_device", C.c_int, [C.c_void_p, C.POINTER(DevicePoints), C.c_void_p, _u64p]),
+    ("sageicp_map_pointcloud_device", C.c_int, [C.c_void_p, C.POINTER(DevicePoints), C.c_void_p, _u64p]),
     ("sageicp_pipeline_create", C.c_void_p, [C.POINTER(PipelineConfig)]),
     ("sageicp_pipeline_destroy", None, [C.c_void_p]),
     ("sageicp_pipeline_register_frame", C.c_int,
@@ -381,6 +390,73 @@ def _device_frame(pts, labels, device):
         f.label_dtype = _LABEL_DTYPES[str(labels.dtype)]
     stream = sys.modules["torch"].cuda.current_stream(pts.device).cuda_stream
     return f, stream
+
+
+def _device_points(out, labels_out, device):
+    """(DevicePoints, stream) for a destination that is a torch tensor on a GPU (and its optional 1-D labels); everything
+    that can be wrong with the arguments raises ValueError here, before any call into the library"""
+    if not _is_device_tensor(out):
+        raise ValueError("out= is a torch tensor on the GPU, not %s" % ("a tensor on %s" % out.device if _is_tensor(out)
+                                                                          else type(out).__name__))
+    cols = 3 if labels_out is not None else 4
+    if out.dim() != 2 or out.shape[1] < cols or out.stride(1) != 1 or (out.shape[0] > 1 and out.stride(0) < cols):
+        raise ValueError("out= is a 2-D tensor with stride(1) == 1, rows that do not overlap and at least %d columns, not "
+                         "shape %s strides %s" % (cols, tuple(out.shape), tuple(out.stride())))
+    xd = _XYZ_DTYPES.get(str(out.dtype))
+    if xd is None:
+        raise ValueError("out= is float32 or float64, not %s" % out.dtype)
+    if labels_out is not None:
+        if not _is_device_tensor(labels_out):
+            raise ValueError("labels_out= is a tensor on the same device as out=")
+        if labels_out.dim() != 1 or labels_out.shape[0] != out.shape[0] or \
+                (labels_out.shape[0] > 1 and labels_out.stride(0) < 1):
+            raise ValueError("labels_out: a 1-D tensor of %d elements, not shape %s" % (out.shape[0],
+                                                                                        tuple(labels_out.shape)))
+        if str(labels_out.dtype) not in _LABEL_DTYPES:
+            raise ValueError("labels_out is uint8, int32 or int64, not %s" % labels_out.dtype)
+        if labels_out.device != out.device:
+            raise ValueError("labels_out on %s, out on %s" % (labels_out.device, out.device))
+    if out.device.type != "cuda" or out.device.index != device:
+        raise ValueError("out= is on %s, the pipeline / map on GPU %d" % (out.device, device))
+    _check_one_hip_runtime()
+    el = out.element_size()
+    d = DevicePoints(out.data_ptr() or None, max(out.stride(0), cols) * el, xd, 0, None, 0, out.shape[0])
+    if labels_out is not None:
+        d.label = labels_out.data_ptr() or None
+        d.label_stride = max(labels_out.stride(0), 1) * labels_out.element_size()
+        d.label_dtype = _LABEL_DTYPES[str(labels_out.dtype)]
+    stream = sys.modules["torch"].cuda.current_stream(out.device).cuda_stream
+    return d, stream
+
+
+def _rows_out(device_index, count, host_rows, device_call, device, dtype, out, labels_out):
+    """SageICP.source / SageICP.LocalMap / VoxelHashMap.Pointcloud: numpy (n, 4) float64 host rows (host_rows(n)); with
+    device=True a fresh (n, 4) tensor on the GPU (float64, or dtype=torch.float32); with out= (and labels_out=) the
+    caller's tensors, returned as the filled views out[:n] (and labels_out[:n]); an out= of fewer rows than there are
+    gets its first len(out) rows (the C entries' cap).  device_call(DevicePoints, stream, n_out) is the C entry;
+    count() the rows there are."""
+    if labels_out is not None and out is None:
+        raise ValueError("labels_out= goes with out=")
+    if out is None and not device:
+        if dtype is not None:
+            raise ValueError("dtype= is for device=True or out= (the host rows are float64)")
+        return host_rows(count())
+    if out is not None:
+        if dtype is not None and dtype != out.dtype:
+            raise ValueError("dtype=%s but out= is %s" % (dtype, out.dtype))
+        d, stream = _device_points(out, labels_out, device_index)
+    else:
+        import torch
+        dt = torch.float64 if dtype is None else dtype
+        if dt not in (torch.float32, torch.float64):
+            raise ValueError("dtype= is torch.float32 or torch.float64, not %s" % (dt,))
+        _check_one_hip_runtime()
+        out = torch.empty((count(), 4), dtype=dt, device=torch.device("cuda", device_index))
+        d, stream = _device_points(out, None, device_index)
+    n = C.c_uint64(0)
+    _check(device_call(C.byref(d), stream, C.byref(n)))
+    k = min(n.value, out.shape[0])
+    return out[:k] if labels_out is None else (out[:k], labels_out[:k])
 
 
 def robin_sweep(vox, far, listed):
@@ -582,11 +658,19 @@ class VoxelHashMap:
         else:
             raise ValueError("Update takes a pose[7] or an origin[3]")
 
-    def Pointcloud(self):
-        n = self.size()
-        out = np.empty((n, 4))
-        lib().sageicp_map_pointcloud(self._h, out.ctypes.data_as(_dp), n)
-        return out
+    def Pointcloud(self, device=False, dtype=None, out=None, labels_out=None):
+        """Pointcloud(): the host rows, numpy (n, 4) float64.  device=True: a fresh (n, 4) torch tensor on the map's GPU
+        (float64, or dtype=torch.float32); out= (and a 1-D uint8 / int32 / int64 labels_out=): the caller's tensors on
+        that GPU, filled with the first rows that fit and returned as out[:n] (labels_out[:n]).  An out= shorter than
+        size() gets only its first len(out) rows, as the C entry writes them: compare the returned length with size(),
+        or size the tensor from it.  Same rows in the same order either way (sageicp_map_pointcloud_device), written in
+        the order of the device's current torch stream; synchronous."""
+        if not device and dtype is None and out is None and labels_out is None:
+            n = self.size()
+            out = np.empty((n, 4))
+            lib().sageicp_map_pointcloud(self._h, out.ctypes.data_as(_dp), n)
+            return out
+        return _map_rows(lambda: self._h, self.device, device, dtype, out, labels_out)
 
     def resident(self):
         """True while the HBM copy of the map is the authority (after a device-side update)"""
@@ -782,12 +866,50 @@ class SageICP:
             _check(lib().sageicp_pipeline_pose(self._h, i, out[i].ctypes.data_as(_dp)))
         return out
 
-    def LocalMap(self):
-        h = lib().sageicp_pipeline_local_map(self._h)
-        n = int(lib().sageicp_map_size(h))
-        out = np.empty((n, 4))
-        lib().sageicp_map_pointcloud(h, out.ctypes.data_as(_dp), n)
-        return out
+    def LocalMap(self, device=False, dtype=None, out=None, labels_out=None):
+        """LocalMap(): the map's rows on the host, numpy (n, 4) float64; the keywords as VoxelHashMap.Pointcloud (an
+        out= shorter than local_map_size() gets its first len(out) rows)"""
+        if not device and dtype is None and out is None and labels_out is None:
+            h = lib().sageicp_pipeline_local_map(self._h)
+            n = int(lib().sageicp_map_size(h))
+            out = np.empty((n, 4))
+            lib().sageicp_map_pointcloud(h, out.ctypes.data_as(_dp), n)
+            return out
+        return _map_rows(lambda: lib().sageicp_pipeline_local_map(self._h), self.config.device, device, dtype, out,
+                         labels_out)
+
+    def source(self, device=False, dtype=None, out=None, labels_out=None):
+        """RegisterFrame's `source` (pipeline/sageICP.cpp:94): the cloud the last successful RegisterFrame registered,
+        n_source rows; none before the first frame, after a failed call and after reinitialize().  Valid until the
+        next RegisterFrame.  The order is the pipeline's: arrival order within each label group (a permutation of the
+        reference's), the reference's under SAGEICP_SOURCE_REFERENCE_ORDER=1.  The keywords as
+        VoxelHashMap.Pointcloud (an out= shorter than source_size() gets its first len(out) rows)."""
+        return _rows_out(self.config.device, self.source_size, self._source_host,
+                         lambda d, s, n: lib().sageicp_pipeline_source_device(self._h, d, s, n),
+                         device, dtype, out, labels_out)
+
+    def source_size(self):
+        """rows of source(): n_source of the last successful RegisterFrame, 0 if there is none"""
+        n = C.c_uint64(0)
+        _check(lib().sageicp_pipeline_source(self._h, None, 0, C.byref(n)))
+        return n.value
+
+    def local_map_size(self):
+        """rows of LocalMap()"""
+        return int(lib().sageicp_map_size(lib().sageicp_pipeline_local_map(self._h)))
+
+    def _source_host(self, n):
+        a = np.empty((n, 4))
+        k = C.c_uint64(0)
+        _check(lib().sageicp_pipeline_source(self._h, a.ctypes.data_as(_dp), n, C.byref(k)))
+        return a
+
+
+def _map_rows(handle, device_index, device, dtype, out, labels_out):
+    """the map's rows on the device (VoxelHashMap.Pointcloud, SageICP.LocalMap); handle() gives the map's handle"""
+    return _rows_out(device_index, lambda: int(lib().sageicp_map_size(handle())), None,
+                     lambda d, s, n: lib().sageicp_map_pointcloud_device(handle(), d, s, n), device, dtype, out,
+                     labels_out)
 
 
 def preprocess(frame, max_range, min_range, label_max_range, device=0, dynamic_vehicle_filter=False, dy_th=0.5,

@@ -182,6 +182,7 @@ void sageicp_map_destroy(sageicp_map *m) {
         (void)hipSetDevice(m->device);
         (void)hipStreamSynchronize(m->sc.stream);
     }
+    if (m->ev_caller) (void)hipEventDestroy(m->ev_caller);
     m->sc.destroy();
     delete m;
 }
@@ -411,16 +412,14 @@ static void pretouch(void *p, size_t bytes) {
     pool.run(static_cast<size_t>(threads), job, static_cast<size_t>(threads));
 }
 
-static int pointcloud_from_device(const sageicp_map *m, double *out, uint64_t cap, uint64_t *n_out) {
-    HIPCHK(hipSetDevice(m->device));
-    hipStream_t s = m->sc.stream;
+// The live points of a resident map packed on stream s in sageicp_map_pointcloud's order: into d_pc (e == nullptr), or
+// straight into a caller's layout (egress.h; the rows at and beyond e->cap are not written).  Synchronous only in
+// reference-order mode.
+static int pack_resident(const sageicp_map *m, const EgressArgs *e, hipStream_t s) {
     const uint64_t total = m->ctr.total_points;
-    *n_out = total;
-    const uint64_t want = out ? std::min(cap, total) : 0;
-    if (!want) return SAGEICP_OK;
     int rc = reserve_update_scratch(m, 0, static_cast<size_t>(m->ctr.blocks_hi) + 1);
     if (rc) return rc;
-    if (total > m->d_pc.capacity()) HIPCHK(m->d_pc.reserve(total + total / 4 + 1024));
+    if (!e && total > m->d_pc.capacity()) HIPCHK(m->d_pc.reserve(total + total / 4 + 1024));
     const DevMap dm = dev_map(m);
     if (m->host.track_order) {
         // reference-order mode: the voxels in the bucket order of the host's array (VoxelHashMap.cpp:132-142), their points
@@ -431,13 +430,32 @@ static int pointcloud_from_device(const sageicp_map *m, double *out, uint64_t ca
         if ((rc = reserve_update_scratch(m, 0, list.size() + 1))) return rc;
         uint32_t *d_list = reinterpret_cast<uint32_t *>(m->up.far_list.data());        // ([nb] uint2: room for the list)
         if (!list.empty()) HIPCHK(hipMemcpyAsync(d_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIPCHK(map_pointcloud_listed(dm, d_list, static_cast<uint32_t>(list.size()), m->up.far_flag.data(), m->up.far_sel.data(), m->up.temp.data(),
-                                     m->up.temp.capacity(), m->d_pc.data(), s));
+        if (e)
+            HIPCHK(map_pointcloud_listed(dm, d_list, static_cast<uint32_t>(list.size()), m->up.far_flag.data(), m->up.far_sel.data(),
+                                         m->up.temp.data(), m->up.temp.capacity(), *e, s));
+        else
+            HIPCHK(map_pointcloud_listed(dm, d_list, static_cast<uint32_t>(list.size()), m->up.far_flag.data(), m->up.far_sel.data(),
+                                         m->up.temp.data(), m->up.temp.capacity(), m->d_pc.data(), s));
         HIPCHK(hipStreamSynchronize(s));                                         // (`list` is pageable and leaves scope)
+    } else if (e) {
+        HIPCHK(map_pointcloud_device(dm, m->ctr.blocks_hi, m->up.far_flag.data(), m->up.far_sel.data(), m->up.temp.data(),
+                                     m->up.temp.capacity(), *e, s));
     } else {
         HIPCHK(map_pointcloud_device(dm, m->ctr.blocks_hi, m->up.far_flag.data(), m->up.far_sel.data(), m->up.temp.data(),
                                      m->up.temp.capacity(), m->d_pc.data(), s));
     }
+    return SAGEICP_OK;
+}
+
+static int pointcloud_from_device(const sageicp_map *m, double *out, uint64_t cap, uint64_t *n_out) {
+    HIPCHK(hipSetDevice(m->device));
+    hipStream_t s = m->sc.stream;
+    const uint64_t total = m->ctr.total_points;
+    *n_out = total;
+    const uint64_t want = out ? std::min(cap, total) : 0;
+    if (!want) return SAGEICP_OK;
+    int rc = pack_resident(m, nullptr, s);
+    if (rc) return rc;
     // The destination is the caller's pageable buffer, and under the reference's interface a FRESH
     // one every call (`std::vector<Eigen::Vector4d> Pointcloud()` returns by value: tens of MB
     // straight from mmap).  The runtime's staged copy moves 63 MB in 1.2 ms into pages that exist —
@@ -772,6 +790,112 @@ sageicp_frame *sageicp_frame_from_device(const sageicp_map *m, const sageicp_dev
     return f;
 }
 
+// ---- outputs into the caller's device memory (egress.hip, egress.h) -------------------------------------------------
+// Everything about a destination that can be known before the stream is touched or anything launched: the layout
+// first (no device needed), then where the memory of its `cap` rows lives, then the stream.
+static int check_device_points(const sageicp_device_points *d, void *stream, int device) {
+    if (!d) return fail(SAGEICP_ERR_INVALID, "null destination");
+    if (d->cap && !d->xyz) return fail(SAGEICP_ERR_INVALID, "device points: xyz is NULL");
+    const size_t ex = d->xyz_dtype == SAGEICP_DTYPE_FLOAT32 || d->xyz_dtype == SAGEICP_DTYPE_FLOAT64 ? dtype_bytes(d->xyz_dtype) : 0;
+    if (!ex) return fail(SAGEICP_ERR_INVALID, "device points: xyz_dtype must be SAGEICP_DTYPE_FLOAT32 or _FLOAT64");
+    const uint64_t cols = d->label ? 3 : 4;
+    if (d->xyz_stride < cols * ex || d->xyz_stride % ex)
+        return fail(SAGEICP_ERR_INVALID, d->label ? "device points: xyz_stride must be a multiple of the element size and "
+                                                    "at least 3 elements"
+                                                  : "device points: xyz_stride must be a multiple of the element size and "
+                                                    "at least 4 elements (the label is column 3)");
+    const size_t el = d->label ? dtype_bytes(d->label_dtype) : 0;
+    if (d->label) {
+        if (!el) return fail(SAGEICP_ERR_INVALID, "device points: label_dtype must be SAGEICP_DTYPE_UINT8, _INT32, _INT64, "
+                                                  "_FLOAT32 or _FLOAT64");
+        if (d->label_stride < el || d->label_stride % el)
+            return fail(SAGEICP_ERR_INVALID, "device points: label_stride must be a positive multiple of the label's size");
+    }
+    if (!d->cap) return SAGEICP_OK;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
+    int rc = check_extent(d->xyz, (d->cap - 1) * d->xyz_stride + cols * ex, device, "device points: xyz");
+    if (!rc && d->label) rc = check_extent(d->label, (d->cap - 1) * d->label_stride + el, device, "device points: label");
+    if (rc) return rc;
+    if (stream) {
+        int sd = -1;
+        const hipError_t e = hipStreamGetDevice(static_cast<hipStream_t>(stream), &sd);
+        (void)hipGetLastError();
+        if (e != hipSuccess || sd != device)
+            return fail(SAGEICP_ERR_INVALID, "stream is not a stream of the handle's device");
+    }
+    return SAGEICP_OK;
+}
+
+static EgressArgs egress_args(const sageicp_device_points &d, int *flags) {
+    EgressArgs a{};
+    a.xyz = static_cast<unsigned char *>(d.xyz);
+    a.xyz_stride = d.xyz_stride;
+    a.xyz_dtype = d.xyz_dtype;
+    a.label = static_cast<unsigned char *>(d.label);
+    a.label_stride = d.label_stride;
+    a.label_dtype = d.label_dtype;
+    a.cap = d.cap;
+    a.flags = flags;
+    return a;
+}
+
+// after the writes enqueued on s: wait for them, then read the label-range flag they may have raised
+static int egress_finish(const int *d_flag, hipStream_t s) {
+    int flags = 0;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&flags, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (flags & kEgressLabelRange)
+        return fail(SAGEICP_ERR_INVALID, "a label does not fit the destination's label type (static_cast<int64_t>(label) "
+                                         "out of its range)");
+    return SAGEICP_OK;
+}
+
+int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_points *dst, void *stream, uint64_t *n_out) {
+    if (!m || !n_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    int rc = check_device_points(dst, stream, m->device);
+    if (rc) return rc;
+    const uint64_t n = sageicp_map_size(m);
+    *n_out = n;
+    const uint64_t want = std::min(dst->cap, n);
+    if (!want) return SAGEICP_OK;
+    if ((rc = m->sc.init(m->device))) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    const hipStream_t s = m->sc.stream;
+    if (!m->d_egress_flag.data()) HIPCHK(m->d_egress_flag.reserve(1));
+    if (!m->ev_caller) HIPCHK(hipEventCreateWithFlags(&m->ev_caller, hipEventDisableTiming));
+    // the map's stream waits for the work the caller enqueued before this call (it may still use the destination)
+    HIPCHK(hipEventRecord(m->ev_caller, static_cast<hipStream_t>(stream)));
+    HIPCHK(hipStreamWaitEvent(s, m->ev_caller, 0));
+    HIPCHK(hipMemsetAsync(m->d_egress_flag.data(), 0, sizeof(int), s));
+    const EgressArgs e = egress_args(*dst, m->d_egress_flag.data());
+    std::vector<double> staged;
+    auto body = [&]() -> int {
+        if (m->on_device && !env_int("SAGEICP_EGRESS_TWO_PASS", 0))
+            return pack_resident(m, &e, s);             // the gather writes the caller's layout itself
+        // two passes: the rows packed into d_pc (from the HBM copy, or staged from the host copy), then k_egress
+        if (m->on_device) {
+            int r = pack_resident(m, nullptr, s);
+            if (r) return r;
+        } else {
+            staged.resize(4 * n);
+            m->host.pointcloud(staged.data(), n);
+            if (n > m->d_pc.capacity()) HIPCHK(m->d_pc.reserve(n + n / 4 + 1024));
+            HIPCHK(hipMemcpyAsync(m->d_pc.data(), staged.data(), n * sizeof(Point4), hipMemcpyHostToDevice, s));
+        }
+        launch_egress(e, m->d_pc.data(), want, s);
+        return SAGEICP_OK;
+    };
+    rc = body();
+    if (rc) {
+        (void)hipStreamSynchronize(s);                  // (`staged` leaves scope)
+        return rc;
+    }
+    return egress_finish(m->d_egress_flag.data(), s);
+}
+
 // RegisterFrame of n points already on `device` (an uploaded frame, or the pipeline's source cloud)
 static int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
                              double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
@@ -1097,6 +1221,12 @@ struct sageicp_pipeline {
     sageicp::DynFilterConfig dyn_cfg;
     // sageConfig::deskew (sageicp_pipeline_set_deskew): off by default; read by the timestamped entry only
     bool deskew_on = false;
+    // the source cloud of the last successful register call (sageicp_pipeline_source*): src_n rows of
+    // prep[src_buf].d_src, 0 when there is none.  Nothing writes that buffer before the next register call: the
+    // prefetch worker fills the other one, and the registration reads d_src without reordering it.
+    uint64_t src_n = 0;
+    int src_buf = 0;
+    mutable DevBuf<int> d_egress_flag;
     explicit sageicp_pipeline(const sageicp_pipeline_config &c) : impl(c), device(c.device) {}
     ~sageicp_pipeline() {
         if (worker.joinable()) worker.join();
@@ -1210,17 +1340,26 @@ static int pipeline_register(sageicp_pipeline *p, const double *frame, const dou
     const int rc = p->impl.register_frame(frame, n, timestamps != nullptr, pose_out, icp_s, total_s, n_source, stats,
                                           Backend{p, timestamps, dev});
     p->announced = false;       // an announcement is consumed by this call, also when it failed or the frame was empty
+    p->src_buf = p->cur;
+    p->src_n = rc == SAGEICP_OK ? p->prep[p->cur].kept_levels[1] : 0;
     return rc;
+}
+// Every register entry drops the last source first: a call that is refused before it reaches pipeline_register (a bad
+// argument, a device frame or timestamps that fail their checks) leaves 0 rows, as one that fails later does.
+static void drop_source(sageicp_pipeline *p) {
+    if (p) p->src_n = 0;
 }
 int sageicp_pipeline_register_frame(sageicp_pipeline *p, const double *frame, uint64_t n,
                                     double pose_out[7], double *icp_s, double *total_s,
                                     uint64_t *n_source, sageicp_stats *stats) {
+    drop_source(p);
     if (!p || !pose_out || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
     return pipeline_register(p, frame, nullptr, n, pose_out, icp_s, total_s, n_source, stats);
 }
 int sageicp_pipeline_register_frame_timestamps(sageicp_pipeline *p, const double *frame, const double *timestamps,
                                                uint64_t n, double pose_out[7], double *icp_s, double *total_s,
                                                uint64_t *n_source, sageicp_stats *stats) {
+    drop_source(p);
     if (!p || !pose_out || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
     if (!p->deskew_on)          // config_.deskew false: the frame passes through, the timestamps are not read
         return pipeline_register(p, frame, nullptr, n, pose_out, icp_s, total_s, n_source, stats);
@@ -1234,6 +1373,7 @@ int sageicp_pipeline_register_frame_timestamps(sageicp_pipeline *p, const double
 int sageicp_pipeline_register_frame_device(sageicp_pipeline *p, const sageicp_device_frame *frame,
                                            const double *timestamps, void *stream, double pose_out[7], double *icp_s,
                                            double *total_s, uint64_t *n_source, sageicp_stats *stats) {
+    drop_source(p);
     if (!p || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
     // without timestamps the one-argument RegisterFrame (never deskews); with deskew off they are not read (not even
     // checked), as in sageicp_pipeline_register_frame_timestamps
@@ -1242,6 +1382,32 @@ int sageicp_pipeline_register_frame_device(sageicp_pipeline *p, const sageicp_de
     if (rc) return rc;
     const sageicp::DeviceSource dev{frame, ts, static_cast<hipStream_t>(stream)};
     return pipeline_register(p, nullptr, ts, frame->n, pose_out, icp_s, total_s, n_source, stats, &dev);
+}
+int sageicp_pipeline_source(const sageicp_pipeline *p, double *out, uint64_t cap, uint64_t *n_out) {
+    if (!p || !n_out || (cap && !out)) return fail(SAGEICP_ERR_INVALID, "null argument");
+    *n_out = p->src_n;
+    const uint64_t want = std::min(cap, p->src_n);
+    if (!want) return SAGEICP_OK;
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipMemcpy(out, p->prep[p->src_buf].d_src.data(), want * sizeof(Point4), hipMemcpyDeviceToHost));
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_source_device(const sageicp_pipeline *p, const sageicp_device_points *dst, void *stream,
+                                   uint64_t *n_out) {
+    if (!p || !n_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    int rc = check_device_points(dst, stream, p->device);
+    if (rc) return rc;
+    *n_out = p->src_n;
+    const uint64_t want = std::min(dst->cap, p->src_n);
+    if (!want) return SAGEICP_OK;
+    HIPCHK(hipSetDevice(p->device));
+    if (!p->d_egress_flag.data()) HIPCHK(p->d_egress_flag.reserve(1));
+    // on the caller's stream, behind the work it enqueued before this call; synchronous: afterwards nothing of the
+    // library touches the destination
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(hipMemsetAsync(p->d_egress_flag.data(), 0, sizeof(int), s));
+    launch_egress(egress_args(*dst, p->d_egress_flag.data()), p->prep[p->src_buf].d_src.data(), want, s);
+    return egress_finish(p->d_egress_flag.data(), s);
 }
 int sageicp_pipeline_set_deskew(sageicp_pipeline *p, int enable) {
     if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
@@ -1308,6 +1474,7 @@ int sageicp_pipeline_dynamic_filter_info(const sageicp_pipeline *p, sageicp_dynf
 int sageicp_pipeline_reinitialize(sageicp_pipeline *p) {
     if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
     p->impl.reinitialize();
+    p->src_n = 0;
     return SAGEICP_OK;
 }
 uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p) { return p ? p->impl.poses.size() : 0; }

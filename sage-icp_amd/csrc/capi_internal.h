@@ -32,6 +32,7 @@
 #include "dyn_rules.h"
 #include "host_map.hpp"
 #include "kernels.h"
+#include "egress.h"
 #include "map_update.h"
 #include "metrics.hpp"
 #include "pipeline.hpp"
@@ -795,6 +796,10 @@ struct sageicp_map {
     mutable UpdateBuffers up;
     // Pointcloud() served from the HBM copy: the packed points before they cross PCIe
     mutable DevBuf<Point4> d_pc;
+    // sageicp_map_pointcloud_device: the label-range flag (egress.h) and the event that orders the caller's stream
+    // before the map's (created with the first call)
+    mutable DevBuf<int> d_egress_flag;
+    mutable hipEvent_t ev_caller = nullptr;
     size_t units_cap() const { return d_pts.capacity() / kUnitPoints; }       // units the point array holds
     size_t blocks_cap() const { return d_zeros.capacity(); }
     size_t cand_slots() const { return d_cand.capacity() ? d_cand.capacity() - 1 - kCandSlack : 0; }

@@ -11,6 +11,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "egress.h"
 #include "sageicp_types.h"
 
 namespace sageicp {
@@ -116,12 +117,17 @@ hipError_t map_evict_listed(const DevMap &M, const uint32_t *d_list, const uint3
 // `out`; counts / offsets: [n_list + 1] scratch.
 hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts, uint32_t *offsets,
                                  void *temp, size_t temp_bytes, Point4 *out, hipStream_t s);
+// ... straight into a caller's layout (egress.h): rows at and beyond out.cap are not written
+hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts, uint32_t *offsets,
+                                 void *temp, size_t temp_bytes, const EgressArgs &out, hipStream_t s);
 
 // Pointcloud() of the HBM copy: the live points of blocks [0, blocks_hi) packed into `out` in
 // block-pool order (what HostMap::pointcloud emits).  counts / offsets: [blocks_hi + 1] scratch;
 // offsets[blocks_hi] is the number of points written.
 hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
                                  void *temp, size_t temp_bytes, Point4 *out, hipStream_t s);
+hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
+                                 void *temp, size_t temp_bytes, const EgressArgs &out, hipStream_t s);
 
 // Re-insert every live voxel into a fresh (larger or tombstone-free) table.
 hipError_t map_rebuild_table(const DevMap &M, Slot *new_table, uint32_t new_mask,

@@ -22,6 +22,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include "egress.h"
 #include "map_update.h"
 
 namespace sageicp {
@@ -482,12 +483,14 @@ __global__ __launch_bounds__(256) void k_pc_counts_listed(DevMap M, const uint32
     }
     counts[j] = c;
 }
+// W: Point4Writer (packed rows) or an EgressWriter (the caller's layout, egress.h)
+template <typename W>
 __global__ __launch_bounds__(256) void k_pc_gather_listed(DevMap M, const uint32_t *list, uint32_t n_list, uint32_t span,
-                                                          const uint32_t *counts, const uint32_t *offsets, Point4 *out) {
+                                                          const uint32_t *counts, const uint32_t *offsets, W out) {
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
     const uint32_t q = static_cast<uint32_t>(i / span), j = static_cast<uint32_t>(i % span);
     if (q >= n_list || j >= counts[q]) return;
-    out[static_cast<size_t>(offsets[q]) + j] = M.pts[static_cast<size_t>(M.regions[list[q]] & 0x0FFFFFFFu) * kDevUnitPoints + j];
+    out(static_cast<size_t>(offsets[q]) + j, M.pts[static_cast<size_t>(M.regions[list[q]] & 0x0FFFFFFFu) * kDevUnitPoints + j]);
 }
 
 __global__ void k_far_after(MapCounters *ctr, const uint32_t *n_sel) {
@@ -528,15 +531,15 @@ __global__ __launch_bounds__(256) void k_pc_counts(DevMap M, uint32_t blocks_hi,
     counts[b] = c;                 // counts[blocks_hi] = 0: its scan entry is the total
 }
 // lane per (block, slot of the largest class): block b's live points, found through its region,
-// land at offsets[b] in block-pool order — the order HostMap::pointcloud emits (host_map.hpp)
+// land at offsets[b] in block-pool order — the order HostMap::pointcloud emits (host_map.hpp).  W: as k_pc_gather_listed
+template <typename W>
 __global__ __launch_bounds__(256) void k_pc_gather_regions(DevMap M, uint32_t blocks_hi, uint32_t span,
                                                            const uint32_t *counts, const uint32_t *offsets,
-                                                           Point4 *out) {
+                                                           W out) {
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
     const uint32_t b = static_cast<uint32_t>(i / span), j = static_cast<uint32_t>(i % span);
     if (b >= blocks_hi || j >= counts[b]) return;
-    out[static_cast<size_t>(offsets[b]) + j] =
-        M.pts[static_cast<size_t>(M.regions[b] & 0x0FFFFFFFu) * kDevUnitPoints + j];
+    out(static_cast<size_t>(offsets[b]) + j, M.pts[static_cast<size_t>(M.regions[b] & 0x0FFFFFFFu) * kDevUnitPoints + j]);
 }
 __global__ __launch_bounds__(256) void k_derive_block_of(DevMap M, uint32_t blocks_hi) {
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
@@ -548,6 +551,12 @@ __global__ void k_rebuild_after(MapCounters *ctr) {
     if (threadIdx.x || blockIdx.x) return;
     ctr->used_slots = ctr->num_voxels;
 }
+
+// the gather kernels' output: the library's packed rows, or the caller's layout
+template <typename F>
+void with_writer(Point4 *out, F &&f) { f(Point4Writer{out}); }
+template <typename F>
+void with_writer(const EgressArgs &out, F &&f) { with_egress_writer(out, f); }
 
 }  // namespace
 
@@ -649,8 +658,9 @@ hipError_t map_update_insert_find_far(const DevMap &M, const UpdatePolicy &P, co
     return hipGetLastError();
 }
 
-hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts, uint32_t *offsets,
-                                 void *temp, size_t temp_bytes, Point4 *out, hipStream_t s) {
+template <typename Out>
+static hipError_t pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts,
+                                    uint32_t *offsets, void *temp, size_t temp_bytes, const Out &out, hipStream_t s) {
     if (n_list == 0) return hipSuccess;
     const int gb = static_cast<int>((n_list + 1u + 255u) / 256u);
     hipLaunchKernelGGL(k_pc_counts_listed, dim3(gb), dim3(256), 0, s, M, d_list, n_list, counts);
@@ -660,13 +670,24 @@ hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32
     if (e != hipSuccess) return e;
     const uint32_t span = static_cast<uint32_t>(M.cap);
     const uint64_t nslots = static_cast<uint64_t>(n_list) * span;
-    hipLaunchKernelGGL(k_pc_gather_listed, dim3(static_cast<unsigned>((nslots + 255) / 256)), dim3(256), 0, s, M,
-                       d_list, n_list, span, counts, offsets, out);
+    const dim3 grid(static_cast<unsigned>((nslots + 255) / 256));
+    with_writer(out, [&](auto w) {
+        hipLaunchKernelGGL(k_pc_gather_listed<decltype(w)>, grid, dim3(256), 0, s, M, d_list, n_list, span, counts, offsets, w);
+    });
     return hipGetLastError();
 }
-
-hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
+hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts, uint32_t *offsets,
                                  void *temp, size_t temp_bytes, Point4 *out, hipStream_t s) {
+    return pointcloud_listed(M, d_list, n_list, counts, offsets, temp, temp_bytes, out, s);
+}
+hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts, uint32_t *offsets,
+                                 void *temp, size_t temp_bytes, const EgressArgs &out, hipStream_t s) {
+    return pointcloud_listed(M, d_list, n_list, counts, offsets, temp, temp_bytes, out, s);
+}
+
+template <typename Out>
+static hipError_t pointcloud_regions(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
+                                     void *temp, size_t temp_bytes, const Out &out, hipStream_t s) {
     if (blocks_hi == 0) return hipSuccess;
     const int gb = static_cast<int>((blocks_hi + 1u + 255u) / 256u);
     hipLaunchKernelGGL(k_pc_counts, dim3(gb), dim3(256), 0, s, M, blocks_hi, counts);
@@ -676,9 +697,19 @@ hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *
     if (e != hipSuccess) return e;
     const uint32_t span = static_cast<uint32_t>(M.cap);
     const uint64_t nslots = static_cast<uint64_t>(blocks_hi) * span;
-    hipLaunchKernelGGL(k_pc_gather_regions, dim3(static_cast<unsigned>((nslots + 255) / 256)), dim3(256), 0, s, M,
-                       blocks_hi, span, counts, offsets, out);
+    const dim3 grid(static_cast<unsigned>((nslots + 255) / 256));
+    with_writer(out, [&](auto w) {
+        hipLaunchKernelGGL(k_pc_gather_regions<decltype(w)>, grid, dim3(256), 0, s, M, blocks_hi, span, counts, offsets, w);
+    });
     return hipGetLastError();
+}
+hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
+                                 void *temp, size_t temp_bytes, Point4 *out, hipStream_t s) {
+    return pointcloud_regions(M, blocks_hi, counts, offsets, temp, temp_bytes, out, s);
+}
+hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
+                                 void *temp, size_t temp_bytes, const EgressArgs &out, hipStream_t s) {
+    return pointcloud_regions(M, blocks_hi, counts, offsets, temp, temp_bytes, out, s);
 }
 
 hipError_t map_rebuild_table(const DevMap &M, Slot *new_table, uint32_t new_mask,
