@@ -62,7 +62,9 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * sageicp_pipeline_set_dynamic_vehicle_filter / sageicp_pipeline_dynamic_filter_info; then frames in device memory —
  * sageicp_device_frame, SAGEICP_DTYPE_*, sageicp_pipeline_register_frame_device, sageicp_frame_from_device; then outputs
  * in device memory — sageicp_device_points, sageicp_pipeline_source, sageicp_pipeline_source_device,
- * sageicp_map_pointcloud_device (additions only: no existing struct or entry changed). */
+ * sageicp_map_pointcloud_device; then key-frame selection — sageicp_occupancy_params, sageicp_key_frame_info,
+ * sageicp_pipeline_set_key_frames, sageicp_pipeline_key_frame_reset / _info / _grid / _grid_device,
+ * sageicp_occupancy_grid, sageicp_occupancy_grid_device (additions only: no existing struct or entry changed). */
 #define SAGEICP_ABI_VERSION 4
 
 /* Filled by sageicp_register_frame*.  Times are microseconds. */
@@ -528,6 +530,62 @@ int sageicp_pipeline_reinitialize(sageicp_pipeline *p);          /* pipeline/sag
 uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p);  /* poses().size() */
 int sageicp_pipeline_pose(const sageicp_pipeline *p, uint64_t index, double pose_out[7]);
 const sageicp_map *sageicp_pipeline_local_map(const sageicp_pipeline *p);   /* LocalMap() */
+
+/* ---- key-frame selection by occupancy overlap (keyframe.hip) ---------------------------------------------------------
+ * The odometry node's key-frame choice (ros/ros2/OdometryServer.cpp:222-243, ros/ros2/Utils.hpp:221-260), run on the
+ * device.  A grid is a bird's-eye occupancy of H rows (y) by W columns (x), cell (y, x) at byte y * W + x of a grid
+ * written out: a point is skipped unless lo <= v <= hi on all three axes; it sets the cell
+ *     occ_x = (int)((x + bounds[0][1]) / ((bounds[0][1] - bounds[0][0]) / W)),
+ *     occ_y = (int)((y + bounds[1][1]) / ((bounds[1][1] - bounds[1][0]) / H))
+ * when 0 <= occ_x < W and 0 <= occ_y < H — the UPPER bound is the offset, as in the reference, and the cast truncates
+ * toward zero (fp64, a true division; the range is tested on the double before the cast).
+ * Refused (SAGEICP_ERR_INVALID): bounds that are not finite or lo >= hi on an axis, occ_h or occ_w outside [1, 4096],
+ * an overlap_th that is not finite. */
+typedef struct sageicp_occupancy_params {
+    double bounds[3][2];        /* (lo, hi) of x, y, z; key_frame_bounds of the launch files */
+    int32_t occ_h, occ_w;       /* key_frame_occ_size: rows (y), columns (x) */
+    double overlap_th;          /* key_frame_overlap: a frame whose overlap is below becomes the key frame */
+} sageicp_occupancy_params;
+typedef struct sageicp_key_frame_info {
+    int32_t enabled;            /* selection is on */
+    int32_t is_key_frame;       /* the last frame registered became the key frame */
+    double overlap;             /* |key & cur| / |key| of the last frame; NaN on a first key frame or when |key| = 0 */
+    uint64_t key_frame_index;   /* the key frame's index in the poses (valid while key_frames > 0) */
+    uint64_t key_frames;        /* key frames taken since selection was switched on or reset */
+    uint64_t key_occupied;      /* |key|: occupied cells of the key grid the last frame was compared with (0 on a first) */
+    uint64_t intersect;         /* |key & cur| of that comparison */
+    double key_pose[7];         /* the key frame's pose (identity while there is none) */
+} sageicp_key_frame_info;
+/* Key-frame selection for every frame the pipeline registers (host rows, timestamps, device frames, prefetched frames),
+ * after its pose is pushed and outside the times the register calls report.  The input is the RAW frame as handed in
+ * (before deskew, the dynamic filter and the crop); with no key frame yet the frame becomes the key frame, otherwise
+ * it is drawn under key_pose^-1 * pose and becomes the key frame when its overlap with the key grid is below
+ * overlap_th (the stored grid is the frame's own, untransformed).  While it is on, a frame with a coordinate that is
+ * not finite is refused whole (no pose pushed); a register call that fails changes nothing of the selection.  Off by
+ * default; off, nothing of it runs.  Switching it on (or setting new params) starts from "no key frame"; params may
+ * be NULL when enable == 0.  sageicp_pipeline_reinitialize keeps the state (the node's ReinitService does); _reset
+ * clears it. */
+int sageicp_pipeline_set_key_frames(sageicp_pipeline *p, int enable, const sageicp_occupancy_params *params);
+int sageicp_pipeline_key_frame_reset(sageicp_pipeline *p);
+int sageicp_pipeline_key_frame_info(const sageicp_pipeline *p, sageicp_key_frame_info *info);
+/* the key grid as occ_h * occ_w bytes (0 / 1; zeros while there is no key frame); cap: bytes at out, at least
+ * occ_h * occ_w.  SAGEICP_ERR_INVALID while selection is off. */
+int sageicp_pipeline_key_frame_grid(const sageicp_pipeline *p, uint8_t *out, uint64_t cap);
+/* the same bytes into the caller's device memory, with sageicp_device_points' checks and stream rules (the extent must
+ * be device memory of the pipeline's device; ordered behind the work on `stream`; synchronous) */
+int sageicp_pipeline_key_frame_grid_device(const sageicp_pipeline *p, uint8_t *out, uint64_t cap,
+                                           void *stream /* hipStream_t; NULL = null stream */);
+/* The grid of n host rows, moved by `pose` first (NULL: identity; the point action of sageicp_transform_points, bit for
+ * bit), into occ_h * occ_w host bytes; params->overlap_th is checked but not used.  A coordinate or a pose that is not
+ * finite refuses the call. */
+int sageicp_occupancy_grid(const double *xyzl, uint64_t n, const double pose[7] /* NULL = identity */,
+                           const sageicp_occupancy_params *params, uint8_t *grid_out, int device);
+/* the same of a frame in device memory (sageicp_device_frame, read through the same conversion as
+ * sageicp_pipeline_register_frame_device, on the device its memory lives on and behind the work on `stream`); the grid
+ * goes to host memory.  Synchronous. */
+int sageicp_occupancy_grid_device(const sageicp_device_frame *frame, const double pose[7] /* NULL = identity */,
+                                  const sageicp_occupancy_params *params, uint8_t *grid_out,
+                                  void *stream /* hipStream_t; NULL = null stream */);
 
 /* ---- KITTI trajectory metrics: sage_icp::metrics (metrics/Metrics.hpp:33-37) ----------------------
  * Host-only (the reference's are CPU code too).  Poses are 4x4 homogeneous matrices, ROW-major

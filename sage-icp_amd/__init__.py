@@ -120,6 +120,43 @@ class DevicePoints(C.Structure):
                 ("label", C.c_void_p), ("label_stride", C.c_uint64), ("cap", C.c_uint64)]
 
 
+class OccupancyParams(C.Structure):
+    """sageicp_occupancy_params: the bird's-eye grid of key-frame selection (bounds of x, y, z; H rows, W columns)"""
+    _fields_ = [("bounds", (C.c_double * 2) * 3), ("occ_h", C.c_int32), ("occ_w", C.c_int32), ("overlap_th", C.c_double)]
+
+
+class KeyFrameInfo(C.Structure):
+    """sageicp_key_frame_info: what key-frame selection decided for the last frame registered"""
+    _fields_ = [("enabled", C.c_int32), ("is_key_frame", C.c_int32), ("overlap", C.c_double),
+                ("key_frame_index", C.c_uint64), ("key_frames", C.c_uint64), ("key_occupied", C.c_uint64),
+                ("intersect", C.c_uint64), ("key_pose", C.c_double * 7)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "key_pose"}
+        d["enabled"], d["is_key_frame"] = bool(self.enabled), bool(self.is_key_frame)
+        d["key_pose"] = np.array(self.key_pose[:], dtype=np.float64)
+        return d
+
+
+# the key-frame parameters of ros/launch/odometry*.launch.py (key_frame_bounds, key_frame_occ_size, key_frame_overlap)
+KEY_FRAME_BOUNDS = ((-51.2, 51.2), (-51.2, 51.2), (-4.0, 2.4))
+KEY_FRAME_OCC_SIZE = (128, 128)
+KEY_FRAME_OVERLAP = 0.5
+
+
+def occupancy_params(bounds=KEY_FRAME_BOUNDS, occ_size=KEY_FRAME_OCC_SIZE, overlap=KEY_FRAME_OVERLAP):
+    """OccupancyParams from the launch files' form: bounds ((x_lo, x_hi), (y_lo, y_hi), (z_lo, z_hi)), occ_size (H, W)"""
+    b = [[float(v) for v in ax] for ax in bounds]
+    if len(b) != 3 or any(len(ax) != 2 for ax in b):
+        raise ValueError("bounds are ((x_lo, x_hi), (y_lo, y_hi), (z_lo, z_hi))")
+    h, w = (int(v) for v in occ_size)
+    p = OccupancyParams()
+    for a in range(3):
+        p.bounds[a][0], p.bounds[a][1] = b[a]
+    p.occ_h, p.occ_w, p.overlap_th = h, w, float(overlap)
+    return p
+
+
 # the SemanticKITTI parameter sets of ros/launch/odometry*.launch.py
 KITTI_VOXEL_LABELS = [[40, 44, 48, 49], [50, 51, 52], [70, 72], [60, 71, 80, 81, 99], [0],
                       [10, 11, 13, 15, 16, 18, 20]]
@@ -235,6 +272,14 @@ _SIGNATURES = [
     ("sageicp_pipeline_source", C.c_int, [C.c_void_p, _dp, C.c_uint64, _u64p]),
     ("sageicp_pipeline_source_device", C.c_int, [C.c_void_p, C.POINTER(DevicePoints), C.c_void_p, _u64p]),
     ("sageicp_map_pointcloud_device", C.c_int, [C.c_void_p, C.POINTER(DevicePoints), C.c_void_p, _u64p]),
+    ("sageicp_pipeline_set_key_frames", C.c_int, [C.c_void_p, C.c_int, C.POINTER(OccupancyParams)]),
+    ("sageicp_pipeline_key_frame_reset", C.c_int, [C.c_void_p]),
+    ("sageicp_pipeline_key_frame_info", C.c_int, [C.c_void_p, C.POINTER(KeyFrameInfo)]),
+    ("sageicp_pipeline_key_frame_grid", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    ("sageicp_pipeline_key_frame_grid_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("sageicp_occupancy_grid", C.c_int, [_dp, C.c_uint64, _dp, C.POINTER(OccupancyParams), C.c_void_p, C.c_int]),
+    ("sageicp_occupancy_grid_device", C.c_int,
+     [C.POINTER(DeviceFrame), _dp, C.POINTER(OccupancyParams), C.c_void_p, C.c_void_p]),
     ("sageicp_pipeline_create", C.c_void_p, [C.POINTER(PipelineConfig)]),
     ("sageicp_pipeline_destroy", None, [C.c_void_p]),
     ("sageicp_pipeline_register_frame", C.c_int,
@@ -733,6 +778,31 @@ def transform_points(pose, pts, device=0):
     return out
 
 
+def occupancy_grid(frame, bounds=KEY_FRAME_BOUNDS, occ_size=KEY_FRAME_OCC_SIZE, pose=None, device=0, labels=None):
+    """The key-frame selection's bird's-eye grid of a frame (EigenToGridMap, ros/ros2/Utils.hpp:221-242), moved by
+    `pose` first if given: (H, W) uint8 numpy, 0 / 1.  `frame` is numpy (n, 4) rows (sageicp_occupancy_grid, on GPU
+    `device`) or a torch tensor on a GPU in the layouts RegisterFrame takes (sageicp_occupancy_grid_device, on the
+    tensor's GPU; `labels` as there)."""
+    params = occupancy_params(bounds, occ_size, 0.0)
+    out = np.zeros((params.occ_h, params.occ_w), dtype=np.uint8)
+    pp = None
+    if pose is not None:
+        pose_a, pp = _d(pose)
+        if pose_a.size != 7:
+            raise ValueError("a pose is (qx, qy, qz, qw, tx, ty, tz)")
+    if _is_device_tensor(frame):
+        f, stream = _device_frame(frame, labels, frame.device.index)
+        _check(lib().sageicp_occupancy_grid_device(C.byref(f), pp, C.byref(params), out.ctypes.data_as(C.c_void_p),
+                                                   stream))
+        return out
+    if labels is not None:
+        raise ValueError("labels= is for a frame that is a torch tensor on a GPU")
+    pts, fp = _d(frame)
+    _check(lib().sageicp_occupancy_grid(fp, pts.reshape(-1, 4).shape[0], pp, C.byref(params),
+                                        out.ctypes.data_as(C.c_void_p), device))
+    return out
+
+
 def align_clouds(src, tgt, kernel, device=0):
     src, sp = _d(src)
     tgt, gp = _d(tgt)
@@ -779,6 +849,44 @@ class SageICP:
         lm = (C.c_int * max(len(landmark_labels), 1))(*landmark_labels)
         _check(lib().sageicp_pipeline_set_dynamic_vehicle_filter(self._h, 1 if enable else 0, dy_th, voxid, lm,
                                                                  len(landmark_labels)))
+
+    def set_key_frames(self, enable=True, bounds=KEY_FRAME_BOUNDS, occ_size=KEY_FRAME_OCC_SIZE, overlap=KEY_FRAME_OVERLAP):
+        """Key-frame selection by occupancy overlap for every frame registered (sageicp_pipeline_set_key_frames; the
+        odometry node's publish_key_frame block): bounds ((x_lo, x_hi), (y_lo, y_hi), (z_lo, z_hi)), occ_size (H, W),
+        overlap the key_frame_overlap threshold — the launch files' values by default.  Starts from "no key frame";
+        drops a prepared frame."""
+        params = occupancy_params(bounds, occ_size, overlap) if enable else None
+        _check(lib().sageicp_pipeline_set_key_frames(self._h, 1 if enable else 0,
+                                                     C.byref(params) if params is not None else None))
+        self._occ_size = (params.occ_h, params.occ_w) if enable else None
+
+    def key_frame_info(self):
+        """dict: enabled, is_key_frame (of the last frame), overlap (NaN on a first key frame or an empty key grid),
+        key_frame_index (into poses()), key_frames (since set_key_frames / key_frame_reset), key_occupied, intersect,
+        key_pose[7]"""
+        info = KeyFrameInfo()
+        _check(lib().sageicp_pipeline_key_frame_info(self._h, C.byref(info)))
+        return info.as_dict()
+
+    def key_frame_reset(self):
+        """back to "no key frame" (reinitialize() keeps the key frame, as the node's ReinitService does)"""
+        _check(lib().sageicp_pipeline_key_frame_reset(self._h))
+
+    def key_frame_grid(self, device=False):
+        """the key frame's grid, (H, W) uint8 (0 / 1; zeros while there is none): numpy, or with device=True a torch
+        tensor on the pipeline's GPU"""
+        h, w = getattr(self, "_occ_size", None) or (0, 0)
+        if not device:
+            out = np.zeros((h, w), dtype=np.uint8)
+            _check(lib().sageicp_pipeline_key_frame_grid(self._h, out.ctypes.data_as(C.c_void_p), out.size))
+            return out
+        import torch
+        _check_one_hip_runtime()
+        dev = torch.device("cuda", self.config.device)
+        out = torch.empty((h, w), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib().sageicp_pipeline_key_frame_grid_device(self._h, out.data_ptr() or None, out.numel(), stream))
+        return out
 
     def dynamic_filter_info(self):
         """dict: what the filter did to the last frame registered (zeros when it was off)"""

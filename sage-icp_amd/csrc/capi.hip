@@ -1227,6 +1227,29 @@ struct sageicp_pipeline {
     uint64_t src_n = 0;
     int src_buf = 0;
     mutable DevBuf<int> d_egress_flag;
+    // key-frame selection (sageicp_pipeline_set_key_frames, keyframe.hip): off by default.  The key grid lives on the
+    // device (d_key); the host holds the key pose and what the last frame's step decided.
+    struct KeyFrames {
+        bool on = false;
+        sageicp_occupancy_params prm{};
+        sageicp::OccGrid g{};
+        bool has_key = false;
+        sageicp::Pose7 key_pose;
+        sageicp_key_frame_info info{};
+        DevBuf<uint32_t> d_key, d_cand, d_cur;     // bitmaps (allocated with the first frame)
+        DevBuf<sageicp::OccDecision> d_dec;
+        PinnedBuf<sageicp::OccDecision> h_dec;
+        // "no key frame"
+        void clear() {
+            has_key = false;
+            key_pose = sageicp::Pose7();
+            info = sageicp_key_frame_info{};
+            info.enabled = on ? 1 : 0;
+            info.overlap = std::numeric_limits<double>::quiet_NaN();
+            for (int i = 0; i < 7; ++i) info.key_pose[i] = key_pose.v[i];
+        }
+        KeyFrames() { clear(); }
+    } kf;
     explicit sageicp_pipeline(const sageicp_pipeline_config &c) : impl(c), device(c.device) {}
     ~sageicp_pipeline() {
         if (worker.joinable()) worker.join();
@@ -1246,6 +1269,7 @@ struct sageicp_pipeline {
         // level 0 (frame_downsample: it goes into the map, AddPoints depends on arrival order)
         // keeps the reference's emission order; level 1 (the registered source) does not need it
         pr.arrival_order_levels = env_int("SAGEICP_SOURCE_REFERENCE_ORDER", 0) ? 0u : 2u;
+        pr.keep_raw = kf.on;
         return pr.run(f, m, impl.max_range_(), impl.min_range_(), impl.label_max_range_(),
                       static_cast<int>(counts.size()), counts.data(), labels.data(), vs.data(),
                       crop, scales, 2, res, false, dyn_on ? &dyn_cfg : nullptr, deskew, dev);
@@ -1265,6 +1289,91 @@ sageicp_pipeline *sageicp_pipeline_create(const sageicp_pipeline_config *c) {
     return p;
 }
 void sageicp_pipeline_destroy(sageicp_pipeline *p) { delete p; }
+// ---- key-frame selection (keyframe.hip) ----------------------------------------------------------------------------
+// the grid of validated params (include/sageicp.h: what is refused)
+static int occ_grid_from(const sageicp_occupancy_params *prm, OccGrid &g) {
+    if (!prm) return fail(SAGEICP_ERR_INVALID, "null occupancy params");
+    for (int a = 0; a < 3; ++a) {
+        const double lo = prm->bounds[a][0], hi = prm->bounds[a][1];
+        if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(SAGEICP_ERR_INVALID, "occupancy bounds are not finite");
+        if (!(lo < hi)) return fail(SAGEICP_ERR_INVALID, "occupancy bounds: lo >= hi on an axis");
+        g.lo[a] = lo;
+        g.hi[a] = hi;
+    }
+    if (prm->occ_h < 1 || prm->occ_h > kOccMaxSide || prm->occ_w < 1 || prm->occ_w > kOccMaxSide)
+        return fail(SAGEICP_ERR_INVALID, "occupancy size: occ_h and occ_w must lie in [1, 4096]");
+    if (!std::isfinite(prm->overlap_th)) return fail(SAGEICP_ERR_INVALID, "the overlap threshold is not finite");
+    g.h = prm->occ_h;
+    g.w = prm->occ_w;
+    // Utils.hpp:224-225: (bounds[0][1] - bounds[0][0]) / occ_size[1], (bounds[1][1] - bounds[1][0]) / occ_size[0]
+    g.x_res = (g.hi[0] - g.lo[0]) / static_cast<double>(g.w);
+    g.y_res = (g.hi[1] - g.lo[1]) / static_cast<double>(g.h);
+    return SAGEICP_OK;
+}
+static OccTransform occ_transform(const double pose[7]) {
+    OccTransform t;
+    quat_to_mat(pose, t.R);                 // as fill_state does for k_tf
+    for (int i = 0; i < 3; ++i) t.t[i] = pose[4 + i];
+    return t;
+}
+// bits of a grid into H * W bytes
+static void occ_unpack_host(const uint32_t *bits, const OccGrid &g, uint8_t *out) {
+    const uint64_t cells = static_cast<uint64_t>(g.h) * g.w;
+    for (uint64_t i = 0; i < cells; ++i) out[i] = static_cast<uint8_t>((bits[i >> 5] >> (i & 31)) & 1u);
+}
+
+// OdometryServer.cpp:222-243 for the frame just registered (its raw rows in prep[cur].d_raw, its pose the last one
+// pushed): the identity grid (the candidate) and, with a key frame, the grid under key_pose^-1 * pose in one pass, then
+// the counts, the decision and the swap on the device.  The host state changes only once the decision is back.
+static int key_frame_step(sageicp_pipeline *p, uint64_t n) {
+    auto &k = p->kf;
+    sageicp::Prep &pr = p->prep[p->cur];
+    const hipStream_t s = pr.stream;
+    const uint32_t words = occ_words(k.g);
+    HIPCHK(hipSetDevice(p->device));
+    if (!k.d_key) {
+        HIPCHK(k.d_cand.reserve(words));
+        HIPCHK(k.d_cur.reserve(words));
+        HIPCHK(k.d_dec.reserve(1));
+        HIPCHK(k.h_dec.reserve(1));
+        HIPCHK(k.d_key.reserve(words));
+    }
+    const Pose7 pose = p->impl.poses.back();
+    OccTransform tf{};
+    if (k.has_key) {                         // sageICP::TransformToLastFrame, pipeline/sageICP.cpp:123-129
+        Pose7 inv, rel;
+        se3_inv(k.key_pose.v, inv.v);
+        se3_mul(inv.v, pose.v, rel.v);
+        tf = occ_transform(rel.v);
+    }
+    HIPCHK(hipMemsetAsync(k.d_cand.data(), 0, words * sizeof(uint32_t), s));
+    if (k.has_key) HIPCHK(hipMemsetAsync(k.d_cur.data(), 0, words * sizeof(uint32_t), s));
+    launch_occ_draw(pr.d_raw.data(), static_cast<int>(n), k.g, k.has_key ? &tf : nullptr, k.d_cand.data(), k.d_cur.data(),
+                    nullptr, env_int("SAGEICP_OCC_GLOBAL", 0) != 0, s);
+    HIPCHK(hipGetLastError());
+    launch_occ_decide(k.d_key.data(), k.d_cand.data(), k.d_cur.data(), words, k.has_key ? 0 : 1, k.prm.overlap_th,
+                      k.d_dec.data(), s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(k.h_dec.data(), k.d_dec.data(), sizeof(OccDecision), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const OccDecision d = *k.h_dec.data();
+    sageicp_key_frame_info &info = k.info;
+    info.is_key_frame = d.take;
+    info.key_occupied = k.has_key ? d.key : 0;
+    info.intersect = k.has_key ? d.inter : 0;
+    // Utils.hpp:257: static_cast<double>(overlap) / total — NaN for 0 / 0, as the device's decision saw it
+    info.overlap = k.has_key ? static_cast<double>(d.inter) / static_cast<double>(d.key)
+                             : std::numeric_limits<double>::quiet_NaN();
+    if (d.take) {
+        k.has_key = true;
+        k.key_pose = pose;
+        info.key_frame_index = p->impl.poses.size() - 1;
+        ++info.key_frames;
+        for (int i = 0; i < 7; ++i) info.key_pose[i] = pose.v[i];
+    }
+    return SAGEICP_OK;
+}
+
 // timestamps: the frame's (deskew on, all finite) or nullptr (the one-argument RegisterFrame).  dev: the frame is in the
 // caller's device memory (`frame` is not read; a non-null `timestamps` only marks deskew on, they are dev's)
 static int pipeline_register(sageicp_pipeline *p, const double *frame, const double *timestamps, uint64_t n,
@@ -1337,11 +1446,13 @@ static int pipeline_register(sageicp_pipeline *p, const double *frame, const dou
             return sageicp_map_update_pose(p->impl.map, fd.data(), n_fd, pose);
         }
     };
-    const int rc = p->impl.register_frame(frame, n, timestamps != nullptr, pose_out, icp_s, total_s, n_source, stats,
-                                          Backend{p, timestamps, dev});
+    int rc = p->impl.register_frame(frame, n, timestamps != nullptr, pose_out, icp_s, total_s, n_source, stats,
+                                    Backend{p, timestamps, dev});
     p->announced = false;       // an announcement is consumed by this call, also when it failed or the frame was empty
     p->src_buf = p->cur;
     p->src_n = rc == SAGEICP_OK ? p->prep[p->cur].kept_levels[1] : 0;
+    // the node's key-frame block runs after RegisterFrame has returned (outside the times reported above)
+    if (rc == SAGEICP_OK && p->kf.on) rc = key_frame_step(p, n);
     return rc;
 }
 // Every register entry drops the last source first: a call that is refused before it reaches pipeline_register (a bad
@@ -1485,6 +1596,179 @@ int sageicp_pipeline_pose(const sageicp_pipeline *p, uint64_t i, double out[7]) 
 }
 const sageicp_map *sageicp_pipeline_local_map(const sageicp_pipeline *p) {
     return p ? p->impl.map : nullptr;
+}
+
+int sageicp_pipeline_set_key_frames(sageicp_pipeline *p, int enable, const sageicp_occupancy_params *params) {
+    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
+    OccGrid g{};
+    if (enable) {
+        int rc = occ_grid_from(params, g);
+        if (rc) return rc;
+    }
+    if (p->worker.joinable()) p->worker.join();     // a frame prepared under the old setting is dropped
+    p->ready = false;
+    auto &k = p->kf;
+    k.on = enable != 0;
+    if (k.on) {
+        k.prm = *params;
+        k.g = g;
+    }
+    // the bitmaps are sized for the grid at the next frame; off, nothing of the selection stays allocated
+    k.d_key.reset();
+    k.d_cand.reset();
+    k.d_cur.reset();
+    if (!k.on) {
+        k.d_dec.reset();
+        k.h_dec.reset();
+        (void)hipSetDevice(p->device);
+        p->prep[0].d_raw.reset();
+        p->prep[1].d_raw.reset();
+    }
+    k.clear();
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_key_frame_reset(sageicp_pipeline *p) {
+    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
+    p->kf.clear();
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_key_frame_info(const sageicp_pipeline *p, sageicp_key_frame_info *info) {
+    if (!p || !info) return fail(SAGEICP_ERR_INVALID, "null argument");
+    *info = p->kf.info;
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_key_frame_grid(const sageicp_pipeline *p, uint8_t *out, uint64_t cap) {
+    if (!p || !out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    const auto &k = p->kf;
+    if (!k.on) return fail(SAGEICP_ERR_INVALID, "key-frame selection is off");
+    const uint64_t cells = static_cast<uint64_t>(k.g.h) * k.g.w;
+    if (cap < cells) return fail(SAGEICP_ERR_INVALID, "the key grid needs occ_h * occ_w bytes");
+    if (!k.has_key) {
+        std::memset(out, 0, cells);
+        return SAGEICP_OK;
+    }
+    std::vector<uint32_t> bits(occ_words(k.g));
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(hipMemcpy(bits.data(), k.d_key.data(), bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    occ_unpack_host(bits.data(), k.g, out);
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_key_frame_grid_device(const sageicp_pipeline *p, uint8_t *out, uint64_t cap, void *stream) {
+    if (!p || !out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    const auto &k = p->kf;
+    if (!k.on) return fail(SAGEICP_ERR_INVALID, "key-frame selection is off");
+    const uint64_t cells = static_cast<uint64_t>(k.g.h) * k.g.w;
+    if (cap < cells) return fail(SAGEICP_ERR_INVALID, "the key grid needs occ_h * occ_w bytes");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
+    int rc = check_extent(out, cells, p->device, "key-frame grid");
+    if (rc) return rc;
+    if (stream) {
+        int sd = -1;
+        const hipError_t e = hipStreamGetDevice(static_cast<hipStream_t>(stream), &sd);
+        (void)hipGetLastError();
+        if (e != hipSuccess || sd != p->device)
+            return fail(SAGEICP_ERR_INVALID, "stream is not a stream of the handle's device");
+    }
+    HIPCHK(hipSetDevice(p->device));
+    // on the caller's stream, behind the work it enqueued before this call; synchronous
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (k.has_key) launch_occ_unpack(k.d_key.data(), k.g, out, s);
+    else HIPCHK(hipMemsetAsync(out, 0, cells, s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    return SAGEICP_OK;
+}
+
+// the grid of n rows already on the device (d_pts), moved by pose (or not), into host bytes; a coordinate that is not
+// finite refuses the call.  On stream s, which is synchronised.
+static int occupancy_on_device(const Point4 *d_pts, uint64_t n, const double *pose, const OccGrid &g, uint8_t *grid_out,
+                               hipStream_t s) {
+    const uint32_t words = occ_words(g);
+    DevBuf<uint32_t> d_bits;
+    DevBuf<int> d_flag;
+    HIPCHK(d_bits.reserve(words));
+    HIPCHK(d_flag.reserve(1));
+    HIPCHK(hipMemsetAsync(d_bits.data(), 0, words * sizeof(uint32_t), s));
+    HIPCHK(hipMemsetAsync(d_flag.data(), 0, sizeof(int), s));
+    const OccTransform tf = pose ? occ_transform(pose) : OccTransform{};
+    launch_occ_draw(d_pts, static_cast<int>(n), g, pose ? &tf : nullptr, pose ? nullptr : d_bits.data(),
+                    pose ? d_bits.data() : nullptr, d_flag.data(), env_int("SAGEICP_OCC_GLOBAL", 0) != 0, s);
+    HIPCHK(hipGetLastError());
+    std::vector<uint32_t> bits(words);
+    int flag = 0;
+    HIPCHK(hipMemcpyAsync(bits.data(), d_bits.data(), words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&flag, d_flag.data(), sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (flag & kOccNonFinite) return fail(SAGEICP_ERR_INVALID, "a coordinate is not finite (NaN / Inf)");
+    occ_unpack_host(bits.data(), g, grid_out);
+    return SAGEICP_OK;
+}
+
+int sageicp_occupancy_grid(const double *xyzl, uint64_t n, const double pose[7], const sageicp_occupancy_params *params,
+                           uint8_t *grid_out, int device) {
+    if ((n && !xyzl) || !grid_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    OccGrid g{};
+    int rc = occ_grid_from(params, g);
+    if (rc) return rc;
+    if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
+    if (pose && !finite_n(pose, 7)) return fail(SAGEICP_ERR_INVALID, "the pose is not finite");
+    for (uint64_t i = 0; i < n; ++i)
+        if (!finite_n(xyzl + 4 * i, 3)) return fail(SAGEICP_ERR_INVALID, "a coordinate is not finite (NaN / Inf)");
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
+    if (device < 0 || device >= count) return fail(SAGEICP_ERR_INVALID, "device ordinal out of range");
+    if (n == 0) {
+        std::memset(grid_out, 0, static_cast<size_t>(g.h) * g.w);
+        return SAGEICP_OK;
+    }
+    DevBuf<Point4> d_p;
+    hipStream_t s = nullptr;
+    auto body = [&]() -> int {
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        HIPCHK(d_p.reserve(n));
+        HIPCHK(hipMemcpyAsync(d_p.data(), xyzl, n * sizeof(Point4), hipMemcpyHostToDevice, s));
+        return occupancy_on_device(d_p.data(), n, pose, g, grid_out, s);
+    };
+    rc = body();
+    if (s) (void)hipStreamSynchronize(s);
+    if (s) (void)hipStreamDestroy(s);
+    return rc;
+}
+int sageicp_occupancy_grid_device(const sageicp_device_frame *frame, const double pose[7],
+                                  const sageicp_occupancy_params *params, uint8_t *grid_out, void *stream) {
+    if (!frame || !grid_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    OccGrid g{};
+    int rc = occ_grid_from(params, g);
+    if (rc) return rc;
+    if (pose && !finite_n(pose, 7)) return fail(SAGEICP_ERR_INVALID, "the pose is not finite");
+    // the device the frame's memory lives on; memory that is not device memory is refused by check_device_frame
+    int device = 0;
+    if (frame->n && frame->xyz) {
+        hipPointerAttribute_t at{};
+        const hipError_t e = hipPointerGetAttributes(&at, frame->xyz);
+        (void)hipGetLastError();
+        if (e == hipSuccess && at.type == hipMemoryTypeDevice) device = at.device;
+    }
+    rc = check_device_frame(frame, nullptr, stream, device);
+    if (rc) return rc;
+    if (frame->n == 0) {
+        std::memset(grid_out, 0, static_cast<size_t>(g.h) * g.w);
+        return SAGEICP_OK;
+    }
+    HIPCHK(hipSetDevice(device));
+    // on the caller's stream, behind the work that wrote the frame; synchronous
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    DevBuf<Point4> d_p;
+    HIPCHK(d_p.reserve(frame->n));
+    launch_ingest(ingest_args(*frame), d_p.data(), s);
+    HIPCHK(hipGetLastError());
+    rc = occupancy_on_device(d_p.data(), frame->n, pose, g, grid_out, s);
+    (void)hipStreamSynchronize(s);          // (d_p leaves scope)
+    return rc;
 }
 
 // ---- KITTI trajectory metrics (metrics/Metrics.cpp) ------------------------------------------------

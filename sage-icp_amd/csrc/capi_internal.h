@@ -464,6 +464,10 @@ struct Prep {
     PinnedBuf<double> h_ts;
     DevBuf<double> d_ts;
     hipEvent_t ev_caller = nullptr;     // a device frame: orders the caller's stream before `stream` (created with the first)
+    // key-frame selection (keyframe.hip): the raw frame copied aside before deskew and the dynamic filter rewrite d_in
+    // in place — its coordinates checked — for the pass that follows the registration (allocated with the first use)
+    bool keep_raw = false;
+    DevBuf<Point4> d_raw;
 
     int init(int dev) {
         if (stream) return SAGEICP_OK;
@@ -584,9 +588,11 @@ struct Prep {
             HIPCHK(hipMemcpyAsync(d_glabels.data(), glabels, nlabels * sizeof(int), hipMemcpyHostToDevice, stream));
         }
         HIPCHK(hipMemsetAsync(d_overflow.data(), 0, sizeof(int), stream));
+        if (keep_raw && d_raw.capacity() < n) HIPCHK(d_raw.reserve(n + n / 4 + 1024));
         if (dev) {
             rc = ingest(*dev, n);
             if (rc) return rc;
+            if (keep_raw) launch_occ_keep(d_in.data(), d_raw.data(), static_cast<int>(n), d_overflow.data(), stream);
             if (deskew) {
                 launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream);
                 HIPCHK(hipGetLastError());
@@ -594,6 +600,7 @@ struct Prep {
         } else {
             std::memcpy(h_pin.data(), frame, n * sizeof(Point4));
             HIPCHK(hipMemcpyAsync(d_in.data(), h_pin.data(), n * sizeof(Point4), hipMemcpyHostToDevice, stream));
+            if (keep_raw) launch_occ_keep(d_in.data(), d_raw.data(), static_cast<int>(n), d_overflow.data(), stream);
             if (deskew) {
                 std::memcpy(h_ts.data(), deskew->timestamps, n * sizeof(double));
                 HIPCHK(hipMemcpyAsync(d_ts.data(), h_ts.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -711,6 +718,8 @@ struct Prep {
         }
         int ovf = 0;
         HIPCHK(hipMemcpy(&ovf, d_overflow.data(), sizeof(int), hipMemcpyDeviceToHost));
+        if (ovf & kOccNonFinite)
+            return fail(SAGEICP_ERR_INVALID, "key-frame selection is on and a coordinate is not finite (NaN / Inf)");
         if (ovf & 2) return fail(SAGEICP_ERR_INVALID, "a label (or, without the range crop, a coordinate) is not finite (NaN / Inf)");
         if (ovf) return fail(SAGEICP_ERR_CAPACITY, "voxel index beyond +-2^19 in VoxelDownsample");
         return SAGEICP_OK;

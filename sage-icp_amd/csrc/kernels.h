@@ -290,6 +290,43 @@ struct IngestArgs {
 };
 void launch_ingest(const IngestArgs &a, Point4 *out, hipStream_t s);
 
+// keyframe.hip: the bird's-eye occupancy grids of key-frame selection (ros/ros2/Utils.hpp:221-260, EigenToGridMap and
+// compute_occ_overlap; the node's block at OdometryServer.cpp:222-243).  A grid is a packed bitmap of H x W cells, row
+// major, cell (y, x) at bit y * W + x of 32-bit words (bit b of word b >> 5 at 1 << (b & 31)).
+constexpr int kOccNonFinite = 16;          // a coordinate that is not finite (Prep::d_overflow; ingest.hip's is 8)
+constexpr int kOccMaxSide = 4096;
+struct OccGrid {
+    double lo[3], hi[3];                // bounds of x, y, z (inclusive)
+    double x_res, y_res;                // (hi - lo) / W, (hi - lo) / H of x and y
+    int h, w;
+};
+struct OccTransform {
+    double R[9];                        // quat_to_mat of the pose, applied as k_tf does
+    double t[3];
+};
+// what the decision kernel leaves for the host
+struct OccDecision {
+    unsigned long long key;             // |key|
+    unsigned long long inter;           // |key & cur|
+    int take;                           // 1: the candidate became the key grid
+    int pad;
+};
+inline uint32_t occ_words(const OccGrid &g) { return static_cast<uint32_t>((static_cast<uint64_t>(g.h) * g.w + 31) / 32); }
+// rows [0, n) of `in` into `out` (the raw frame the key-frame pass reads after the registration); a coordinate that is
+// not finite raises kOccNonFinite in *flags
+void launch_occ_keep(const Point4 *in, Point4 *out, int n, int *flags, hipStream_t s);
+// One pass over n rows: the identity grid into `id` (if not null) and the grid of the rows under `tf` into `cur` (if
+// not null); both bitmaps must be zeroed first.  A coordinate that is not finite raises kOccNonFinite in *flags (if not
+// null) and sets no cell.  force_global: skip the LDS privatisation (the path two grids that do not fit take).
+void launch_occ_draw(const Point4 *in, int n, const OccGrid &g, const OccTransform *tf, uint32_t *id, uint32_t *cur,
+                     int *flags, bool force_global, hipStream_t s);
+// one workgroup: with force == 0, counts |key| and |key & cur| and takes the candidate if |key & cur| / |key| < th;
+// with force == 1 takes it without counting (the first key frame).  Taking copies `cand` over `key`.
+void launch_occ_decide(uint32_t *key, const uint32_t *cand, const uint32_t *cur, uint32_t words, int force, double th,
+                       OccDecision *out, hipStream_t s);
+// a bitmap into H * W bytes (0 / 1), cell (y, x) at y * W + x
+void launch_occ_unpack(const uint32_t *bits, const OccGrid &g, unsigned char *out, hipStream_t s);
+
 // sort.hip: re-ordering of a frame along the Morton curve of its map-frame voxels
 size_t sort_temp_bytes(int n);
 // ... and the dispatch order of k_icp's stripes: `order` = the stripes by `work`, heaviest first (stable); `work` is zeroed
