@@ -408,70 +408,64 @@ def _check_one_hip_runtime():
     _one_runtime[0] = True       # (torch loads its runtime when it is imported, before any tensor exists)
 
 
-def _device_frame(pts, labels, device):
-    """(DeviceFrame, stream) for a torch tensor on a GPU; everything that can be wrong with the arguments raises
-    ValueError here, before any call into the library"""
-    if pts.dim() != 2 or pts.shape[1] < (3 if labels is not None else 4) or pts.stride(1) != 1:
-        raise ValueError("a device frame is a 2-D tensor with stride(1) == 1 and at least %d columns, not shape %s "
-                         "strides %s" % (3 if labels is not None else 4, tuple(pts.shape), tuple(pts.stride())))
+def _current_stream(device):
+    """the handle of torch's current stream on `device`: the library's work on torch tensors is ordered behind it"""
+    return sys.modules["torch"].cuda.current_stream(device).cuda_stream
+
+
+# the wording of _device_rows' messages for a frame that is read and for a destination that is written
+_FRAME_WORDS = {
+    "shape": "a device frame is a 2-D tensor with stride(1) == 1 and at least %d columns, not shape %s strides %s",
+    "dtype": "a device frame is float32 or float64, not %s",
+    "labels": "labels of a device frame are a tensor on the same device",
+    "labels_shape": "labels: a 1-D tensor of %d elements, not shape %s",
+    "labels_dtype": "labels are uint8, int32 or int64, not %s",
+    "labels_device": "labels on %s, points on %s",
+    "device": "the frame is on %s, the pipeline / map on GPU %d",
+}
+_OUT_WORDS = {
+    "shape": "out= is a 2-D tensor with stride(1) == 1, rows that do not overlap and at least %d columns, not shape %s "
+             "strides %s",
+    "dtype": "out= is float32 or float64, not %s",
+    "labels": "labels_out= is a tensor on the same device as out=",
+    "labels_shape": "labels_out: a 1-D tensor of %d elements, not shape %s",
+    "labels_dtype": "labels_out is uint8, int32 or int64, not %s",
+    "labels_device": "labels_out on %s, out on %s",
+    "device": "out= is on %s, the pipeline / map on GPU %d",
+}
+
+
+def _device_rows(struct, pts, labels, device, words, distinct=False):
+    """(struct, stream) for rows that are a torch tensor on a GPU and their optional 1-D labels: a frame (DeviceFrame) or
+    a destination (DevicePoints, distinct: its rows must not overlap).  Everything that can be wrong with the arguments
+    raises ValueError here, before any call into the library; `words` are the messages."""
+    cols = 3 if labels is not None else 4
+    if pts.dim() != 2 or pts.shape[1] < cols or pts.stride(1) != 1 or \
+            (distinct and pts.shape[0] > 1 and pts.stride(0) < cols):
+        raise ValueError(words["shape"] % (cols, tuple(pts.shape), tuple(pts.stride())))
     xd = _XYZ_DTYPES.get(str(pts.dtype))
     if xd is None:
-        raise ValueError("a device frame is float32 or float64, not %s" % pts.dtype)
+        raise ValueError(words["dtype"] % pts.dtype)
     if labels is not None:
         if not _is_device_tensor(labels):
-            raise ValueError("labels of a device frame are a tensor on the same device")
-        if labels.dim() != 1 or labels.shape[0] != pts.shape[0]:
-            raise ValueError("labels: a 1-D tensor of %d elements, not shape %s" % (pts.shape[0], tuple(labels.shape)))
+            raise ValueError(words["labels"])
+        if labels.dim() != 1 or labels.shape[0] != pts.shape[0] or \
+                (distinct and labels.shape[0] > 1 and labels.stride(0) < 1):
+            raise ValueError(words["labels_shape"] % (pts.shape[0], tuple(labels.shape)))
         if str(labels.dtype) not in _LABEL_DTYPES:
-            raise ValueError("labels are uint8, int32 or int64, not %s" % labels.dtype)
+            raise ValueError(words["labels_dtype"] % labels.dtype)
         if labels.device != pts.device:
-            raise ValueError("labels on %s, points on %s" % (labels.device, pts.device))
+            raise ValueError(words["labels_device"] % (labels.device, pts.device))
     if pts.device.type != "cuda" or pts.device.index != device:
-        raise ValueError("the frame is on %s, the pipeline / map on GPU %d" % (pts.device, device))
+        raise ValueError(words["device"] % (pts.device, device))
     _check_one_hip_runtime()
-    f = DeviceFrame(pts.data_ptr() or None, pts.stride(0) * pts.element_size(), xd, 0, None, 0, pts.shape[0])
+    # (a destination of one row may have any row stride: it is described as rows that do not overlap)
+    min_xyz, min_label = (cols, 1) if distinct else (0, 0)
+    r = struct(pts.data_ptr() or None, max(pts.stride(0), min_xyz) * pts.element_size(), xd, 0, None, 0, pts.shape[0])
     if labels is not None:
-        f.label, f.label_stride = labels.data_ptr() or None, labels.stride(0) * labels.element_size()
-        f.label_dtype = _LABEL_DTYPES[str(labels.dtype)]
-    stream = sys.modules["torch"].cuda.current_stream(pts.device).cuda_stream
-    return f, stream
-
-
-def _device_points(out, labels_out, device):
-    """(DevicePoints, stream) for a destination that is a torch tensor on a GPU (and its optional 1-D labels); everything
-    that can be wrong with the arguments raises ValueError here, before any call into the library"""
-    if not _is_device_tensor(out):
-        raise ValueError("out= is a torch tensor on the GPU, not %s" % ("a tensor on %s" % out.device if _is_tensor(out)
-                                                                          else type(out).__name__))
-    cols = 3 if labels_out is not None else 4
-    if out.dim() != 2 or out.shape[1] < cols or out.stride(1) != 1 or (out.shape[0] > 1 and out.stride(0) < cols):
-        raise ValueError("out= is a 2-D tensor with stride(1) == 1, rows that do not overlap and at least %d columns, not "
-                         "shape %s strides %s" % (cols, tuple(out.shape), tuple(out.stride())))
-    xd = _XYZ_DTYPES.get(str(out.dtype))
-    if xd is None:
-        raise ValueError("out= is float32 or float64, not %s" % out.dtype)
-    if labels_out is not None:
-        if not _is_device_tensor(labels_out):
-            raise ValueError("labels_out= is a tensor on the same device as out=")
-        if labels_out.dim() != 1 or labels_out.shape[0] != out.shape[0] or \
-                (labels_out.shape[0] > 1 and labels_out.stride(0) < 1):
-            raise ValueError("labels_out: a 1-D tensor of %d elements, not shape %s" % (out.shape[0],
-                                                                                        tuple(labels_out.shape)))
-        if str(labels_out.dtype) not in _LABEL_DTYPES:
-            raise ValueError("labels_out is uint8, int32 or int64, not %s" % labels_out.dtype)
-        if labels_out.device != out.device:
-            raise ValueError("labels_out on %s, out on %s" % (labels_out.device, out.device))
-    if out.device.type != "cuda" or out.device.index != device:
-        raise ValueError("out= is on %s, the pipeline / map on GPU %d" % (out.device, device))
-    _check_one_hip_runtime()
-    el = out.element_size()
-    d = DevicePoints(out.data_ptr() or None, max(out.stride(0), cols) * el, xd, 0, None, 0, out.shape[0])
-    if labels_out is not None:
-        d.label = labels_out.data_ptr() or None
-        d.label_stride = max(labels_out.stride(0), 1) * labels_out.element_size()
-        d.label_dtype = _LABEL_DTYPES[str(labels_out.dtype)]
-    stream = sys.modules["torch"].cuda.current_stream(out.device).cuda_stream
-    return d, stream
+        r.label, r.label_stride = labels.data_ptr() or None, max(labels.stride(0), min_label) * labels.element_size()
+        r.label_dtype = _LABEL_DTYPES[str(labels.dtype)]
+    return r, _current_stream(pts.device)
 
 
 def _rows_out(device_index, count, host_rows, device_call, device, dtype, out, labels_out):
@@ -489,7 +483,9 @@ def _rows_out(device_index, count, host_rows, device_call, device, dtype, out, l
     if out is not None:
         if dtype is not None and dtype != out.dtype:
             raise ValueError("dtype=%s but out= is %s" % (dtype, out.dtype))
-        d, stream = _device_points(out, labels_out, device_index)
+        if not _is_device_tensor(out):
+            raise ValueError("out= is a torch tensor on the GPU, not %s" % ("a tensor on %s" % out.device if _is_tensor(out)
+                                                                              else type(out).__name__))
     else:
         import torch
         dt = torch.float64 if dtype is None else dtype
@@ -497,7 +493,7 @@ def _rows_out(device_index, count, host_rows, device_call, device, dtype, out, l
             raise ValueError("dtype= is torch.float32 or torch.float64, not %s" % (dt,))
         _check_one_hip_runtime()
         out = torch.empty((count(), 4), dtype=dt, device=torch.device("cuda", device_index))
-        d, stream = _device_points(out, None, device_index)
+    d, stream = _device_rows(DevicePoints, out, labels_out, device_index, _OUT_WORDS, distinct=True)
     n = C.c_uint64(0)
     _check(device_call(C.byref(d), stream, C.byref(n)))
     k = min(n.value, out.shape[0])
@@ -540,7 +536,7 @@ class Frame:
 
     def __init__(self, vmap, pts, labels=None):
         if _is_device_tensor(pts):
-            f, stream = _device_frame(pts, labels, vmap.device)
+            f, stream = _device_rows(DeviceFrame, pts, labels, vmap.device, _FRAME_WORDS)
             self.n = int(f.n)
             self._h = lib().sageicp_frame_from_device(vmap._h, C.byref(f), stream)
             if not self._h:
@@ -791,7 +787,7 @@ def occupancy_grid(frame, bounds=KEY_FRAME_BOUNDS, occ_size=KEY_FRAME_OCC_SIZE, 
         if pose_a.size != 7:
             raise ValueError("a pose is (qx, qy, qz, qw, tx, ty, tz)")
     if _is_device_tensor(frame):
-        f, stream = _device_frame(frame, labels, frame.device.index)
+        f, stream = _device_rows(DeviceFrame, frame, labels, frame.device.index, _FRAME_WORDS)
         _check(lib().sageicp_occupancy_grid_device(C.byref(f), pp, C.byref(params), out.ctypes.data_as(C.c_void_p),
                                                    stream))
         return out
@@ -884,7 +880,7 @@ class SageICP:
         _check_one_hip_runtime()
         dev = torch.device("cuda", self.config.device)
         out = torch.empty((h, w), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _current_stream(dev)
         _check(lib().sageicp_pipeline_key_frame_grid_device(self._h, out.data_ptr() or None, out.numel(), stream))
         return out
 
@@ -935,7 +931,7 @@ class SageICP:
             if str(timestamps.dtype) != "torch.float64" or timestamps.dim() != 1 or \
                     timestamps.shape[0] != frame.shape[0] or timestamps.stride(0) != 1:
                 raise ValueError("timestamps: a contiguous 1-D float64 tensor of %d elements" % frame.shape[0])
-        f, stream = _device_frame(frame, labels, self.config.device)
+        f, stream = _device_rows(DeviceFrame, frame, labels, self.config.device, _FRAME_WORDS)
         out = np.empty(7)
         icp, tot, ns = C.c_double(0), C.c_double(0), C.c_uint64(0)
         st = Stats()

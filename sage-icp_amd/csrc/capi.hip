@@ -561,45 +561,39 @@ int sageicp_align_clouds(const double *src, const double *tgt, uint64_t n, doubl
     Scratch sc;
     int rc = sc.init(device);
     if (rc) return rc;
-    auto body = [&]() -> int {
-        HIPCHK(hipSetDevice(device));
-        int r;
-        if ((r = sc.reserve_frame(n))) return r;
-        if ((r = sc.reserve_tgt(n))) return r;
-        hipStream_t s = sc.stream;
-        if (n) {
-            HIPCHK(hipMemcpyAsync(sc.d_frame.data(), src, n * sizeof(Point4), hipMemcpyHostToDevice, s));
-            HIPCHK(hipMemcpyAsync(sc.d_tgt.data(), tgt, n * sizeof(Point4), hipMemcpyHostToDevice, s));
-        }
-        double I[7];
-        identity_pose(I);
-        fill_state(sc.h_state.data(), I);
-        HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
-        if ((r = sc.reserve_partials(128))) return r;
-        GnParams gp{sc.d_frame.data(), sc.d_tgt.data(), static_cast<int>(n), kernel, sc.d_partials.data()};
-        FinParams fp{};
-        fp.st = sc.d_state.data();
-        fp.partials = sc.d_partials.data();
-        fp.nparts = launch_gn(gp, s);
-        fp.mode = 0;
-        fp.standalone = 1;
-        launch_fin(fp, s);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        // one step from identity: T_icp == est
-        for (int i = 0; i < 7; ++i) pose_out[i] = sc.h_state.data()->T_icp[i];
-        if (JTJ_out || JTr_out) {
-            double JTJ[36], JTr[6];
-            assemble_normal_equations(sc.h_state.data()->sums, JTJ, JTr);
-            if (JTJ_out) std::memcpy(JTJ_out, JTJ, sizeof(JTJ));
-            if (JTr_out) std::memcpy(JTr_out, JTr, sizeof(JTr));
-        }
-        return SAGEICP_OK;
-    };
-    rc = body();
-    sc.destroy();
-    return rc;
+    HIPCHK(hipSetDevice(device));
+    if ((rc = sc.reserve_frame(n))) return rc;
+    if ((rc = sc.reserve_tgt(n))) return rc;
+    hipStream_t s = sc.stream;
+    if (n) {
+        HIPCHK(hipMemcpyAsync(sc.d_frame.data(), src, n * sizeof(Point4), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(sc.d_tgt.data(), tgt, n * sizeof(Point4), hipMemcpyHostToDevice, s));
+    }
+    double I[7];
+    identity_pose(I);
+    fill_state(sc.h_state.data(), I);
+    HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
+    if ((rc = sc.reserve_partials(128))) return rc;
+    GnParams gp{sc.d_frame.data(), sc.d_tgt.data(), static_cast<int>(n), kernel, sc.d_partials.data()};
+    FinParams fp{};
+    fp.st = sc.d_state.data();
+    fp.partials = sc.d_partials.data();
+    fp.nparts = launch_gn(gp, s);
+    fp.mode = 0;
+    fp.standalone = 1;
+    launch_fin(fp, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    // one step from identity: T_icp == est
+    for (int i = 0; i < 7; ++i) pose_out[i] = sc.h_state.data()->T_icp[i];
+    if (JTJ_out || JTr_out) {
+        double JTJ[36], JTr[6];
+        assemble_normal_equations(sc.h_state.data()->sums, JTJ, JTr);
+        if (JTJ_out) std::memcpy(JTJ_out, JTJ, sizeof(JTJ));
+        if (JTr_out) std::memcpy(JTr_out, JTr, sizeof(JTr));
+    }
+    return SAGEICP_OK;
 }
 
 // ---- TransformPoints --------------------------------------------------------------------------
@@ -609,25 +603,19 @@ int sageicp_transform_points(const double pose[7], double *xyzl, uint64_t n, int
     Scratch sc;
     int rc = sc.init(device);
     if (rc) return rc;
-    auto body = [&]() -> int {
-        HIPCHK(hipSetDevice(device));
-        int r;
-        if ((r = sc.reserve_frame(n))) return r;
-        hipStream_t s = sc.stream;
-        fill_state(sc.h_state.data(), pose);
-        HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
-        if (n) {
-            HIPCHK(hipMemcpyAsync(sc.d_frame.data(), xyzl, n * sizeof(Point4), hipMemcpyHostToDevice, s));
-            launch_tf(sc.d_frame.data(), static_cast<int>(n), sc.d_state.data(), s);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(xyzl, sc.d_frame.data(), n * sizeof(Point4), hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(hipStreamSynchronize(s));
-        return SAGEICP_OK;
-    };
-    rc = body();
-    sc.destroy();
-    return rc;
+    HIPCHK(hipSetDevice(device));
+    if ((rc = sc.reserve_frame(n))) return rc;
+    hipStream_t s = sc.stream;
+    fill_state(sc.h_state.data(), pose);
+    HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
+    if (n) {
+        HIPCHK(hipMemcpyAsync(sc.d_frame.data(), xyzl, n * sizeof(Point4), hipMemcpyHostToDevice, s));
+        launch_tf(sc.d_frame.data(), static_cast<int>(n), sc.d_state.data(), s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(xyzl, sc.d_frame.data(), n * sizeof(Point4), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return SAGEICP_OK;
 }
 
 // ---- RegisterFrame ----------------------------------------------------------------------------
@@ -667,24 +655,26 @@ int sageicp_map_loop_status(const sageicp_map *m, sageicp_loop_status *out) {
     return SAGEICP_OK;
 }
 
-sageicp_frame *sageicp_frame_upload(const sageicp_map *m, const double *frame, uint64_t n) {
-    if (!m || (n && !frame)) { fail(SAGEICP_ERR_INVALID, "null argument"); return nullptr; }
+// a frame of n rows on the map's device, its memory allocated (the first step of both frame entries; nullptr: failed)
+static std::unique_ptr<sageicp_frame> new_frame(const sageicp_map *m, uint64_t n) {
     if (m->sc.init(m->device)) return nullptr;
     if (hipSetDevice(m->device) != hipSuccess) { fail(SAGEICP_ERR_HIP, "hipSetDevice"); return nullptr; }
-    sageicp_frame *f = new sageicp_frame;
+    auto f = std::make_unique<sageicp_frame>();
     f->device = m->device;
     f->n = n;
-    if (f->d.reserve(std::max<uint64_t>(n, 1)) != hipSuccess) {
-        fail(SAGEICP_ERR_HIP, "hipMalloc(frame)");
-        delete f;
-        return nullptr;
-    }
+    if (f->d.reserve(std::max<uint64_t>(n, 1)) != hipSuccess) { fail(SAGEICP_ERR_HIP, "hipMalloc(frame)"); return nullptr; }
+    return f;
+}
+
+sageicp_frame *sageicp_frame_upload(const sageicp_map *m, const double *frame, uint64_t n) {
+    if (!m || (n && !frame)) { fail(SAGEICP_ERR_INVALID, "null argument"); return nullptr; }
+    std::unique_ptr<sageicp_frame> f = new_frame(m, n);
+    if (!f) return nullptr;
     if (n && hipMemcpy(f->d.data(), frame, n * sizeof(Point4), hipMemcpyHostToDevice) != hipSuccess) {
         fail(SAGEICP_ERR_HIP, "hipMemcpy(frame)");
-        delete f;
         return nullptr;
     }
-    return f;
+    return f.release();
 }
 
 void sageicp_frame_destroy(sageicp_frame *f) {
@@ -693,7 +683,7 @@ void sageicp_frame_destroy(sageicp_frame *f) {
     delete f;
 }
 
-// ---- frames in the caller's device memory (ingest.hip) ------------------------------------------------------------
+// ---- rows in the caller's device memory: frames in (ingest.hip), outputs out (egress.hip, egress.h) ---------------
 static size_t dtype_bytes(int32_t t) {
     switch (t) {
     case SAGEICP_DTYPE_FLOAT32: return 4;
@@ -705,78 +695,124 @@ static size_t dtype_bytes(int32_t t) {
     }
 }
 
-// the first and the last byte of an extent must be device memory of `device` (this library's runtime's view of it:
-// a pointer of another HIP runtime loaded into the process is unknown here, and refused like host memory)
+// the device whose memory p is, as this library's runtime sees it (false: not device memory — host, pinned or managed
+// memory, or a pointer of another HIP runtime loaded into the process, which is unknown here)
+static bool device_of(const void *p, int *device) {
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    (void)hipGetLastError();            // an unknown pointer leaves an error behind that the next call must not see
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice) return false;
+    *device = at.device;
+    return true;
+}
+
+// the first and the last byte of an extent must be device memory of `device`
 static int check_extent(const void *p, uint64_t bytes, int device, const char *what) {
     const char *ends[2] = {static_cast<const char *>(p), static_cast<const char *>(p) + bytes - 1};
     for (const char *q : ends) {
-        hipPointerAttribute_t at{};
-        const hipError_t e = hipPointerGetAttributes(&at, q);
-        (void)hipGetLastError();        // an unknown pointer leaves an error behind that the next call must not see
-        if (e != hipSuccess || at.type != hipMemoryTypeDevice)
+        int d = -1;
+        if (!device_of(q, &d))
             return fail(SAGEICP_ERR_INVALID, std::string(what) + " is not device memory of this process's HIP runtime "
                                              "(host, pinned and managed memory are refused, not copied)");
-        if (at.device != device)
-            return fail(SAGEICP_ERR_INVALID, std::string(what) + " lives on device " + std::to_string(at.device) +
+        if (d != device)
+            return fail(SAGEICP_ERR_INVALID, std::string(what) + " lives on device " + std::to_string(d) +
                                              ", the handle on device " + std::to_string(device));
     }
     return SAGEICP_OK;
 }
 
-// Everything about a device frame that can be known before the stream is touched or anything launched: the layout
-// first (no device needed), then the size, then where the memory lives.  ts: the n timestamps that will be read, or
-// nullptr.
-static int check_device_frame(const sageicp_device_frame *f, const double *ts, void *stream, int device) {
-    if (!f) return fail(SAGEICP_ERR_INVALID, "null device frame");
-    if (f->n && !f->xyz) return fail(SAGEICP_ERR_INVALID, "device frame: xyz is NULL");
-    const size_t ex = f->xyz_dtype == SAGEICP_DTYPE_FLOAT32 || f->xyz_dtype == SAGEICP_DTYPE_FLOAT64 ? dtype_bytes(f->xyz_dtype) : 0;
-    if (!ex) return fail(SAGEICP_ERR_INVALID, "device frame: xyz_dtype must be SAGEICP_DTYPE_FLOAT32 or _FLOAT64");
-    const uint64_t cols = f->label ? 3 : 4;
-    if (f->xyz_stride < cols * ex || f->xyz_stride % ex)
-        return fail(SAGEICP_ERR_INVALID, f->label ? "device frame: xyz_stride must be a multiple of the element size and "
-                                                    "at least 3 elements"
-                                                  : "device frame: xyz_stride must be a multiple of the element size and "
-                                                    "at least 4 elements (the label is column 3)");
-    size_t el = 0;
-    if (f->label) {
-        el = f->label_dtype == SAGEICP_DTYPE_UINT8 || f->label_dtype == SAGEICP_DTYPE_INT32 ||
-             f->label_dtype == SAGEICP_DTYPE_INT64 ? dtype_bytes(f->label_dtype) : 0;
-        if (!el) return fail(SAGEICP_ERR_INVALID, "device frame: label_dtype must be SAGEICP_DTYPE_UINT8, _INT32 or _INT64");
-        if (f->label_stride < el || f->label_stride % el)
-            return fail(SAGEICP_ERR_INVALID, "device frame: label_stride must be a positive multiple of the label's size");
-    }
-    if (f->n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
-    if (!f->n) return SAGEICP_OK;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
-    int rc = check_extent(f->xyz, (f->n - 1) * f->xyz_stride + cols * ex, device, "device frame: xyz");
-    if (!rc && f->label) rc = check_extent(f->label, (f->n - 1) * f->label_stride + el, device, "device frame: label");
-    if (!rc && ts) rc = check_extent(ts, f->n * sizeof(double), device, "timestamps");
-    if (rc) return rc;
-    if (stream) {
-        int sd = -1;
-        const hipError_t e = hipStreamGetDevice(static_cast<hipStream_t>(stream), &sd);
-        (void)hipGetLastError();
-        if (e != hipSuccess || sd != device)
-            return fail(SAGEICP_ERR_INVALID, "stream is not a stream of the handle's device");
-    }
+// a caller's stream (NULL: the null stream) must be one of `device`
+static int check_stream(void *stream, int device) {
+    if (!stream) return SAGEICP_OK;
+    int sd = -1;
+    const hipError_t e = hipStreamGetDevice(static_cast<hipStream_t>(stream), &sd);
+    (void)hipGetLastError();
+    if (e != hipSuccess || sd != device) return fail(SAGEICP_ERR_INVALID, "stream is not a stream of the handle's device");
     return SAGEICP_OK;
+}
+
+// Strided rows in a caller's device memory: a frame's n (sageicp_device_frame) or a destination's cap
+// (sageicp_device_points).  Host-side only: the kernels take IngestArgs / EgressArgs.
+struct CallerRows {
+    const void *xyz;
+    uint64_t xyz_stride;
+    int32_t xyz_dtype;
+    const void *label;
+    uint64_t label_stride;
+    int32_t label_dtype;
+    uint64_t rows;
+};
+// what differs between a frame and a destination
+struct RowRules {
+    const char *prefix;                 // of the messages
+    unsigned label_dtypes;              // bit t: SAGEICP_DTYPE t is a valid label_dtype
+    const char *label_dtypes_text;
+    uint64_t max_rows;                  // (refused as a frame that is too large)
+};
+static const RowRules kFrameRows{
+    "device frame: ", 1u << SAGEICP_DTYPE_UINT8 | 1u << SAGEICP_DTYPE_INT32 | 1u << SAGEICP_DTYPE_INT64,
+    "SAGEICP_DTYPE_UINT8, _INT32 or _INT64", kMaxQueries};
+static const RowRules kPointsRows{
+    "device points: ", 1u << SAGEICP_DTYPE_UINT8 | 1u << SAGEICP_DTYPE_INT32 | 1u << SAGEICP_DTYPE_INT64 |
+                       1u << SAGEICP_DTYPE_FLOAT32 | 1u << SAGEICP_DTYPE_FLOAT64,
+    "SAGEICP_DTYPE_UINT8, _INT32, _INT64, _FLOAT32 or _FLOAT64", std::numeric_limits<uint64_t>::max()};
+
+// Everything about caller rows that can be known before the stream is touched or anything launched: the layout first
+// (no device needed), then where the memory of the rows (and of the n timestamps `ts` that will be read, if given)
+// lives, then the stream.  found: an entry without a handle works on the device xyz lives on (`device` is not read): it
+// is looked up once the layout has passed, and stored there.
+static int check_rows(const CallerRows &r, const RowRules &k, const double *ts, void *stream, int device,
+                      int *found = nullptr) {
+    const std::string pre = k.prefix;
+    if (r.rows && !r.xyz) return fail(SAGEICP_ERR_INVALID, pre + "xyz is NULL");
+    const size_t ex = r.xyz_dtype == SAGEICP_DTYPE_FLOAT32 || r.xyz_dtype == SAGEICP_DTYPE_FLOAT64 ? dtype_bytes(r.xyz_dtype) : 0;
+    if (!ex) return fail(SAGEICP_ERR_INVALID, pre + "xyz_dtype must be SAGEICP_DTYPE_FLOAT32 or _FLOAT64");
+    const uint64_t cols = r.label ? 3 : 4;
+    if (r.xyz_stride < cols * ex || r.xyz_stride % ex)
+        return fail(SAGEICP_ERR_INVALID, pre + (r.label ? "xyz_stride must be a multiple of the element size and at least 3 "
+                                                          "elements"
+                                                        : "xyz_stride must be a multiple of the element size and at least 4 "
+                                                          "elements (the label is column 3)"));
+    size_t el = 0;
+    if (r.label) {
+        el = dtype_bytes(r.label_dtype) && ((k.label_dtypes >> r.label_dtype) & 1u) ? dtype_bytes(r.label_dtype) : 0;
+        if (!el) return fail(SAGEICP_ERR_INVALID, pre + "label_dtype must be " + k.label_dtypes_text);
+        if (r.label_stride < el || r.label_stride % el)
+            return fail(SAGEICP_ERR_INVALID, pre + "label_stride must be a positive multiple of the label's size");
+    }
+    if (r.rows > k.max_rows) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
+    if (!r.rows) return SAGEICP_OK;
+    int rc = require_device();
+    if (rc) return rc;
+    if (found) {                        // (memory that is not device memory is refused just below)
+        device = 0;
+        (void)device_of(r.xyz, &device);
+        *found = device;
+    }
+    rc = check_extent(r.xyz, (r.rows - 1) * r.xyz_stride + cols * ex, device, (pre + "xyz").c_str());
+    if (!rc && r.label) rc = check_extent(r.label, (r.rows - 1) * r.label_stride + el, device, (pre + "label").c_str());
+    if (!rc && ts) rc = check_extent(ts, r.rows * sizeof(double), device, "timestamps");
+    return rc ? rc : check_stream(stream, device);
+}
+
+static int check_device_frame(const sageicp_device_frame *f, const double *ts, void *stream, int device,
+                              int *found = nullptr) {
+    if (!f) return fail(SAGEICP_ERR_INVALID, "null device frame");
+    return check_rows({f->xyz, f->xyz_stride, f->xyz_dtype, f->label, f->label_stride, f->label_dtype, f->n}, kFrameRows,
+                      ts, stream, device, found);
+}
+
+static int check_device_points(const sageicp_device_points *d, void *stream, int device) {
+    if (!d) return fail(SAGEICP_ERR_INVALID, "null destination");
+    return check_rows({d->xyz, d->xyz_stride, d->xyz_dtype, d->label, d->label_stride, d->label_dtype, d->cap},
+                      kPointsRows, nullptr, stream, device);
 }
 
 sageicp_frame *sageicp_frame_from_device(const sageicp_map *m, const sageicp_device_frame *fr, void *stream) {
     if (!m) { fail(SAGEICP_ERR_INVALID, "null argument"); return nullptr; }
     if (check_device_frame(fr, nullptr, stream, m->device)) return nullptr;
-    if (m->sc.init(m->device)) return nullptr;
-    if (hipSetDevice(m->device) != hipSuccess) { fail(SAGEICP_ERR_HIP, "hipSetDevice"); return nullptr; }
-    sageicp_frame *f = new sageicp_frame;
-    f->device = m->device;
-    f->n = fr->n;
-    if (f->d.reserve(std::max<uint64_t>(fr->n, 1)) != hipSuccess) {
-        fail(SAGEICP_ERR_HIP, "hipMalloc(frame)");
-        delete f;
-        return nullptr;
-    }
+    std::unique_ptr<sageicp_frame> f = new_frame(m, fr->n);
+    if (!f) return nullptr;
     // on the caller's stream, behind the work that wrote the buffers; synchronous: afterwards nothing reads them
     const hipStream_t s = static_cast<hipStream_t>(stream);
     launch_ingest(ingest_args(*fr), f->d.data(), s);
@@ -784,48 +820,9 @@ sageicp_frame *sageicp_frame_from_device(const sageicp_map *m, const sageicp_dev
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {
         fail(SAGEICP_ERR_HIP, std::string("ingest of a device frame: ") + hipGetErrorString(e));
-        delete f;
         return nullptr;
     }
-    return f;
-}
-
-// ---- outputs into the caller's device memory (egress.hip, egress.h) -------------------------------------------------
-// Everything about a destination that can be known before the stream is touched or anything launched: the layout
-// first (no device needed), then where the memory of its `cap` rows lives, then the stream.
-static int check_device_points(const sageicp_device_points *d, void *stream, int device) {
-    if (!d) return fail(SAGEICP_ERR_INVALID, "null destination");
-    if (d->cap && !d->xyz) return fail(SAGEICP_ERR_INVALID, "device points: xyz is NULL");
-    const size_t ex = d->xyz_dtype == SAGEICP_DTYPE_FLOAT32 || d->xyz_dtype == SAGEICP_DTYPE_FLOAT64 ? dtype_bytes(d->xyz_dtype) : 0;
-    if (!ex) return fail(SAGEICP_ERR_INVALID, "device points: xyz_dtype must be SAGEICP_DTYPE_FLOAT32 or _FLOAT64");
-    const uint64_t cols = d->label ? 3 : 4;
-    if (d->xyz_stride < cols * ex || d->xyz_stride % ex)
-        return fail(SAGEICP_ERR_INVALID, d->label ? "device points: xyz_stride must be a multiple of the element size and "
-                                                    "at least 3 elements"
-                                                  : "device points: xyz_stride must be a multiple of the element size and "
-                                                    "at least 4 elements (the label is column 3)");
-    const size_t el = d->label ? dtype_bytes(d->label_dtype) : 0;
-    if (d->label) {
-        if (!el) return fail(SAGEICP_ERR_INVALID, "device points: label_dtype must be SAGEICP_DTYPE_UINT8, _INT32, _INT64, "
-                                                  "_FLOAT32 or _FLOAT64");
-        if (d->label_stride < el || d->label_stride % el)
-            return fail(SAGEICP_ERR_INVALID, "device points: label_stride must be a positive multiple of the label's size");
-    }
-    if (!d->cap) return SAGEICP_OK;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
-    int rc = check_extent(d->xyz, (d->cap - 1) * d->xyz_stride + cols * ex, device, "device points: xyz");
-    if (!rc && d->label) rc = check_extent(d->label, (d->cap - 1) * d->label_stride + el, device, "device points: label");
-    if (rc) return rc;
-    if (stream) {
-        int sd = -1;
-        const hipError_t e = hipStreamGetDevice(static_cast<hipStream_t>(stream), &sd);
-        (void)hipGetLastError();
-        if (e != hipSuccess || sd != device)
-            return fail(SAGEICP_ERR_INVALID, "stream is not a stream of the handle's device");
-    }
-    return SAGEICP_OK;
+    return f.release();
 }
 
 static EgressArgs egress_args(const sageicp_device_points &d, int *flags) {
@@ -841,11 +838,20 @@ static EgressArgs egress_args(const sageicp_device_points &d, int *flags) {
     return a;
 }
 
-// after the writes enqueued on s: wait for them, then read the label-range flag they may have raised
-static int egress_finish(const int *d_flag, hipStream_t s) {
+// The rows that write(EgressArgs) enqueues on s into a caller's destination, behind a zeroed label-range flag: waited
+// for, then the flag they may have raised read.  Synchronous also when write fails part-way: nothing this call
+// enqueued runs on once it has returned.
+static int egress_into(DevBuf<int> &flag, const sageicp_device_points &dst, hipStream_t s,
+                       const std::function<int(const EgressArgs &)> &write) {
+    if (!flag) HIPCHK(flag.reserve(1));
+    HIPCHK(hipMemsetAsync(flag.data(), 0, sizeof(int), s));
+    if (int rc = write(egress_args(dst, flag.data()))) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
     int flags = 0;
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&flags, d_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&flags, flag.data(), sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (flags & kEgressLabelRange)
         return fail(SAGEICP_ERR_INVALID, "a label does not fit the destination's label type (static_cast<int64_t>(label) "
@@ -864,15 +870,12 @@ int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_poi
     if ((rc = m->sc.init(m->device))) return rc;
     HIPCHK(hipSetDevice(m->device));
     const hipStream_t s = m->sc.stream;
-    if (!m->d_egress_flag.data()) HIPCHK(m->d_egress_flag.reserve(1));
     if (!m->ev_caller) HIPCHK(hipEventCreateWithFlags(&m->ev_caller, hipEventDisableTiming));
     // the map's stream waits for the work the caller enqueued before this call (it may still use the destination)
     HIPCHK(hipEventRecord(m->ev_caller, static_cast<hipStream_t>(stream)));
     HIPCHK(hipStreamWaitEvent(s, m->ev_caller, 0));
-    HIPCHK(hipMemsetAsync(m->d_egress_flag.data(), 0, sizeof(int), s));
-    const EgressArgs e = egress_args(*dst, m->d_egress_flag.data());
-    std::vector<double> staged;
-    auto body = [&]() -> int {
+    std::vector<double> staged;                         // (read by a copy on s: egress_into waits for it)
+    return egress_into(m->d_egress_flag, *dst, s, [&](const EgressArgs &e) -> int {
         if (m->on_device && !env_int("SAGEICP_EGRESS_TWO_PASS", 0))
             return pack_resident(m, &e, s);             // the gather writes the caller's layout itself
         // two passes: the rows packed into d_pc (from the HBM copy, or staged from the host copy), then k_egress
@@ -887,13 +890,7 @@ int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_poi
         }
         launch_egress(e, m->d_pc.data(), want, s);
         return SAGEICP_OK;
-    };
-    rc = body();
-    if (rc) {
-        (void)hipStreamSynchronize(s);                  // (`staged` leaves scope)
-        return rc;
-    }
-    return egress_finish(m->d_egress_flag.data(), s);
+    });
 }
 
 // RegisterFrame of n points already on `device` (an uploaded frame, or the pipeline's source cloud)
@@ -1058,22 +1055,31 @@ void sageicp_comm_destroy(sageicp_comm *c) {
 }
 
 // ---- Preprocess / VoxelDownsample on the device --------------------------------------------------
-int sageicp_preprocess(const double *frame, uint64_t n, double max_range, double min_range,
-                       double label_max_range, double *out, uint64_t *n_out, int device) {
-    if (!n_out || (n && (!frame || !out))) return fail(SAGEICP_ERR_INVALID, "null argument");
+// One level of a Prep of its own on `device` (Prep::run's arguments), its cloud copied to out; info: the dynamic
+// filter's, with dyn_cfg
+static int prep_one_level(int device, const double *frame, uint64_t n, double max_range, double min_range,
+                          double label_max_range, int n_groups, const int *gcounts, const int *glabels, const double *gvs,
+                          int crop, double scale, const DynFilterConfig *dyn_cfg, double *out, uint64_t *n_out,
+                          sageicp_dynfilter_info *info) {
     Prep pr;
     int rc = pr.init(device);
     if (rc) return rc;
     std::vector<std::vector<double>> res;
-    const int crop = 1;
-    const double scale = 0.0;       // crop only
-    rc = pr.run(frame, n, max_range, min_range, label_max_range, 0, nullptr, nullptr, nullptr, &crop,
-                &scale, 1, res);
-    pr.destroy();
+    rc = pr.run(frame, n, max_range, min_range, label_max_range, n_groups, gcounts, glabels, gvs, &crop, &scale, 1, res,
+                true, dyn_cfg);
     if (rc) return rc;
     *n_out = res[0].size() / 4;
     if (!res[0].empty()) std::memcpy(out, res[0].data(), res[0].size() * sizeof(double));
+    if (info) *info = pr.dyn.info;
     return SAGEICP_OK;
+}
+
+int sageicp_preprocess(const double *frame, uint64_t n, double max_range, double min_range,
+                       double label_max_range, double *out, uint64_t *n_out, int device) {
+    if (!n_out || (n && (!frame || !out))) return fail(SAGEICP_ERR_INVALID, "null argument");
+    // crop only (scale 0)
+    return prep_one_level(device, frame, n, max_range, min_range, label_max_range, 0, nullptr, nullptr, nullptr, 1, 0.0,
+                          nullptr, out, n_out, nullptr);
 }
 
 int sageicp_voxel_downsample(const double *frame, uint64_t n, int n_groups,
@@ -1083,18 +1089,8 @@ int sageicp_voxel_downsample(const double *frame, uint64_t n, int n_groups,
     if (!n_out || (n && (!frame || !out)) || n_groups < 0 ||
         (n_groups && (!group_label_counts || !group_labels || !group_voxel_size)) || !(vox_scale > 0.0))
         return fail(SAGEICP_ERR_INVALID, "bad argument");
-    Prep pr;
-    int rc = pr.init(device);
-    if (rc) return rc;
-    std::vector<std::vector<double>> res;
-    const int crop = 0;
-    rc = pr.run(frame, n, 0, 0, 0, n_groups, group_label_counts, group_labels, group_voxel_size, &crop,
-                &vox_scale, 1, res);
-    pr.destroy();
-    if (rc) return rc;
-    *n_out = res[0].size() / 4;
-    if (!res[0].empty()) std::memcpy(out, res[0].data(), res[0].size() * sizeof(double));
-    return SAGEICP_OK;
+    return prep_one_level(device, frame, n, 0, 0, 0, n_groups, group_label_counts, group_labels, group_voxel_size, 0,
+                          vox_scale, nullptr, out, n_out, nullptr);
 }
 
 int sageicp_preprocess_dynamic(const double *frame, uint64_t n, double max_range, double min_range,
@@ -1109,21 +1105,9 @@ int sageicp_preprocess_dynamic(const double *frame, uint64_t n, double max_range
     cfg.dy_th = dy_th;
     cfg.dynamic_labels.assign(dynamic_labels, dynamic_labels + n_dynamic);
     cfg.landmark_labels.assign(landmark_labels, landmark_labels + n_landmark);
-    Prep pr;
-    int rc = pr.init(device);
-    if (rc) return rc;
-    std::vector<std::vector<double>> res;
-    const int crop = 0;
-    const double scale = 0.0;       // one pass-through level: the filtered cloud, downloaded
-    rc = pr.run(frame, n, max_range, min_range, label_max_range, 0, nullptr, nullptr, nullptr, &crop, &scale, 1, res,
-                true, &cfg);
-    const sageicp_dynfilter_info got = pr.dyn.info;
-    pr.destroy();
-    if (rc) return rc;
-    *n_out = res[0].size() / 4;
-    if (!res[0].empty()) std::memcpy(out, res[0].data(), res[0].size() * sizeof(double));
-    if (info) *info = got;
-    return SAGEICP_OK;
+    // one pass-through level (no crop, scale 0): the filtered cloud, downloaded
+    return prep_one_level(device, frame, n, max_range, min_range, label_max_range, 0, nullptr, nullptr, nullptr, 0, 0.0,
+                          &cfg, out, n_out, info);
 }
 
 int sageicp_cluster_emission_order(const uint32_t *sizes, uint64_t n, uint32_t *order_out) {
@@ -1154,30 +1138,22 @@ int sageicp_deskew_scan(const double *frame, const double *timestamps, uint64_t 
     se3_mul(inv, finish_pose, rel);
     se3_log(rel, delta.v);
     if (n == 0) return SAGEICP_OK;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
-    if (device < 0 || device >= count) return fail(SAGEICP_ERR_INVALID, "device ordinal out of range");
+    int rc = require_device(device);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(device));
     DevBuf<Point4> d_p;
     DevBuf<double> d_t;
-    hipStream_t s = nullptr;
-    auto body = [&]() -> int {
-        HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIPCHK(d_p.reserve(n));
-        HIPCHK(d_t.reserve(n));
-        HIPCHK(hipMemcpyAsync(d_p.data(), frame, n * sizeof(Point4), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(d_t.data(), timestamps, n * sizeof(double), hipMemcpyHostToDevice, s));
-        launch_deskew(d_p.data(), d_p.data(), d_t.data(), static_cast<int>(n), delta, s);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out, d_p.data(), n * sizeof(Point4), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        return SAGEICP_OK;
-    };
-    const int rc = body();
-    if (s) (void)hipStreamSynchronize(s);
-    if (s) (void)hipStreamDestroy(s);
-    return rc;
+    OwnedStream s;                      // (after the buffers: waited for before they are freed)
+    HIPCHK(s.create());
+    HIPCHK(d_p.reserve(n));
+    HIPCHK(d_t.reserve(n));
+    HIPCHK(hipMemcpyAsync(d_p.data(), frame, n * sizeof(Point4), hipMemcpyHostToDevice, s.get()));
+    HIPCHK(hipMemcpyAsync(d_t.data(), timestamps, n * sizeof(double), hipMemcpyHostToDevice, s.get()));
+    launch_deskew(d_p.data(), d_p.data(), d_t.data(), static_cast<int>(n), delta, s.get());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, d_p.data(), n * sizeof(Point4), hipMemcpyDeviceToHost, s.get()));
+    HIPCHK(hipStreamSynchronize(s.get()));
+    return SAGEICP_OK;
 }
 
 // ---- pipeline counterpart -----------------------------------------------------------------------
@@ -1512,13 +1488,13 @@ int sageicp_pipeline_source_device(const sageicp_pipeline *p, const sageicp_devi
     const uint64_t want = std::min(dst->cap, p->src_n);
     if (!want) return SAGEICP_OK;
     HIPCHK(hipSetDevice(p->device));
-    if (!p->d_egress_flag.data()) HIPCHK(p->d_egress_flag.reserve(1));
     // on the caller's stream, behind the work it enqueued before this call; synchronous: afterwards nothing of the
     // library touches the destination
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    HIPCHK(hipMemsetAsync(p->d_egress_flag.data(), 0, sizeof(int), s));
-    launch_egress(egress_args(*dst, p->d_egress_flag.data()), p->prep[p->src_buf].d_src.data(), want, s);
-    return egress_finish(p->d_egress_flag.data(), s);
+    return egress_into(p->d_egress_flag, *dst, s, [&](const EgressArgs &e) {
+        launch_egress(e, p->prep[p->src_buf].d_src.data(), want, s);
+        return SAGEICP_OK;
+    });
 }
 int sageicp_pipeline_set_deskew(sageicp_pipeline *p, int enable) {
     if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
@@ -1637,12 +1613,18 @@ int sageicp_pipeline_key_frame_info(const sageicp_pipeline *p, sageicp_key_frame
     *info = p->kf.info;
     return SAGEICP_OK;
 }
-int sageicp_pipeline_key_frame_grid(const sageicp_pipeline *p, uint8_t *out, uint64_t cap) {
+// what both key-grid entries check first: the selection is on and `cap` bytes hold the grid's *cells
+static int key_grid_cells(const sageicp_pipeline *p, const uint8_t *out, uint64_t cap, uint64_t *cells) {
     if (!p || !out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    if (!p->kf.on) return fail(SAGEICP_ERR_INVALID, "key-frame selection is off");
+    *cells = static_cast<uint64_t>(p->kf.g.h) * p->kf.g.w;
+    if (cap < *cells) return fail(SAGEICP_ERR_INVALID, "the key grid needs occ_h * occ_w bytes");
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_key_frame_grid(const sageicp_pipeline *p, uint8_t *out, uint64_t cap) {
+    uint64_t cells = 0;
+    if (int rc = key_grid_cells(p, out, cap, &cells)) return rc;
     const auto &k = p->kf;
-    if (!k.on) return fail(SAGEICP_ERR_INVALID, "key-frame selection is off");
-    const uint64_t cells = static_cast<uint64_t>(k.g.h) * k.g.w;
-    if (cap < cells) return fail(SAGEICP_ERR_INVALID, "the key grid needs occ_h * occ_w bytes");
     if (!k.has_key) {
         std::memset(out, 0, cells);
         return SAGEICP_OK;
@@ -1654,26 +1636,16 @@ int sageicp_pipeline_key_frame_grid(const sageicp_pipeline *p, uint8_t *out, uin
     return SAGEICP_OK;
 }
 int sageicp_pipeline_key_frame_grid_device(const sageicp_pipeline *p, uint8_t *out, uint64_t cap, void *stream) {
-    if (!p || !out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    const auto &k = p->kf;
-    if (!k.on) return fail(SAGEICP_ERR_INVALID, "key-frame selection is off");
-    const uint64_t cells = static_cast<uint64_t>(k.g.h) * k.g.w;
-    if (cap < cells) return fail(SAGEICP_ERR_INVALID, "the key grid needs occ_h * occ_w bytes");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
-    int rc = check_extent(out, cells, p->device, "key-frame grid");
+    uint64_t cells = 0;
+    int rc = key_grid_cells(p, out, cap, &cells);
+    if (!rc) rc = require_device();
+    if (!rc) rc = check_extent(out, cells, p->device, "key-frame grid");
+    if (!rc) rc = check_stream(stream, p->device);
     if (rc) return rc;
-    if (stream) {
-        int sd = -1;
-        const hipError_t e = hipStreamGetDevice(static_cast<hipStream_t>(stream), &sd);
-        (void)hipGetLastError();
-        if (e != hipSuccess || sd != p->device)
-            return fail(SAGEICP_ERR_INVALID, "stream is not a stream of the handle's device");
-    }
     HIPCHK(hipSetDevice(p->device));
     // on the caller's stream, behind the work it enqueued before this call; synchronous
     const hipStream_t s = static_cast<hipStream_t>(stream);
+    const auto &k = p->kf;
     if (k.has_key) launch_occ_unpack(k.d_key.data(), k.g, out, s);
     else HIPCHK(hipMemsetAsync(out, 0, cells, s));
     HIPCHK(hipGetLastError());
@@ -1716,27 +1688,18 @@ int sageicp_occupancy_grid(const double *xyzl, uint64_t n, const double pose[7],
     if (pose && !finite_n(pose, 7)) return fail(SAGEICP_ERR_INVALID, "the pose is not finite");
     for (uint64_t i = 0; i < n; ++i)
         if (!finite_n(xyzl + 4 * i, 3)) return fail(SAGEICP_ERR_INVALID, "a coordinate is not finite (NaN / Inf)");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
-    if (device < 0 || device >= count) return fail(SAGEICP_ERR_INVALID, "device ordinal out of range");
+    if (int rc = require_device(device)) return rc;
     if (n == 0) {
         std::memset(grid_out, 0, static_cast<size_t>(g.h) * g.w);
         return SAGEICP_OK;
     }
+    HIPCHK(hipSetDevice(device));
     DevBuf<Point4> d_p;
-    hipStream_t s = nullptr;
-    auto body = [&]() -> int {
-        HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIPCHK(d_p.reserve(n));
-        HIPCHK(hipMemcpyAsync(d_p.data(), xyzl, n * sizeof(Point4), hipMemcpyHostToDevice, s));
-        return occupancy_on_device(d_p.data(), n, pose, g, grid_out, s);
-    };
-    rc = body();
-    if (s) (void)hipStreamSynchronize(s);
-    if (s) (void)hipStreamDestroy(s);
-    return rc;
+    OwnedStream s;                      // (after the buffer: waited for before it is freed)
+    HIPCHK(s.create());
+    HIPCHK(d_p.reserve(n));
+    HIPCHK(hipMemcpyAsync(d_p.data(), xyzl, n * sizeof(Point4), hipMemcpyHostToDevice, s.get()));
+    return occupancy_on_device(d_p.data(), n, pose, g, grid_out, s.get());
 }
 int sageicp_occupancy_grid_device(const sageicp_device_frame *frame, const double pose[7],
                                   const sageicp_occupancy_params *params, uint8_t *grid_out, void *stream) {
@@ -1745,15 +1708,9 @@ int sageicp_occupancy_grid_device(const sageicp_device_frame *frame, const doubl
     int rc = occ_grid_from(params, g);
     if (rc) return rc;
     if (pose && !finite_n(pose, 7)) return fail(SAGEICP_ERR_INVALID, "the pose is not finite");
-    // the device the frame's memory lives on; memory that is not device memory is refused by check_device_frame
+    // no handle: the work runs on the device the frame's memory lives on, looked up once its layout has passed
     int device = 0;
-    if (frame->n && frame->xyz) {
-        hipPointerAttribute_t at{};
-        const hipError_t e = hipPointerGetAttributes(&at, frame->xyz);
-        (void)hipGetLastError();
-        if (e == hipSuccess && at.type == hipMemoryTypeDevice) device = at.device;
-    }
-    rc = check_device_frame(frame, nullptr, stream, device);
+    rc = check_device_frame(frame, nullptr, stream, device, &device);
     if (rc) return rc;
     if (frame->n == 0) {
         std::memset(grid_out, 0, static_cast<size_t>(g.h) * g.w);

@@ -116,6 +116,20 @@ inline int fail(int code, const std::string &msg) {
             return fail(SAGEICP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
+// There is no CPU fallback: an entry that needs the device fails without one, and one that names a device needs the
+// ordinal of a visible one.
+inline int require_device() {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
+    return SAGEICP_OK;
+}
+inline int require_device(int device) {
+    if (int rc = require_device()) return rc;
+    if (device < 0 || device >= sageicp_device_count()) return fail(SAGEICP_ERR_INVALID, "device ordinal out of range");
+    return SAGEICP_OK;
+}
+
 inline double now_us() {
     using namespace std::chrono;
     return duration<double, std::micro>(steady_clock::now().time_since_epoch()).count();
@@ -164,12 +178,14 @@ struct Scratch {
     IcpProgress *d_prog = nullptr; // its device address
     std::vector<hipEvent_t> events;  // 5 per profiled iteration
 
+    Scratch() = default;
+    Scratch(Scratch &&) = default;
+    Scratch &operator=(Scratch &&) = default;       // (destroy() empties the scratch by assigning a fresh one)
+    ~Scratch() { destroy(); }
+
     int init(int dev) {
         if (stream) return SAGEICP_OK;
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-            return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
-        if (dev < 0 || dev >= count) return fail(SAGEICP_ERR_INVALID, "device ordinal out of range");
+        if (int rc = require_device(dev)) return rc;
         device = dev;
         HIPCHK(hipSetDevice(device));
         {
@@ -469,12 +485,14 @@ struct Prep {
     bool keep_raw = false;
     DevBuf<Point4> d_raw;
 
+    Prep() = default;
+    Prep(Prep &&) = default;
+    Prep &operator=(Prep &&) = default;             // (destroy() empties the buffers by assigning a fresh Prep)
+    ~Prep() { destroy(); }
+
     int init(int dev) {
         if (stream) return SAGEICP_OK;
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-            return fail(SAGEICP_ERR_NO_DEVICE, "no HIP device visible (gfx950 required; no CPU fallback)");
-        if (dev < 0 || dev >= count) return fail(SAGEICP_ERR_INVALID, "device ordinal out of range");
+        if (int rc = require_device(dev)) return rc;
         device = dev;
         HIPCHK(hipSetDevice(device));
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));

@@ -1,6 +1,7 @@
 // Owners of the host side's device memory (hipMalloc) and pinned host memory (hipHostMalloc): one block each,
 // freed by the destructor, moved but never copied.  The caller decides how much to hold (the growth policies stay
 // at the call sites: capacities reach the kernels); the owner only allocates, keeps a prefix when asked, and frees.
+// Beside them, the owner of a one-call stream.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -91,5 +92,25 @@ template <typename T>
 using DevBuf = Buffer<T, DeviceMemory>;
 template <typename T, unsigned Flags = hipHostMallocDefault>
 using PinnedBuf = Buffer<T, PinnedMemory<Flags>>;
+
+// The stream of one call, created on the current device: the destructor waits for it, then destroys it.  Declared
+// after the buffers its work uses, it goes first, so no buffer is freed under a copy or a kernel still running.
+class OwnedStream {
+public:
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream &) = delete;
+    OwnedStream &operator=(const OwnedStream &) = delete;
+    ~OwnedStream() {
+        if (!s_) return;
+        (void)hipStreamSynchronize(s_);
+        (void)hipStreamDestroy(s_);
+    }
+
+    hipError_t create() { return hipStreamCreateWithFlags(&s_, hipStreamNonBlocking); }
+    hipStream_t get() const { return s_; }
+
+private:
+    hipStream_t s_ = nullptr;
+};
 
 }  // namespace sageicp

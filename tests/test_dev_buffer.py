@@ -1,5 +1,5 @@
-"""The owners of device and pinned memory (csrc/dev_buffer.h), compiled by g++ against stand-ins for the six HIP
-calls they make, defined below: every allocation is counted and every call logged, so the order of frees and
+"""The owners of device and pinned memory and of a one-call stream (csrc/dev_buffer.h), compiled by g++ against
+stand-ins for the eight HIP calls they make, defined below: every allocation is counted and every call logged, so the order of frees and
 allocations, the bytes copied and what is left alive can be checked without a GPU.  A program of its own, not a
 library loaded here: in a process that has the HIP runtime loaded, its symbols would take the stand-ins' place.
 CPU only."""
@@ -26,7 +26,7 @@ namespace {
 int live = 0;             // blocks allocated and not yet freed (device and pinned)
 int fail_next = 0;        // the next allocation fails
 size_t copied = 0;        // bytes of the last copy
-std::string trace;        // 'A' allocation, 'F' free, 'C' copy, 'S' synchronisation
+std::string trace;        // 'A' allocation, 'F' free, 'C' copy, 'S' synchronisation, 'N' new stream, 'D' stream destroyed
 hipError_t alloc(void **p, size_t bytes) {
     if (fail_next) {
         fail_next = 0;
@@ -59,6 +59,16 @@ hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKin
 }
 hipError_t hipStreamSynchronize(hipStream_t) {
     trace += 'S';
+    return hipSuccess;
+}
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned int) {
+    static int stream;
+    *s = reinterpret_cast<hipStream_t>(&stream);
+    trace += 'N';
+    return hipSuccess;
+}
+hipError_t hipStreamDestroy(hipStream_t) {
+    trace += 'D';
     return hipSuccess;
 }
 
@@ -151,6 +161,23 @@ static int a_failed_grow_keeps_the_old_block() {
     return 0;
 }
 
+static int a_stream_owner_waits_then_destroys_before_the_buffers_go() {
+    {
+        OwnedStream never_created;
+        CHECK(never_created.get() == nullptr);
+    }
+    CHECK(trace.empty());                       // (nothing to wait for or destroy)
+    {
+        DevBuf<int> d;
+        CHECK(d.reserve(4) == hipSuccess);
+        OwnedStream s;                          // declared after the buffer: destroyed before it
+        CHECK(s.create() == hipSuccess && s.get() != nullptr && trace == "AN");
+        trace.clear();
+    }
+    CHECK(trace == "SDF" && live == 0);
+    return 0;
+}
+
 // argv[1]: the case; prints the line of the first failed check (0: none), then the blocks still alive
 int main(int argc, char **argv) {
     if (argc != 2) return 2;
@@ -163,6 +190,8 @@ int main(int argc, char **argv) {
     if (c == "grow_copies_exactly_keep_elements") line = grow_copies_exactly_keep_elements();
     if (c == "a_failed_reserve_leaves_the_owner_empty") line = a_failed_reserve_leaves_the_owner_empty();
     if (c == "a_failed_grow_keeps_the_old_block") line = a_failed_grow_keeps_the_old_block();
+    if (c == "a_stream_owner_waits_then_destroys_before_the_buffers_go")
+        line = a_stream_owner_waits_then_destroys_before_the_buffers_go();
     std::printf("%d %d\n", line, live);
     return 0;
 }
@@ -170,7 +199,8 @@ int main(int argc, char **argv) {
 
 CASES = ["destroyed_owners_free_everything", "a_move_hands_over_the_block", "move_assignment_frees_the_old_block",
          "reserve_frees_before_it_allocates", "grow_copies_exactly_keep_elements",
-         "a_failed_reserve_leaves_the_owner_empty", "a_failed_grow_keeps_the_old_block"]
+         "a_failed_reserve_leaves_the_owner_empty", "a_failed_grow_keeps_the_old_block",
+         "a_stream_owner_waits_then_destroys_before_the_buffers_go"]
 
 
 @pytest.fixture(scope="module")

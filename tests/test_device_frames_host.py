@@ -76,6 +76,18 @@ def test_frame_from_device_refuses_a_bad_layout_before_any_device_query(sage, ca
     assert "device frame" in msg or "too large" in msg, msg
 
 
+@pytest.mark.parametrize("case", sorted(BAD_LAYOUTS))
+def test_occupancy_grid_device_refuses_a_bad_layout_before_any_device_query(sage, case):
+    f = _frame(sage, **BAD_LAYOUTS[case])
+    params = sage.occupancy_params()            # valid: only the layout is wrong
+    grid = np.zeros(params.occ_h * params.occ_w, dtype=np.uint8)
+    assert sage.lib().sageicp_occupancy_grid_device(ctypes.byref(f), None, ctypes.byref(params),
+                                                    grid.ctypes.data_as(ctypes.c_void_p), None) == sage.ERR_INVALID
+    msg = sage.lib().sageicp_last_error().decode()
+    assert "device frame" in msg or "too large" in msg, msg
+    assert "device memory" not in msg
+
+
 def test_null_frame_and_null_handles(sage, pipeline):
     assert _register(sage, pipeline, None) == sage.ERR_INVALID
     f = _frame(sage)
