@@ -393,41 +393,43 @@ __device__ __forceinline__ long long dpp_i64(long long v) {
     hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
     return (static_cast<long long>(hi) << 32) | static_cast<unsigned>(lo);
 }
-// lane i <- lane i + N (the lanes this is used on — the first lanes of queries — always have their partner
-// inside the wave; shifts below 16 stay inside a row of 16 lanes: DPP row_shl, no LDS traffic)
+// lane i <- lane i + N (the lanes whose results are used — those of the first query of a block — always have
+// their partner inside the wave; shifts below 16 stay inside a row of 16 lanes: DPP row_shl, no LDS traffic)
 template <int N>
 __device__ __forceinline__ double lane_shl_f64(double v) {
     if constexpr (N < 16) return dpp_f64<0x100 + N>(v);
     else return __shfl_down(v, N, 64);
 }
 
-// A wave's 16 pair terms per query (t[], on the first lane of every query; zeros for a query without a pair)
-// -> block sums -> digits -> added into the workgroup's accumulators `wgacc` (LDS, kWgAccWords 64-bit words).
-// `red` = LDS scratch of this wave, 16 fp64 per block.
+// A wave's 16 pair terms per query -> block sums -> digits -> added into the workgroup's accumulators `wgacc`
+// (LDS, kWgAccWords 64-bit words).  The terms are spread over the W lanes of a query: lane ci holds components
+// ci K .. ci K + K - 1 (K = 16 / W; zeros for a query without a pair).  `red` = LDS scratch of this wave, 16 fp64
+// per block.
 template <int LW>
-__device__ __forceinline__ void wave_terms_to_wgacc(const double (&t)[kCount], unsigned pairs, int lane, double *red,
+__device__ __forceinline__ void wave_terms_to_wgacc(const double (&t)[kCount >> LW], unsigned pairs, int lane, double *red,
                                                     unsigned long long *wgacc, double limit, double scale) {
-    constexpr int W = 1 << LW, QW = 64 >> LW, NBLK = QW / 4;
-    // A. block sums, (t0 + t1) + (t2 + t3), on the first lane of every block
-    double y[kCount];
+    constexpr int W = 1 << LW, QW = 64 >> LW, NBLK = QW / 4, K = kCount >> LW;
+    // A. block sums, (t0 + t1) + (t2 + t3), on the lanes of the first query of every block
+    double y[K];
 #pragma unroll
-    for (int c = 0; c < kCount; ++c) {
-        const double x = t[c] + lane_shl_f64<W>(t[c]);
-        y[c] = x + lane_shl_f64<2 * W>(x);
+    for (int k = 0; k < K; ++k) {
+        const double x = t[k] + lane_shl_f64<W>(t[k]);
+        y[k] = x + lane_shl_f64<2 * W>(x);
     }
-    // B. four blocks at a time (512 B of scratch whatever the lanes per query): the blocks' first lanes park
-    // their 16 sums, C. lane (c, j) = (lane >> 2, lane & 3) converts component c of block j
+    // B. four blocks at a time (512 B of scratch whatever the lanes per query): the lanes of the blocks' first
+    // queries park their K sums each (component-major: the block's 16 in order), C. lane (c, j) = (lane >> 2,
+    // lane & 3) converts component c of block j
     const int c = lane >> 2, j = lane & 3;
     long long d0 = 0, d1 = 0, d2 = 0;
     bool ok = true;
     const int blk = lane / (4 * W);
-    const bool first = (lane & (4 * W - 1)) == 0;
+    const bool first = (lane & (4 * W - 1)) < W;
 #pragma unroll
     for (int r = 0; r < NBLK; r += 4) {
         if (first && blk >= r && blk < r + 4) {
-            double *dst = red + (blk - r) * kCount;
+            double *dst = red + (blk - r) * kCount + (lane & (W - 1)) * K;
 #pragma unroll
-            for (int cc = 0; cc < kCount; ++cc) dst[cc] = y[cc];
+            for (int k = 0; k < K; ++k) dst[k] = y[k];
         }
         // (values pass from lane to lane through LDS here: the hardware serves a wave's LDS instructions in
         // order, but the COMPILER has to be told that the loads below see other lanes' stores)
@@ -1359,36 +1361,46 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
             LP_T(6);
         }
         PROBE_NN_WORK(P, q, valid && ci == 0u, npairs);
-        // Branch-free: every lane computes the terms of "its" pair from operands that are zeroed unless it is the
-        // first lane of a query with an accepted answer (the products are then exact zeros of either sign, which
-        // the block sums and their digits do not tell apart) — clearing sixteen fp64 registers twice around two
-        // nested branches cost more than the selects.
-        double t[kCount];
-        const bool cand = found && ci == 0u;
-        if constexpr (!PERSIST) g = load_point(pts, cand ? woff : 0u);      // (the other lanes re-read record 0: no branch)
+        // Branch-free: every lane of a query computes the terms of the query's pair and keeps the K = 16 / W of
+        // them wave_terms_to_wgacc takes from it (components ci K .. ci K + K - 1), zeroed unless the query has an
+        // accepted answer (exact zeros of either sign, which the block sums and their digits do not tell apart).
+        // One lane per query (W = 1) zeroes the operands instead: clearing sixteen fp64 registers twice around
+        // two nested branches cost more than the selects.
+        constexpr int K = kCount >> LW;
+        double t[K];
+        if constexpr (!PERSIST) g = load_point(pts, found ? woff : 0u);     // (a query without an answer re-reads record 0: no branch)
         const double rx0 = s.x - g.x, ry0 = s.y - g.y, rz0 = s.z - g.z;
         // (closest_neighboor - point).head<3>().norm() < max_correspondance_distance (VoxelHashMap.cpp:111)
-        const bool use = cand && SAGE_SQNORM3_ACCEPT(rx0 * rx0, ry0 * ry0, rz0 * rz0) <= P.accept_r2;
+        const bool use = found && SAGE_SQNORM3_ACCEPT(rx0 * rx0, ry0 * ry0, rz0 * rz0) <= P.accept_r2;
         {
             // residual.squaredNorm() (Registration.cpp:79): its own reduction (sageicp_types.h)
             const double r2 = SAGE_SQNORM3_RESID(rx0 * rx0, ry0 * ry0, rz0 * rz0);
             const double k = P.kernel;
             const double den = k + r2;
             const double wq = (k * k) / (den * den);   // square(th) / square(th + residual2)
-            const double w = use ? wq : 0.0;
-            const double sx = use ? s.x : 0.0, sy = use ? s.y : 0.0, sz = use ? s.z : 0.0;
-            const double rx = use ? rx0 : 0.0, ry = use ? ry0 : 0.0, rz = use ? rz0 : 0.0;
+            const bool z = W == 1;                     // zero the operands (W = 1) or the kept terms
+            const double w = !z || use ? wq : 0.0;
+            const double sx = !z || use ? s.x : 0.0, sy = !z || use ? s.y : 0.0, sz = !z || use ? s.z : 0.0;
+            const double rx = !z || use ? rx0 : 0.0, ry = !z || use ? ry0 : 0.0, rz = !z || use ? rz0 : 0.0;
             const double wsx = w * sx, wsy = w * sy, wsz = w * sz;
-            t[kW] = w;
-            t[kWsx] = wsx; t[kWsy] = wsy; t[kWsz] = wsz;
-            t[kWxx] = wsx * sx; t[kWxy] = wsx * sy; t[kWxz] = wsx * sz;
-            t[kWyy] = wsy * sy; t[kWyz] = wsy * sz; t[kWzz] = wsz * sz;
-            t[kWrx] = w * rx; t[kWry] = w * ry; t[kWrz] = w * rz;
-            t[kWcx] = w * (sy * rz - sz * ry);
-            t[kWcy] = w * (sz * rx - sx * rz);
-            t[kWcz] = w * (sx * ry - sy * rx);
+            double u[kCount];
+            u[kW] = w;
+            u[kWsx] = wsx; u[kWsy] = wsy; u[kWsz] = wsz;
+            u[kWxx] = wsx * sx; u[kWxy] = wsx * sy; u[kWxz] = wsx * sz;
+            u[kWyy] = wsy * sy; u[kWyz] = wsy * sz; u[kWzz] = wsz * sz;
+            u[kWrx] = w * rx; u[kWry] = w * ry; u[kWrz] = w * rz;
+            u[kWcx] = w * (sy * rz - sz * ry);
+            u[kWcy] = w * (sz * rx - sx * rz);
+            u[kWcz] = w * (sx * ry - sy * rx);
+#pragma unroll
+            for (int kk = 0; kk < K; ++kk) {
+                double v = u[kk];
+#pragma unroll
+                for (int l = 1; l < W; ++l) v = ci == static_cast<unsigned>(l) ? u[l * K + kk] : v;
+                t[kk] = z || use ? v : 0.0;
+            }
         }
-        const unsigned pairs = static_cast<unsigned>(__popcll(__ballot(use)));
+        const unsigned pairs = static_cast<unsigned>(__popcll(__ballot(use && ci == 0u)));
         if constexpr (PERSIST) {
             // k_loop: block sums -> exact digits -> the workgroup's accumulators (the rows stay: the scratch
             // is the running wave's own)
