@@ -525,7 +525,7 @@ int sageicp_get_correspondences(const sageicp_map *m, const double *q, uint64_t 
                       s));
     const int lw = icp_lw(n, sparse_voxels(m));
     if ((rc = ensure_cand(m, wants_filter(m, n, sem_th)))) return rc;
-    const IcpParams ip = icp_params(m, sc.d_sorted.data(), n, sem_th, lw);     // identity pose, no loop state
+    const IcpParams ip = icp_params(m, sc.d_sorted.data(), n, sem_th, lw, 0);  // identity pose, no loop state
     launch_rows(ip, s);
     launch_icp(ip, lw, false, s);
     HIPCHK(hipGetLastError());

@@ -155,7 +155,7 @@ struct Scratch {
     DevBuf<double> d_partials;
     DevBuf<long long> d_acc;       // fixed-point accumulators of the Gauss-Newton sums (kernels.h, kAcc*)
     DevBuf<LoopShared> d_loop;     // what the workgroups of k_loop share inside its launch (kernels.h)
-    unsigned long long go_word = 0; // (host source of a `go` word sent by a copy: run_icp)
+    unsigned long long go_word = 0; // (host source of a `go` word sent by a copy: SolverGuard)
     hipStream_t stream2 = nullptr; // the solving wave of the one-launch loop runs here, beside the grid on `stream`
                                    // (created with the first such launch: a process has few hardware queues, and
                                    // streams that never run anything still take their turn on them)
@@ -867,7 +867,7 @@ struct sageicp_comm {
 
 // ---- the library's translation units call each other through these --------------------------------------
 // capi.hip: the C ABI.  capi_mirror.hip: the HBM mirror of a map and Update() on the device.  capi_run.hip: the ICP
-// loop (plan_loop, run_icp), the RCCL binding and the single-process multi-GPU mode.
+// loop (plan_loop, run_icp and its attempts), the RCCL binding and the single-process multi-GPU mode.
 namespace sageicp_impl {
 struct Rccl {
     void *h = nullptr;
@@ -899,7 +899,7 @@ void identity_pose(double T[7]);
 void fill_state(IcpState *st, const double init[7]);
 bool sparse_voxels(const sageicp_map *m);
 bool wants_filter(const sageicp_map *m, uint64_t n, double sem_th);
-IcpParams icp_params(const sageicp_map *m, const Point4 *d_queries, uint64_t n, double sem_th, int lw);
+IcpParams icp_params(const sageicp_map *m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift);
 int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const double init[7], double max_dist, double kernel,
             double sem_th, sageicp_comm *comm, double out[7], sageicp_stats *stats, double us_upload, double t_begin);
 int device_update_all(sageicp_map *m, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points);

@@ -89,16 +89,9 @@ static bool wants_flat(const sageicp_map *m, int lw) {
     return env_int("SAGEICP_FLAT", mp < (2ull << lw) * mv ? 1 : 0) != 0;
 }
 
-// (raised while a frame whose sums left the range of the fixed-point accumulators is registered again at a
-// coarser scale: the sums are accumulated at 2^(-24 g_acc_shift) of their value — see the end of run_icp)
-static thread_local int g_acc_shift = 0;
-// (a frame started again because a peer rank left its one-launch loop: see the end of run_icp)
-static thread_local int g_restarts = 0;
-static thread_local bool g_no_loop = false;
-static thread_local bool g_no_chain = false;     // (a frame registered again after its chained launches timed out)
-
-// k_icp's arguments for a search of `n` queries against the HBM copy of `m`
-IcpParams icp_params(const sageicp_map *m, const Point4 *d_queries, uint64_t n, double sem_th, int lw) {
+// k_icp's arguments for a search of `n` queries against the HBM copy of `m`; the sums are accumulated at
+// 2^(-24 acc_shift) of their value (run_icp raises the shift for a frame whose sums left the fixed-point range)
+IcpParams icp_params(const sageicp_map *m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift) {
     const Scratch &sc = m->sc;
     IcpParams ip{};
     ip.frame = d_queries;
@@ -141,7 +134,7 @@ IcpParams icp_params(const sageicp_map *m, const Point4 *d_queries, uint64_t n, 
     ip.accept_r2 = -1.0;
     ip.nn_prev = sc.d_prev.data();
     ip.work = sc.d_work.data();
-    ip.acc_scale = std::ldexp(1.0, -24 * std::max(g_acc_shift, std::min(2, std::max(0, env_int("SAGEICP_ACC_SHIFT", 0)))));
+    ip.acc_scale = std::ldexp(1.0, -24 * std::max(acc_shift, std::min(2, std::max(0, env_int("SAGEICP_ACC_SHIFT", 0)))));
     {
         // k_fin adds the accumulator copies in 64-bit integers: blocks x limit < 2^62 (kernels.hip, kDigitLimitCounted)
         const uint64_t blocks = std::max<uint64_t>(1, (n + 3) / 4);
@@ -300,79 +293,58 @@ static bool plan_loop(const sageicp_map *m, uint64_t n, double sem_th, LoopPlan 
     return ok;
 }
 
-// The ICP loop of Registration.cpp:127-138 as a stream of launches: k_icp (search + accumulation)
-// and k_fin (reduce, solve, compose, test) per iteration — or, for a frame that fits the machine
-// and is not sharded over GPUs, as ONE launch (k_loop).
-// (raised while a frame whose sums left the range of the fixed-point accumulators is registered again
-// at a coarser scale — see the end of run_icp)
+// ---- run_icp: the ICP loop of Registration.cpp:127-138, in one of three forms ---------------------------
+//   one launch         k_loop beside its solving wave: a frame that fits the machine (plan_loop), not sharded by RCCL;
+//   chained launches   a k_icp launch per iteration beside the same solving wave, no k_fin between them: frames
+//                      beyond the LDS on one GPU;
+//   k_icp + k_fin      a launch per iteration with the solve between the launches, polled through a host-mapped
+//                      word or (RCCL: every rank enqueues the same all-reduces) in fixed chunks.
+// A call is a sequence of ATTEMPTS (run_icp); every attempt plans again, and a frame is registered again
+//   1. inside an attempt, when a wait of its one-launch loop timed out or a peer left it: with k_icp + k_fin, on the
+//      same plan and the same sorted frame (run_one_launch, run_attempt);
+//   2. without the chain, when the chained launches timed out (Iterations::run_polled);
+//   3. without the one-launch loop, when a peer rank lost ITS one-launch loop while this rank was in k_fin form;
+//   4. at a coarser accumulator scale, when a Gauss-Newton sum left the fixed-point range (2 - 4: run_icp).
+struct Attempt {
+    int acc_shift = 0;          // the sums are accumulated at 2^(-24 acc_shift) of their value
+    int restarts = 0;           // times the frame was started again after a peer left its one-launch loop
+    bool no_loop = false;       // ... after which: lanes per query as the plan says; the loop form not again for this frame
+    bool no_chain = false;      // the chained launches of this frame timed out
+};
 
+// What the attempts of a call share: its arguments and what follows from them and the knobs alone.
+struct IcpCall {
+    const sageicp_map *m;
+    const Point4 *d_frame;
+    uint64_t n;
+    const double *init;
+    double max_dist, kernel, sem_th;
+    sageicp_comm *comm;
+    Scratch &sc;                // (m's)
+    hipStream_t s;              // (sc.stream)
+    bool p2p, polled, prof, prof2, counting;
+    int max_it;
+    P2pParams xp;               // direct exchange of the sums with the peer GPUs (k_fin mode 3, or the solving wave)
 
-int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const double init[7],
-            double max_dist, double kernel, double sem_th, sageicp_comm *comm, double out[7],
-            sageicp_stats *stats, double us_upload, double t_begin) {
-    Scratch &sc = m->sc;
-    hipStream_t s = sc.stream;
-    if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
-    int rc;
-    const bool prof = g_profiling != 0;
-    const bool prof2 = g_profiling >= 2;
-    // Single GPU: iterations are enqueued a few ahead of the GPU, which reports its progress
-    // through a host-mapped word (no stream synchronisation inside the loop).  With an RCCL
-    // communicator every rank must enqueue the same number of all-reduces, so the loop advances
-    // in fixed chunks (4, 8, 16, 16, ...) with one synchronisation per chunk instead.
-    const bool p2p = comm && comm->p2p;
-    if (comm && !p2p && !comm->comm)
-        return fail(SAGEICP_ERR_INVALID, "communicator without RCCL needs a connected p2p exchange");
-    // (the direct exchange enqueues no collective, so its loop can be polled like the 1-GPU one)
-    const bool polled = (!comm || p2p) && env_int("SAGEICP_CHUNKED", 0) == 0;
-    if (prof && (rc = sc.reserve_events(polled ? kMaxIterations : kChunkMax))) return rc;
-    // (probes only: SAGEICP_MAX_ITER stops either loop early — the launch-per-iteration loop then simply runs out of launches)
-    const int max_it = std::min(kMaxIterations, std::max(1, env_int("SAGEICP_MAX_ITER", kMaxIterations)));
-
-    fill_state(sc.h_state.data(), init);
-    if (polled) {
-        std::memset(sc.h_prog.data(), 0, sizeof(IcpProgress));
-        sc.h_state.data()->progress = sc.d_prog;
-    }
-    HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
-
-    // Lanes per query are decided in ONE place, whichever loop then runs: a frame that fits the one-launch
-    // loop takes that loop's choice also when the launch-per-iteration loop registers it (a launch that timed
-    // out, the calls of the cool-down after it) — the fixed-point sums are rounded once per group of queries,
-    // so their bits depend on the lanes per query and on nothing else, and a call repeated gives the same bits.
-    LoopPlan plan{};
-    // (SAGEICP_CHUNKED=1 asks for the chunked launch-per-iteration loop by name)
-    const bool loop_shape = (!comm || (p2p && !comm->device_shared && env_int("SAGEICP_CHUNKED", 0) == 0)) &&
-                            plan_loop(m, n, sem_th, &plan);
-    const bool restarted = g_no_loop;          // (lanes per query as the plan says; the loop form not again for this frame)
-    const int lw = loop_shape ? plan.lw : icp_lw(n, sparse_voxels(m));
-    // a launch that timed out (its grid was not resident as a whole: the GPU is shared with other work)
-    // cost 50 ms before the frame went through the other loop: the next calls do not try again
-    bool use_loop = loop_shape && !restarted;
-    sc.last_fallback = !loop_shape ? SAGEICP_LOOP_FALLBACK_DOES_NOT_FIT : (restarted ? SAGEICP_LOOP_FALLBACK_PEER : SAGEICP_LOOP_FALLBACK_NONE);
-    if (use_loop && sc.loop_cooldown > 0) {
-        --sc.loop_cooldown;
-        use_loop = false;
-        sc.last_fallback = SAGEICP_LOOP_FALLBACK_COOLDOWN;
-    }
-    const unsigned loop_waves = use_loop ? static_cast<unsigned>((n + (64u >> plan.lw) - 1) / (64u >> plan.lw)) : 0u;
-    if ((rc = ensure_cand(m, wants_filter(m, n, sem_th)))) return rc;
-    if ((rc = sc.reserve_sort(n))) return rc;
-    IcpParams ip = icp_params(m, sc.d_sorted.data(), n, sem_th, lw);
-    ip.check_done = 1;
-    ip.apply_pose = 1;
-    ip.kernel = kernel;
-    ip.accept_r2 = accept_threshold(max_dist);
-    // (the counters behind sum_candidates / pairs_evaluated cost ~45 vector instructions per pass, a memset and a
-    // launch per frame: a caller that wants the other statistics only — bench.py's timed region — switches them off)
-    const bool counting = stats && g_counting != 0;
-    ip.counters = counting ? sc.d_cand.data() : nullptr;
-    if (counting) HIPCHK(hipMemsetAsync(sc.d_cand.data(), 0, sizeof(unsigned long long) * 2 * (std::max(ip.nwaves, loop_waves) + 1), s));
-
-    // direct exchange of the sums with the peer GPUs (k_fin mode 3, or the solving wave of the one-launch loop)
-    P2pParams xp{};
-    xp.nranks = 1;
-    if (p2p) {
+    int constants(bool want_stats) {
+        prof = g_profiling != 0;
+        prof2 = g_profiling >= 2;
+        // Single GPU: iterations are enqueued a few ahead of the GPU, which reports its progress
+        // through a host-mapped word (no stream synchronisation inside the loop).  With an RCCL
+        // communicator every rank must enqueue the same number of all-reduces, so the loop advances
+        // in fixed chunks (4, 8, 16, 16, ...) with one synchronisation per chunk instead.
+        p2p = comm && comm->p2p;
+        if (comm && !p2p && !comm->comm)
+            return fail(SAGEICP_ERR_INVALID, "communicator without RCCL needs a connected p2p exchange");
+        // (the direct exchange enqueues no collective, so its loop can be polled like the 1-GPU one)
+        polled = (!comm || p2p) && env_int("SAGEICP_CHUNKED", 0) == 0;
+        // (probes only: SAGEICP_MAX_ITER stops either loop early — the launch-per-iteration loop then simply runs out of launches)
+        max_it = std::min(kMaxIterations, std::max(1, env_int("SAGEICP_MAX_ITER", kMaxIterations)));
+        // (the counters behind sum_candidates / pairs_evaluated cost ~45 vector instructions per pass, a memset and a
+        // launch per frame: a caller that wants the other statistics only — bench.py's timed region — switches them off)
+        counting = want_stats && g_counting != 0;
+        xp.nranks = 1;
+        if (!p2p) return SAGEICP_OK;
         xp.nranks = comm->nranks;
         xp.rank = comm->rank;
         for (int r = 0; r < comm->nranks; ++r) xp.block[r] = comm->blocks[r];
@@ -380,119 +352,29 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
         // a peer's sums normally arrive within microseconds, but its FIRST launches of a process (code
         // object loading) or a GPU shared with other work can take a second: five seconds of in-kernel
         // waiting is a failure (SAGEICP_P2P_TIMEOUT_S overrides, e.g. under a debugger)
-        xp.timeout_ticks = 100000000ull * static_cast<unsigned long long>(
-                               std::max(1, env_int("SAGEICP_P2P_TIMEOUT_S", 5)));
+        xp.timeout_ticks = 100000000ull * static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_P2P_TIMEOUT_S", 5)));
         if (const int ticks = env_int("SAGEICP_P2P_TIMEOUT_TICKS", 0))      // tests: provoke a timeout
             xp.timeout_ticks = static_cast<unsigned long long>(ticks);
+        return SAGEICP_OK;
     }
-    LoopParams L{};
-    // The solving wave is launched well before its grid; should this call leave in between (an allocation or a launch
-    // failing), it must not sit there waiting for a grid that never comes (and write its abort into the state of a
-    // later call): the guard sends it home with the word the grid would have sent for a frame it refuses.
-    struct SolverGuard {
-        Scratch *sc = nullptr;
-        unsigned long long epoch = 0;
-        ~SolverGuard() {
-            if (!sc) return;
-            const unsigned long long word = epoch | 0x8000000000000000ull;
-            (void)hipMemcpyAsync(&sc->d_loop.data()->go[0], &word, sizeof(word), hipMemcpyHostToDevice, sc->stream);
-            (void)hipStreamSynchronize(sc->stream);
-            (void)hipStreamSynchronize(sc->stream2);
+    // the state of a registration that starts at `init`, on its way to the device
+    int start_state() const {
+        fill_state(sc.h_state.data(), init);
+        if (polled) {
+            std::memset(sc.h_prog.data(), 0, sizeof(IcpProgress));
+            sc.h_state.data()->progress = sc.d_prog;
         }
-    } solver_guard;
-    // Frames beyond the LDS on one GPU: the launches of the iterations CHAINED (kernels.h, IcpParams::chain) — no k_fin between
-    // them, the solving wave of the one-launch loop resident beside them.  (Not after a one-launch loop that timed out in this
-    // call or its cool-down: a GPU that did not hold that grid is not asked to hold a resident solving wave either.)
-    const int chain_grid = n > 0 ? icp_blocks_for(static_cast<int>(n), lw) : 0;
-    // (profiling level 2 asks for the time of every kernel of every iteration, k_fin's too: the form with k_fin)
-    // (Under a communicator with the direct exchange the form exists too — the exchange is the solving wave's, as in the
-    // one-launch loop; parity-green and in step when a rank loses it, tests/test_gpu_parity.py — but it is OFF unless
-    // SAGEICP_CHAIN_COMM=1: the only place it could be measured, two processes sharing one GPU, runs c4 twice as slowly
-    // with it (42.7 against 21.0 ms per frame: the waiting launches of two processes on one device's queues,
-    // profiles/r06/run63.sh); on a GPU per rank it has never run.  Never for several ranks of one process on one device.)
-    const bool chain_comm = comm && p2p && !comm->device_shared && env_int("SAGEICP_CHAIN_COMM", 0) != 0;
-    const bool chain = !loop_shape && (!comm || chain_comm) && polled && n > 0 &&
-                       chain_grid / kChainReplicas <= 255 && !g_no_chain && !prof2 && env_int("SAGEICP_CHAIN", 1) != 0;
-    if ((use_loop || chain) && (rc = sc.loop_streams())) return rc;
-    if (chain) {
-        L.sh = sc.d_loop.data();
-        L.st = sc.d_state.data();
-        L.wgs = chain_grid;                       // every workgroup of a launch sends its sums, also the ones past the frame's end
-        L.copies = kChainReplicas;
-        L.progress = sc.d_prog;
-        L.timeout_ticks = 100000ull * static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_LOOP_TIMEOUT_MS", 50)));
-        if (const int ticks = env_int("SAGEICP_LOOP_TIMEOUT_TICKS", 0)) L.timeout_ticks = static_cast<unsigned long long>(ticks);
-        // (the solving wave waits for a whole LAUNCH here, not for resident workgroups: the first launch of a process
-        // loads code objects, a big frame's launch takes its hundred microseconds)
-        L.count_timeout_ticks = std::max<unsigned long long>(L.timeout_ticks, 20ull * 100000ull) * 10ull;
-        if (comm) {
-            // (as for the one-launch loop: a launch waits for a pose that waits for the peers' sums — its patience has to
-            // outlast the exchange's; the solving wave's wait for its OWN launch stays local)
-            L.shared_loop = 1;
-            if (env_int("SAGEICP_LOOP_TIMEOUT_TICKS", 0) == 0)
-                L.timeout_ticks = std::max(L.timeout_ticks, xp.timeout_ticks + 100000000ull);
-            // (tests: ONE rank of a communicator loses its launches — the others must follow it out of the exchange)
-            if (env_int("SAGEICP_LOOP_COUNT_TIMEOUT_RANK", -1) == comm->rank)
-                L.count_timeout_ticks = static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_LOOP_COUNT_TIMEOUT_TICKS", 1)));
-        }
-        L.max_iterations = max_it;
-        L.epoch = ++sc.loop_epoch;
-        for (int i = 0; i < 7; ++i) L.T0[i] = init[i];
-        L.acc_unscale = 1.0 / ip.acc_scale;
-        launch_loop_solve(L, xp, sc.stream2);
+        HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
+        return SAGEICP_OK;
+    }
+    // ... and back on the host once everything enqueued has run (the counters of `nwaves` waves summed first)
+    int fetch_state(unsigned nwaves) const {
+        if (counting) launch_sum_counters(sc.d_cand.data(), static_cast<int>(nwaves), sc.d_state.data(), s);
         HIPCHK(hipGetLastError());
-        solver_guard.sc = &sc;
-        solver_guard.epoch = L.epoch;
-        HIPCHK(hipEventRecord(sc.ev_solve, sc.stream2));
+        HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return SAGEICP_OK;
     }
-    if (use_loop) {
-        // ---- the whole loop in one launch (kernels.hip, k_loop): first its solving wave, on its own stream —
-        // it has to hold its registers before the grid fills the machine; it waits for the grid's go
-        L.sh = sc.d_loop.data();
-        L.st = sc.d_state.data();
-        L.nw = plan.nw;
-        L.gpw = plan.gpw;
-        L.wgs = plan.wgs;
-        L.copies = kLoopReplicas;
-        L.progress = nullptr;
-        L.contiguous = env_int("SAGEICP_LOOP_CONTIGUOUS", 0) ? 1 : 0;
-        {
-            const uint64_t qw = 64u >> plan.lw, groups = (n + qw - 1) / qw;
-            for (int x = 0; x <= 8; ++x) L.xcd_first[x] = static_cast<uint32_t>(groups * x / 8);
-            // (an XCD's workgroups must be able to hold its range)
-            const uint64_t nwg = static_cast<uint64_t>(plan.wgs / 8);
-            for (int x = 0; x < 8; ++x)
-                if (L.contiguous == 1 && (L.xcd_first[x + 1] - L.xcd_first[x] + nwg - 1) / nwg > static_cast<uint64_t>(plan.gpw)) L.contiguous = 0;
-        }
-        // a wait inside the launch normally takes microseconds; 50 ms of it means the grid is not
-        // resident as a whole (SAGEICP_LOOP_TIMEOUT_MS overrides, e.g. under a debugger)
-        L.timeout_ticks = 100000ull * static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_LOOP_TIMEOUT_MS", 50)));
-        if (const int ticks = env_int("SAGEICP_LOOP_TIMEOUT_TICKS", 0))      // tests: provoke a timeout
-            L.timeout_ticks = static_cast<unsigned long long>(ticks);
-        // (under a communicator the workgroups wait for a pose that waits for the peers' sums: their patience has
-        // to outlast the exchange's — a peer's first launches of a process can take a second)
-        L.count_timeout_ticks = L.timeout_ticks;       // (the solving wave's wait for its own workgroups: local, short)
-        if (comm && env_int("SAGEICP_LOOP_TIMEOUT_TICKS", 0) == 0)
-            L.timeout_ticks = std::max(L.timeout_ticks, xp.timeout_ticks + 100000000ull);
-        // (tests: ONE rank of a communicator loses its grid — the others must follow it out of the launch)
-        if (comm && env_int("SAGEICP_LOOP_COUNT_TIMEOUT_RANK", -1) == comm->rank)
-            L.count_timeout_ticks = static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_LOOP_COUNT_TIMEOUT_TICKS", 1)));
-        L.max_iterations = max_it;
-        L.epoch = ++sc.loop_epoch;
-        for (int i = 0; i < 7; ++i) L.T0[i] = init[i];
-        L.acc_unscale = 1.0 / ip.acc_scale;
-        L.shared_loop = comm ? 1 : 0;
-        L.prio = std::min(3, std::max(0, env_int("SAGEICP_LOOP_PRIO", 3)));
-        L.deal = env_int("SAGEICP_LOOP_DEAL", 1) ? 1 : 0;
-#ifndef SAGE_LOOP_INGRID          // (the counter-collection twin keeps the solving wave inside the grid: kernels.hip)
-        launch_loop_solve(L, xp, sc.stream2);
-        HIPCHK(hipGetLastError());
-        solver_guard.sc = &sc;
-        solver_guard.epoch = L.epoch;
-        HIPCHK(hipEventRecord(sc.ev_solve, sc.stream2));
-#endif
-    }
-
     // Spatial ordering of the frame: the loop runs on a copy sorted by map-frame voxel under the
     // initial guess, so that the queries of a wave share home voxels and neighbouring waves touch
     // neighbouring voxel blocks (L1 / L2 hits, similar work per lane), and every query's
@@ -500,132 +382,292 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
     // query crosses a voxel face.  (Round 1 re-sorted when the pose had drifted half a voxel; with a
     // lane per query that no longer pays for its ~90 us: 45.3 against 47.2 us per iteration on the
     // c2 cold start, profiles/README.md.)
-    // ... from kSortFrameFrom points on (kernels.h); SAGEICP_SORT_FROM overrides the size (0: always sorted)
-    if (n > 0 && n < static_cast<uint64_t>(std::max(0, env_int("SAGEICP_SORT_FROM", kSortFrameFrom))))
-        HIPCHK(check_copy_frame(d_frame, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), comm == nullptr, s));
-    else if (n > 0)
-        HIPCHK(sort_frame(d_frame, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), true, comm == nullptr,
-                          m->host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(),
-                          sc.d_sort_temp.capacity(), s));
+    int order_frame() const {
+        // ... from kSortFrameFrom points on (kernels.h); SAGEICP_SORT_FROM overrides the size (0: always sorted)
+        if (n > 0 && n < static_cast<uint64_t>(std::max(0, env_int("SAGEICP_SORT_FROM", kSortFrameFrom))))
+            HIPCHK(check_copy_frame(d_frame, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), comm == nullptr, s));
+        else if (n > 0)
+            HIPCHK(sort_frame(d_frame, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), true, comm == nullptr,
+                              m->host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(),
+                              sc.d_sort_temp.capacity(), s));
+        return SAGEICP_OK;
+    }
+};
 
-    double us_nn = 0, us_fin = 0;
-    uint32_t nn_launches = 0;
-    bool looped = false;
-    if (use_loop) {
-        // ---- ... then the grid (the shared block zeroed first: the solving wave starts on the grid's go)
-        if (prof && (rc = sc.reserve_events(1))) return rc;
-        IcpParams lp = ip;
-        lp.filter = plan.filter ? ip.filter : 0;
-        lp.nwaves = loop_waves;
-        HIPCHK(hipMemsetAsync(sc.d_loop.data(), 0, offsetof(LoopShared, acc32), s));      // (the chained launches' copies are not this loop's)
-        if (prof) HIPCHK(hipEventRecord(sc.events[1], s));
-        launch_loop(lp, L, plan.lw, s);
-        if (hipPeekAtLastError() == hipSuccess) solver_guard.sc = nullptr;      // the grid is on its way: it will say go
-        if (prof) HIPCHK(hipEventRecord(sc.events[2], s));
-#ifndef SAGE_LOOP_INGRID
-        HIPCHK(hipStreamWaitEvent(s, sc.ev_solve, 0));             // the solving wave writes the final state
+// What an attempt runs: lanes per query, the one-launch loop's shape and whether it is used, whether the launches
+// are chained.  Leaves the cool-down bookkeeping and last_fallback of the handle as this attempt found them.
+struct AttemptPlan {
+    LoopPlan loop{};            // (valid where loop_shape)
+    bool loop_shape = false, use_loop = false, chain = false;      // the frame fits the one-launch loop; this attempt runs it
+    int lw = 0, chain_grid = 0;
+    unsigned loop_waves = 0;
+};
+static AttemptPlan plan_attempt(const IcpCall &c, const Attempt &a) {
+    Scratch &sc = c.sc;
+    const sageicp_comm *comm = c.comm;
+    const uint64_t n = c.n;
+    AttemptPlan p;
+    // Lanes per query are decided in ONE place, whichever loop then runs: a frame that fits the one-launch
+    // loop takes that loop's choice also when the launch-per-iteration loop registers it (a launch that timed
+    // out, the calls of the cool-down after it) — the fixed-point sums are rounded once per group of queries,
+    // so their bits depend on the lanes per query and on nothing else, and a call repeated gives the same bits.
+    // (SAGEICP_CHUNKED=1 asks for the chunked launch-per-iteration loop by name)
+    p.loop_shape = (!comm || (c.p2p && !comm->device_shared && env_int("SAGEICP_CHUNKED", 0) == 0)) &&
+                   plan_loop(c.m, n, c.sem_th, &p.loop);
+    p.lw = p.loop_shape ? p.loop.lw : icp_lw(n, sparse_voxels(c.m));
+    // a launch that timed out (its grid was not resident as a whole: the GPU is shared with other work)
+    // cost 50 ms before the frame went through the other loop: the next calls do not try again
+    p.use_loop = p.loop_shape && !a.no_loop;
+    sc.last_fallback = !p.loop_shape ? SAGEICP_LOOP_FALLBACK_DOES_NOT_FIT : (a.no_loop ? SAGEICP_LOOP_FALLBACK_PEER : SAGEICP_LOOP_FALLBACK_NONE);
+    // (every attempt of a call comes through here: a frame registered again during a cool-down takes one cool-down
+    // call per attempt, as it did when the attempts were recursive calls)
+    if (p.use_loop && sc.loop_cooldown > 0) {
+        --sc.loop_cooldown;
+        p.use_loop = false;
+        sc.last_fallback = SAGEICP_LOOP_FALLBACK_COOLDOWN;
+    }
+    p.loop_waves = p.use_loop ? static_cast<unsigned>((n + (64u >> p.loop.lw) - 1) / (64u >> p.loop.lw)) : 0u;
+    // Frames beyond the LDS on one GPU: the launches of the iterations CHAINED (kernels.h, IcpParams::chain) — no k_fin between
+    // them, the solving wave of the one-launch loop resident beside them.  (Not after a one-launch loop that timed out in this
+    // call or its cool-down: a GPU that did not hold that grid is not asked to hold a resident solving wave either.)
+    p.chain_grid = n > 0 ? icp_blocks_for(static_cast<int>(n), p.lw) : 0;
+    // (profiling level 2 asks for the time of every kernel of every iteration, k_fin's too: the form with k_fin)
+    // (Under a communicator with the direct exchange the form exists too — the exchange is the solving wave's, as in the
+    // one-launch loop; parity-green and in step when a rank loses it, tests/test_gpu_parity.py — but it is OFF unless
+    // SAGEICP_CHAIN_COMM=1: the only place it could be measured, two processes sharing one GPU, runs c4 twice as slowly
+    // with it (42.7 against 21.0 ms per frame: the waiting launches of two processes on one device's queues,
+    // profiles/r06/run63.sh); on a GPU per rank it has never run.  Never for several ranks of one process on one device.)
+    const bool chain_comm = comm && c.p2p && !comm->device_shared && env_int("SAGEICP_CHAIN_COMM", 0) != 0;
+    p.chain = !p.loop_shape && (!comm || chain_comm) && c.polled && n > 0 &&
+              p.chain_grid / kChainReplicas <= 255 && !a.no_chain && !c.prof2 && env_int("SAGEICP_CHAIN", 1) != 0;
+    return p;
+}
+
+// Is the solving wave a launch of its own (k_loop_solve on stream2)?  Always beside chained launches; beside k_loop
+// except in the counter-collection twin, which keeps it inside the grid (kernels.hip, SAGE_LOOP_INGRID).
+static bool solver_is_own_launch(const AttemptPlan &p) {
+#ifdef SAGE_LOOP_INGRID
+    return p.chain;
+#else
+    return p.chain || p.use_loop;
 #endif
-        if (counting) launch_sum_counters(sc.d_cand.data(), static_cast<int>(lp.nwaves), sc.d_state.data(), s);
+}
+
+// The solving wave's arguments, for the one-launch loop or for the chained launches (p.use_loop or p.chain).  Every
+// call takes a new epoch of the handle's shared block.
+static LoopParams solver_params(const IcpCall &c, const AttemptPlan &p, double acc_unscale) {
+    LoopParams L{};
+    L.sh = c.sc.d_loop.data();
+    L.st = c.sc.d_state.data();
+    // a wait inside the launch normally takes microseconds; 50 ms of it means the grid is not
+    // resident as a whole (SAGEICP_LOOP_TIMEOUT_MS overrides, e.g. under a debugger)
+    L.timeout_ticks = 100000ull * static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_LOOP_TIMEOUT_MS", 50)));
+    const int test_ticks = env_int("SAGEICP_LOOP_TIMEOUT_TICKS", 0);      // tests: provoke a timeout
+    if (test_ticks) L.timeout_ticks = static_cast<unsigned long long>(test_ticks);
+    if (p.chain) {
+        L.wgs = p.chain_grid;                     // every workgroup of a launch sends its sums, also the ones past the frame's end
+        L.copies = kChainReplicas;
+        L.progress = c.sc.d_prog;
+        // (the solving wave waits for a whole LAUNCH here, not for resident workgroups: the first launch of a process
+        // loads code objects, a big frame's launch takes its hundred microseconds)
+        L.count_timeout_ticks = std::max<unsigned long long>(L.timeout_ticks, 20ull * 100000ull) * 10ull;
+    } else {
+        L.nw = p.loop.nw; L.gpw = p.loop.gpw; L.wgs = p.loop.wgs;
+        L.copies = kLoopReplicas;
+        L.progress = nullptr;
+        L.contiguous = env_int("SAGEICP_LOOP_CONTIGUOUS", 0) ? 1 : 0;
+        const uint64_t qw = 64u >> p.loop.lw, groups = (c.n + qw - 1) / qw;
+        for (int x = 0; x <= 8; ++x) L.xcd_first[x] = static_cast<uint32_t>(groups * x / 8);
+        // (an XCD's workgroups must be able to hold its range)
+        const uint64_t nwg = static_cast<uint64_t>(p.loop.wgs / 8);
+        for (int x = 0; x < 8; ++x)
+            if (L.contiguous == 1 && (L.xcd_first[x + 1] - L.xcd_first[x] + nwg - 1) / nwg > static_cast<uint64_t>(p.loop.gpw)) L.contiguous = 0;
+        L.count_timeout_ticks = L.timeout_ticks;       // (the solving wave's wait for its own workgroups: local, short)
+        L.prio = std::min(3, std::max(0, env_int("SAGEICP_LOOP_PRIO", 3)));
+        L.deal = env_int("SAGEICP_LOOP_DEAL", 1) ? 1 : 0;
+    }
+    if (c.comm) {
+        // (under a communicator the workgroups — or a chained launch — wait for a pose that waits for the peers' sums:
+        // their patience has to outlast the exchange's — a peer's first launches of a process can take a second; the
+        // solving wave's wait for its OWN grid or launch stays local)
+        L.shared_loop = 1;
+        if (test_ticks == 0) L.timeout_ticks = std::max(L.timeout_ticks, c.xp.timeout_ticks + 100000000ull);
+        // (tests: ONE rank of a communicator loses its grid or its launches — the others must follow it out of the exchange)
+        if (env_int("SAGEICP_LOOP_COUNT_TIMEOUT_RANK", -1) == c.comm->rank)
+            L.count_timeout_ticks = static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_LOOP_COUNT_TIMEOUT_TICKS", 1)));
+    }
+    L.max_iterations = c.max_it;
+    L.epoch = ++c.sc.loop_epoch;
+    for (int i = 0; i < 7; ++i) L.T0[i] = c.init[i];
+    L.acc_unscale = acc_unscale;
+    return L;
+}
+
+// The solving wave is launched well before its grid; should this call leave in between (an allocation or a launch
+// failing), it must not sit there waiting for a grid that never comes (and write its abort into the state of a
+// later call): the guard sends it home with the word the grid would have sent for a frame it refuses.  Armed by start();
+// released once the grid, or launch 0 of a chain, is enqueued without error.
+struct SolverGuard {
+    Scratch &sc;
+    unsigned long long epoch = 0;
+    bool armed = false;
+    explicit SolverGuard(Scratch &s) : sc(s) {}
+    ~SolverGuard() {                              // leaving the call: the word is sent and both streams are waited for
+        if (!armed) return;
+        const unsigned long long word = epoch | 0x8000000000000000ull;
+        (void)hipMemcpyAsync(&sc.d_loop.data()->go[0], &word, sizeof(word), hipMemcpyHostToDevice, sc.stream);
+        (void)hipStreamSynchronize(sc.stream);
+        (void)hipStreamSynchronize(sc.stream2);
+    }
+    // the solving wave on its own stream — it has to hold its registers before the grid fills the machine; it waits
+    // for the grid's (or launch 0's) go
+    int start(const LoopParams &L, const P2pParams &xp) {
+        launch_loop_solve(L, xp, sc.stream2);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (sc.h_state.data()->bad_input && !comm) {
-            looped = true;                     // (reported below)
-        } else if (sc.h_state.data()->exchange_failed) {
-            looped = true;                     // (reported below)
-        } else if (sc.h_state.data()->loop_aborted || !sc.h_state.data()->done) {
-            // a wait inside the launch timed out (the grid was not resident as a whole: another stream
-            // or process held CUs): the launch-per-iteration loop below registers the frame instead,
-            // with the same lanes per query
-            if (sc.h_state.data()->peer_aborted) {
-                // not this rank's grid: a peer lost its one-launch loop and every rank left the same exchange with it
-                // (sageicp_types.h, P2pBlock::abort_tag) — this frame goes through the other form on every rank, in step; no cool-down here
-                sc.last_fallback = SAGEICP_LOOP_FALLBACK_PEER;
-            } else {
-            sc.loop_cooldown = std::max(0, env_int("SAGEICP_LOOP_COOLDOWN", 256));
-            if (env_int("SAGEICP_LOOP_TIMEOUT_TICKS", 0) == 0 && env_int("SAGEICP_LOOP_COUNT_TIMEOUT_RANK", -1) < 0 && sc.loop_derate < 16) ++sc.loop_derate;
-            ++sc.loop_timeouts;
-            sc.last_fallback = SAGEICP_LOOP_FALLBACK_TIMEOUT;
-            {
-                // (said out loud once per process: the fast path was lost, and what it cost)
-                static std::atomic<int> told{0};
-                if (told.exchange(1) == 0 && env_int("SAGEICP_QUIET", 0) == 0)
-                    std::fprintf(stderr, "sageicp: a wait inside the one-launch ICP loop timed out (the GPU is shared with other work, or "
-                                         "fewer workgroups are resident than planned): this frame goes through the launch-per-iteration "
-                                         "loop, the next %d calls of this map too, later plans take %d workgroups fewer "
-                                         "(sageicp_map_loop_status() reports the state)\n", sc.loop_cooldown, 32 * sc.loop_derate);
-            }
-            }
-            // (under a communicator the solving wave told the peers through the exchange it was about to make: they left
-            // it with this rank, the exchange counts as made on every rank, and all of them register the frame again below)
-            fill_state(sc.h_state.data(), init);
-            if (polled) {
-                std::memset(sc.h_prog.data(), 0, sizeof(IcpProgress));
-                sc.h_state.data()->progress = sc.d_prog;
-            }
-            HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
-            if (counting) HIPCHK(hipMemsetAsync(sc.d_cand.data(), 0, sizeof(unsigned long long) * 2 * (ip.nwaves + 1), s));
-            use_loop = false;
-        } else {
-            looped = true;
-            if (prof) {
-                float a = 0;
-                (void)hipEventElapsedTime(&a, sc.events[1], sc.events[2]);
-                us_nn = 1e3 * a;
-                nn_launches = static_cast<uint32_t>(std::max(1, sc.h_state.data()->iter));   // per iteration
-            }
+        epoch = L.epoch;
+        armed = true;
+        HIPCHK(hipEventRecord(sc.ev_solve, sc.stream2));
+        return SAGEICP_OK;
+    }
+    void disarm() { armed = false; }
+    int send_home_now() {                         // in stream order, the call going on (the copy's source outlives it: Scratch::go_word)
+        sc.go_word = epoch | 0x8000000000000000ull;
+        HIPCHK(hipMemcpyAsync(&sc.d_loop.data()->go[0], &sc.go_word, sizeof(sc.go_word), hipMemcpyHostToDevice, sc.stream));
+        armed = false;
+        return SAGEICP_OK;
+    }
+};
+
+struct AttemptResult {
+    bool looped = false;        // the one-launch loop did the work
+    bool chain = false;         // the launches were chained ...
+    bool chain_gave_up = false; // ... and a wait of theirs timed out: the state on the host is not a registration's
+    int lw = 0;
+    bool compact_scan = false;
+    double us_nn = 0, us_fin = 0;       // device time between the profiling events (sageicp_set_profiling)
+    uint32_t nn_launches = 0;
+};
+
+// ---- the whole loop in one launch (kernels.hip, k_loop): the solving wave is waiting, now the grid (the shared block
+// zeroed first: the solving wave starts on the grid's go).  r.looped: the state on the host is this loop's — the
+// frame's pose, or what is reported without trying another form (a bad input outside a communicator, a failed
+// exchange).  Otherwise the loop gave up and the state has been started again for the k_icp + k_fin form.
+static int run_one_launch(const IcpCall &c, const AttemptPlan &p, const IcpParams &ip, const LoopParams &L,
+                          SolverGuard &guard, AttemptResult &r) {
+    Scratch &sc = c.sc;
+    hipStream_t s = c.s;
+    int rc;
+    if (c.prof && (rc = sc.reserve_events(1))) return rc;
+    IcpParams lp = ip;
+    lp.filter = p.loop.filter ? ip.filter : 0;
+    lp.nwaves = p.loop_waves;
+    HIPCHK(hipMemsetAsync(sc.d_loop.data(), 0, offsetof(LoopShared, acc32), s));      // (the chained launches' copies are not this loop's)
+    if (c.prof) HIPCHK(hipEventRecord(sc.events[1], s));
+    launch_loop(lp, L, p.loop.lw, s);
+    if (hipPeekAtLastError() == hipSuccess) guard.disarm();      // the grid is on its way: it will say go
+    if (c.prof) HIPCHK(hipEventRecord(sc.events[2], s));
+    if (solver_is_own_launch(p)) HIPCHK(hipStreamWaitEvent(s, sc.ev_solve, 0));      // the solving wave writes the final state
+    if ((rc = c.fetch_state(lp.nwaves))) return rc;
+    const IcpState &st = *sc.h_state.data();
+    r.looped = true;
+    if ((st.bad_input && !c.comm) || st.exchange_failed) return SAGEICP_OK;      // (reported by run_icp)
+    if (!st.loop_aborted && st.done) {
+        if (c.prof) {
+            float a = 0;
+            (void)hipEventElapsedTime(&a, sc.events[1], sc.events[2]);
+            r.us_nn = 1e3 * a;
+            r.nn_launches = static_cast<uint32_t>(std::max(1, st.iter));   // per iteration
         }
+        return SAGEICP_OK;
     }
-    if (n > 0 && !looped) {
-        launch_rows(ip, s);
-        HIPCHK(hipMemsetAsync(sc.d_prev.data(), 0xFF, n * sizeof(uint2), s));     // no previous answers yet
+    // a wait inside the launch timed out (the grid was not resident as a whole: another stream
+    // or process held CUs): the launch-per-iteration loop registers the frame instead,
+    // with the same lanes per query
+    r.looped = false;
+    if (st.peer_aborted) {
+        // not this rank's grid: a peer lost its one-launch loop and every rank left the same exchange with it
+        // (sageicp_types.h, P2pBlock::abort_tag) — this frame goes through the other form on every rank, in step; no cool-down here
+        sc.last_fallback = SAGEICP_LOOP_FALLBACK_PEER;
+    } else {
+        sc.loop_cooldown = std::max(0, env_int("SAGEICP_LOOP_COOLDOWN", 256));
+        if (env_int("SAGEICP_LOOP_TIMEOUT_TICKS", 0) == 0 && env_int("SAGEICP_LOOP_COUNT_TIMEOUT_RANK", -1) < 0 && sc.loop_derate < 16) ++sc.loop_derate;
+        ++sc.loop_timeouts;
+        sc.last_fallback = SAGEICP_LOOP_FALLBACK_TIMEOUT;
+        // (said out loud once per process: the fast path was lost, and what it cost)
+        static std::atomic<int> told{0};
+        if (told.exchange(1) == 0 && env_int("SAGEICP_QUIET", 0) == 0)
+            std::fprintf(stderr, "sageicp: a wait inside the one-launch ICP loop timed out (the GPU is shared with other work, or "
+                                 "fewer workgroups are resident than planned): this frame goes through the launch-per-iteration "
+                                 "loop, the next %d calls of this map too, later plans take %d workgroups fewer "
+                                 "(sageicp_map_loop_status() reports the state)\n", sc.loop_cooldown, 32 * sc.loop_derate);
     }
+    // (under a communicator the solving wave told the peers through the exchange it was about to make: they left
+    // it with this rank, the exchange counts as made on every rank, and all of them register the frame again)
+    if ((rc = c.start_state())) return rc;
+    if (c.counting) HIPCHK(hipMemsetAsync(sc.d_cand.data(), 0, sizeof(unsigned long long) * 2 * (ip.nwaves + 1), s));
+    return SAGEICP_OK;
+}
 
-    // The workgroups of k_icp add their sums into fixed-point accumulators (kernels.h) that k_fin
-    // reads in one round trip.
-    HIPCHK(hipMemsetAsync(sc.d_acc.data(), 0, sizeof(long long) * kAccReplicas * kAccWords, s));
-    ip.acc = sc.d_acc.data();
-    if (chain) {
-        // ... or, chained, into the counted accumulators of the shared block the solving wave reads (zeroed first: the
-        // solving wave starts on launch 0's go)
-        HIPCHK(hipMemsetAsync(sc.d_loop.data(), 0, sizeof(LoopShared), s));
-        ip.chain = sc.d_loop.data();
-        ip.chain_timeout = L.timeout_ticks;
-        ip.chain_epoch = L.epoch;
-        ip.digit_limit = std::min(ip.digit_limit, std::ldexp(1.0, 40));       // (counted words: kernels.hip, kDigitLimitCounted)
-    }
+// ---- the launch-per-iteration forms: what one iteration enqueues, and the polled and the chunked loop over them
+struct Iterations {
+    const IcpCall &c;
+    SolverGuard &guard;
+    AttemptResult &r;
+    IcpParams &ip;
+    const int lw;
+    const bool chain;
+    Scratch &sc = c.sc;
+    hipStream_t s = c.s;
     FinParams fp{};
-    fp.st = sc.d_state.data();
-    fp.partials = nullptr;
-    fp.acc = ip.acc;
-    fp.acc_unscale = 1.0 / ip.acc_scale;
-    fp.nparts = 0;
-    fp.mode = p2p ? 3 : (comm ? 1 : 0);
-    fp.standalone = 0;
-    if (p2p) fp.p2p = xp;
-
-    // one iteration; `slot` indexes its 5 profiling events
-    // Profiling level 1 brackets k_icp in one iteration out of 8 (two event records cost ~6 us of
-    // stream time): the roofline figure is the mean over that sample; level 2: every kernel of
-    // every iteration.
-    auto sampled = [&](int iteration) { return prof2 || (prof && (iteration & 7) == 4); };
     // Heaviest first (kernels.h, IcpParams::stripe_order): the stripes of k_icp are dispatched in the order of the work
     // iterations 0, 3 and 15 measured (a cold registration's first passes are not its later ones; from then on the heavy
     // regions stay the heavy regions).  The sort's buffers are the frame sort's, free once the frame is in order.
-    const unsigned stripes = (n > 0 && !looped) ? static_cast<unsigned>(icp_stripes_for(static_cast<int>(n), lw)) : 0u;
-    // (three small sorts per frame: worth it from ~40k points on — c1 through this loop: +4.5 % with them)
-    const bool lpt = stripes >= 16 && stripes <= sc.sort_cap && stripe_sort_temp_bytes(stripes) <= sc.d_sort_temp.capacity() &&
-                     env_int("SAGEICP_LPT", n >= 40000 ? 1 : 0) != 0;
-    uint32_t *st_work = sc.d_keys.data(), *st_sorted = sc.d_keys.data() + stripes, *st_iota = sc.d_vals.data(), *st_order = sc.d_vals.data() + stripes;
-    if (lpt) stripe_order_init(st_work, st_iota, stripes, s);
-    auto measures = [&](int iteration) { return lpt && (iteration == 0 || iteration == 3 || iteration == 15); };
-    auto enqueue_iteration = [&](int slot, int iteration) -> int {
+    unsigned stripes = 0;
+    bool lpt = false;
+    uint32_t *st_work = nullptr, *st_sorted = nullptr, *st_iota = nullptr, *st_order = nullptr;
+
+    // Profiling level 1 brackets k_icp in one iteration out of 8 (two event records cost ~6 us of
+    // stream time): the roofline figure is the mean over that sample; level 2: every kernel of
+    // every iteration.
+    bool sampled(int iteration) const { return c.prof2 || (c.prof && (iteration & 7) == 4); }
+    bool measures(int iteration) const { return lpt && (iteration == 0 || iteration == 3 || iteration == 15); }
+
+    // where the sums go, k_fin's arguments, the stripe order
+    int begin(const LoopParams &L) {
+        // The workgroups of k_icp add their sums into fixed-point accumulators (kernels.h) that k_fin
+        // reads in one round trip (zeroed by run_attempt).
+        ip.acc = sc.d_acc.data();
+        if (chain) {
+            // ... or, chained, into the counted accumulators of the shared block the solving wave reads (zeroed first: the
+            // solving wave starts on launch 0's go)
+            HIPCHK(hipMemsetAsync(sc.d_loop.data(), 0, sizeof(LoopShared), s));
+            ip.chain = sc.d_loop.data();
+            ip.chain_timeout = L.timeout_ticks;
+            ip.chain_epoch = L.epoch;
+            ip.digit_limit = std::min(ip.digit_limit, std::ldexp(1.0, 40));       // (counted words: kernels.hip, kDigitLimitCounted)
+        }
+        fp.st = sc.d_state.data();
+        fp.partials = nullptr; fp.nparts = 0; fp.standalone = 0;
+        fp.acc = ip.acc;
+        fp.acc_unscale = 1.0 / ip.acc_scale;
+        fp.mode = c.p2p ? 3 : (c.comm ? 1 : 0);
+        if (c.p2p) fp.p2p = c.xp;
+        stripes = c.n > 0 ? static_cast<unsigned>(icp_stripes_for(static_cast<int>(c.n), lw)) : 0u;
+        // (three small sorts per frame: worth it from ~40k points on — c1 through this loop: +4.5 % with them)
+        lpt = stripes >= 16 && stripes <= sc.sort_cap && stripe_sort_temp_bytes(stripes) <= sc.d_sort_temp.capacity() &&
+              env_int("SAGEICP_LPT", c.n >= 40000 ? 1 : 0) != 0;
+        st_work = sc.d_keys.data(); st_sorted = sc.d_keys.data() + stripes; st_iota = sc.d_vals.data(); st_order = sc.d_vals.data() + stripes;
+        if (lpt) stripe_order_init(st_work, st_iota, stripes, s);
+        return SAGEICP_OK;
+    }
+    // one iteration; `slot` indexes its 5 profiling events
+    int enqueue(int slot, int iteration) {
         const bool ev = sampled(iteration);
         if (ev) HIPCHK(hipEventRecord(sc.events[5 * slot + 1], s));
         ip.stripe_work = measures(iteration) ? st_work : nullptr;
         ip.chain_iter = iteration;
         launch_icp(ip, lw, true, s);
-        if (chain && iteration == 0 && hipPeekAtLastError() == hipSuccess) solver_guard.sc = nullptr;      // launch 0 will say go
+        if (chain && iteration == 0 && hipPeekAtLastError() == hipSuccess) guard.disarm();      // launch 0 will say go
         if (measures(iteration)) {
             HIPCHK(stripe_order_sort(st_work, st_sorted, st_iota, st_order, stripes, sc.d_sort_temp.data(), sc.d_sort_temp.capacity(), s));
             ip.stripe_order = st_order;
@@ -633,31 +675,32 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
         if (ev) HIPCHK(hipEventRecord(sc.events[5 * slot + 2], s));
         if (chain) return SAGEICP_OK;                  // (the solving wave is already waiting for this launch's sums)
         launch_fin(fp, s);
-        if (comm && !p2p) {     // k_fin left the local sums in state->sums
-            ncclResult_t r = g_rccl.AllReduce(sc.d_state.data()->sums, sc.d_state.data()->sums, kNumSums,
-                                              ncclDouble, ncclSum, comm->comm, s);
-            if (r != ncclSuccess)
+        if (c.comm && !c.p2p) {     // k_fin left the local sums in state->sums
+            ncclResult_t e = g_rccl.AllReduce(sc.d_state.data()->sums, sc.d_state.data()->sums, kNumSums,
+                                              ncclDouble, ncclSum, c.comm->comm, s);
+            if (e != ncclSuccess)
                 return fail(SAGEICP_ERR_RCCL, std::string("ncclAllReduce: ") +
-                                                  (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?"));
+                                                  (g_rccl.GetErrorString ? g_rccl.GetErrorString(e) : "?"));
             FinParams f2 = fp;
             f2.mode = 2;
             launch_fin(f2, s);
         }
-        if (prof2) HIPCHK(hipEventRecord(sc.events[5 * slot + 3], s));
+        if (c.prof2) HIPCHK(hipEventRecord(sc.events[5 * slot + 3], s));
         return SAGEICP_OK;
-    };
-    auto harvest = [&](int slot) {
+    }
+    void harvest(int slot) {
         float a = 0, b = 0;
         (void)hipEventElapsedTime(&a, sc.events[5 * slot + 1], sc.events[5 * slot + 2]);
-        if (prof2) (void)hipEventElapsedTime(&b, sc.events[5 * slot + 2], sc.events[5 * slot + 3]);
-        us_nn += 1e3 * a; us_fin += 1e3 * b;
-        ++nn_launches;
-    };
-    // (nothing the host does depends on WHEN it looks at the progress word: a call repeated gives
-    // the same bits)
-    if (looped) {
-        // (the one-launch loop has run; the state is on the host)
-    } else if (polled) {
+        if (c.prof2) (void)hipEventElapsedTime(&b, sc.events[5 * slot + 2], sc.events[5 * slot + 3]);
+        r.us_nn += 1e3 * a; r.us_fin += 1e3 * b;
+        ++r.nn_launches;
+    }
+
+    // The polled loop: iterations are enqueued `depth` ahead of the progress word the device writes.  (Nothing the
+    // host does depends on WHEN it looks at the word: a call repeated gives the same bits.)  r.chain_gave_up: a wait
+    // of the chained launches timed out, and the frame has to be registered again without the chain.
+    int run_polled() {
+        int rc;
         const int depth = std::min(8, std::max(1, env_int("SAGEICP_DEPTH", 4)));
         volatile unsigned long long *word = &sc.h_prog.data()->word;
         int enq = 0;
@@ -667,8 +710,8 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
             const unsigned long long w = *word;
             const int comp = static_cast<int>(w & 0xFFFFFFFFull);
             if (w >> 32) break;                                  // converged or out of iterations
-            if (enq < max_it && enq - comp < depth) {
-                if ((rc = enqueue_iteration(enq, enq))) return rc;
+            if (enq < c.max_it && enq - comp < depth) {
+                if ((rc = enqueue(enq, enq))) return rc;
                 ++enq;
                 spins = 0;
                 continue;
@@ -678,7 +721,7 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
                 const hipError_t q = hipStreamQuery(s);
                 if (q != hipSuccess && q != hipErrorNotReady)
                     return fail(SAGEICP_ERR_HIP, std::string("ICP loop: ") + hipGetErrorString(q));
-                if (q == hipSuccess && (*word >> 32) == 0 && enq >= max_it)
+                if (q == hipSuccess && (*word >> 32) == 0 && enq >= c.max_it)
                     break;     // everything ran and nothing flagged the end: read the state below
                 if (chain && q == hipSuccess) {
                     // chained: every launch enqueued has run, and the solving wave has said nothing new for a whole
@@ -691,76 +734,141 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
                 }
             }
         }
-        if (chain && solver_guard.sc) {
-            // no launch was enqueued at all (the sort refused the frame — a non-finite point — before the host got to
-            // iteration 0): nobody will tell the solving wave to start, so it is sent home here, not when this call returns
-            sc.go_word = solver_guard.epoch | 0x8000000000000000ull;
-            HIPCHK(hipMemcpyAsync(&sc.d_loop.data()->go[0], &sc.go_word, sizeof(sc.go_word), hipMemcpyHostToDevice, s));
-            solver_guard.sc = nullptr;
-        }
+        // no launch was enqueued at all (the sort refused the frame — a non-finite point — before the host got to
+        // iteration 0): nobody will tell the solving wave to start, so it is sent home here, not when this call returns
+        if (chain && guard.armed && (rc = guard.send_home_now())) return rc;
         if (chain) HIPCHK(hipStreamWaitEvent(s, sc.ev_solve, 0));      // the solving wave writes the final state
-        if (counting) launch_sum_counters(sc.d_cand.data(), static_cast<int>(ip.nwaves), sc.d_state.data(), s);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (chain && (sc.h_state.data()->loop_aborted || !sc.h_state.data()->done) && !sc.h_state.data()->bad_input) {
+        if ((rc = c.fetch_state(ip.nwaves))) return rc;
+        const IcpState &st = *sc.h_state.data();
+        if (chain && (st.loop_aborted || !st.done) && !st.bad_input) {
             // a wait timed out (the solving wave was not resident beside the launches, or a launch took longer than its
             // patience): the frame again with k_fin between the launches — same lanes per query, same bits
             static std::atomic<int> told{0};
             if (told.exchange(1) == 0 && env_int("SAGEICP_QUIET", 0) == 0)
                 std::fprintf(stderr, "sageicp: a wait inside the chained ICP launches timed out: this frame is registered again with "
                                      "k_fin between the launches\n");
-            g_no_chain = true;
-            const int rc2 = run_icp(m, d_frame, n, init, max_dist, kernel, sem_th, comm, out, stats, us_upload, t_begin);
-            g_no_chain = false;
-            return rc2;
+            r.chain_gave_up = true;
+            return SAGEICP_OK;
         }
-        if (prof)
-            for (int k = 0; k < sc.h_state.data()->iter && k < enq; ++k)      // the rest were no-ops
+        if (c.prof)
+            for (int k = 0; k < st.iter && k < enq; ++k)      // the rest were no-ops
                 if (sampled(k)) harvest(k);
-    } else {
-        int launched = 0;
-        int chunk = 4;
+        return SAGEICP_OK;
+    }
+    // The chunked loop (RCCL, or SAGEICP_CHUNKED=1): one synchronisation per chunk.
+    int run_chunked() {
+        const IcpState &st = *sc.h_state.data();
+        int rc, launched = 0, chunk = 4;
         for (;;) {
             const int todo = std::min(chunk, kMaxIterations - launched);
             for (int k = 0; k < todo; ++k)
-                if ((rc = enqueue_iteration(k, launched + k))) return rc;
-            if (counting) launch_sum_counters(sc.d_cand.data(), static_cast<int>(ip.nwaves), sc.d_state.data(), s);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (prof) {
-                const int executed = std::min(todo, sc.h_state.data()->iter - launched);   // the rest were no-ops
+                if ((rc = enqueue(k, launched + k))) return rc;
+            if ((rc = c.fetch_state(ip.nwaves))) return rc;
+            if (c.prof) {
+                const int executed = std::min(todo, st.iter - launched);   // the rest were no-ops
                 for (int k = 0; k < executed; ++k)
                     if (sampled(launched + k)) harvest(k);
             }
             launched += todo;
-            if (sc.h_state.data()->done || launched >= kMaxIterations) break;
+            if (st.done || launched >= kMaxIterations) return SAGEICP_OK;
             chunk = std::min(kChunkMax, chunk * 2);   // 4, 8, 16, 16, ... : few syncs, bounded no-op tail
         }
     }
-    const IcpState &st = *sc.h_state.data();
-    if (st.peer_aborted && !looped && comm && g_restarts < 4) {
-        // a peer gave up its one-launch loop at an exchange this rank made from k_fin: every rank starts the frame again
-        // (this one in the form it already had)
-        ++g_restarts;
-        g_no_loop = true;
-        const int rc2 = run_icp(m, d_frame, n, init, max_dist, kernel, sem_th, comm, out, stats, us_upload, t_begin);
-        g_no_loop = false;
-        --g_restarts;
-        return rc2;
+};
+
+// One attempt, from the upload of the state to the state back on the host.  What is enqueued on the handle's two
+// streams, in order: the state, the counters zeroed, the solving wave (stream2) BEFORE the sort, the sort,
+// then the one-launch loop — and, unless that did the work, rows, previous answers, accumulators and the launches.
+static int run_attempt(const IcpCall &c, const Attempt &a, AttemptResult &r) {
+    Scratch &sc = c.sc;
+    int rc;
+    if ((rc = c.start_state())) return rc;
+    const AttemptPlan p = plan_attempt(c, a);
+    if ((rc = ensure_cand(c.m, wants_filter(c.m, c.n, c.sem_th)))) return rc;
+    if ((rc = sc.reserve_sort(c.n))) return rc;
+    IcpParams ip = icp_params(c.m, sc.d_sorted.data(), c.n, c.sem_th, p.lw, a.acc_shift);
+    ip.check_done = 1; ip.apply_pose = 1;
+    ip.kernel = c.kernel;
+    ip.accept_r2 = accept_threshold(c.max_dist);
+    ip.counters = c.counting ? sc.d_cand.data() : nullptr;
+    if (c.counting) HIPCHK(hipMemsetAsync(sc.d_cand.data(), 0, sizeof(unsigned long long) * 2 * (std::max(ip.nwaves, p.loop_waves) + 1), c.s));
+    LoopParams L{};
+    SolverGuard guard(sc);
+    if (p.use_loop || p.chain) {
+        if ((rc = sc.loop_streams())) return rc;
+        L = solver_params(c, p, 1.0 / ip.acc_scale);
+        if (solver_is_own_launch(p) && (rc = guard.start(L, c.xp))) return rc;
     }
-    if (st.bad_input)
-        return fail(SAGEICP_ERR_INVALID, "the frame holds a coordinate or label that is not finite (NaN / Inf)");
-    if (st.acc_overflow && !comm && g_acc_shift < 2) {
-        // |sum over four queries| >= 2^46 or 2^62 / blocks of the frame (2^40 in the one-launch loop): georeferenced coordinates (UTM: ~3e6 m,
-        // 4 s^2 = 4e13; 10^7 m beyond) do that.  The reference has no such limit: the frame is registered again
-        // with the sums accumulated at 2^-24, then 2^-48 of their value — the same exact integer arithmetic on
-        // digits of weight 2^24, 2^-16, 2^-56 (what is dropped lies 2^80 below the limit either way).
-        ++g_acc_shift;
-        const int rc2 = run_icp(m, d_frame, n, init, max_dist, kernel, sem_th, comm, out, stats, us_upload, t_begin);
-        --g_acc_shift;
-        return rc2;
+    if ((rc = c.order_frame())) return rc;
+    r = AttemptResult{};
+    r.lw = p.lw;
+    r.chain = p.chain;
+    if (p.use_loop && (rc = run_one_launch(c, p, ip, L, guard, r))) return rc;
+    r.compact_scan = r.looped ? p.loop.filter && ip.filter : ip.filter != 0;
+    if (c.n > 0 && !r.looped) {
+        launch_rows(ip, c.s);
+        HIPCHK(hipMemsetAsync(sc.d_prev.data(), 0xFF, c.n * sizeof(uint2), c.s));     // no previous answers yet
+    }
+    // (zeroed also behind a one-launch loop that did the work, which nothing reads: kept as it was, profiles/r14/README.md)
+    HIPCHK(hipMemsetAsync(sc.d_acc.data(), 0, sizeof(long long) * kAccReplicas * kAccWords, c.s));
+    if (r.looped) return SAGEICP_OK;
+    // (after a one-launch loop that gave up: its plan's lanes, the frame as sorted, never chained — p.chain needs
+    // !p.loop_shape —, last_fallback and the cool-down as run_one_launch left them)
+    Iterations it{c, guard, r, ip, p.lw, p.chain};
+    if ((rc = it.begin(L))) return rc;
+    return c.polled ? it.run_polled() : it.run_chunked();
+}
+
+static void fill_stats(sageicp_stats *stats, const IcpState &st, uint64_t n, const AttemptResult &r, double us_upload, double t_begin) {
+    std::memset(stats, 0, sizeof(*stats));
+    stats->iterations = st.iter; stats->converged = st.converged;
+    stats->n_queries = n;
+    stats->n_corr_first = st.iter > 0 ? st.n_corr[0] : 0;
+    stats->n_corr_last = st.iter > 0 ? st.n_corr[std::min(st.iter, kHistory) - 1] : 0;
+    stats->last_step_norm = st.last_step_norm;
+    stats->us_upload = us_upload;
+    stats->us_nn = r.us_nn; stats->us_fin = r.us_fin;
+    stats->nn_launches = r.nn_launches;
+    stats->sum_candidates = st.sum_candidates; stats->pairs_evaluated = st.sum_pairs;
+    stats->lanes_per_query = 1u << r.lw;
+    stats->compact_scan = r.compact_scan ? 1u : 0u;
+    stats->single_launch = r.looped ? 1u : 0u;
+    for (int i = 0; i < 64 && i < st.iter; ++i) stats->n_corr_hist[i] = st.n_corr[i];
+    stats->us_wall = now_us() - t_begin;             // (the whole call's, every attempt included)
+}
+
+int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const double init[7],
+            double max_dist, double kernel, double sem_th, sageicp_comm *comm, double out[7],
+            sageicp_stats *stats, double us_upload, double t_begin) {
+    Scratch &sc = m->sc;
+    if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
+    int rc;
+    IcpCall c{m, d_frame, n, init, max_dist, kernel, sem_th, comm, sc, sc.stream, false, false, false, false, false, 0, P2pParams{}};
+    if ((rc = c.constants(stats != nullptr))) return rc;
+    if (c.prof && (rc = sc.reserve_events(c.polled ? kMaxIterations : kChunkMax))) return rc;
+    Attempt a;
+    AttemptResult r;
+    const IcpState &st = *sc.h_state.data();
+    for (;;) {
+        if ((rc = run_attempt(c, a, r))) return rc;
+        if (r.chain_gave_up) {
+            a.no_chain = true;
+        } else if (st.peer_aborted && !r.looped && comm && a.restarts < 4) {
+            // a peer gave up its one-launch loop at an exchange this rank made from k_fin: every rank starts the frame again
+            // (this one in the form it already had)
+            ++a.restarts;
+            a.no_loop = true;
+        } else if (st.bad_input) {
+            return fail(SAGEICP_ERR_INVALID, "the frame holds a coordinate or label that is not finite (NaN / Inf)");
+        } else if (st.acc_overflow && !comm && a.acc_shift < 2) {
+            // |sum over four queries| >= 2^46 or 2^62 / blocks of the frame (2^40 in the one-launch loop): georeferenced coordinates (UTM: ~3e6 m,
+            // 4 s^2 = 4e13; 10^7 m beyond) do that.  The reference has no such limit: the frame is registered again
+            // with the sums accumulated at 2^-24, then 2^-48 of their value — the same exact integer arithmetic on
+            // digits of weight 2^24, 2^-16, 2^-56 (what is dropped lies 2^80 below the limit either way).
+            ++a.acc_shift;
+        } else {
+            break;
+        }
     }
     if (st.acc_overflow)
         return fail(SAGEICP_ERR_CAPACITY, "a Gauss-Newton sum left the range of the fixed-point accumulators "
@@ -777,30 +885,12 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
         return fail(SAGEICP_ERR_RCCL, "direct exchange: a peer's sums did not arrive in time");
     }
     for (int i = 0; i < 7; ++i) out[i] = st.T[i];
-    if (looped) ++sc.calls_single_launch; else ++sc.calls_per_iteration;
-    if (!looped && chain) ++sc.calls_chained;
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->iterations = st.iter;
-        stats->converged = st.converged;
-        stats->n_queries = n;
-        stats->n_corr_first = st.iter > 0 ? st.n_corr[0] : 0;
-        stats->n_corr_last = st.iter > 0 ? st.n_corr[std::min(st.iter, kHistory) - 1] : 0;
-        stats->last_step_norm = st.last_step_norm;
-        stats->us_upload = us_upload;
-        stats->us_nn = us_nn; stats->us_fin = us_fin;
-        stats->nn_launches = nn_launches;
-        stats->sum_candidates = st.sum_candidates;
-        stats->pairs_evaluated = st.sum_pairs;
-        stats->lanes_per_query = 1u << lw;
-        stats->compact_scan = (looped ? plan.filter && ip.filter : ip.filter != 0) ? 1u : 0u;
-        stats->single_launch = looped ? 1u : 0u;
-        for (int i = 0; i < 64 && i < st.iter; ++i) stats->n_corr_hist[i] = st.n_corr[i];
-        stats->us_wall = now_us() - t_begin;
-    }
+    // (counted once, by the attempt that registered the frame)
+    if (r.looped) ++sc.calls_single_launch; else ++sc.calls_per_iteration;
+    if (!r.looped && r.chain) ++sc.calls_chained;
+    if (stats) fill_stats(stats, st, n, r, us_upload, t_begin);
     return SAGEICP_OK;
 }
-
 
 // ---- single-process multi-GPU mode -------------------------------------------------------------
 // Update(points, pose) on every copy of the map.  `d_points` (optional) lives on rank 0's device.

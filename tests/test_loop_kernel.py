@@ -280,6 +280,32 @@ def test_timeout_inside_the_launch_falls_back(gpu_sage, oracle):
     assert forms == [(0, 2), (0, 2), (1, 0)]                                        # ... _COOLDOWN twice, then _NONE
 
 
+def test_timeout_inside_the_chained_launches_registers_again_with_k_fin(gpu_sage, oracle):
+    """the chained launches (no one-launch loop: SAGEICP_LOOP=0) as they are, not chained (SAGEICP_CHAIN=0), and with
+    SAGEICP_LOOP_TIMEOUT_TICKS=1, where every wait of the launches and of their solving wave gives up at once and the
+    frame is registered again with k_fin between the launches: one pose to the bit, and only the first call counts
+    as chained"""
+    from sage_icp_amd import synthetic as syn
+    w, om = _workload(gpu_sage, oracle, "c2", 0.05)
+    p = syn.PARAMS["cold"]
+    s0 = w["map"].loop_status()
+    runs = []
+    for env in ({}, {"SAGEICP_CHAIN": 0}, {"SAGEICP_LOOP_TIMEOUT_TICKS": 1}):
+        with Env(SAGEICP_LOOP=0, **env):
+            runs.append(gpu_sage.register_frame(w["scan"], w["map"], gpu_sage.IDENTITY, p["max_dist"], p["kernel"],
+                                                p["sem_th"], return_stats=True))
+        print(env, runs[-1][1].iterations, runs[-1][1].n_corr_first, runs[-1][1].n_corr_last,
+              w["map"].loop_status().calls_chained - s0.calls_chained)
+    (a, sa), (b, sb), (c, sc) = runs
+    assert np.array_equal(a, b) and np.array_equal(a, c)
+    _same(sa, sb)
+    _same(sa, sc)
+    assert sa.single_launch == 0 and sb.single_launch == 0 and sc.single_launch == 0
+    s1 = w["map"].loop_status()
+    assert s1.calls_chained == s0.calls_chained + 1
+    assert s1.calls_per_iteration == s0.calls_per_iteration + 3 and s1.calls_single_launch == s0.calls_single_launch
+
+
 def test_streamed_frames_through_the_pipeline(gpu_sage, oracle):
     """the per-frame pipeline (sageicp_pipeline_*) registers 24k-point sources: both loops, same poses"""
     from sage_icp_amd import synthetic as syn
