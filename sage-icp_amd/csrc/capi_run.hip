@@ -496,6 +496,8 @@ static LoopParams solver_params(const IcpCall &c, const AttemptPlan &p, double a
         if (env_int("SAGEICP_LOOP_COUNT_TIMEOUT_RANK", -1) == c.comm->rank)
             L.count_timeout_ticks = static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_LOOP_COUNT_TIMEOUT_TICKS", 1)));
     }
+    // (tests: the workgroups on other copies of the pose than their XCD's — any copy is the pose; kernels.h, kLoopPoseCopies)
+    L.pose_map = std::min(2, std::max(0, env_int("SAGEICP_LOOP_POSE_MAP", 0)));
     L.max_iterations = c.max_it;
     L.epoch = ++c.sc.loop_epoch;
     for (int i = 0; i < 7; ++i) L.T0[i] = c.init[i];
@@ -643,6 +645,7 @@ struct Iterations {
             HIPCHK(hipMemsetAsync(sc.d_loop.data(), 0, sizeof(LoopShared), s));
             ip.chain = sc.d_loop.data();
             ip.chain_timeout = L.timeout_ticks;
+            ip.chain_pose_map = L.pose_map;
             ip.chain_epoch = L.epoch;
             ip.digit_limit = std::min(ip.digit_limit, std::ldexp(1.0, 40));       // (counted words: kernels.hip, kDigitLimitCounted)
         }

@@ -90,6 +90,7 @@ struct IcpParams {
     // solve under it.  Same sums, same solve: the same bits.
     LoopShared *chain;        // non-null: this launch is iteration `chain_iter` of a chained loop
     int chain_iter;
+    int chain_pose_map;       // as LoopParams::pose_map
     unsigned long long chain_timeout;   // 100-MHz ticks a workgroup waits for its pose
     unsigned long long chain_epoch;     // launch 0 tells the solving wave to start (LoopShared::go)
 };
@@ -174,11 +175,19 @@ constexpr int kLoopReplicas = SAGE_LOOP_REPLICAS;      // accumulator copies (wo
 // no different from eight: profiles/r06/replicas_ab.txt, copies_ab.txt.  The chained launches' 32 and k_fin's 32 keep the
 // same property: b % 32 determines b % 8.)
 constexpr int kLoopPoseGranules = 25;      // R[9], t[3] as 24 x {tag, 32 bits} + {tag, done}
+// The pose is published kLoopPoseCopies times, each copy in a 256-byte block of its own: workgroup b polls copy b & 7 —
+// its XCD's, by the observed mapping of workgroups to XCDs; speed only: every copy is the whole pose
+// (LoopParams::pose_map moves the workgroups onto other copies, tests/test_pose_broadcast.py).  The aim: the ~200
+// polling waves of an XCD look at lines of their own, away from the other XCDs' pollers and from the accumulators the
+// solving wave is reading.  That 256 bytes separate L2 channels for these agent-scope accesses is ASSUMED, not
+// documented; what the copies buy is in profiles/r15/ (pose held per XCD, chain_{parent,new}_*.txt).
+constexpr int kLoopPoseCopies = 8;
+constexpr int kLoopPoseStride = 32;        // words of 8 bytes from one copy to the next
 constexpr int kChainReplicas = 32;         // accumulator copies of the chained launches (k_icp: thousands of workgroups, <= 255 per copy)
 struct LoopShared {
     long long acc[2][kLoopReplicas][kAccWords];         // as FinParams::acc, one set per iteration parity, every word
                                                         // (digit << 8) | workgroups in it; word 51: (workgroups whose sums overflowed << 8) | workgroups
-    unsigned long long pose[32];                        // granules (tag << 32) | payload, tag = iteration + 1
+    unsigned long long pose[kLoopPoseCopies][kLoopPoseStride];      // per copy: granules (tag << 32) | payload, tag = iteration + 1
     unsigned long long abort_word[16];                  // [0] != 0: a wait timed out somewhere — everybody leaves
     unsigned long long go[16];                          // [0]: the call's epoch, stored by k_loop's first workgroup when the
                                                         // grid has started (bit 63: the frame holds a non-finite point)
@@ -210,6 +219,7 @@ struct LoopParams {
                                    // the workgroup's slot on the CU) mod waves — instead of first come first served (k_loop)
     int copies;                    // accumulator copies the workgroups add into: kLoopReplicas (k_loop: LoopShared::acc) or
                                    // kChainReplicas (chained k_icp launches: LoopShared::acc32)
+    int pose_map;                  // which copy of the pose workgroup b polls (loop_pose_copy): 0: b & 7 | 1: copy 0 | 2: (b + 3) & 7
     IcpProgress *progress;         // optional (chained launches): the host-mapped word the host steers its look-ahead by
 };
 struct LoopArgs {                  // k_loop's one argument: its passes re-read it from the kernel-argument segment

@@ -565,10 +565,15 @@ struct PairFullFlat {
 // wave publishes after iteration it - 1 (25 self-tagged granules, tag = it; kernels.h, LoopShared) and hands it to the
 // workgroup through LDS.  smem[kWgGo] != 0: the workgroup leaves — the loop ended before this iteration (the done granule
 // carries an older tag, or this tag with its done word set), or a wait timed out somewhere.
+// Which of the kLoopPoseCopies copies of the pose workgroup b looks at (kernels.h): its XCD's by default.
+__device__ __forceinline__ unsigned loop_pose_copy(int pose_map) {
+    const unsigned b = blockIdx.x;
+    return pose_map == 1 ? 0u : ((pose_map == 2 ? b + 3u : b) & static_cast<unsigned>(kLoopPoseCopies - 1));
+}
 __device__ __forceinline__ void chain_wait_pose(const IcpParams &P, uint32_t *smem, int lane) {
     LoopShared *sh = P.chain;
     const unsigned long long tag = static_cast<unsigned long long>(P.chain_iter);
-    const unsigned long long *src = lane < kLoopPoseGranules ? &sh->pose[lane] : &sh->abort_word[0];
+    const unsigned long long *src = lane < kLoopPoseGranules ? &sh->pose[loop_pose_copy(P.chain_pose_map)][lane] : &sh->abort_word[0];
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     unsigned go = 0u;
     unsigned long long g;
@@ -1793,8 +1798,8 @@ __global__ __launch_bounds__(kFinThreads) void k_fin(FinParams P) {
 //   wave              workgroups (two sets alternate; the one just read is cleared for the iteration
 //                     after the next), [exchanges the sums with the peer GPUs,] solves, composes, tests,
 //                     and publishes the next pose as 25 self-tagged 8-byte granules (tag = iteration
-//                     + 1: the data is the flag, no fence on either side);
-//   wave 0 of every   polls the granules (one relaxed agent-scope load per lane and pass), hands the
+//                     + 1: the data is the flag, no fence on either side), one copy per XCD;
+//   wave 0 of every   polls its XCD's granules (one relaxed agent-scope load per lane and pass), hands the
 //   workgroup         pose to its workgroup through LDS;  __syncthreads();  next iteration.
 // Every word the workgroups share is accessed with agent-scope atomics only.  Every wait is bounded:
 // a timeout raises LoopShared::abort_word and IcpState::loop_aborted, everybody leaves, and the host
@@ -1907,19 +1912,31 @@ __device__ __forceinline__ void exchange_abort_wave(const P2pParams &X, unsigned
 struct SolveLds {
     double T[14];              // T[7] | T_icp[7]
     double S[kNumSums];
-    double pub[12];
-    long long digits[kAccWords];
 };
+// 64 bits of lane `src` (wave-uniform), on every lane
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int src) {
+    const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<unsigned>(v)), src));
+    const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<unsigned>(v >> 32)), src));
+    return (static_cast<unsigned long long>(hi) << 32) | lo;
+}
+// The lane index, derived anew: what the compiler can trace to threadIdx it knows to be the same in every iteration
+// of the solving wave's loop, and it would keep every select mask and address made from it alive across the solve.
+__device__ __forceinline__ int lane_now() {
+    unsigned l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return static_cast<int>(l);
+}
 template <int COPIES>
 __device__ __forceinline__ unsigned loop_finish_iteration(const LoopParams &L, const P2pParams &X, SolveLds &m, int it,
                                                           unsigned long long &xg) {
     LoopShared *sh = L.sh;
     IcpState *st = L.st;
     const int lane = static_cast<int>(threadIdx.x & 63u);          // (one wave)
-    double *sT = m.T, *S = m.S, *pub = m.pub;
-    long long *digits = m.digits;
+    double *sT = m.T, *S = m.S;
     const unsigned long long tag = static_cast<unsigned long long>(it) + 1ull;
 
+    double sum = 0.0;          // lane l < kAccValues: value l of this iteration's sums
+    bool overflow;
     // 1. the sums of this iteration's set of accumulators: read (one round trip per pass) until every word
     // says that all the workgroups adding into it are in (its low byte counts them, wgacc_flush) —
     // the read that finds them complete IS the read of the sums.  The set is then cleared for the
@@ -1949,11 +1966,11 @@ __device__ __forceinline__ unsigned loop_finish_iteration(const LoopParams &L, c
                 if (lane == 0) {
                     st_agent(&sh->abort_word[0], 1ull);
                     st->loop_aborted = 1;
-                    st_agent(&sh->pose[24], (tag << 32) | 2ull);
                     if (L.progress)        // (chained launches: the host stops enqueuing)
                         __hip_atomic_store(&L.progress->word, (1ull << 32) | static_cast<unsigned long long>(it), __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_SYSTEM);
                 }
+                if (const int al = lane_now(); al < kLoopPoseCopies) st_agent(&sh->pose[al][24], (tag << 32) | 2ull);      // (every copy's done word)
                 if (X.nranks > 1) {
                     // the peers are inside (or on their way to) this very exchange: they leave it with us, and every
                     // rank registers the frame again through the launch-per-iteration form, in step (run_icp)
@@ -1974,22 +1991,21 @@ __device__ __forceinline__ unsigned loop_finish_iteration(const LoopParams &L, c
 #pragma unroll
         for (int r = 0; r < COPIES; ++r)
             __hip_atomic_store(&acc[r][lane], 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        digits[lane] = d;
-        __builtin_amdgcn_wave_barrier();
-        if (lane < kNumSums) {
-            double r = 0.0;
-            if (lane < kAccValues) {
-                const double a = static_cast<double>(digits[3 * lane]);
-                const double b = static_cast<double>(digits[3 * lane + 1]);
-                const double c = static_cast<double>(digits[3 * lane + 2]);
-                r = a + (b * 9.094947017729282e-13 + c * 8.271806125530277e-25);      // 2^-40, 2^-80
-                if (lane < kCount) r *= L.acc_unscale;     // (a power of two; the pair count is not scaled)
-            }
-            S[lane] = r;
+        // the three digits of value l, held by the lanes 3 l .. 3 l + 2, come to lane l across the lanes (no trip
+        // through LDS and no barrier in the chain the grid waits for)
+        const int sl = lane_now();
+        const int s3 = 3 * (sl < kAccValues ? sl : 0);
+        const double a = static_cast<double>(__shfl(d, s3));
+        const double b = static_cast<double>(__shfl(d, s3 + 1));
+        const double c = static_cast<double>(__shfl(d, s3 + 2));
+        if (lane < kAccValues) {
+            sum = a + (b * 9.094947017729282e-13 + c * 8.271806125530277e-25);      // 2^-40, 2^-80
+            if (lane < kCount) sum *= L.acc_unscale;     // (a power of two; the pair count is not scaled)
         }
+        if (lane < kNumSums) S[lane] = sum;
+        overflow = readlane_u64(static_cast<unsigned long long>(d), 3 * kAccValues) != 0ull;      // workgroups whose sums left the range (wgacc_flush)
         __builtin_amdgcn_wave_barrier();
     }
-    const bool overflow = digits[3 * kAccValues] != 0;       // workgroups whose sums left the range (wgacc_flush)
     LOOP_STAMP_SOLVER(it, 1);
 
     // 2. multi-GPU: this rank's sums -> the sums over all ranks (direct exchange over xGMI, P2pBlock)
@@ -2005,11 +2021,11 @@ __device__ __forceinline__ unsigned loop_finish_iteration(const LoopParams &L, c
                 st_agent(&sh->abort_word[0], 1ull);
                 st->loop_aborted = 1;
                 st->peer_aborted = 1;
-                st_agent(&sh->pose[24], (tag << 32) | 2ull);
                 if (L.progress)        // (chained launches: the host stops enqueuing)
                     __hip_atomic_store(&L.progress->word, (1ull << 32) | static_cast<unsigned long long>(it), __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_SYSTEM);
             }
+            if (const int al = lane_now(); al < kLoopPoseCopies) st_agent(&sh->pose[al][24], (tag << 32) | 2ull);      // (every copy's done word)
             return 2u;
         }
     }
@@ -2048,18 +2064,26 @@ __device__ __forceinline__ unsigned loop_finish_iteration(const LoopParams &L, c
     // for its sums; the flag is raised and the host reports it when the loop has ended everywhere)
     if (overflow && !L.shared_loop) done = 1u;
     if (exchange_failed) done = 1u;
-    if (lane == 0) {
+    // 4. publish: 24 halves of R, t and the done word, each with its tag, once per copy of the pose — before the
+    // bookkeeping below: the grid waits for these words, nobody for the history (and the wait that follows would
+    // otherwise sit out those stores' round trip).  Every lane but lane 1 (which composed T_icp) holds the same R and t:
+    // the lanes 2 + l and 34 + l select granule l from their own registers — no trip through LDS —, one store
+    // instruction writes two copies, four write them all, fire and forget.
+    const int pl = lane_now();
+    const int gl = (pl & 31) - 2;
+    uint32_t word = done;                  // granule 24
 #pragma unroll
-        for (int i = 0; i < 9; ++i) pub[i] = Rn[i];
-        pub[9] = Tn[4]; pub[10] = Tn[5]; pub[11] = Tn[6];
+    for (int i = 0; i < 12; ++i) {
+        const unsigned long long v = static_cast<unsigned long long>(__double_as_longlong(i < 9 ? Rn[i] : Tn[i - 5]));
+        if ((gl >> 1) == i) word = static_cast<uint32_t>((gl & 1) ? v >> 32 : v);
     }
-    __builtin_amdgcn_wave_barrier();
     LOOP_STAMP_SOLVER(it, 2);
-    // 4. publish: 24 halves of R, t and the done word, each with its tag — before the bookkeeping below: the grid waits
-    // for these words, nobody for the history (and the wait that follows would otherwise sit out those stores' round trip)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the clears of step 1, issued microseconds ago)
-    if (lane < 24) st_agent(&sh->pose[lane], (tag << 32) | reinterpret_cast<const uint32_t *>(pub)[lane]);
-    if (lane == 24) st_agent(&sh->pose[24], (tag << 32) | done);
+    if (gl >= 0 && gl < kLoopPoseGranules) {
+#pragma unroll
+        for (int c = 0; c < kLoopPoseCopies; c += 2)
+            st_agent(&sh->pose[c + (pl >> 5)][gl], (tag << 32) | word);
+    }
     if (lane == 0) {
         if (it < kHistory) st->n_corr[it] = static_cast<uint32_t>(S[kCount]);
         if (overflow) st->acc_overflow = 1;
@@ -2421,7 +2445,7 @@ void k_loop(LoopArgs A) {
             unsigned long long g = tag << 32;
             bool aborted = false;
             for (;;) {
-                if (lane < kLoopPoseGranules) g = ld_agent(&sh->pose[lane]);
+                if (lane < kLoopPoseGranules) g = ld_agent(&sh->pose[loop_pose_copy(L.pose_map)][lane]);
                 const bool ok = (g >> 32) == tag;
                 if (__all(ok)) break;
                 unsigned long long ab = 0ull;
@@ -2435,12 +2459,13 @@ void k_loop(LoopArgs A) {
                     aborted = true;
                     break;
                 }
-                // (more than a thousand workgroups wait here for most of an iteration, all on the same four
-                // cache lines: a pass every ~0.3 us each leaves the L2 channel that serves them — and the
-                // accumulators the solving wave is reading — alone)
+                // (more than a thousand workgroups wait here for most of an iteration — since the pose has a copy per
+                // XCD, some two hundred per copy, on four cache lines of their own: a pass every ~0.3 us each keeps
+                // the L2 that serves them, and the accumulators the solving wave is reading, quiet)
                 __builtin_amdgcn_s_sleep(SAGE_LOOP_POLL_SLEEP);
                 // (a big grid backs off twice as long: c2's 1,664 workgroups 30.7 -> 30.3 us per iteration, flat from there
-                // to six times as long; c1's 640 prefer the short one — same-box A/B, profiles/r05/poll_sleep.txt)
+                // to six times as long; c1's 640 prefer the short one — same-box A/B, profiles/r05/poll_sleep.txt, taken
+                // when all of them polled ONE block; with a copy per XCD: profiles/r15/README.md)
                 if (L.wgs > 1024) __builtin_amdgcn_s_sleep(SAGE_LOOP_POLL_SLEEP);
             }
             if (aborted) {
