@@ -178,12 +178,6 @@ void sageicp_map_destroy(sageicp_map *m) {
     m->ranks.clear();
     for (sageicp_map *r : m->replicas) sageicp_map_destroy(r);
     m->replicas.clear();
-    if (m->sc.stream) {
-        (void)hipSetDevice(m->device);
-        (void)hipStreamSynchronize(m->sc.stream);
-    }
-    if (m->ev_caller) (void)hipEventDestroy(m->ev_caller);
-    m->sc.destroy();
     delete m;
 }
 
@@ -201,8 +195,8 @@ static int clone_on_device(const sageicp_map *src, sageicp_map *m) {
     int rc = m->sc.init(m->device);
     if (rc) return rc;
     HIPCHK(hipSetDevice(m->device));
-    hipStream_t s = m->sc.stream;
-    HIPCHK(hipStreamSynchronize(src->sc.stream));
+    hipStream_t s = m->sc.stream.get();
+    HIPCHK(hipStreamSynchronize(src->sc.stream.get()));
     HIPCHK(m->d_table.reserve(src->d_table.capacity()));
     HIPCHK(hipMemcpyAsync(m->d_table.data(), src->d_table.data(), src->d_table.capacity() * sizeof(Slot),
                           hipMemcpyDeviceToDevice, s));
@@ -449,7 +443,7 @@ static int pack_resident(const sageicp_map *m, const EgressArgs *e, hipStream_t 
 
 static int pointcloud_from_device(const sageicp_map *m, double *out, uint64_t cap, uint64_t *n_out) {
     HIPCHK(hipSetDevice(m->device));
-    hipStream_t s = m->sc.stream;
+    hipStream_t s = m->sc.stream.get();
     const uint64_t total = m->ctr.total_points;
     *n_out = total;
     const uint64_t want = out ? std::min(cap, total) : 0;
@@ -512,7 +506,7 @@ int sageicp_get_correspondences(const sageicp_map *m, const double *q, uint64_t 
     if ((rc = sc.reserve_frame(n))) return rc;
     if ((rc = sc.reserve_nn(n))) return rc;
     if ((rc = sc.reserve_sort(n))) return rc;
-    hipStream_t s = sc.stream;
+    hipStream_t s = sc.stream.get();
     HIPCHK(hipMemcpyAsync(sc.d_frame.data(), q, n * sizeof(Point4), hipMemcpyHostToDevice, s));
     double I[7];
     identity_pose(I);
@@ -564,7 +558,7 @@ int sageicp_align_clouds(const double *src, const double *tgt, uint64_t n, doubl
     HIPCHK(hipSetDevice(device));
     if ((rc = sc.reserve_frame(n))) return rc;
     if ((rc = sc.reserve_tgt(n))) return rc;
-    hipStream_t s = sc.stream;
+    hipStream_t s = sc.stream.get();
     if (n) {
         HIPCHK(hipMemcpyAsync(sc.d_frame.data(), src, n * sizeof(Point4), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(sc.d_tgt.data(), tgt, n * sizeof(Point4), hipMemcpyHostToDevice, s));
@@ -605,7 +599,7 @@ int sageicp_transform_points(const double pose[7], double *xyzl, uint64_t n, int
     if (rc) return rc;
     HIPCHK(hipSetDevice(device));
     if ((rc = sc.reserve_frame(n))) return rc;
-    hipStream_t s = sc.stream;
+    hipStream_t s = sc.stream.get();
     fill_state(sc.h_state.data(), pose);
     HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
     if (n) {
@@ -636,7 +630,7 @@ int sageicp_register_frame(const sageicp_map *m, const double *frame, uint64_t n
     Scratch &sc = m->sc;
     if ((rc = sc.reserve_frame(n))) return rc;
     if (n) HIPCHK(hipMemcpyAsync(sc.d_frame.data(), frame, n * sizeof(Point4), hipMemcpyHostToDevice,
-                                 sc.stream));
+                                 sc.stream.get()));
     const double us_upload = now_us() - t0;
     return run_icp(m, sc.d_frame.data(), n, init, max_dist, kernel, sem_th, nullptr, pose_out, stats,
                    us_upload, t0);
@@ -869,11 +863,11 @@ int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_poi
     if (!want) return SAGEICP_OK;
     if ((rc = m->sc.init(m->device))) return rc;
     HIPCHK(hipSetDevice(m->device));
-    const hipStream_t s = m->sc.stream;
-    if (!m->ev_caller) HIPCHK(hipEventCreateWithFlags(&m->ev_caller, hipEventDisableTiming));
+    const hipStream_t s = m->sc.stream.get();
+    if (!m->ev_caller) HIPCHK(m->ev_caller.create(hipEventDisableTiming));
     // the map's stream waits for the work the caller enqueued before this call (it may still use the destination)
-    HIPCHK(hipEventRecord(m->ev_caller, static_cast<hipStream_t>(stream)));
-    HIPCHK(hipStreamWaitEvent(s, m->ev_caller, 0));
+    HIPCHK(hipEventRecord(m->ev_caller.get(), static_cast<hipStream_t>(stream)));
+    HIPCHK(hipStreamWaitEvent(s, m->ev_caller.get(), 0));
     std::vector<double> staged;                         // (read by a copy on s: egress_into waits for it)
     return egress_into(m->d_egress_flag, *dst, s, [&](const EgressArgs &e) -> int {
         if (m->on_device && !env_int("SAGEICP_EGRESS_TWO_PASS", 0))
@@ -1161,9 +1155,8 @@ struct sageicp_pipeline {
     sageicp::Pipeline impl;
     // Preprocess() + Voxelize() depend on the raw frame only (not on the pose, not on the map), so
     // the next frame's can run while this one registers (sageicp_pipeline_prefetch): two sets of
-    // buffers and streams, `cur` the one the frame being registered lives in.  (Not with deskew on: a
+    // buffers and streams (prep[2], below), `cur` the one the frame being registered lives in.  (Not with deskew on: a
     // deskewed frame depends on the poses of the two frames before it, so prefetch is refused then.)
-    sageicp::Prep prep[2];
     int cur = 0;
     int device;
     std::thread worker;                  // runs the announced frame's voxelize on prep[cur ^ 1]
@@ -1226,11 +1219,11 @@ struct sageicp_pipeline {
         }
         KeyFrames() { clear(); }
     } kf;
+    // (after the buffers that work on their streams touches — d_egress_flag, kf's: the Preps wait and go first)
+    sageicp::Prep prep[2];
     explicit sageicp_pipeline(const sageicp_pipeline_config &c) : impl(c), device(c.device) {}
     ~sageicp_pipeline() {
-        if (worker.joinable()) worker.join();
-        prep[0].destroy();
-        prep[1].destroy();
+        if (worker.joinable()) worker.join();          // (it works on a Prep: joined before either goes)
     }
     int voxelize_into(sageicp::Prep &pr, const double *f, uint64_t m, const sageicp::DeskewArgs *deskew = nullptr,
                       const sageicp::DeviceSource *dev = nullptr) {
@@ -1304,7 +1297,7 @@ static void occ_unpack_host(const uint32_t *bits, const OccGrid &g, uint8_t *out
 static int key_frame_step(sageicp_pipeline *p, uint64_t n) {
     auto &k = p->kf;
     sageicp::Prep &pr = p->prep[p->cur];
-    const hipStream_t s = pr.stream;
+    const hipStream_t s = pr.stream.get();
     const uint32_t words = occ_words(k.g);
     HIPCHK(hipSetDevice(p->device));
     if (!k.d_key) {

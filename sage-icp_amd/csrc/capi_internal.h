@@ -140,7 +140,7 @@ constexpr int kChunkMax = 16;
 
 struct Scratch {
     int device = -1;
-    hipStream_t stream = nullptr;
+    OwnedStream stream;
     DevBuf<Point4> d_frame, d_tgt;
     DevBuf<int32_t> d_nn;
     // Morton re-ordering of the frame (sort.hip)
@@ -156,11 +156,11 @@ struct Scratch {
     DevBuf<long long> d_acc;       // fixed-point accumulators of the Gauss-Newton sums (kernels.h, kAcc*)
     DevBuf<LoopShared> d_loop;     // what the workgroups of k_loop share inside its launch (kernels.h)
     unsigned long long go_word = 0; // (host source of a `go` word sent by a copy: SolverGuard)
-    hipStream_t stream2 = nullptr; // the solving wave of the one-launch loop runs here, beside the grid on `stream`
+    OwnedStream stream2;           // the solving wave of the one-launch loop runs here, beside the grid on `stream`
                                    // (created with the first such launch: a process has few hardware queues, and
                                    // streams that never run anything still take their turn on them)
     std::vector<uint32_t> cu_mask; // of both streams (empty: the whole device)
-    hipEvent_t ev_solve = nullptr; // ... and this says that it has finished
+    OwnedEvent ev_solve;           // ... and this says that it has finished
     unsigned long long loop_epoch = 0;
     int num_cus = 0;               // CUs the streams of this handle may use (the whole device, or its share: below)
     int cu_share_i = 0, cu_share_k = 1;   // SAGEICP_CU_SHARE=i/k: the i-th of k equal parts of the device's CUs (several
@@ -176,12 +176,16 @@ struct Scratch {
     PinnedBuf<IcpState> h_state;
     PinnedBuf<IcpProgress, hipHostMallocMapped | hipHostMallocCoherent> h_prog;   // written by the device every iteration
     IcpProgress *d_prog = nullptr; // its device address
-    std::vector<hipEvent_t> events;  // 5 per profiled iteration
+    std::vector<OwnedEvent> events;  // 5 per profiled iteration
 
-    Scratch() = default;
-    Scratch(Scratch &&) = default;
-    Scratch &operator=(Scratch &&) = default;       // (destroy() empties the scratch by assigning a fresh one)
-    ~Scratch() { destroy(); }
+    ~Scratch() { wait(); }          // (then the members go: nothing runs on the streams any more)
+    // waits for both streams, with the device current (a scratch that never created a stream calls nothing)
+    void wait() const {
+        if (!stream) return;
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream.get());
+        if (stream2) (void)hipStreamSynchronize(stream2.get());
+    }
 
     int init(int dev) {
         if (stream) return SAGEICP_OK;
@@ -207,13 +211,13 @@ struct Scratch {
             const int per = num_cus / cu_share_k, lo = cu_share_i * per;
             std::vector<uint32_t> mask((num_cus + 31) / 32, 0u);
             for (int c = lo; c < lo + per; ++c) mask[c / 32] |= 1u << (c % 32);
-            HIPCHK(hipExtStreamCreateWithCUMask(&stream, static_cast<uint32_t>(mask.size()), mask.data()));
+            HIPCHK(stream.create(static_cast<uint32_t>(mask.size()), mask.data()));
             cu_mask = mask;
             num_cus = per;
         } else {
             cu_share_i = 0;
             cu_share_k = 1;
-            HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            HIPCHK(stream.create());
         }
         HIPCHK(d_state.reserve(1));
         HIPCHK(d_acc.reserve(kAccReplicas * kAccWords));
@@ -228,19 +232,20 @@ struct Scratch {
     int loop_streams() {
         if (stream2) return SAGEICP_OK;
         HIPCHK(hipSetDevice(device));
-        if (!cu_mask.empty()) HIPCHK(hipExtStreamCreateWithCUMask(&stream2, static_cast<uint32_t>(cu_mask.size()), cu_mask.data()));
+        if (!cu_mask.empty()) HIPCHK(stream2.create(static_cast<uint32_t>(cu_mask.size()), cu_mask.data()));
         else {
             // a stream of its own priority gets a hardware queue of its own: the solving wave runs for the whole
             // loop, and whatever shared its queue (a process has four) would wait behind it — the pipeline's
             // prefetch stream did (2.74 against 2.17 ms per streamed frame, profiles/r05/stream.txt)
             int least = 0, greatest = 0;
             (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-            if (hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, greatest) != hipSuccess) {
+            if (stream2.create(greatest) != hipSuccess) {
                 (void)hipGetLastError();
-                HIPCHK(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
+                HIPCHK(stream2.create());
             }
         }
-        HIPCHK(hipEventCreateWithFlags(&ev_solve, hipEventDisableTiming));
+        // (if this fails, stream2 exists and the next call returns above: ev_solve stays empty)
+        HIPCHK(ev_solve.create(hipEventDisableTiming));
         return SAGEICP_OK;
     }
     int reserve_frame(size_t n) {
@@ -278,24 +283,11 @@ struct Scratch {
     }
     int reserve_events(size_t iterations) {
         while (events.size() < 5 * iterations) {
-            hipEvent_t e;
-            HIPCHK(hipEventCreate(&e));
-            events.push_back(e);
+            OwnedEvent e;
+            HIPCHK(e.create(hipEventDefault));
+            events.push_back(std::move(e));
         }
         return SAGEICP_OK;
-    }
-    void destroy() {
-        if (!stream) return;
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(stream);
-        if (stream2) (void)hipStreamSynchronize(stream2);
-        if (ev_solve) (void)hipEventDestroy(ev_solve);
-        if (stream2) (void)hipStreamDestroy(stream2);
-        for (auto &e : events) (void)hipEventDestroy(e);
-        events.clear();
-        const hipStream_t s = stream;
-        *this = Scratch();              // (releases the buffers: nothing runs on the streams any more)
-        (void)hipStreamDestroy(s);
     }
 };
 
@@ -410,13 +402,12 @@ struct DynFilter {
     DevBuf<unsigned char> d_temp;
     PinnedBuf<uint4> h_rec;                    // the component table
     PinnedBuf<uint32_t> h_off;                 // output offset per component (~0: dropped)
-    hipEvent_t ev[6] = {};                     // device time of the three launch batches (sageicp_set_profiling)
-    hipEvent_t ev_table = nullptr;
+    OwnedEvent ev[6];                          // device time of the three launch batches (sageicp_set_profiling)
+    OwnedEvent ev_table;
     std::vector<uint32_t> order_scratch, size_scratch;
     sageicp_dynfilter_info info{};             // of the last run
 
     int reserve(size_t n, size_t nlabels);
-    void destroy();
     int run(const Point4 *in, uint64_t n, double max_range, double min_range, double label_max_range,
             const DynFilterConfig &cfg, Point4 *tmp, Point4 *out, int *d_ovf, uint64_t &n_out, hipStream_t s);
 };
@@ -451,7 +442,7 @@ inline IngestArgs ingest_args(const sageicp_device_frame &f) {
 // ---- device preprocessing (preprocess.hip): buffers of one pipeline ------------------------------
 struct Prep {
     int device = -1;
-    hipStream_t stream = nullptr;
+    OwnedStream stream;
     size_t cap = 0;                     // points the buffers of reserve() hold (all of them: 0 after a failed reserve)
     DevBuf<Point4> d_in, d_tmp, d_fd, d_src;
     DevBuf<uint32_t> d_slot, d_skey, d_sval, d_winner;
@@ -479,23 +470,26 @@ struct Prep {
     // the timestamps of a frame that is deskewed (allocated with the first such frame): pinned staging, device copy
     PinnedBuf<double> h_ts;
     DevBuf<double> d_ts;
-    hipEvent_t ev_caller = nullptr;     // a device frame: orders the caller's stream before `stream` (created with the first)
+    OwnedEvent ev_caller;               // a device frame: orders the caller's stream before `stream` (created with the first)
     // key-frame selection (keyframe.hip): the raw frame copied aside before deskew and the dynamic filter rewrite d_in
     // in place — its coordinates checked — for the pass that follows the registration (allocated with the first use)
     bool keep_raw = false;
     DevBuf<Point4> d_raw;
 
-    Prep() = default;
-    Prep(Prep &&) = default;
-    Prep &operator=(Prep &&) = default;             // (destroy() empties the buffers by assigning a fresh Prep)
-    ~Prep() { destroy(); }
+    // waits for the stream with the device current, then the members go, dyn's among them: nothing runs on the stream
+    // any more (a Prep that never created its stream calls nothing)
+    ~Prep() {
+        if (!stream) return;
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream.get());
+    }
 
     int init(int dev) {
         if (stream) return SAGEICP_OK;
         if (int rc = require_device(dev)) return rc;
         device = dev;
         HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        HIPCHK(stream.create());
         HIPCHK(d_nkept.reserve(2));
         HIPCHK(d_overflow.reserve(1));
         HIPCHK(d_gcounts.reserve(8));
@@ -535,36 +529,26 @@ struct Prep {
         HIPCHK(h_ts.reserve(c));
         return SAGEICP_OK;
     }
-    void destroy() {
-        if (!stream) return;
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(stream);
-        dyn.destroy();
-        if (ev_caller) (void)hipEventDestroy(ev_caller);
-        const hipStream_t s = stream;
-        *this = Prep();                 // (releases the buffers: nothing runs on the stream any more)
-        (void)hipStreamDestroy(s);
-    }
 
     // The raw frame of a device source into d_in (and its timestamps into d_ts), after the work the caller enqueued on
     // its stream.  Timestamps are checked here, before anything reads them: a non-finite one refuses the frame (the
     // host entry's check, sageicp_pipeline_register_frame_timestamps).  The caller's buffers are last read by this
     // launch, which the first level's synchronisation waits for: run() returns with them released.
     int ingest(const DeviceSource &src, uint64_t n) {
-        if (!ev_caller) HIPCHK(hipEventCreateWithFlags(&ev_caller, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(ev_caller, src.stream));
-        HIPCHK(hipStreamWaitEvent(stream, ev_caller, 0));
+        if (!ev_caller) HIPCHK(ev_caller.create(hipEventDisableTiming));
+        HIPCHK(hipEventRecord(ev_caller.get(), src.stream));
+        HIPCHK(hipStreamWaitEvent(stream.get(), ev_caller.get(), 0));
         IngestArgs a = ingest_args(*src.frame);
         a.n = static_cast<int>(n);
         a.ts = src.timestamps;
         a.ts_out = src.timestamps ? d_ts.data() : nullptr;
         a.flags = d_overflow.data();
-        launch_ingest(a, d_in.data(), stream);
+        launch_ingest(a, d_in.data(), stream.get());
         HIPCHK(hipGetLastError());
         if (src.timestamps) {
             int flags = 0;
-            HIPCHK(hipMemcpyAsync(&flags, d_overflow.data(), sizeof(int), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
+            HIPCHK(hipMemcpyAsync(&flags, d_overflow.data(), sizeof(int), hipMemcpyDeviceToHost, stream.get()));
+            HIPCHK(hipStreamSynchronize(stream.get()));
             if (flags & kIngestBadTimestamp) return fail(SAGEICP_ERR_INVALID, "deskew is on and a timestamp is not finite");
         }
         return SAGEICP_OK;
@@ -602,27 +586,27 @@ struct Prep {
         out.assign(n_levels, std::vector<double>());
         if (n == 0) return SAGEICP_OK;
         if (n_groups > 0) {
-            HIPCHK(hipMemcpyAsync(d_gcounts.data(), gcounts, n_groups * sizeof(int), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemcpyAsync(d_glabels.data(), glabels, nlabels * sizeof(int), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(d_gcounts.data(), gcounts, n_groups * sizeof(int), hipMemcpyHostToDevice, stream.get()));
+            HIPCHK(hipMemcpyAsync(d_glabels.data(), glabels, nlabels * sizeof(int), hipMemcpyHostToDevice, stream.get()));
         }
-        HIPCHK(hipMemsetAsync(d_overflow.data(), 0, sizeof(int), stream));
+        HIPCHK(hipMemsetAsync(d_overflow.data(), 0, sizeof(int), stream.get()));
         if (keep_raw && d_raw.capacity() < n) HIPCHK(d_raw.reserve(n + n / 4 + 1024));
         if (dev) {
             rc = ingest(*dev, n);
             if (rc) return rc;
-            if (keep_raw) launch_occ_keep(d_in.data(), d_raw.data(), static_cast<int>(n), d_overflow.data(), stream);
+            if (keep_raw) launch_occ_keep(d_in.data(), d_raw.data(), static_cast<int>(n), d_overflow.data(), stream.get());
             if (deskew) {
-                launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream);
+                launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream.get());
                 HIPCHK(hipGetLastError());
             }
         } else {
             std::memcpy(h_pin.data(), frame, n * sizeof(Point4));
-            HIPCHK(hipMemcpyAsync(d_in.data(), h_pin.data(), n * sizeof(Point4), hipMemcpyHostToDevice, stream));
-            if (keep_raw) launch_occ_keep(d_in.data(), d_raw.data(), static_cast<int>(n), d_overflow.data(), stream);
+            HIPCHK(hipMemcpyAsync(d_in.data(), h_pin.data(), n * sizeof(Point4), hipMemcpyHostToDevice, stream.get()));
+            if (keep_raw) launch_occ_keep(d_in.data(), d_raw.data(), static_cast<int>(n), d_overflow.data(), stream.get());
             if (deskew) {
                 std::memcpy(h_ts.data(), deskew->timestamps, n * sizeof(double));
-                HIPCHK(hipMemcpyAsync(d_ts.data(), h_ts.data(), n * sizeof(double), hipMemcpyHostToDevice, stream));
-                launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream);
+                HIPCHK(hipMemcpyAsync(d_ts.data(), h_ts.data(), n * sizeof(double), hipMemcpyHostToDevice, stream.get()));
+                launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream.get());
                 HIPCHK(hipGetLastError());
             }
         }
@@ -631,7 +615,7 @@ struct Prep {
         uint64_t cur = n;
         if (dyn_cfg) {      // the filtered cloud replaces the frame in d_in (the filter has read it by then)
             int r = dyn.run(d_in.data(), n, max_range, min_range, label_max_range, *dyn_cfg, d_tmp.data(), d_in.data(), d_overflow.data(), cur,
-                            stream);
+                            stream.get());
             if (r) return r;
         }
         for (int l = 0; l < n_levels; ++l) {
@@ -648,18 +632,18 @@ struct Prep {
             const bool reorder = g_reference_order && P.n_groups > 0 && !((arrival_order_levels >> l) & 1u);
             P.out_keys = reorder ? d_okeys.data() : nullptr;
             Point4 *dst = outs[l & 1];
-            HIPCHK(voxel_downsample_device(P, d_sort_temp.data(), d_sort_temp.capacity(), d_nkept.data() + (l & 1), dst, stream));
+            HIPCHK(voxel_downsample_device(P, d_sort_temp.data(), d_sort_temp.capacity(), d_nkept.data() + (l & 1), dst, stream.get()));
             uint32_t kept = 0;
-            HIPCHK(hipMemcpyAsync(&kept, d_nkept.data() + (l & 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
+            HIPCHK(hipMemcpyAsync(&kept, d_nkept.data() + (l & 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream.get()));
+            HIPCHK(hipStreamSynchronize(stream.get()));
             kept_levels[l & 1] = kept;
             if (reorder && kept) {
                 // the reference's emission order (Preprocessing.cpp:76-82): replay, group by
                 // group, the insertions into its robin_map and permute the survivors
                 const double t0 = now_us();
                 HIPCHK(hipMemcpyAsync(h_keys.data(), d_okeys.data(), kept * sizeof(unsigned long long),
-                                      hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
+                                      hipMemcpyDeviceToHost, stream.get()));
+                HIPCHK(hipStreamSynchronize(stream.get()));
                 const double t1 = now_us();
                 h_hash.resize(kept);
                 // survivors are grouped (stable sort by group); the groups' tables are independent:
@@ -713,9 +697,9 @@ struct Prep {
                     for (size_t r = 0; r < runs.size(); ++r) replay(r);
                 }
                 const double t2 = now_us();
-                HIPCHK(hipMemcpyAsync(d_perm.data(), h_perm.data(), kept * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-                launch_vds_permute(dst, d_perm.data(), kept, d_tmp.data(), stream);
-                HIPCHK(hipMemcpyAsync(dst, d_tmp.data(), kept * sizeof(Point4), hipMemcpyDeviceToDevice, stream));
+                HIPCHK(hipMemcpyAsync(d_perm.data(), h_perm.data(), kept * sizeof(uint32_t), hipMemcpyHostToDevice, stream.get()));
+                launch_vds_permute(dst, d_perm.data(), kept, d_tmp.data(), stream.get());
+                HIPCHK(hipMemcpyAsync(dst, d_tmp.data(), kept * sizeof(Point4), hipMemcpyDeviceToDevice, stream.get()));
                 us_order += now_us() - t0;
                 if (env_int("SAGEICP_DEBUG_ORDER", 0)) {
                     std::string rs;
@@ -726,8 +710,8 @@ struct Prep {
             }
             if (download) {       // otherwise the level's cloud stays in d_fd / d_src for the caller
                 Point4 *hp = h_pin.data() + static_cast<size_t>(1 + (l & 1)) * cap;
-                if (kept) HIPCHK(hipMemcpyAsync(hp, dst, kept * sizeof(Point4), hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
+                if (kept) HIPCHK(hipMemcpyAsync(hp, dst, kept * sizeof(Point4), hipMemcpyDeviceToHost, stream.get()));
+                HIPCHK(hipStreamSynchronize(stream.get()));
                 out[l].resize(4 * static_cast<size_t>(kept));
                 if (kept) std::memcpy(out[l].data(), hp, kept * sizeof(Point4));
             }
@@ -826,7 +810,7 @@ struct sageicp_map {
     // sageicp_map_pointcloud_device: the label-range flag (egress.h) and the event that orders the caller's stream
     // before the map's (created with the first call)
     mutable DevBuf<int> d_egress_flag;
-    mutable hipEvent_t ev_caller = nullptr;
+    mutable OwnedEvent ev_caller;
     size_t units_cap() const { return d_pts.capacity() / kUnitPoints; }       // units the point array holds
     size_t blocks_cap() const { return d_zeros.capacity(); }
     size_t cand_slots() const { return d_cand.capacity() ? d_cand.capacity() - 1 - kCandSlack : 0; }
@@ -840,6 +824,8 @@ struct sageicp_map {
     // ranks would sum Gauss-Newton terms computed against different maps, so every later entry
     // refuses the handle until Clear() has emptied all copies
     bool replicas_diverged = false;
+    // the buffers above are used on sc's streams and go before sc does: the streams are waited for first
+    ~sageicp_map() { sc.wait(); }
 };
 
 struct sageicp_frame {

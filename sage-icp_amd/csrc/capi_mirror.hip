@@ -20,7 +20,7 @@ int reserve_stage(const sageicp_map *m, size_t bytes) {
 // target for an offset of one past the end), the first `keep` units preserved.
 int reserve_device_points(const sageicp_map *m, size_t units, size_t keep) {
     if (units <= m->units_cap()) return SAGEICP_OK;
-    hipStream_t s = m->sc.stream;
+    hipStream_t s = m->sc.stream.get();
     HIPCHK(m->d_pts.grow(units * kUnitPoints + 1, keep * kUnitPoints, s));
     const double qnan = std::numeric_limits<double>::quiet_NaN();
     const Point4 pad{qnan, qnan, qnan, qnan};
@@ -32,7 +32,7 @@ int reserve_device_points(const sageicp_map *m, size_t units, size_t keep) {
 // d_regions for at least `blocks` blocks, the first `keep` preserved, the rest marked free
 int reserve_device_regions(const sageicp_map *m, size_t blocks, size_t keep) {
     if (blocks <= m->d_regions.capacity()) return SAGEICP_OK;
-    hipStream_t s = m->sc.stream;
+    hipStream_t s = m->sc.stream.get();
     keep = std::min(keep, m->d_regions.capacity());
     HIPCHK(m->d_regions.grow(blocks, keep, s));
     HIPCHK(hipMemsetAsync(m->d_regions.data() + keep, 0xFF, (blocks - keep) * sizeof(uint32_t), s));      // kNoRegion
@@ -48,7 +48,7 @@ int sync_mirror(const sageicp_map *m) {
     HIPCHK(hipSetDevice(m->device));
     if (m->on_device) return SAGEICP_OK;      // the HBM copy is the map
     const HostMap &h = m->host;
-    hipStream_t s = m->sc.stream;
+    hipStream_t s = m->sc.stream.get();
     bool any = false;
     bool table_full = h.table_all_dirty || m->mirror_stale_all;
     if (h.table.size() != m->d_table.capacity()) {
@@ -134,7 +134,7 @@ int sync_mirror(const sageicp_map *m) {
 // (`derive` false: the coming search scans the full records — small frames, sparse voxels — so only
 // the allocation is kept in step and the copy stays marked stale for the search that wants it)
 int ensure_cand(const sageicp_map *m, bool derive) {
-    hipStream_t s = m->sc.stream;
+    hipStream_t s = m->sc.stream.get();
     const size_t slots = m->units_cap() * kUnitPoints;
     if (!m->d_cand_flags.data()) {
         HIPCHK(m->d_cand_flags.reserve(4));
@@ -166,7 +166,7 @@ bool map_is_empty(const sageicp_map *m) {
 int ensure_host(const sageicp_map *m) {
     if (!m->on_device) return SAGEICP_OK;
     HIPCHK(hipSetDevice(m->device));
-    hipStream_t s = m->sc.stream;
+    hipStream_t s = m->sc.stream.get();
     HostMap &h = const_cast<HostMap &>(m->host);
     const MapCounters c = m->ctr;
     std::vector<Slot> tab(m->d_table.capacity());
@@ -239,7 +239,7 @@ int reserve_update_scratch(const sageicp_map *m, size_t n, size_t nb) {
 
 // (re)allocate the per-block device arrays for `blocks` blocks, keeping the first `keep` blocks
 int grow_device_blocks(const sageicp_map *m, size_t blocks, size_t keep) {
-    hipStream_t s = m->sc.stream;
+    hipStream_t s = m->sc.stream.get();
     if (int rc = reserve_device_regions(m, blocks, keep)) return rc;
     if (blocks > m->blocks_cap()) {
         keep = std::min(keep, m->blocks_cap());
@@ -260,7 +260,7 @@ int grow_device_blocks(const sageicp_map *m, size_t blocks, size_t keep) {
 // the unit allocator's device arrays: per-class stacks able to hold every region the point array
 // can be cut into, and the scratch list of one pass's released regions (at most one per point)
 int reserve_unit_stacks(const sageicp_map *m, size_t n) {
-    hipStream_t s = m->sc.stream;
+    hipStream_t s = m->sc.stream.get();
     const HostMap &h = m->host;
     for (int k = 0; k < h.n_classes; ++k) {
         const size_t need = m->units_cap() / h.class_units(k) + 1;
@@ -307,7 +307,7 @@ int device_update(sageicp_map *m, const double *xyzl, uint64_t n, const double p
     int rc = m->sc.init(m->device);
     if (rc) return rc;
     HIPCHK(hipSetDevice(m->device));
-    hipStream_t s = m->sc.stream;
+    hipStream_t s = m->sc.stream.get();
     const HostMap &h = m->host;
     if (!m->on_device) {
         if ((rc = sync_mirror(m))) return rc;       // table + points as the host has them

@@ -517,24 +517,24 @@ struct SolverGuard {
     ~SolverGuard() {                              // leaving the call: the word is sent and both streams are waited for
         if (!armed) return;
         const unsigned long long word = epoch | 0x8000000000000000ull;
-        (void)hipMemcpyAsync(&sc.d_loop.data()->go[0], &word, sizeof(word), hipMemcpyHostToDevice, sc.stream);
-        (void)hipStreamSynchronize(sc.stream);
-        (void)hipStreamSynchronize(sc.stream2);
+        (void)hipMemcpyAsync(&sc.d_loop.data()->go[0], &word, sizeof(word), hipMemcpyHostToDevice, sc.stream.get());
+        (void)hipStreamSynchronize(sc.stream.get());
+        (void)hipStreamSynchronize(sc.stream2.get());
     }
     // the solving wave on its own stream — it has to hold its registers before the grid fills the machine; it waits
     // for the grid's (or launch 0's) go
     int start(const LoopParams &L, const P2pParams &xp) {
-        launch_loop_solve(L, xp, sc.stream2);
+        launch_loop_solve(L, xp, sc.stream2.get());
         HIPCHK(hipGetLastError());
         epoch = L.epoch;
         armed = true;
-        HIPCHK(hipEventRecord(sc.ev_solve, sc.stream2));
+        HIPCHK(hipEventRecord(sc.ev_solve.get(), sc.stream2.get()));
         return SAGEICP_OK;
     }
     void disarm() { armed = false; }
     int send_home_now() {                         // in stream order, the call going on (the copy's source outlives it: Scratch::go_word)
         sc.go_word = epoch | 0x8000000000000000ull;
-        HIPCHK(hipMemcpyAsync(&sc.d_loop.data()->go[0], &sc.go_word, sizeof(sc.go_word), hipMemcpyHostToDevice, sc.stream));
+        HIPCHK(hipMemcpyAsync(&sc.d_loop.data()->go[0], &sc.go_word, sizeof(sc.go_word), hipMemcpyHostToDevice, sc.stream.get()));
         armed = false;
         return SAGEICP_OK;
     }
@@ -564,11 +564,11 @@ static int run_one_launch(const IcpCall &c, const AttemptPlan &p, const IcpParam
     lp.filter = p.loop.filter ? ip.filter : 0;
     lp.nwaves = p.loop_waves;
     HIPCHK(hipMemsetAsync(sc.d_loop.data(), 0, offsetof(LoopShared, acc32), s));      // (the chained launches' copies are not this loop's)
-    if (c.prof) HIPCHK(hipEventRecord(sc.events[1], s));
+    if (c.prof) HIPCHK(hipEventRecord(sc.events[1].get(), s));
     launch_loop(lp, L, p.loop.lw, s);
     if (hipPeekAtLastError() == hipSuccess) guard.disarm();      // the grid is on its way: it will say go
-    if (c.prof) HIPCHK(hipEventRecord(sc.events[2], s));
-    if (solver_is_own_launch(p)) HIPCHK(hipStreamWaitEvent(s, sc.ev_solve, 0));      // the solving wave writes the final state
+    if (c.prof) HIPCHK(hipEventRecord(sc.events[2].get(), s));
+    if (solver_is_own_launch(p)) HIPCHK(hipStreamWaitEvent(s, sc.ev_solve.get(), 0));      // the solving wave writes the final state
     if ((rc = c.fetch_state(lp.nwaves))) return rc;
     const IcpState &st = *sc.h_state.data();
     r.looped = true;
@@ -576,7 +576,7 @@ static int run_one_launch(const IcpCall &c, const AttemptPlan &p, const IcpParam
     if (!st.loop_aborted && st.done) {
         if (c.prof) {
             float a = 0;
-            (void)hipEventElapsedTime(&a, sc.events[1], sc.events[2]);
+            (void)hipEventElapsedTime(&a, sc.events[1].get(), sc.events[2].get());
             r.us_nn = 1e3 * a;
             r.nn_launches = static_cast<uint32_t>(std::max(1, st.iter));   // per iteration
         }
@@ -666,7 +666,7 @@ struct Iterations {
     // one iteration; `slot` indexes its 5 profiling events
     int enqueue(int slot, int iteration) {
         const bool ev = sampled(iteration);
-        if (ev) HIPCHK(hipEventRecord(sc.events[5 * slot + 1], s));
+        if (ev) HIPCHK(hipEventRecord(sc.events[5 * slot + 1].get(), s));
         ip.stripe_work = measures(iteration) ? st_work : nullptr;
         ip.chain_iter = iteration;
         launch_icp(ip, lw, true, s);
@@ -675,7 +675,7 @@ struct Iterations {
             HIPCHK(stripe_order_sort(st_work, st_sorted, st_iota, st_order, stripes, sc.d_sort_temp.data(), sc.d_sort_temp.capacity(), s));
             ip.stripe_order = st_order;
         }
-        if (ev) HIPCHK(hipEventRecord(sc.events[5 * slot + 2], s));
+        if (ev) HIPCHK(hipEventRecord(sc.events[5 * slot + 2].get(), s));
         if (chain) return SAGEICP_OK;                  // (the solving wave is already waiting for this launch's sums)
         launch_fin(fp, s);
         if (c.comm && !c.p2p) {     // k_fin left the local sums in state->sums
@@ -688,13 +688,13 @@ struct Iterations {
             f2.mode = 2;
             launch_fin(f2, s);
         }
-        if (c.prof2) HIPCHK(hipEventRecord(sc.events[5 * slot + 3], s));
+        if (c.prof2) HIPCHK(hipEventRecord(sc.events[5 * slot + 3].get(), s));
         return SAGEICP_OK;
     }
     void harvest(int slot) {
         float a = 0, b = 0;
-        (void)hipEventElapsedTime(&a, sc.events[5 * slot + 1], sc.events[5 * slot + 2]);
-        if (c.prof2) (void)hipEventElapsedTime(&b, sc.events[5 * slot + 2], sc.events[5 * slot + 3]);
+        (void)hipEventElapsedTime(&a, sc.events[5 * slot + 1].get(), sc.events[5 * slot + 2].get());
+        if (c.prof2) (void)hipEventElapsedTime(&b, sc.events[5 * slot + 2].get(), sc.events[5 * slot + 3].get());
         r.us_nn += 1e3 * a; r.us_fin += 1e3 * b;
         ++r.nn_launches;
     }
@@ -740,7 +740,7 @@ struct Iterations {
         // no launch was enqueued at all (the sort refused the frame — a non-finite point — before the host got to
         // iteration 0): nobody will tell the solving wave to start, so it is sent home here, not when this call returns
         if (chain && guard.armed && (rc = guard.send_home_now())) return rc;
-        if (chain) HIPCHK(hipStreamWaitEvent(s, sc.ev_solve, 0));      // the solving wave writes the final state
+        if (chain) HIPCHK(hipStreamWaitEvent(s, sc.ev_solve.get(), 0));      // the solving wave writes the final state
         if ((rc = c.fetch_state(ip.nwaves))) return rc;
         const IcpState &st = *sc.h_state.data();
         if (chain && (st.loop_aborted || !st.done) && !st.bad_input) {
@@ -846,7 +846,7 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
     Scratch &sc = m->sc;
     if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
     int rc;
-    IcpCall c{m, d_frame, n, init, max_dist, kernel, sem_th, comm, sc, sc.stream, false, false, false, false, false, 0, P2pParams{}};
+    IcpCall c{m, d_frame, n, init, max_dist, kernel, sem_th, comm, sc, sc.stream.get(), false, false, false, false, false, 0, P2pParams{}};
     if ((rc = c.constants(stats != nullptr))) return rc;
     if (c.prof && (rc = sc.reserve_events(c.polled ? kMaxIterations : kChunkMax))) return rc;
     Attempt a;
@@ -1018,13 +1018,13 @@ int register_sharded(const sageicp_map *m, const double *h_frame, const Point4 *
             if (cnt) {
                 if (h_frame)
                     HIPCHK(hipMemcpyAsync(sc.d_frame.data(), h_frame + 4 * lo, cnt * sizeof(Point4),
-                                          hipMemcpyHostToDevice, sc.stream));
+                                          hipMemcpyHostToDevice, sc.stream.get()));
                 else if (k == 0)
                     mine = d_frame + lo;
                 else
                     HIPCHK(hipMemcpyPeerAsync(sc.d_frame.data(), mk->device, d_frame + lo, m->device,
-                                              cnt * sizeof(Point4), sc.stream));
-                HIPCHK(hipStreamSynchronize(sc.stream));     // the shard has arrived (or the copy failed: here, not in the loop)
+                                              cnt * sizeof(Point4), sc.stream.get()));
+                HIPCHK(hipStreamSynchronize(sc.stream.get()));     // the shard has arrived (or the copy failed: here, not in the loop)
             }
             return SAGEICP_OK;
         };

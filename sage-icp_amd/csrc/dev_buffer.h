@@ -1,13 +1,26 @@
-// Owners of the host side's device memory (hipMalloc) and pinned host memory (hipHostMalloc): one block each,
-// freed by the destructor, moved but never copied.  The caller decides how much to hold (the growth policies stay
-// at the call sites: capacities reach the kernels); the owner only allocates, keeps a prefix when asked, and frees.
-// Beside them, the owner of a one-call stream.
+// Owners of what the host side holds on a device: device memory (hipMalloc) and pinned host memory (hipHostMalloc), one
+// block each; streams; events.  Each releases what it holds in its destructor, is moved (the source is left empty) but
+// never copied, and does nothing when it holds nothing.  The caller decides how much memory to hold (the growth policies
+// stay at the call sites: capacities reach the kernels) and when a stream or an event is created; the owner only
+// allocates, keeps a prefix when asked, and releases.
+//
+// What a handle that holds several of them (Scratch, Prep, sageicp_map, sageicp_pipeline: capi_internal.h, capi.hip)
+// keeps when it goes:
+//  - its device is made current before anything is released;
+//  - every stream of the handle has been waited for before a buffer that its work may touch is freed and before an
+//    event recorded on it is destroyed: the handle's destructor body waits, then the members go in reverse order of
+//    declaration, whatever that is (a one-call stream has no handle around it: declared after the buffers its work
+//    uses, it goes first);
+//  - the pipeline's worker thread is joined before either Prep goes;
+//  - a handle that never created its stream releases nothing and calls nothing.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
+#include <utility>
 
 namespace sageicp {
 
@@ -93,24 +106,66 @@ using DevBuf = Buffer<T, DeviceMemory>;
 template <typename T, unsigned Flags = hipHostMallocDefault>
 using PinnedBuf = Buffer<T, PinnedMemory<Flags>>;
 
-// The stream of one call, created on the current device: the destructor waits for it, then destroys it.  Declared
-// after the buffers its work uses, it goes first, so no buffer is freed under a copy or a kernel still running.
+// A stream, created on the current device into an empty owner: the destructor waits for it, then destroys it.
 class OwnedStream {
 public:
     OwnedStream() = default;
     OwnedStream(const OwnedStream &) = delete;
     OwnedStream &operator=(const OwnedStream &) = delete;
-    ~OwnedStream() {
+    OwnedStream(OwnedStream &&o) noexcept : s_(std::exchange(o.s_, nullptr)) {}
+    OwnedStream &operator=(OwnedStream &&o) noexcept {
+        if (this != &o) {
+            reset();
+            s_ = std::exchange(o.s_, nullptr);
+        }
+        return *this;
+    }
+    ~OwnedStream() { reset(); }
+
+    hipError_t create() { return hipStreamCreateWithFlags(&s_, hipStreamNonBlocking); }
+    hipError_t create(int priority) { return hipStreamCreateWithPriority(&s_, hipStreamNonBlocking, priority); }
+    // on the CUs of `mask` only (one bit per CU, `words` words)
+    hipError_t create(uint32_t words, const uint32_t *mask) { return hipExtStreamCreateWithCUMask(&s_, words, mask); }
+    hipStream_t get() const { return s_; }
+    explicit operator bool() const { return s_ != nullptr; }
+
+private:
+    void reset() {
         if (!s_) return;
         (void)hipStreamSynchronize(s_);
         (void)hipStreamDestroy(s_);
+        s_ = nullptr;
     }
+    hipStream_t s_ = nullptr;
+};
 
-    hipError_t create() { return hipStreamCreateWithFlags(&s_, hipStreamNonBlocking); }
-    hipStream_t get() const { return s_; }
+// An event, created on the current device into an empty owner, for timing (hipEventDefault) or for ordering only
+// (hipEventDisableTiming): the destructor destroys it.
+class OwnedEvent {
+public:
+    OwnedEvent() = default;
+    OwnedEvent(const OwnedEvent &) = delete;
+    OwnedEvent &operator=(const OwnedEvent &) = delete;
+    OwnedEvent(OwnedEvent &&o) noexcept : e_(std::exchange(o.e_, nullptr)) {}
+    OwnedEvent &operator=(OwnedEvent &&o) noexcept {
+        if (this != &o) {
+            reset();
+            e_ = std::exchange(o.e_, nullptr);
+        }
+        return *this;
+    }
+    ~OwnedEvent() { reset(); }
+
+    hipError_t create(unsigned flags) { return hipEventCreateWithFlags(&e_, flags); }
+    hipEvent_t get() const { return e_; }
+    explicit operator bool() const { return e_ != nullptr; }
 
 private:
-    hipStream_t s_ = nullptr;
+    void reset() {
+        if (e_) (void)hipEventDestroy(e_);
+        e_ = nullptr;
+    }
+    hipEvent_t e_ = nullptr;
 };
 
 }  // namespace sageicp

@@ -366,13 +366,6 @@ int DynFilter::reserve(size_t n, size_t nlabels) {
     return SAGEICP_OK;
 }
 
-void DynFilter::destroy() {
-    for (auto &e : ev)
-        if (e) (void)hipEventDestroy(e);
-    if (ev_table) (void)hipEventDestroy(ev_table);
-    *this = DynFilter();
-}
-
 int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_range, double label_max_range,
                    const DynFilterConfig &cfg, Point4 *tmp, Point4 *out, int *d_ovf, uint64_t &n_out, hipStream_t s) {
     const double t0 = now_us();
@@ -385,7 +378,7 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
     size_t temp_bytes = d_temp.capacity();     // (rocprim takes the size by reference)
     const bool prof = g_profiling != 0;
     if (prof && !ev[0])
-        for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+        for (auto &e : ev) HIPCHK(e.create(hipEventDefault));
     std::vector<uint32_t> lab(cfg.dynamic_labels.begin(), cfg.dynamic_labels.end());
     lab.insert(lab.end(), cfg.landmark_labels.begin(), cfg.landmark_labels.end());
 
@@ -399,7 +392,7 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
     P.ctr = d_ctr.data(); P.ovf = d_ovf;
 
     // ---- classify, compact -------------------------------------------------------------------------------------
-    if (prof) HIPCHK(hipEventRecord(ev[0], s));
+    if (prof) HIPCHK(hipEventRecord(ev[0].get(), s));
     if (!lab.empty()) HIPCHK(hipMemcpyAsync(d_labels.data(), lab.data(), lab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemsetAsync(d_ctr.data(), 0, 4 * sizeof(uint32_t), s));
     hipLaunchKernelGGL(k_dyn_classify, dim3(grid_of(n)), dim3(256), 0, s, P);
@@ -409,7 +402,7 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_ctr.data(), d_ctr.data(), 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(h_ctr.data() + 4, d_ovf, sizeof(int), hipMemcpyDeviceToHost, s));
-    if (prof) HIPCHK(hipEventRecord(ev[1], s));
+    if (prof) HIPCHK(hipEventRecord(ev[1].get(), s));
     HIPCHK(hipStreamSynchronize(s));
     const int ovf1 = static_cast<int>(h_ctr.data()[4]);
     if (ovf1 & 2) return fail(SAGEICP_ERR_INVALID, "a label is not finite (NaN / Inf)");
@@ -422,14 +415,14 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
         info.us_wall = now_us() - t0;
         if (prof) {
             float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            HIPCHK(hipEventElapsedTime(&ms, ev[0].get(), ev[1].get()));
             info.us_device = 1e3 * ms;
         }
         return SAGEICP_OK;
     }
 
     // ---- grids, components, counts, the component table ------------------------------------------------------------
-    if (prof) HIPCHK(hipEventRecord(ev[2], s));
+    if (prof) HIPCHK(hipEventRecord(ev[2].get(), s));
     unsigned long long *vkey_s = d_vkey.data() + cap, *lkey_s = d_lkey.data() + cap;
     uint32_t *vidx = d_vval.data() + cap, *lidx = d_lval.data() + cap;
     HIPCHK(rocprim::radix_sort_pairs(d_temp.data(), temp_bytes, d_vkey.data(), vkey_s, d_vval.data(), vidx, nv, 0, 3 * kCellBits, s));
@@ -449,8 +442,8 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
     HIPCHK(hipMemcpyAsync(h_ctr.data(), d_ctr.data(), 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(h_ctr.data() + 4, d_ovf, sizeof(int), hipMemcpyDeviceToHost, s));
     if (max_rec) HIPCHK(hipMemcpyAsync(h_rec.data(), d_rec.data(), max_rec * sizeof(uint4), hipMemcpyDeviceToHost, s));
-    if (!ev_table) HIPCHK(hipEventCreateWithFlags(&ev_table, hipEventDisableTiming));
-    HIPCHK(hipEventRecord(ev_table, s));
+    if (!ev_table) HIPCHK(ev_table.create(hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ev_table.get(), s));
     // grouping of the points by component runs while the host works on the table
     uint32_t *rkey = d_rkv.data(), *rval = d_rkv.data() + cap;
     unsigned bits = 1;
@@ -458,9 +451,9 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
     HIPCHK(rocprim::radix_sort_pairs(d_temp.data(), temp_bytes, d_root.data(), rkey, d_vval.data(), rval, nv, 0, bits, s));
     hipLaunchKernelGGL(k_dyn_starts, dim3(grid_of(nv)), dim3(256), 0, s, rkey, nv, d_start.data());
     HIPCHK(hipGetLastError());
-    if (prof) HIPCHK(hipEventRecord(ev[3], s));
+    if (prof) HIPCHK(hipEventRecord(ev[3].get(), s));
     const double th0 = now_us();
-    HIPCHK(hipEventSynchronize(ev_table));
+    HIPCHK(hipEventSynchronize(ev_table.get()));
     if (h_ctr.data()[4] & 4) return fail(SAGEICP_ERR_HIP, "dynamic vehicle filter: union-find invariant broken");
     const uint32_t ncl = h_ctr.data()[3];
     if (ncl > max_rec) return fail(SAGEICP_ERR_HIP, "dynamic vehicle filter: inconsistent component table");
@@ -492,12 +485,12 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
 
     // ---- scatter ---------------------------------------------------------------------------------------------------
     if (kept) {
-        if (prof) HIPCHK(hipEventRecord(ev[4], s));
+        if (prof) HIPCHK(hipEventRecord(ev[4].get(), s));
         HIPCHK(hipMemcpyAsync(d_off.data(), h_off.data(), ncl * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_dyn_scatter, dim3(grid_of(nv)), dim3(256), 0, s, rkey, rval, nv, d_start.data(), d_rec_of_root.data(),
                            d_off.data(), d_vframe.data(), tmp, out);
         HIPCHK(hipGetLastError());
-        if (prof) HIPCHK(hipEventRecord(ev[5], s));
+        if (prof) HIPCHK(hipEventRecord(ev[5].get(), s));
     }
     // h_off is read by the copy above: it must not be rewritten by the next frame before the copy ran.  The caller
     // synchronises the stream before its next use of this filter (the down-sampling levels wait for their counts).
@@ -505,9 +498,9 @@ int DynFilter::run(const Point4 *in, uint64_t n, double max_range, double min_ra
     if (prof) {
         HIPCHK(hipStreamSynchronize(s));
         float a = 0, b = 0, c = 0;
-        HIPCHK(hipEventElapsedTime(&a, ev[0], ev[1]));
-        HIPCHK(hipEventElapsedTime(&b, ev[2], ev[3]));
-        if (kept) HIPCHK(hipEventElapsedTime(&c, ev[4], ev[5]));
+        HIPCHK(hipEventElapsedTime(&a, ev[0].get(), ev[1].get()));
+        HIPCHK(hipEventElapsedTime(&b, ev[2].get(), ev[3].get()));
+        if (kept) HIPCHK(hipEventElapsedTime(&c, ev[4].get(), ev[5].get()));
         info.us_device = 1e3 * (static_cast<double>(a) + b + c);
     }
     return SAGEICP_OK;
