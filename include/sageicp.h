@@ -179,6 +179,12 @@ int sageicp_map_resident(const sageicp_map *map);
  * of sparsely filled voxels does not pay max_points_per_voxel slots for each.  SAGEICP_SIZE_CLASSES=0
  * in the environment when the map is created gives every voxel a full-size region instead. */
 uint64_t sageicp_map_point_slots(const sageicp_map *map);
+/* Two read-only entries for tests (host-side words only, no device call; additions, the ABI version stays).
+ * sageicp_voxel_hash: the hash the slot table is keyed by (home slot = hash & (capacity - 1)).
+ * sageicp_map_table_stats: out[0] the capacity of the slot table of whichever copy is the authority, out[1] its used
+ * slots (live + tombstoned: the device-side update leaves tombstones, the host table never does), out[2] its live voxels. */
+uint32_t sageicp_voxel_hash(int32_t x, int32_t y, int32_t z);
+int sageicp_map_table_stats(const sageicp_map *map, uint64_t out[3]);
 /* Push pending host-side changes to the HBM mirror now (otherwise done lazily by the next
  * search).  Lets a caller keep the refresh out of a timed region. */
 int sageicp_map_sync(const sageicp_map *map);

@@ -227,6 +227,8 @@ _SIGNATURES = [
     ("sageicp_map_pointcloud", C.c_uint64, [C.c_void_p, _dp, C.c_uint64]),
     ("sageicp_map_resident", C.c_int, [C.c_void_p]),
     ("sageicp_map_point_slots", C.c_uint64, [C.c_void_p]),
+    ("sageicp_voxel_hash", C.c_uint32, [C.c_int32, C.c_int32, C.c_int32]),
+    ("sageicp_map_table_stats", C.c_int, [C.c_void_p, _u64p]),
     ("sageicp_map_sync", C.c_int, [C.c_void_p]),
     ("sageicp_get_correspondences", C.c_int,
      [C.c_void_p, _dp, C.c_uint64, C.c_double, C.c_double, _dp, _dp, _u64p, _i64p]),
@@ -362,6 +364,11 @@ def _d(a):
 
 def device_count():
     return int(lib().sageicp_device_count())
+
+
+def voxel_hash(x, y, z):
+    """the hash the map's slot table is keyed by (sageicp_voxel_hash; for tests)"""
+    return int(lib().sageicp_voxel_hash(int(x), int(y), int(z)))
 
 
 # ---- frames that are torch tensors on a GPU (sageicp_device_frame) ------------------------------------------------------
@@ -720,6 +727,12 @@ class VoxelHashMap:
     def point_slots(self):
         """32-B point slots the voxel storage occupies (size-classed regions, free ones included)"""
         return int(lib().sageicp_map_point_slots(self._h))
+
+    def table_stats(self):
+        """(capacity, used slots, live voxels) of the slot table of whichever copy is the authority (for tests)"""
+        out = (C.c_uint64 * 3)()
+        _check(lib().sageicp_map_table_stats(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def sync(self):
         _check(lib().sageicp_map_sync(self._h))

@@ -480,6 +480,23 @@ uint64_t sageicp_map_point_slots(const sageicp_map *m) {
     return static_cast<uint64_t>(m->on_device ? m->ctr.units_hi : m->host.units_hi) * kUnitPoints;
 }
 
+// ---- for tests: the slot hash, and the state of the authoritative slot table (host-side words only) ----
+uint32_t sageicp_voxel_hash(int32_t x, int32_t y, int32_t z) { return sageicp::voxel_hash(x, y, z); }
+
+int sageicp_map_table_stats(const sageicp_map *m, uint64_t out[3]) {
+    if (!m || !out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    if (m->on_device) {          // (the counters of the last device pass, kept on the host with the handle)
+        out[0] = m->d_table.capacity();
+        out[1] = m->ctr.used_slots;
+        out[2] = m->ctr.num_voxels;
+    } else {                     // (the host table deletes by backward shift: no tombstones)
+        out[0] = m->host.table.size();
+        out[1] = m->host.num_voxels;
+        out[2] = m->host.num_voxels;
+    }
+    return SAGEICP_OK;
+}
+
 int sageicp_map_sync(const sageicp_map *m) {
     if (!m) return fail(SAGEICP_ERR_INVALID, "null map");
     if (int rc = sync_mirror(m)) return rc;
