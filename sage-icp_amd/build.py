@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["csrc/kernels.hip", "csrc/sort.hip", "csrc/preprocess.hip", "csrc/dyn_filter.hip", "csrc/deskew.hip",
            "csrc/ingest.hip", "csrc/egress.hip", "csrc/keyframe.hip", "csrc/map_update.hip",
            "csrc/capi_mirror.hip", "csrc/capi_run.hip", "csrc/capi.hip"]
-HEADERS = ["csrc/kernels.h", "csrc/dev_buffer.h", "csrc/sageicp_types.h", "csrc/se3_math.h", "csrc/host_map.hpp", "csrc/pipeline.hpp", "csrc/map_update.h", "csrc/egress.h", "csrc/metrics.hpp", "csrc/robin_order.hpp", "csrc/capi_internal.h", "csrc/dyn_rules.h", "csrc/probes.h", "csrc/icp_body.h",
+HEADERS = ["csrc/kernels.h", "csrc/dev_buffer.h", "csrc/sageicp_types.h", "csrc/se3_math.h", "csrc/host_map.hpp", "csrc/pipeline.hpp", "csrc/map_update.h", "csrc/egress.h", "csrc/metrics.hpp", "csrc/robin_order.hpp", "csrc/capi_internal.h", "csrc/dyn_rules.h", "csrc/probes.h", "csrc/icp_body.h", "csrc/fin_kernel.h", "csrc/loop_kernel.h",
            "../include/sageicp.h"]
 OUT = os.path.join(HERE, "libsageicp_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
@@ -96,7 +96,7 @@ PROBE_DEFINES = ("SAGE_NN_TIMING", "SAGE_LOOP_TIMING", "SAGE_GN_TIMING", "SAGE_I
 
 
 def compile_probe_variants(jobs=None):
-    """Smoke target: the device code of kernels.hip with each probe switch (csrc/probes.h and the stamps beside the loops),
+    """Smoke target: the device code of kernels.hip with each probe switch (csrc/probes.h),
     compiled and thrown away — so that the instrumented builds profiles/ relies on do not rot.  Returns {define: stderr}
     of the variants that failed (empty: all fine)."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

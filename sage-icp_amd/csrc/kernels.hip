@@ -1,8 +1,14 @@
 // Hand-written HIP kernels for gfx950 (CDNA4, wave64) — SAGE-ICP registration hot path.
 // One ICP iteration = k_icp -> k_fin, both on one stream, no host round trip.
 //
-// This file holds the kernels, their helpers and the launchers; the search body that k_icp and k_loop share
-// (icp_body: everything between a wave's queries and their sums) lives in icp_body.h, included below.
+// One translation unit in five files.  This one holds the lane helpers, the small kernels (k_derive_cand, k_rows, k_gn,
+// k_tf, the scatter kernels), the fixed-point sums, what the search body and the one-launch loop share (LoopGroup, the
+// LDS header words, LoopLds — the one description of a k_loop workgroup's LDS —, chain_wait_pose), k_icp and every
+// launcher.  Included below, by this file only:
+//   icp_body.h     the search body k_icp and k_loop share (icp_body: everything between a wave's queries and their sums)
+//   fin_kernel.h   the launch-per-iteration finish: WaveLanes, the reductions, solve_and_publish, exchange_sums, k_fin
+//   loop_kernel.h  the one-launch loop: the solving wave (loop_finish_iteration, k_loop_solve) and k_loop with its phases
+//   probes.h       the instrumentation of the probe builds (included first; empty in the product)
 //
 //   k_icp    VoxelHashMap::GetCorrespondences (core/VoxelHashMap.cpp:48-130) and the accumulation
 //            of AlignClouds (core/Registration.cpp:59-90) in ONE launch.  W = 1..16 lanes own a
@@ -17,11 +23,12 @@
 //            lexicographic (distance, enumeration order) argmin = the reference's sequential
 //            strict-< scan, index for index.  Fused epilogue: acceptance test on the unscaled
 //            distance (VoxelHashMap.cpp:111), robust weight and the 16 closed-form fp64 sums of
-//            JtJ / Jtr per accepted pair, reduced in a fixed order to one partial per workgroup.
+//            JtJ / Jtr per accepted pair, added as exact fixed-point digits into shared accumulators (below).
 //   k_rows   builds every query's neighbourhood row after a (re-)sort of the frame (27 lanes probe
 //            the GPU-resident open-addressed hash per query).
-//   k_fin    one workgroup: fixed-order reduction of the partials (bit-reproducible), [exchange of
-//            the sums with the peer GPUs,] 6x6 LDL^T solve and SE3 exp with their divisions /
+//   k_fin    one workgroup: exact sum of the accumulators' copies (integers: bit-reproducible; the
+//            fixed-order reduction of fp64 partials remains for k_gn's), [exchange of the sums
+//            with the peer GPUs,] 6x6 LDL^T solve and SE3 exp with their divisions /
 //            sincos spread over lanes, pose composition and the convergence test
 //            (Registration.cpp:92-93,135-137).
 //   k_gn     the accumulation alone on explicit pairs (the stand-alone AlignClouds entry).
@@ -361,7 +368,8 @@ __host__ __device__ constexpr unsigned icp_wave_words(int lw) {
 // to_digits: v = a + b 2^-40 + c 2^-80 exactly (three integers of at most 40 bits and a sign, each exactly
 // representable), each as int64 through the 2^52 + 2^51 trick (both numbers lie in [2^52, 2^53): their
 // bit patterns differ by exactly the integer).  `ok` is cleared when |a| leaves the range the accumulators
-// have room for: the overflow flag then sends the frame through the fp64 partials (capi.hip).
+// have room for: the overflow flag (IcpState::acc_overflow) makes the host register the frame again with the sums scaled
+// down (capi_run.hip, acc_shift), and report it when that is not enough.
 __device__ __forceinline__ void to_digits(double v, double limit, long long &d0, long long &d1, long long &d2, bool &ok) {
     const double a = __builtin_rint(v);
     const double r1 = (v - a) * 1099511627776.0;             // 2^40, exact
@@ -500,28 +508,40 @@ struct LoopGroup {
     unsigned long long *wgacc; // LDS: the workgroup's fixed-point accumulators (wave_terms_to_wgacc)
     unsigned q_first;          // the workgroup's first query (slot 0; a multiple of four)
     unsigned slot;             // this pass's slot in the per-wave counters (IcpParams::counters)
-#ifdef SAGE_LOOP_TIMING
-    unsigned long long ph[8], tprev;           // probe builds: cycles per phase of the body, summed over the iterations
-#endif
+    PROBE_LOOP_GROUP_FIELDS    // probe builds: cycles per phase of the body in this pass (probes.h); nothing in the product
 };
 constexpr int kLoopMaxWaves = kLoopMaxWavesHost;   // waves per workgroup of k_loop (<= 512 threads)
 constexpr unsigned kLoopStripe = kLoopStripeHost;  // workgroups of k_loop per XCD stripe (its grid: a multiple of 32)
 constexpr int kNoVoxel = 0x7FFFFFFF;        // a home voxel no point has (|index| < 2^20): row not built yet
 constexpr unsigned kStPrev = 16, kStKey = 18;
-// LDS of a k_loop workgroup (words): header { arrival counter | next group | the pose of this iteration
-// (R[9], t[3]) | done | the workgroup's fixed-point accumulators } | the groups { rows, state } |
-// one scratch for the transposed block sums per wave
+// LDS of a k_loop workgroup (words).  Its header: arrival counter | next unit | done | the pose of this iteration
+// (R[9], t[3]) | the probe builds' counts | the waves' first units | the workgroup's fixed-point accumulators; what
+// follows the header is laid out by LoopLds below.
 constexpr unsigned kLpArrive = 0, kLpNext = 1, kLpDone = 2;
 constexpr unsigned kLpPose = 4;                                    // 12 doubles, 16-B aligned
 constexpr unsigned kLpDbg = kLpPose + 24u;                         // probe builds: max points of a query | stale queries | points
 constexpr unsigned kLpFirst = kLpDbg + 4u;                         // per wave: the unit it takes first in every iteration (LoopParams::deal)
 constexpr unsigned kLpAcc = kLpFirst + 8u;                         // kWgAccWords 64-bit words
 constexpr unsigned kLpHeaderWords = (kLpAcc + 2u * kWgAccWords + 15u) & ~15u;
-__host__ __device__ constexpr unsigned loop_group_words(int lw) {
-    return static_cast<unsigned>((kRowLdsStride + kLoopStateWords) * (64 >> lw));
-}
 __host__ __device__ constexpr unsigned loop_red_words() { return 2u * kCount * 4u; }    // 16 fp64 for each of four blocks of queries
 __host__ __device__ constexpr unsigned loop_perm_words(unsigned nblk) { return 2u * ((nblk + 7u) & ~7u); }   // perm | work, 32-B aligned
+// THE layout of that LDS, as word offsets from its start, for 2^lw lanes per query, nw waves and gpw units of
+// 64 >> lw queries per workgroup:
+//   header | perm[blocks] | work[blocks] | rows of the workgroup's queries | their state records | nw x scratch
+// (blocks = gpw x (64 >> lw) / 4, rounded up to eight).  k_loop takes its pointers from it and the host the size it asks
+// for (`end`): there is no second spelling.  (W: unsigned in the kernel; size_t on the host, where a gpw from the
+// environment must not wrap.)
+template <typename W>
+struct LoopLds {
+    W perm, work, rows, state, red, end;       // red: wave 0's scratch, wave w's at red + w loop_red_words()
+    __host__ __device__ constexpr LoopLds(int lw, W nw, W gpw)
+        : perm(kLpHeaderWords),
+          work(perm + loop_perm_words(static_cast<unsigned>(gpw) * ((64u >> lw) / 4u)) / 2u),
+          rows(perm + loop_perm_words(static_cast<unsigned>(gpw) * ((64u >> lw) / 4u))),
+          state(rows + gpw * static_cast<W>(64 >> lw) * static_cast<W>(kRowLdsStride)),
+          red(state + gpw * static_cast<W>(64 >> lw) * static_cast<W>(kLoopStateWords)),
+          end(red + nw * loop_red_words()) {}
+};
 
 // Chained launches (IcpParams::chain): wave 0 of a workgroup of the launch of iteration `it` waits for the pose the solving
 // wave publishes after iteration it - 1 (25 self-tagged granules, tag = it; kernels.h, LoopShared) and hands it to the
@@ -593,1056 +613,13 @@ void k_icp(IcpParams P) {
     PROBE_DELAY_REPEAT(P, (icp_body<LW, FUSED, FILT, false, FLATQ>(P, smem)));
 }
 
-// ------------------------------------------------------------------------------------ WaveLanes
-// Lane policy (se3_math.h) for the wave that finishes an iteration: its 64 lanes all hold the
-// same (uniform) values, so independent fp64 divisions / sincos arguments are moved to separate
-// lanes, evaluated by ONE vector instruction sequence, and read back with v_readlane.  A serial
-// lane spent ~2 us of every iteration in the 21 divisions of the 6x6 LDL^T alone.
-// Must be called with lanes 0..5 active and uniform operands.
-struct WaveLanes {
-    static __device__ __forceinline__ void divide6(const double (&n)[6], const double (&d)[6],
-                                                   double (&q)[6]) {
-        const int lane = static_cast<int>(threadIdx.x & 63u);
-        double nn = n[0], dd = d[0];
-#pragma unroll
-        for (int i = 1; i < 6; ++i) {
-            nn = (lane == i) ? n[i] : nn;
-            dd = (lane == i) ? d[i] : dd;
-        }
-        const double qq = nn / dd;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) q[i] = readlane_f64(qq, i);
-    }
-    static __device__ __forceinline__ void sincos2(double a0, double a1, double &s0, double &c0,
-                                                   double &s1, double &c1) {
-        const int lane = static_cast<int>(threadIdx.x & 63u);
-        double sv, cv;
-        sincos(lane == 1 ? a1 : a0, &sv, &cv);
-        s0 = readlane_f64(sv, 0); c0 = readlane_f64(cv, 0);
-        s1 = readlane_f64(sv, 1); c1 = readlane_f64(cv, 1);
-    }
-    static __device__ __forceinline__ void sqrt2(double a0, double a1, double &r0, double &r1) {
-        const int lane = static_cast<int>(threadIdx.x & 63u);
-        const double v = sqrt(lane == 1 ? a1 : a0);
-        r0 = readlane_f64(v, 0);
-        r1 = readlane_f64(v, 1);
-    }
-    // (the operands are uniform, so is b: taken as the wave's, a scalar branch)
-    static __device__ __forceinline__ bool uniform(bool b) { return __all(b); }
-};
+}  // namespace sageicp
 
-// ------------------------------------------------------------------------------ finish_iteration
-// Executed by ONE workgroup of 1024 threads once per ICP iteration (k_fin): fixed-order reduction
-// of the workgroup partials of k_icp (bit-reproducible), then the first wave solves the normal
-// equations from the 16 closed-form sums (se3_math.h solve_normal_equations_t: the block-structured
-// solve, the register-resident pivoted 6x6 LDL^T where its guard refuses), applies SE3 exp, composes
-// the pose and tests convergence (Registration.cpp:92-93,135-137).
-#ifdef SAGE_GN_TIMING
-__device__ unsigned long long g_gn_phase[16];
-#define FIN_STAMP(i) do { if (threadIdx.x == 0) fin_t[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define FIN_STAMP(i) do { } while (0)
-#endif
+// the launch-per-iteration finish (k_fin) and the one-launch loop (k_loop, k_loop_solve)
+#include "fin_kernel.h"
+#include "loop_kernel.h"
 
-constexpr int kFinThreads = 1024;
-constexpr int kFinSlices = 102;             // 10 fp64 pairs per partial x 102 slices = 1020 threads
-
-// Returns false (on every thread) when *done is set: the loop has finished and this launch is a
-// no-op.  The flag is fetched together with the partials — one memory round trip, not two.
-__device__ __forceinline__ bool reduce_partials(const double *partials, int nparts, double *S /* LDS [kNumSums] */,
-                                                const int32_t *done) {
-    __shared__ double part[kFinSlices][kNumSums];
-    __shared__ double part2[6][kNumSums];
-    const int t = static_cast<int>(threadIdx.x);
-    const int pr = t % 10, sl = t / 10;
-    if (sl < kFinSlices) {
-        // fixed summation order; the loads are independent: up to 24 in flight per thread (one
-        // memory round trip for up to 2,448 partials, the cold-L2 latency is what this kernel costs)
-        double2 v = make_double2(0.0, 0.0);
-        const double2 *src = reinterpret_cast<const double2 *>(partials) + pr;
-        bool first = true;
-        for (int b = sl; b < nparts; b += 24 * kFinSlices) {
-            double2 u[24];
-#pragma unroll
-            for (int k = 0; k < 24; ++k) {
-                const int bb = b + k * kFinSlices;
-                u[k] = bb < nparts ? src[static_cast<size_t>(bb) * 10] : make_double2(0.0, 0.0);
-            }
-            if (first && done) {
-                // a vector load like the ones above (the index is zero, but formally per lane), so
-                // that it travels with them: a scalar load would be waited for before the partials
-                // are even requested
-                const int32_t d = done[__builtin_amdgcn_mbcnt_lo(0u, 0u)];
-                if (__builtin_amdgcn_readfirstlane(d)) return false;
-                first = false;
-            }
-#pragma unroll
-            for (int k = 0; k < 24; ++k) { v.x += u[k].x; v.y += u[k].y; }
-        }
-        if (first && done) {                   // no partials at all (an empty frame)
-            const int32_t d = done[__builtin_amdgcn_mbcnt_lo(0u, 0u)];
-            if (__builtin_amdgcn_readfirstlane(d)) return false;
-        }
-        part[sl][2 * pr] = v.x;
-        part[sl][2 * pr + 1] = v.y;
-    } else if (done) {
-        const int32_t d = done[__builtin_amdgcn_mbcnt_lo(0u, 0u)];
-        if (__builtin_amdgcn_readfirstlane(d)) return false;
-    }
-    __syncthreads();
-    if (t < 6 * kNumSums) {
-        const int c = t % kNumSums, g = t / kNumSums;
-        double v = 0.0;
-#pragma unroll
-        for (int k = 0; k < kFinSlices / 6; ++k) v += part[g * (kFinSlices / 6) + k][c];
-        part2[g][c] = v;
-    }
-    __syncthreads();
-    if (t < kNumSums) {
-        double v = part2[0][t];
-#pragma unroll
-        for (int g = 1; g < 6; ++g) v += part2[g][t];
-        S[t] = v;
-    }
-    __syncthreads();
-    return true;
-}
-
-// The sums from the fixed-point accumulators k_icp's workgroups added into (kernels.h): one round
-// trip for 16 KB, the replicas added exactly (integers), three digits -> one fp64 per sum, and the
-// accumulators cleared for the next iteration.  Returns false when *done is set (see above).
-__device__ __forceinline__ bool reduce_accumulators(long long *acc, double *S /* LDS [kNumSums] */,
-                                                    const int32_t *done, int32_t *overflow, double unscale) {
-    __shared__ long long part[kAccReplicas][kAccWords];
-    __shared__ long long part2[8][kAccWords];
-    const int t = static_cast<int>(threadIdx.x);
-    // 2,048 words over 1,024 threads: 16 B each, one coalesced round trip
-    typedef long long ll2 __attribute__((ext_vector_type(2)));
-    ll2 *src = reinterpret_cast<ll2 *>(acc);
-    const ll2 v = src[t];
-    if (done) {
-        const int32_t d = done[__builtin_amdgcn_mbcnt_lo(0u, 0u)];      // travels with the load above
-        if (__builtin_amdgcn_readfirstlane(d)) return false;
-    }
-    ll2 z;
-    z.x = 0; z.y = 0;
-    src[t] = z;                                                          // cleared for the next launch of k_icp
-    reinterpret_cast<ll2 *>(&part[0][0])[t] = v;
-    __syncthreads();
-    if (t < 8 * kAccWords) {
-        const int w = t % kAccWords, g = t / kAccWords;
-        long long s = 0;
-#pragma unroll
-        for (int k = 0; k < kAccReplicas / 8; ++k) s += part[g * (kAccReplicas / 8) + k][w];
-        part2[g][w] = s;
-    }
-    __syncthreads();
-    if (t < kAccWords) {
-        long long s = 0;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) s += part2[g][t];
-        part[0][t] = s;
-    }
-    __syncthreads();
-    if (t < kNumSums) {
-        double r = 0.0;
-        if (t < kAccValues) {
-            const double a = static_cast<double>(part[0][3 * t]);
-            const double b = static_cast<double>(part[0][3 * t + 1]);
-            const double c = static_cast<double>(part[0][3 * t + 2]);
-            r = a + (b * 9.094947017729282e-13 + c * 8.271806125530277e-25);      // 2^-40, 2^-80
-            if (t < kCount) r *= unscale;      // (a power of two; the pair count is not scaled)
-        }
-        S[t] = r;
-        if (t == 0 && part[0][kAccWords - 1] != 0) *overflow = 1;
-    }
-    __syncthreads();
-    return true;
-}
-
-// the solve: wave 0, all 64 lanes, uniform data (see WaveLanes); lane 0 / lane 1 publish the state
-// The loop state the finish needs (the two poses the estimate is composed with, the iteration
-// count), requested by the first wave BEFORE the reduction so that its cold round trip (~0.7 us)
-// runs under it instead of after the solve.
-struct FinState {
-    double rhs[7];            // lane 1: T_icp, the other lanes: T
-    int iter;
-};
-__device__ __forceinline__ FinState prefetch_state(const IcpState *st) {
-    FinState f;
-    const int lane = static_cast<int>(threadIdx.x);
-    const double *src = (lane == 1) ? st->T_icp : st->T;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) f.rhs[i] = src[i];
-    f.iter = st->iter;
-    return f;
-}
-
-__device__ __forceinline__ void solve_and_publish(IcpState *st, const double *S, const FinState &pre) {
-#ifdef SAGE_GN_TIMING
-    unsigned long long fin_t[8];
-#endif
-    FIN_STAMP(1);
-    const int lane = static_cast<int>(threadIdx.x);
-    double x[6], est[7], nrm;
-    solve_normal_equations_t<WaveLanes>(S, x);
-    FIN_STAMP(2);
-    se3_exp_sqrt_t<WaveLanes>(x, est, SAGE_SQNORM6(x), nrm);        // nrm = |x|, beside the exponential's sqrt
-    FIN_STAMP(3);
-
-    // the two compositions (Registration.cpp:135 and the cumulative pose) on lanes 0 and 1
-    double Tn[7];
-    se3_mul(est, pre.rhs, Tn);
-    if (lane < 2) {
-        double *dst = (lane == 1) ? st->T_icp : st->T;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) dst[i] = Tn[i];
-    }
-    if (lane != 0) return;
-    quat_to_mat(Tn, st->R);
-
-    // ||log(exp(x))|| == ||x|| on the principal branch up to a few ulps, so the reference's
-    // estimation.log().norm() (Registration.cpp:137) is taken from x without the atan2 / sincos
-    // round trip on one serial lane — except where those ulps could matter: a step within 1e-12
-    // (relative 1e-8; the two differ by ~1e-19 there) of the stop threshold, or |omega| >= 3,
-    // goes through the exact log so that the stop iteration is the reference's in every case.
-    if (!(x[3] * x[3] + x[4] * x[4] + x[5] * x[5] < 9.0) ||
-        fabs(nrm - kEstimationThreshold) < 1e-12) {
-        double lg[6];
-        se3_log(est, lg);
-        nrm = sqrt(SAGE_SQNORM6(lg));          // the reduction order of a 6-vector's norm(): sageicp_types.h
-    }
-    st->last_step_norm = nrm;
-    const int it = pre.iter;
-    if (it < kHistory) st->n_corr[it] = static_cast<uint32_t>(S[kCount]);
-    st->iter = it + 1;
-    unsigned long long done = 0;
-    if (nrm < kEstimationThreshold) {
-        st->converged = 1;
-        st->done = 1;
-        done = 1;
-    } else if (it + 1 >= kMaxIterations) {
-        st->done = 1;
-        done = 1;
-    }
-    if (st->done) done = 1;                    // e.g. stopped by a failed multi-GPU exchange
-    if (IcpProgress *pg = st->progress) {
-        // host-mapped, a relaxed system-scope (write-through) store: the host only steers its
-        // look-ahead by this word and reads the final state through an ordinary copy after the loop
-        const unsigned long long seq = static_cast<unsigned long long>(it + 1);
-        __hip_atomic_store(&pg->word, (done << 32) | seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-#ifdef SAGE_GN_TIMING
-    fin_t[4] = __builtin_amdgcn_s_memrealtime();
-    for (int i = 1; i < 4; ++i) atomicAdd(&g_gn_phase[8 + i], fin_t[i + 1] - fin_t[i]);
-    atomicAdd(&g_gn_phase[4], 1ull);
-#endif
-}
-
-// --------------------------------------------------------------------------------- exchange_sums
-// One workgroup per rank (the last arriver of k_gn), see P2pBlock.  st->sums holds this rank's
-// sums on entry and the sums over all ranks on exit.  Stores to the peers are system-scope
-// write-through atomics, completed (s_waitcnt) and fenced before the tag goes out; the tags are
-// polled with system-scope loads and an acquire fence precedes the reads of the rows.
-__device__ __forceinline__ void exchange_sums(IcpState *st, const P2pParams &X) {
-    const int t = static_cast<int>(threadIdx.x);
-    const unsigned long long g = *X.exchanges;
-    const int slot = static_cast<int>(g & 1ull);
-    const unsigned long long tag = g + 1ull;
-    if (t < kNumSums) {
-        const double v = st->sums[t];
-        for (int r = 0; r < X.nranks; ++r)
-            __hip_atomic_store(&X.block[r]->sums[slot][X.rank][t], v, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (t == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-        for (int r = 0; r < X.nranks; ++r)
-            __hip_atomic_store(&X.block[r]->flag[X.rank], tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    P2pBlock *mine = X.block[X.rank];
-    __shared__ int s_late;
-    if (t == 0) s_late = 0;
-    __syncthreads();
-    if (t < X.nranks) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (__hip_atomic_load(&mine->flag[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < tag) {
-            __builtin_amdgcn_s_sleep(4);
-            if (__builtin_amdgcn_s_memrealtime() - t0 > X.timeout_ticks) {
-                s_late = 1;
-                break;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-        // a peer gave up its one-launch loop at this exchange (P2pBlock::abort_tag)
-        if (__hip_atomic_load(&mine->abort_tag[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == tag) s_late = 2;
-    }
-    __syncthreads();
-    if (t == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    __syncthreads();
-    if (t < kNumSums) {
-        double s = 0.0;
-        for (int r = 0; r < X.nranks; ++r)       // rank order: the same sum on every rank
-            s += __hip_atomic_load(&mine->sums[slot][r][t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        st->sums[t] = s;
-    }
-    if (t == 0) {
-        *X.exchanges = tag;
-        if (s_late == 2) {                     // every rank leaves this exchange and starts the frame again (run_icp)
-            st->peer_aborted = 1;
-            st->done = 1;
-        } else if (s_late) {                   // stop the loop; the host reports the failure
-            st->exchange_failed = 1;
-            st->done = 1;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------ k_fin
-__global__ __launch_bounds__(kFinThreads) void k_fin(FinParams P) {
-    __shared__ double S[kNumSums];
-    IcpState *st = P.st;
-    if (P.mode == 2 && !P.standalone && st->done) return;
-#ifdef SAGE_GN_TIMING
-    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-#endif
-    FinState pre{};
-    if (threadIdx.x < 64) pre = prefetch_state(st);
-    if (P.mode != 2) {
-        if (P.acc) {
-            if (!reduce_accumulators(P.acc, S, P.standalone ? nullptr : &st->done, &st->acc_overflow, P.acc_unscale)) return;
-        } else if (!reduce_partials(P.partials, P.nparts, S, P.standalone ? nullptr : &st->done)) return;
-#ifdef SAGE_GN_TIMING
-        if (threadIdx.x == 0) atomicAdd(&g_gn_phase[8], __builtin_amdgcn_s_memrealtime() - t_start);
-#endif
-        if (threadIdx.x < kNumSums) st->sums[threadIdx.x] = S[threadIdx.x];
-        if (P.mode == 1) return;
-        if (P.mode == 3) {
-            __syncthreads();
-            exchange_sums(st, P.p2p);
-            __syncthreads();
-            if (threadIdx.x < kNumSums) S[threadIdx.x] = st->sums[threadIdx.x];
-            __syncthreads();
-        }
-    } else {
-        if (threadIdx.x < kNumSums) S[threadIdx.x] = st->sums[threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x >= 64) return;
-    solve_and_publish(st, S, pre);
-}
-
-// ------------------------------------------------------------------------------------ k_loop
-// The whole loop of Registration.cpp:127-138 in one launch of the query workgroups (k_loop) beside a
-// one-wave solving kernel (k_loop_solve) on a second stream (kernels.h, LoopShared).  Per iteration:
-//   every wave        takes the workgroup's groups one after another from an LDS counter and runs
-//                     icp_body<PERSIST> on each — pose from LDS, per-query state and rows in LDS —,
-//                     which parks the group's sums in the workgroup's LDS;
-//   last wave of a    adds the workgroup's sums into the fixed-point accumulators: (digit << 8) + 1 per
-//   workgroup         word, fire and forget — the low byte of every word counts who is in it;
-//   the solving       reads this iteration's set of accumulators until every word counts all its
-//   wave              workgroups (two sets alternate; the one just read is cleared for the iteration
-//                     after the next), [exchanges the sums with the peer GPUs,] solves, composes, tests,
-//                     and publishes the next pose as 25 self-tagged 8-byte granules (tag = iteration
-//                     + 1: the data is the flag, no fence on either side), one copy per XCD;
-//   wave 0 of every   polls its XCD's granules (one relaxed agent-scope load per lane and pass), hands the
-//   workgroup         pose to its workgroup through LDS;  __syncthreads();  next iteration.
-// Every word the workgroups share is accessed with agent-scope atomics only.  Every wait is bounded:
-// a timeout raises LoopShared::abort_word and IcpState::loop_aborted, everybody leaves, and the host
-// registers the frame through the launch-per-iteration loop instead (a grid that is not fully
-// resident — another process or stream holding CUs — ends this way, not in a hang).
-#ifdef SAGE_LOOP_TIMING
-// probe builds: 100-MHz stamps of the first kLoopTimedIters iterations — per workgroup when it counted
-// itself in and when it had the next pose; for the solving wave when all counts were in, the sums
-// read, the step solved, the pose published
-constexpr int kLoopTimedIters = 32, kLoopTimedWgs = 2048;
-__device__ unsigned long long g_loop_wg[kLoopTimedIters][kLoopTimedWgs][4];     // counted in | pose held | a wave took a unit beyond one per wave | ... finished it
-__device__ unsigned g_loop_wginfo[kLoopTimedIters][kLoopTimedWgs][4];     // HW_ID | max points of a query | stale queries | points
-__device__ unsigned long long g_loop_solver[kLoopTimedIters][4];
-__device__ unsigned long long g_loop_solver2[kLoopTimedIters][4];      // inside the solve: after the solve | the exponential (and the sqrt of the step norm) | the composition | the norm test
-__device__ unsigned long long g_loop_wave[kLoopTimedIters][kLoopTimedWgs][8][2];      // per wave: its FIRST unit of the iteration: end stamp | start stamp (low 32) << 32 ... see LOOP_STAMP_WAVE
-__device__ unsigned long long g_loop_phase[16];     // [0..7] cycles per body phase, [8] wait for the pose, [9] closing a workgroup, [10] group passes
-#define LOOP_STAMP_SOLVER(it, k) do { if ((it) < kLoopTimedIters && (threadIdx.x & 63u) == 0u) g_loop_solver[it][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define LOOP_STAMP_SOLVER2(it, k) do { if ((it) < kLoopTimedIters && (threadIdx.x & 63u) == 0u) g_loop_solver2[it][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-extern "C" void sageicp_debug_loop_solver2(unsigned long long *out) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_loop_solver2), sizeof(unsigned long long) * kLoopTimedIters * 4);
-}
-#define LOOP_STAMP_WG(it, k) do { if ((it) < kLoopTimedIters && blockIdx.x < kLoopTimedWgs && (threadIdx.x & 63u) == 0u) g_loop_wg[it][blockIdx.x][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
-extern "C" void sageicp_debug_loop_phases(unsigned long long *out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_loop_phase), sizeof(unsigned long long) * 16);
-    if (reset) {
-        unsigned long long z[16] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_loop_phase), z, sizeof(z));
-    }
-}
-extern "C" void sageicp_debug_loop_waves(unsigned long long *out) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_loop_wave), sizeof(unsigned long long) * kLoopTimedIters * kLoopTimedWgs * 8 * 2);
-}
-extern "C" void sageicp_debug_loop_info(unsigned *info) {
-    (void)hipMemcpyFromSymbol(info, HIP_SYMBOL(g_loop_wginfo), sizeof(unsigned) * kLoopTimedIters * kLoopTimedWgs * 4);
-}
-extern "C" void sageicp_debug_loop_times(unsigned long long *wg, unsigned long long *solver) {
-    (void)hipMemcpyFromSymbol(wg, HIP_SYMBOL(g_loop_wg), sizeof(unsigned long long) * kLoopTimedIters * kLoopTimedWgs * 4);
-    (void)hipMemcpyFromSymbol(solver, HIP_SYMBOL(g_loop_solver), sizeof(unsigned long long) * kLoopTimedIters * 4);
-}
-#else
-#define LOOP_STAMP_SOLVER(it, k) do { } while (0)
-#define LOOP_STAMP_SOLVER2(it, k) do { } while (0)
-#define LOOP_STAMP_WG(it, k) do { } while (0)
-#endif
-
-
-// exchange_sums for ONE wave (the solving wave of k_loop_solve): S (LDS) holds this rank's sums on entry
-// and the sums over all ranks, added in rank order, on exit; `g` is the exchange counter (the same on
-// every rank).  Returns 0, 1 when a peer's sums did not arrive in time, 2 when a peer gave up its one-launch loop at
-// this exchange (P2pBlock::abort_tag).
-__device__ __forceinline__ int exchange_sums_wave(double *S, const P2pParams &X, unsigned long long g) {
-    const int lane = static_cast<int>(threadIdx.x & 63u);
-    const int slot = static_cast<int>(g & 1ull);
-    const unsigned long long tag = g + 1ull;
-    if (lane < kNumSums) {
-        const double v = S[lane];
-        for (int r = 0; r < X.nranks; ++r)
-            __hip_atomic_store(&X.block[r]->sums[slot][X.rank][lane], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0)
-        for (int r = 0; r < X.nranks; ++r)
-            __hip_atomic_store(&X.block[r]->flag[X.rank], tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    P2pBlock *mine = X.block[X.rank];
-    bool late = false, gone = false;
-    if (lane < X.nranks) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (__hip_atomic_load(&mine->flag[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < tag) {
-            __builtin_amdgcn_s_sleep(2);
-            if (__builtin_amdgcn_s_memrealtime() - t0 > X.timeout_ticks) {
-                late = true;
-                break;
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-        gone = __hip_atomic_load(&mine->abort_tag[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == tag;
-    }
-    late = __any(late);
-    gone = __any(gone);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    if (lane < kNumSums) {
-        double s = 0.0;
-        for (int r = 0; r < X.nranks; ++r)       // rank order: the same sum on every rank
-            s += __hip_atomic_load(&mine->sums[slot][r][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        S[lane] = s;
-    }
-    __builtin_amdgcn_wave_barrier();
-    return gone ? 2 : (late ? 1 : 0);
-}
-// This rank leaves its one-launch loop at exchange `g` (a wait inside the launch timed out): the peers are told through
-// the flag of that exchange, so that everybody leaves it together.
-__device__ __forceinline__ void exchange_abort_wave(const P2pParams &X, unsigned long long g) {
-    const int lane = static_cast<int>(threadIdx.x & 63u);
-    if (lane == 0)
-        for (int r = 0; r < X.nranks; ++r)
-            __hip_atomic_store(&X.block[r]->abort_tag[X.rank], g + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0)          // ... and the flag of the exchange, so that nobody waits for this rank's sums
-        for (int r = 0; r < X.nranks; ++r)
-            __hip_atomic_store(&X.block[r]->flag[X.rank], g + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// One iteration's finish by the solving wave (all 64 lanes, uniform data).  Returns the value of the
-// done granule it published: 0 go on, 1 finished, 2 aborted.
-struct SolveLds {
-    double T[14];              // T[7] | T_icp[7]
-    double S[kNumSums];
-};
-// 64 bits of lane `src` (wave-uniform), on every lane
-__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int src) {
-    const unsigned lo = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<unsigned>(v)), src));
-    const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<unsigned>(v >> 32)), src));
-    return (static_cast<unsigned long long>(hi) << 32) | lo;
-}
-// The lane index, derived anew: what the compiler can trace to threadIdx it knows to be the same in every iteration
-// of the solving wave's loop, and it would keep every select mask and address made from it alive across the solve.
-__device__ __forceinline__ int lane_now() {
-    unsigned l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return static_cast<int>(l);
-}
-template <int COPIES>
-__device__ __forceinline__ unsigned loop_finish_iteration(const LoopParams &L, const P2pParams &X, SolveLds &m, int it,
-                                                          unsigned long long &xg) {
-    LoopShared *sh = L.sh;
-    IcpState *st = L.st;
-    const int lane = static_cast<int>(threadIdx.x & 63u);          // (one wave)
-    double *sT = m.T, *S = m.S;
-    const unsigned long long tag = static_cast<unsigned long long>(it) + 1ull;
-
-    double sum = 0.0;          // lane l < kAccValues: value l of this iteration's sums
-    bool overflow;
-    // 1. the sums of this iteration's set of accumulators: read (one round trip per pass) until every word
-    // says that all the workgroups adding into it are in (its low byte counts them, wgacc_flush) —
-    // the read that finds them complete IS the read of the sums.  The set is then cleared for the
-    // iteration after the next (the clears are complete long before that pose is published: the waits
-    // of the next iteration's passes cover them).
-    {
-        const long long per = static_cast<long long>(L.wgs / COPIES);      // workgroups adding into each copy
-        long long (*acc)[kAccWords] = COPIES == kLoopReplicas ? sh->acc[it & 1] : sh->acc32[it & 1];
-        long long v[COPIES];
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        for (;;) {
-#pragma unroll
-            for (int r = 0; r < COPIES; ++r)
-                v[r] = __hip_atomic_load(&acc[r][lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            bool ok = true;
-            if (lane <= 3 * kAccValues) {          // (word 3 kAccValues: the overflow count, counted like the sums)
-#pragma unroll
-                for (int r = 0; r < COPIES; ++r) ok &= (v[r] & 255ll) == per;
-            }
-            if (__all(ok)) break;
-            unsigned long long ab = 0ull;
-            if (lane == 0) ab = ld_agent(&sh->abort_word[0]);
-            // (its own workgroups' counts are a local matter: the short wait also under a communicator, where the
-            // workgroups' patience — timeout_ticks — has to outlast the exchange with the peers)
-            const bool late = __builtin_amdgcn_s_memrealtime() - t0 > L.count_timeout_ticks;
-            if (__any(ab != 0ull) || late) {
-                if (lane == 0) {
-                    st_agent(&sh->abort_word[0], 1ull);
-                    st->loop_aborted = 1;
-                    if (L.progress)        // (chained launches: the host stops enqueuing)
-                        __hip_atomic_store(&L.progress->word, (1ull << 32) | static_cast<unsigned long long>(it), __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-                if (const int al = lane_now(); al < kLoopPoseCopies) st_agent(&sh->pose[al][24], (tag << 32) | 2ull);      // (every copy's done word)
-                if (X.nranks > 1) {
-                    // the peers are inside (or on their way to) this very exchange: they leave it with us, and every
-                    // rank registers the frame again through the launch-per-iteration form, in step (run_icp)
-                    exchange_abort_wave(X, xg);
-                    xg += 1ull;
-                    if (lane == 0) *X.exchanges = xg;
-                }
-                return 2u;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        LOOP_STAMP_SOLVER(it, 0);
-        long long d = 0;
-        if (lane <= 3 * kAccValues) {
-#pragma unroll
-            for (int r = 0; r < COPIES; ++r) d += (v[r] - per) >> 8;       // (exact: the low byte is the count)
-        }
-#pragma unroll
-        for (int r = 0; r < COPIES; ++r)
-            __hip_atomic_store(&acc[r][lane], 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // the three digits of value l, held by the lanes 3 l .. 3 l + 2, come to lane l across the lanes (no trip
-        // through LDS and no barrier in the chain the grid waits for)
-        const int sl = lane_now();
-        const int s3 = 3 * (sl < kAccValues ? sl : 0);
-        const double a = static_cast<double>(__shfl(d, s3));
-        const double b = static_cast<double>(__shfl(d, s3 + 1));
-        const double c = static_cast<double>(__shfl(d, s3 + 2));
-        if (lane < kAccValues) {
-            sum = a + (b * 9.094947017729282e-13 + c * 8.271806125530277e-25);      // 2^-40, 2^-80
-            if (lane < kCount) sum *= L.acc_unscale;     // (a power of two; the pair count is not scaled)
-        }
-        if (lane < kNumSums) S[lane] = sum;
-        overflow = readlane_u64(static_cast<unsigned long long>(d), 3 * kAccValues) != 0ull;      // workgroups whose sums left the range (wgacc_flush)
-        __builtin_amdgcn_wave_barrier();
-    }
-    LOOP_STAMP_SOLVER(it, 1);
-
-    // 2. multi-GPU: this rank's sums -> the sums over all ranks (direct exchange over xGMI, P2pBlock)
-    bool exchange_failed = false;
-    if (X.nranks > 1) {
-        const int ex = exchange_sums_wave(S, X, xg);
-        xg += 1ull;
-        if (lane == 0) *X.exchanges = xg;
-        exchange_failed = ex == 1;
-        if (ex == 2) {
-            // a peer gave up its one-launch loop at this exchange: so does this rank (its workgroups see the abort word)
-            if (lane == 0) {
-                st_agent(&sh->abort_word[0], 1ull);
-                st->loop_aborted = 1;
-                st->peer_aborted = 1;
-                if (L.progress)        // (chained launches: the host stops enqueuing)
-                    __hip_atomic_store(&L.progress->word, (1ull << 32) | static_cast<unsigned long long>(it), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-            if (const int al = lane_now(); al < kLoopPoseCopies) st_agent(&sh->pose[al][24], (tag << 32) | 2ull);      // (every copy's done word)
-            return 2u;
-        }
-    }
-
-    // 3. solve, compose, test (Registration.cpp:92-93,135-137) — as k_fin's solve_and_publish
-    double x[6], est[7], nrm;
-    solve_normal_equations_t<WaveLanes>(S, x);
-    LOOP_STAMP_SOLVER2(it, 0);
-    se3_exp_sqrt_t<WaveLanes>(x, est, SAGE_SQNORM6(x), nrm);        // nrm = |x|, beside the exponential's sqrt
-    LOOP_STAMP_SOLVER2(it, 1);
-    double rhs[7], Tn[7];
-    {
-        const double *src = sT + (lane == 1 ? 7 : 0);      // lane 1: T_icp, the other lanes: T
-#pragma unroll
-        for (int i = 0; i < 7; ++i) rhs[i] = src[i];
-    }
-    se3_mul(est, rhs, Tn);
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 2) {
-        double *dst = sT + (lane == 1 ? 7 : 0);
-#pragma unroll
-        for (int i = 0; i < 7; ++i) dst[i] = Tn[i];
-    }
-    double Rn[9];
-    quat_to_mat(Tn, Rn);
-    LOOP_STAMP_SOLVER2(it, 2);
-    if (!(x[3] * x[3] + x[4] * x[4] + x[5] * x[5] < 9.0) || fabs(nrm - kEstimationThreshold) < 1e-12) {
-        double lg[6];                                      // see solve_and_publish
-        se3_log(est, lg);
-        nrm = sqrt(SAGE_SQNORM6(lg));
-    }
-    LOOP_STAMP_SOLVER2(it, 3);
-    const bool converged = nrm < kEstimationThreshold;
-    unsigned done = (converged || it + 1 >= L.max_iterations) ? 1u : 0u;
-    // (under a communicator an overflow on this rank alone must not end its loop: the peers would wait
-    // for its sums; the flag is raised and the host reports it when the loop has ended everywhere)
-    if (overflow && !L.shared_loop) done = 1u;
-    if (exchange_failed) done = 1u;
-    // 4. publish: 24 halves of R, t and the done word, each with its tag, once per copy of the pose — before the
-    // bookkeeping below: the grid waits for these words, nobody for the history (and the wait that follows would
-    // otherwise sit out those stores' round trip).  Every lane but lane 1 (which composed T_icp) holds the same R and t:
-    // the lanes 2 + l and 34 + l select granule l from their own registers — no trip through LDS —, one store
-    // instruction writes two copies, four write them all, fire and forget.
-    const int pl = lane_now();
-    const int gl = (pl & 31) - 2;
-    uint32_t word = done;                  // granule 24
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-        const unsigned long long v = static_cast<unsigned long long>(__double_as_longlong(i < 9 ? Rn[i] : Tn[i - 5]));
-        if ((gl >> 1) == i) word = static_cast<uint32_t>((gl & 1) ? v >> 32 : v);
-    }
-    LOOP_STAMP_SOLVER(it, 2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the clears of step 1, issued microseconds ago)
-    if (gl >= 0 && gl < kLoopPoseGranules) {
-#pragma unroll
-        for (int c = 0; c < kLoopPoseCopies; c += 2)
-            st_agent(&sh->pose[c + (pl >> 5)][gl], (tag << 32) | word);
-    }
-    if (lane == 0) {
-        if (it < kHistory) st->n_corr[it] = static_cast<uint32_t>(S[kCount]);
-        if (overflow) st->acc_overflow = 1;
-        if (exchange_failed) st->exchange_failed = 1;
-        if (done) {
-            // the final loop state, for the host (ordinary stores: the end of the kernel publishes them)
-#pragma unroll
-            for (int i = 0; i < 7; ++i) st->T[i] = Tn[i];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) st->R[i] = Rn[i];
-            st->last_step_norm = nrm;
-            st->iter = it + 1;
-            st->done = 1;
-            st->converged = (converged && !exchange_failed) ? 1 : 0;
-        }
-    }
-    if (done && lane == 1) {
-#pragma unroll
-        for (int i = 0; i < 7; ++i) st->T_icp[i] = Tn[i];
-    }
-    if (L.progress && lane == 0)       // (chained launches: the host keeps a few launches enqueued ahead and stops at `done`)
-        __hip_atomic_store(&L.progress->word, (static_cast<unsigned long long>(done ? 1u : 0u) << 32) | static_cast<unsigned long long>(it + 1),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (done && lane < kNumSums) st->sums[lane] = S[lane];
-    LOOP_STAMP_SOLVER(it, 3);
-    return done;
-}
-
-// The solving wave: one workgroup of one wave, launched on its own stream beside k_loop's grid (the
-// solve needs ~120 registers, the search 72: in one kernel every wave would pay for the solver).
-struct SolveArgs {
-    LoopParams L;
-    P2pParams X;
-};
-template <int COPIES>      // (two kernels: the one beside k_loop keeps its registers — 157, the grid's residency margin was measured with it)
-__global__ __launch_bounds__(64) void k_loop_solve(SolveArgs A) {
-    __shared__ SolveLds m;
-    __builtin_amdgcn_s_setprio(3);             // (the grid waits for this wave: its SIMD's other waves can)
-    {
-        // Launched before the frame is even sorted, so that this wave holds its registers when the grid
-        // of k_loop fills the machine; it waits here until the grid's first workgroup says that the
-        // shared block has been zeroed and the loop has started (LoopShared::go == this call's epoch).
-        const int lane = static_cast<int>(threadIdx.x & 63u);
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        for (;;) {
-            const unsigned long long g = ld_agent(&A.L.sh->go[0]);
-            if ((g & 0x7FFFFFFFFFFFFFFFull) == A.L.epoch) {
-                if (g >> 63) return;                        // (sort.hip found a non-finite point: the host reports it)
-                break;
-            }
-            // (the sort, the upload of a frame and a mirror refresh precede the grid: seconds, not the
-            // microseconds of the waits inside the loop)
-            if (__builtin_amdgcn_s_memrealtime() - t0 > 1000ull * A.L.timeout_ticks + 1000000000ull) {
-                if (lane == 0) A.L.st->loop_aborted = 1;
-                return;
-            }
-            __builtin_amdgcn_s_sleep(32);
-        }
-        if (lane < 14) m.T[lane] = lane < 7 ? A.L.T0[lane] : (lane == 10 ? 1.0 : 0.0);     // T | T_icp = identity (x, y, z, w | t)
-    }
-    unsigned long long xg = A.X.nranks > 1 ? *A.X.exchanges : 0ull;
-    __builtin_amdgcn_wave_barrier();
-    for (int it = 0;; ++it) {
-        // (the arguments are re-read from the kernel-argument segment every iteration: see k_loop)
-        auto ka = __builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(ka));
-        const SolveArgs &K = *(const SolveArgs *)(ka);
-        if (loop_finish_iteration<COPIES>(K.L, K.X, m, it, xg)) return;
-    }
-}
-
-#ifndef SAGE_LOOP_POLL_SLEEP
-#define SAGE_LOOP_POLL_SLEEP 8     // x 64 clocks between two looks of a workgroup at the pose granules
-#endif
-// (Tried and dropped, profiles/r05/mix_ab_*.txt: a workgroup with more units of queries than waves registering
-// PAIRS of units at half the lanes per query, one wave per pair, so that every wave makes one pass — bit-identical,
-// the sums being exact from the blocks of four queries on, and slower: 37.5 against 34.6 us per iteration on c2.  A
-// wave's pass lasts as long as its lanes have points to look at: two units at half the lanes are two passes' worth.)
-template <int LW, bool FILT>
-__global__ __launch_bounds__(64 * kLoopMaxWaves) __attribute__((amdgpu_waves_per_eu(SAGE_LOOP_OCC, 8)))
-void k_loop(LoopArgs A) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-    constexpr int QW = 64 >> LW;
-    const IcpParams &P = A.P;
-    const LoopParams &L = A.L;
-    const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
-    const int nw = L.nw;
-    const unsigned gpw = static_cast<unsigned>(L.gpw);
-    double *s_pose = reinterpret_cast<double *>(smem + kLpPose);
-
-    {
-        // (sort.hip found a non-finite point: nobody starts, the host reports it — except under a communicator,
-        // where the ranks must keep exchanging in step)
-        const bool bad = !L.shared_loop && P.st->bad_input;
-        if (blockIdx.x == 0 && threadIdx.x == 0)
-            st_agent(&L.sh->go[0], L.epoch | (bad ? 0x8000000000000000ull : 0ull));      // the solving wave may start
-        if (bad) return;
-    }
-
-#ifdef SAGE_LOOP_INGRID
-    // Counter-collection twin (profiles/run_profiles.sh builds it as a variant library): rocprofv3 --pmc runs one
-    // kernel at a time, which the grid and its solving wave — two kernels that talk to each other — do not survive.
-    // Here the solving wave is one more workgroup of THIS grid (its path spills under the search's register budget:
-    // the twin is for bytes and instruction counts, not for time).
-    if (blockIdx.x == gridDim.x - 1u) {
-        if (threadIdx.x >= 64u) return;
-        SolveLds &m = *reinterpret_cast<SolveLds *>(smem);
-        const int lane = static_cast<int>(threadIdx.x & 63u);
-        if (lane < 14) m.T[lane] = lane < 7 ? L.T0[lane] : (lane == 10 ? 1.0 : 0.0);
-        __builtin_amdgcn_wave_barrier();
-        P2pParams X{};
-        X.nranks = 1;
-        unsigned long long xg = 0ull;
-        for (int it = 0;; ++it)
-            if (loop_finish_iteration<kLoopReplicas>(L, X, m, it, xg)) return;
-    }
-#endif
-
-    // ---- the units (of QW queries) this workgroup owns for the whole call ----------------------------
-    // Workgroup b is dispatched to XCD b % 8 (observed; speed only).  Striped: XCD x serves the stripes
-    // x, x + 8, ... of kLoopStripe workgroups' worth of the spatially sorted frame (every XCD gets the
-    // same mix of dense and sparse regions, every L2 sees the whole map).  Contiguous: XCD x serves the
-    // units [xcd_first[x], xcd_first[x + 1]) — one compact region of the map per L2, the boundaries
-    // chosen by the host so that the XCDs hold equal work.
-    // Either way the units are dealt out EVENLY over the workgroups that serve them — floor or ceil of
-    // units / workgroups each, never more than gpw: a frame of 7,500 units on 1,664 resident workgroups
-    // of four waves gives 844 of them a fifth unit instead of leaving 200 with none.
-    unsigned g0, gcnt;
-    {
-        const unsigned xcd = blockIdx.x & 7u, jb = blockIdx.x >> 3;
-        const unsigned ngroups = (static_cast<unsigned>(P.n) + QW - 1u) / QW;
-        unsigned lo = 0u, cnt = ngroups, idx, nwg;
-        if (L.contiguous == 1) {
-            lo = L.xcd_first[xcd];
-            cnt = L.xcd_first[xcd + 1u] - lo;
-            idx = jb;
-            nwg = static_cast<unsigned>(L.wgs) >> 3;
-        } else {
-            idx = ((jb / kLoopStripe) * 8u + xcd) * kLoopStripe + (jb % kLoopStripe);
-            nwg = static_cast<unsigned>(L.wgs);
-        }
-        const unsigned base = cnt / nwg, extra = cnt - base * nwg;      // `extra` workgroups serve base + 1 groups
-        g0 = lo + idx * base + min(idx, extra);
-        gcnt = min(gpw, base + (idx < extra ? 1u : 0u));
-    }
-    unsigned long long *wgacc = reinterpret_cast<unsigned long long *>(smem + kLpAcc);
-    // LDS after the header: perm[gpw * QW / 4] | work[gpw * QW / 4] | rows of the workgroup's queries | their state
-    // records | one scratch for the transposed block sums per wave
-    constexpr unsigned BPW = QW / 4;                                  // blocks of four queries per pass
-    const unsigned nblk_max = gpw * BPW, nblk = gcnt * BPW;
-    uint32_t *perm = smem + kLpHeaderWords;
-    uint32_t *work = perm + loop_perm_words(nblk_max) / 2u;
-    uint32_t *rows = perm + loop_perm_words(nblk_max);
-    uint32_t *state = rows + gpw * QW * kRowLdsStride;
-    double *red = reinterpret_cast<double *>(state + gpw * QW * kLoopStateWords + static_cast<unsigned>(wv) * loop_red_words());
-
-    // ---- set-up: the initial pose, the state records of the groups' queries --------------------------
-    if (threadIdx.x < 9) s_pose[threadIdx.x] = P.st->R[threadIdx.x];
-    else if (threadIdx.x < 12) s_pose[threadIdx.x] = P.st->T[4 + threadIdx.x - 9];
-    if (threadIdx.x == 0) {
-        smem[kLpArrive] = 0u;
-        smem[kLpNext] = 0u;
-        smem[kLpDone] = 0u;
-#ifdef SAGE_LOOP_TIMING
-        smem[kLpDbg] = 0u; smem[kLpDbg + 1] = 0u; smem[kLpDbg + 2] = 0u;
-#endif
-    }
-    if (L.deal && (threadIdx.x & 63u) == 0u) {
-        // The heaviest unit of a workgroup (its blocks are ordered by work) should not meet the heaviest units of the
-        // other workgroups of its CU on one SIMD: a workgroup's four waves sit on the four SIMDs, one wave of every
-        // workgroup of the CU per SIMD, and a SIMD's issue slots are what its waves share.  Workgroup r of the CU
-        // (its waves' slot number) hands unit (s + r) mod waves to its wave on SIMD s: every SIMD gets the same mix.
-        unsigned hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        smem[kLpFirst + static_cast<unsigned>(wv)] = (((hw >> 4) & 3u) + (hw & 15u)) % static_cast<unsigned>(nw);
-    }
-    for (unsigned i = threadIdx.x; i < 2u * kWgAccWords; i += blockDim.x) smem[kLpAcc + i] = 0u;
-    for (unsigned i = threadIdx.x; i < nblk_max; i += blockDim.x) {
-        perm[i] = i;                           // the order of the frame, until the blocks' work is known
-        work[i] = 0u;
-    }
-    for (unsigned sl = threadIdx.x; sl < gcnt * QW; sl += blockDim.x) {
-        const unsigned q = g0 * QW + sl;       // slot sl of this workgroup
-        const Point4 f = P.frame[q < static_cast<unsigned>(P.n) ? q : 0u];
-        {
-            uint32_t *lst = state + sl * kLoopStateWords;
-            *reinterpret_cast<Point4 *>(lst) = f;
-            Point4 z;
-            z.x = z.y = z.z = z.l = 0.0;
-            *reinterpret_cast<Point4 *>(lst + 8) = z;
-            *reinterpret_cast<uint4 *>(lst + kStPrev) = make_uint4(0xFFFFFFFFu, 0u, static_cast<uint32_t>(kNoVoxel),
-                                                                   static_cast<uint32_t>(kNoVoxel));   // no answer, no row yet:
-            *reinterpret_cast<uint4 *>(lst + kStPrev + 4) = make_uint4(static_cast<uint32_t>(kNoVoxel), 0u, 0u, 0u);   // the first pass builds it
-        }
-    }
-    __syncthreads();
-    if (L.deal) {
-        // (two waves of a workgroup on one SIMD would ask for the same unit: the first keeps it, the others take what is
-        // left — every wave derives the same table, wave 0 stores it)
-        unsigned claimed = 0u, kept = 0u, table[kLoopMaxWaves];
-        for (int w2 = 0; w2 < nw; ++w2) {
-            const unsigned pr = smem[kLpFirst + static_cast<unsigned>(w2)];
-            table[w2] = pr;
-            if (!((claimed >> pr) & 1u)) { claimed |= 1u << pr; kept |= 1u << w2; }
-        }
-        for (int w2 = 0; w2 < nw; ++w2)
-            if (!((kept >> w2) & 1u)) {
-                const unsigned pr = static_cast<unsigned>(__builtin_ctz(~claimed));
-                table[w2] = pr;
-                claimed |= 1u << pr;
-            }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w2 = 0; w2 < nw; ++w2) smem[kLpFirst + static_cast<unsigned>(w2)] = table[w2];
-            smem[kLpNext] = static_cast<unsigned>(nw);
-        }
-        __syncthreads();
-    }
-#ifdef SAGE_LOOP_TIMING
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long t_wait = 0, t_close = 0, n_pass = 0;
-#endif
-
-    for (int it = 0;; ++it) {
-        // Every iteration (and every pass of the body) re-reads its arguments from the kernel-argument
-        // segment — scalar loads from the constant cache, as a wave of k_icp does at its start — and
-        // re-derives its lane index: values the compiler knows to be invariant across this loop it would
-        // hoist out of it and keep alive, ~50 scalars and a dozen vector registers the scan needs.
-        auto ka = __builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(ka));
-        const LoopArgs &K = *(const LoopArgs *)(ka);
-        const LoopParams &L = K.L;
-        LoopShared *sh = L.sh;
-        unsigned lane_u;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_u));
-        const int lane = static_cast<int>(lane_u);
-        // the workgroup's groups, first come first served: a wave held up by a heavy query takes fewer
-        bool dealt = L.deal != 0;
-        for (;;) {
-            unsigned gi = 0u;
-            if (dealt) {
-                // (this wave's first unit is fixed by where it sits; the units beyond one per wave go first come first served)
-                dealt = false;
-                gi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(smem[kLpFirst + static_cast<unsigned>(wv)])));
-                if (gi >= gcnt) continue;
-            } else {
-                if (lane == 0)
-                    gi = __hip_atomic_fetch_add(&smem[kLpNext], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                gi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(gi)));
-                if (gi >= gcnt) break;
-            }
-            if (L.prio) {
-                // A SIMD's issue slots go to its waves by priority: the wave with the heaviest unit of its workgroup (the
-                // units are ordered by last iteration's work) runs at the highest, the lightest at the lowest, a unit beyond
-                // one per wave — it starts late — at `prio` (3 by default).  The work of a SIMD does not change with the order, but
-                // its END does: the long chains run while there is other work to fill their stalls with, and what
-                // is left to run alone at the end of an iteration are the short ones (c2: 31.2 -> 28.2 us per iteration,
-                // profiles/r06/deal_ab.txt).
-                const unsigned rk = gi >= static_cast<unsigned>(nw) ? static_cast<unsigned>(L.prio) : 3u - min(gi, 3u);
-                switch (rk) {
-                    case 0: __builtin_amdgcn_s_setprio(0); break;
-                    case 1: __builtin_amdgcn_s_setprio(1); break;
-                    case 2: __builtin_amdgcn_s_setprio(2); break;
-                    default: __builtin_amdgcn_s_setprio(3); break;
-                }
-            }
-#ifdef SAGE_LOOP_TIMING
-            if (gi >= static_cast<unsigned>(nw)) LOOP_STAMP_WG(it, 2);
-            const unsigned long long t_unit = __builtin_amdgcn_s_memrealtime();
-#endif
-            LoopGroup G;
-            G.rows = rows;
-            G.state = state;
-            G.perm = perm;
-            G.work = work;
-            G.unit = gi;
-            G.red = red;
-            G.wgacc = wgacc;
-            G.q_first = g0 * QW;
-            G.slot = g0 + gi;
-#ifdef SAGE_LOOP_TIMING
-            for (int i = 0; i < 8; ++i) G.ph[i] = 0;
-            G.tprev = __builtin_amdgcn_s_memtime();
-            ++n_pass;
-#endif
-            {
-                auto kb = __builtin_amdgcn_kernarg_segment_ptr();
-                asm volatile("" : "+s"(kb));
-                icp_body<LW, true, FILT, true>(((const LoopArgs *)(kb))->P, smem, &G, s_pose);
-            }
-#ifdef SAGE_LOOP_TIMING
-            if (gi >= static_cast<unsigned>(nw)) LOOP_STAMP_WG(it, 3);
-            if (it < kLoopTimedIters && blockIdx.x < kLoopTimedWgs && lane == 0 && wv < 8 && gi < static_cast<unsigned>(nw)) {
-                unsigned hw;
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-                g_loop_wave[it][blockIdx.x][wv][0] = __builtin_amdgcn_s_memrealtime();
-                g_loop_wave[it][blockIdx.x][wv][1] = (t_unit << 24) | (static_cast<unsigned long long>(gi & 0xFFu) << 16) | (hw & 0xFFFFu);
-            }
-#endif
-#ifdef SAGE_LOOP_TIMING
-            for (int i = 0; i < 8; ++i) ph[i] += G.ph[i];
-#endif
-        }
-#ifdef SAGE_LOOP_TIMING
-        const unsigned long long t_a = __builtin_amdgcn_s_memtime();
-#endif
-        // (what the ticket orders — the groups' sums — lives in LDS, which serves a CU's waves in order)
-        unsigned prior = 0u;
-        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        if (lane == 0)
-            prior = __hip_atomic_fetch_add(&smem[kLpArrive], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __atomic_signal_fence(__ATOMIC_SEQ_CST);
-        prior = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(prior)));
-        const bool last = prior == static_cast<unsigned>(nw) - 1u;
-        if (last) {
-            // this wave closes the workgroup's iteration
-            wgacc_flush<true>(wgacc, &sh->acc[it & 1][blockIdx.x & (kLoopReplicas - 1)][0], &sh->acc[it & 1][0][kAccWords - 1]);
-            if (lane == 0) {                   // everybody is in: ready for the next iteration
-                smem[kLpArrive] = 0u;
-                smem[kLpNext] = L.deal ? static_cast<unsigned>(nw) : 0u;
-            }
-            // The next iteration's order of the workgroup's blocks: heaviest first, by what they cost in this one (a
-            // rank sort on one wave: lane i counts the blocks that go before block i).  Blocks of like work then
-            // share a wave — whose pass lasts as long as its heaviest query — and the heaviest waves start first.
-            // (Which blocks share a wave does not reach the sums: they are exact from the block on.)
-            if (nblk <= 64u && nblk > BPW) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                const unsigned i = static_cast<unsigned>(lane);
-                const unsigned wi = i < nblk ? work[i] : 0u;
-                unsigned rank = 0u;
-                for (unsigned j = 0; j < nblk; ++j) {
-                    const unsigned wj = work[j];
-                    rank += (wj > wi || (wj == wi && j < i)) ? 1u : 0u;
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                if (i < nblk) {
-                    perm[rank] = i;
-                    work[i] = 0u;
-                }
-            }
-#ifdef SAGE_LOOP_TIMING
-            if (lane == 0 && it < kLoopTimedIters && blockIdx.x < kLoopTimedWgs) {
-                unsigned hw;
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-                unsigned xcc;
-                asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-                unsigned *o = g_loop_wginfo[it][blockIdx.x];
-                o[0] = (xcc << 28) | (hw & 0x0FFFFFFFu);
-                o[1] = smem[kLpDbg]; o[2] = smem[kLpDbg + 1]; o[3] = smem[kLpDbg + 2];
-                smem[kLpDbg] = 0u; smem[kLpDbg + 1] = 0u; smem[kLpDbg + 2] = 0u;
-            }
-#endif
-            LOOP_STAMP_WG(it, 0);
-        }
-        if (wv == 0) {
-            // the next pose, for this workgroup
-            const unsigned long long tag = static_cast<unsigned long long>(it) + 1ull;
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            unsigned long long g = tag << 32;
-            bool aborted = false;
-            for (;;) {
-                if (lane < kLoopPoseGranules) g = ld_agent(&sh->pose[loop_pose_copy(L.pose_map)][lane]);
-                const bool ok = (g >> 32) == tag;
-                if (__all(ok)) break;
-                unsigned long long ab = 0ull;
-                if (lane == 0) ab = ld_agent(&sh->abort_word[0]);
-                const bool late = __builtin_amdgcn_s_memrealtime() - t0 > L.timeout_ticks;
-                if (__any(ab != 0ull) || late) {
-                    if (lane == 0 && late) {
-                        st_agent(&sh->abort_word[0], 1ull);
-                        L.st->loop_aborted = 1;
-                    }
-                    aborted = true;
-                    break;
-                }
-                // (more than a thousand workgroups wait here for most of an iteration — since the pose has a copy per
-                // XCD, some two hundred per copy, on four cache lines of their own: a pass every ~0.3 us each keeps
-                // the L2 that serves them, and the accumulators the solving wave is reading, quiet)
-                __builtin_amdgcn_s_sleep(SAGE_LOOP_POLL_SLEEP);
-                // (a big grid backs off twice as long: c2's 1,664 workgroups 30.7 -> 30.3 us per iteration, flat from there
-                // to six times as long; c1's 640 prefer the short one — same-box A/B, profiles/r05/poll_sleep.txt, taken
-                // when all of them polled ONE block; with a copy per XCD: profiles/r15/README.md)
-                if (L.wgs > 1024) __builtin_amdgcn_s_sleep(SAGE_LOOP_POLL_SLEEP);
-            }
-            if (aborted) {
-                if (lane == 0) smem[kLpDone] = 2u;
-            } else {
-                if (lane < 24) reinterpret_cast<uint32_t *>(s_pose)[lane] = static_cast<uint32_t>(g);
-                if (lane == 24) smem[kLpDone] = static_cast<uint32_t>(g);
-            }
-            LOOP_STAMP_WG(it, 1);
-        }
-#ifdef SAGE_LOOP_TIMING
-        const unsigned long long t_b = __builtin_amdgcn_s_memtime();
-        if (last) t_close += t_b - t_a;
-#endif
-        __syncthreads();
-#ifdef SAGE_LOOP_TIMING
-        t_wait += __builtin_amdgcn_s_memtime() - t_b;
-#endif
-        if (smem[kLpDone]) break;
-    }
-#ifdef SAGE_LOOP_TIMING
-    if ((threadIdx.x & 63u) == 0u) {
-        for (int i = 0; i < 8; ++i) atomicAdd(&g_loop_phase[i], ph[i]);
-        atomicAdd(&g_loop_phase[8], t_wait);
-        atomicAdd(&g_loop_phase[9], t_close);
-        atomicAdd(&g_loop_phase[10], n_pass);
-    }
-#endif
-}
+namespace sageicp {
 
 // ------------------------------------------------------------------------------------ k_gn
 // AlignClouds' accumulation (Registration.cpp:62-90) on explicit pairs: every pair is taken.
@@ -1711,50 +688,6 @@ __global__ __launch_bounds__(256) void k_tf(Point4 *pts, int n, const IcpState *
     p.x = x; p.y = y; p.z = z;
     pts[i] = p;
 }
-
-#ifdef SAGE_GN_TIMING
-extern "C" void sageicp_debug_gn_phases(unsigned long long out[16], int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gn_phase), sizeof(unsigned long long) * 16);
-    if (reset) {
-        unsigned long long z[16] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gn_phase), z, sizeof(z));
-    }
-}
-#endif
-#ifdef SAGE_NN_TIMING
-extern "C" void sageicp_debug_nn_spans(unsigned long long *out, unsigned nwaves, int next_iter) {
-    // raw {start, end, HW_ID, pairs of lane 0} of the first `nwaves` waves of the k_icp launch of
-    // the iteration chosen by the previous call; `next_iter` chooses the one the next loop records
-    if (nwaves > kNnTimingSlots) nwaves = kNnTimingSlots;
-    if (out) (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_nn_span), 4ull * nwaves * sizeof(unsigned long long));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_nn_span_iter), &next_iter, sizeof(int));
-}
-extern "C" void sageicp_debug_nn_raw(unsigned long long *out, unsigned nwaves) {
-    // per wave slot, summed over the launches since the last reset: 5 phases and the lifetime
-    // (shader cycles), the lifetime in 100-MHz ticks, launches
-    if (nwaves > kNnTimingSlots) nwaves = kNnTimingSlots;
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_nn_phase), 8ull * nwaves * sizeof(unsigned long long));
-}
-extern "C" void sageicp_debug_nn_phases(unsigned long long out[16], int reset) {
-    // out: [0..4] summed cycles of the five phases (loads, row, home scan, rest of the search,
-    // epilogue), [5] summed wave lifetime (shader cycles), [6] the same in 100-MHz ticks, [7] waves,
-    // [8] the slowest wave slot's mean lifetime (cycles), [9] slots used
-    std::vector<unsigned long long> h(8ull * kNnTimingSlots);
-    (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_nn_phase), h.size() * sizeof(unsigned long long));
-    for (int i = 0; i < 16; ++i) out[i] = 0;
-    for (unsigned s = 0; s < kNnTimingSlots; ++s) {
-        const unsigned long long *t = &h[8ull * s];
-        if (!t[7]) continue;
-        for (int k = 0; k < 8; ++k) out[k] += t[k];
-        if (t[5] / t[7] > out[8]) out[8] = t[5] / t[7];
-        ++out[9];
-    }
-    if (reset) {
-        std::fill(h.begin(), h.end(), 0ull);
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_nn_phase), h.data(), h.size() * sizeof(unsigned long long));
-    }
-}
-#endif
 
 // ------------------------------------------------------------------------------- mirror refresh
 // Scatter the records the host changed since the last sync into the HBM mirror: one staged copy
@@ -1881,8 +814,7 @@ void launch_icp(const IcpParams &p, int lw, bool fused, hipStream_t s) {
 }
 
 size_t loop_lds_bytes(int lw, int nw, int gpw) {
-    return sizeof(uint32_t) * (kLpHeaderWords + loop_perm_words(static_cast<unsigned>(gpw) * ((64u >> lw) / 4u)) +
-                               static_cast<size_t>(gpw) * loop_group_words(lw) + static_cast<size_t>(nw) * loop_red_words());
+    return sizeof(uint32_t) * LoopLds<size_t>(lw, static_cast<size_t>(nw), static_cast<size_t>(gpw)).end;
 }
 // the kernel of a shape, as an untyped pointer (what the occupancy query and the launch take)
 static const void *loop_kernel(int lw, bool filter) {

@@ -1,6 +1,7 @@
-"""The instrumented builds behind profiles/ (csrc/probes.h: SAGE_NN_TIMING, SAGE_LOOP_TIMING, SAGE_ICP_DELAY_PROBE; the
-stamps beside the loops: SAGE_GN_TIMING; the counter-collection twin: SAGE_LOOP_INGRID) must keep compiling: each switch,
-device code of kernels.hip only, compiled and thrown away.  CPU only (hipcc cross-compiles gfx950)."""
+"""The instrumented builds behind profiles/ (csrc/probes.h holds all of their instrumentation: SAGE_NN_TIMING,
+SAGE_LOOP_TIMING, SAGE_GN_TIMING, SAGE_ICP_DELAY_PROBE; the counter-collection twin, SAGE_LOOP_INGRID, changes the protocol
+of k_loop and lives in loop_kernel.h) must keep compiling: each switch, device code of kernels.hip — with icp_body.h,
+fin_kernel.h and loop_kernel.h, which it includes — only, compiled and thrown away.  CPU only (hipcc cross-compiles gfx950)."""
 import importlib.util
 import os
 
