@@ -18,6 +18,9 @@ namespace sageicp {
 #ifndef SAGE_LOOP_FLAT_MINW
 #define SAGE_LOOP_FLAT_MINW 8      // k_loop: flat-order scan from this many lanes per query (icp_body)
 #endif
+#ifndef SAGE_SCAN_AHEAD
+#define SAGE_SCAN_AHEAD 1          // per-voxel restart scan: open a lane's next voxel one step ahead (icp_body)
+#endif
 
 // a pair of scanned points in flight: compact records (FILT) or full ones
 struct PairCompact {
@@ -395,6 +398,7 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
     // compact record of point k lives (bytes).  Only the key of the winner is
     // tracked; its offset is rebuilt from the row once per query.
     unsigned k = ci, kend = 0u, off = 0u;
+    unsigned pk = 0u, needs = 0u, wn = 0u;     // AHEAD (below): packed cursor, `need` with its end mark, the next voxel's row word
     // The reference's comparison, fp64, on a full record.  Branch-free: a lane that holds no
     // candidate here (`on` false) turns its distance into a NaN, which loses every comparison.
     auto evaluate = [&](const Point4 &nb, bool on, unsigned key) {
@@ -489,6 +493,23 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
     // 213 -> 223 frames/s; against c2's and c4's ~12 points per voxel the per-voxel restart is the faster
     // one by 1.5 and 5 %, profiles/r04/flat_where.txt).
     constexpr bool FLAT = PERSIST ? (W >= SAGE_LOOP_FLAT_MINW) : FLATQ;
+    // AHEAD (per-voxel restart order only): the same points on the same lanes, with the cursor kept otherwise.
+    //  - One register `pk` holds the key of the lane's next point in its low half and slot - points-in-the-voxel in its
+    //    high half: negative while the lane has a point (`ha`), below -W while it has a second one (`hb`); one add
+    //    advances both.  (Keys stay under 2^13, the steps of a scan add less than 2^13 more: no carry into the high half.)
+    //  - The row word of the lane's NEXT voxel, `wn`, is read from LDS at the end of issue(), under the loads just sent
+    //    and the other set's consume(); the step that finds the open voxel exhausted takes it in ONE divergent region (as
+    //    selects it cost 48 B more scratch in k_loop): no LDS round trip and no loop inside the step.  A lane opens at most one voxel per step: one in which it has no point
+    //    (fewer points than its lane index; `need` holds no empty voxel, it is masked by `occ`) costs it an idle step.
+    //    Lane 0 of the query has a point in every voxel of `need` and at least as many as any other lane, so it takes
+    //    the steps it took before and no lane takes more: the scan is as long as it was.
+    //  - `needs` is `need` with bit 31 set: its lowest set bit is always defined, and an exhausted mask reads row word
+    //    31 (kRowOcc, inside the row), which nothing takes.
+    //  The descriptor read ahead lives inside one scan(): rows are rebuilt before the first.
+    //  (Where the registers allow: not the plain nearest-neighbour query on full records, k_icp<*, false, false, false>,
+    //  69 -> 76 registers, nor k_loop at two lanes per query, one more spilled register; profiles/r19/resource_usage.txt.)
+    constexpr bool AHEAD = SAGE_SCAN_AHEAD != 0 && !FLAT && (PERSIST ? W >= 4 : (FUSED || FILT));
+    constexpr unsigned kNeedEnd = 0x80000000u;
     using Pair = std::conditional_t<FLAT, std::conditional_t<FILT, PairCompactFlat, PairFullFlat>,
                                     std::conditional_t<FILT, PairCompact, PairFull>>;
     auto scan = [&](unsigned need, const Point4 *seed, bool seeded, unsigned seed_key) {
@@ -510,6 +531,7 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
             k += h ? static_cast<unsigned>(W) : 0u;
             off += h ? static_cast<unsigned>(W) << SHC : 0u;
         };
+        auto pair_hb = [&](unsigned p) { return static_cast<int>(p) < -static_cast<int>(static_cast<unsigned>(W) << 16); };
         auto issue = [&](Pair &n, bool &more) {
             if constexpr (FLAT) {
                 unsigned oa, ob;
@@ -527,6 +549,35 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
                 __builtin_amdgcn_sched_barrier(0);
                 more = (k < kend) | (need != 0u);
                 return;
+            } else if constexpr (AHEAD) {
+                // (one test, not two nested ones)
+                const bool adv = (static_cast<int>(pk) >= 0) & (needs != kNeedEnd);
+                if (adv) {                                       // exhausted, and another voxel to open: at most one
+                    const unsigned v = static_cast<unsigned>(__builtin_ctz(needs));
+                    const unsigned cnt = wn & 255u;
+                    pk = ((ci - cnt) << 16) + ((v << 8) | ci);
+                    off = (((wn >> 8) * kUnitPoints) + ci) << SHC;
+                    npairs += cnt;
+                    needs &= needs - 1u;
+                }
+                n.ka = pk;                                       // (consume() reads ha, hb and the key from it)
+                if constexpr (FILT) n.oa = off;
+                n.ha = static_cast<int>(pk) < 0;
+                n.hb = pair_hb(pk);
+                const unsigned oa = n.ha ? off : 0u;             // (idle lanes re-read record 0, as below)
+                if constexpr (FILT) {
+                    n.a = load_cand(cands, oa);
+                    n.b = load_cand(cands, oa, W << SHC);
+                } else {
+                    const unsigned ob = n.hb ? off + (static_cast<unsigned>(W) << SHC) : 0u;
+                    n.a = load_point(pts, oa);
+                    n.b = load_point(pts, ob);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                pk += 2u * W * 0x10001u;
+                off += (2u * W) << SHC;
+                wn = lrow[__builtin_ctz(needs)];                 // the voxel after: in flight until the next issue()
+                more = (static_cast<int>(pk) < 0) | (needs != kNeedEnd);
             } else {
             while (k >= kend && need) {        // open this lane's next voxel
                 const unsigned v = static_cast<unsigned>(__builtin_ctz(need));
@@ -565,15 +616,17 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
         };
         auto consume = [&](const Pair &n) {
             unsigned kb;                        // b's key: W points on in a's voxel, or its own (flat order)
-            if constexpr (FLAT) kb = n.kb; else kb = n.ka + W;
+            const unsigned ka = AHEAD ? n.ka & 0xFFFFu : n.ka;
+            const bool ha = AHEAD ? static_cast<int>(n.ka) < 0 : n.ha, hb = AHEAD ? pair_hb(n.ka) : n.hb;
+            if constexpr (FLAT) kb = n.kb; else kb = ka + W;
             if constexpr (!FILT) {
-                evaluate(n.a, n.ha, n.ka);
-                evaluate(n.b, n.hb, kb);
+                evaluate(n.a, ha, ka);
+                evaluate(n.b, hb, kb);
             } else {
             // (the candidate already held — the seed met again in its voxel — needs no second look)
             float dla, dlb;
             const float da = dist32(n.a, dla), db = dist32(n.b, dlb);
-            const bool la = n.ha & !(da > Tmax) & (n.ka != bkey), lb = n.hb & !(db > Tmax) & (kb != bkey);
+            const bool la = ha & !(da > Tmax) & (ka != bkey), lb = hb & !(db > Tmax) & (kb != bkey);
             PROBE_NN_CONSUME(np);
             if (__ballot(la | lb)) {
             const bool pa = la & tight(n.a, da, dla), pb = lb & tight(n.b, db, dlb);
@@ -587,7 +640,7 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
                 if constexpr (FLAT) ob = n.ob; else ob = n.oa + (static_cast<unsigned>(W) << SHC);
                 const Point4 ea = load_point(pts, pa ? n.oa << 1 : 0u);
                 const Point4 eb = load_point(pts, pb ? ob << 1 : 0u);
-                evaluate(ea, pa, n.ka);
+                evaluate(ea, pa, ka);
                 evaluate(eb, pb, kb);
                 fb = min_f64(fb, best);
                 set_thresholds();
@@ -602,6 +655,12 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
         // slow waves are not waiting for their loads.  Two sets everywhere; the switch is gone.)
         Pair A, B;
         bool more = false;
+        if constexpr (AHEAD) {
+            pk = 0u;                            // no voxel open
+            off = 0u;
+            needs = need | kNeedEnd;
+            wn = lrow[__builtin_ctz(needs)];
+        }
         issue(A, more);
         // the seed's load is older than A's: waiting for it leaves A's loads in flight
         if (seed) evaluate(*seed, seeded, seed_key);
@@ -618,7 +677,7 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
             consume(A);
             issue(A, more);
             consume(B);
-            if (!__ballot(A.ha | more)) break;
+            if (!__ballot((AHEAD ? static_cast<int>(A.ka) < 0 : A.ha) | more)) break;
         }
     };
 
