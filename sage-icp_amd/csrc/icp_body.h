@@ -21,6 +21,12 @@ namespace sageicp {
 #ifndef SAGE_SCAN_AHEAD
 #define SAGE_SCAN_AHEAD 1          // per-voxel restart scan: open a lane's next voxel one step ahead (icp_body)
 #endif
+#ifndef SAGE_ROW_SHIFT_LAYER
+#define SAGE_ROW_SHIFT_LAYER 1     // stale row after a step into a neighbouring voxel: probe only the new layer (icp_body, row_shift.h)
+#endif                             // (2, measurements only: the path compiled in but never taken, results as with 0)
+#ifndef SAGE_ROW_SHIFT_MAXW
+#define SAGE_ROW_SHIFT_MAXW 4      // ... in k_loop up to this many lanes per query (8, 16: trial builds, profiles/r20)
+#endif
 
 // a pair of scanned points in flight: compact records (FILT) or full ones
 struct PairCompact {
@@ -289,34 +295,96 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
                                dzu = static_cast<unsigned>(s.kz) - rk.z;
                 const bool nearv = dxu + 1u <= 2u && dyu + 1u <= 2u && dzu + 1u <= 2u;
                 const int dx = static_cast<int>(dxu), dy = static_cast<int>(dyu), dz = static_cast<int>(dzu);
-                // the old words of this lane's voxels (LDS is in order within a wave: every read here
-                // precedes the writes below, also those of the query's other lanes)
-                uint32_t ow[NV];
-                bool reuse[NV];
+                // k_loop at four lanes: a step into a neighbouring voxel costs what it needs (row_shift.h).  The kept
+                // words move by ONE offset under one mask, the occupancy mask is the old one shifted, and the 9 / 15 / 19
+                // new voxels are dealt over the query's lanes by rank: a lane has all its probes of a face crossing
+                // (three at most) in flight at once, whatever the axis.  It repeats the walk's pattern below — old words,
+                // `start`, `finish` — over its own, shorter lists.  (Eight and sixteen lanes keep the walk: SAGE_ROW_SHIFT_MAXW.)
+                constexpr bool kLayer = SAGE_ROW_SHIFT_LAYER && PERSIST && W >= 4 && W <= SAGE_ROW_SHIFT_MAXW;
+                bool shifted = false;
+                if constexpr (kLayer) {
+                    if (nearv && (SAGE_ROW_SHIFT_LAYER != 2 || P.n < 0)) {
+                        shifted = true;
+                        const uint32_t kept = rowshift::kept_mask(dx, dy, dz);
+                        // the old words of this lane's kept voxels (LDS is in order within a wave: every read here
+                        // precedes the writes below, also those of the query's other lanes)
+                        // (`kept` has 27 bits: bit W * j of `kl` is never set for a v = ci + W * j >= 27, which so is
+                        // neither read nor written)
+                        const uint32_t kl = kept >> ci;
+                        uint32_t ow[NV];
 #pragma unroll
-                for (int j = 0; j < NV; ++j) {
-                    const int v = static_cast<int>(ci) + W * j;
-                    const unsigned a = static_cast<unsigned>(v / 9) + dxu, b = static_cast<unsigned>((v / 3) % 3) + dyu,
-                                   c = static_cast<unsigned>(v % 3) + dzu;
-                    reuse[j] = nearv && v < 27 && a <= 2u && b <= 2u && c <= 2u;
-                    ow[j] = lrow[reuse[j] ? a * 9u + b * 3u + c : 0u];
-                }
-                uint32_t sl[NV];
-                int4 e[NV];
-                constexpr int NB = PERSIST ? 4 : 3;       // probes in flight per lane (k_icp: its register budget)
+                        for (int j = 0; j < NV; ++j) {
+                            const bool kp = (kl >> (W * j)) & 1u;
+                            const int v = static_cast<int>(ci) + W * j;
+                            ow[j] = lrow[kp ? rowshift::old_position(static_cast<uint32_t>(v), dx, dy, dz) : 0u];
+                        }
+                        if (ci == 0u) o = rowshift::shifted_mask(occ, dx, dy, dz);
+                        uint32_t nm = rowshift::lane_first<W>(rowshift::new_mask(dx, dy, dz), ci);
+                        constexpr int NL = (19 + W - 1) / W;      // new voxels per lane at most (a corner)
+                        constexpr int NB = 3;                     // probes in flight per lane: a face crossing is one batch
 #pragma unroll
-                for (int j0 = 0; j0 < NV; j0 += NB) {
+                        for (int j0 = 0; j0 < NL; j0 += NB) {
+                            if (j0 == 0 || nm != 0u) {          // (a later batch only for a lane with voxels left: edges, corners)
+                                int nv[NB];
+                                bool has[NB];
+                                uint32_t sl[NB];
+                                int4 e[NB];
 #pragma unroll
-                    for (int j = j0; j < j0 + NB && j < NV; ++j) {
-                        sl[j] = 0u;
-                        e[j] = make_int4(0, 0, 0, 0);
-                        if (!reuse[j]) start(static_cast<int>(ci) + W * j, sl[j], e[j]);
+                                for (int j = 0; j < NB && j0 + j < NL; ++j) {
+                                    has[j] = nm != 0u;
+                                    nv[j] = has[j] ? static_cast<int>(rowshift::lowest(nm)) : 0;     // (0: never probed, never stored)
+                                    nm = rowshift::lane_next<W>(nm);
+                                    sl[j] = 0u;
+                                    e[j] = make_int4(0, 0, 0, 0);
+                                    if (has[j]) start(nv[j], sl[j], e[j]);
+                                }
+                                if (j0 == 0) {
+                                    // under the loads: the kept words take their new places, C_q is re-summed
+#pragma unroll
+                                    for (int j = 0; j < NV; ++j) {
+                                        if ((kl >> (W * j)) & 1u) {
+                                            lrow[static_cast<int>(ci) + W * j] = ow[j];
+                                            cq += (ow[j] == kEmptySlot) ? 0u : (ow[j] & 255u);
+                                        }
+                                    }
+                                }
+#pragma unroll
+                                for (int j = 0; j < NB && j0 + j < NL; ++j)
+                                    if (has[j]) finish(nv[j], sl[j], e[j]);
+                            }
+                        }
                     }
+                }
+                if (!shifted) {
+                    // the old words of this lane's voxels (LDS is in order within a wave: every read here
+                    // precedes the writes below, also those of the query's other lanes)
+                    uint32_t ow[NV];
+                    bool reuse[NV];
 #pragma unroll
-                    for (int j = j0; j < j0 + NB && j < NV; ++j) {
+                    for (int j = 0; j < NV; ++j) {
                         const int v = static_cast<int>(ci) + W * j;
-                        if (reuse[j]) tally(v, ow[j]);
-                        else finish(v, sl[j], e[j]);
+                        const unsigned a = static_cast<unsigned>(v / 9) + dxu, b = static_cast<unsigned>((v / 3) % 3) + dyu,
+                                       c = static_cast<unsigned>(v % 3) + dzu;
+                        reuse[j] = nearv && v < 27 && a <= 2u && b <= 2u && c <= 2u;
+                        ow[j] = lrow[reuse[j] ? a * 9u + b * 3u + c : 0u];
+                    }
+                    uint32_t sl[NV];
+                    int4 e[NV];
+                    constexpr int NB = PERSIST ? 4 : 3;       // probes in flight per lane (k_icp: its register budget)
+#pragma unroll
+                    for (int j0 = 0; j0 < NV; j0 += NB) {
+#pragma unroll
+                        for (int j = j0; j < j0 + NB && j < NV; ++j) {
+                            sl[j] = 0u;
+                            e[j] = make_int4(0, 0, 0, 0);
+                            if (!reuse[j]) start(static_cast<int>(ci) + W * j, sl[j], e[j]);
+                        }
+#pragma unroll
+                        for (int j = j0; j < j0 + NB && j < NV; ++j) {
+                            const int v = static_cast<int>(ci) + W * j;
+                            if (reuse[j]) tally(v, ow[j]);
+                            else finish(v, sl[j], e[j]);
+                        }
                     }
                 }
                 // the previous answer under the new enumeration, if its voxel is still one of the 27

@@ -590,6 +590,7 @@ __device__ __forceinline__ void chain_wait_pose(const IcpParams &P, uint32_t *sm
 }  // namespace sageicp
 
 // icp_body, the search both k_icp and k_loop run on the queries of a wave; it calls the helpers above
+#include "row_shift.h"
 #include "icp_body.h"
 
 namespace sageicp {
