@@ -81,10 +81,13 @@ __device__ __forceinline__ unsigned icp_wave_of_stripe(const IcpParams &P, int w
 }
 
 // one axis of the face gaps (icp_body): g[0] / g[2] the pre-scaled squared gap to the layer below / above, g[1] = 0
-__device__ __forceinline__ void axis_gaps(double v, int k, double vs, double sc, double (&g)[3]) {
+// (GIVEN, k_loop: `fs` = fl(1e-9 vs) comes from LoopArgs::face_slack — an fp64 literal has to sit in a register pair, and
+// k_loop kept this one in scratch memory across its iteration loop; k_icp forms the product here, as it always did)
+template <bool GIVEN>
+__device__ __forceinline__ void axis_gaps(double v, int k, double vs, double sc, double fs, double (&g)[3]) {
     const double below_hi = static_cast<double>(k <= 0 ? k - 1 : k) * vs;
     const double above_lo = static_cast<double>(k >= 0 ? k + 1 : k) * vs;
-    const double slack = 1e-9 * vs + 1e-13 * fabs(v);
+    const double slack = (GIVEN ? fs : 1e-9 * vs) + 1e-13 * fabs(v);
     const double lo = fmax((v - below_hi) - slack, 0.0);
     const double hi = fmax((above_lo - v) - slack, 0.0);
     g[0] = (lo * lo) * sc;
@@ -230,12 +233,12 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
     }
     const Query s = [&]() {
         if constexpr (PERSIST) {
-            return make_query<(W >= 4)>(f, pose, pose + 9, 1, P.voxel_size, P.inv_voxel_size);
+            return make_query<(W >= 4)>(f, pose, pose + 9, 1, P.voxel_size, P.inv_voxel_size, static_cast<unsigned>(lane));
         } else if constexpr (FUSED) {
             const double *lpose = reinterpret_cast<const double *>(smem + kWgPose);       // the workgroup's copy
-            return make_query<(W >= 4)>(f, lpose, lpose + 9, P.apply_pose, P.voxel_size, P.inv_voxel_size);
+            return make_query<(W >= 4)>(f, lpose, lpose + 9, P.apply_pose, P.voxel_size, P.inv_voxel_size, threadIdx.x);
         } else {
-            return make_query<(W >= 4)>(f, P.st->R, P.st->T + 4, P.apply_pose, P.voxel_size, P.inv_voxel_size);
+            return make_query<(W >= 4)>(f, P.st->R, P.st->T + 4, P.apply_pose, P.voxel_size, P.inv_voxel_size, threadIdx.x);
         }
     }();
     const bool stale = valid && (static_cast<uint32_t>(s.kx) != rk.x || static_cast<uint32_t>(s.ky) != rk.y ||
@@ -430,9 +433,16 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
                 if (ci == 0u) {
                     *reinterpret_cast<uint2 *>(lst + kStKey) = make_uint2(static_cast<uint32_t>(s.kx), static_cast<uint32_t>(s.ky));
                     *reinterpret_cast<uint2 *>(lst + kStKey + 2) = make_uint2(static_cast<uint32_t>(s.kz), o);
+                    lst[kStPrev] = prev.x;         // (re-keyed or dropped: read again below)
                 }
             }
         }
+    }
+    if constexpr (PERSIST) {
+        // k_loop: the previous answer's key is not carried through the rebuild and the scans in a register — the state
+        // record has it (a rebuilt row's lanes have just stored theirs), and whoever needs it reads it there.
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        prev.x = lst[opaque_v(kStPrev)];
     }
     if (!valid) occ = 0u;
 
@@ -445,9 +455,13 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
     double gx[3], gy[3], gz[3];
     {
         const double vs = P.voxel_size, sc = P.prune_scale;
-        axis_gaps(s.x, s.kx, vs, sc, gx);
-        axis_gaps(s.y, s.ky, vs, sc, gy);
-        axis_gaps(s.z, s.kz, vs, sc, gz);
+        double fs = 0.0;
+        // (k_loop's P is LoopArgs::P, the first member of its one argument: the product is read from the kernel-argument
+        // segment here, beside vs and sc — handed down through G it sat in two scalar registers all through the rebuild)
+        if constexpr (PERSIST) fs = reinterpret_cast<const LoopArgs *>(&P)->face_slack;
+        axis_gaps<PERSIST>(s.x, s.kx, vs, sc, fs, gx);
+        axis_gaps<PERSIST>(s.y, s.ky, vs, sc, fs, gy);
+        axis_gaps<PERSIST>(s.z, s.kz, vs, sc, fs, gz);
     }
     NN_T(np, 1);
     LP_T(PERSIST, G, 1);
@@ -818,8 +832,14 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
     if constexpr (PERSIST) {
         // what this block cost: the most points one of its queries was handed (a rebuilt row counts as a few more) —
         // next iteration's order of the workgroup's blocks (k_loop)
+        // (the lane index anew, from it the block's slot in this iteration's order again, and with that where the
+        // query's state record lies: none of them is kept across the scans)
+        lane = lane_now();
+        const unsigned qe = static_cast<unsigned>(lane) >> LW;
+        const unsigned bs = G->perm[G->unit * (QW / 4) + (qe >> 2)];
+        lst = G->state + (bs * 4u + (qe & 3u)) * kLoopStateWords;
         if (valid && ci == 0u)
-            (void)__hip_atomic_fetch_max(G->work + bslot, npairs + (stale ? 48u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            (void)__hip_atomic_fetch_max(G->work + bs, npairs + (stale ? 48u : 0u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
 
     unsigned mkey, woff;
@@ -865,7 +885,7 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
             // map is constant during a call, and the key was carried over if the row was rebuilt):
             // only a query whose answer changed fetches a record, on all of its lanes (one request:
             // the same address), since every lane evaluates the seed.
-            const bool changed = found && mkey != prev.x;
+            const bool changed = found && mkey != lst[opaque_v(kStPrev)];
             g = *reinterpret_cast<const Point4 *>(lst + 8);
             if (__ballot(changed)) {
                 const Point4 t = load_point(pts, changed ? woff : 0u);
@@ -921,7 +941,7 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
         if constexpr (PERSIST) {
             // k_loop: block sums -> exact digits -> the workgroup's accumulators (the rows stay: the scratch
             // is the running wave's own)
-            wave_terms_to_wgacc<LW>(t, pairs, lane, G->red, G->wgacc, kDigitLimitCounted, P.acc_scale);
+            wave_terms_to_wgacc<LW, true>(t, pairs, lane, G->red, G->wgacc, kDigitLimitCounted, P.acc_scale);
             PROBE_LOOP_WAVE_STATS(smem, valid, ci, npairs, stale, lane);
             LP_T(PERSIST, G, 7);
             return;                             // (k_loop closes the workgroup's iteration itself)

@@ -225,6 +225,10 @@ struct LoopParams {
 struct LoopArgs {                  // k_loop's one argument: its passes re-read it from the kernel-argument segment
     IcpParams P;
     LoopParams L;
+    double face_slack;             // fl(1e-9 * P.voxel_size), by launch_loop: the absolute part of the face gaps' slack (icp_body.h,
+                                   // axis_gaps).  k_icp forms the product in every pass from the literal; k_loop had to park that
+                                   // literal, a register pair, in scratch memory across its iteration loop, and takes the product
+                                   // from here, with the pass's other arguments
 };
 #ifndef SAGE_LOOP_OCC
 #define SAGE_LOOP_OCC 7        // waves per SIMD k_loop's register allocation allows (72 registers), i.e. 28 waves per CU

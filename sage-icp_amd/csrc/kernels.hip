@@ -286,9 +286,10 @@ __device__ __forceinline__ int voxel_index(double x, double voxel_size, double i
     }
     return k;
 }
+// (`quad_lane`, QUAD only: the caller's lane index — k_loop derives it anew in every pass, icp_body)
 template <bool QUAD = false>
 __device__ __forceinline__ Query make_query(const Point4 &f, const double *R, const double *t, int apply_pose,
-                                            double voxel_size, double inv_vs = 0.0) {
+                                            double voxel_size, double inv_vs = 0.0, unsigned quad_lane = 0u) {
     Query q;
     q.x = f.x; q.y = f.y; q.z = f.z; q.l = f.l;
     if (apply_pose) {
@@ -297,7 +298,7 @@ __device__ __forceinline__ Query make_query(const Point4 &f, const double *R, co
         q.z = R[6] * f.x + R[7] * f.y + R[8] * f.z + t[2];
     }
     if constexpr (QUAD) {
-        const unsigned a = threadIdx.x & 3u;
+        const unsigned a = quad_lane & 3u;
         const double num = a == 0u ? q.x : (a == 1u ? q.y : q.z);
         const unsigned k = static_cast<unsigned>(voxel_index(num, voxel_size, inv_vs));
         q.kx = static_cast<int>(dpp_u32<0x00>(k));       // quad_perm [0,0,0,0]
@@ -403,12 +404,25 @@ __device__ __forceinline__ double lane_shl_f64(double v) {
     if constexpr (N < 16) return dpp_f64<0x100 + N>(v);
     else return __shfl_down(v, N, 64);
 }
+// ... for k_loop: `lane` is the caller's lane index, derived inside the iteration loop — __shfl_down takes its own from a
+// builtin the compiler hoists out of that loop and keeps.  (Lanes whose partner would lie beyond the wave get another
+// lane's value instead of their own: their results are not used.)
+template <int N>
+__device__ __forceinline__ double lane_shl_f64_at(double v, int lane) {
+    if constexpr (N < 16) {
+        return dpp_f64<0x100 + N>(v);
+    } else {
+        const int a = ((lane + N) & 63) << 2;
+        const int lo = __builtin_amdgcn_ds_bpermute(a, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(a, __double2hiint(v));
+        return __hiloint2double(hi, lo);
+    }
+}
 
 // A wave's 16 pair terms per query -> block sums -> digits -> added into the workgroup's accumulators `wgacc`
 // (LDS, kWgAccWords 64-bit words).  The terms are spread over the W lanes of a query: lane ci holds components
 // ci K .. ci K + K - 1 (K = 16 / W; zeros for a query without a pair).  `red` = LDS scratch of this wave, 16 fp64
 // per block.
-template <int LW>
+template <int LW, bool FRESH = false>
 __device__ __forceinline__ void wave_terms_to_wgacc(const double (&t)[kCount >> LW], unsigned pairs, int lane, double *red,
                                                     unsigned long long *wgacc, double limit, double scale) {
     constexpr int W = 1 << LW, QW = 64 >> LW, NBLK = QW / 4, K = kCount >> LW;
@@ -416,8 +430,13 @@ __device__ __forceinline__ void wave_terms_to_wgacc(const double (&t)[kCount >> 
     double y[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const double x = t[k] + lane_shl_f64<W>(t[k]);
-        y[k] = x + lane_shl_f64<2 * W>(x);
+        if constexpr (FRESH) {
+            const double x = t[k] + lane_shl_f64_at<W>(t[k], lane);
+            y[k] = x + lane_shl_f64_at<2 * W>(x, lane);
+        } else {
+            const double x = t[k] + lane_shl_f64<W>(t[k]);
+            y[k] = x + lane_shl_f64<2 * W>(x);
+        }
     }
     // B. four blocks at a time (512 B of scratch whatever the lanes per query): the lanes of the blocks' first
     // queries park their K sums each (component-major: the block's 16 in order), C. lane (c, j) = (lane >> 2,
@@ -453,6 +472,29 @@ __device__ __forceinline__ void wave_terms_to_wgacc(const double (&t)[kCount >> 
         (void)__hip_atomic_fetch_add(wgacc + 3 * kCount, static_cast<unsigned long long>(pairs), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// The lane index, derived anew: what the compiler can trace to threadIdx it knows to be the same in every iteration
+// of a loop inside the kernel (k_loop's, the solving wave's), and it would keep every select mask and address made
+// from it alive across that loop — in registers the pass needs, or in scratch.
+__device__ __forceinline__ int lane_now() {
+    unsigned l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return static_cast<int>(l);
+}
+// A wave-uniform value of the set-up (k_loop: its wave, its units, its workgroup's index) as the iteration loop uses
+// it: the value stays in its scalar register, what is derived from it is derived where it is used — behind this the
+// compiler cannot see that it is the same in every iteration.
+__device__ __forceinline__ unsigned opaque_s(unsigned x) {
+    asm volatile("" : "+s"(x));
+    return x;
+}
+
+// ... and an LDS index behind which a word is read AGAIN instead of being carried in a register from its first read
+// (an index, not a pointer or a volatile access: either would lose the LDS address space and read through flat memory)
+__device__ __forceinline__ unsigned opaque_v(unsigned x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
 // The workgroup's accumulators (LDS) -> the shared ones: lane l sends word l (digit l % 3 of value l / 3) as ONE
 // fire-and-forget 64-bit integer atomic into the copy `dst`, and clears the word for the next iteration.
 // COUNTED (k_loop): every word also counts its contributions — a workgroup adds (digit << 8) + 1, the low
@@ -462,14 +504,22 @@ __device__ __forceinline__ void wave_terms_to_wgacc(const double (&t)[kCount >> 
 // one of eight counters — ran an iteration in the same time, profiles/r04/loop_times_counted_words.txt against
 // loop_times_xcd_stripes_rowshift.txt: this one is kept for having one protocol less and no ordering
 // assumption at all.)
-template <bool COUNTED = false>
+// FRESH (k_loop, inside its iteration loop): the lane index is derived here (lane_now) and the zero that clears the
+// words is made here — neither lives across the loop.
+template <bool COUNTED = false, bool FRESH = false>
 __device__ __forceinline__ void wgacc_flush(unsigned long long *wgacc, long long *dst, long long *overflow) {
-    const int lane = static_cast<int>(threadIdx.x & 63u);
+    const int lane = FRESH ? lane_now() : static_cast<int>(threadIdx.x & 63u);
     const int l = min(lane, static_cast<int>(kWgAccWords) - 1);
     const long long x = static_cast<long long>(wgacc[l]);
     const bool ok = wgacc[kWgAccWords - 1] == 0ull;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if (lane < static_cast<int>(kWgAccWords)) wgacc[lane] = 0ull;
+    unsigned long long zero = 0ull;
+    if constexpr (FRESH) {
+        unsigned zl, zh;
+        asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0" : "=v"(zl), "=v"(zh));
+        zero = (static_cast<unsigned long long>(zh) << 32) | zl;
+    }
+    if (lane < static_cast<int>(kWgAccWords)) wgacc[lane] = zero;
     if constexpr (COUNTED) {
         // (the overflow travels IN the counted words: word 3 kAccValues of the copy counts its workgroups like the
         // others and carries, as its "digit", how many of them overflowed — whoever finds the counts complete has
@@ -548,8 +598,7 @@ struct LoopLds {
 // workgroup through LDS.  smem[kWgGo] != 0: the workgroup leaves — the loop ended before this iteration (the done granule
 // carries an older tag, or this tag with its done word set), or a wait timed out somewhere.
 // Which of the kLoopPoseCopies copies of the pose workgroup b looks at (kernels.h): its XCD's by default.
-__device__ __forceinline__ unsigned loop_pose_copy(int pose_map) {
-    const unsigned b = blockIdx.x;
+__device__ __forceinline__ unsigned loop_pose_copy(int pose_map, unsigned b = blockIdx.x) {
     return pose_map == 1 ? 0u : ((pose_map == 2 ? b + 3u : b) & static_cast<unsigned>(kLoopPoseCopies - 1));
 }
 __device__ __forceinline__ void chain_wait_pose(const IcpParams &P, uint32_t *smem, int lane) {
@@ -844,6 +893,7 @@ void launch_loop(const IcpParams &p, const LoopParams &l, int lw, hipStream_t s)
     LoopArgs a;
     a.P = p;
     a.L = l;
+    a.face_slack = 1e-9 * p.voxel_size;        // (one IEEE product of the same two numbers, here as in k_icp's passes)
     void *args[] = {&a};
 #ifdef SAGE_LOOP_INGRID
     (void)hipLaunchKernel(loop_kernel(lw, p.filter != 0), dim3(l.wgs + 1), dim3(64 * l.nw), args, lds, s);

@@ -98,13 +98,6 @@ __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v,
     const unsigned hi = static_cast<unsigned>(__builtin_amdgcn_readlane(static_cast<int>(static_cast<unsigned>(v >> 32)), src));
     return (static_cast<unsigned long long>(hi) << 32) | lo;
 }
-// The lane index, derived anew: what the compiler can trace to threadIdx it knows to be the same in every iteration
-// of the solving wave's loop, and it would keep every select mask and address made from it alive across the solve.
-__device__ __forceinline__ int lane_now() {
-    unsigned l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return static_cast<int>(l);
-}
 // The solving wave gives the loop up at iteration `it` (tag = it + 1: its own wait timed out, somebody raised the abort
 // word, or — `peer` — a peer GPU gave up at this exchange).  `sh`, `st`: L.sh and L.st as the caller holds them (read
 // from L again they cost the solving kernels scalar loads).  Writes: the abort word, which every workgroup's wait looks at;
@@ -368,6 +361,7 @@ void k_loop(LoopArgs A) {
     constexpr int QW = 64 >> LW;
     const IcpParams &P = A.P;
     const LoopParams &L = A.L;
+    // (set-up only; the iteration loop below takes what it needs of this from its arguments and through opaque_s)
     const int wv = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
     const int nw = L.nw;
     const unsigned gpw = static_cast<unsigned>(L.gpw);
@@ -428,15 +422,13 @@ void k_loop(LoopArgs A) {
         g0 = lo + idx * base + min(idx, extra);
         gcnt = min(gpw, base + (idx < extra ? 1u : 0u));
     }
-    unsigned long long *wgacc = reinterpret_cast<unsigned long long *>(smem + kLpAcc);
     constexpr unsigned BPW = QW / 4;                                  // blocks of four queries per pass
-    const unsigned nblk_max = gpw * BPW, nblk = gcnt * BPW;
-    const LoopLds<unsigned> lds(LW, static_cast<unsigned>(nw), gpw);  // (kernels.hip: the one description of this LDS)
-    uint32_t *perm = smem + lds.perm;
-    uint32_t *work = smem + lds.work;
-    uint32_t *rows = smem + lds.rows;
-    uint32_t *state = smem + lds.state;
-    double *red = reinterpret_cast<double *>(smem + lds.red + static_cast<unsigned>(wv) * loop_red_words());
+    // (set-up only, like nw and gpw: the iteration loop lays the LDS out again from its arguments)
+    const unsigned nblk_max = gpw * BPW;
+    const LoopLds<unsigned> lds0(LW, static_cast<unsigned>(nw), gpw); // (kernels.hip: the one description of this LDS)
+    uint32_t *perm0 = smem + lds0.perm;
+    uint32_t *work0 = smem + lds0.work;
+    uint32_t *state0 = smem + lds0.state;
 
     // ---- set-up: the initial pose, the state records of the groups' queries --------------------------
     if (threadIdx.x < 9) s_pose[threadIdx.x] = P.st->R[threadIdx.x];
@@ -458,14 +450,14 @@ void k_loop(LoopArgs A) {
     }
     for (unsigned i = threadIdx.x; i < 2u * kWgAccWords; i += blockDim.x) smem[kLpAcc + i] = 0u;
     for (unsigned i = threadIdx.x; i < nblk_max; i += blockDim.x) {
-        perm[i] = i;                           // the order of the frame, until the blocks' work is known
-        work[i] = 0u;
+        perm0[i] = i;                          // the order of the frame, until the blocks' work is known
+        work0[i] = 0u;
     }
     for (unsigned sl = threadIdx.x; sl < gcnt * QW; sl += blockDim.x) {
         const unsigned q = g0 * QW + sl;       // slot sl of this workgroup
         const Point4 f = P.frame[q < static_cast<unsigned>(P.n) ? q : 0u];
         {
-            uint32_t *lst = state + sl * kLoopStateWords;
+            uint32_t *lst = state0 + sl * kLoopStateWords;
             *reinterpret_cast<Point4 *>(lst) = f;
             Point4 z;
             z.x = z.y = z.z = z.l = 0.0;
@@ -498,57 +490,68 @@ void k_loop(LoopArgs A) {
         }
         __syncthreads();
     }
+    // who this wave is, in ONE scalar for the loop below: the workgroup's index and, in the low three bits, its wave
+    static_assert(kLoopMaxWaves <= 8, "k_loop keeps the wave's index in three bits");
+    const unsigned who = (blockIdx.x << 3) | static_cast<unsigned>(wv);
     PROBE_LOOP_BEGIN(lp);
 
+    // THE RULE of the iteration loop: nothing derived from threadIdx or blockIdx, and no predicate, offset or pointer
+    // derived from the set-up's scalars, is used inside it.  Three scalars cross it as VALUES — `who`, `g0` and `gcnt`,
+    // each read through opaque_s where it is used —; the lane index is lane_now() at every use; nw, gpw and the LDS
+    // layout come from the arguments, re-read where they are needed (scalar loads from the constant cache, as a wave of
+    // k_icp does at its start).  What the compiler can prove invariant it hoists in front of the loop and keeps alive
+    // across the pass: at 72 registers that meant 48 B of scratch and 32 scalars parked in a register's lanes, reloaded
+    // inside the pass or not as the allocation fell (5 % of c2, profiles/r20/README.md).  tests/test_loop_resources.py
+    // holds the kernels at no scratch.  (icp_body follows the same rule for the values of a pass: icp_body.h.)
+
     for (int it = 0;; ++it) {
-        // Every iteration (and every pass of the body) re-reads its arguments from the kernel-argument
-        // segment — scalar loads from the constant cache, as a wave of k_icp does at its start — and
-        // re-derives its lane index: values the compiler knows to be invariant across this loop it would
-        // hoist out of it and keep alive, ~50 scalars and a dozen vector registers the scan needs.
         auto ka = __builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(ka));
-        const LoopArgs &K = *(const LoopArgs *)(ka);
-        const LoopParams &L = K.L;
-        LoopShared *sh = L.sh;
-        unsigned lane_u;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_u));
-        const int lane = static_cast<int>(lane_u);
         // the workgroup's groups, first come first served: a wave held up by a heavy query takes fewer
-        bool dealt = L.deal != 0;
+        bool dealt = ((const LoopArgs *)(ka))->L.deal != 0;
         for (;;) {
             unsigned gi = 0u;
             if (dealt) {
                 // (this wave's first unit is fixed by where it sits; the units beyond one per wave go first come first served)
                 dealt = false;
-                gi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(smem[kLpFirst + static_cast<unsigned>(wv)])));
-                if (gi >= gcnt) continue;
+                gi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(smem[kLpFirst + (opaque_s(who) & 7u)])));
+                if (gi >= opaque_s(gcnt)) continue;
             } else {
-                if (lane == 0)
+                if (lane_now() == 0)
                     gi = __hip_atomic_fetch_add(&smem[kLpNext], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 gi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(gi)));
-                if (gi >= gcnt) break;
+                if (gi >= opaque_s(gcnt)) break;
             }
-            if (L.prio) loop_set_priority(gi, nw, L.prio);
-            PROBE_LOOP_UNIT_BEGIN(it, gi, nw, t_unit);
+            // (the pass's arguments, and where the workgroup's LDS lies, from the kernel-argument segment: see above)
+            auto kb = __builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(kb));
+            const LoopArgs &B = *(const LoopArgs *)(kb);
+            if (B.L.prio) loop_set_priority(gi, B.L.nw, B.L.prio);
+            PROBE_LOOP_UNIT_BEGIN(it, gi, B.L.nw, t_unit);
+            const LoopLds<unsigned> lds(LW, static_cast<unsigned>(B.L.nw), static_cast<unsigned>(B.L.gpw));
+            const unsigned first = opaque_s(g0);
             LoopGroup G;
-            G.rows = rows;
-            G.state = state;
-            G.perm = perm;
-            G.work = work;
+            G.rows = smem + lds.rows;
+            G.state = smem + lds.state;
+            G.perm = smem + lds.perm;
+            G.work = smem + lds.work;
             G.unit = gi;
-            G.red = red;
-            G.wgacc = wgacc;
-            G.q_first = g0 * QW;
-            G.slot = g0 + gi;
+            G.red = reinterpret_cast<double *>(smem + lds.red + (opaque_s(who) & 7u) * loop_red_words());
+            G.wgacc = reinterpret_cast<unsigned long long *>(smem + kLpAcc);
+            G.q_first = first * QW;
+            G.slot = first + gi;
             PROBE_LOOP_PASS_BEGIN(lp, G);
-            {
-                auto kb = __builtin_amdgcn_kernarg_segment_ptr();
-                asm volatile("" : "+s"(kb));
-                icp_body<LW, true, FILT, true>(((const LoopArgs *)(kb))->P, smem, &G, s_pose);
-            }
-            PROBE_LOOP_UNIT_END(lp, G, it, gi, nw, wv, lane, t_unit);
+            icp_body<LW, true, FILT, true>(B.P, smem, &G, s_pose);
+            PROBE_LOOP_UNIT_END(lp, G, it, gi, B.L.nw, static_cast<int>(opaque_s(who) & 7u), lane_now(), t_unit);
         }
         PROBE_LOOP_MARK(t_a);
+        // the close: its arguments and its lane index anew (nothing of the passes' is kept for it)
+        auto kc = __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kc));
+        const LoopParams &L = ((const LoopArgs *)(kc))->L;
+        LoopShared *sh = L.sh;
+        const int lane = lane_now();
+        const unsigned me = opaque_s(who), wg = me >> 3;
         // (what the ticket orders — the groups' sums — lives in LDS, which serves a CU's waves in order)
         unsigned prior = 0u;
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
@@ -556,19 +559,23 @@ void k_loop(LoopArgs A) {
             prior = __hip_atomic_fetch_add(&smem[kLpArrive], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __atomic_signal_fence(__ATOMIC_SEQ_CST);
         prior = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(prior)));
-        const bool last = prior == static_cast<unsigned>(nw) - 1u;
+        const bool last = prior == static_cast<unsigned>(L.nw) - 1u;
         if (last) {
             // this wave closes the workgroup's iteration
-            wgacc_flush<true>(wgacc, &sh->acc[it & 1][blockIdx.x & (kLoopReplicas - 1)][0], &sh->acc[it & 1][0][kAccWords - 1]);
+            wgacc_flush<true, true>(reinterpret_cast<unsigned long long *>(smem + kLpAcc), &sh->acc[it & 1][wg & (kLoopReplicas - 1)][0],
+                                    &sh->acc[it & 1][0][kAccWords - 1]);
             if (lane == 0) {                   // everybody is in: ready for the next iteration
                 smem[kLpArrive] = 0u;
-                smem[kLpNext] = L.deal ? static_cast<unsigned>(nw) : 0u;
+                smem[kLpNext] = L.deal ? static_cast<unsigned>(L.nw) : 0u;
             }
             // The next iteration's order of the workgroup's blocks: heaviest first, by what they cost in this one (a
             // rank sort on one wave: lane i counts the blocks that go before block i).  Blocks of like work then
             // share a wave — whose pass lasts as long as its heaviest query — and the heaviest waves start first.
             // (Which blocks share a wave does not reach the sums: they are exact from the block on.)
+            const unsigned nblk = opaque_s(gcnt) * BPW;
             if (nblk <= 64u && nblk > BPW) {
+                const LoopLds<unsigned> lds(LW, static_cast<unsigned>(L.nw), static_cast<unsigned>(L.gpw));
+                uint32_t *perm = smem + lds.perm, *work = smem + lds.work;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 const unsigned i = static_cast<unsigned>(lane);
                 const unsigned wi = i < nblk ? work[i] : 0u;
@@ -586,14 +593,14 @@ void k_loop(LoopArgs A) {
             PROBE_LOOP_WG_INFO(smem, it, lane);
             LOOP_STAMP_WG(it, 0);
         }
-        if (wv == 0) {
+        if ((me & 7u) == 0u) {
             // the next pose, for this workgroup
             const unsigned long long tag = static_cast<unsigned long long>(it) + 1ull;
             const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
             unsigned long long g = tag << 32;
             bool aborted = false;
             for (;;) {
-                if (lane < kLoopPoseGranules) g = ld_agent(&sh->pose[loop_pose_copy(L.pose_map)][lane]);
+                if (lane < kLoopPoseGranules) g = ld_agent(&sh->pose[loop_pose_copy(L.pose_map, wg)][lane]);
                 const bool ok = (g >> 32) == tag;
                 if (__all(ok)) break;
                 unsigned long long ab = 0ull;
