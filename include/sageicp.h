@@ -64,7 +64,10 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * in device memory — sageicp_device_points, sageicp_pipeline_source, sageicp_pipeline_source_device,
  * sageicp_map_pointcloud_device; then key-frame selection — sageicp_occupancy_params, sageicp_key_frame_info,
  * sageicp_pipeline_set_key_frames, sageicp_pipeline_key_frame_reset / _info / _grid / _grid_device,
- * sageicp_occupancy_grid, sageicp_occupancy_grid_device (additions only: no existing struct or entry changed). */
+ * sageicp_occupancy_grid, sageicp_occupancy_grid_device; then PointCloud2 payloads — sageicp_msg_layout, sageicp_msg_colors,
+ * SAGEICP_MSG_*, sageicp_pipeline_register_frame_msg / _msg_device, sageicp_pipeline_source_msg / _msg_device,
+ * sageicp_map_pointcloud_msg / _msg_device, sageicp_msg_output_fields (additions only: no existing struct or entry
+ * changed). */
 #define SAGEICP_ABI_VERSION 4
 
 /* Filled by sageicp_register_frame*.  Times are microseconds. */
@@ -592,6 +595,92 @@ int sageicp_occupancy_grid(const double *xyzl, uint64_t n, const double pose[7] 
 int sageicp_occupancy_grid_device(const sageicp_device_frame *frame, const double pose[7] /* NULL = identity */,
                                   const sageicp_occupancy_params *params, uint8_t *grid_out,
                                   void *stream /* hipStream_t; NULL = null stream */);
+
+/* ---- sensor_msgs/PointCloud2 payloads (msg.hip): the odometry node's two message conversions ---------------------------
+ * ros/ros2/Utils.hpp:55-198 on the device (additions only, the ABI version stays): PointCloud2ToEigen + GetTimestamps
+ * at the input (OdometryServer.cpp:160-167), EigenToPointCloud2 at the two outputs (:214, :219).  Little-endian only.
+ *
+ * Input.  An incoming message's `data` as n = height * width records of point_step bytes (the reference's iterators
+ * step by point_step and ignore row_step; so does this).  x, y, z are FLOAT32, the label UINT8 or FLOAT32, the stamp
+ * uint32 or float64, each at any byte offset; neither `data` nor point_step need be a multiple of 4.  Every value
+ * becomes a double through a plain cast.  uint32 stamps follow NormalizeTimestamps (Utils.hpp:68-77): with their maximum
+ * below 1 (all zero) they stay as cast, otherwise each is (double)t / (double)max, an fp64 division; float64 stamps
+ * pass through unchanged. */
+typedef struct sageicp_msg_layout {      /* an incoming PointCloud2's fields, as PointCloud2ToEigen / GetTimestamps read them */
+    uint32_t point_step;                 /* bytes between points; every field used ends within it; at most 1024 */
+    uint32_t x_offset, y_offset, z_offset;   /* FLOAT32 */
+    uint32_t label_offset;  int32_t label_dtype;   /* SAGEICP_DTYPE_UINT8 or _FLOAT32 */
+    int32_t  time_kind;                  /* 0 none; 1 uint32, normalised by its maximum; 2 float64 as is */
+    uint32_t time_offset;
+} sageicp_msg_layout;
+/* the node's color_list (std::map<int, int>): n (key, value) pairs; a later pair with the same key wins */
+typedef struct sageicp_msg_colors { const int32_t *keys, *values; uint32_t n; } sageicp_msg_colors;
+/* sageicp_pipeline_register_frame of a message in host memory: the n * point_step raw bytes cross PCIe (not 32-byte
+ * rows) and are unpacked into the pipeline's buffers on its stream.
+ * From the point where the rows are on the device the frame is treated as sageicp_pipeline_register_frame_device treats
+ * a device frame — key frames on the raw rows, the dynamic filter, an announcement of sageicp_pipeline_prefetch consumed,
+ * the non-finite checks — and the pose is bit for bit what the same values give as host rows.
+ * Deskew off: the time field is never read, whatever time_kind says (OdometryServer.cpp:161-164).
+ * Deskew on and time_kind == 0: SAGEICP_ERR_INVALID, no pose pushed.
+ * Deskew on with stamps: they are read and checked on every frame, as sageicp_pipeline_register_frame_timestamps does
+ * (a float64 stamp that is not finite: SAGEICP_ERR_INVALID, no pose pushed).
+ * n == 0 is a valid empty frame and reads nothing (the reference's max_element of no stamps is undefined).
+ * Refused before anything is enqueued and without needing a device (SAGEICP_ERR_INVALID): a NULL layout; point_step 0
+ * or above 1024; a field that ends beyond point_step; a label_dtype or time_kind other than the above;
+ * data_bytes < n * point_step (the reference would read out of bounds); n > 2^26 - 4; NULL data with n > 0. */
+int sageicp_pipeline_register_frame_msg(sageicp_pipeline *p, const void *data, uint64_t data_bytes, uint64_t n,
+                                        const sageicp_msg_layout *layout, double pose_out[7], double *icp_seconds,
+                                        double *total_seconds, uint64_t *n_source, sageicp_stats *stats /* optional */);
+/* the same of a message whose data is in the caller's device memory, with sageicp_device_frame's checks and stream
+ * rules: the first and the last byte of the n * point_step extent must be device memory of the pipeline's device (host,
+ * pinned and managed memory are refused, not copied); the read is ordered behind the work on `stream`; synchronous. */
+int sageicp_pipeline_register_frame_msg_device(sageicp_pipeline *p, const void *data, uint64_t data_bytes, uint64_t n,
+                                               const sageicp_msg_layout *layout,
+                                               void *stream /* hipStream_t; NULL = null stream */, double pose_out[7],
+                                               double *icp_seconds, double *total_seconds, uint64_t *n_source,
+                                               sageicp_stats *stats /* optional */);
+/* Output.  The record CreatePointCloud2Msg + FillPointCloud2XYZlRGB write (Utils.hpp:104-145), point_step 21:
+ *   bytes 0-11  x, y, z as (float) casts          byte 12  the label as uint8
+ *   bytes 13-16 rgb: the colour of (int)label, the table's int converted to uint32_t
+ *   bytes 17-20 zero (the bytes data.resize leaves)
+ * Label rule: trunc(label) must lie in [0, 255] (-0.5 gives 0; 256 does not fit: where static_cast<uint8_t> is defined).
+ * Colour rule: the table must hold a colour for (int)label (the reference's map::at throws where it does not); keys
+ * outside 0..255 can never match and are ignored.  A row that breaks either rule makes the call SAGEICP_ERR_INVALID, and
+ * the destination's contents are then unspecified. */
+#define SAGEICP_MSG_POINT_STEP 21
+#define SAGEICP_MSG_X_OFFSET 0
+#define SAGEICP_MSG_Y_OFFSET 4
+#define SAGEICP_MSG_Z_OFFSET 8
+#define SAGEICP_MSG_LABEL_OFFSET 12
+#define SAGEICP_MSG_RGB_OFFSET 13
+/* sensor_msgs/PointField datatype codes */
+#define SAGEICP_MSG_FIELD_UINT8 2
+#define SAGEICP_MSG_FIELD_UINT32 6
+#define SAGEICP_MSG_FIELD_FLOAT32 7
+#define SAGEICP_MSG_FIELD_FLOAT64 8
+typedef struct sageicp_msg_field { char name[8]; uint32_t offset; int32_t datatype; uint32_t count; } sageicp_msg_field;
+/* the outgoing record's field table (x, y, z, label, rgb), for msg.fields: returns the number of fields, writes the
+ * first min(cap, that) of them.  No device needed. */
+uint32_t sageicp_msg_output_fields(sageicp_msg_field *out, uint32_t cap);
+/* sageicp_pipeline_source's rows, in its order, as 21-byte records in host memory: *n_out is the number of rows there
+ * are, the first min(cap_points, n) are written (min(cap_points, n) * 21 bytes, no byte beyond them).  out may be NULL
+ * only when cap_points == 0.  colors: NULL or n == 0 is an empty table; n > 0 with a NULL array is refused. */
+int sageicp_pipeline_source_msg(const sageicp_pipeline *p, const sageicp_msg_colors *colors, void *out,
+                                uint64_t cap_points, uint64_t *n_out);
+/* the same into the caller's device memory (any alignment), with sageicp_device_points' checks and stream rules: the
+ * extent of cap_points * 21 bytes must be device memory of the handle's device; ordered behind the work on `stream`;
+ * synchronous */
+int sageicp_pipeline_source_msg_device(const sageicp_pipeline *p, const sageicp_msg_colors *colors, void *out,
+                                       uint64_t cap_points, void *stream /* hipStream_t; NULL = null stream */,
+                                       uint64_t *n_out);
+/* sageicp_map_pointcloud's rows, in its order (the bucket order in reference-order mode), as 21-byte records: packed on
+ * the device from the HBM copy while it is the authority, staged from the host copy while it is not (as
+ * sageicp_map_pointcloud_device); either way the records are written on the device */
+int sageicp_map_pointcloud_msg(const sageicp_map *map, const sageicp_msg_colors *colors, void *out, uint64_t cap_points,
+                               uint64_t *n_out);
+int sageicp_map_pointcloud_msg_device(const sageicp_map *map, const sageicp_msg_colors *colors, void *out,
+                                      uint64_t cap_points, void *stream /* hipStream_t; NULL = null stream */,
+                                      uint64_t *n_out);
 
 /* ---- KITTI trajectory metrics: sage_icp::metrics (metrics/Metrics.hpp:33-37) ----------------------
  * Host-only (the reference's are CPU code too).  Poses are 4x4 homogeneous matrices, ROW-major

@@ -120,6 +120,26 @@ class DevicePoints(C.Structure):
                 ("label", C.c_void_p), ("label_stride", C.c_uint64), ("cap", C.c_uint64)]
 
 
+class MsgLayout(C.Structure):
+    """sageicp_msg_layout: an incoming PointCloud2's fields as PointCloud2ToEigen / GetTimestamps read them"""
+    _fields_ = [("point_step", C.c_uint32), ("x_offset", C.c_uint32), ("y_offset", C.c_uint32), ("z_offset", C.c_uint32),
+                ("label_offset", C.c_uint32), ("label_dtype", C.c_int32), ("time_kind", C.c_int32),
+                ("time_offset", C.c_uint32)]
+
+
+class MsgColors(C.Structure):
+    """sageicp_msg_colors: the node's color_list as (key, value) pairs"""
+    _fields_ = [("keys", C.POINTER(C.c_int32)), ("values", C.POINTER(C.c_int32)), ("n", C.c_uint32)]
+
+
+class MsgField(C.Structure):
+    """sageicp_msg_field: one entry of the outgoing record's field table"""
+    _fields_ = [("name", C.c_char * 8), ("offset", C.c_uint32), ("datatype", C.c_int32), ("count", C.c_uint32)]
+
+
+MSG_POINT_STEP = 21      # SAGEICP_MSG_POINT_STEP
+
+
 class OccupancyParams(C.Structure):
     """sageicp_occupancy_params: the bird's-eye grid of key-frame selection (bounds of x, y, z; H rows, W columns)"""
     _fields_ = [("bounds", (C.c_double * 2) * 3), ("occ_h", C.c_int32), ("occ_w", C.c_int32), ("overlap_th", C.c_double)]
@@ -282,6 +302,18 @@ _SIGNATURES = [
     ("sageicp_occupancy_grid", C.c_int, [_dp, C.c_uint64, _dp, C.POINTER(OccupancyParams), C.c_void_p, C.c_int]),
     ("sageicp_occupancy_grid_device", C.c_int,
      [C.POINTER(DeviceFrame), _dp, C.POINTER(OccupancyParams), C.c_void_p, C.c_void_p]),
+    ("sageicp_pipeline_register_frame_msg", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(MsgLayout), _dp, _dp, _dp, _u64p, C.POINTER(Stats)]),
+    ("sageicp_pipeline_register_frame_msg_device", C.c_int,
+     [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(MsgLayout), C.c_void_p, _dp, _dp, _dp, _u64p,
+      C.POINTER(Stats)]),
+    ("sageicp_msg_output_fields", C.c_uint32, [C.POINTER(MsgField), C.c_uint32]),
+    ("sageicp_pipeline_source_msg", C.c_int, [C.c_void_p, C.POINTER(MsgColors), C.c_void_p, C.c_uint64, _u64p]),
+    ("sageicp_pipeline_source_msg_device", C.c_int,
+     [C.c_void_p, C.POINTER(MsgColors), C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
+    ("sageicp_map_pointcloud_msg", C.c_int, [C.c_void_p, C.POINTER(MsgColors), C.c_void_p, C.c_uint64, _u64p]),
+    ("sageicp_map_pointcloud_msg_device", C.c_int,
+     [C.c_void_p, C.POINTER(MsgColors), C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
     ("sageicp_pipeline_create", C.c_void_p, [C.POINTER(PipelineConfig)]),
     ("sageicp_pipeline_destroy", None, [C.c_void_p]),
     ("sageicp_pipeline_register_frame", C.c_int,
@@ -507,6 +539,177 @@ def _rows_out(device_index, count, host_rows, device_call, device, dtype, out, l
     return out[:k] if labels_out is None else (out[:k], labels_out[:k])
 
 
+# ---- sensor_msgs/PointCloud2 (sageicp_msg_layout) ---------------------------------------------------------
+class PointField:
+    """sensor_msgs/PointField: a plain container with the message's attribute names and datatype codes"""
+    INT8, UINT8, INT16, UINT16, INT32, UINT32, FLOAT32, FLOAT64 = 1, 2, 3, 4, 5, 6, 7, 8
+
+    def __init__(self, name, offset, datatype, count=1):
+        self.name, self.offset, self.datatype, self.count = name, int(offset), int(datatype), int(count)
+
+    def __repr__(self):
+        return "PointField(%r, %d, %d, %d)" % (self.name, self.offset, self.datatype, self.count)
+
+
+class PointCloud2:
+    """sensor_msgs/PointCloud2 without ROS: a plain container, for tests and callers that have no rclpy.  Anything with
+    these attributes (rclpy's message among them) is taken wherever this is.  data: bytes, a bytearray, an array('B'), a
+    numpy uint8 array, or a 1-D uint8 torch tensor on the pipeline's GPU."""
+
+    def __init__(self, fields, point_step, data, width=None, height=1, is_bigendian=False, row_step=None, header=None):
+        self.header = header
+        self.fields = list(fields)
+        self.point_step = int(point_step)
+        self.height = int(height)
+        self.width = int(width) if width is not None else (len(data) // self.point_step if self.point_step else 0)
+        self.row_step = int(row_step) if row_step is not None else self.width * self.point_step
+        self.is_bigendian = bool(is_bigendian)
+        self.is_dense = True
+        self.data = data
+
+
+_FIELD_TYPE_NAMES = {1: "INT8", 2: "UINT8", 3: "INT16", 4: "UINT16", 5: "INT32", 6: "UINT32", 7: "FLOAT32", 8: "FLOAT64"}
+NO_TIME_FIELD = "Field 't', 'timestamp', or 'time'  does not exist"      # GetTimestampField's text, ros/ros2/Utils.hpp:63
+
+
+def _is_message(x):
+    return hasattr(x, "fields") and hasattr(x, "point_step") and hasattr(x, "data")
+
+
+def _field_as(field, datatype, why=""):
+    if int(field.datatype) != datatype:
+        raise ValueError("field '%s' is declared %s; it is read as %s%s (the reference would reinterpret its bytes)"
+                         % (field.name, _FIELD_TYPE_NAMES.get(int(field.datatype), "datatype %d" % field.datatype),
+                            _FIELD_TYPE_NAMES[datatype], why))
+    return int(field.offset)
+
+
+def pointcloud2_layout(msg, want_time):
+    """The MsgLayout of a PointCloud2 by the reference's field-name rules: x, y, z and label by name (the
+    first of a name, as sensor_msgs' iterators take it), FLOAT32 each, the label UINT8 when the message has exactly five
+    fields; with want_time the LAST field named t, timestamp (UINT32) or time (FLOAT64).  ValueError names what does
+    not fit; a big-endian message is refused."""
+    if getattr(msg, "is_bigendian", False):
+        raise ValueError("a big-endian PointCloud2 is not supported")
+    fields = list(msg.fields)
+
+    def named(name):
+        for f in fields:
+            if f.name == name:
+                return f
+        raise ValueError("Field %s does not exist" % name)
+
+    lay = MsgLayout()
+    lay.point_step = int(msg.point_step)
+    lay.x_offset = _field_as(named("x"), PointField.FLOAT32)
+    lay.y_offset = _field_as(named("y"), PointField.FLOAT32)
+    lay.z_offset = _field_as(named("z"), PointField.FLOAT32)
+    if len(fields) == 5:            # the fields.size() == 5 switch of PointCloud2ToEigen, Utils.hpp:167
+        lay.label_offset = _field_as(named("label"), PointField.UINT8, " in a message of exactly five fields")
+        lay.label_dtype = DTYPE_UINT8
+    else:
+        lay.label_offset = _field_as(named("label"), PointField.FLOAT32, " in a message of %d fields" % len(fields))
+        lay.label_dtype = DTYPE_FLOAT32
+    lay.time_kind, lay.time_offset = 0, 0
+    if want_time:
+        tf = None
+        for f in fields:
+            if f.name in ("t", "timestamp", "time"):
+                tf = f
+        if tf is None or not int(getattr(tf, "count", 1)):
+            raise ValueError(NO_TIME_FIELD)
+        if tf.name == "time":
+            lay.time_offset, lay.time_kind = _field_as(tf, PointField.FLOAT64), 2
+        else:
+            lay.time_offset, lay.time_kind = _field_as(tf, PointField.UINT32), 1
+    return lay
+
+
+def _message_data(data, device_index):
+    """(address, bytes, keep-alive, stream or None) of a message's data; stream is not None for a device tensor"""
+    if _is_tensor(data):
+        if str(data.dtype) != "torch.uint8" or data.dim() != 1 or (data.shape[0] > 1 and data.stride(0) != 1):
+            raise ValueError("message data as a tensor is a contiguous 1-D uint8 tensor, not %s shape %s"
+                             % (data.dtype, tuple(data.shape)))
+        if data.device.type == "cpu":
+            data = data.numpy()
+        else:
+            if data.device.type != "cuda" or data.device.index != device_index:
+                raise ValueError("the message data is on %s, the pipeline on GPU %d" % (data.device, device_index))
+            _check_one_hip_runtime()
+            return data.data_ptr() or None, int(data.shape[0]), data, _current_stream(data.device)
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8 or data.ndim != 1:
+            raise ValueError("message data as an array is 1-D uint8, not %s shape %s" % (data.dtype, data.shape))
+        a = np.ascontiguousarray(data)
+    else:
+        a = np.frombuffer(data, dtype=np.uint8)
+    return (a.ctypes.data or None) if a.size else None, int(a.size), a, None
+
+
+def msg_output_fields():
+    """the field table of the outgoing 21-byte record (sageicp_msg_output_fields) as PointFields"""
+    buf = (MsgField * 8)()
+    k = lib().sageicp_msg_output_fields(buf, 8)
+    return [PointField(buf[i].name.decode(), buf[i].offset, buf[i].datatype, buf[i].count) for i in range(k)]
+
+
+def output_pointcloud2(records, header=None):
+    """a PointCloud2 around (n, 21) records (source_msg / LocalMapMsg / PointcloudMsg), as CreatePointCloud2Msg lays
+    it out: the five fields, point_step 21, height 1, width n"""
+    n = int(records.shape[0])
+    return PointCloud2(msg_output_fields(), MSG_POINT_STEP, records.reshape(-1), width=n, height=1, header=header)
+
+
+def _msg_colors(colors):
+    """MsgColors of a {label: colour} mapping or (label, colour) pairs; None: an empty table"""
+    pairs = list(colors.items()) if hasattr(colors, "items") else list(colors or ())
+    n = len(pairs)
+    keys = (C.c_int32 * max(n, 1))(*[int(k) for k, _ in pairs])
+    vals = (C.c_int32 * max(n, 1))(*[int(v) for _, v in pairs])
+    c = MsgColors(keys, vals, n)
+    c._keep = (keys, vals)
+    return c
+
+
+def _records_out(device_index, count, host_call, device_call, colors, device, out):
+    """source_msg / LocalMapMsg / PointcloudMsg: the rows as (n, 21) uint8 records — numpy, with device=True a fresh
+    tensor on the GPU, with out= the caller's buffer (a C-contiguous uint8 numpy array or a contiguous uint8 tensor on
+    the GPU, 1-D or (k, 21), any base alignment): its first min(rows that fit, n) records are written and returned as a
+    view.  host_call(colors, ptr, cap, n_out) / device_call(colors, ptr, cap, stream, n_out) are the C entries."""
+    c = _msg_colors(colors)
+    n = C.c_uint64(0)
+    if out is None and not device:
+        a = np.empty((count(), MSG_POINT_STEP), dtype=np.uint8)
+        _check(host_call(C.byref(c), a.ctypes.data_as(C.c_void_p) if a.size else None, a.shape[0], C.byref(n)))
+        return a[:min(n.value, a.shape[0])]
+    if out is None:
+        import torch
+        _check_one_hip_runtime()
+        out = torch.empty((count(), MSG_POINT_STEP), dtype=torch.uint8, device=torch.device("cuda", device_index))
+    if isinstance(out, np.ndarray):
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or not out.flags.writeable:
+            raise ValueError("out= as an array is writable C-contiguous uint8")
+        if out.ndim == 2 and out.shape[1] != MSG_POINT_STEP or out.ndim not in (1, 2):
+            raise ValueError("out= is 1-D or (k, %d)" % MSG_POINT_STEP)
+        cap = out.size // MSG_POINT_STEP
+        _check(host_call(C.byref(c), out.ctypes.data_as(C.c_void_p) if cap else None, cap, C.byref(n)))
+        k = min(n.value, cap)
+        return out.reshape(-1)[:k * MSG_POINT_STEP].reshape(k, MSG_POINT_STEP)
+    if not _is_device_tensor(out):
+        raise ValueError("out= is a uint8 numpy array or a uint8 torch tensor on the GPU")
+    if str(out.dtype) != "torch.uint8" or not out.is_contiguous() or out.dim() not in (1, 2) or \
+            (out.dim() == 2 and out.shape[1] != MSG_POINT_STEP):
+        raise ValueError("out= as a tensor is contiguous uint8, 1-D or (k, %d)" % MSG_POINT_STEP)
+    if out.device.type != "cuda" or out.device.index != device_index:
+        raise ValueError("out= is on %s, the pipeline / map on GPU %d" % (out.device, device_index))
+    _check_one_hip_runtime()
+    cap = out.numel() // MSG_POINT_STEP
+    _check(device_call(C.byref(c), (out.data_ptr() or None) if cap else None, cap, _current_stream(out.device), C.byref(n)))
+    k = min(n.value, cap)
+    return out.reshape(-1)[:k * MSG_POINT_STEP].view(k, MSG_POINT_STEP)
+
+
 def robin_sweep(vox, far, listed):
     """sageicp_robin_sweep: (erased voxels in erasure order, iteration order of the rest)"""
     v = np.ascontiguousarray(vox, dtype=np.int32).reshape(-1, 3)
@@ -720,6 +923,15 @@ class VoxelHashMap:
             return out
         return _map_rows(lambda: self._h, self.device, device, dtype, out, labels_out)
 
+    def PointcloudMsg(self, colors, device=False, out=None):
+        """Pointcloud()'s rows, in its order, as the (n, 21) uint8 records EigenToPointCloud2 writes
+        (sageicp_map_pointcloud_msg[_device]; colors: {label: colour}): numpy, a fresh tensor with device=True, or the
+        caller's out= (see _records_out).  A label outside [0, 255] or without a colour raises (ERR_INVALID)."""
+        return _records_out(self.device, self.size,
+                            lambda c, o, cap, n: lib().sageicp_map_pointcloud_msg(self._h, c, o, cap, n),
+                            lambda c, o, cap, s, n: lib().sageicp_map_pointcloud_msg_device(self._h, c, o, cap, s, n),
+                            colors, device, out)
+
     def resident(self):
         """True while the HBM copy of the map is the authority (after a device-side update)"""
         return bool(lib().sageicp_map_resident(self._h))
@@ -832,6 +1044,7 @@ class SageICP:
         self._h = lib().sageicp_pipeline_create(C.byref(self.config))
         if not self._h:
             raise SageIcpError(ERR_INVALID, (lib().sageicp_last_error() or b"").decode())
+        self._deskew_on = False
         dyn = getattr(self.config, "_dynamic", None)
         if dyn and dyn["enable"]:
             self.set_dynamic_vehicle_filter(True, dyn["dy_th"], dyn["voxid"], dyn["landmarks"])
@@ -842,6 +1055,7 @@ class SageICP:
         """sageConfig::deskew (sageicp_pipeline_set_deskew): RegisterFrame(frame, timestamps) deskews from the third
         pose on.  Drops a prepared or announced frame; prefetch() is refused while it is on."""
         _check(lib().sageicp_pipeline_set_deskew(self._h, 1 if enable else 0))
+        self._deskew_on = bool(enable)
         if enable:
             self._announced = ()
 
@@ -915,7 +1129,14 @@ class SageICP:
         `frame` may be a torch tensor on the pipeline's GPU (float32 / float64, stride(1) == 1, x y z in columns 0-2 and
         the label in column 3, or `labels`: a 1-D uint8 / int32 / int64 tensor on the same device, column 3 then
         ignored); `timestamps` are then a tensor on that device too.  The frame is read in the order of the device's
-        current torch stream, and not any more once the call has returned."""
+        current torch stream, and not any more once the call has returned.
+        `frame` may also be a sensor_msgs/PointCloud2 (sage.PointCloud2, rclpy's, anything with their attributes): its
+        fields are read by the reference's rules (pointcloud2_layout), the stamps exactly when deskew is on, and its
+        data goes to the device as it is (host bytes) or is read in place (a uint8 tensor on the pipeline's GPU)."""
+        if _is_message(frame):
+            if timestamps is not None or labels is not None:
+                raise ValueError("a PointCloud2 carries its own labels and stamps: timestamps= and labels= do not apply")
+            return self._register_msg(frame)
         if _is_device_tensor(frame):
             return self._register_device(frame, timestamps, labels)
         if labels is not None:
@@ -935,6 +1156,30 @@ class SageICP:
             _check(lib().sageicp_pipeline_register_frame_timestamps(self._h, pp, tp, n, out.ctypes.data_as(_dp),
                                                                     C.byref(icp), C.byref(tot), C.byref(ns),
                                                                     C.byref(st)))
+        return out, icp.value, tot.value, ns.value, st
+
+    def _register_msg(self, msg):
+        lay = pointcloud2_layout(msg, self._deskew_on)
+        # (the reference's iterators ignore row_step; so does this)
+        return self.RegisterFrameBytes(msg.data, int(msg.height) * int(msg.width), lay)
+
+    def RegisterFrameBytes(self, data, n, layout):
+        """RegisterFrame of n records described by a MsgLayout (sageicp_pipeline_register_frame_msg[_device]) — what
+        RegisterFrame(msg) calls once the field-name rules have given the layout; `data` as PointCloud2.data"""
+        lay = layout
+        ptr, nbytes, keep, stream = _message_data(data, self.config.device)
+        out = np.empty(7)
+        icp, tot, ns = C.c_double(0), C.c_double(0), C.c_uint64(0)
+        st = Stats()
+        if stream is None:
+            _check(lib().sageicp_pipeline_register_frame_msg(self._h, ptr, nbytes, n, C.byref(lay),
+                                                             out.ctypes.data_as(_dp), C.byref(icp), C.byref(tot),
+                                                             C.byref(ns), C.byref(st)))
+        else:
+            _check(lib().sageicp_pipeline_register_frame_msg_device(self._h, ptr, nbytes, n, C.byref(lay), stream,
+                                                                    out.ctypes.data_as(_dp), C.byref(icp), C.byref(tot),
+                                                                    C.byref(ns), C.byref(st)))
+        del keep
         return out, icp.value, tot.value, ns.value, st
 
     def _register_device(self, frame, timestamps, labels):
@@ -1004,6 +1249,22 @@ class SageICP:
         return _rows_out(self.config.device, self.source_size, self._source_host,
                          lambda d, s, n: lib().sageicp_pipeline_source_device(self._h, d, s, n),
                          device, dtype, out, labels_out)
+
+    def source_msg(self, colors, device=False, out=None):
+        """source()'s rows, in its order, as the (n, 21) uint8 records the node publishes for the frame
+        (sageicp_pipeline_source_msg[_device]); the arguments as VoxelHashMap.PointcloudMsg"""
+        return _records_out(self.config.device, self.source_size,
+                            lambda c, o, cap, n: lib().sageicp_pipeline_source_msg(self._h, c, o, cap, n),
+                            lambda c, o, cap, s, n: lib().sageicp_pipeline_source_msg_device(self._h, c, o, cap, s, n),
+                            colors, device, out)
+
+    def LocalMapMsg(self, colors, device=False, out=None):
+        """LocalMap()'s rows, in its order, as (n, 21) uint8 records; the arguments as VoxelHashMap.PointcloudMsg"""
+        h = lambda: lib().sageicp_pipeline_local_map(self._h)
+        return _records_out(self.config.device, self.local_map_size,
+                            lambda c, o, cap, n: lib().sageicp_map_pointcloud_msg(h(), c, o, cap, n),
+                            lambda c, o, cap, s, n: lib().sageicp_map_pointcloud_msg_device(h(), c, o, cap, s, n),
+                            colors, device, out)
 
     def source_size(self):
         """rows of source(): n_source of the last successful RegisterFrame, 0 if there is none"""

@@ -1213,6 +1213,7 @@ struct sageicp_pipeline {
     uint64_t src_n = 0;
     int src_buf = 0;
     mutable DevBuf<int> d_egress_flag;
+    mutable DevBuf<unsigned char> d_msg;           // sageicp_pipeline_source_msg: the records before they cross PCIe
     // key-frame selection (sageicp_pipeline_set_key_frames, keyframe.hip): off by default.  The key grid lives on the
     // device (d_key); the host holds the key pose and what the last frame's step decided.
     struct KeyFrames {
@@ -1376,6 +1377,16 @@ static int pipeline_register(sageicp_pipeline *p, const double *frame, const dou
         const sageicp::DeviceSource *dev;
         int voxelize(const double *f, uint64_t m, uint64_t &n_src, const double *delta) {
             if (p->worker.joinable()) p->worker.join();
+            if (dev && dev->msg && m == 0) {     // an empty message: no rows, no device work (an announcement is dropped)
+                sageicp::Prep &pr = p->prep[p->cur];
+                pr.kept_levels[0] = pr.kept_levels[1] = 0;
+                pr.dyn_ran = false;
+                pr.dyn.info = sageicp_dynfilter_info{};
+                p->ready = false;
+                p->announced = false;
+                n_src = 0;
+                return SAGEICP_OK;
+            }
             int r;
             if (delta) {                         // deskewed: depends on the last two poses, never prepared ahead
                 sageicp::DeskewArgs da{dev ? nullptr : ts, {}};
@@ -1422,6 +1433,7 @@ static int pipeline_register(sageicp_pipeline *p, const double *frame, const dou
         int update_map(const double pose[7]) {
             const sageicp::Prep &pr = p->prep[p->cur];
             const uint64_t n_fd = pr.kept_levels[0];
+            if (dev && dev->msg && !n_fd && map_is_empty(p->impl.map)) return SAGEICP_OK;   // nothing into nothing
             if (p->impl.map_update_on_device_())
                 return device_update_all(p->impl.map, nullptr, n_fd, pose, pr.d_fd.data());
             std::vector<double> fd(4 * n_fd);
@@ -1438,7 +1450,7 @@ static int pipeline_register(sageicp_pipeline *p, const double *frame, const dou
     p->src_buf = p->cur;
     p->src_n = rc == SAGEICP_OK ? p->prep[p->cur].kept_levels[1] : 0;
     // the node's key-frame block runs after RegisterFrame has returned (outside the times reported above)
-    if (rc == SAGEICP_OK && p->kf.on) rc = key_frame_step(p, n);
+    if (rc == SAGEICP_OK && p->kf.on && !(dev && dev->msg && n == 0)) rc = key_frame_step(p, n);
     return rc;
 }
 // Every register entry drops the last source first: a call that is refused before it reaches pipeline_register (a bad
@@ -1480,6 +1492,202 @@ int sageicp_pipeline_register_frame_device(sageicp_pipeline *p, const sageicp_de
     const sageicp::DeviceSource dev{frame, ts, static_cast<hipStream_t>(stream)};
     return pipeline_register(p, nullptr, ts, frame->n, pose_out, icp_s, total_s, n_source, stats, &dev);
 }
+
+// ---- sensor_msgs/PointCloud2 payloads (msg.hip) ---------------------------------------------------------------------
+// everything about a message that can be known without a device (include/sageicp.h: what is refused)
+static int check_msg(const sageicp_msg_layout *l, const void *data, uint64_t data_bytes, uint64_t n) {
+    if (!l) return fail(SAGEICP_ERR_INVALID, "message: null layout");
+    if (l->point_step == 0 || l->point_step > kMsgMaxStep)
+        return fail(SAGEICP_ERR_INVALID, "message: point_step must lie in [1, 1024]");
+    const auto ends_within = [&](uint32_t off, uint32_t size) { return static_cast<uint64_t>(off) + size <= l->point_step; };
+    if (!ends_within(l->x_offset, 4)) return fail(SAGEICP_ERR_INVALID, "message: field x ends beyond point_step");
+    if (!ends_within(l->y_offset, 4)) return fail(SAGEICP_ERR_INVALID, "message: field y ends beyond point_step");
+    if (!ends_within(l->z_offset, 4)) return fail(SAGEICP_ERR_INVALID, "message: field z ends beyond point_step");
+    if (l->label_dtype != SAGEICP_DTYPE_UINT8 && l->label_dtype != SAGEICP_DTYPE_FLOAT32)
+        return fail(SAGEICP_ERR_INVALID, "message: label_dtype must be SAGEICP_DTYPE_UINT8 or _FLOAT32");
+    if (!ends_within(l->label_offset, l->label_dtype == SAGEICP_DTYPE_UINT8 ? 1 : 4))
+        return fail(SAGEICP_ERR_INVALID, "message: field label ends beyond point_step");
+    if (l->time_kind < 0 || l->time_kind > 2)
+        return fail(SAGEICP_ERR_INVALID, "message: time_kind must be 0 (none), 1 (uint32) or 2 (float64)");
+    if (l->time_kind && !ends_within(l->time_offset, l->time_kind == 1 ? 4 : 8))
+        return fail(SAGEICP_ERR_INVALID, "message: the time field ends beyond point_step");
+    if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
+    if (data_bytes < n * l->point_step)
+        return fail(SAGEICP_ERR_INVALID, "message: data holds fewer than n * point_step bytes");
+    if (n && !data) return fail(SAGEICP_ERR_INVALID, "message: data is NULL");
+    return SAGEICP_OK;
+}
+static int register_msg(sageicp_pipeline *p, const void *data, uint64_t data_bytes, uint64_t n,
+                        const sageicp_msg_layout *layout, bool on_device, void *stream, double pose_out[7], double *icp_s,
+                        double *total_s, uint64_t *n_source, sageicp_stats *stats) {
+    drop_source(p);
+    if (!p || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    int rc = check_msg(layout, data, data_bytes, n);
+    if (rc) return rc;
+    // deskew off: the time field is never read, whatever the layout says (OdometryServer.cpp:161-164)
+    const bool want_time = p->deskew_on;
+    if (want_time && layout->time_kind == 0)
+        return fail(SAGEICP_ERR_INVALID, "deskew is on and the message has no time field (time_kind 0)");
+    if (n && on_device) {
+        if ((rc = require_device())) return rc;
+        if ((rc = check_extent(data, n * layout->point_step, p->device, "message data"))) return rc;
+        if ((rc = check_stream(stream, p->device))) return rc;
+    }
+    const unsigned char *bytes = static_cast<const unsigned char *>(data);
+    const sageicp::MsgSource msg{on_device ? nullptr : bytes, on_device ? bytes : nullptr, *layout, want_time};
+    const sageicp::DeviceSource dev{nullptr, nullptr, static_cast<hipStream_t>(stream), &msg};
+    static const double kDeskew = 0.0;     // (a non-null marker that deskew is asked for: the stamps are the message's)
+    return pipeline_register(p, nullptr, want_time ? &kDeskew : nullptr, n, pose_out, icp_s, total_s, n_source, stats, &dev);
+}
+int sageicp_pipeline_register_frame_msg(sageicp_pipeline *p, const void *data, uint64_t data_bytes, uint64_t n,
+                                        const sageicp_msg_layout *layout, double pose_out[7], double *icp_s,
+                                        double *total_s, uint64_t *n_source, sageicp_stats *stats) {
+    return register_msg(p, data, data_bytes, n, layout, false, nullptr, pose_out, icp_s, total_s, n_source, stats);
+}
+int sageicp_pipeline_register_frame_msg_device(sageicp_pipeline *p, const void *data, uint64_t data_bytes, uint64_t n,
+                                               const sageicp_msg_layout *layout, void *stream, double pose_out[7],
+                                               double *icp_s, double *total_s, uint64_t *n_source, sageicp_stats *stats) {
+    return register_msg(p, data, data_bytes, n, layout, true, stream, pose_out, icp_s, total_s, n_source, stats);
+}
+
+uint32_t sageicp_msg_output_fields(sageicp_msg_field *out, uint32_t cap) {
+    static const sageicp_msg_field kFields[5] = {          // CreatePointCloud2Msg, Utils.hpp:109-113
+        {"x", SAGEICP_MSG_X_OFFSET, SAGEICP_MSG_FIELD_FLOAT32, 1},
+        {"y", SAGEICP_MSG_Y_OFFSET, SAGEICP_MSG_FIELD_FLOAT32, 1},
+        {"z", SAGEICP_MSG_Z_OFFSET, SAGEICP_MSG_FIELD_FLOAT32, 1},
+        {"label", SAGEICP_MSG_LABEL_OFFSET, SAGEICP_MSG_FIELD_UINT8, 1},
+        {"rgb", SAGEICP_MSG_RGB_OFFSET, SAGEICP_MSG_FIELD_UINT32, 1}};
+    for (uint32_t i = 0; out && i < std::min<uint32_t>(cap, 5); ++i) out[i] = kFields[i];
+    return 5;
+}
+
+// the node's color_list as the 256-entry table the label rule leaves room for: keys outside 0..255 can never match
+static int color_table(const sageicp_msg_colors *c, MsgColorTable &t) {
+    std::memset(&t, 0, sizeof(t));
+    if (!c || !c->n) return SAGEICP_OK;
+    if (!c->keys || !c->values) return fail(SAGEICP_ERR_INVALID, "colour table: n > 0 with a NULL array");
+    for (uint32_t i = 0; i < c->n; ++i) {
+        const int32_t k = c->keys[i];
+        if (k < 0 || k > 255) continue;
+        t.value[k] = static_cast<uint32_t>(c->values[i]);
+        t.present[k >> 5] |= 1u << (k & 31);
+    }
+    return SAGEICP_OK;
+}
+
+// `want` packed rows as records at d_out (device memory) on s, behind a zeroed flag word; with host_out the records
+// follow to host memory.  Waited for, then the flags the rows may have raised read.
+static int pack_msg(DevBuf<int> &flag, const Point4 *d_rows, uint64_t want, const MsgColorTable &t, unsigned char *d_out,
+                    void *host_out, hipStream_t s) {
+    if (!flag) HIPCHK(flag.reserve(1));
+    HIPCHK(hipMemsetAsync(flag.data(), 0, sizeof(int), s));
+    launch_msg_pack(d_rows, want, t, d_out, flag.data(), s);
+    int flags = 0;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&flags, flag.data(), sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && host_out)
+        e = hipMemcpyAsync(host_out, d_out, want * SAGEICP_MSG_POINT_STEP, hipMemcpyDeviceToHost, s);
+    const hipError_t w = hipStreamSynchronize(s);        // (also after a failure: nothing enqueued here runs on)
+    HIPCHK(e);
+    HIPCHK(w);
+    if (flags & kMsgLabelRange)
+        return fail(SAGEICP_ERR_INVALID, "a label does not fit the record's uint8 (trunc(label) outside [0, 255])");
+    if (flags & kMsgNoColor) return fail(SAGEICP_ERR_INVALID, "the colour table has no colour for a label");
+    return SAGEICP_OK;
+}
+static int reserve_records(DevBuf<unsigned char> &d_msg, uint64_t want) {
+    const size_t bytes = static_cast<size_t>(want) * SAGEICP_MSG_POINT_STEP;
+    if (bytes > d_msg.capacity()) HIPCHK(d_msg.reserve(bytes + bytes / 4 + 4096));
+    return SAGEICP_OK;
+}
+// a caller's destination of cap records in device memory, and its stream
+static int check_records_out(const void *out, uint64_t cap, void *stream, int device) {
+    if (!cap) return SAGEICP_OK;
+    if (!out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = check_extent(out, cap * SAGEICP_MSG_POINT_STEP, device, "message records: out"))) return rc;
+    return check_stream(stream, device);
+}
+
+int sageicp_pipeline_source_msg(const sageicp_pipeline *p, const sageicp_msg_colors *colors, void *out, uint64_t cap,
+                                uint64_t *n_out) {
+    if (!p || !n_out || (cap && !out)) return fail(SAGEICP_ERR_INVALID, "null argument");
+    MsgColorTable t;
+    int rc = color_table(colors, t);
+    if (rc) return rc;
+    *n_out = p->src_n;
+    const uint64_t want = std::min(cap, p->src_n);
+    if (!want) return SAGEICP_OK;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = reserve_records(p->d_msg, want))) return rc;
+    const sageicp::Prep &pr = p->prep[p->src_buf];
+    return pack_msg(p->d_egress_flag, pr.d_src.data(), want, t, p->d_msg.data(), out, pr.stream.get());
+}
+int sageicp_pipeline_source_msg_device(const sageicp_pipeline *p, const sageicp_msg_colors *colors, void *out,
+                                       uint64_t cap, void *stream, uint64_t *n_out) {
+    if (!p || !n_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    MsgColorTable t;
+    int rc = color_table(colors, t);
+    if (rc) return rc;
+    if ((rc = check_records_out(out, cap, stream, p->device))) return rc;
+    *n_out = p->src_n;
+    const uint64_t want = std::min(cap, p->src_n);
+    if (!want) return SAGEICP_OK;
+    HIPCHK(hipSetDevice(p->device));
+    // on the caller's stream, behind the work it enqueued before this call; synchronous
+    return pack_msg(p->d_egress_flag, p->prep[p->src_buf].d_src.data(), want, t, static_cast<unsigned char *>(out), nullptr,
+                    static_cast<hipStream_t>(stream));
+}
+
+// sageicp_map_pointcloud's rows into d_pc on s: packed from the HBM copy, or staged from the host copy (`staged` must
+// live until s has been waited for)
+static int map_rows_packed(const sageicp_map *m, uint64_t n, std::vector<double> &staged, hipStream_t s) {
+    if (m->on_device) return pack_resident(m, nullptr, s);
+    staged.resize(4 * n);
+    m->host.pointcloud(staged.data(), n);
+    if (n > m->d_pc.capacity()) HIPCHK(m->d_pc.reserve(n + n / 4 + 1024));
+    HIPCHK(hipMemcpyAsync(m->d_pc.data(), staged.data(), n * sizeof(Point4), hipMemcpyHostToDevice, s));
+    return SAGEICP_OK;
+}
+static int map_msg(const sageicp_map *m, const sageicp_msg_colors *colors, void *out, uint64_t cap, bool on_device,
+                   void *stream, uint64_t *n_out) {
+    if (!m || !n_out || (cap && !out)) return fail(SAGEICP_ERR_INVALID, "null argument");
+    MsgColorTable t;
+    int rc = color_table(colors, t);
+    if (rc) return rc;
+    if (on_device && (rc = check_records_out(out, cap, stream, m->device))) return rc;
+    const uint64_t n = sageicp_map_size(m);
+    *n_out = n;
+    const uint64_t want = std::min(cap, n);
+    if (!want) return SAGEICP_OK;
+    if ((rc = m->sc.init(m->device))) return rc;
+    HIPCHK(hipSetDevice(m->device));
+    const hipStream_t s = m->sc.stream.get();
+    if (on_device) {        // the map's stream waits for the work the caller enqueued before this call
+        if (!m->ev_caller) HIPCHK(m->ev_caller.create(hipEventDisableTiming));
+        HIPCHK(hipEventRecord(m->ev_caller.get(), static_cast<hipStream_t>(stream)));
+        HIPCHK(hipStreamWaitEvent(s, m->ev_caller.get(), 0));
+    } else if ((rc = reserve_records(m->d_msg, want))) {
+        return rc;
+    }
+    std::vector<double> staged;
+    if ((rc = map_rows_packed(m, n, staged, s))) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    return pack_msg(m->d_egress_flag, m->d_pc.data(), want, t,
+                    on_device ? static_cast<unsigned char *>(out) : m->d_msg.data(), on_device ? nullptr : out, s);
+}
+int sageicp_map_pointcloud_msg(const sageicp_map *m, const sageicp_msg_colors *colors, void *out, uint64_t cap,
+                               uint64_t *n_out) {
+    return map_msg(m, colors, out, cap, false, nullptr, n_out);
+}
+int sageicp_map_pointcloud_msg_device(const sageicp_map *m, const sageicp_msg_colors *colors, void *out, uint64_t cap,
+                                      void *stream, uint64_t *n_out) {
+    return map_msg(m, colors, out, cap, true, stream, n_out);
+}
+
 int sageicp_pipeline_source(const sageicp_pipeline *p, double *out, uint64_t cap, uint64_t *n_out) {
     if (!p || !n_out || (cap && !out)) return fail(SAGEICP_ERR_INVALID, "null argument");
     *n_out = p->src_n;

@@ -33,6 +33,7 @@
 #include "host_map.hpp"
 #include "kernels.h"
 #include "egress.h"
+#include "msg.h"
 #include "map_update.h"
 #include "metrics.hpp"
 #include "pipeline.hpp"
@@ -422,10 +423,21 @@ struct DeskewArgs {
 // A raw frame in the caller's device memory (sageicp_device_frame, validated by capi.hip): the ingest kernel reads it
 // into d_in on Prep::stream once that stream has waited for the caller's.  timestamps: device, n of them, or nullptr
 // (not asked for); they are copied to d_ts and checked in the same pass.
+struct MsgSource;
 struct DeviceSource {
     const sageicp_device_frame *frame;
     const double *timestamps;
     hipStream_t stream;
+    const MsgSource *msg = nullptr;     // the frame is a message's payload instead (frame and timestamps are not read)
+};
+// A sensor_msgs/PointCloud2 payload (sageicp_msg_layout, validated by capi.hip): n records in host memory, which are
+// uploaded as they are, or in the caller's device memory, read in place behind DeviceSource::stream.  k_msg_unpack
+// (msg.hip) writes the rows into d_in and, with want_time, the stamps into d_ts.
+struct MsgSource {
+    const unsigned char *host;          // one of the two is set
+    const unsigned char *device;
+    sageicp_msg_layout layout;
+    bool want_time;                     // deskew is on: the time field is read and checked (layout.time_kind != 0)
 };
 inline IngestArgs ingest_args(const sageicp_device_frame &f) {
     IngestArgs a{};
@@ -475,6 +487,11 @@ struct Prep {
     // in place — its coordinates checked — for the pass that follows the registration (allocated with the first use)
     bool keep_raw = false;
     DevBuf<Point4> d_raw;
+    // a message's payload (MsgSource): pinned staging and device copy of host bytes, the maximum of uint32 stamps
+    // (allocated with the first such frame)
+    PinnedBuf<unsigned char> h_blob;
+    DevBuf<unsigned char> d_blob;
+    DevBuf<uint32_t> d_tmax;
 
     // waits for the stream with the device current, then the members go, dyn's among them: nothing runs on the stream
     // any more (a Prep that never created its stream calls nothing)
@@ -535,6 +552,7 @@ struct Prep {
     // host entry's check, sageicp_pipeline_register_frame_timestamps).  The caller's buffers are last read by this
     // launch, which the first level's synchronisation waits for: run() returns with them released.
     int ingest(const DeviceSource &src, uint64_t n) {
+        if (src.msg) return ingest_msg(*src.msg, src.stream, n);
         if (!ev_caller) HIPCHK(ev_caller.create(hipEventDisableTiming));
         HIPCHK(hipEventRecord(ev_caller.get(), src.stream));
         HIPCHK(hipStreamWaitEvent(stream.get(), ev_caller.get(), 0));
@@ -546,6 +564,58 @@ struct Prep {
         launch_ingest(a, d_in.data(), stream.get());
         HIPCHK(hipGetLastError());
         if (src.timestamps) {
+            int flags = 0;
+            HIPCHK(hipMemcpyAsync(&flags, d_overflow.data(), sizeof(int), hipMemcpyDeviceToHost, stream.get()));
+            HIPCHK(hipStreamSynchronize(stream.get()));
+            if (flags & kIngestBadTimestamp) return fail(SAGEICP_ERR_INVALID, "deskew is on and a timestamp is not finite");
+        }
+        return SAGEICP_OK;
+    }
+
+    // The same of a message's payload: host bytes cross PCIe as they are (through the pinned staging copy), device bytes
+    // are read in place behind the caller's stream.  uint32 stamps are normalised by their maximum in a second small
+    // pass (NormalizeTimestamps); float64 stamps are checked like a device frame's.
+    int ingest_msg(const MsgSource &m, hipStream_t caller, uint64_t n) {
+        const size_t bytes = static_cast<size_t>(n) * m.layout.point_step;
+        const unsigned char *d = m.device;
+        if (m.host) {
+            if (bytes > h_blob.capacity()) {
+                const size_t c = bytes + bytes / 4 + 4096;
+                h_blob.reset();
+                HIPCHK(d_blob.reserve(c));
+                HIPCHK(h_blob.reserve(c));
+            }
+            std::memcpy(h_blob.data(), m.host, bytes);
+            HIPCHK(hipMemcpyAsync(d_blob.data(), h_blob.data(), bytes, hipMemcpyHostToDevice, stream.get()));
+            d = d_blob.data();
+        } else {
+            if (!ev_caller) HIPCHK(ev_caller.create(hipEventDisableTiming));
+            HIPCHK(hipEventRecord(ev_caller.get(), caller));
+            HIPCHK(hipStreamWaitEvent(stream.get(), ev_caller.get(), 0));
+        }
+        MsgUnpackArgs a{};
+        a.data = d;
+        a.point_step = m.layout.point_step;
+        a.x_offset = m.layout.x_offset; a.y_offset = m.layout.y_offset; a.z_offset = m.layout.z_offset;
+        a.label_offset = m.layout.label_offset;
+        a.label_dtype = m.layout.label_dtype;
+        a.time_kind = m.want_time ? m.layout.time_kind : 0;
+        a.time_offset = m.layout.time_offset;
+        a.n = static_cast<int>(n);
+        a.ts_out = a.time_kind ? d_ts.data() : nullptr;
+        a.flags = d_overflow.data();
+        if (a.time_kind == 1) {
+            if (!d_tmax) HIPCHK(d_tmax.reserve(1));
+            HIPCHK(hipMemsetAsync(d_tmax.data(), 0, sizeof(uint32_t), stream.get()));
+            a.ts_max = d_tmax.data();
+        }
+        launch_msg_unpack(a, d_in.data(), stream.get());
+        HIPCHK(hipGetLastError());
+        if (a.time_kind == 1) {
+            launch_msg_normalize(d_ts.data(), a.n, d_tmax.data(), stream.get());
+            HIPCHK(hipGetLastError());
+        }
+        if (a.time_kind == 2) {
             int flags = 0;
             HIPCHK(hipMemcpyAsync(&flags, d_overflow.data(), sizeof(int), hipMemcpyDeviceToHost, stream.get()));
             HIPCHK(hipStreamSynchronize(stream.get()));
@@ -578,7 +648,7 @@ struct Prep {
         for (int g = 0; g < n_groups; ++g) nlabels += static_cast<size_t>(gcounts[g]);
         int rc = reserve(n, nlabels);
         if (rc) return rc;
-        if (deskew || (dev && dev->timestamps)) {
+        if (deskew || (dev && (dev->timestamps || (dev->msg && dev->msg->want_time)))) {
             rc = reserve_timestamps(n);
             if (rc) return rc;
         }
@@ -807,6 +877,8 @@ struct sageicp_map {
     mutable UpdateBuffers up;
     // Pointcloud() served from the HBM copy: the packed points before they cross PCIe
     mutable DevBuf<Point4> d_pc;
+    // sageicp_map_pointcloud_msg: the 21-byte records before they cross PCIe
+    mutable DevBuf<unsigned char> d_msg;
     // sageicp_map_pointcloud_device: the label-range flag (egress.h) and the event that orders the caller's stream
     // before the map's (created with the first call)
     mutable DevBuf<int> d_egress_flag;
