@@ -881,10 +881,8 @@ int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_poi
     if ((rc = m->sc.init(m->device))) return rc;
     HIPCHK(hipSetDevice(m->device));
     const hipStream_t s = m->sc.stream.get();
-    if (!m->ev_caller) HIPCHK(m->ev_caller.create(hipEventDisableTiming));
     // the map's stream waits for the work the caller enqueued before this call (it may still use the destination)
-    HIPCHK(hipEventRecord(m->ev_caller.get(), static_cast<hipStream_t>(stream)));
-    HIPCHK(hipStreamWaitEvent(s, m->ev_caller.get(), 0));
+    if ((rc = stream_after_caller(m->ev_caller, static_cast<hipStream_t>(stream), s))) return rc;
     std::vector<double> staged;                         // (read by a copy on s: egress_into waits for it)
     return egress_into(m->d_egress_flag, *dst, s, [&](const EgressArgs &e) -> int {
         if (m->on_device && !env_int("SAGEICP_EGRESS_TWO_PASS", 0))
@@ -1066,21 +1064,16 @@ void sageicp_comm_destroy(sageicp_comm *c) {
 }
 
 // ---- Preprocess / VoxelDownsample on the device --------------------------------------------------
-// One level of a Prep of its own on `device` (Prep::run's arguments), its cloud copied to out; info: the dynamic
-// filter's, with dyn_cfg
-static int prep_one_level(int device, const double *frame, uint64_t n, double max_range, double min_range,
-                          double label_max_range, int n_groups, const int *gcounts, const int *glabels, const double *gvs,
-                          int crop, double scale, const DynFilterConfig *dyn_cfg, double *out, uint64_t *n_out,
+// The one level of `job` on a Prep of its own on `device`, its cloud copied to out; info: the dynamic filter's, with
+// job.dyn
+static int prep_one_level(int device, const double *frame, uint64_t n, const PrepJob &job, double *out, uint64_t *n_out,
                           sageicp_dynfilter_info *info) {
     Prep pr;
     int rc = pr.init(device);
     if (rc) return rc;
-    std::vector<std::vector<double>> res;
-    rc = pr.run(frame, n, max_range, min_range, label_max_range, n_groups, gcounts, glabels, gvs, &crop, &scale, 1, res,
-                true, dyn_cfg);
-    if (rc) return rc;
-    *n_out = res[0].size() / 4;
-    if (!res[0].empty()) std::memcpy(out, res[0].data(), res[0].size() * sizeof(double));
+    if ((rc = pr.run(frame, n, job))) return rc;
+    *n_out = pr.kept_levels[0];
+    if ((rc = pr.fetch(0, out))) return rc;
     if (info) *info = pr.dyn.info;
     return SAGEICP_OK;
 }
@@ -1088,9 +1081,11 @@ static int prep_one_level(int device, const double *frame, uint64_t n, double ma
 int sageicp_preprocess(const double *frame, uint64_t n, double max_range, double min_range,
                        double label_max_range, double *out, uint64_t *n_out, int device) {
     if (!n_out || (n && (!frame || !out))) return fail(SAGEICP_ERR_INVALID, "null argument");
-    // crop only (scale 0)
-    return prep_one_level(device, frame, n, max_range, min_range, label_max_range, 0, nullptr, nullptr, nullptr, 1, 0.0,
-                          nullptr, out, n_out, nullptr);
+    PrepJob job;
+    job.max_range = max_range; job.min_range = min_range; job.label_max_range = label_max_range;
+    job.n_levels = 1;
+    job.levels[0] = {/*crop*/ 1, /*scale*/ 0.0};         // crop only
+    return prep_one_level(device, frame, n, job, out, n_out, nullptr);
 }
 
 int sageicp_voxel_downsample(const double *frame, uint64_t n, int n_groups,
@@ -1100,8 +1095,12 @@ int sageicp_voxel_downsample(const double *frame, uint64_t n, int n_groups,
     if (!n_out || (n && (!frame || !out)) || n_groups < 0 ||
         (n_groups && (!group_label_counts || !group_labels || !group_voxel_size)) || !(vox_scale > 0.0))
         return fail(SAGEICP_ERR_INVALID, "bad argument");
-    return prep_one_level(device, frame, n, 0, 0, 0, n_groups, group_label_counts, group_labels, group_voxel_size, 0,
-                          vox_scale, nullptr, out, n_out, nullptr);
+    PrepJob job;
+    job.n_groups = n_groups;
+    job.group_counts = group_label_counts; job.group_labels = group_labels; job.group_voxel_size = group_voxel_size;
+    job.n_levels = 1;
+    job.levels[0] = {/*crop*/ 0, vox_scale};
+    return prep_one_level(device, frame, n, job, out, n_out, nullptr);
 }
 
 int sageicp_preprocess_dynamic(const double *frame, uint64_t n, double max_range, double min_range,
@@ -1116,9 +1115,12 @@ int sageicp_preprocess_dynamic(const double *frame, uint64_t n, double max_range
     cfg.dy_th = dy_th;
     cfg.dynamic_labels.assign(dynamic_labels, dynamic_labels + n_dynamic);
     cfg.landmark_labels.assign(landmark_labels, landmark_labels + n_landmark);
-    // one pass-through level (no crop, scale 0): the filtered cloud, downloaded
-    return prep_one_level(device, frame, n, max_range, min_range, label_max_range, 0, nullptr, nullptr, nullptr, 0, 0.0,
-                          &cfg, out, n_out, info);
+    PrepJob job;
+    job.max_range = max_range; job.min_range = min_range; job.label_max_range = label_max_range;
+    job.dyn = &cfg;
+    job.n_levels = 1;
+    job.levels[0] = {/*crop*/ 0, /*scale*/ 0.0};         // a pass-through level: the filtered cloud, downloaded
+    return prep_one_level(device, frame, n, job, out, n_out, info);
 }
 
 int sageicp_cluster_emission_order(const uint32_t *sizes, uint64_t n, uint32_t *order_out) {
@@ -1250,16 +1252,19 @@ struct sageicp_pipeline {
         std::vector<int> counts, labels;
         std::vector<double> vs;
         impl.group_tables(counts, labels, vs);
-        const int crop[2] = {1, 0};
-        const double scales[2] = {0.5, 1.5};
-        std::vector<std::vector<double>> res;
+        sageicp::PrepJob job;
+        job.max_range = impl.max_range_(); job.min_range = impl.min_range_(); job.label_max_range = impl.label_max_range_();
+        job.n_groups = static_cast<int>(counts.size());
+        job.group_counts = counts.data(); job.group_labels = labels.data(); job.group_voxel_size = vs.data();
+        job.n_levels = 2;
+        job.levels[0] = {/*crop*/ 1, /*scale*/ 0.5};
+        job.levels[1] = {/*crop*/ 0, /*scale*/ 1.5};
+        job.dyn = dyn_on ? &dyn_cfg : nullptr; job.deskew = deskew; job.dev = dev;
         // level 0 (frame_downsample: it goes into the map, AddPoints depends on arrival order)
         // keeps the reference's emission order; level 1 (the registered source) does not need it
         pr.arrival_order_levels = env_int("SAGEICP_SOURCE_REFERENCE_ORDER", 0) ? 0u : 2u;
         pr.keep_raw = kf.on;
-        return pr.run(f, m, impl.max_range_(), impl.min_range_(), impl.label_max_range_(),
-                      static_cast<int>(counts.size()), counts.data(), labels.data(), vs.data(),
-                      crop, scales, 2, res, false, dyn_on ? &dyn_cfg : nullptr, deskew, dev);
+        return pr.run(f, m, job);
     }
 };
 
@@ -1664,13 +1669,10 @@ static int map_msg(const sageicp_map *m, const sageicp_msg_colors *colors, void 
     if ((rc = m->sc.init(m->device))) return rc;
     HIPCHK(hipSetDevice(m->device));
     const hipStream_t s = m->sc.stream.get();
-    if (on_device) {        // the map's stream waits for the work the caller enqueued before this call
-        if (!m->ev_caller) HIPCHK(m->ev_caller.create(hipEventDisableTiming));
-        HIPCHK(hipEventRecord(m->ev_caller.get(), static_cast<hipStream_t>(stream)));
-        HIPCHK(hipStreamWaitEvent(s, m->ev_caller.get(), 0));
-    } else if ((rc = reserve_records(m->d_msg, want))) {
-        return rc;
-    }
+    // (on the device: the map's stream waits for the work the caller enqueued before this call)
+    if (on_device) rc = stream_after_caller(m->ev_caller, static_cast<hipStream_t>(stream), s);
+    else rc = reserve_records(m->d_msg, want);
+    if (rc) return rc;
     std::vector<double> staged;
     if ((rc = map_rows_packed(m, n, staged, s))) {
         (void)hipStreamSynchronize(s);

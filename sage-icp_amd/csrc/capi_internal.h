@@ -1,6 +1,6 @@
 // Internals shared by the translation units of libsageicp_hip.so's host side (capi.hip, capi_mirror.hip,
-// capi_run.hip): error channel, tuning knobs, the per-handle device scratch, the pipeline's buffers, the opaque
-// handles of include/sageicp.h.  Not part of the C ABI.
+// capi_run.hip, prep.hip): error channel, tuning knobs, the per-handle device scratch, the pipeline's buffers (prep.h),
+// the opaque handles of include/sageicp.h.  Not part of the C ABI.
 #pragma once
 
 #include <dlfcn.h>
@@ -128,6 +128,15 @@ inline int require_device() {
 inline int require_device(int device) {
     if (int rc = require_device()) return rc;
     if (device < 0 || device >= sageicp_device_count()) return fail(SAGEICP_ERR_INVALID, "device ordinal out of range");
+    return SAGEICP_OK;
+}
+
+// The work the caller enqueued on its stream before this call goes before whatever `ours` runs from here on (`ev`:
+// created with the first use, on the current device).
+inline int stream_after_caller(OwnedEvent &ev, hipStream_t caller, hipStream_t ours) {
+    if (!ev) HIPCHK(ev.create(hipEventDisableTiming));
+    HIPCHK(hipEventRecord(ev.get(), caller));
+    HIPCHK(hipStreamWaitEvent(ours, ev.get(), 0));
     return SAGEICP_OK;
 }
 
@@ -384,421 +393,10 @@ inline void cluster_emission_order(const uint32_t *sizes, size_t n, uint32_t *or
 }
 // cluster_is_static (Preprocessing.cpp:141-158): dyn_rules.h
 
-struct DynFilterConfig {
-    double dy_th = 0.5;
-    std::vector<uint32_t> dynamic_labels;      // the reference's std::vector<int>, compared as uint32_t
-    std::vector<uint32_t> landmark_labels;
-};
-
-// buffers of one Prep; run() filters a frame already on the device (n points at `in`) into `out` (may be `in`),
-// passing the cropped points through `tmp` (n points)
-struct DynFilter {
-    size_t cap = 0;                            // points the buffers of reserve() hold (all of them: 0 after a failed reserve)
-    DevBuf<uint32_t> d_labels, d_ctr;
-    PinnedBuf<uint32_t> h_ctr;                 // [0..3] counters, [4] flags
-    DevBuf<unsigned long long> d_cnt, d_pos, d_vkey, d_lkey, d_count;
-    DevBuf<float4> d_vp, d_vs, d_lp, d_ls;
-    DevBuf<uint32_t> d_vval, d_lval, d_vframe, d_parent, d_root, d_size, d_rec_of_root, d_start, d_rkv, d_off;
-    DevBuf<uint4> d_rec;
-    DevBuf<unsigned char> d_temp;
-    PinnedBuf<uint4> h_rec;                    // the component table
-    PinnedBuf<uint32_t> h_off;                 // output offset per component (~0: dropped)
-    OwnedEvent ev[6];                          // device time of the three launch batches (sageicp_set_profiling)
-    OwnedEvent ev_table;
-    std::vector<uint32_t> order_scratch, size_scratch;
-    sageicp_dynfilter_info info{};             // of the last run
-
-    int reserve(size_t n, size_t nlabels);
-    int run(const Point4 *in, uint64_t n, double max_range, double min_range, double label_max_range,
-            const DynFilterConfig &cfg, Point4 *tmp, Point4 *out, int *d_ovf, uint64_t &n_out, hipStream_t s);
-};
-
-// ---- deskew of a frame before it is preprocessed (deskew.hip; core/Deskew.cpp:36-50) ---------------------------
-struct DeskewArgs {
-    const double *timestamps;           // host, one per point, all finite (checked by the caller); a device frame's are in
-                                        // its DeviceSource
-    DeskewTangent delta;                // (start.inverse() * finish).log()
-};
-
-// A raw frame in the caller's device memory (sageicp_device_frame, validated by capi.hip): the ingest kernel reads it
-// into d_in on Prep::stream once that stream has waited for the caller's.  timestamps: device, n of them, or nullptr
-// (not asked for); they are copied to d_ts and checked in the same pass.
-struct MsgSource;
-struct DeviceSource {
-    const sageicp_device_frame *frame;
-    const double *timestamps;
-    hipStream_t stream;
-    const MsgSource *msg = nullptr;     // the frame is a message's payload instead (frame and timestamps are not read)
-};
-// A sensor_msgs/PointCloud2 payload (sageicp_msg_layout, validated by capi.hip): n records in host memory, which are
-// uploaded as they are, or in the caller's device memory, read in place behind DeviceSource::stream.  k_msg_unpack
-// (msg.hip) writes the rows into d_in and, with want_time, the stamps into d_ts.
-struct MsgSource {
-    const unsigned char *host;          // one of the two is set
-    const unsigned char *device;
-    sageicp_msg_layout layout;
-    bool want_time;                     // deskew is on: the time field is read and checked (layout.time_kind != 0)
-};
-inline IngestArgs ingest_args(const sageicp_device_frame &f) {
-    IngestArgs a{};
-    a.xyz = static_cast<const unsigned char *>(f.xyz);
-    a.xyz_stride = f.xyz_stride;
-    a.xyz_dtype = f.xyz_dtype;
-    a.label = static_cast<const unsigned char *>(f.label);
-    a.label_stride = f.label_stride;
-    a.label_dtype = f.label_dtype;
-    a.n = static_cast<int>(f.n);
-    return a;
-}
-
-// ---- device preprocessing (preprocess.hip): buffers of one pipeline ------------------------------
-struct Prep {
-    int device = -1;
-    OwnedStream stream;
-    size_t cap = 0;                     // points the buffers of reserve() hold (all of them: 0 after a failed reserve)
-    DevBuf<Point4> d_in, d_tmp, d_fd, d_src;
-    DevBuf<uint32_t> d_slot, d_skey, d_sval, d_winner;
-    DevBuf<unsigned long long> d_keys;
-    DevBuf<unsigned char> d_sort_temp;
-    DevBuf<unsigned long long> d_okeys;      // survivors' voxel keys (reference-order emission)
-    DevBuf<uint32_t> d_perm;
-    PinnedBuf<unsigned long long> h_keys;
-    PinnedBuf<uint32_t> h_perm;
-    std::vector<uint32_t> h_hash;
-    RobinScratch rscratch[8];                // bucket arrays of the order replay, one pair per label group
-    std::unique_ptr<ReplayPool> pool;        // parked helper threads of the order replays
-    double us_order = 0;                // host time of the last run's order replays
-    // levels whose survivors are emitted in arrival order even under g_reference_order (bit l): the
-    // pipeline's second level — its cloud is only registered, and registration sorts its frame
-    // spatially first, so its emission order reaches nothing but the order of fp64 summation
-    unsigned arrival_order_levels = 0;
-    DevBuf<uint32_t> d_nkept;           // [2]
-    DevBuf<int> d_overflow;
-    DevBuf<int> d_gcounts, d_glabels;
-    PinnedBuf<Point4> h_pin;            // staging for the raw frame and the results
-    uint32_t kept_levels[2] = {0, 0};   // points the last run left in d_fd / d_src
-    DynFilter dyn;                      // the dynamic vehicle filter's buffers (allocated with its first use)
-    bool dyn_ran = false;               // the last run filtered (dyn.info describes its frame)
-    // the timestamps of a frame that is deskewed (allocated with the first such frame): pinned staging, device copy
-    PinnedBuf<double> h_ts;
-    DevBuf<double> d_ts;
-    OwnedEvent ev_caller;               // a device frame: orders the caller's stream before `stream` (created with the first)
-    // key-frame selection (keyframe.hip): the raw frame copied aside before deskew and the dynamic filter rewrite d_in
-    // in place — its coordinates checked — for the pass that follows the registration (allocated with the first use)
-    bool keep_raw = false;
-    DevBuf<Point4> d_raw;
-    // a message's payload (MsgSource): pinned staging and device copy of host bytes, the maximum of uint32 stamps
-    // (allocated with the first such frame)
-    PinnedBuf<unsigned char> h_blob;
-    DevBuf<unsigned char> d_blob;
-    DevBuf<uint32_t> d_tmax;
-
-    // waits for the stream with the device current, then the members go, dyn's among them: nothing runs on the stream
-    // any more (a Prep that never created its stream calls nothing)
-    ~Prep() {
-        if (!stream) return;
-        (void)hipSetDevice(device);
-        (void)hipStreamSynchronize(stream.get());
-    }
-
-    int init(int dev) {
-        if (stream) return SAGEICP_OK;
-        if (int rc = require_device(dev)) return rc;
-        device = dev;
-        HIPCHK(hipSetDevice(device));
-        HIPCHK(stream.create());
-        HIPCHK(d_nkept.reserve(2));
-        HIPCHK(d_overflow.reserve(1));
-        HIPCHK(d_gcounts.reserve(8));
-        return SAGEICP_OK;
-    }
-    int reserve(size_t n, size_t nlabels) {
-        if (nlabels > d_glabels.capacity()) HIPCHK(d_glabels.reserve(nlabels + 16));
-        if (n <= cap) return SAGEICP_OK;
-        cap = 0;
-        const size_t c = n + n / 4 + 1024;
-        uint32_t t = 1024;
-        while (t < 2 * c) t <<= 1;
-        HIPCHK(d_in.reserve(c));
-        HIPCHK(d_tmp.reserve(c));
-        HIPCHK(d_fd.reserve(c));
-        HIPCHK(d_src.reserve(c));
-        HIPCHK(d_slot.reserve(c));
-        HIPCHK(d_skey.reserve(2 * c));
-        HIPCHK(d_sval.reserve(2 * c));
-        HIPCHK(d_keys.reserve(t));
-        HIPCHK(d_winner.reserve(t));
-        HIPCHK(d_okeys.reserve(c));
-        HIPCHK(d_perm.reserve(c));
-        HIPCHK(h_keys.reserve(c));
-        HIPCHK(h_perm.reserve(c));
-        HIPCHK(d_sort_temp.reserve(vds_sort_temp_bytes(static_cast<int>(c))));
-        HIPCHK(h_pin.reserve(3 * c));
-        cap = c;
-        return SAGEICP_OK;
-    }
-    // (the staging copy goes first and comes back last: after a failed reserve it is empty)
-    int reserve_timestamps(size_t n) {
-        if (n <= h_ts.capacity()) return SAGEICP_OK;
-        const size_t c = n + n / 4 + 1024;
-        h_ts.reset();
-        HIPCHK(d_ts.reserve(c));
-        HIPCHK(h_ts.reserve(c));
-        return SAGEICP_OK;
-    }
-
-    // The raw frame of a device source into d_in (and its timestamps into d_ts), after the work the caller enqueued on
-    // its stream.  Timestamps are checked here, before anything reads them: a non-finite one refuses the frame (the
-    // host entry's check, sageicp_pipeline_register_frame_timestamps).  The caller's buffers are last read by this
-    // launch, which the first level's synchronisation waits for: run() returns with them released.
-    int ingest(const DeviceSource &src, uint64_t n) {
-        if (src.msg) return ingest_msg(*src.msg, src.stream, n);
-        if (!ev_caller) HIPCHK(ev_caller.create(hipEventDisableTiming));
-        HIPCHK(hipEventRecord(ev_caller.get(), src.stream));
-        HIPCHK(hipStreamWaitEvent(stream.get(), ev_caller.get(), 0));
-        IngestArgs a = ingest_args(*src.frame);
-        a.n = static_cast<int>(n);
-        a.ts = src.timestamps;
-        a.ts_out = src.timestamps ? d_ts.data() : nullptr;
-        a.flags = d_overflow.data();
-        launch_ingest(a, d_in.data(), stream.get());
-        HIPCHK(hipGetLastError());
-        if (src.timestamps) {
-            int flags = 0;
-            HIPCHK(hipMemcpyAsync(&flags, d_overflow.data(), sizeof(int), hipMemcpyDeviceToHost, stream.get()));
-            HIPCHK(hipStreamSynchronize(stream.get()));
-            if (flags & kIngestBadTimestamp) return fail(SAGEICP_ERR_INVALID, "deskew is on and a timestamp is not finite");
-        }
-        return SAGEICP_OK;
-    }
-
-    // The same of a message's payload: host bytes cross PCIe as they are (through the pinned staging copy), device bytes
-    // are read in place behind the caller's stream.  uint32 stamps are normalised by their maximum in a second small
-    // pass (NormalizeTimestamps); float64 stamps are checked like a device frame's.
-    int ingest_msg(const MsgSource &m, hipStream_t caller, uint64_t n) {
-        const size_t bytes = static_cast<size_t>(n) * m.layout.point_step;
-        const unsigned char *d = m.device;
-        if (m.host) {
-            if (bytes > h_blob.capacity()) {
-                const size_t c = bytes + bytes / 4 + 4096;
-                h_blob.reset();
-                HIPCHK(d_blob.reserve(c));
-                HIPCHK(h_blob.reserve(c));
-            }
-            std::memcpy(h_blob.data(), m.host, bytes);
-            HIPCHK(hipMemcpyAsync(d_blob.data(), h_blob.data(), bytes, hipMemcpyHostToDevice, stream.get()));
-            d = d_blob.data();
-        } else {
-            if (!ev_caller) HIPCHK(ev_caller.create(hipEventDisableTiming));
-            HIPCHK(hipEventRecord(ev_caller.get(), caller));
-            HIPCHK(hipStreamWaitEvent(stream.get(), ev_caller.get(), 0));
-        }
-        MsgUnpackArgs a{};
-        a.data = d;
-        a.point_step = m.layout.point_step;
-        a.x_offset = m.layout.x_offset; a.y_offset = m.layout.y_offset; a.z_offset = m.layout.z_offset;
-        a.label_offset = m.layout.label_offset;
-        a.label_dtype = m.layout.label_dtype;
-        a.time_kind = m.want_time ? m.layout.time_kind : 0;
-        a.time_offset = m.layout.time_offset;
-        a.n = static_cast<int>(n);
-        a.ts_out = a.time_kind ? d_ts.data() : nullptr;
-        a.flags = d_overflow.data();
-        if (a.time_kind == 1) {
-            if (!d_tmax) HIPCHK(d_tmax.reserve(1));
-            HIPCHK(hipMemsetAsync(d_tmax.data(), 0, sizeof(uint32_t), stream.get()));
-            a.ts_max = d_tmax.data();
-        }
-        launch_msg_unpack(a, d_in.data(), stream.get());
-        HIPCHK(hipGetLastError());
-        if (a.time_kind == 1) {
-            launch_msg_normalize(d_ts.data(), a.n, d_tmax.data(), stream.get());
-            HIPCHK(hipGetLastError());
-        }
-        if (a.time_kind == 2) {
-            int flags = 0;
-            HIPCHK(hipMemcpyAsync(&flags, d_overflow.data(), sizeof(int), hipMemcpyDeviceToHost, stream.get()));
-            HIPCHK(hipStreamSynchronize(stream.get()));
-            if (flags & kIngestBadTimestamp) return fail(SAGEICP_ERR_INVALID, "deskew is on and a timestamp is not finite");
-        }
-        return SAGEICP_OK;
-    }
-
-    // levels: each {do_crop, scale}; a scale <= 0 means "crop only" (no voxel test).  Runs the
-    // levels in sequence on the device, each feeding the next, and returns every level's cloud.
-    // With `dyn_cfg` the frame first goes through Preprocess()'s dynamic vehicle filter (dyn_filter.hip), which
-    // crops it itself: the levels then start from the filtered cloud with the crop off.
-    // With `deskew` the uploaded frame is deskewed in place before anything else reads it (the reference's order:
-    // DeSkewScan, then Preprocess, then Voxelize; pipeline/sageICP.cpp:36-52).
-    // With `dev` the raw frame comes from the caller's device memory instead of `frame` (ingest()); everything after
-    // it reaches d_in is the same.
-    int run(const double *frame, uint64_t n, double max_range, double min_range,
-            double label_max_range, int n_groups, const int *gcounts, const int *glabels,
-            const double *gvs, const int *crop, const double *scales, int n_levels,
-            std::vector<std::vector<double>> &out, bool download = true,
-            const DynFilterConfig *dyn_cfg = nullptr, const DeskewArgs *deskew = nullptr,
-            const DeviceSource *dev = nullptr) {
-        kept_levels[0] = kept_levels[1] = 0;
-        us_order = 0;
-        dyn_ran = dyn_cfg != nullptr;
-        dyn.info = sageicp_dynfilter_info{};
-        if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
-        if (n_groups > 8) return fail(SAGEICP_ERR_INVALID, "at most 8 label groups");
-        size_t nlabels = 0;
-        for (int g = 0; g < n_groups; ++g) nlabels += static_cast<size_t>(gcounts[g]);
-        int rc = reserve(n, nlabels);
-        if (rc) return rc;
-        if (deskew || (dev && (dev->timestamps || (dev->msg && dev->msg->want_time)))) {
-            rc = reserve_timestamps(n);
-            if (rc) return rc;
-        }
-        HIPCHK(hipSetDevice(device));
-        out.assign(n_levels, std::vector<double>());
-        if (n == 0) return SAGEICP_OK;
-        if (n_groups > 0) {
-            HIPCHK(hipMemcpyAsync(d_gcounts.data(), gcounts, n_groups * sizeof(int), hipMemcpyHostToDevice, stream.get()));
-            HIPCHK(hipMemcpyAsync(d_glabels.data(), glabels, nlabels * sizeof(int), hipMemcpyHostToDevice, stream.get()));
-        }
-        HIPCHK(hipMemsetAsync(d_overflow.data(), 0, sizeof(int), stream.get()));
-        if (keep_raw && d_raw.capacity() < n) HIPCHK(d_raw.reserve(n + n / 4 + 1024));
-        if (dev) {
-            rc = ingest(*dev, n);
-            if (rc) return rc;
-            if (keep_raw) launch_occ_keep(d_in.data(), d_raw.data(), static_cast<int>(n), d_overflow.data(), stream.get());
-            if (deskew) {
-                launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream.get());
-                HIPCHK(hipGetLastError());
-            }
-        } else {
-            std::memcpy(h_pin.data(), frame, n * sizeof(Point4));
-            HIPCHK(hipMemcpyAsync(d_in.data(), h_pin.data(), n * sizeof(Point4), hipMemcpyHostToDevice, stream.get()));
-            if (keep_raw) launch_occ_keep(d_in.data(), d_raw.data(), static_cast<int>(n), d_overflow.data(), stream.get());
-            if (deskew) {
-                std::memcpy(h_ts.data(), deskew->timestamps, n * sizeof(double));
-                HIPCHK(hipMemcpyAsync(d_ts.data(), h_ts.data(), n * sizeof(double), hipMemcpyHostToDevice, stream.get()));
-                launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream.get());
-                HIPCHK(hipGetLastError());
-            }
-        }
-        const Point4 *in = d_in.data();
-        Point4 *outs[2] = {d_fd.data(), d_src.data()};
-        uint64_t cur = n;
-        if (dyn_cfg) {      // the filtered cloud replaces the frame in d_in (the filter has read it by then)
-            int r = dyn.run(d_in.data(), n, max_range, min_range, label_max_range, *dyn_cfg, d_tmp.data(), d_in.data(), d_overflow.data(), cur,
-                            stream.get());
-            if (r) return r;
-        }
-        for (int l = 0; l < n_levels; ++l) {
-            VdsParams P{};
-            P.in = in; P.n = static_cast<int>(cur); P.do_crop = dyn_cfg ? 0 : crop[l];
-            P.max_range = max_range; P.min_range = min_range; P.label_max_range = label_max_range;
-            P.n_groups = scales[l] > 0.0 ? n_groups : -1;
-            P.group_counts = d_gcounts.data(); P.group_labels = d_glabels.data();
-            for (int g = 0; g < n_groups; ++g) P.group_vs[g] = gvs[g];
-            P.scale = scales[l];
-            P.keys = d_keys.data(); P.winner = d_winner.data(); P.mask = static_cast<uint32_t>(d_keys.capacity() - 1);
-            P.tmp = d_tmp.data(); P.slot_of = d_slot.data(); P.sort_key = d_skey.data(); P.sort_val = d_sval.data();
-            P.overflow = d_overflow.data();
-            const bool reorder = g_reference_order && P.n_groups > 0 && !((arrival_order_levels >> l) & 1u);
-            P.out_keys = reorder ? d_okeys.data() : nullptr;
-            Point4 *dst = outs[l & 1];
-            HIPCHK(voxel_downsample_device(P, d_sort_temp.data(), d_sort_temp.capacity(), d_nkept.data() + (l & 1), dst, stream.get()));
-            uint32_t kept = 0;
-            HIPCHK(hipMemcpyAsync(&kept, d_nkept.data() + (l & 1), sizeof(uint32_t), hipMemcpyDeviceToHost, stream.get()));
-            HIPCHK(hipStreamSynchronize(stream.get()));
-            kept_levels[l & 1] = kept;
-            if (reorder && kept) {
-                // the reference's emission order (Preprocessing.cpp:76-82): replay, group by
-                // group, the insertions into its robin_map and permute the survivors
-                const double t0 = now_us();
-                HIPCHK(hipMemcpyAsync(h_keys.data(), d_okeys.data(), kept * sizeof(unsigned long long),
-                                      hipMemcpyDeviceToHost, stream.get()));
-                HIPCHK(hipStreamSynchronize(stream.get()));
-                const double t1 = now_us();
-                h_hash.resize(kept);
-                // survivors are grouped (stable sort by group); the groups' tables are independent:
-                // one host thread per group hashes and replays its run and writes its part of the
-                // permutation in place
-                std::vector<std::pair<uint32_t, uint32_t>> runs;
-                for (uint32_t a = 0; a < kept;) {
-                    const unsigned long long g = h_keys.data()[a] >> 60;
-                    uint32_t lo = a, hi = kept;            // first index of another group (binary search: the runs are long)
-                    while (hi - lo > 1) {
-                        const uint32_t mid = lo + (hi - lo) / 2;
-                        if ((h_keys.data()[mid] >> 60) == g) lo = mid; else hi = mid;
-                    }
-                    runs.emplace_back(a, hi);
-                    a = hi;
-                }
-                auto replay = [&](size_t r) {
-                    const uint32_t a = runs[r].first, b = runs[r].second;
-                    for (uint32_t i = a; i < b; ++i) h_hash[i] = static_cast<uint32_t>(h_keys.data()[i] & 0xFFFFFu);   // hashed on the device
-                    std::vector<uint32_t> part;
-                    part.reserve(b - a);
-                    if (!RobinOrderReplay::iteration_order(h_hash.data() + a, b - a, a, part, &rscratch[r & 7])) {
-                        // a probe distance the replay does not model (robin_order.hpp): this group keeps
-                        // its arrival order — said once, loudly, because the poses of a stream then
-                        // differ from the reference's by centimetres
-                        static std::atomic<bool> told{false};
-                        if (!told.exchange(true))
-                            std::fprintf(stderr, "sageicp: VoxelDownsample: a label group of %u voxels exceeds the probe "
-                                                 "distance the tsl::robin_map replay models; it is emitted in arrival order\n",
-                                         b - a);
-                        part.resize(b - a);
-                        for (uint32_t i = a; i < b; ++i) part[i - a] = i;
-                    }
-                    std::memcpy(h_perm.data() + a, part.data(), (b - a) * sizeof(uint32_t));
-                };
-                // The groups' replays are independent and the largest (half of the survivors on street
-                // scenes) is the critical path: every group gets its own thread — parked helpers of
-                // this Prep, woken per level (starting threads costs what a small replay does) —
-                // largest first, the calling thread takes part.
-                std::vector<size_t> by_size(runs.size());
-                for (size_t r = 0; r < runs.size(); ++r) by_size[r] = r;
-                std::sort(by_size.begin(), by_size.end(), [&](size_t x, size_t y) {
-                    return runs[x].second - runs[x].first > runs[y].second - runs[y].first;
-                });
-                if (kept > 8192 && runs.size() > 1) {
-                    if (!pool) pool.reset(new ReplayPool);
-                    const size_t hw = std::max(1u, std::thread::hardware_concurrency());
-                    pool->run(runs.size(), [&](size_t k) { replay(by_size[k]); },
-                              std::min<size_t>(hw, static_cast<size_t>(std::max(1, env_int("SAGEICP_REPLAY_THREADS", 8)))));
-                } else {
-                    for (size_t r = 0; r < runs.size(); ++r) replay(r);
-                }
-                const double t2 = now_us();
-                HIPCHK(hipMemcpyAsync(d_perm.data(), h_perm.data(), kept * sizeof(uint32_t), hipMemcpyHostToDevice, stream.get()));
-                launch_vds_permute(dst, d_perm.data(), kept, d_tmp.data(), stream.get());
-                HIPCHK(hipMemcpyAsync(dst, d_tmp.data(), kept * sizeof(Point4), hipMemcpyDeviceToDevice, stream.get()));
-                us_order += now_us() - t0;
-                if (env_int("SAGEICP_DEBUG_ORDER", 0)) {
-                    std::string rs;
-                    for (auto &r : runs) rs += " " + std::to_string(r.second - r.first);
-                    std::fprintf(stderr, "order level %d: kept %u, fetch keys %.0f us, replay %.0f us (runs:%s), rest %.0f us\n",
-                                 l, kept, t1 - t0, t2 - t1, rs.c_str(), now_us() - t2);
-                }
-            }
-            if (download) {       // otherwise the level's cloud stays in d_fd / d_src for the caller
-                Point4 *hp = h_pin.data() + static_cast<size_t>(1 + (l & 1)) * cap;
-                if (kept) HIPCHK(hipMemcpyAsync(hp, dst, kept * sizeof(Point4), hipMemcpyDeviceToHost, stream.get()));
-                HIPCHK(hipStreamSynchronize(stream.get()));
-                out[l].resize(4 * static_cast<size_t>(kept));
-                if (kept) std::memcpy(out[l].data(), hp, kept * sizeof(Point4));
-            }
-            in = dst;
-            cur = kept;
-        }
-        int ovf = 0;
-        HIPCHK(hipMemcpy(&ovf, d_overflow.data(), sizeof(int), hipMemcpyDeviceToHost));
-        if (ovf & kOccNonFinite)
-            return fail(SAGEICP_ERR_INVALID, "key-frame selection is on and a coordinate is not finite (NaN / Inf)");
-        if (ovf & 2) return fail(SAGEICP_ERR_INVALID, "a label (or, without the range crop, a coordinate) is not finite (NaN / Inf)");
-        if (ovf) return fail(SAGEICP_ERR_CAPACITY, "voxel index beyond +-2^19 in VoxelDownsample");
-        return SAGEICP_OK;
-    }
-};
-
 }  // namespace sageicp
+
+// the frame-preparation driver in front of registration (prep.hip): DynFilter, the frame sources, PrepJob, Prep
+#include "prep.h"
 
 using namespace sageicp;
 

@@ -4,7 +4,7 @@
 // stay at the call sites: capacities reach the kernels) and when a stream or an event is created; the owner only
 // allocates, keeps a prefix when asked, and releases.
 //
-// What a handle that holds several of them (Scratch, Prep, sageicp_map, sageicp_pipeline: capi_internal.h, capi.hip)
+// What a handle that holds several of them (Scratch, Prep, sageicp_map, sageicp_pipeline: capi_internal.h, prep.h, capi.hip)
 // keeps when it goes:
 //  - its device is made current before anything is released;
 //  - every stream of the handle has been waited for before a buffer that its work may touch is freed and before an

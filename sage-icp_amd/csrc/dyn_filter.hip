@@ -5,7 +5,7 @@
 // component smaller than 5 is dropped.  Output: the other kept points in frame order, then the kept clusters in PCL's
 // cluster order, each in ascending frame order.
 //
-// Device form (all on the Prep's stream):
+// Device form (all on the Prep's stream; DynFilter, the buffers, is declared with Prep in prep.h):
 //   k_dyn_classify   crop + label zeroing as in the filter-off branch; a flag per point (dropped / inlier / vehicle)
 //                    and the landmark points L appended by wave-aggregated atomics (their order does not matter)
 //   exclusive scan   inlier and vehicle positions in one 64-bit scan (inliers low 32 bits, vehicles high)

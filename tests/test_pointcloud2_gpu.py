@@ -259,48 +259,57 @@ def _message(sage, fields, step, rows, t=None, device=False):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["plain", "deskew", "dynamic_filter", "key_frames"])
+@pytest.mark.parametrize("mode", ["plain", "deskew", "dynamic_filter", "key_frames", "all_on"])
 def test_a_stream_of_messages_is_the_stream_of_host_rows(gpu_sage, mode):
+    """all_on: deskew, the dynamic filter and key frames together, and a fourth pipeline fed the rows as a device frame
+    (a tensor of rows and a tensor of the normalised stamps): every source meets the same keep-raw, deskew and filter"""
     sage = gpu_sage
-    if mode == "dynamic_filter":
+    deskew, dyn, keys = mode in ("deskew", "all_on"), mode in ("dynamic_filter", "all_on"), mode in ("key_frames", "all_on")
+    if dyn:
         from sage_icp_amd import synthetic_dynamic as sd
         frames = [np.ascontiguousarray(f, dtype=np.float64) for f in sd.make_dynamic_stream(21, 10, n=30000)[0]]
     else:
         frames = _frames(10)
     # the float32-rounded values: what a message can carry
     frames = [np.column_stack([f[:, :3].astype(np.float32).astype(np.float64), f[:, 3]]) for f in frames]
-    cfg = dict(deskew=mode == "deskew", dynamic_vehicle_filter=mode == "dynamic_filter")
-    pipes = [sage.SageICP(sage.make_pipeline_config(**cfg)) for _ in range(3)]
-    if mode == "key_frames":
+    cfg = dict(deskew=deskew, dynamic_vehicle_filter=dyn)
+    # host message, device message, host rows; all_on: and a device frame
+    pipes = [sage.SageICP(sage.make_pipeline_config(**cfg)) for _ in range(4 if mode == "all_on" else 3)]
+    others = [p for p in pipes if p is not pipes[2]]
+    if keys:
         for p in pipes:
             p.set_key_frames(True)
-    fields, step = (SIX, 24) if mode == "deskew" else (FIVE, 21)
+    fields, step = (SIX, 24) if deskew else (FIVE, 21)
     rng = np.random.default_rng(3)
     for k, f in enumerate(frames):
-        t = rng.integers(0, 100000, len(f), dtype=np.uint32) if mode == "deskew" else None
+        t = rng.integers(0, 100000, len(f), dtype=np.uint32) if deskew else None
+        ts = pc2ref.normalize_timestamps(t.astype(np.float64)) if deskew else None
         host, dev = _message(sage, fields, step, f, t), _message(sage, fields, step, f, t, device=True)
         ra, rb = pipes[0].RegisterFrame(host), pipes[1].RegisterFrame(dev)
-        rc = pipes[2].RegisterFrame(f, pc2ref.normalize_timestamps(t.astype(np.float64))) if mode == "deskew" \
-            else pipes[2].RegisterFrame(f)
+        rc = pipes[2].RegisterFrame(f, ts) if deskew else pipes[2].RegisterFrame(f)
         _same(ra, rc, pipes[0], pipes[2], (k, "host message"))
         _same(rb, rc, pipes[1], pipes[2], (k, "device message"))
-        if mode == "deskew":
-            assert pipes[0].deskew_info()[0] == pipes[1].deskew_info()[0] == (k >= 3)
-        if mode == "dynamic_filter":
+        if mode == "all_on":
+            rd = pipes[3].RegisterFrame(torch.from_numpy(f).to(DEV), timestamps=torch.from_numpy(ts).to(DEV))
+            _same(rd, rc, pipes[3], pipes[2], (k, "device frame"))
+        if deskew:
+            assert all(p.deskew_info()[0] == (k >= 3) for p in pipes), k
+        if dyn:
             info = [p.dynamic_filter_info() for p in pipes]
             assert info[2]["vehicle_points"] > 0
             for key in ("vehicle_points", "landmark_points", "clusters", "clusters_kept", "points_removed"):
-                assert info[0][key] == info[1][key] == info[2][key], (k, key)
-        if mode == "key_frames":
+                assert all(i[key] == info[2][key] for i in info), (k, key)
+        if keys:
             info = [p.key_frame_info() for p in pipes]
             for key in ("is_key_frame", "key_frame_index", "key_frames", "key_occupied", "intersect"):
-                assert info[0][key] == info[1][key] == info[2][key], (k, key)
-    assert np.array_equal(_bits(pipes[0].poses()), _bits(pipes[2].poses()))
-    assert np.array_equal(_bits(pipes[1].poses()), _bits(pipes[2].poses()))
-    assert np.array_equal(_bits(pipes[0].LocalMap()), _bits(pipes[2].LocalMap()))
-    if mode == "key_frames":
+                assert all(i[key] == info[2][key] for i in info), (k, key)
+    for p in others:
+        assert np.array_equal(_bits(p.poses()), _bits(pipes[2].poses()))
+        assert np.array_equal(_bits(p.LocalMap()), _bits(pipes[2].LocalMap()))
+    if keys:
         assert pipes[2].key_frame_info()["key_frames"] >= 1
-        assert np.array_equal(pipes[0].key_frame_grid(), pipes[2].key_frame_grid())
+        for p in others:
+            assert np.array_equal(p.key_frame_grid(), pipes[2].key_frame_grid())
 
 
 @pytest.mark.gpu
