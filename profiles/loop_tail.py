@@ -98,6 +98,19 @@ if hasattr(sage.lib(), "sageicp_debug_loop_waves"):
         simd = ((meta >> np.uint64(4)) & np.uint64(3)).astype(int)
         slot = (meta & np.uint64(0xF)).astype(int)
         print("iteration %d, first units of the %d waves of a workgroup:" % (it, nwv))
+        if hasattr(sage.lib(), "sageicp_debug_loop_wave_pose"):
+            # the hop the staged first pass is about: the workgroup's poller holds the pose -> a wave's first pass reaches its
+            # first instruction that needs the pose (the stamp in front of make_query), over all waves with a first unit
+            wp = np.zeros((IT, WG, 8), dtype=np.uint64)
+            sage.lib().sageicp_debug_loop_wave_pose(wp.ctypes.data_as(C.c_void_p))
+            for jt in (6, 12, 20):
+                if jt >= min(IT, st.iterations):
+                    continue
+                use = wp[jt][used][:, :nwv].astype(np.float64) / 100.0
+                heldw = wg[jt - 1, used, 1][:, None]
+                hop = (use - heldw)[(wv[jt][used][:, :nwv, 0] > 0) & (use > 0)]
+                print("   iteration %d: pose held by the workgroup -> first pose-dependent instruction of a wave's first pass: p10 %.2f p50 %.2f p90 %.2f p99 %.2f p100 %.2f us (%d waves)"
+                      % (jt, q(hop, .1), q(hop, .5), q(hop, .9), q(hop, .99), hop.max(), hop.size))
         for k in range(nwv):
             print("   wave %d: SIMD histogram %s | slot histogram %s | unit taken histogram %s | start p50 %.2f | end p10 %.2f p50 %.2f p90 %.2f p100 %.2f"
                   % (k, np.bincount(simd[:, k], minlength=4).tolist(), np.bincount(slot[:, k], minlength=10).tolist(),

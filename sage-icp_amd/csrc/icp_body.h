@@ -115,12 +115,30 @@ __device__ __forceinline__ bool reduce_argmin(double best, unsigned bkey, bool v
     return found;
 }
 
+// k_loop: what a pass holds when it reaches its first use of the pose — the front of the body, which k_loop runs in
+// front of its wait for that pose (HALF below).  One member per value, no vectors: what is read from LDS as four words and
+// carried as four words stays a register quadruple to the allocator, alive as long as its longest-lived word — the label
+// lives through the scans, and its quadruple went to scratch memory.
+struct LoopStaged {
+    unsigned qslot;            // the query's slot in the workgroup (its row and its state record)
+    double fx, fy, fz, fl;     // the frame point
+    unsigned prev_key, prev_off;               // the previous answer
+    unsigned kx, ky, kz, occ;  // the home voxel the row was built for | the row's occupancy
+    int pli;                   // the query's label class
+};
+
 // PERSIST (k_loop): the body runs on group `G` — rows and per-query state in LDS — with the pose from
 // `pose` (LDS: R[9], t[3]); nothing is read from or written to the global rows / nn_prev arrays;
 // the body ends with the group's sums added to the workgroup's accumulators G->wgacc.
-template <int LW, bool FUSED, bool FILT, bool PERSIST = false, bool FLATQ = false>
-__device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, LoopGroup *G = nullptr, const double *pose = nullptr) {
+// HALF (k_loop): the pass is cut at the line where the pose is first used.  1, the stage half: everything in front of
+// that line — the lane, the block's slot from `perm`, the query's state record, the buffer resources, the label class —
+// into `S`, and nothing else: no store, no use of `pose`.  2, the run half: from make_query on, out of `S`.  0: both,
+// back to back (k_icp).
+template <int LW, bool FUSED, bool FILT, bool PERSIST = false, bool FLATQ = false, int HALF = 0>
+__device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, LoopGroup *G = nullptr, const double *pose = nullptr,
+                                         LoopStaged *S = nullptr) {
     static_assert(!PERSIST || FUSED, "the persistent loop always accumulates");
+    static_assert(PERSIST ? (HALF == 1 || HALF == 2) : HALF == 0, "k_loop runs the pass in two halves, k_icp in one");
     constexpr int W = 1 << LW;                 // lanes per query
     constexpr int QW = 64 >> LW;               // queries per wave
     constexpr int SH = 5;                      // points are addressed by byte offset
@@ -164,8 +182,12 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
     // aligned group of lanes, which is all the exact block sums ask for (wave_terms_to_wgacc).
     unsigned q, qslot = 0u, bslot = 0u;
     if constexpr (PERSIST) {
-        bslot = G->perm[G->unit * (QW / 4) + static_cast<unsigned>(qw >> 2)];
-        qslot = bslot * 4u + (static_cast<unsigned>(qw) & 3u);
+        if constexpr (HALF == 1) {
+            bslot = G->perm[G->unit * (QW / 4) + static_cast<unsigned>(qw >> 2)];
+            qslot = bslot * 4u + (static_cast<unsigned>(qw) & 3u);
+        } else {
+            qslot = S->qslot;
+        }
         q = G->q_first + qslot;
     } else {
         q = wave_id * QW + static_cast<unsigned>(qw);
@@ -197,15 +219,23 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
     if constexpr (PERSIST) {
         // k_loop: everything is already here, in LDS — the state record and the row
         lst = G->state + qslot * kLoopStateWords;
-        const uint4 fa = *reinterpret_cast<const uint4 *>(lst), fb = *reinterpret_cast<const uint4 *>(lst + 4);
-        const uint4 pk = *reinterpret_cast<const uint4 *>(lst + kStPrev);
-        const uint2 ko = *reinterpret_cast<const uint2 *>(lst + kStPrev + 4);
-        f.x = __hiloint2double(static_cast<int>(fa.y), static_cast<int>(fa.x));
-        f.y = __hiloint2double(static_cast<int>(fa.w), static_cast<int>(fa.z));
-        f.z = __hiloint2double(static_cast<int>(fb.y), static_cast<int>(fb.x));
-        f.l = __hiloint2double(static_cast<int>(fb.w), static_cast<int>(fb.z));
-        prev = make_uint2(pk.x, pk.y);
-        rk = make_uint4(pk.z, pk.w, ko.x, ko.y);
+        if constexpr (HALF == 1) {
+            const uint4 fa = *reinterpret_cast<const uint4 *>(lst), fb = *reinterpret_cast<const uint4 *>(lst + 4);
+            const uint4 pk = *reinterpret_cast<const uint4 *>(lst + kStPrev);
+            const uint2 ko = *reinterpret_cast<const uint2 *>(lst + kStPrev + 4);
+            S->qslot = qslot;
+            S->fx = __hiloint2double(static_cast<int>(fa.y), static_cast<int>(fa.x));
+            S->fy = __hiloint2double(static_cast<int>(fa.w), static_cast<int>(fa.z));
+            S->fz = __hiloint2double(static_cast<int>(fb.y), static_cast<int>(fb.x));
+            S->fl = __hiloint2double(static_cast<int>(fb.w), static_cast<int>(fb.z));
+            S->prev_key = pk.x; S->prev_off = pk.y;
+            S->kx = pk.z; S->ky = pk.w; S->kz = ko.x; S->occ = ko.y;
+            S->pli = static_cast<int>(S->fl);
+            return;
+        }
+        f.x = S->fx; f.y = S->fy; f.z = S->fz; f.l = S->fl;
+        prev = make_uint2(S->prev_key, S->prev_off);
+        rk = make_uint4(S->kx, S->ky, S->kz, S->occ);
     } else {
         rk = *reinterpret_cast<const uint4 *>(grow + kRowKey);
         if (FUSED) prev = P.nn_prev[qc];
@@ -231,6 +261,7 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
             if (smem[kWgGo]) return;
         }
     }
+    PROBE_LOOP_POSE_USE(PERSIST, G);
     const Query s = [&]() {
         if constexpr (PERSIST) {
             return make_query<(W >= 4)>(f, pose, pose + 9, 1, P.voxel_size, P.inv_voxel_size, static_cast<unsigned>(lane));
@@ -471,7 +502,7 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
     // travels as a kernel argument so that it sits in scalar registers
     double best = P.dist_init;                 // scaled squared distance
     unsigned bkey = 0xFFFFFFFFu;               // (voxel << 8) | slot: the enumeration order
-    const int pli = static_cast<int>(s.l);
+    const int pli = HALF == 2 ? S->pli : static_cast<int>(s.l);
     const double th = P.sem_th;
     unsigned npairs = 0u;                      // points this query's lanes were handed
 
@@ -801,7 +832,8 @@ __device__ __forceinline__ void icp_body(const IcpParams &P, uint32_t *smem, Loo
         // a (nine voxels, one add and one compare each on top of the shared gy + gz sums), the
         // layers meet in two DPP exchanges.  Same operands, same association: the same mask as
         // the loop below, in 40 instructions instead of 100.
-        const unsigned a = ci & 3u;
+        // (k_loop: from the lane index anew — make_query's copy of these two bits otherwise lives through the first scan)
+        const unsigned a = (PERSIST ? static_cast<unsigned>(lane_now()) : ci) & 3u;
         const double ga = a == 0u ? gx[0] : (a == 2u ? gx[2] : 0.0);
         unsigned layer = 0u;
 #pragma unroll

@@ -564,10 +564,11 @@ constexpr int kLoopMaxWaves = kLoopMaxWavesHost;   // waves per workgroup of k_l
 constexpr unsigned kLoopStripe = kLoopStripeHost;  // workgroups of k_loop per XCD stripe (its grid: a multiple of 32)
 constexpr int kNoVoxel = 0x7FFFFFFF;        // a home voxel no point has (|index| < 2^20): row not built yet
 constexpr unsigned kStPrev = 16, kStKey = 18;
-// LDS of a k_loop workgroup (words).  Its header: arrival counter | next unit | done | the pose of this iteration
+// LDS of a k_loop workgroup (words).  Its header: arrival counter | next unit | done | the iteration the workgroup is in
+// (counted by the wave that closes one; nobody holds the number in a register through a pass) | the pose of this iteration
 // (R[9], t[3]) | the probe builds' counts | the waves' first units | the workgroup's fixed-point accumulators; what
 // follows the header is laid out by LoopLds below.
-constexpr unsigned kLpArrive = 0, kLpNext = 1, kLpDone = 2;
+constexpr unsigned kLpArrive = 0, kLpNext = 1, kLpDone = 2, kLpIter = 3;
 constexpr unsigned kLpPose = 4;                                    // 12 doubles, 16-B aligned
 constexpr unsigned kLpDbg = kLpPose + 24u;                         // probe builds: max points of a query | stale queries | points
 constexpr unsigned kLpFirst = kLpDbg + 4u;                         // per wave: the unit it takes first in every iteration (LoopParams::deal)

@@ -18,8 +18,10 @@ namespace sageicp {
 //                     after the next), [exchanges the sums with the peer GPUs,] solves, composes, tests,
 //                     and publishes the next pose as 25 self-tagged 8-byte granules (tag = iteration
 //                     + 1: the data is the flag, no fence on either side), one copy per XCD;
+//   every wave        behind a barrier (the closing wave has written the next order of the blocks): runs the front of
+//                     its first pass of the next iteration, the part that does not need the pose (icp_body, HALF 1);
 //   wave 0 of every   polls its XCD's granules (one relaxed agent-scope load per lane and pass), hands the
-//   workgroup         pose to its workgroup through LDS;  __syncthreads();  next iteration.
+//   workgroup         pose to its workgroup through LDS;  __syncthreads();  the staged passes go on with the pose.
 // Every word the workgroups share is accessed with agent-scope atomics only.  Every wait is bounded:
 // a timeout raises LoopShared::abort_word and IcpState::loop_aborted, everybody leaves, and the host
 // registers the frame through the launch-per-iteration loop instead (a grid that is not fully
@@ -437,6 +439,7 @@ void k_loop(LoopArgs A) {
         smem[kLpArrive] = 0u;
         smem[kLpNext] = 0u;
         smem[kLpDone] = 0u;
+        smem[kLpIter] = 0u;
         PROBE_LOOP_CLEAR_STATS(smem);
     }
     if (L.deal && (threadIdx.x & 63u) == 0u) {
@@ -502,47 +505,130 @@ void k_loop(LoopArgs A) {
     // k_icp does at its start).  What the compiler can prove invariant it hoists in front of the loop and keeps alive
     // across the pass: at 72 registers that meant 48 B of scratch and 32 scalars parked in a register's lanes, reloaded
     // inside the pass or not as the allocation fell (5 % of c2, profiles/r20/README.md).  tests/test_loop_resources.py
-    // holds the kernels at no scratch.  (icp_body follows the same rule for the values of a pass: icp_body.h.)
+    // holds the kernels at no scratch.  (icp_body follows the same rule for the values of a pass: icp_body.h.)  The
+    // iteration's number is not among them: the workgroup's LDS header has it (kLpIter, counted by the closing wave), and
+    // the two places that need it — the poll's tag, the close's accumulator set — read it there.
 
-    for (int it = 0;; ++it) {
-        auto ka = __builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(ka));
-        // the workgroup's groups, first come first served: a wave held up by a heavy query takes fewer
-        bool dealt = ((const LoopArgs *)(ka))->L.deal != 0;
-        for (;;) {
-            unsigned gi = 0u;
-            if (dealt) {
-                // (this wave's first unit is fixed by where it sits; the units beyond one per wave go first come first served)
-                dealt = false;
-                gi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(smem[kLpFirst + (opaque_s(who) & 7u)])));
-                if (gi >= opaque_s(gcnt)) continue;
-            } else {
-                if (lane_now() == 0)
-                    gi = __hip_atomic_fetch_add(&smem[kLpNext], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                gi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(gi)));
-                if (gi >= opaque_s(gcnt)) break;
-            }
-            // (the pass's arguments, and where the workgroup's LDS lies, from the kernel-argument segment: see above)
-            auto kb = __builtin_amdgcn_kernarg_segment_ptr();
-            asm volatile("" : "+s"(kb));
-            const LoopArgs &B = *(const LoopArgs *)(kb);
-            if (B.L.prio) loop_set_priority(gi, B.L.nw, B.L.prio);
-            PROBE_LOOP_UNIT_BEGIN(it, gi, B.L.nw, t_unit);
+    for (;;) {
+        PROBE_LOOP_IT(it, smem);
+        // The workgroup's units.  A pass is cut in two (icp_body, HALF): the half that does not need the pose — arguments,
+        // unit, priority, LDS layout, `perm`, the query's state record — and the rest.  A wave's FIRST pass of an iteration
+        // is staged in front of the wait for that pose: the wave leaves the barrier behind the wait with its query in
+        // registers, and the next thing it does is read the pose.  The units beyond one per wave go first come first
+        // served, staged behind the run before: a wave held up by a heavy query takes fewer.  (One copy of the run half
+        // in the code; the stage half, some forty instructions, stands twice.)
+        // ("no unit" is a value of `gi`, and the staged values are set on every path, also the one that stages nothing: a
+        // flag sat in a register pair all through the run half, and a value left open on one path into the wait is, to the
+        // register allocator, one that lives round the loop)
+        constexpr unsigned kNoUnit = 0xFFFFFFFFu;
+        LoopStaged S{};
+        PROBE_LOOP_UNIT_VAR(t_unit);
+        // where unit `u` of the workgroup lies, from the arguments `B` (the LDS layout is not carried from the stage half
+        // to the run half: each lays it out for itself, beside its other scalar work and under its LDS reads — carried, it
+        // was eight more scalars to hold through the run half, and k_loop<2, true> spilled four)
+        auto group_of = [&](unsigned u, const LoopArgs &B) {
             const LoopLds<unsigned> lds(LW, static_cast<unsigned>(B.L.nw), static_cast<unsigned>(B.L.gpw));
-            const unsigned first = opaque_s(g0);
+            const unsigned first_unit = opaque_s(g0);
             LoopGroup G;
             G.rows = smem + lds.rows;
             G.state = smem + lds.state;
             G.perm = smem + lds.perm;
             G.work = smem + lds.work;
-            G.unit = gi;
+            G.unit = u;
             G.red = reinterpret_cast<double *>(smem + lds.red + (opaque_s(who) & 7u) * loop_red_words());
             G.wgacc = reinterpret_cast<unsigned long long *>(smem + kLpAcc);
-            G.q_first = first * QW;
-            G.slot = first + gi;
-            PROBE_LOOP_PASS_BEGIN(lp, G);
-            icp_body<LW, true, FILT, true>(B.P, smem, &G, s_pose);
-            PROBE_LOOP_UNIT_END(lp, G, it, gi, B.L.nw, static_cast<int>(opaque_s(who) & 7u), lane_now(), t_unit);
+            G.q_first = first_unit * QW;
+            G.slot = first_unit + u;
+            return G;
+        };
+        // takes unit `u`: the wave's priority, the stage half of the pass
+        auto stage = [&](unsigned u) {
+            // (the pass's arguments, and where the workgroup's LDS lies, from the kernel-argument segment: see above)
+            auto kb = __builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(kb));
+            const LoopArgs &B = *(const LoopArgs *)(kb);
+            if (B.L.prio) loop_set_priority(u, B.L.nw, B.L.prio);
+            PROBE_LOOP_UNIT_BEGIN(it, u, B.L.nw, t_unit);
+            LoopGroup G = group_of(u, B);
+            icp_body<LW, true, FILT, true, false, 1>(B.P, smem, &G, nullptr, &S);
+        };
+        auto ka = __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        unsigned gi = kNoUnit;
+        // (this wave's first unit is fixed by where it sits; without the deal, or with more waves than units, it stages
+        // nothing and goes to the counter behind the barrier)
+        if (((const LoopArgs *)(ka))->L.deal) {
+            gi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(smem[kLpFirst + (opaque_s(who) & 7u)])));
+            if (gi >= opaque_s(gcnt)) gi = kNoUnit;
+        }
+        if (gi != kNoUnit) stage(gi);
+        {
+            const LoopParams &L = ((const LoopArgs *)(ka))->L;
+            // the pose of this iteration, for this workgroup (the first iteration's is the set-up's)
+            // (the iteration's number, as the wait needs it — test, tag —, from the workgroup's header)
+            const unsigned itn = (opaque_s(who) & 7u) == 0u ? static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(smem[kLpIter]))) : 0u;
+            if (itn != 0u) {
+                LoopShared *sh = L.sh;
+                const int lane = lane_now();
+                const unsigned wg = opaque_s(who) >> 3;
+                const unsigned long long tag = static_cast<unsigned long long>(itn);
+                const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+                unsigned long long g = tag << 32;
+                bool aborted = false;
+                for (;;) {
+                    if (lane < kLoopPoseGranules) g = ld_agent(&sh->pose[loop_pose_copy(L.pose_map, wg)][lane]);
+                    const bool ok = (g >> 32) == tag;
+                    if (__all(ok)) break;
+                    unsigned long long ab = 0ull;
+                    if (lane == 0) ab = ld_agent(&sh->abort_word[0]);
+                    const bool late = __builtin_amdgcn_s_memrealtime() - t0 > L.timeout_ticks;
+                    if (__any(ab != 0ull) || late) {
+                        if (lane == 0 && late) {
+                            st_agent(&sh->abort_word[0], 1ull);
+                            L.st->loop_aborted = 1;
+                        }
+                        aborted = true;
+                        break;
+                    }
+                    // (more than a thousand workgroups wait here for most of an iteration — since the pose has a copy per
+                    // XCD, some two hundred per copy, on four cache lines of their own: a pass every ~0.3 us each keeps
+                    // the L2 that serves them, and the accumulators the solving wave is reading, quiet)
+                    __builtin_amdgcn_s_sleep(SAGE_LOOP_POLL_SLEEP);
+                    // (a big grid backs off twice as long: c2's 1,664 workgroups 30.7 -> 30.3 us per iteration, flat from there
+                    // to six times as long; c1's 640 prefer the short one — same-box A/B, profiles/r05/poll_sleep.txt, taken
+                    // when all of them polled ONE block; with a copy per XCD: profiles/r15/README.md)
+                    if (L.wgs > 1024) __builtin_amdgcn_s_sleep(SAGE_LOOP_POLL_SLEEP);
+                }
+                if (aborted) {
+                    if (lane == 0) smem[kLpDone] = 2u;
+                } else {
+                    if (lane < 24) smem[kLpPose + static_cast<unsigned>(lane)] = static_cast<uint32_t>(g);
+                    if (lane == 24) smem[kLpDone] = static_cast<uint32_t>(g);
+                }
+                LOOP_STAMP_WG(itn - 1u, 1);
+            }
+        }
+        PROBE_LOOP_WAIT_BEGIN(t_b);
+        __syncthreads();
+        PROBE_LOOP_WAITED(lp, t_b);
+        // (a wave that leaves here has staged and written nothing)
+        if (smem[kLpDone]) break;
+        for (;;) {
+            if (gi != kNoUnit) {
+                auto kb = __builtin_amdgcn_kernarg_segment_ptr();
+                asm volatile("" : "+s"(kb));
+                const LoopArgs &B = *(const LoopArgs *)(kb);
+                LoopGroup G = group_of(opaque_s(gi), B);
+                PROBE_LOOP_PASS_BEGIN(lp, G);
+                icp_body<LW, true, FILT, true, false, 2>(B.P, smem, &G, reinterpret_cast<const double *>(smem + kLpPose), &S);
+                PROBE_LOOP_UNIT_END(lp, G, it, gi, B.L.nw, static_cast<int>(opaque_s(who) & 7u), lane_now(), t_unit);
+            }
+            gi = 0u;
+            if (lane_now() == 0)
+                gi = __hip_atomic_fetch_add(&smem[kLpNext], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            gi = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(gi)));
+            if (gi >= opaque_s(gcnt)) break;
+            stage(gi);
         }
         PROBE_LOOP_MARK(t_a);
         // the close: its arguments and its lane index anew (nothing of the passes' is kept for it)
@@ -561,11 +647,13 @@ void k_loop(LoopArgs A) {
         prior = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(prior)));
         const bool last = prior == static_cast<unsigned>(L.nw) - 1u;
         if (last) {
-            // this wave closes the workgroup's iteration
+            // this wave closes the workgroup's iteration, and counts it
+            const int it = __builtin_amdgcn_readfirstlane(static_cast<int>(smem[kLpIter]));
             wgacc_flush<true, true>(reinterpret_cast<unsigned long long *>(smem + kLpAcc), &sh->acc[it & 1][wg & (kLoopReplicas - 1)][0],
                                     &sh->acc[it & 1][0][kAccWords - 1]);
             if (lane == 0) {                   // everybody is in: ready for the next iteration
                 smem[kLpArrive] = 0u;
+                smem[kLpIter] = static_cast<unsigned>(it) + 1u;
                 smem[kLpNext] = L.deal ? static_cast<unsigned>(L.nw) : 0u;
             }
             // The next iteration's order of the workgroup's blocks: heaviest first, by what they cost in this one (a
@@ -593,48 +681,12 @@ void k_loop(LoopArgs A) {
             PROBE_LOOP_WG_INFO(smem, it, lane);
             LOOP_STAMP_WG(it, 0);
         }
-        if ((me & 7u) == 0u) {
-            // the next pose, for this workgroup
-            const unsigned long long tag = static_cast<unsigned long long>(it) + 1ull;
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            unsigned long long g = tag << 32;
-            bool aborted = false;
-            for (;;) {
-                if (lane < kLoopPoseGranules) g = ld_agent(&sh->pose[loop_pose_copy(L.pose_map, wg)][lane]);
-                const bool ok = (g >> 32) == tag;
-                if (__all(ok)) break;
-                unsigned long long ab = 0ull;
-                if (lane == 0) ab = ld_agent(&sh->abort_word[0]);
-                const bool late = __builtin_amdgcn_s_memrealtime() - t0 > L.timeout_ticks;
-                if (__any(ab != 0ull) || late) {
-                    if (lane == 0 && late) {
-                        st_agent(&sh->abort_word[0], 1ull);
-                        L.st->loop_aborted = 1;
-                    }
-                    aborted = true;
-                    break;
-                }
-                // (more than a thousand workgroups wait here for most of an iteration — since the pose has a copy per
-                // XCD, some two hundred per copy, on four cache lines of their own: a pass every ~0.3 us each keeps
-                // the L2 that serves them, and the accumulators the solving wave is reading, quiet)
-                __builtin_amdgcn_s_sleep(SAGE_LOOP_POLL_SLEEP);
-                // (a big grid backs off twice as long: c2's 1,664 workgroups 30.7 -> 30.3 us per iteration, flat from there
-                // to six times as long; c1's 640 prefer the short one — same-box A/B, profiles/r05/poll_sleep.txt, taken
-                // when all of them polled ONE block; with a copy per XCD: profiles/r15/README.md)
-                if (L.wgs > 1024) __builtin_amdgcn_s_sleep(SAGE_LOOP_POLL_SLEEP);
-            }
-            if (aborted) {
-                if (lane == 0) smem[kLpDone] = 2u;
-            } else {
-                if (lane < 24) reinterpret_cast<uint32_t *>(s_pose)[lane] = static_cast<uint32_t>(g);
-                if (lane == 24) smem[kLpDone] = static_cast<uint32_t>(g);
-            }
-            LOOP_STAMP_WG(it, 1);
-        }
-        PROBE_LOOP_CLOSED(lp, last, t_a, t_b);
+        PROBE_LOOP_CLOSED(lp, last, t_a);
+        PROBE_LOOP_WAIT_BEGIN(t_c);
+        // the closing wave has written the next iteration's `perm`, unit counter and arrival count: nobody stages before
+        // (the waves waited at the barrier behind the poll for just as long before: the pose cannot come before the close)
         __syncthreads();
-        PROBE_LOOP_WAITED(lp, t_b);
-        if (smem[kLpDone]) break;
+        PROBE_LOOP_WAITED(lp, t_c);
     }
     PROBE_LOOP_END(lp);
 }

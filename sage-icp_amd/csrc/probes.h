@@ -117,7 +117,9 @@ extern "C" void sageicp_debug_nn_phases(unsigned long long out[16], int reset) {
 // -------------------------------------------------------------------------------------------- SAGE_LOOP_TIMING
 #ifdef SAGE_LOOP_TIMING
 // (icp_body<PERSIST>: cycles per phase into the pass's LoopGroup `G`, summed by k_loop; `persist`: a constant expression)
-#define PROBE_LOOP_GROUP_FIELDS unsigned long long ph[8], tprev;      /* LoopGroup: cycles per phase of the body in this pass | the last stamp */
+#define PROBE_LOOP_GROUP_FIELDS unsigned long long ph[8], tprev, tpose;      /* LoopGroup: cycles per phase of the body in this pass | the last stamp | 100-MHz stamp of the pass's first use of the pose */
+// (icp_body<PERSIST>, in front of make_query: the first instruction of the pass that needs the pose)
+#define PROBE_LOOP_POSE_USE(persist, G) do { if constexpr (persist) (G)->tpose = __builtin_amdgcn_s_memrealtime(); } while (0)
 #define LP_T(persist, G, i) do { if constexpr (persist) { const unsigned long long _t = __builtin_amdgcn_s_memtime(); (G)->ph[i] += _t - (G)->tprev; (G)->tprev = _t; } } while (0)
 // per workgroup and iteration: max points of a query | stale queries | points (LDS words kLpDbg ..)
 #define PROBE_LOOP_WAVE_STATS(smem, valid, ci, npairs, stale, lane)                                                        \
@@ -142,6 +144,7 @@ __device__ unsigned g_loop_wginfo[kLoopTimedIters][kLoopTimedWgs][4];     // HW_
 __device__ unsigned long long g_loop_solver[kLoopTimedIters][4];
 __device__ unsigned long long g_loop_solver2[kLoopTimedIters][4];      // inside the solve: after the solve | the exponential (and the sqrt of the step norm) | the composition | the norm test
 __device__ unsigned long long g_loop_wave[kLoopTimedIters][kLoopTimedWgs][8][2];      // per wave: its FIRST unit of the iteration: end stamp | start stamp (low 32) << 32 ... see PROBE_LOOP_UNIT_END
+__device__ unsigned long long g_loop_wave_pose[kLoopTimedIters][kLoopTimedWgs][8];    // ... and when that pass first used the pose (PROBE_LOOP_POSE_USE)
 __device__ unsigned long long g_loop_phase[16];     // [0..7] cycles per body phase, [8] wait for the pose, [9] closing a workgroup, [10] group passes
 #define LOOP_STAMP_SOLVER(it, k) do { if ((it) < kLoopTimedIters && (threadIdx.x & 63u) == 0u) g_loop_solver[it][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #define LOOP_STAMP_SOLVER2(it, k) do { if ((it) < kLoopTimedIters && (threadIdx.x & 63u) == 0u) g_loop_solver2[it][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -152,10 +155,13 @@ __device__ unsigned long long g_loop_phase[16];     // [0..7] cycles per body ph
     unsigned long long lp##_ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};                                                              \
     unsigned long long lp##_t_wait = 0, lp##_t_close = 0, lp##_n_pass = 0
 #define PROBE_LOOP_CLEAR_STATS(smem) { (smem)[kLpDbg] = 0u; (smem)[kLpDbg + 1] = 0u; (smem)[kLpDbg + 2] = 0u; }
-// a wave has taken unit `gi` (declares `t_unit`, the stamp) | the pass on it starts | ... is over
+// the iteration's number under the name given, for the stamps of the passes (k_loop keeps it in its LDS header)
+#define PROBE_LOOP_IT(it, smem) const int it = __builtin_amdgcn_readfirstlane(static_cast<int>((smem)[kLpIter]))
+// the stamp `t_unit` | a wave has taken unit `gi` (sets it; the stage half follows) | the run half of the pass on it starts | ... is over
+#define PROBE_LOOP_UNIT_VAR(t_unit) unsigned long long t_unit = 0
 #define PROBE_LOOP_UNIT_BEGIN(it, gi, nw, t_unit)                                                                          \
     if ((gi) >= static_cast<unsigned>(nw)) LOOP_STAMP_WG(it, 2);                                                           \
-    const unsigned long long t_unit = __builtin_amdgcn_s_memrealtime()
+    t_unit = __builtin_amdgcn_s_memrealtime()
 #define PROBE_LOOP_PASS_BEGIN(lp, G)                                                                                       \
     {                                                                                                                      \
         for (int i = 0; i < 8; ++i) (G).ph[i] = 0;                                                                         \
@@ -170,6 +176,7 @@ __device__ unsigned long long g_loop_phase[16];     // [0..7] cycles per body ph
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));                                               \
             g_loop_wave[it][blockIdx.x][wv][0] = __builtin_amdgcn_s_memrealtime();                                         \
             g_loop_wave[it][blockIdx.x][wv][1] = ((t_unit) << 24) | (static_cast<unsigned long long>((gi) & 0xFFu) << 16) | (hw & 0xFFFFu); \
+            g_loop_wave_pose[it][blockIdx.x][wv] = (G).tpose;                                                              \
         }                                                                                                                  \
         for (int i = 0; i < 8; ++i) lp##_ph[i] += (G).ph[i];                                                               \
     }
@@ -189,10 +196,10 @@ __device__ unsigned long long g_loop_phase[16];     // [0..7] cycles per body ph
             (smem)[kLpDbg] = 0u; (smem)[kLpDbg + 1] = 0u; (smem)[kLpDbg + 2] = 0u;                                         \
         }                                                                                                                  \
     }
-// before the barrier (declares `t_b`; `t_a`: the mark after the wave's last pass) | after it
-#define PROBE_LOOP_CLOSED(lp, last, t_a, t_b)                                                                              \
-    const unsigned long long t_b = __builtin_amdgcn_s_memtime();                                                           \
-    if (last) lp##_t_close += t_b - (t_a)
+// behind the close (`t_a`: the mark after the wave's last pass) | before a barrier (declares `t_b`) | after it
+#define PROBE_LOOP_CLOSED(lp, last, t_a)                                                                                   \
+    if (last) lp##_t_close += __builtin_amdgcn_s_memtime() - (t_a)
+#define PROBE_LOOP_WAIT_BEGIN(t_b) const unsigned long long t_b = __builtin_amdgcn_s_memtime()
 #define PROBE_LOOP_WAITED(lp, t_b) lp##_t_wait += __builtin_amdgcn_s_memtime() - (t_b)
 #define PROBE_LOOP_END(lp)                                                                                                 \
     {                                                                                                                      \
@@ -216,6 +223,9 @@ extern "C" void sageicp_debug_loop_phases(unsigned long long *out, int reset) {
 extern "C" void sageicp_debug_loop_waves(unsigned long long *out) {
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_loop_wave), sizeof(unsigned long long) * kLoopTimedIters * kLoopTimedWgs * 8 * 2);
 }
+extern "C" void sageicp_debug_loop_wave_pose(unsigned long long *out) {
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_loop_wave_pose), sizeof(unsigned long long) * kLoopTimedIters * kLoopTimedWgs * 8);
+}
 extern "C" void sageicp_debug_loop_info(unsigned *info) {
     (void)hipMemcpyFromSymbol(info, HIP_SYMBOL(g_loop_wginfo), sizeof(unsigned) * kLoopTimedIters * kLoopTimedWgs * 4);
 }
@@ -231,12 +241,16 @@ extern "C" void sageicp_debug_loop_times(unsigned long long *wg, unsigned long l
 #define LOOP_STAMP_WG(it, k) do { } while (0)
 #define PROBE_LOOP_BEGIN(lp) ((void)0)
 #define PROBE_LOOP_CLEAR_STATS(smem) ((void)0)
+#define PROBE_LOOP_POSE_USE(persist, G) do { } while (0)
+#define PROBE_LOOP_UNIT_VAR(t_unit) ((void)0)
+#define PROBE_LOOP_IT(it, smem) ((void)0)
 #define PROBE_LOOP_UNIT_BEGIN(it, gi, nw, t_unit) ((void)0)
 #define PROBE_LOOP_PASS_BEGIN(lp, G) ((void)0)
 #define PROBE_LOOP_UNIT_END(lp, G, it, gi, nw, wv, lane, t_unit) ((void)0)
 #define PROBE_LOOP_MARK(t) ((void)0)
 #define PROBE_LOOP_WG_INFO(smem, it, lane) ((void)0)
-#define PROBE_LOOP_CLOSED(lp, last, t_a, t_b) ((void)0)
+#define PROBE_LOOP_CLOSED(lp, last, t_a) ((void)0)
+#define PROBE_LOOP_WAIT_BEGIN(t_b) ((void)0)
 #define PROBE_LOOP_WAITED(lp, t_b) ((void)0)
 #define PROBE_LOOP_END(lp) ((void)0)
 #define PROBE_LOOP_WAVE_STATS(smem, valid, ci, npairs, stale, lane) do { } while (0)
