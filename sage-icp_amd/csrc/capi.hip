@@ -38,6 +38,272 @@ const char *env_cached(const char *name) {
 std::atomic<int> g_reference_order{1};
 }  // namespace sageicp
 
+// ---- helpers that capi_pipeline.hip calls too (capi_internal.h) ------------------------------------------------------
+namespace sageicp_impl {
+// ---- rows in the caller's device memory: frames in (ingest.hip), outputs out (egress.hip, egress.h) ---------------
+static size_t dtype_bytes(int32_t t) {
+    switch (t) {
+    case SAGEICP_DTYPE_FLOAT32: return 4;
+    case SAGEICP_DTYPE_FLOAT64: return 8;
+    case SAGEICP_DTYPE_UINT8: return 1;
+    case SAGEICP_DTYPE_INT32: return 4;
+    case SAGEICP_DTYPE_INT64: return 8;
+    default: return 0;
+    }
+}
+
+// the device whose memory p is, as this library's runtime sees it (false: not device memory — host, pinned or managed
+// memory, or a pointer of another HIP runtime loaded into the process, which is unknown here)
+static bool device_of(const void *p, int *device) {
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    (void)hipGetLastError();            // an unknown pointer leaves an error behind that the next call must not see
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice) return false;
+    *device = at.device;
+    return true;
+}
+
+// the first and the last byte of an extent must be device memory of `device`
+int check_extent(const void *p, uint64_t bytes, int device, const char *what) {
+    const char *ends[2] = {static_cast<const char *>(p), static_cast<const char *>(p) + bytes - 1};
+    for (const char *q : ends) {
+        int d = -1;
+        if (!device_of(q, &d))
+            return fail(SAGEICP_ERR_INVALID, std::string(what) + " is not device memory of this process's HIP runtime "
+                                             "(host, pinned and managed memory are refused, not copied)");
+        if (d != device)
+            return fail(SAGEICP_ERR_INVALID, std::string(what) + " lives on device " + std::to_string(d) +
+                                             ", the handle on device " + std::to_string(device));
+    }
+    return SAGEICP_OK;
+}
+
+// a caller's stream (NULL: the null stream) must be one of `device`
+int check_stream(void *stream, int device) {
+    if (!stream) return SAGEICP_OK;
+    int sd = -1;
+    const hipError_t e = hipStreamGetDevice(static_cast<hipStream_t>(stream), &sd);
+    (void)hipGetLastError();
+    if (e != hipSuccess || sd != device) return fail(SAGEICP_ERR_INVALID, "stream is not a stream of the handle's device");
+    return SAGEICP_OK;
+}
+
+// Strided rows in a caller's device memory: a frame's n (sageicp_device_frame) or a destination's cap
+// (sageicp_device_points).  Host-side only: the kernels take IngestArgs / EgressArgs.
+struct CallerRows {
+    const void *xyz;
+    uint64_t xyz_stride;
+    int32_t xyz_dtype;
+    const void *label;
+    uint64_t label_stride;
+    int32_t label_dtype;
+    uint64_t rows;
+};
+// what differs between a frame and a destination
+struct RowRules {
+    const char *prefix;                 // of the messages
+    unsigned label_dtypes;              // bit t: SAGEICP_DTYPE t is a valid label_dtype
+    const char *label_dtypes_text;
+    uint64_t max_rows;                  // (refused as a frame that is too large)
+};
+static const RowRules kFrameRows{
+    "device frame: ", 1u << SAGEICP_DTYPE_UINT8 | 1u << SAGEICP_DTYPE_INT32 | 1u << SAGEICP_DTYPE_INT64,
+    "SAGEICP_DTYPE_UINT8, _INT32 or _INT64", kMaxQueries};
+static const RowRules kPointsRows{
+    "device points: ", 1u << SAGEICP_DTYPE_UINT8 | 1u << SAGEICP_DTYPE_INT32 | 1u << SAGEICP_DTYPE_INT64 |
+                       1u << SAGEICP_DTYPE_FLOAT32 | 1u << SAGEICP_DTYPE_FLOAT64,
+    "SAGEICP_DTYPE_UINT8, _INT32, _INT64, _FLOAT32 or _FLOAT64", std::numeric_limits<uint64_t>::max()};
+
+// Everything about caller rows that can be known before the stream is touched or anything launched: the layout first
+// (no device needed), then where the memory of the rows (and of the n timestamps `ts` that will be read, if given)
+// lives, then the stream.  found: an entry without a handle works on the device xyz lives on (`device` is not read): it
+// is looked up once the layout has passed, and stored there.
+static int check_rows(const CallerRows &r, const RowRules &k, const double *ts, void *stream, int device,
+                      int *found = nullptr) {
+    const std::string pre = k.prefix;
+    if (r.rows && !r.xyz) return fail(SAGEICP_ERR_INVALID, pre + "xyz is NULL");
+    const size_t ex = r.xyz_dtype == SAGEICP_DTYPE_FLOAT32 || r.xyz_dtype == SAGEICP_DTYPE_FLOAT64 ? dtype_bytes(r.xyz_dtype) : 0;
+    if (!ex) return fail(SAGEICP_ERR_INVALID, pre + "xyz_dtype must be SAGEICP_DTYPE_FLOAT32 or _FLOAT64");
+    const uint64_t cols = r.label ? 3 : 4;
+    if (r.xyz_stride < cols * ex || r.xyz_stride % ex)
+        return fail(SAGEICP_ERR_INVALID, pre + (r.label ? "xyz_stride must be a multiple of the element size and at least 3 "
+                                                          "elements"
+                                                        : "xyz_stride must be a multiple of the element size and at least 4 "
+                                                          "elements (the label is column 3)"));
+    size_t el = 0;
+    if (r.label) {
+        el = dtype_bytes(r.label_dtype) && ((k.label_dtypes >> r.label_dtype) & 1u) ? dtype_bytes(r.label_dtype) : 0;
+        if (!el) return fail(SAGEICP_ERR_INVALID, pre + "label_dtype must be " + k.label_dtypes_text);
+        if (r.label_stride < el || r.label_stride % el)
+            return fail(SAGEICP_ERR_INVALID, pre + "label_stride must be a positive multiple of the label's size");
+    }
+    if (r.rows > k.max_rows) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
+    if (!r.rows) return SAGEICP_OK;
+    int rc = require_device();
+    if (rc) return rc;
+    if (found) {                        // (memory that is not device memory is refused just below)
+        device = 0;
+        (void)device_of(r.xyz, &device);
+        *found = device;
+    }
+    rc = check_extent(r.xyz, (r.rows - 1) * r.xyz_stride + cols * ex, device, (pre + "xyz").c_str());
+    if (!rc && r.label) rc = check_extent(r.label, (r.rows - 1) * r.label_stride + el, device, (pre + "label").c_str());
+    if (!rc && ts) rc = check_extent(ts, r.rows * sizeof(double), device, "timestamps");
+    return rc ? rc : check_stream(stream, device);
+}
+
+int check_device_frame(const sageicp_device_frame *f, const double *ts, void *stream, int device, int *found) {
+    if (!f) return fail(SAGEICP_ERR_INVALID, "null device frame");
+    return check_rows({f->xyz, f->xyz_stride, f->xyz_dtype, f->label, f->label_stride, f->label_dtype, f->n}, kFrameRows,
+                      ts, stream, device, found);
+}
+
+int check_device_points(const sageicp_device_points *d, void *stream, int device) {
+    if (!d) return fail(SAGEICP_ERR_INVALID, "null destination");
+    return check_rows({d->xyz, d->xyz_stride, d->xyz_dtype, d->label, d->label_stride, d->label_dtype, d->cap},
+                      kPointsRows, nullptr, stream, device);
+}
+
+static EgressArgs egress_args(const sageicp_device_points &d, int *flags) {
+    EgressArgs a{};
+    a.xyz = static_cast<unsigned char *>(d.xyz);
+    a.xyz_stride = d.xyz_stride;
+    a.xyz_dtype = d.xyz_dtype;
+    a.label = static_cast<unsigned char *>(d.label);
+    a.label_stride = d.label_stride;
+    a.label_dtype = d.label_dtype;
+    a.cap = d.cap;
+    a.flags = flags;
+    return a;
+}
+
+// The rows that write(EgressArgs) enqueues on s into a caller's destination, behind a zeroed label-range flag: waited
+// for, then the flag they may have raised read.  Synchronous also when write fails part-way: nothing this call
+// enqueued runs on once it has returned.
+int egress_into(DevBuf<int> &flag, const sageicp_device_points &dst, hipStream_t s,
+                       const std::function<int(const EgressArgs &)> &write) {
+    if (!flag) HIPCHK(flag.reserve(1));
+    HIPCHK(hipMemsetAsync(flag.data(), 0, sizeof(int), s));
+    if (int rc = write(egress_args(dst, flag.data()))) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    int flags = 0;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&flags, flag.data(), sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (flags & kEgressLabelRange)
+        return fail(SAGEICP_ERR_INVALID, "a label does not fit the destination's label type (static_cast<int64_t>(label) "
+                                         "out of its range)");
+    return SAGEICP_OK;
+}
+
+// RegisterFrame of n points already on `device` (an uploaded frame, or the pipeline's source cloud)
+int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
+                             double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
+                             sageicp_stats *stats) {
+    if (!m || !init || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    if (device != m->device) return fail(SAGEICP_ERR_INVALID, "frame and map live on different devices");
+    if (comm && comm->device != m->device) return fail(SAGEICP_ERR_INVALID, "comm and map live on different devices");
+    const double t0 = now_us();
+    if (map_is_empty(m)) {
+        std::memcpy(pose_out, init, 56);
+        if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->n_queries = n; }
+        return SAGEICP_OK;
+    }
+    if (!m->replicas.empty()) {
+        if (comm) return fail(SAGEICP_ERR_INVALID, "a map that spans several devices shards the frame itself");
+        return register_sharded(m, nullptr, d_frame, n, init, max_dist, kernel, sem_th, pose_out, stats, t0);
+    }
+    int rc = sync_mirror(m);
+    if (rc) return rc;
+    const double us_upload = now_us() - t0;
+    return run_icp(m, d_frame, n, init, max_dist, kernel, sem_th, comm, pose_out, stats, us_upload, t0);
+}
+
+// ---- occupancy grids (keyframe.hip) --------------------------------------------------------------------------------
+// the grid of validated params (include/sageicp.h: what is refused)
+int occ_grid_from(const sageicp_occupancy_params *prm, OccGrid &g) {
+    if (!prm) return fail(SAGEICP_ERR_INVALID, "null occupancy params");
+    for (int a = 0; a < 3; ++a) {
+        const double lo = prm->bounds[a][0], hi = prm->bounds[a][1];
+        if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(SAGEICP_ERR_INVALID, "occupancy bounds are not finite");
+        if (!(lo < hi)) return fail(SAGEICP_ERR_INVALID, "occupancy bounds: lo >= hi on an axis");
+        g.lo[a] = lo;
+        g.hi[a] = hi;
+    }
+    if (prm->occ_h < 1 || prm->occ_h > kOccMaxSide || prm->occ_w < 1 || prm->occ_w > kOccMaxSide)
+        return fail(SAGEICP_ERR_INVALID, "occupancy size: occ_h and occ_w must lie in [1, 4096]");
+    if (!std::isfinite(prm->overlap_th)) return fail(SAGEICP_ERR_INVALID, "the overlap threshold is not finite");
+    g.h = prm->occ_h;
+    g.w = prm->occ_w;
+    // Utils.hpp:224-225: (bounds[0][1] - bounds[0][0]) / occ_size[1], (bounds[1][1] - bounds[1][0]) / occ_size[0]
+    g.x_res = (g.hi[0] - g.lo[0]) / static_cast<double>(g.w);
+    g.y_res = (g.hi[1] - g.lo[1]) / static_cast<double>(g.h);
+    return SAGEICP_OK;
+}
+OccTransform occ_transform(const double pose[7]) {
+    OccTransform t;
+    quat_to_mat(pose, t.R);                 // as fill_state does for k_tf
+    for (int i = 0; i < 3; ++i) t.t[i] = pose[4 + i];
+    return t;
+}
+// bits of a grid into H * W bytes
+void occ_unpack_host(const uint32_t *bits, const OccGrid &g, uint8_t *out) {
+    const uint64_t cells = static_cast<uint64_t>(g.h) * g.w;
+    for (uint64_t i = 0; i < cells; ++i) out[i] = static_cast<uint8_t>((bits[i >> 5] >> (i & 31)) & 1u);
+}
+
+// ---- sensor_msgs/PointCloud2 records out (msg.hip) ------------------------------------------------------------------
+// the node's color_list as the 256-entry table the label rule leaves room for: keys outside 0..255 can never match
+int color_table(const sageicp_msg_colors *c, MsgColorTable &t) {
+    std::memset(&t, 0, sizeof(t));
+    if (!c || !c->n) return SAGEICP_OK;
+    if (!c->keys || !c->values) return fail(SAGEICP_ERR_INVALID, "colour table: n > 0 with a NULL array");
+    for (uint32_t i = 0; i < c->n; ++i) {
+        const int32_t k = c->keys[i];
+        if (k < 0 || k > 255) continue;
+        t.value[k] = static_cast<uint32_t>(c->values[i]);
+        t.present[k >> 5] |= 1u << (k & 31);
+    }
+    return SAGEICP_OK;
+}
+
+// `want` packed rows as records at d_out (device memory) on s, behind a zeroed flag word; with host_out the records
+// follow to host memory.  Waited for, then the flags the rows may have raised read.
+int pack_msg(DevBuf<int> &flag, const Point4 *d_rows, uint64_t want, const MsgColorTable &t, unsigned char *d_out,
+             void *host_out, hipStream_t s) {
+    if (!flag) HIPCHK(flag.reserve(1));
+    HIPCHK(hipMemsetAsync(flag.data(), 0, sizeof(int), s));
+    launch_msg_pack(d_rows, want, t, d_out, flag.data(), s);
+    int flags = 0;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(&flags, flag.data(), sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && host_out)
+        e = hipMemcpyAsync(host_out, d_out, want * SAGEICP_MSG_POINT_STEP, hipMemcpyDeviceToHost, s);
+    const hipError_t w = hipStreamSynchronize(s);        // (also after a failure: nothing enqueued here runs on)
+    HIPCHK(e);
+    HIPCHK(w);
+    if (flags & kMsgLabelRange)
+        return fail(SAGEICP_ERR_INVALID, "a label does not fit the record's uint8 (trunc(label) outside [0, 255])");
+    if (flags & kMsgNoColor) return fail(SAGEICP_ERR_INVALID, "the colour table has no colour for a label");
+    return SAGEICP_OK;
+}
+int reserve_records(DevBuf<unsigned char> &d_msg, uint64_t want) {
+    const size_t bytes = static_cast<size_t>(want) * SAGEICP_MSG_POINT_STEP;
+    if (bytes > d_msg.capacity()) HIPCHK(d_msg.reserve(bytes + bytes / 4 + 4096));
+    return SAGEICP_OK;
+}
+// a caller's destination of cap records in device memory, and its stream
+int check_records_out(const void *out, uint64_t cap, void *stream, int device) {
+    if (!cap) return SAGEICP_OK;
+    if (!out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    int rc = require_device();
+    if (rc) return rc;
+    if ((rc = check_extent(out, cap * SAGEICP_MSG_POINT_STEP, device, "message records: out"))) return rc;
+    return check_stream(stream, device);
+}
+}  // namespace sageicp_impl
 
 // =============================================================================================
 extern "C" {
@@ -694,131 +960,6 @@ void sageicp_frame_destroy(sageicp_frame *f) {
     delete f;
 }
 
-// ---- rows in the caller's device memory: frames in (ingest.hip), outputs out (egress.hip, egress.h) ---------------
-static size_t dtype_bytes(int32_t t) {
-    switch (t) {
-    case SAGEICP_DTYPE_FLOAT32: return 4;
-    case SAGEICP_DTYPE_FLOAT64: return 8;
-    case SAGEICP_DTYPE_UINT8: return 1;
-    case SAGEICP_DTYPE_INT32: return 4;
-    case SAGEICP_DTYPE_INT64: return 8;
-    default: return 0;
-    }
-}
-
-// the device whose memory p is, as this library's runtime sees it (false: not device memory — host, pinned or managed
-// memory, or a pointer of another HIP runtime loaded into the process, which is unknown here)
-static bool device_of(const void *p, int *device) {
-    hipPointerAttribute_t at{};
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    (void)hipGetLastError();            // an unknown pointer leaves an error behind that the next call must not see
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice) return false;
-    *device = at.device;
-    return true;
-}
-
-// the first and the last byte of an extent must be device memory of `device`
-static int check_extent(const void *p, uint64_t bytes, int device, const char *what) {
-    const char *ends[2] = {static_cast<const char *>(p), static_cast<const char *>(p) + bytes - 1};
-    for (const char *q : ends) {
-        int d = -1;
-        if (!device_of(q, &d))
-            return fail(SAGEICP_ERR_INVALID, std::string(what) + " is not device memory of this process's HIP runtime "
-                                             "(host, pinned and managed memory are refused, not copied)");
-        if (d != device)
-            return fail(SAGEICP_ERR_INVALID, std::string(what) + " lives on device " + std::to_string(d) +
-                                             ", the handle on device " + std::to_string(device));
-    }
-    return SAGEICP_OK;
-}
-
-// a caller's stream (NULL: the null stream) must be one of `device`
-static int check_stream(void *stream, int device) {
-    if (!stream) return SAGEICP_OK;
-    int sd = -1;
-    const hipError_t e = hipStreamGetDevice(static_cast<hipStream_t>(stream), &sd);
-    (void)hipGetLastError();
-    if (e != hipSuccess || sd != device) return fail(SAGEICP_ERR_INVALID, "stream is not a stream of the handle's device");
-    return SAGEICP_OK;
-}
-
-// Strided rows in a caller's device memory: a frame's n (sageicp_device_frame) or a destination's cap
-// (sageicp_device_points).  Host-side only: the kernels take IngestArgs / EgressArgs.
-struct CallerRows {
-    const void *xyz;
-    uint64_t xyz_stride;
-    int32_t xyz_dtype;
-    const void *label;
-    uint64_t label_stride;
-    int32_t label_dtype;
-    uint64_t rows;
-};
-// what differs between a frame and a destination
-struct RowRules {
-    const char *prefix;                 // of the messages
-    unsigned label_dtypes;              // bit t: SAGEICP_DTYPE t is a valid label_dtype
-    const char *label_dtypes_text;
-    uint64_t max_rows;                  // (refused as a frame that is too large)
-};
-static const RowRules kFrameRows{
-    "device frame: ", 1u << SAGEICP_DTYPE_UINT8 | 1u << SAGEICP_DTYPE_INT32 | 1u << SAGEICP_DTYPE_INT64,
-    "SAGEICP_DTYPE_UINT8, _INT32 or _INT64", kMaxQueries};
-static const RowRules kPointsRows{
-    "device points: ", 1u << SAGEICP_DTYPE_UINT8 | 1u << SAGEICP_DTYPE_INT32 | 1u << SAGEICP_DTYPE_INT64 |
-                       1u << SAGEICP_DTYPE_FLOAT32 | 1u << SAGEICP_DTYPE_FLOAT64,
-    "SAGEICP_DTYPE_UINT8, _INT32, _INT64, _FLOAT32 or _FLOAT64", std::numeric_limits<uint64_t>::max()};
-
-// Everything about caller rows that can be known before the stream is touched or anything launched: the layout first
-// (no device needed), then where the memory of the rows (and of the n timestamps `ts` that will be read, if given)
-// lives, then the stream.  found: an entry without a handle works on the device xyz lives on (`device` is not read): it
-// is looked up once the layout has passed, and stored there.
-static int check_rows(const CallerRows &r, const RowRules &k, const double *ts, void *stream, int device,
-                      int *found = nullptr) {
-    const std::string pre = k.prefix;
-    if (r.rows && !r.xyz) return fail(SAGEICP_ERR_INVALID, pre + "xyz is NULL");
-    const size_t ex = r.xyz_dtype == SAGEICP_DTYPE_FLOAT32 || r.xyz_dtype == SAGEICP_DTYPE_FLOAT64 ? dtype_bytes(r.xyz_dtype) : 0;
-    if (!ex) return fail(SAGEICP_ERR_INVALID, pre + "xyz_dtype must be SAGEICP_DTYPE_FLOAT32 or _FLOAT64");
-    const uint64_t cols = r.label ? 3 : 4;
-    if (r.xyz_stride < cols * ex || r.xyz_stride % ex)
-        return fail(SAGEICP_ERR_INVALID, pre + (r.label ? "xyz_stride must be a multiple of the element size and at least 3 "
-                                                          "elements"
-                                                        : "xyz_stride must be a multiple of the element size and at least 4 "
-                                                          "elements (the label is column 3)"));
-    size_t el = 0;
-    if (r.label) {
-        el = dtype_bytes(r.label_dtype) && ((k.label_dtypes >> r.label_dtype) & 1u) ? dtype_bytes(r.label_dtype) : 0;
-        if (!el) return fail(SAGEICP_ERR_INVALID, pre + "label_dtype must be " + k.label_dtypes_text);
-        if (r.label_stride < el || r.label_stride % el)
-            return fail(SAGEICP_ERR_INVALID, pre + "label_stride must be a positive multiple of the label's size");
-    }
-    if (r.rows > k.max_rows) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
-    if (!r.rows) return SAGEICP_OK;
-    int rc = require_device();
-    if (rc) return rc;
-    if (found) {                        // (memory that is not device memory is refused just below)
-        device = 0;
-        (void)device_of(r.xyz, &device);
-        *found = device;
-    }
-    rc = check_extent(r.xyz, (r.rows - 1) * r.xyz_stride + cols * ex, device, (pre + "xyz").c_str());
-    if (!rc && r.label) rc = check_extent(r.label, (r.rows - 1) * r.label_stride + el, device, (pre + "label").c_str());
-    if (!rc && ts) rc = check_extent(ts, r.rows * sizeof(double), device, "timestamps");
-    return rc ? rc : check_stream(stream, device);
-}
-
-static int check_device_frame(const sageicp_device_frame *f, const double *ts, void *stream, int device,
-                              int *found = nullptr) {
-    if (!f) return fail(SAGEICP_ERR_INVALID, "null device frame");
-    return check_rows({f->xyz, f->xyz_stride, f->xyz_dtype, f->label, f->label_stride, f->label_dtype, f->n}, kFrameRows,
-                      ts, stream, device, found);
-}
-
-static int check_device_points(const sageicp_device_points *d, void *stream, int device) {
-    if (!d) return fail(SAGEICP_ERR_INVALID, "null destination");
-    return check_rows({d->xyz, d->xyz_stride, d->xyz_dtype, d->label, d->label_stride, d->label_dtype, d->cap},
-                      kPointsRows, nullptr, stream, device);
-}
-
 sageicp_frame *sageicp_frame_from_device(const sageicp_map *m, const sageicp_device_frame *fr, void *stream) {
     if (!m) { fail(SAGEICP_ERR_INVALID, "null argument"); return nullptr; }
     if (check_device_frame(fr, nullptr, stream, m->device)) return nullptr;
@@ -834,40 +975,6 @@ sageicp_frame *sageicp_frame_from_device(const sageicp_map *m, const sageicp_dev
         return nullptr;
     }
     return f.release();
-}
-
-static EgressArgs egress_args(const sageicp_device_points &d, int *flags) {
-    EgressArgs a{};
-    a.xyz = static_cast<unsigned char *>(d.xyz);
-    a.xyz_stride = d.xyz_stride;
-    a.xyz_dtype = d.xyz_dtype;
-    a.label = static_cast<unsigned char *>(d.label);
-    a.label_stride = d.label_stride;
-    a.label_dtype = d.label_dtype;
-    a.cap = d.cap;
-    a.flags = flags;
-    return a;
-}
-
-// The rows that write(EgressArgs) enqueues on s into a caller's destination, behind a zeroed label-range flag: waited
-// for, then the flag they may have raised read.  Synchronous also when write fails part-way: nothing this call
-// enqueued runs on once it has returned.
-static int egress_into(DevBuf<int> &flag, const sageicp_device_points &dst, hipStream_t s,
-                       const std::function<int(const EgressArgs &)> &write) {
-    if (!flag) HIPCHK(flag.reserve(1));
-    HIPCHK(hipMemsetAsync(flag.data(), 0, sizeof(int), s));
-    if (int rc = write(egress_args(dst, flag.data()))) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    int flags = 0;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&flags, flag.data(), sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (flags & kEgressLabelRange)
-        return fail(SAGEICP_ERR_INVALID, "a label does not fit the destination's label type (static_cast<int64_t>(label) "
-                                         "out of its range)");
-    return SAGEICP_OK;
 }
 
 int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_points *dst, void *stream, uint64_t *n_out) {
@@ -902,28 +1009,6 @@ int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_poi
     });
 }
 
-// RegisterFrame of n points already on `device` (an uploaded frame, or the pipeline's source cloud)
-static int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
-                             double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
-                             sageicp_stats *stats) {
-    if (!m || !init || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    if (device != m->device) return fail(SAGEICP_ERR_INVALID, "frame and map live on different devices");
-    if (comm && comm->device != m->device) return fail(SAGEICP_ERR_INVALID, "comm and map live on different devices");
-    const double t0 = now_us();
-    if (map_is_empty(m)) {
-        std::memcpy(pose_out, init, 56);
-        if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->n_queries = n; }
-        return SAGEICP_OK;
-    }
-    if (!m->replicas.empty()) {
-        if (comm) return fail(SAGEICP_ERR_INVALID, "a map that spans several devices shards the frame itself");
-        return register_sharded(m, nullptr, d_frame, n, init, max_dist, kernel, sem_th, pose_out, stats, t0);
-    }
-    int rc = sync_mirror(m);
-    if (rc) return rc;
-    const double us_upload = now_us() - t0;
-    return run_icp(m, d_frame, n, init, max_dist, kernel, sem_th, comm, pose_out, stats, us_upload, t0);
-}
 
 int sageicp_register_frame_resident(const sageicp_map *m, const sageicp_frame *f,
                                     const double init[7], double max_dist, double kernel,
@@ -1071,7 +1156,7 @@ static int prep_one_level(int device, const double *frame, uint64_t n, const Pre
     Prep pr;
     int rc = pr.init(device);
     if (rc) return rc;
-    if ((rc = pr.run(frame, n, job))) return rc;
+    if ((rc = pr.run(FrameSource::host_rows(frame, n), job))) return rc;
     *n_out = pr.kept_levels[0];
     if ((rc = pr.fetch(0, out))) return rc;
     if (info) *info = pr.dyn.info;
@@ -1169,392 +1254,6 @@ int sageicp_deskew_scan(const double *frame, const double *timestamps, uint64_t 
     return SAGEICP_OK;
 }
 
-// ---- pipeline counterpart -----------------------------------------------------------------------
-struct sageicp_pipeline {
-    sageicp::Pipeline impl;
-    // Preprocess() + Voxelize() depend on the raw frame only (not on the pose, not on the map), so
-    // the next frame's can run while this one registers (sageicp_pipeline_prefetch): two sets of
-    // buffers and streams (prep[2], below), `cur` the one the frame being registered lives in.  (Not with deskew on: a
-    // deskewed frame depends on the poses of the two frames before it, so prefetch is refused then.)
-    int cur = 0;
-    int device;
-    std::thread worker;                  // runs the announced frame's voxelize on prep[cur ^ 1]
-    bool announced = false;              // _prefetch named the frame that follows the next one registered
-    const double *an_frame = nullptr;
-    uint64_t an_n = 0;
-    bool ready = false;                  // prep[cur ^ 1] holds (or the worker is filling it with) pf_frame
-    const double *pf_frame = nullptr;
-    uint64_t pf_n = 0;
-    uint64_t an_print = 0, pf_print = 0; // content fingerprints (a buffer re-used for other data is another frame)
-    // FNV-1a over n and 64 rows spread over the frame: cheap, and enough to tell a buffer that was
-    // refilled since it was announced from the frame that was announced
-    static uint64_t fingerprint(const double *f, uint64_t m) {
-        uint64_t h = 1469598103934665603ull ^ m;
-        if (!f || !m) return h;
-        const uint64_t step = std::max<uint64_t>(1, m / 64);
-        for (uint64_t i = 0; i < m; i += step) {
-            uint64_t w[4];
-            std::memcpy(w, f + 4 * i, 32);
-            for (uint64_t x : w) { h ^= x; h *= 1099511628211ull; }
-        }
-        uint64_t w[4];
-        std::memcpy(w, f + 4 * (m - 1), 32);
-        for (uint64_t x : w) { h ^= x; h *= 1099511628211ull; }
-        return h;
-    }
-    int pf_rc = 0;
-    std::string pf_err;
-    // Preprocess()'s dynamic vehicle filter (sageicp_pipeline_set_dynamic_vehicle_filter): off by default
-    bool dyn_on = false;
-    sageicp::DynFilterConfig dyn_cfg;
-    // sageConfig::deskew (sageicp_pipeline_set_deskew): off by default; read by the timestamped entry only
-    bool deskew_on = false;
-    // the source cloud of the last successful register call (sageicp_pipeline_source*): src_n rows of
-    // prep[src_buf].d_src, 0 when there is none.  Nothing writes that buffer before the next register call: the
-    // prefetch worker fills the other one, and the registration reads d_src without reordering it.
-    uint64_t src_n = 0;
-    int src_buf = 0;
-    mutable DevBuf<int> d_egress_flag;
-    mutable DevBuf<unsigned char> d_msg;           // sageicp_pipeline_source_msg: the records before they cross PCIe
-    // key-frame selection (sageicp_pipeline_set_key_frames, keyframe.hip): off by default.  The key grid lives on the
-    // device (d_key); the host holds the key pose and what the last frame's step decided.
-    struct KeyFrames {
-        bool on = false;
-        sageicp_occupancy_params prm{};
-        sageicp::OccGrid g{};
-        bool has_key = false;
-        sageicp::Pose7 key_pose;
-        sageicp_key_frame_info info{};
-        DevBuf<uint32_t> d_key, d_cand, d_cur;     // bitmaps (allocated with the first frame)
-        DevBuf<sageicp::OccDecision> d_dec;
-        PinnedBuf<sageicp::OccDecision> h_dec;
-        // "no key frame"
-        void clear() {
-            has_key = false;
-            key_pose = sageicp::Pose7();
-            info = sageicp_key_frame_info{};
-            info.enabled = on ? 1 : 0;
-            info.overlap = std::numeric_limits<double>::quiet_NaN();
-            for (int i = 0; i < 7; ++i) info.key_pose[i] = key_pose.v[i];
-        }
-        KeyFrames() { clear(); }
-    } kf;
-    // (after the buffers that work on their streams touches — d_egress_flag, kf's: the Preps wait and go first)
-    sageicp::Prep prep[2];
-    explicit sageicp_pipeline(const sageicp_pipeline_config &c) : impl(c), device(c.device) {}
-    ~sageicp_pipeline() {
-        if (worker.joinable()) worker.join();          // (it works on a Prep: joined before either goes)
-    }
-    int voxelize_into(sageicp::Prep &pr, const double *f, uint64_t m, const sageicp::DeskewArgs *deskew = nullptr,
-                      const sageicp::DeviceSource *dev = nullptr) {
-        int rc = pr.init(device);
-        if (rc) return rc;
-        std::vector<int> counts, labels;
-        std::vector<double> vs;
-        impl.group_tables(counts, labels, vs);
-        sageicp::PrepJob job;
-        job.max_range = impl.max_range_(); job.min_range = impl.min_range_(); job.label_max_range = impl.label_max_range_();
-        job.n_groups = static_cast<int>(counts.size());
-        job.group_counts = counts.data(); job.group_labels = labels.data(); job.group_voxel_size = vs.data();
-        job.n_levels = 2;
-        job.levels[0] = {/*crop*/ 1, /*scale*/ 0.5};
-        job.levels[1] = {/*crop*/ 0, /*scale*/ 1.5};
-        job.dyn = dyn_on ? &dyn_cfg : nullptr; job.deskew = deskew; job.dev = dev;
-        // level 0 (frame_downsample: it goes into the map, AddPoints depends on arrival order)
-        // keeps the reference's emission order; level 1 (the registered source) does not need it
-        pr.arrival_order_levels = env_int("SAGEICP_SOURCE_REFERENCE_ORDER", 0) ? 0u : 2u;
-        pr.keep_raw = kf.on;
-        return pr.run(f, m, job);
-    }
-};
-
-sageicp_pipeline *sageicp_pipeline_create(const sageicp_pipeline_config *c) {
-    if (!c || c->n_groups < 0 || (c->n_groups && (!c->group_label_counts || !c->group_voxel_size))) {
-        fail(SAGEICP_ERR_INVALID, "sageicp_pipeline_create: bad config");
-        return nullptr;
-    }
-    sageicp_pipeline *p = new sageicp_pipeline(*c);
-    if (!p->impl.ok()) {
-        delete p;
-        return nullptr;
-    }
-    return p;
-}
-void sageicp_pipeline_destroy(sageicp_pipeline *p) { delete p; }
-// ---- key-frame selection (keyframe.hip) ----------------------------------------------------------------------------
-// the grid of validated params (include/sageicp.h: what is refused)
-static int occ_grid_from(const sageicp_occupancy_params *prm, OccGrid &g) {
-    if (!prm) return fail(SAGEICP_ERR_INVALID, "null occupancy params");
-    for (int a = 0; a < 3; ++a) {
-        const double lo = prm->bounds[a][0], hi = prm->bounds[a][1];
-        if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(SAGEICP_ERR_INVALID, "occupancy bounds are not finite");
-        if (!(lo < hi)) return fail(SAGEICP_ERR_INVALID, "occupancy bounds: lo >= hi on an axis");
-        g.lo[a] = lo;
-        g.hi[a] = hi;
-    }
-    if (prm->occ_h < 1 || prm->occ_h > kOccMaxSide || prm->occ_w < 1 || prm->occ_w > kOccMaxSide)
-        return fail(SAGEICP_ERR_INVALID, "occupancy size: occ_h and occ_w must lie in [1, 4096]");
-    if (!std::isfinite(prm->overlap_th)) return fail(SAGEICP_ERR_INVALID, "the overlap threshold is not finite");
-    g.h = prm->occ_h;
-    g.w = prm->occ_w;
-    // Utils.hpp:224-225: (bounds[0][1] - bounds[0][0]) / occ_size[1], (bounds[1][1] - bounds[1][0]) / occ_size[0]
-    g.x_res = (g.hi[0] - g.lo[0]) / static_cast<double>(g.w);
-    g.y_res = (g.hi[1] - g.lo[1]) / static_cast<double>(g.h);
-    return SAGEICP_OK;
-}
-static OccTransform occ_transform(const double pose[7]) {
-    OccTransform t;
-    quat_to_mat(pose, t.R);                 // as fill_state does for k_tf
-    for (int i = 0; i < 3; ++i) t.t[i] = pose[4 + i];
-    return t;
-}
-// bits of a grid into H * W bytes
-static void occ_unpack_host(const uint32_t *bits, const OccGrid &g, uint8_t *out) {
-    const uint64_t cells = static_cast<uint64_t>(g.h) * g.w;
-    for (uint64_t i = 0; i < cells; ++i) out[i] = static_cast<uint8_t>((bits[i >> 5] >> (i & 31)) & 1u);
-}
-
-// OdometryServer.cpp:222-243 for the frame just registered (its raw rows in prep[cur].d_raw, its pose the last one
-// pushed): the identity grid (the candidate) and, with a key frame, the grid under key_pose^-1 * pose in one pass, then
-// the counts, the decision and the swap on the device.  The host state changes only once the decision is back.
-static int key_frame_step(sageicp_pipeline *p, uint64_t n) {
-    auto &k = p->kf;
-    sageicp::Prep &pr = p->prep[p->cur];
-    const hipStream_t s = pr.stream.get();
-    const uint32_t words = occ_words(k.g);
-    HIPCHK(hipSetDevice(p->device));
-    if (!k.d_key) {
-        HIPCHK(k.d_cand.reserve(words));
-        HIPCHK(k.d_cur.reserve(words));
-        HIPCHK(k.d_dec.reserve(1));
-        HIPCHK(k.h_dec.reserve(1));
-        HIPCHK(k.d_key.reserve(words));
-    }
-    const Pose7 pose = p->impl.poses.back();
-    OccTransform tf{};
-    if (k.has_key) {                         // sageICP::TransformToLastFrame, pipeline/sageICP.cpp:123-129
-        Pose7 inv, rel;
-        se3_inv(k.key_pose.v, inv.v);
-        se3_mul(inv.v, pose.v, rel.v);
-        tf = occ_transform(rel.v);
-    }
-    HIPCHK(hipMemsetAsync(k.d_cand.data(), 0, words * sizeof(uint32_t), s));
-    if (k.has_key) HIPCHK(hipMemsetAsync(k.d_cur.data(), 0, words * sizeof(uint32_t), s));
-    launch_occ_draw(pr.d_raw.data(), static_cast<int>(n), k.g, k.has_key ? &tf : nullptr, k.d_cand.data(), k.d_cur.data(),
-                    nullptr, env_int("SAGEICP_OCC_GLOBAL", 0) != 0, s);
-    HIPCHK(hipGetLastError());
-    launch_occ_decide(k.d_key.data(), k.d_cand.data(), k.d_cur.data(), words, k.has_key ? 0 : 1, k.prm.overlap_th,
-                      k.d_dec.data(), s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(k.h_dec.data(), k.d_dec.data(), sizeof(OccDecision), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    const OccDecision d = *k.h_dec.data();
-    sageicp_key_frame_info &info = k.info;
-    info.is_key_frame = d.take;
-    info.key_occupied = k.has_key ? d.key : 0;
-    info.intersect = k.has_key ? d.inter : 0;
-    // Utils.hpp:257: static_cast<double>(overlap) / total — NaN for 0 / 0, as the device's decision saw it
-    info.overlap = k.has_key ? static_cast<double>(d.inter) / static_cast<double>(d.key)
-                             : std::numeric_limits<double>::quiet_NaN();
-    if (d.take) {
-        k.has_key = true;
-        k.key_pose = pose;
-        info.key_frame_index = p->impl.poses.size() - 1;
-        ++info.key_frames;
-        for (int i = 0; i < 7; ++i) info.key_pose[i] = pose.v[i];
-    }
-    return SAGEICP_OK;
-}
-
-// timestamps: the frame's (deskew on, all finite) or nullptr (the one-argument RegisterFrame).  dev: the frame is in the
-// caller's device memory (`frame` is not read; a non-null `timestamps` only marks deskew on, they are dev's)
-static int pipeline_register(sageicp_pipeline *p, const double *frame, const double *timestamps, uint64_t n,
-                             double pose_out[7], double *icp_s, double *total_s, uint64_t *n_source,
-                             sageicp_stats *stats, const sageicp::DeviceSource *dev = nullptr) {
-    // Deskew (deskew.hip) on the uploaded frame when the pipeline decides so, then Preprocess + Voxelize on the
-    // device (preprocess.hip): crop + scale 0.5, then scale 1.5.
-    // Neither cloud comes back to the host: the source is registered and the down-sampled frame
-    // inserted into the map from where the kernels left them (only a host-side map update
-    // downloads its points).
-    struct Backend {
-        sageicp_pipeline *p;
-        const double *ts;
-        const sageicp::DeviceSource *dev;
-        int voxelize(const double *f, uint64_t m, uint64_t &n_src, const double *delta) {
-            if (p->worker.joinable()) p->worker.join();
-            if (dev && dev->msg && m == 0) {     // an empty message: no rows, no device work (an announcement is dropped)
-                sageicp::Prep &pr = p->prep[p->cur];
-                pr.kept_levels[0] = pr.kept_levels[1] = 0;
-                pr.dyn_ran = false;
-                pr.dyn.info = sageicp_dynfilter_info{};
-                p->ready = false;
-                p->announced = false;
-                n_src = 0;
-                return SAGEICP_OK;
-            }
-            int r;
-            if (delta) {                         // deskewed: depends on the last two poses, never prepared ahead
-                sageicp::DeskewArgs da{dev ? nullptr : ts, {}};
-                for (int k = 0; k < 6; ++k) da.delta.v[k] = delta[k];
-                p->ready = false;
-                r = p->voxelize_into(p->prep[p->cur], f, m, &da, dev);
-            } else if (!dev && p->ready && p->pf_frame == f && p->pf_n == m &&
-                p->pf_print == sageicp_pipeline::fingerprint(f, m)) {   // prepared while the last frame registered
-                r = p->pf_rc ? fail(p->pf_rc, p->pf_err) : SAGEICP_OK;
-                p->cur ^= 1;
-            } else {                                                 // none, another frame or a device frame: dropped
-                r = p->voxelize_into(p->prep[p->cur], f, m, nullptr, dev);
-            }
-            p->ready = false;
-            n_src = p->prep[p->cur].kept_levels[1];
-            if (r == SAGEICP_OK && p->announced) {
-                // the frame after this one: its Preprocess() + Voxelize() run on the other set of
-                // buffers (own stream, own host thread) under this frame's ICP loop and map update
-                p->ready = true;
-                p->pf_frame = p->an_frame;
-                p->pf_n = p->an_n;
-                p->pf_print = p->an_print;
-                p->pf_rc = 0;
-                p->pf_err.clear();
-                sageicp_pipeline *q = p;
-                sageicp::Prep *dst = &p->prep[p->cur ^ 1];
-                const double *nf = p->an_frame;
-                const uint64_t nn = p->an_n;
-                p->worker = std::thread([q, dst, nf, nn] {
-                    (void)hipSetDevice(q->device);
-                    q->pf_rc = q->voxelize_into(*dst, nf, nn);
-                    if (q->pf_rc) q->pf_err = g_err;                 // the error text is per thread
-                });
-            }
-            p->announced = false;
-            return r;
-        }
-        int register_source(const double guess[7], double max_dist, double kernel, double sem_th,
-                            double pose[7], sageicp_stats *stats) {
-            // the source cloud in the Prep buffers
-            return register_resident(p->impl.map, p->prep[p->cur].d_src.data(), p->prep[p->cur].kept_levels[1],
-                                     p->device, guess, max_dist, kernel, sem_th, nullptr, pose, stats);
-        }
-        int update_map(const double pose[7]) {
-            const sageicp::Prep &pr = p->prep[p->cur];
-            const uint64_t n_fd = pr.kept_levels[0];
-            if (dev && dev->msg && !n_fd && map_is_empty(p->impl.map)) return SAGEICP_OK;   // nothing into nothing
-            if (p->impl.map_update_on_device_())
-                return device_update_all(p->impl.map, nullptr, n_fd, pose, pr.d_fd.data());
-            std::vector<double> fd(4 * n_fd);
-            if (n_fd) {
-                HIPCHK(hipSetDevice(p->device));
-                HIPCHK(hipMemcpy(fd.data(), pr.d_fd.data(), n_fd * sizeof(Point4), hipMemcpyDeviceToHost));
-            }
-            return sageicp_map_update_pose(p->impl.map, fd.data(), n_fd, pose);
-        }
-    };
-    int rc = p->impl.register_frame(frame, n, timestamps != nullptr, pose_out, icp_s, total_s, n_source, stats,
-                                    Backend{p, timestamps, dev});
-    p->announced = false;       // an announcement is consumed by this call, also when it failed or the frame was empty
-    p->src_buf = p->cur;
-    p->src_n = rc == SAGEICP_OK ? p->prep[p->cur].kept_levels[1] : 0;
-    // the node's key-frame block runs after RegisterFrame has returned (outside the times reported above)
-    if (rc == SAGEICP_OK && p->kf.on && !(dev && dev->msg && n == 0)) rc = key_frame_step(p, n);
-    return rc;
-}
-// Every register entry drops the last source first: a call that is refused before it reaches pipeline_register (a bad
-// argument, a device frame or timestamps that fail their checks) leaves 0 rows, as one that fails later does.
-static void drop_source(sageicp_pipeline *p) {
-    if (p) p->src_n = 0;
-}
-int sageicp_pipeline_register_frame(sageicp_pipeline *p, const double *frame, uint64_t n,
-                                    double pose_out[7], double *icp_s, double *total_s,
-                                    uint64_t *n_source, sageicp_stats *stats) {
-    drop_source(p);
-    if (!p || !pose_out || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
-    return pipeline_register(p, frame, nullptr, n, pose_out, icp_s, total_s, n_source, stats);
-}
-int sageicp_pipeline_register_frame_timestamps(sageicp_pipeline *p, const double *frame, const double *timestamps,
-                                               uint64_t n, double pose_out[7], double *icp_s, double *total_s,
-                                               uint64_t *n_source, sageicp_stats *stats) {
-    drop_source(p);
-    if (!p || !pose_out || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
-    if (!p->deskew_on)          // config_.deskew false: the frame passes through, the timestamps are not read
-        return pipeline_register(p, frame, nullptr, n, pose_out, icp_s, total_s, n_source, stats);
-    // checked on every frame, also before the third pose exists, so that a bad stream fails on its first frame
-    if (n && !timestamps) return fail(SAGEICP_ERR_INVALID, "deskew is on and timestamps is NULL");
-    for (uint64_t i = 0; i < n; ++i)
-        if (!std::isfinite(timestamps[i])) return fail(SAGEICP_ERR_INVALID, "deskew is on and a timestamp is not finite");
-    static const double kNone = 0.0;       // (n == 0: a non-null marker that deskew is asked for)
-    return pipeline_register(p, frame, timestamps ? timestamps : &kNone, n, pose_out, icp_s, total_s, n_source, stats);
-}
-int sageicp_pipeline_register_frame_device(sageicp_pipeline *p, const sageicp_device_frame *frame,
-                                           const double *timestamps, void *stream, double pose_out[7], double *icp_s,
-                                           double *total_s, uint64_t *n_source, sageicp_stats *stats) {
-    drop_source(p);
-    if (!p || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    // without timestamps the one-argument RegisterFrame (never deskews); with deskew off they are not read (not even
-    // checked), as in sageicp_pipeline_register_frame_timestamps
-    const double *ts = p->deskew_on ? timestamps : nullptr;
-    int rc = check_device_frame(frame, ts, stream, p->device);
-    if (rc) return rc;
-    const sageicp::DeviceSource dev{frame, ts, static_cast<hipStream_t>(stream)};
-    return pipeline_register(p, nullptr, ts, frame->n, pose_out, icp_s, total_s, n_source, stats, &dev);
-}
-
-// ---- sensor_msgs/PointCloud2 payloads (msg.hip) ---------------------------------------------------------------------
-// everything about a message that can be known without a device (include/sageicp.h: what is refused)
-static int check_msg(const sageicp_msg_layout *l, const void *data, uint64_t data_bytes, uint64_t n) {
-    if (!l) return fail(SAGEICP_ERR_INVALID, "message: null layout");
-    if (l->point_step == 0 || l->point_step > kMsgMaxStep)
-        return fail(SAGEICP_ERR_INVALID, "message: point_step must lie in [1, 1024]");
-    const auto ends_within = [&](uint32_t off, uint32_t size) { return static_cast<uint64_t>(off) + size <= l->point_step; };
-    if (!ends_within(l->x_offset, 4)) return fail(SAGEICP_ERR_INVALID, "message: field x ends beyond point_step");
-    if (!ends_within(l->y_offset, 4)) return fail(SAGEICP_ERR_INVALID, "message: field y ends beyond point_step");
-    if (!ends_within(l->z_offset, 4)) return fail(SAGEICP_ERR_INVALID, "message: field z ends beyond point_step");
-    if (l->label_dtype != SAGEICP_DTYPE_UINT8 && l->label_dtype != SAGEICP_DTYPE_FLOAT32)
-        return fail(SAGEICP_ERR_INVALID, "message: label_dtype must be SAGEICP_DTYPE_UINT8 or _FLOAT32");
-    if (!ends_within(l->label_offset, l->label_dtype == SAGEICP_DTYPE_UINT8 ? 1 : 4))
-        return fail(SAGEICP_ERR_INVALID, "message: field label ends beyond point_step");
-    if (l->time_kind < 0 || l->time_kind > 2)
-        return fail(SAGEICP_ERR_INVALID, "message: time_kind must be 0 (none), 1 (uint32) or 2 (float64)");
-    if (l->time_kind && !ends_within(l->time_offset, l->time_kind == 1 ? 4 : 8))
-        return fail(SAGEICP_ERR_INVALID, "message: the time field ends beyond point_step");
-    if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
-    if (data_bytes < n * l->point_step)
-        return fail(SAGEICP_ERR_INVALID, "message: data holds fewer than n * point_step bytes");
-    if (n && !data) return fail(SAGEICP_ERR_INVALID, "message: data is NULL");
-    return SAGEICP_OK;
-}
-static int register_msg(sageicp_pipeline *p, const void *data, uint64_t data_bytes, uint64_t n,
-                        const sageicp_msg_layout *layout, bool on_device, void *stream, double pose_out[7], double *icp_s,
-                        double *total_s, uint64_t *n_source, sageicp_stats *stats) {
-    drop_source(p);
-    if (!p || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    int rc = check_msg(layout, data, data_bytes, n);
-    if (rc) return rc;
-    // deskew off: the time field is never read, whatever the layout says (OdometryServer.cpp:161-164)
-    const bool want_time = p->deskew_on;
-    if (want_time && layout->time_kind == 0)
-        return fail(SAGEICP_ERR_INVALID, "deskew is on and the message has no time field (time_kind 0)");
-    if (n && on_device) {
-        if ((rc = require_device())) return rc;
-        if ((rc = check_extent(data, n * layout->point_step, p->device, "message data"))) return rc;
-        if ((rc = check_stream(stream, p->device))) return rc;
-    }
-    const unsigned char *bytes = static_cast<const unsigned char *>(data);
-    const sageicp::MsgSource msg{on_device ? nullptr : bytes, on_device ? bytes : nullptr, *layout, want_time};
-    const sageicp::DeviceSource dev{nullptr, nullptr, static_cast<hipStream_t>(stream), &msg};
-    static const double kDeskew = 0.0;     // (a non-null marker that deskew is asked for: the stamps are the message's)
-    return pipeline_register(p, nullptr, want_time ? &kDeskew : nullptr, n, pose_out, icp_s, total_s, n_source, stats, &dev);
-}
-int sageicp_pipeline_register_frame_msg(sageicp_pipeline *p, const void *data, uint64_t data_bytes, uint64_t n,
-                                        const sageicp_msg_layout *layout, double pose_out[7], double *icp_s,
-                                        double *total_s, uint64_t *n_source, sageicp_stats *stats) {
-    return register_msg(p, data, data_bytes, n, layout, false, nullptr, pose_out, icp_s, total_s, n_source, stats);
-}
-int sageicp_pipeline_register_frame_msg_device(sageicp_pipeline *p, const void *data, uint64_t data_bytes, uint64_t n,
-                                               const sageicp_msg_layout *layout, void *stream, double pose_out[7],
-                                               double *icp_s, double *total_s, uint64_t *n_source, sageicp_stats *stats) {
-    return register_msg(p, data, data_bytes, n, layout, true, stream, pose_out, icp_s, total_s, n_source, stats);
-}
-
 uint32_t sageicp_msg_output_fields(sageicp_msg_field *out, uint32_t cap) {
     static const sageicp_msg_field kFields[5] = {          // CreatePointCloud2Msg, Utils.hpp:109-113
         {"x", SAGEICP_MSG_X_OFFSET, SAGEICP_MSG_FIELD_FLOAT32, 1},
@@ -1564,85 +1263,6 @@ uint32_t sageicp_msg_output_fields(sageicp_msg_field *out, uint32_t cap) {
         {"rgb", SAGEICP_MSG_RGB_OFFSET, SAGEICP_MSG_FIELD_UINT32, 1}};
     for (uint32_t i = 0; out && i < std::min<uint32_t>(cap, 5); ++i) out[i] = kFields[i];
     return 5;
-}
-
-// the node's color_list as the 256-entry table the label rule leaves room for: keys outside 0..255 can never match
-static int color_table(const sageicp_msg_colors *c, MsgColorTable &t) {
-    std::memset(&t, 0, sizeof(t));
-    if (!c || !c->n) return SAGEICP_OK;
-    if (!c->keys || !c->values) return fail(SAGEICP_ERR_INVALID, "colour table: n > 0 with a NULL array");
-    for (uint32_t i = 0; i < c->n; ++i) {
-        const int32_t k = c->keys[i];
-        if (k < 0 || k > 255) continue;
-        t.value[k] = static_cast<uint32_t>(c->values[i]);
-        t.present[k >> 5] |= 1u << (k & 31);
-    }
-    return SAGEICP_OK;
-}
-
-// `want` packed rows as records at d_out (device memory) on s, behind a zeroed flag word; with host_out the records
-// follow to host memory.  Waited for, then the flags the rows may have raised read.
-static int pack_msg(DevBuf<int> &flag, const Point4 *d_rows, uint64_t want, const MsgColorTable &t, unsigned char *d_out,
-                    void *host_out, hipStream_t s) {
-    if (!flag) HIPCHK(flag.reserve(1));
-    HIPCHK(hipMemsetAsync(flag.data(), 0, sizeof(int), s));
-    launch_msg_pack(d_rows, want, t, d_out, flag.data(), s);
-    int flags = 0;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&flags, flag.data(), sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && host_out)
-        e = hipMemcpyAsync(host_out, d_out, want * SAGEICP_MSG_POINT_STEP, hipMemcpyDeviceToHost, s);
-    const hipError_t w = hipStreamSynchronize(s);        // (also after a failure: nothing enqueued here runs on)
-    HIPCHK(e);
-    HIPCHK(w);
-    if (flags & kMsgLabelRange)
-        return fail(SAGEICP_ERR_INVALID, "a label does not fit the record's uint8 (trunc(label) outside [0, 255])");
-    if (flags & kMsgNoColor) return fail(SAGEICP_ERR_INVALID, "the colour table has no colour for a label");
-    return SAGEICP_OK;
-}
-static int reserve_records(DevBuf<unsigned char> &d_msg, uint64_t want) {
-    const size_t bytes = static_cast<size_t>(want) * SAGEICP_MSG_POINT_STEP;
-    if (bytes > d_msg.capacity()) HIPCHK(d_msg.reserve(bytes + bytes / 4 + 4096));
-    return SAGEICP_OK;
-}
-// a caller's destination of cap records in device memory, and its stream
-static int check_records_out(const void *out, uint64_t cap, void *stream, int device) {
-    if (!cap) return SAGEICP_OK;
-    if (!out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = check_extent(out, cap * SAGEICP_MSG_POINT_STEP, device, "message records: out"))) return rc;
-    return check_stream(stream, device);
-}
-
-int sageicp_pipeline_source_msg(const sageicp_pipeline *p, const sageicp_msg_colors *colors, void *out, uint64_t cap,
-                                uint64_t *n_out) {
-    if (!p || !n_out || (cap && !out)) return fail(SAGEICP_ERR_INVALID, "null argument");
-    MsgColorTable t;
-    int rc = color_table(colors, t);
-    if (rc) return rc;
-    *n_out = p->src_n;
-    const uint64_t want = std::min(cap, p->src_n);
-    if (!want) return SAGEICP_OK;
-    HIPCHK(hipSetDevice(p->device));
-    if ((rc = reserve_records(p->d_msg, want))) return rc;
-    const sageicp::Prep &pr = p->prep[p->src_buf];
-    return pack_msg(p->d_egress_flag, pr.d_src.data(), want, t, p->d_msg.data(), out, pr.stream.get());
-}
-int sageicp_pipeline_source_msg_device(const sageicp_pipeline *p, const sageicp_msg_colors *colors, void *out,
-                                       uint64_t cap, void *stream, uint64_t *n_out) {
-    if (!p || !n_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    MsgColorTable t;
-    int rc = color_table(colors, t);
-    if (rc) return rc;
-    if ((rc = check_records_out(out, cap, stream, p->device))) return rc;
-    *n_out = p->src_n;
-    const uint64_t want = std::min(cap, p->src_n);
-    if (!want) return SAGEICP_OK;
-    HIPCHK(hipSetDevice(p->device));
-    // on the caller's stream, behind the work it enqueued before this call; synchronous
-    return pack_msg(p->d_egress_flag, p->prep[p->src_buf].d_src.data(), want, t, static_cast<unsigned char *>(out), nullptr,
-                    static_cast<hipStream_t>(stream));
 }
 
 // sageicp_map_pointcloud's rows into d_pc on s: packed from the HBM copy, or staged from the host copy (`staged` must
@@ -1688,189 +1308,6 @@ int sageicp_map_pointcloud_msg(const sageicp_map *m, const sageicp_msg_colors *c
 int sageicp_map_pointcloud_msg_device(const sageicp_map *m, const sageicp_msg_colors *colors, void *out, uint64_t cap,
                                       void *stream, uint64_t *n_out) {
     return map_msg(m, colors, out, cap, true, stream, n_out);
-}
-
-int sageicp_pipeline_source(const sageicp_pipeline *p, double *out, uint64_t cap, uint64_t *n_out) {
-    if (!p || !n_out || (cap && !out)) return fail(SAGEICP_ERR_INVALID, "null argument");
-    *n_out = p->src_n;
-    const uint64_t want = std::min(cap, p->src_n);
-    if (!want) return SAGEICP_OK;
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpy(out, p->prep[p->src_buf].d_src.data(), want * sizeof(Point4), hipMemcpyDeviceToHost));
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_source_device(const sageicp_pipeline *p, const sageicp_device_points *dst, void *stream,
-                                   uint64_t *n_out) {
-    if (!p || !n_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    int rc = check_device_points(dst, stream, p->device);
-    if (rc) return rc;
-    *n_out = p->src_n;
-    const uint64_t want = std::min(dst->cap, p->src_n);
-    if (!want) return SAGEICP_OK;
-    HIPCHK(hipSetDevice(p->device));
-    // on the caller's stream, behind the work it enqueued before this call; synchronous: afterwards nothing of the
-    // library touches the destination
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    return egress_into(p->d_egress_flag, *dst, s, [&](const EgressArgs &e) {
-        launch_egress(e, p->prep[p->src_buf].d_src.data(), want, s);
-        return SAGEICP_OK;
-    });
-}
-int sageicp_pipeline_set_deskew(sageicp_pipeline *p, int enable) {
-    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
-    if (p->worker.joinable()) p->worker.join();     // an announced or prepared frame is dropped
-    p->announced = false;
-    p->ready = false;
-    p->deskew_on = enable != 0;
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_deskew_info(const sageicp_pipeline *p, int *applied, double delta_out[6]) {
-    if (!p || !applied || !delta_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    *applied = p->impl.deskew_applied ? 1 : 0;
-    for (int k = 0; k < 6; ++k) delta_out[k] = p->impl.deskew_delta[k];
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_prefetch(sageicp_pipeline *p, const double *frame, uint64_t n) {
-    if (!p || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
-    if (p->deskew_on)
-        return fail(SAGEICP_ERR_INVALID, "sageicp_pipeline_prefetch: deskew is on: a deskewed frame's Preprocess() needs "
-                                         "the pose of the frame registered before it, so it cannot be prepared ahead");
-    p->announced = true;
-    p->an_frame = frame;
-    p->an_n = n;
-    p->an_print = sageicp_pipeline::fingerprint(frame, n);
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_prefetch_wait(sageicp_pipeline *p) {
-    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
-    if (p->worker.joinable()) p->worker.join();     // what it prepared stays (`ready`)
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_prefetch_cancel(sageicp_pipeline *p) {
-    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
-    if (p->worker.joinable()) p->worker.join();     // nothing reads an announced buffer after this
-    p->announced = false;
-    p->ready = false;
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_set_dynamic_vehicle_filter(sageicp_pipeline *p, int enable, double dy_th,
-                                                int voxid, const int *landmark_labels, int n_landmark) {
-    if (!p || n_landmark < 0 || (n_landmark && !landmark_labels) || !std::isfinite(dy_th))
-        return fail(SAGEICP_ERR_INVALID, "bad argument");
-    std::vector<int> counts, labels;
-    std::vector<double> vs;
-    p->impl.group_tables(counts, labels, vs);
-    if (voxid < 0 || voxid >= static_cast<int>(counts.size()))
-        return fail(SAGEICP_ERR_INVALID, "dynamic_vehicle_voxid is not a label group of the config");
-    if (p->worker.joinable()) p->worker.join();     // a frame prepared under the old setting is dropped
-    p->ready = false;
-    int off = 0;
-    for (int g = 0; g < voxid; ++g) off += counts[g];
-    p->dyn_on = enable != 0;
-    p->dyn_cfg.dy_th = dy_th;
-    p->dyn_cfg.dynamic_labels.assign(labels.begin() + off, labels.begin() + off + counts[voxid]);
-    p->dyn_cfg.landmark_labels.assign(landmark_labels, landmark_labels + n_landmark);
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_dynamic_filter_info(const sageicp_pipeline *p, sageicp_dynfilter_info *info) {
-    if (!p || !info) return fail(SAGEICP_ERR_INVALID, "null argument");
-    const sageicp::Prep &pr = p->prep[p->cur];
-    *info = pr.dyn_ran ? pr.dyn.info : sageicp_dynfilter_info{};
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_reinitialize(sageicp_pipeline *p) {
-    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
-    p->impl.reinitialize();
-    p->src_n = 0;
-    return SAGEICP_OK;
-}
-uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p) { return p ? p->impl.poses.size() : 0; }
-int sageicp_pipeline_pose(const sageicp_pipeline *p, uint64_t i, double out[7]) {
-    if (!p || !out || i >= p->impl.poses.size()) return fail(SAGEICP_ERR_INVALID, "bad pose index");
-    for (int k = 0; k < 7; ++k) out[k] = p->impl.poses[i].v[k];
-    return SAGEICP_OK;
-}
-const sageicp_map *sageicp_pipeline_local_map(const sageicp_pipeline *p) {
-    return p ? p->impl.map : nullptr;
-}
-
-int sageicp_pipeline_set_key_frames(sageicp_pipeline *p, int enable, const sageicp_occupancy_params *params) {
-    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
-    OccGrid g{};
-    if (enable) {
-        int rc = occ_grid_from(params, g);
-        if (rc) return rc;
-    }
-    if (p->worker.joinable()) p->worker.join();     // a frame prepared under the old setting is dropped
-    p->ready = false;
-    auto &k = p->kf;
-    k.on = enable != 0;
-    if (k.on) {
-        k.prm = *params;
-        k.g = g;
-    }
-    // the bitmaps are sized for the grid at the next frame; off, nothing of the selection stays allocated
-    k.d_key.reset();
-    k.d_cand.reset();
-    k.d_cur.reset();
-    if (!k.on) {
-        k.d_dec.reset();
-        k.h_dec.reset();
-        (void)hipSetDevice(p->device);
-        p->prep[0].d_raw.reset();
-        p->prep[1].d_raw.reset();
-    }
-    k.clear();
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_key_frame_reset(sageicp_pipeline *p) {
-    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
-    p->kf.clear();
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_key_frame_info(const sageicp_pipeline *p, sageicp_key_frame_info *info) {
-    if (!p || !info) return fail(SAGEICP_ERR_INVALID, "null argument");
-    *info = p->kf.info;
-    return SAGEICP_OK;
-}
-// what both key-grid entries check first: the selection is on and `cap` bytes hold the grid's *cells
-static int key_grid_cells(const sageicp_pipeline *p, const uint8_t *out, uint64_t cap, uint64_t *cells) {
-    if (!p || !out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    if (!p->kf.on) return fail(SAGEICP_ERR_INVALID, "key-frame selection is off");
-    *cells = static_cast<uint64_t>(p->kf.g.h) * p->kf.g.w;
-    if (cap < *cells) return fail(SAGEICP_ERR_INVALID, "the key grid needs occ_h * occ_w bytes");
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_key_frame_grid(const sageicp_pipeline *p, uint8_t *out, uint64_t cap) {
-    uint64_t cells = 0;
-    if (int rc = key_grid_cells(p, out, cap, &cells)) return rc;
-    const auto &k = p->kf;
-    if (!k.has_key) {
-        std::memset(out, 0, cells);
-        return SAGEICP_OK;
-    }
-    std::vector<uint32_t> bits(occ_words(k.g));
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpy(bits.data(), k.d_key.data(), bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    occ_unpack_host(bits.data(), k.g, out);
-    return SAGEICP_OK;
-}
-int sageicp_pipeline_key_frame_grid_device(const sageicp_pipeline *p, uint8_t *out, uint64_t cap, void *stream) {
-    uint64_t cells = 0;
-    int rc = key_grid_cells(p, out, cap, &cells);
-    if (!rc) rc = require_device();
-    if (!rc) rc = check_extent(out, cells, p->device, "key-frame grid");
-    if (!rc) rc = check_stream(stream, p->device);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(p->device));
-    // on the caller's stream, behind the work it enqueued before this call; synchronous
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    const auto &k = p->kf;
-    if (k.has_key) launch_occ_unpack(k.d_key.data(), k.g, out, s);
-    else HIPCHK(hipMemsetAsync(out, 0, cells, s));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    return SAGEICP_OK;
 }
 
 // the grid of n rows already on the device (d_pts), moved by pose (or not), into host bytes; a coordinate that is not

@@ -1,6 +1,7 @@
-// Internals shared by the translation units of libsageicp_hip.so's host side (capi.hip, capi_mirror.hip,
-// capi_run.hip, prep.hip): error channel, tuning knobs, the per-handle device scratch, the pipeline's buffers (prep.h),
-// the opaque handles of include/sageicp.h.  Not part of the C ABI.
+// Internals shared by the translation units of libsageicp_hip.so's host side (capi.hip, capi_pipeline.hip,
+// capi_mirror.hip, capi_run.hip, prep.hip): error channel, tuning knobs, the per-handle device scratch, the pipeline's
+// frame source and buffers (prep.h) and its prefetch state (prefetch.h), the opaque handles of include/sageicp.h except
+// the pipeline's (capi_pipeline.hip).  Not part of the C ABI.
 #pragma once
 
 #include <dlfcn.h>
@@ -37,6 +38,7 @@
 #include "map_update.h"
 #include "metrics.hpp"
 #include "pipeline.hpp"
+#include "prefetch.h"
 #include "robin_order.hpp"
 #include "se3_math.h"
 #include "sageicp_types.h"
@@ -395,7 +397,7 @@ inline void cluster_emission_order(const uint32_t *sizes, size_t n, uint32_t *or
 
 }  // namespace sageicp
 
-// the frame-preparation driver in front of registration (prep.hip): DynFilter, the frame sources, PrepJob, Prep
+// the frame-preparation driver in front of registration (prep.hip): DynFilter, FrameSource, PrepJob, Prep
 #include "prep.h"
 
 using namespace sageicp;
@@ -522,7 +524,8 @@ struct sageicp_comm {
 };
 
 // ---- the library's translation units call each other through these --------------------------------------
-// capi.hip: the C ABI.  capi_mirror.hip: the HBM mirror of a map and Update() on the device.  capi_run.hip: the ICP
+// capi.hip: the C ABI of maps, frames, communicators and the stand-alone entries.  capi_pipeline.hip: the pipeline
+// handle and its entries.  capi_mirror.hip: the HBM mirror of a map and Update() on the device.  capi_run.hip: the ICP
 // loop (plan_loop, run_icp and its attempts), the RCCL binding and the single-process multi-GPU mode.
 namespace sageicp_impl {
 struct Rccl {
@@ -538,6 +541,24 @@ struct Rccl {
 };
 extern Rccl g_rccl;
 int load_rccl();
+// capi.hip: a caller's device memory and stream, checked; rows and records out; occupancy grids
+int check_extent(const void *p, uint64_t bytes, int device, const char *what);
+int check_stream(void *stream, int device);
+int check_device_frame(const sageicp_device_frame *f, const double *ts, void *stream, int device, int *found = nullptr);
+int check_device_points(const sageicp_device_points *d, void *stream, int device);
+int egress_into(DevBuf<int> &flag, const sageicp_device_points &dst, hipStream_t s,
+                const std::function<int(const EgressArgs &)> &write);
+int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
+                      double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
+                      sageicp_stats *stats);
+int color_table(const sageicp_msg_colors *c, MsgColorTable &t);
+int pack_msg(DevBuf<int> &flag, const Point4 *d_rows, uint64_t want, const MsgColorTable &t, unsigned char *d_out,
+             void *host_out, hipStream_t s);
+int reserve_records(DevBuf<unsigned char> &d_msg, uint64_t want);
+int check_records_out(const void *out, uint64_t cap, void *stream, int device);
+int occ_grid_from(const sageicp_occupancy_params *prm, OccGrid &g);
+OccTransform occ_transform(const double pose[7]);
+void occ_unpack_host(const uint32_t *bits, const OccGrid &g, uint8_t *out);
 // capi_mirror.hip
 int reserve_device_points(const sageicp_map *m, size_t units, size_t keep);
 int sync_mirror(const sageicp_map *m);

@@ -4,14 +4,14 @@
 // stay at the call sites: capacities reach the kernels) and when a stream or an event is created; the owner only
 // allocates, keeps a prefix when asked, and releases.
 //
-// What a handle that holds several of them (Scratch, Prep, sageicp_map, sageicp_pipeline: capi_internal.h, prep.h, capi.hip)
-// keeps when it goes:
+// What a handle that holds several of them (Scratch, Prep, sageicp_map, sageicp_pipeline: capi_internal.h, prep.h,
+// capi_pipeline.hip) keeps when it goes:
 //  - its device is made current before anything is released;
 //  - every stream of the handle has been waited for before a buffer that its work may touch is freed and before an
 //    event recorded on it is destroyed: the handle's destructor body waits, then the members go in reverse order of
 //    declaration, whatever that is (a one-call stream has no handle around it: declared after the buffers its work
 //    uses, it goes first);
-//  - the pipeline's worker thread is joined before either Prep goes;
+//  - the pipeline's worker thread is joined (Prefetch, prefetch.h: declared after the Preps) before either Prep goes;
 //  - a handle that never created its stream releases nothing and calls nothing.
 #pragma once
 

@@ -14,10 +14,10 @@
 // The PCL Euclidean-clustering "dynamic vehicle filter" (Preprocessing.cpp:95-172) runs on the device
 // (dyn_filter.hip) when sageicp_pipeline_set_dynamic_vehicle_filter switched it on, before the
 // down-sampling.  Deskewing (core/Deskew.cpp) runs on the device (deskew.hip) on the raw frame before anything else
-// when the caller passes timestamps, and three poses or more exist.  The down-sampled clouds come from the backend in the reference's
-// emission order (the bucket order of its tsl::robin_map, Preprocessing.cpp:76-82, replayed by
-// csrc/robin_order.hpp) unless sageicp_set_downsample_order(0) selected arrival order per label
-// group.
+// when this call reads the frame's stamps (FrameSource::read_stamps, prep.h) and three poses or more exist.  The
+// down-sampled clouds come from the backend in the reference's emission order (the bucket order of its tsl::robin_map,
+// Preprocessing.cpp:76-82, replayed by csrc/robin_order.hpp) unless sageicp_set_downsample_order(0) selected arrival
+// order per label group.
 #pragma once
 
 #include <algorithm>
@@ -67,19 +67,20 @@ public:
         sageicp_map_clear(map);
     }
 
-    // pipeline/sageICP.cpp:36-95.  The three device stages are supplied by the caller (capi.hip):
-    //   be.voxelize(frame, n, n_source, delta)  DeSkewScan() if delta != nullptr (deskew.hip; core/Deskew.cpp:36-50),
+    // pipeline/sageICP.cpp:36-95.  The three device stages are supplied by the caller (capi_pipeline.hip), which holds
+    // the raw frame of this call (FrameSource, prep.h):
+    //   be.voxelize(n_source, delta)         DeSkewScan() if delta != nullptr (deskew.hip; core/Deskew.cpp:36-50),
     //                                        then Preprocess() + Voxelize() (preprocess.hip;
     //                                        core/Preprocessing.cpp:173-187,44-84,
     //                                        pipeline/sageICP.cpp:57-67,97-101); both clouds stay
     //                                        on the device
     //   be.register_source(guess, max_corr, kernel, sem_th, pose, stats)    RegisterFrame(source, ...)
     //   be.update_map(pose)                  local_map_.Update(frame_downsample, pose)
-    // deskew: RegisterFrame(frame, timestamps) with config_.deskew (the caller has the timestamps); false: the
-    // one-argument RegisterFrame(frame), which never deskews.
+    // deskew: RegisterFrame(frame, timestamps) with config_.deskew (the source's read_stamps); false: the one-argument
+    // RegisterFrame(frame), which never deskews.
     template <typename Backend>
-    int register_frame(const double *frame, uint64_t n, bool deskew, double pose_out[7], double *icp_s,
-                       double *total_s, uint64_t *n_source, sageicp_stats *stats, Backend &&be) {
+    int register_frame(bool deskew, double pose_out[7], double *icp_s, double *total_s, uint64_t *n_source,
+                       sageicp_stats *stats, Backend &&be) {
         const auto t_pre = std::chrono::steady_clock::now();
         deskew_applied = false;
         for (double &d : deskew_delta) d = 0.0;
@@ -92,7 +93,7 @@ public:
             deskew_applied = true;
         }
         uint64_t n_src = 0;
-        int rc = be.voxelize(frame, n, n_src, deskew_applied ? deskew_delta : nullptr);
+        int rc = be.voxelize(n_src, deskew_applied ? deskew_delta : nullptr);
         if (rc) return rc;
         const double sigma = adaptive_threshold();
         Pose7 prediction;                                     // GetPredictionModel()

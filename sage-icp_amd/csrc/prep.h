@@ -1,7 +1,7 @@
-// The per-frame driver in front of registration: what a frame is prepared from (host rows, a device frame, a message),
-// what it passes through (deskew, the dynamic vehicle filter) and the buffers of one preparation (Prep).  Declarations
-// only: Prep's bodies are in prep.hip, DynFilter's in dyn_filter.hip.  Included by capi_internal.h after the helpers the
-// declarations name (ReplayPool); not part of the C ABI.
+// The per-frame driver in front of registration: what a frame is prepared from (FrameSource: host rows, a device frame,
+// a message), what it passes through (deskew, the dynamic vehicle filter) and the buffers of one preparation (Prep).
+// Declarations only: Prep's bodies are in prep.hip, DynFilter's in dyn_filter.hip.  Included by capi_internal.h after the
+// helpers the declarations name (ReplayPool); not part of the C ABI.
 #pragma once
 
 namespace sageicp {
@@ -35,31 +35,51 @@ struct DynFilter {
             const DynFilterConfig &cfg, Point4 *tmp, Point4 *out, int *d_ovf, uint64_t &n_out, hipStream_t s);
 };
 
-// ---- deskew of a frame before it is preprocessed (deskew.hip; core/Deskew.cpp:36-50) ---------------------------
-struct DeskewArgs {
-    const double *timestamps;           // host, one per point, all finite (checked by the caller); a device frame's are in
-                                        // its DeviceSource
-    DeskewTangent delta;                // (start.inverse() * finish).log()
-};
+// ---- the raw frame of one call ----------------------------------------------------------------------------------------
+// Where the frame comes from, said once: n rows in host memory; a sageicp_device_frame in the caller's device memory
+// (validated by capi.hip), which the ingest kernel reads into d_in on Prep::stream once that stream has waited for the
+// caller's; or n records of a sensor_msgs/PointCloud2 payload (sageicp_msg_layout, validated by capi_pipeline.hip) —
+// host bytes are uploaded as they are, device bytes are read in place behind the caller's stream — which k_msg_unpack
+// (msg.hip) turns into rows.  What follows the load does not know which.
+struct FrameSource {
+    enum Kind { kHostRows, kDeviceFrame, kMessage };
+    Kind kind = kHostRows;
+    uint64_t n = 0;
+    const double *rows = nullptr;                   // kHostRows: x, y, z, label
+    const sageicp_device_frame *frame = nullptr;    // kDeviceFrame
+    const unsigned char *payload = nullptr;         // kMessage: n * layout.point_step bytes, in device memory or not
+    bool payload_on_device = false;
+    sageicp_msg_layout layout{};
+    // The pipeline's deskew is on and this call reads the frame's stamps, one per point: `stamps` in host memory (host
+    // rows, all finite: checked by the caller), `stamps` in device memory (a device frame), the layout's time field (a
+    // message).  Off: the one-argument RegisterFrame, which never deskews; no stamp is read.
+    bool read_stamps = false;
+    const double *stamps = nullptr;
+    hipStream_t stream = nullptr;                   // the caller's: read for device memory only
 
-// A raw frame in the caller's device memory (sageicp_device_frame, validated by capi.hip): the ingest kernel reads it
-// into d_in on Prep::stream once that stream has waited for the caller's.  timestamps: device, n of them, or nullptr
-// (not asked for); they are copied to d_ts and checked in the same pass.
-struct MsgSource;
-struct DeviceSource {
-    const sageicp_device_frame *frame;
-    const double *timestamps;
-    hipStream_t stream;
-    const MsgSource *msg = nullptr;     // the frame is a message's payload instead (frame and timestamps are not read)
-};
-// A sensor_msgs/PointCloud2 payload (sageicp_msg_layout, validated by capi.hip): n records in host memory, which are
-// uploaded as they are, or in the caller's device memory, read in place behind DeviceSource::stream.  k_msg_unpack
-// (msg.hip) writes the rows into d_in and, with want_time, the stamps into d_ts.
-struct MsgSource {
-    const unsigned char *host;          // one of the two is set
-    const unsigned char *device;
-    sageicp_msg_layout layout;
-    bool want_time;                     // deskew is on: the time field is read and checked (layout.time_kind != 0)
+    static FrameSource host_rows(const double *rows, uint64_t n, bool read_stamps = false, const double *stamps = nullptr) {
+        FrameSource s;
+        s.n = n; s.rows = rows; s.read_stamps = read_stamps; s.stamps = stamps;
+        return s;
+    }
+    static FrameSource device_frame(const sageicp_device_frame *f, const double *stamps, hipStream_t stream) {
+        FrameSource s;
+        s.kind = kDeviceFrame; s.n = f->n; s.frame = f; s.stream = stream;
+        s.read_stamps = stamps != nullptr; s.stamps = stamps;       // (without stamps it is never deskewed)
+        return s;
+    }
+    static FrameSource message(const void *payload, bool on_device, uint64_t n, const sageicp_msg_layout &layout,
+                               bool read_stamps, hipStream_t stream) {
+        FrameSource s;
+        s.kind = kMessage; s.n = n; s.layout = layout; s.read_stamps = read_stamps; s.stream = stream;
+        s.payload = static_cast<const unsigned char *>(payload); s.payload_on_device = on_device;
+        return s;
+    }
+    // an empty message: no rows, no device work
+    bool empty_message() const { return kind == kMessage && n == 0; }
+    // The stamps go to d_ts with the frame.  Host stamps cross PCIe only when the frame is deskewed (three poses or
+    // more); a device frame's and a message's are copied and checked in the load's own pass whenever they are read.
+    bool stamps_to_device(bool deskewed) const { return read_stamps && (kind != kHostRows || deskewed); }
 };
 inline IngestArgs ingest_args(const sageicp_device_frame &f) {
     IngestArgs a{};
@@ -92,10 +112,8 @@ struct PrepJob {
     const DynFilterConfig *dyn = nullptr;
     // With `deskew` the loaded frame is deskewed in place before anything else reads it (the reference's order:
     // DeSkewScan, then Preprocess, then Voxelize; pipeline/sageICP.cpp:36-52).
-    const DeskewArgs *deskew = nullptr;
-    // With `dev` the raw frame comes from the caller's device memory, or from a message, instead of the host rows;
-    // everything after it reaches d_in is the same.
-    const DeviceSource *dev = nullptr;
+    // The tangent is (start.inverse() * finish).log() (core/Deskew.cpp:36); the stamps are the FrameSource's.
+    const DeskewTangent *deskew = nullptr;
 };
 
 // ---- device preprocessing (preprocess.hip): buffers of one pipeline ------------------------------
@@ -133,7 +151,7 @@ struct Prep {
     // in place — its coordinates checked — for the pass that follows the registration (allocated with the first use)
     bool keep_raw = false;
     DevBuf<Point4> d_raw;
-    // a message's payload (MsgSource): pinned staging and device copy of host bytes, the maximum of uint32 stamps
+    // a message's payload (FrameSource::kMessage): pinned staging and device copy of host bytes, the maximum of uint32 stamps
     // (allocated with the first such frame)
     PinnedBuf<unsigned char> h_blob;
     DevBuf<unsigned char> d_blob;
@@ -143,9 +161,8 @@ struct Prep {
     // any more (a Prep that never created its stream calls nothing)
     ~Prep();
     int init(int dev);
-    // Prepares one frame: n rows of x, y, z, label at `frame`, or job.dev's.  Every level's cloud stays on the device
-    // (kept_levels, d_fd / d_src).
-    int run(const double *frame, uint64_t n, const PrepJob &job);
+    // Prepares one frame.  Every level's cloud stays on the device (kept_levels, d_fd / d_src).
+    int run(const FrameSource &src, const PrepJob &job);
     // the cloud the last run left at `level`, copied to dst (4 * kept_levels[level] doubles)
     int fetch(int level, double *dst);
 
@@ -153,12 +170,12 @@ private:
     int reserve(size_t n, size_t nlabels);
     int reserve_timestamps(size_t n);
     // the phases of run(), in its order
-    int reset_and_reserve(uint64_t n, const PrepJob &job);
-    int load(const double *frame, uint64_t n, const PrepJob &job);
-    int ingest(const DeviceSource &src, uint64_t n);
-    int ingest_msg(const MsgSource &m, hipStream_t caller, uint64_t n);
+    int reset_and_reserve(const FrameSource &src, const PrepJob &job);
+    int load(const FrameSource &src, bool stamps);
+    int ingest(const FrameSource &src, bool stamps);
+    int ingest_msg(const FrameSource &src, bool stamps);
     int refuse_bad_timestamp();
-    int keep_raw_and_deskew(uint64_t n, const DeskewArgs *deskew);
+    int keep_raw_and_deskew(uint64_t n, const DeskewTangent *deskew);
     int downsample(int level, const Point4 *in, uint64_t n, const PrepJob &job, bool reorder, Point4 *dst, uint32_t &kept);
     int restore_reference_order(int level, Point4 *dst, uint32_t kept);
     int refuse_flags();

@@ -62,11 +62,12 @@ int Prep::reserve_timestamps(size_t n) {
     return SAGEICP_OK;
 }
 
-int Prep::run(const double *frame, uint64_t n, const PrepJob &job) {
+int Prep::run(const FrameSource &src, const PrepJob &job) {
     assert(job.n_levels <= 2);
-    int rc = reset_and_reserve(n, job);
+    const uint64_t n = src.n;
+    int rc = reset_and_reserve(src, job);
     if (rc || n == 0) return rc;
-    if ((rc = load(frame, n, job))) return rc;
+    if ((rc = load(src, src.stamps_to_device(job.deskew != nullptr)))) return rc;
     if ((rc = keep_raw_and_deskew(n, job.deskew))) return rc;
     const Point4 *in = d_in.data();
     Point4 *const outs[2] = {d_fd.data(), d_src.data()};
@@ -89,7 +90,8 @@ int Prep::run(const double *frame, uint64_t n, const PrepJob &job) {
 
 // What the last run left is forgotten, the buffers hold n points, and — for a frame that has points — the group tables
 // are on the device and the flag word is clear.
-int Prep::reset_and_reserve(uint64_t n, const PrepJob &job) {
+int Prep::reset_and_reserve(const FrameSource &src, const PrepJob &job) {
+    const uint64_t n = src.n;
     kept_levels[0] = kept_levels[1] = 0;
     dyn_ran = job.dyn != nullptr;
     dyn.info = sageicp_dynfilter_info{};
@@ -98,8 +100,7 @@ int Prep::reset_and_reserve(uint64_t n, const PrepJob &job) {
     size_t nlabels = 0;
     for (int g = 0; g < job.n_groups; ++g) nlabels += static_cast<size_t>(job.group_counts[g]);
     if (int rc = reserve(n, nlabels)) return rc;
-    const DeviceSource *dev = job.dev;
-    if (job.deskew || (dev && (dev->timestamps || (dev->msg && dev->msg->want_time))))
+    if (job.deskew || src.stamps_to_device(false))
         if (int rc = reserve_timestamps(n)) return rc;
     HIPCHK(hipSetDevice(device));
     if (n == 0) return SAGEICP_OK;
@@ -112,53 +113,53 @@ int Prep::reset_and_reserve(uint64_t n, const PrepJob &job) {
     return SAGEICP_OK;
 }
 
-// The raw frame into d_in and, when deskew reads them, its stamps into d_ts: from host rows, or from job.dev.  What
-// follows does not know which.
-int Prep::load(const double *frame, uint64_t n, const PrepJob &job) {
-    if (job.dev) return ingest(*job.dev, n);
-    std::memcpy(h_pin.data(), frame, n * sizeof(Point4));
+// The raw frame into d_in and, with `stamps` (FrameSource::stamps_to_device), its stamps into d_ts.  What follows does
+// not know where from.
+int Prep::load(const FrameSource &src, bool stamps) {
+    if (src.kind == FrameSource::kDeviceFrame) return ingest(src, stamps);
+    if (src.kind == FrameSource::kMessage) return ingest_msg(src, stamps);
+    const uint64_t n = src.n;
+    std::memcpy(h_pin.data(), src.rows, n * sizeof(Point4));
     HIPCHK(hipMemcpyAsync(d_in.data(), h_pin.data(), n * sizeof(Point4), hipMemcpyHostToDevice, stream.get()));
-    if (job.deskew) {
-        std::memcpy(h_ts.data(), job.deskew->timestamps, n * sizeof(double));
+    if (stamps) {
+        std::memcpy(h_ts.data(), src.stamps, n * sizeof(double));
         HIPCHK(hipMemcpyAsync(d_ts.data(), h_ts.data(), n * sizeof(double), hipMemcpyHostToDevice, stream.get()));
     }
     return SAGEICP_OK;
 }
 
-// The raw frame of a device source into d_in (and its timestamps into d_ts), after the work the caller enqueued on
+// The raw frame of a device frame into d_in (and its timestamps into d_ts), after the work the caller enqueued on
 // its stream.  Timestamps are checked here, before anything reads them: a non-finite one refuses the frame (the
 // host entry's check, sageicp_pipeline_register_frame_timestamps).  The caller's buffers are last read by this
 // launch, which the first level's synchronisation waits for: run() returns with them released.
-int Prep::ingest(const DeviceSource &src, uint64_t n) {
-    if (src.msg) return ingest_msg(*src.msg, src.stream, n);
+int Prep::ingest(const FrameSource &src, bool stamps) {
     if (int rc = stream_after_caller(ev_caller, src.stream, stream.get())) return rc;
     IngestArgs a = ingest_args(*src.frame);
-    a.n = static_cast<int>(n);
-    a.ts = src.timestamps;
-    a.ts_out = src.timestamps ? d_ts.data() : nullptr;
+    a.ts = stamps ? src.stamps : nullptr;
+    a.ts_out = stamps ? d_ts.data() : nullptr;
     a.flags = d_overflow.data();
     launch_ingest(a, d_in.data(), stream.get());
     HIPCHK(hipGetLastError());
-    return src.timestamps ? refuse_bad_timestamp() : SAGEICP_OK;
+    return stamps ? refuse_bad_timestamp() : SAGEICP_OK;
 }
 
 // The same of a message's payload: host bytes cross PCIe as they are (through the pinned staging copy), device bytes
 // are read in place behind the caller's stream.  uint32 stamps are normalised by their maximum in a second small
 // pass (NormalizeTimestamps); float64 stamps are checked like a device frame's.
-int Prep::ingest_msg(const MsgSource &m, hipStream_t caller, uint64_t n) {
-    const size_t bytes = static_cast<size_t>(n) * m.layout.point_step;
-    const unsigned char *d = m.device;
-    if (m.host) {
+int Prep::ingest_msg(const FrameSource &m, bool stamps) {
+    const size_t bytes = static_cast<size_t>(m.n) * m.layout.point_step;
+    const unsigned char *d = m.payload;
+    if (!m.payload_on_device) {
         if (bytes > h_blob.capacity()) {
             const size_t c = bytes + bytes / 4 + 4096;
             h_blob.reset();
             HIPCHK(d_blob.reserve(c));
             HIPCHK(h_blob.reserve(c));
         }
-        std::memcpy(h_blob.data(), m.host, bytes);
+        std::memcpy(h_blob.data(), m.payload, bytes);
         HIPCHK(hipMemcpyAsync(d_blob.data(), h_blob.data(), bytes, hipMemcpyHostToDevice, stream.get()));
         d = d_blob.data();
-    } else if (int rc = stream_after_caller(ev_caller, caller, stream.get())) {
+    } else if (int rc = stream_after_caller(ev_caller, m.stream, stream.get())) {
         return rc;
     }
     MsgUnpackArgs a{};
@@ -167,9 +168,9 @@ int Prep::ingest_msg(const MsgSource &m, hipStream_t caller, uint64_t n) {
     a.x_offset = m.layout.x_offset; a.y_offset = m.layout.y_offset; a.z_offset = m.layout.z_offset;
     a.label_offset = m.layout.label_offset;
     a.label_dtype = m.layout.label_dtype;
-    a.time_kind = m.want_time ? m.layout.time_kind : 0;
+    a.time_kind = stamps ? m.layout.time_kind : 0;
     a.time_offset = m.layout.time_offset;
-    a.n = static_cast<int>(n);
+    a.n = static_cast<int>(m.n);
     a.ts_out = a.time_kind ? d_ts.data() : nullptr;
     a.flags = d_overflow.data();
     if (a.time_kind == 1) {
@@ -196,10 +197,10 @@ int Prep::refuse_bad_timestamp() {
 }
 
 // the raw frame aside for the key-frame pass (its coordinates checked), then deskew in place
-int Prep::keep_raw_and_deskew(uint64_t n, const DeskewArgs *deskew) {
+int Prep::keep_raw_and_deskew(uint64_t n, const DeskewTangent *deskew) {
     if (keep_raw) launch_occ_keep(d_in.data(), d_raw.data(), static_cast<int>(n), d_overflow.data(), stream.get());
     if (deskew) {
-        launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), deskew->delta, stream.get());
+        launch_deskew(d_in.data(), d_in.data(), d_ts.data(), static_cast<int>(n), *deskew, stream.get());
         HIPCHK(hipGetLastError());
     }
     return SAGEICP_OK;
