@@ -291,7 +291,8 @@ int sageicp_comm_describe(const sageicp_comm *comm, sageicp_comm_info *out);
  * sageicp_voxel_downsample: core/Preprocessing.cpp:44-84: per label group g, the first point that
  * falls into a voxel of size group_voxel_size[g] * vox_scale is kept; points whose label is in no
  * group are dropped.  Output order: see sageicp_set_downsample_order (default: the reference's).
- * out: capacity n*4 doubles.  At most 8 groups; voxel indices must fit +-2^19. */
+ * out: capacity n*4 doubles.  At most 8 groups; voxel indices must fit +-2^19.  Every group_voxel_size[g] * vox_scale
+ * must be finite and above 0, else SAGEICP_ERR_INVALID (sageicp_pipeline_create asks the same of its sizes). */
 /* Emission order of sageicp_voxel_downsample and of the pipeline's two down-sampling levels:
  * 1 (default) = the reference's — the bucket order of the tsl::robin_map v1.0.1 its VoxelDownsample
  * iterates (Preprocessing.cpp:76-82), replayed on the host from the survivors' voxel keys, so that

@@ -1180,6 +1180,12 @@ int sageicp_voxel_downsample(const double *frame, uint64_t n, int n_groups,
     if (!n_out || (n && (!frame || !out)) || n_groups < 0 ||
         (n_groups && (!group_label_counts || !group_labels || !group_voxel_size)) || !(vox_scale > 0.0))
         return fail(SAGEICP_ERR_INVALID, "bad argument");
+    // (p / vs of a NaN size is NaN and its cast to int undefined; a size of 0 puts every index beyond the key range)
+    for (int g = 0; g < n_groups; ++g) {
+        const double vs = group_voxel_size[g] * vox_scale;
+        if (!(std::isfinite(vs) && vs > 0.0))
+            return fail(SAGEICP_ERR_INVALID, "a label group's voxel size times vox_scale is not finite or not above 0");
+    }
     PrepJob job;
     job.n_groups = n_groups;
     job.group_counts = group_label_counts; job.group_labels = group_labels; job.group_voxel_size = group_voxel_size;

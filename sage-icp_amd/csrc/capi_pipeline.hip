@@ -85,6 +85,12 @@ sageicp_pipeline *sageicp_pipeline_create(const sageicp_pipeline_config *c) {
         fail(SAGEICP_ERR_INVALID, "sageicp_pipeline_create: bad config");
         return nullptr;
     }
+    // (both levels' scales, 0.5 and 1.5, are positive constants: the sizes decide)
+    for (int g = 0; g < c->n_groups; ++g)
+        if (!(std::isfinite(c->group_voxel_size[g]) && c->group_voxel_size[g] > 0.0)) {
+            fail(SAGEICP_ERR_INVALID, "sageicp_pipeline_create: a label group's voxel size is not finite or not above 0");
+            return nullptr;
+        }
     sageicp_pipeline *p = new sageicp_pipeline(*c);
     if (!p->impl.ok()) {
         delete p;

@@ -9,6 +9,8 @@ stream with per-frame pose parity, free-running."""
 import numpy as np
 import pytest
 
+from prepref import py_preprocess as _py_preprocess, py_voxel_downsample as _py_voxel_downsample
+
 
 def _pose_err(oracle, A, B):
     e = oracle.se3_log(oracle.se3_mul(oracle.se3_inv(A), B))
@@ -142,32 +144,6 @@ def test_prefetch_recognises_a_refilled_buffer_and_can_be_cancelled(gpu_sage, re
     b.prefetch(frames[4])
     assert np.array_equal(b.RegisterFrame(frames[4])[0], ref[3])
     assert np.array_equal(a.LocalMap(), b.LocalMap())
-
-
-def _py_preprocess(frame, max_range, min_range, label_max_range):
-    out = []
-    for p in frame:
-        norm = float(np.sqrt((p[0] * p[0] + p[1] * p[1]) + p[2] * p[2]))     # point.head<3>().norm(): packet reduction
-        if norm < max_range and norm > min_range:
-            out.append([p[0], p[1], p[2], 0.0 if norm > label_max_range else p[3]])
-    return np.array(out).reshape(-1, 4)
-
-
-def _py_voxel_downsample(frame, voxel_labels, voxel_size, scale):
-    """core/Preprocessing.cpp:44-84 restated: first point per voxel per group; emitted group by
-    group in input order"""
-    grids = [dict() for _ in voxel_labels]
-    for p in frame:
-        label = int(p[3])
-        group = next((g for g, ls in enumerate(voxel_labels) if label in ls), -1)
-        if group < 0:
-            continue
-        vs = voxel_size[group] * scale
-        key = (int(p[0] / vs), int(p[1] / vs), int(p[2] / vs))
-        if key not in grids[group]:
-            grids[group][key] = p
-    out = [p for g in grids for p in g.values()]
-    return np.array(out).reshape(-1, 4)
 
 
 @pytest.mark.gpu
