@@ -21,6 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch                                                    # noqa: E402  (before the library: one HIP runtime)
 import sage_icp_amd as sage                                     # noqa: E402
+if os.environ.get("LOOP_LIB"):           # a variant build of the library (A/B runs)
+    sage.LIB_PATH = os.path.abspath(os.environ["LOOP_LIB"])
 from sage_icp_amd import synthetic as syn                       # noqa: E402
 
 DEV = "cuda:0"

@@ -38,166 +38,7 @@ const char *env_cached(const char *name) {
 std::atomic<int> g_reference_order{1};
 }  // namespace sageicp
 
-// ---- helpers that capi_pipeline.hip calls too (capi_internal.h) ------------------------------------------------------
 namespace sageicp_impl {
-// ---- rows in the caller's device memory: frames in (ingest.hip), outputs out (egress.hip, egress.h) ---------------
-static size_t dtype_bytes(int32_t t) {
-    switch (t) {
-    case SAGEICP_DTYPE_FLOAT32: return 4;
-    case SAGEICP_DTYPE_FLOAT64: return 8;
-    case SAGEICP_DTYPE_UINT8: return 1;
-    case SAGEICP_DTYPE_INT32: return 4;
-    case SAGEICP_DTYPE_INT64: return 8;
-    default: return 0;
-    }
-}
-
-// the device whose memory p is, as this library's runtime sees it (false: not device memory — host, pinned or managed
-// memory, or a pointer of another HIP runtime loaded into the process, which is unknown here)
-static bool device_of(const void *p, int *device) {
-    hipPointerAttribute_t at{};
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    (void)hipGetLastError();            // an unknown pointer leaves an error behind that the next call must not see
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice) return false;
-    *device = at.device;
-    return true;
-}
-
-// the first and the last byte of an extent must be device memory of `device`
-int check_extent(const void *p, uint64_t bytes, int device, const char *what) {
-    const char *ends[2] = {static_cast<const char *>(p), static_cast<const char *>(p) + bytes - 1};
-    for (const char *q : ends) {
-        int d = -1;
-        if (!device_of(q, &d))
-            return fail(SAGEICP_ERR_INVALID, std::string(what) + " is not device memory of this process's HIP runtime "
-                                             "(host, pinned and managed memory are refused, not copied)");
-        if (d != device)
-            return fail(SAGEICP_ERR_INVALID, std::string(what) + " lives on device " + std::to_string(d) +
-                                             ", the handle on device " + std::to_string(device));
-    }
-    return SAGEICP_OK;
-}
-
-// a caller's stream (NULL: the null stream) must be one of `device`
-int check_stream(void *stream, int device) {
-    if (!stream) return SAGEICP_OK;
-    int sd = -1;
-    const hipError_t e = hipStreamGetDevice(static_cast<hipStream_t>(stream), &sd);
-    (void)hipGetLastError();
-    if (e != hipSuccess || sd != device) return fail(SAGEICP_ERR_INVALID, "stream is not a stream of the handle's device");
-    return SAGEICP_OK;
-}
-
-// Strided rows in a caller's device memory: a frame's n (sageicp_device_frame) or a destination's cap
-// (sageicp_device_points).  Host-side only: the kernels take IngestArgs / EgressArgs.
-struct CallerRows {
-    const void *xyz;
-    uint64_t xyz_stride;
-    int32_t xyz_dtype;
-    const void *label;
-    uint64_t label_stride;
-    int32_t label_dtype;
-    uint64_t rows;
-};
-// what differs between a frame and a destination
-struct RowRules {
-    const char *prefix;                 // of the messages
-    unsigned label_dtypes;              // bit t: SAGEICP_DTYPE t is a valid label_dtype
-    const char *label_dtypes_text;
-    uint64_t max_rows;                  // (refused as a frame that is too large)
-};
-static const RowRules kFrameRows{
-    "device frame: ", 1u << SAGEICP_DTYPE_UINT8 | 1u << SAGEICP_DTYPE_INT32 | 1u << SAGEICP_DTYPE_INT64,
-    "SAGEICP_DTYPE_UINT8, _INT32 or _INT64", kMaxQueries};
-static const RowRules kPointsRows{
-    "device points: ", 1u << SAGEICP_DTYPE_UINT8 | 1u << SAGEICP_DTYPE_INT32 | 1u << SAGEICP_DTYPE_INT64 |
-                       1u << SAGEICP_DTYPE_FLOAT32 | 1u << SAGEICP_DTYPE_FLOAT64,
-    "SAGEICP_DTYPE_UINT8, _INT32, _INT64, _FLOAT32 or _FLOAT64", std::numeric_limits<uint64_t>::max()};
-
-// Everything about caller rows that can be known before the stream is touched or anything launched: the layout first
-// (no device needed), then where the memory of the rows (and of the n timestamps `ts` that will be read, if given)
-// lives, then the stream.  found: an entry without a handle works on the device xyz lives on (`device` is not read): it
-// is looked up once the layout has passed, and stored there.
-static int check_rows(const CallerRows &r, const RowRules &k, const double *ts, void *stream, int device,
-                      int *found = nullptr) {
-    const std::string pre = k.prefix;
-    if (r.rows && !r.xyz) return fail(SAGEICP_ERR_INVALID, pre + "xyz is NULL");
-    const size_t ex = r.xyz_dtype == SAGEICP_DTYPE_FLOAT32 || r.xyz_dtype == SAGEICP_DTYPE_FLOAT64 ? dtype_bytes(r.xyz_dtype) : 0;
-    if (!ex) return fail(SAGEICP_ERR_INVALID, pre + "xyz_dtype must be SAGEICP_DTYPE_FLOAT32 or _FLOAT64");
-    const uint64_t cols = r.label ? 3 : 4;
-    if (r.xyz_stride < cols * ex || r.xyz_stride % ex)
-        return fail(SAGEICP_ERR_INVALID, pre + (r.label ? "xyz_stride must be a multiple of the element size and at least 3 "
-                                                          "elements"
-                                                        : "xyz_stride must be a multiple of the element size and at least 4 "
-                                                          "elements (the label is column 3)"));
-    size_t el = 0;
-    if (r.label) {
-        el = dtype_bytes(r.label_dtype) && ((k.label_dtypes >> r.label_dtype) & 1u) ? dtype_bytes(r.label_dtype) : 0;
-        if (!el) return fail(SAGEICP_ERR_INVALID, pre + "label_dtype must be " + k.label_dtypes_text);
-        if (r.label_stride < el || r.label_stride % el)
-            return fail(SAGEICP_ERR_INVALID, pre + "label_stride must be a positive multiple of the label's size");
-    }
-    if (r.rows > k.max_rows) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
-    if (!r.rows) return SAGEICP_OK;
-    int rc = require_device();
-    if (rc) return rc;
-    if (found) {                        // (memory that is not device memory is refused just below)
-        device = 0;
-        (void)device_of(r.xyz, &device);
-        *found = device;
-    }
-    rc = check_extent(r.xyz, (r.rows - 1) * r.xyz_stride + cols * ex, device, (pre + "xyz").c_str());
-    if (!rc && r.label) rc = check_extent(r.label, (r.rows - 1) * r.label_stride + el, device, (pre + "label").c_str());
-    if (!rc && ts) rc = check_extent(ts, r.rows * sizeof(double), device, "timestamps");
-    return rc ? rc : check_stream(stream, device);
-}
-
-int check_device_frame(const sageicp_device_frame *f, const double *ts, void *stream, int device, int *found) {
-    if (!f) return fail(SAGEICP_ERR_INVALID, "null device frame");
-    return check_rows({f->xyz, f->xyz_stride, f->xyz_dtype, f->label, f->label_stride, f->label_dtype, f->n}, kFrameRows,
-                      ts, stream, device, found);
-}
-
-int check_device_points(const sageicp_device_points *d, void *stream, int device) {
-    if (!d) return fail(SAGEICP_ERR_INVALID, "null destination");
-    return check_rows({d->xyz, d->xyz_stride, d->xyz_dtype, d->label, d->label_stride, d->label_dtype, d->cap},
-                      kPointsRows, nullptr, stream, device);
-}
-
-static EgressArgs egress_args(const sageicp_device_points &d, int *flags) {
-    EgressArgs a{};
-    a.xyz = static_cast<unsigned char *>(d.xyz);
-    a.xyz_stride = d.xyz_stride;
-    a.xyz_dtype = d.xyz_dtype;
-    a.label = static_cast<unsigned char *>(d.label);
-    a.label_stride = d.label_stride;
-    a.label_dtype = d.label_dtype;
-    a.cap = d.cap;
-    a.flags = flags;
-    return a;
-}
-
-// The rows that write(EgressArgs) enqueues on s into a caller's destination, behind a zeroed label-range flag: waited
-// for, then the flag they may have raised read.  Synchronous also when write fails part-way: nothing this call
-// enqueued runs on once it has returned.
-int egress_into(DevBuf<int> &flag, const sageicp_device_points &dst, hipStream_t s,
-                       const std::function<int(const EgressArgs &)> &write) {
-    if (!flag) HIPCHK(flag.reserve(1));
-    HIPCHK(hipMemsetAsync(flag.data(), 0, sizeof(int), s));
-    if (int rc = write(egress_args(dst, flag.data()))) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    int flags = 0;
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&flags, flag.data(), sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (flags & kEgressLabelRange)
-        return fail(SAGEICP_ERR_INVALID, "a label does not fit the destination's label type (static_cast<int64_t>(label) "
-                                         "out of its range)");
-    return SAGEICP_OK;
-}
-
 // RegisterFrame of n points already on `device` (an uploaded frame, or the pipeline's source cloud)
 int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
                              double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
@@ -221,88 +62,6 @@ int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, i
     return run_icp(m, d_frame, n, init, max_dist, kernel, sem_th, comm, pose_out, stats, us_upload, t0);
 }
 
-// ---- occupancy grids (keyframe.hip) --------------------------------------------------------------------------------
-// the grid of validated params (include/sageicp.h: what is refused)
-int occ_grid_from(const sageicp_occupancy_params *prm, OccGrid &g) {
-    if (!prm) return fail(SAGEICP_ERR_INVALID, "null occupancy params");
-    for (int a = 0; a < 3; ++a) {
-        const double lo = prm->bounds[a][0], hi = prm->bounds[a][1];
-        if (!std::isfinite(lo) || !std::isfinite(hi)) return fail(SAGEICP_ERR_INVALID, "occupancy bounds are not finite");
-        if (!(lo < hi)) return fail(SAGEICP_ERR_INVALID, "occupancy bounds: lo >= hi on an axis");
-        g.lo[a] = lo;
-        g.hi[a] = hi;
-    }
-    if (prm->occ_h < 1 || prm->occ_h > kOccMaxSide || prm->occ_w < 1 || prm->occ_w > kOccMaxSide)
-        return fail(SAGEICP_ERR_INVALID, "occupancy size: occ_h and occ_w must lie in [1, 4096]");
-    if (!std::isfinite(prm->overlap_th)) return fail(SAGEICP_ERR_INVALID, "the overlap threshold is not finite");
-    g.h = prm->occ_h;
-    g.w = prm->occ_w;
-    // Utils.hpp:224-225: (bounds[0][1] - bounds[0][0]) / occ_size[1], (bounds[1][1] - bounds[1][0]) / occ_size[0]
-    g.x_res = (g.hi[0] - g.lo[0]) / static_cast<double>(g.w);
-    g.y_res = (g.hi[1] - g.lo[1]) / static_cast<double>(g.h);
-    return SAGEICP_OK;
-}
-OccTransform occ_transform(const double pose[7]) {
-    OccTransform t;
-    quat_to_mat(pose, t.R);                 // as fill_state does for k_tf
-    for (int i = 0; i < 3; ++i) t.t[i] = pose[4 + i];
-    return t;
-}
-// bits of a grid into H * W bytes
-void occ_unpack_host(const uint32_t *bits, const OccGrid &g, uint8_t *out) {
-    const uint64_t cells = static_cast<uint64_t>(g.h) * g.w;
-    for (uint64_t i = 0; i < cells; ++i) out[i] = static_cast<uint8_t>((bits[i >> 5] >> (i & 31)) & 1u);
-}
-
-// ---- sensor_msgs/PointCloud2 records out (msg.hip) ------------------------------------------------------------------
-// the node's color_list as the 256-entry table the label rule leaves room for: keys outside 0..255 can never match
-int color_table(const sageicp_msg_colors *c, MsgColorTable &t) {
-    std::memset(&t, 0, sizeof(t));
-    if (!c || !c->n) return SAGEICP_OK;
-    if (!c->keys || !c->values) return fail(SAGEICP_ERR_INVALID, "colour table: n > 0 with a NULL array");
-    for (uint32_t i = 0; i < c->n; ++i) {
-        const int32_t k = c->keys[i];
-        if (k < 0 || k > 255) continue;
-        t.value[k] = static_cast<uint32_t>(c->values[i]);
-        t.present[k >> 5] |= 1u << (k & 31);
-    }
-    return SAGEICP_OK;
-}
-
-// `want` packed rows as records at d_out (device memory) on s, behind a zeroed flag word; with host_out the records
-// follow to host memory.  Waited for, then the flags the rows may have raised read.
-int pack_msg(DevBuf<int> &flag, const Point4 *d_rows, uint64_t want, const MsgColorTable &t, unsigned char *d_out,
-             void *host_out, hipStream_t s) {
-    if (!flag) HIPCHK(flag.reserve(1));
-    HIPCHK(hipMemsetAsync(flag.data(), 0, sizeof(int), s));
-    launch_msg_pack(d_rows, want, t, d_out, flag.data(), s);
-    int flags = 0;
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(&flags, flag.data(), sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && host_out)
-        e = hipMemcpyAsync(host_out, d_out, want * SAGEICP_MSG_POINT_STEP, hipMemcpyDeviceToHost, s);
-    const hipError_t w = hipStreamSynchronize(s);        // (also after a failure: nothing enqueued here runs on)
-    HIPCHK(e);
-    HIPCHK(w);
-    if (flags & kMsgLabelRange)
-        return fail(SAGEICP_ERR_INVALID, "a label does not fit the record's uint8 (trunc(label) outside [0, 255])");
-    if (flags & kMsgNoColor) return fail(SAGEICP_ERR_INVALID, "the colour table has no colour for a label");
-    return SAGEICP_OK;
-}
-int reserve_records(DevBuf<unsigned char> &d_msg, uint64_t want) {
-    const size_t bytes = static_cast<size_t>(want) * SAGEICP_MSG_POINT_STEP;
-    if (bytes > d_msg.capacity()) HIPCHK(d_msg.reserve(bytes + bytes / 4 + 4096));
-    return SAGEICP_OK;
-}
-// a caller's destination of cap records in device memory, and its stream
-int check_records_out(const void *out, uint64_t cap, void *stream, int device) {
-    if (!cap) return SAGEICP_OK;
-    if (!out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    int rc = require_device();
-    if (rc) return rc;
-    if ((rc = check_extent(out, cap * SAGEICP_MSG_POINT_STEP, device, "message records: out"))) return rc;
-    return check_stream(stream, device);
-}
 }  // namespace sageicp_impl
 
 // =============================================================================================
@@ -624,121 +383,6 @@ int sageicp_map_update_pose_device(sageicp_map *m, const double *xyzl, uint64_t 
     return device_update_all(m, xyzl, n, pose, nullptr);
 }
 
-// Pointcloud() while the HBM copy is the authority: packed on the device (block counts -> prefix
-// sum -> gather, block-pool order like the host's), only size() x 32 B cross PCIe, and the map
-// stays where it is — the node's per-frame LocalMap() (ros/ros2/OdometryServer.cpp:211-220 under
-// publish_frame, the launch files' default) costs the copy of the live points and nothing else:
-// no table rebuild, no re-upload before the next RegisterFrame.
-// Make the pages of [p, p + bytes) exist — the range is about to be overwritten as a whole — from
-// SAGEICP_TOUCH_THREADS (default 4; 0: off) parked threads, each a contiguous share populated with
-// one madvise(MADV_POPULATE_WRITE) call (Linux 5.14) or, where that is refused, by a byte written
-// into every page.  (Measured and not kept: asking for huge pages first — no better; the copy cut
-// in pieces running behind the populating threads — slower than populate-then-copy, 3.1 vs 2.2 ms.)
-static void pretouch(void *p, size_t bytes) {
-    static const int threads = env_int("SAGEICP_TOUCH_THREADS", 4);
-    constexpr size_t kPage = 4096;
-    if (threads <= 0 || bytes < (size_t{4} << 20)) return;
-    static ReplayPool pool;
-    static std::mutex one_at_a_time;
-    std::lock_guard<std::mutex> lk(one_at_a_time);
-    char *base = static_cast<char *>(p);
-    // whole pages inside the range go through madvise; the ragged ends are touched
-    char *lo_al = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(base) + kPage - 1) & ~(kPage - 1));
-    char *hi_al = reinterpret_cast<char *>(reinterpret_cast<uintptr_t>(base + bytes) & ~(kPage - 1));
-    *static_cast<volatile char *>(base) = 0;
-    *static_cast<volatile char *>(base + bytes - 1) = 0;
-    if (hi_al <= lo_al) return;
-#ifdef MADV_HUGEPAGE
-    // where the kernel hands out transparent huge pages on request (.../transparent_hugepage/enabled = madvise, the
-    // usual setting), the 2-MB-aligned inside of the range is faulted in as ~20 huge pages instead of ~11,000 small
-    // ones: 2.95 against 3.11 ms per LocalMap() of 46 MB (SAGEICP_HUGEPAGES=0: off)
-    static const int huge = env_int("SAGEICP_HUGEPAGES", 1);
-    if (huge) {
-        constexpr uintptr_t kHuge = uintptr_t{2} << 20;
-        const uintptr_t h0 = (reinterpret_cast<uintptr_t>(lo_al) + kHuge - 1) & ~(kHuge - 1);
-        const uintptr_t h1 = reinterpret_cast<uintptr_t>(hi_al) & ~(kHuge - 1);
-        if (h1 > h0) (void)madvise(reinterpret_cast<void *>(h0), h1 - h0, MADV_HUGEPAGE);
-    }
-#endif
-    const size_t pages = static_cast<size_t>(hi_al - lo_al) / kPage, share = (pages + threads - 1) / threads;
-    const std::function<void(size_t)> job = [&](size_t t) {
-        const size_t lo = t * share, hi = std::min(pages, lo + share);
-        if (lo >= hi) return;
-#ifdef MADV_POPULATE_WRITE
-        if (madvise(lo_al + lo * kPage, (hi - lo) * kPage, MADV_POPULATE_WRITE) == 0) return;
-#endif
-        for (size_t i = lo; i < hi; ++i) *static_cast<volatile char *>(lo_al + i * kPage) = 0;
-    };
-    pool.run(static_cast<size_t>(threads), job, static_cast<size_t>(threads));
-}
-
-// The live points of a resident map packed on stream s in sageicp_map_pointcloud's order: into d_pc (e == nullptr), or
-// straight into a caller's layout (egress.h; the rows at and beyond e->cap are not written).  Synchronous only in
-// reference-order mode.
-static int pack_resident(const sageicp_map *m, const EgressArgs *e, hipStream_t s) {
-    const uint64_t total = m->ctr.total_points;
-    int rc = reserve_update_scratch(m, 0, static_cast<size_t>(m->ctr.blocks_hi) + 1);
-    if (rc) return rc;
-    if (!e && total > m->d_pc.capacity()) HIPCHK(m->d_pc.reserve(total + total / 4 + 1024));
-    const DevMap dm = dev_map(m);
-    if (m->host.track_order) {
-        // reference-order mode: the voxels in the bucket order of the host's array (VoxelHashMap.cpp:132-142), their points
-        // packed on the device in that order
-        std::vector<uint32_t> list;
-        list.reserve(m->host.order.size());
-        m->host.order.for_each([&](uint32_t b) { list.push_back(b); });
-        if ((rc = reserve_update_scratch(m, 0, list.size() + 1))) return rc;
-        uint32_t *d_list = reinterpret_cast<uint32_t *>(m->up.far_list.data());        // ([nb] uint2: room for the list)
-        if (!list.empty()) HIPCHK(hipMemcpyAsync(d_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        if (e)
-            HIPCHK(map_pointcloud_listed(dm, d_list, static_cast<uint32_t>(list.size()), m->up.far_flag.data(), m->up.far_sel.data(),
-                                         m->up.temp.data(), m->up.temp.capacity(), *e, s));
-        else
-            HIPCHK(map_pointcloud_listed(dm, d_list, static_cast<uint32_t>(list.size()), m->up.far_flag.data(), m->up.far_sel.data(),
-                                         m->up.temp.data(), m->up.temp.capacity(), m->d_pc.data(), s));
-        HIPCHK(hipStreamSynchronize(s));                                         // (`list` is pageable and leaves scope)
-    } else if (e) {
-        HIPCHK(map_pointcloud_device(dm, m->ctr.blocks_hi, m->up.far_flag.data(), m->up.far_sel.data(), m->up.temp.data(),
-                                     m->up.temp.capacity(), *e, s));
-    } else {
-        HIPCHK(map_pointcloud_device(dm, m->ctr.blocks_hi, m->up.far_flag.data(), m->up.far_sel.data(), m->up.temp.data(),
-                                     m->up.temp.capacity(), m->d_pc.data(), s));
-    }
-    return SAGEICP_OK;
-}
-
-static int pointcloud_from_device(const sageicp_map *m, double *out, uint64_t cap, uint64_t *n_out) {
-    HIPCHK(hipSetDevice(m->device));
-    hipStream_t s = m->sc.stream.get();
-    const uint64_t total = m->ctr.total_points;
-    *n_out = total;
-    const uint64_t want = out ? std::min(cap, total) : 0;
-    if (!want) return SAGEICP_OK;
-    int rc = pack_resident(m, nullptr, s);
-    if (rc) return rc;
-    // The destination is the caller's pageable buffer, and under the reference's interface a FRESH
-    // one every call (`std::vector<Eigen::Vector4d> Pointcloud()` returns by value: tens of MB
-    // straight from mmap).  The runtime's staged copy moves 63 MB in 1.2 ms into pages that exist —
-    // and in 3.4 ms into pages that do not: two thirds of the call were first-touch faults taken one
-    // by one inside the copy (profiles/pointcloud_probe.py).  So the pages are made to exist first, by a
-    // few parked host threads side by side, while the device packs the points.
-    pretouch(out, want * sizeof(Point4));
-    HIPCHK(hipMemcpyAsync(out, m->d_pc.data(), want * sizeof(Point4), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return SAGEICP_OK;
-}
-
-uint64_t sageicp_map_pointcloud(const sageicp_map *m, double *out, uint64_t cap) {
-    if (!m) return 0;
-    if (m->on_device) {
-        uint64_t n = 0;
-        if (pointcloud_from_device(m, out, cap, &n)) return 0;
-        return n;
-    }
-    if (out) pretouch(out, static_cast<size_t>(std::min<uint64_t>(cap, m->host.total_points)) * sizeof(Point4));
-    return m->host.pointcloud(out, out ? cap : 0);
-}
-
 int sageicp_map_resident(const sageicp_map *m) { return (m && m->on_device) ? 1 : 0; }
 
 uint64_t sageicp_map_point_slots(const sageicp_map *m) {
@@ -977,39 +621,6 @@ sageicp_frame *sageicp_frame_from_device(const sageicp_map *m, const sageicp_dev
     return f.release();
 }
 
-int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_points *dst, void *stream, uint64_t *n_out) {
-    if (!m || !n_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    int rc = check_device_points(dst, stream, m->device);
-    if (rc) return rc;
-    const uint64_t n = sageicp_map_size(m);
-    *n_out = n;
-    const uint64_t want = std::min(dst->cap, n);
-    if (!want) return SAGEICP_OK;
-    if ((rc = m->sc.init(m->device))) return rc;
-    HIPCHK(hipSetDevice(m->device));
-    const hipStream_t s = m->sc.stream.get();
-    // the map's stream waits for the work the caller enqueued before this call (it may still use the destination)
-    if ((rc = stream_after_caller(m->ev_caller, static_cast<hipStream_t>(stream), s))) return rc;
-    std::vector<double> staged;                         // (read by a copy on s: egress_into waits for it)
-    return egress_into(m->d_egress_flag, *dst, s, [&](const EgressArgs &e) -> int {
-        if (m->on_device && !env_int("SAGEICP_EGRESS_TWO_PASS", 0))
-            return pack_resident(m, &e, s);             // the gather writes the caller's layout itself
-        // two passes: the rows packed into d_pc (from the HBM copy, or staged from the host copy), then k_egress
-        if (m->on_device) {
-            int r = pack_resident(m, nullptr, s);
-            if (r) return r;
-        } else {
-            staged.resize(4 * n);
-            m->host.pointcloud(staged.data(), n);
-            if (n > m->d_pc.capacity()) HIPCHK(m->d_pc.reserve(n + n / 4 + 1024));
-            HIPCHK(hipMemcpyAsync(m->d_pc.data(), staged.data(), n * sizeof(Point4), hipMemcpyHostToDevice, s));
-        }
-        launch_egress(e, m->d_pc.data(), want, s);
-        return SAGEICP_OK;
-    });
-}
-
-
 int sageicp_register_frame_resident(const sageicp_map *m, const sageicp_frame *f,
                                     const double init[7], double max_dist, double kernel,
                                     double sem_th, sageicp_comm *comm, double pose_out[7],
@@ -1222,11 +833,6 @@ int sageicp_cluster_emission_order(const uint32_t *sizes, uint64_t n, uint32_t *
 }
 
 // ---- DeSkewScan on the device (deskew.hip) -----------------------------------------------------------
-static bool finite_n(const double *v, uint64_t n) {
-    for (uint64_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
 int sageicp_deskew_scan(const double *frame, const double *timestamps, uint64_t n, const double start_pose[7],
                         const double finish_pose[7], double *out, int device) {
     if (!start_pose || !finish_pose || (n && (!frame || !timestamps || !out)))
@@ -1269,126 +875,6 @@ uint32_t sageicp_msg_output_fields(sageicp_msg_field *out, uint32_t cap) {
         {"rgb", SAGEICP_MSG_RGB_OFFSET, SAGEICP_MSG_FIELD_UINT32, 1}};
     for (uint32_t i = 0; out && i < std::min<uint32_t>(cap, 5); ++i) out[i] = kFields[i];
     return 5;
-}
-
-// sageicp_map_pointcloud's rows into d_pc on s: packed from the HBM copy, or staged from the host copy (`staged` must
-// live until s has been waited for)
-static int map_rows_packed(const sageicp_map *m, uint64_t n, std::vector<double> &staged, hipStream_t s) {
-    if (m->on_device) return pack_resident(m, nullptr, s);
-    staged.resize(4 * n);
-    m->host.pointcloud(staged.data(), n);
-    if (n > m->d_pc.capacity()) HIPCHK(m->d_pc.reserve(n + n / 4 + 1024));
-    HIPCHK(hipMemcpyAsync(m->d_pc.data(), staged.data(), n * sizeof(Point4), hipMemcpyHostToDevice, s));
-    return SAGEICP_OK;
-}
-static int map_msg(const sageicp_map *m, const sageicp_msg_colors *colors, void *out, uint64_t cap, bool on_device,
-                   void *stream, uint64_t *n_out) {
-    if (!m || !n_out || (cap && !out)) return fail(SAGEICP_ERR_INVALID, "null argument");
-    MsgColorTable t;
-    int rc = color_table(colors, t);
-    if (rc) return rc;
-    if (on_device && (rc = check_records_out(out, cap, stream, m->device))) return rc;
-    const uint64_t n = sageicp_map_size(m);
-    *n_out = n;
-    const uint64_t want = std::min(cap, n);
-    if (!want) return SAGEICP_OK;
-    if ((rc = m->sc.init(m->device))) return rc;
-    HIPCHK(hipSetDevice(m->device));
-    const hipStream_t s = m->sc.stream.get();
-    // (on the device: the map's stream waits for the work the caller enqueued before this call)
-    if (on_device) rc = stream_after_caller(m->ev_caller, static_cast<hipStream_t>(stream), s);
-    else rc = reserve_records(m->d_msg, want);
-    if (rc) return rc;
-    std::vector<double> staged;
-    if ((rc = map_rows_packed(m, n, staged, s))) {
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    return pack_msg(m->d_egress_flag, m->d_pc.data(), want, t,
-                    on_device ? static_cast<unsigned char *>(out) : m->d_msg.data(), on_device ? nullptr : out, s);
-}
-int sageicp_map_pointcloud_msg(const sageicp_map *m, const sageicp_msg_colors *colors, void *out, uint64_t cap,
-                               uint64_t *n_out) {
-    return map_msg(m, colors, out, cap, false, nullptr, n_out);
-}
-int sageicp_map_pointcloud_msg_device(const sageicp_map *m, const sageicp_msg_colors *colors, void *out, uint64_t cap,
-                                      void *stream, uint64_t *n_out) {
-    return map_msg(m, colors, out, cap, true, stream, n_out);
-}
-
-// the grid of n rows already on the device (d_pts), moved by pose (or not), into host bytes; a coordinate that is not
-// finite refuses the call.  On stream s, which is synchronised.
-static int occupancy_on_device(const Point4 *d_pts, uint64_t n, const double *pose, const OccGrid &g, uint8_t *grid_out,
-                               hipStream_t s) {
-    const uint32_t words = occ_words(g);
-    DevBuf<uint32_t> d_bits;
-    DevBuf<int> d_flag;
-    HIPCHK(d_bits.reserve(words));
-    HIPCHK(d_flag.reserve(1));
-    HIPCHK(hipMemsetAsync(d_bits.data(), 0, words * sizeof(uint32_t), s));
-    HIPCHK(hipMemsetAsync(d_flag.data(), 0, sizeof(int), s));
-    const OccTransform tf = pose ? occ_transform(pose) : OccTransform{};
-    launch_occ_draw(d_pts, static_cast<int>(n), g, pose ? &tf : nullptr, pose ? nullptr : d_bits.data(),
-                    pose ? d_bits.data() : nullptr, d_flag.data(), env_int("SAGEICP_OCC_GLOBAL", 0) != 0, s);
-    HIPCHK(hipGetLastError());
-    std::vector<uint32_t> bits(words);
-    int flag = 0;
-    HIPCHK(hipMemcpyAsync(bits.data(), d_bits.data(), words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&flag, d_flag.data(), sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (flag & kOccNonFinite) return fail(SAGEICP_ERR_INVALID, "a coordinate is not finite (NaN / Inf)");
-    occ_unpack_host(bits.data(), g, grid_out);
-    return SAGEICP_OK;
-}
-
-int sageicp_occupancy_grid(const double *xyzl, uint64_t n, const double pose[7], const sageicp_occupancy_params *params,
-                           uint8_t *grid_out, int device) {
-    if ((n && !xyzl) || !grid_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    OccGrid g{};
-    int rc = occ_grid_from(params, g);
-    if (rc) return rc;
-    if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
-    if (pose && !finite_n(pose, 7)) return fail(SAGEICP_ERR_INVALID, "the pose is not finite");
-    for (uint64_t i = 0; i < n; ++i)
-        if (!finite_n(xyzl + 4 * i, 3)) return fail(SAGEICP_ERR_INVALID, "a coordinate is not finite (NaN / Inf)");
-    if (int rc = require_device(device)) return rc;
-    if (n == 0) {
-        std::memset(grid_out, 0, static_cast<size_t>(g.h) * g.w);
-        return SAGEICP_OK;
-    }
-    HIPCHK(hipSetDevice(device));
-    DevBuf<Point4> d_p;
-    OwnedStream s;                      // (after the buffer: waited for before it is freed)
-    HIPCHK(s.create());
-    HIPCHK(d_p.reserve(n));
-    HIPCHK(hipMemcpyAsync(d_p.data(), xyzl, n * sizeof(Point4), hipMemcpyHostToDevice, s.get()));
-    return occupancy_on_device(d_p.data(), n, pose, g, grid_out, s.get());
-}
-int sageicp_occupancy_grid_device(const sageicp_device_frame *frame, const double pose[7],
-                                  const sageicp_occupancy_params *params, uint8_t *grid_out, void *stream) {
-    if (!frame || !grid_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    OccGrid g{};
-    int rc = occ_grid_from(params, g);
-    if (rc) return rc;
-    if (pose && !finite_n(pose, 7)) return fail(SAGEICP_ERR_INVALID, "the pose is not finite");
-    // no handle: the work runs on the device the frame's memory lives on, looked up once its layout has passed
-    int device = 0;
-    rc = check_device_frame(frame, nullptr, stream, device, &device);
-    if (rc) return rc;
-    if (frame->n == 0) {
-        std::memset(grid_out, 0, static_cast<size_t>(g.h) * g.w);
-        return SAGEICP_OK;
-    }
-    HIPCHK(hipSetDevice(device));
-    // on the caller's stream, behind the work that wrote the frame; synchronous
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    DevBuf<Point4> d_p;
-    HIPCHK(d_p.reserve(frame->n));
-    launch_ingest(ingest_args(*frame), d_p.data(), s);
-    HIPCHK(hipGetLastError());
-    rc = occupancy_on_device(d_p.data(), frame->n, pose, g, grid_out, s);
-    (void)hipStreamSynchronize(s);          // (d_p leaves scope)
-    return rc;
 }
 
 // ---- KITTI trajectory metrics (metrics/Metrics.cpp) ------------------------------------------------

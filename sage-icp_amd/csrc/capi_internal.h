@@ -1,7 +1,8 @@
 // Internals shared by the translation units of libsageicp_hip.so's host side (capi.hip, capi_pipeline.hip,
-// capi_mirror.hip, capi_run.hip, prep.hip): error channel, tuning knobs, the per-handle device scratch, the pipeline's
-// frame source and buffers (prep.h) and its prefetch state (prefetch.h), the opaque handles of include/sageicp.h except
-// the pipeline's (capi_pipeline.hip).  Not part of the C ABI.
+// capi_outputs.hip, caller_mem.hip, capi_mirror.hip, capi_run.hip, prep.hip): error channel, tuning knobs, the
+// per-handle device scratch, the pipeline's frame source and buffers (prep.h) and its prefetch state (prefetch.h), the
+// checks of a caller's device memory (caller_mem.h), the way out (outputs.h), the opaque handles of include/sageicp.h
+// except the pipeline's (capi_pipeline.hip).  Not part of the C ABI.
 #pragma once
 
 #include <dlfcn.h>
@@ -140,6 +141,12 @@ inline int stream_after_caller(OwnedEvent &ev, hipStream_t caller, hipStream_t o
     HIPCHK(hipEventRecord(ev.get(), caller));
     HIPCHK(hipStreamWaitEvent(ours, ev.get(), 0));
     return SAGEICP_OK;
+}
+
+inline bool finite_n(const double *v, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
 }
 
 inline double now_us() {
@@ -402,6 +409,9 @@ inline void cluster_emission_order(const uint32_t *sizes, size_t n, uint32_t *or
 
 using namespace sageicp;
 
+#include "caller_mem.h"
+#include "outputs.h"
+
 // ---- opaque handles -----------------------------------------------------------------------
 struct sageicp_map {
     HostMap host;
@@ -475,14 +485,7 @@ struct sageicp_map {
         }
     };
     mutable UpdateBuffers up;
-    // Pointcloud() served from the HBM copy: the packed points before they cross PCIe
-    mutable DevBuf<Point4> d_pc;
-    // sageicp_map_pointcloud_msg: the 21-byte records before they cross PCIe
-    mutable DevBuf<unsigned char> d_msg;
-    // sageicp_map_pointcloud_device: the label-range flag (egress.h) and the event that orders the caller's stream
-    // before the map's (created with the first call)
-    mutable DevBuf<int> d_egress_flag;
-    mutable OwnedEvent ev_caller;
+    mutable sageicp_impl::OutputBuffers out;     // sageicp_map_pointcloud*: the exports work in these (outputs.h)
     size_t units_cap() const { return d_pts.capacity() / kUnitPoints; }       // units the point array holds
     size_t blocks_cap() const { return d_zeros.capacity(); }
     size_t cand_slots() const { return d_cand.capacity() ? d_cand.capacity() - 1 - kCandSlack : 0; }
@@ -525,8 +528,10 @@ struct sageicp_comm {
 
 // ---- the library's translation units call each other through these --------------------------------------
 // capi.hip: the C ABI of maps, frames, communicators and the stand-alone entries.  capi_pipeline.hip: the pipeline
-// handle and its entries.  capi_mirror.hip: the HBM mirror of a map and Update() on the device.  capi_run.hip: the ICP
-// loop (plan_loop, run_icp and its attempts), the RCCL binding and the single-process multi-GPU mode.
+// handle and its entries.  capi_outputs.hip: rows, records and grids out (outputs.h).  caller_mem.hip: the checks of a
+// caller's device memory (caller_mem.h).  capi_mirror.hip: the HBM mirror of a map and Update() on the device.
+// capi_run.hip: the ICP loop (plan_loop, run_icp and its attempts), the RCCL binding and the single-process multi-GPU
+// mode.
 namespace sageicp_impl {
 struct Rccl {
     void *h = nullptr;
@@ -541,24 +546,10 @@ struct Rccl {
 };
 extern Rccl g_rccl;
 int load_rccl();
-// capi.hip: a caller's device memory and stream, checked; rows and records out; occupancy grids
-int check_extent(const void *p, uint64_t bytes, int device, const char *what);
-int check_stream(void *stream, int device);
-int check_device_frame(const sageicp_device_frame *f, const double *ts, void *stream, int device, int *found = nullptr);
-int check_device_points(const sageicp_device_points *d, void *stream, int device);
-int egress_into(DevBuf<int> &flag, const sageicp_device_points &dst, hipStream_t s,
-                const std::function<int(const EgressArgs &)> &write);
+// capi.hip
 int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
                       double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
                       sageicp_stats *stats);
-int color_table(const sageicp_msg_colors *c, MsgColorTable &t);
-int pack_msg(DevBuf<int> &flag, const Point4 *d_rows, uint64_t want, const MsgColorTable &t, unsigned char *d_out,
-             void *host_out, hipStream_t s);
-int reserve_records(DevBuf<unsigned char> &d_msg, uint64_t want);
-int check_records_out(const void *out, uint64_t cap, void *stream, int device);
-int occ_grid_from(const sageicp_occupancy_params *prm, OccGrid &g);
-OccTransform occ_transform(const double pose[7]);
-void occ_unpack_host(const uint32_t *bits, const OccGrid &g, uint8_t *out);
 // capi_mirror.hip
 int reserve_device_points(const sageicp_map *m, size_t units, size_t keep);
 int sync_mirror(const sageicp_map *m);

@@ -3,7 +3,7 @@
 // device frame, a message — and pipeline_register runs Pipeline::register_frame (pipeline.hpp) over a backend that
 // holds it: Prep (prep.hip) prepares the frame, or hands over the one the prefetch worker prepared (prefetch.h); the
 // registration and the map update are capi.hip's and capi_run.hip's.  Then the key-frame step, the exported source
-// cloud and the switches.  Host code only.  Part of libsageicp_hip.so's host side: capi_internal.h.
+// cloud (through outputs.h's driver) and the switches.  Host code only.  Part of libsageicp_hip.so's host side: capi_internal.h.
 #include "capi_internal.h"
 
 extern "C" {
@@ -28,8 +28,7 @@ struct sageicp_pipeline {
     // prefetch worker fills the other one, and the registration reads d_src without reordering it.
     uint64_t src_n = 0;
     int src_buf = 0;
-    mutable DevBuf<int> d_egress_flag;
-    mutable DevBuf<unsigned char> d_msg;           // sageicp_pipeline_source_msg: the records before they cross PCIe
+    mutable OutputBuffers out;                     // sageicp_pipeline_source*: the exports work in these (outputs.h)
     // key-frame selection (sageicp_pipeline_set_key_frames, keyframe.hip): off by default.  The key grid lives on the
     // device (d_key); the host holds the key pose and what the last frame's step decided.
     struct KeyFrames {
@@ -53,7 +52,7 @@ struct sageicp_pipeline {
         }
         KeyFrames() { clear(); }
     } kf;
-    // (after the buffers that work on their streams touches — d_egress_flag, kf's: the Preps wait and go first)
+    // (after the buffers that work on their streams touches — out, kf's: the Preps wait and go first)
     Prep prep[2];
     // (after the Preps: its worker runs voxelize_into on prep[cur ^ 1], and is joined before either goes)
     Prefetch pf;
@@ -323,61 +322,38 @@ int sageicp_pipeline_register_frame_msg_device(sageicp_pipeline *p, const void *
     return register_msg(p, data, data_bytes, n, layout, true, stream, pose_out, icp_s, total_s, n_source, stats);
 }
 
-int sageicp_pipeline_source_msg(const sageicp_pipeline *p, const sageicp_msg_colors *colors, void *out, uint64_t cap,
-                                uint64_t *n_out) {
-    if (!p || !n_out || (cap && !out)) return fail(SAGEICP_ERR_INVALID, "null argument");
+// ---- the registered source cloud out (outputs.h) --------------------------------------------------------------------
+// src_n rows of prep[src_buf].d_src, there on that Prep's stream
+static RowSource source_rows(const sageicp_pipeline *p) {
+    const Prep &pr = p->prep[p->src_buf];
+    return RowSource::packed(pr.d_src.data(), p->src_n, pr.stream.get());
+}
+static int source_msg(const sageicp_pipeline *p, const sageicp_msg_colors *colors, void *out, uint64_t cap, bool on_device,
+                      void *stream, uint64_t *n_out) {
+    if (!p || !n_out || (!on_device && cap && !out)) return fail(SAGEICP_ERR_INVALID, "null argument");
     MsgColorTable t;
     int rc = color_table(colors, t);
     if (rc) return rc;
-    *n_out = p->src_n;
-    const uint64_t want = std::min(cap, p->src_n);
-    if (!want) return SAGEICP_OK;
-    HIPCHK(hipSetDevice(p->device));
-    if ((rc = reserve_records(p->d_msg, want))) return rc;
-    const Prep &pr = p->prep[p->src_buf];
-    return pack_msg(p->d_egress_flag, pr.d_src.data(), want, t, p->d_msg.data(), out, pr.stream.get());
+    if (on_device && (rc = check_records_out(out, cap, stream, p->device))) return rc;
+    return export_rows(p->out, p->device, source_rows(p), RowSink::records_out(out, cap, t, on_device, stream), n_out);
+}
+int sageicp_pipeline_source_msg(const sageicp_pipeline *p, const sageicp_msg_colors *colors, void *out, uint64_t cap,
+                                uint64_t *n_out) {
+    return source_msg(p, colors, out, cap, false, nullptr, n_out);
 }
 int sageicp_pipeline_source_msg_device(const sageicp_pipeline *p, const sageicp_msg_colors *colors, void *out,
                                        uint64_t cap, void *stream, uint64_t *n_out) {
-    if (!p || !n_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    MsgColorTable t;
-    int rc = color_table(colors, t);
-    if (rc) return rc;
-    if ((rc = check_records_out(out, cap, stream, p->device))) return rc;
-    *n_out = p->src_n;
-    const uint64_t want = std::min(cap, p->src_n);
-    if (!want) return SAGEICP_OK;
-    HIPCHK(hipSetDevice(p->device));
-    // on the caller's stream, behind the work it enqueued before this call; synchronous
-    return pack_msg(p->d_egress_flag, p->prep[p->src_buf].d_src.data(), want, t, static_cast<unsigned char *>(out), nullptr,
-                    static_cast<hipStream_t>(stream));
+    return source_msg(p, colors, out, cap, true, stream, n_out);
 }
-
 int sageicp_pipeline_source(const sageicp_pipeline *p, double *out, uint64_t cap, uint64_t *n_out) {
     if (!p || !n_out || (cap && !out)) return fail(SAGEICP_ERR_INVALID, "null argument");
-    *n_out = p->src_n;
-    const uint64_t want = std::min(cap, p->src_n);
-    if (!want) return SAGEICP_OK;
-    HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpy(out, p->prep[p->src_buf].d_src.data(), want * sizeof(Point4), hipMemcpyDeviceToHost));
-    return SAGEICP_OK;
+    return export_rows(p->out, p->device, source_rows(p), RowSink::host_rows(out, cap), n_out);
 }
 int sageicp_pipeline_source_device(const sageicp_pipeline *p, const sageicp_device_points *dst, void *stream,
                                    uint64_t *n_out) {
     if (!p || !n_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    int rc = check_device_points(dst, stream, p->device);
-    if (rc) return rc;
-    *n_out = p->src_n;
-    const uint64_t want = std::min(dst->cap, p->src_n);
-    if (!want) return SAGEICP_OK;
-    HIPCHK(hipSetDevice(p->device));
-    // on the caller's stream, behind the work it enqueued before this call; synchronous: afterwards nothing of the
-    // library touches the destination
-    const hipStream_t s = static_cast<hipStream_t>(stream);
-    return egress_into(p->d_egress_flag, *dst, s, [&](const EgressArgs &e) {
-        launch_egress(e, p->prep[p->src_buf].d_src.data(), want, s);
-        return SAGEICP_OK;
-    });
+    if (int rc = check_device_points(dst, stream, p->device)) return rc;
+    return export_rows(p->out, p->device, source_rows(p), RowSink::device_rows(dst, stream), n_out);
 }
 int sageicp_pipeline_set_deskew(sageicp_pipeline *p, int enable) {
     if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
@@ -503,11 +479,8 @@ int sageicp_pipeline_key_frame_grid(const sageicp_pipeline *p, uint8_t *out, uin
         std::memset(out, 0, cells);
         return SAGEICP_OK;
     }
-    std::vector<uint32_t> bits(occ_words(k.g));
     HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipMemcpy(bits.data(), k.d_key.data(), bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    occ_unpack_host(bits.data(), k.g, out);
-    return SAGEICP_OK;
+    return occ_bytes_to_host(k.d_key.data(), k.g, out);
 }
 int sageicp_pipeline_key_frame_grid_device(const sageicp_pipeline *p, uint8_t *out, uint64_t cap, void *stream) {
     uint64_t cells = 0;
@@ -518,13 +491,8 @@ int sageicp_pipeline_key_frame_grid_device(const sageicp_pipeline *p, uint8_t *o
     if (rc) return rc;
     HIPCHK(hipSetDevice(p->device));
     // on the caller's stream, behind the work it enqueued before this call; synchronous
-    const hipStream_t s = static_cast<hipStream_t>(stream);
     const auto &k = p->kf;
-    if (k.has_key) launch_occ_unpack(k.d_key.data(), k.g, out, s);
-    else HIPCHK(hipMemsetAsync(out, 0, cells, s));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
-    return SAGEICP_OK;
+    return occ_bytes_to_device(k.has_key ? k.d_key.data() : nullptr, k.g, out, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

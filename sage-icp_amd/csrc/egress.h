@@ -88,8 +88,13 @@ struct Point4Writer {
     Point4 *out;
     __device__ __forceinline__ void operator()(size_t i, const Point4 &p) const { out[i] = p; }
 };
+// where a gather of the local map writes (map_update.h): the library's packed rows, or a caller's layout
+struct RowsOut {
+    Point4 *packed;                     // nullptr: `caller`
+    EgressArgs caller;
+};
 
-// f(EgressWriter<T, L, Vec>{a}) for the layout of `a` (validated by capi.hip).  A float32 row without its label
+// f(EgressWriter<T, L, Vec>{a}) for the layout of `a` (validated by caller_mem.hip).  A float32 row without its label
 // column has no 16-B store (12 B), so it always takes the element-wise form.
 template <typename T, typename L, typename F>
 inline void with_egress_vec(const EgressArgs &a, F &&f) {
@@ -114,6 +119,13 @@ template <typename F>
 inline void with_egress_writer(const EgressArgs &a, F &&f) {
     if (a.xyz_dtype == SAGEICP_DTYPE_FLOAT32) with_egress_label<float>(a, f);
     else with_egress_label<double>(a, f);
+}
+
+// f(Point4Writer) or f(EgressWriter) for either output of a gather
+template <typename F>
+inline void with_writer(const RowsOut &out, F &&f) {
+    if (out.packed) f(Point4Writer{out.packed});
+    else with_egress_writer(out.caller, f);
 }
 
 // k_egress: rows [0, n) of `in` (n <= cap) into the caller's layout, one lane per row

@@ -1,5 +1,5 @@
 // The library's Point4 rows out into a caller's device memory (include/sageicp.h, sageicp_device_points): the pipeline's
-// registered source cloud, and the local map when it is staged from the host copy.  The inverse of k_ingest
+// registered source cloud, and the local map when it is staged from the host copy (capi_outputs.hip drives both).  The inverse of k_ingest
 // (ingest.hip): one lane per row, the conversions and 16-B stores of EgressWriter (egress.h).
 #include <hip/hip_runtime.h>
 

@@ -290,7 +290,7 @@ void launch_deskew(const Point4 *in, Point4 *out, const double *ts, int n, const
 
 // ingest.hip: a frame in a caller's device memory (include/sageicp.h, sageicp_device_frame) into n Point4 rows, every
 // value a plain (double) conversion; optionally the frame's fp64 timestamps copied alongside, a non-finite one raising
-// kIngestBadTimestamp in *flags.  The layout has been validated by the caller (capi.hip).
+// kIngestBadTimestamp in *flags.  The layout has been validated by the caller (caller_mem.hip).
 constexpr int kIngestBadTimestamp = 8;      // (Prep::d_overflow: 1, 2 are preprocess.hip's, 4 dyn_filter.hip's)
 struct IngestArgs {
     const unsigned char *xyz;           // row i at xyz + i * xyz_stride

@@ -113,21 +113,17 @@ hipError_t map_update_device(const DevMap &M, const UpdatePolicy &P, const Updat
 hipError_t map_update_insert_find_far(const DevMap &M, const UpdatePolicy &P, const UpdateScratch &S, int n,
                                       const double pose[7], uint32_t blocks_hi_bound, hipStream_t s);
 hipError_t map_evict_listed(const DevMap &M, const uint32_t *d_list, const uint32_t *d_n, uint32_t bound, hipStream_t s);
-// Pointcloud() in a given order of the voxels: the points of blocks list[0], list[1], ... (n_list of them) packed into
-// `out`; counts / offsets: [n_list + 1] scratch.
+// Pointcloud() in a given order of the voxels: the points of blocks list[0], list[1], ... (n_list of them) into `out`
+// (egress.h): packed, or straight into a caller's layout, where rows at and beyond its cap are not written.  counts /
+// offsets: [n_list + 1] scratch.
 hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts, uint32_t *offsets,
-                                 void *temp, size_t temp_bytes, Point4 *out, hipStream_t s);
-// ... straight into a caller's layout (egress.h): rows at and beyond out.cap are not written
-hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts, uint32_t *offsets,
-                                 void *temp, size_t temp_bytes, const EgressArgs &out, hipStream_t s);
+                                 void *temp, size_t temp_bytes, const RowsOut &out, hipStream_t s);
 
-// Pointcloud() of the HBM copy: the live points of blocks [0, blocks_hi) packed into `out` in
+// Pointcloud() of the HBM copy: the live points of blocks [0, blocks_hi) into `out` (as above) in
 // block-pool order (what HostMap::pointcloud emits).  counts / offsets: [blocks_hi + 1] scratch;
-// offsets[blocks_hi] is the number of points written.
+// offsets[blocks_hi] is the number of points the map holds.
 hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
-                                 void *temp, size_t temp_bytes, Point4 *out, hipStream_t s);
-hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
-                                 void *temp, size_t temp_bytes, const EgressArgs &out, hipStream_t s);
+                                 void *temp, size_t temp_bytes, const RowsOut &out, hipStream_t s);
 
 // Re-insert every live voxel into a fresh (larger or tombstone-free) table.
 hipError_t map_rebuild_table(const DevMap &M, Slot *new_table, uint32_t new_mask,

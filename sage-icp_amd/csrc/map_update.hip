@@ -552,12 +552,6 @@ __global__ void k_rebuild_after(MapCounters *ctr) {
     ctr->used_slots = ctr->num_voxels;
 }
 
-// the gather kernels' output: the library's packed rows, or the caller's layout
-template <typename F>
-void with_writer(Point4 *out, F &&f) { f(Point4Writer{out}); }
-template <typename F>
-void with_writer(const EgressArgs &out, F &&f) { with_egress_writer(out, f); }
-
 }  // namespace
 
 void map_derive_block_of(const DevMap &M, uint32_t blocks_hi, hipStream_t s) {
@@ -658,9 +652,8 @@ hipError_t map_update_insert_find_far(const DevMap &M, const UpdatePolicy &P, co
     return hipGetLastError();
 }
 
-template <typename Out>
-static hipError_t pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts,
-                                    uint32_t *offsets, void *temp, size_t temp_bytes, const Out &out, hipStream_t s) {
+hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts, uint32_t *offsets,
+                                 void *temp, size_t temp_bytes, const RowsOut &out, hipStream_t s) {
     if (n_list == 0) return hipSuccess;
     const int gb = static_cast<int>((n_list + 1u + 255u) / 256u);
     hipLaunchKernelGGL(k_pc_counts_listed, dim3(gb), dim3(256), 0, s, M, d_list, n_list, counts);
@@ -676,18 +669,9 @@ static hipError_t pointcloud_listed(const DevMap &M, const uint32_t *d_list, uin
     });
     return hipGetLastError();
 }
-hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts, uint32_t *offsets,
-                                 void *temp, size_t temp_bytes, Point4 *out, hipStream_t s) {
-    return pointcloud_listed(M, d_list, n_list, counts, offsets, temp, temp_bytes, out, s);
-}
-hipError_t map_pointcloud_listed(const DevMap &M, const uint32_t *d_list, uint32_t n_list, uint32_t *counts, uint32_t *offsets,
-                                 void *temp, size_t temp_bytes, const EgressArgs &out, hipStream_t s) {
-    return pointcloud_listed(M, d_list, n_list, counts, offsets, temp, temp_bytes, out, s);
-}
 
-template <typename Out>
-static hipError_t pointcloud_regions(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
-                                     void *temp, size_t temp_bytes, const Out &out, hipStream_t s) {
+hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
+                                 void *temp, size_t temp_bytes, const RowsOut &out, hipStream_t s) {
     if (blocks_hi == 0) return hipSuccess;
     const int gb = static_cast<int>((blocks_hi + 1u + 255u) / 256u);
     hipLaunchKernelGGL(k_pc_counts, dim3(gb), dim3(256), 0, s, M, blocks_hi, counts);
@@ -702,14 +686,6 @@ static hipError_t pointcloud_regions(const DevMap &M, uint32_t blocks_hi, uint32
         hipLaunchKernelGGL(k_pc_gather_regions<decltype(w)>, grid, dim3(256), 0, s, M, blocks_hi, span, counts, offsets, w);
     });
     return hipGetLastError();
-}
-hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
-                                 void *temp, size_t temp_bytes, Point4 *out, hipStream_t s) {
-    return pointcloud_regions(M, blocks_hi, counts, offsets, temp, temp_bytes, out, s);
-}
-hipError_t map_pointcloud_device(const DevMap &M, uint32_t blocks_hi, uint32_t *counts, uint32_t *offsets,
-                                 void *temp, size_t temp_bytes, const EgressArgs &out, hipStream_t s) {
-    return pointcloud_regions(M, blocks_hi, counts, offsets, temp, temp_bytes, out, s);
 }
 
 hipError_t map_rebuild_table(const DevMap &M, Slot *new_table, uint32_t new_mask,

@@ -6,7 +6,7 @@
 //   k_msg_normalize NormalizeTimestamps (Utils.hpp:68-77) of uint32 stamps: divided by their maximum unless it is 0.
 //   k_msg_pack     CreatePointCloud2Msg + FillPointCloud2XYZlRGB: packed Point4 rows into the 21-byte records the node
 //                  publishes (include/sageicp.h, SAGEICP_MSG_*).
-// The layouts have been validated by the caller (check_msg, capi_pipeline.hip).
+// The layouts have been validated by the caller (check_msg, capi_pipeline.hip); the pack is driven by capi_outputs.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -37,7 +37,7 @@ struct DynFilter {
 
 // ---- the raw frame of one call ----------------------------------------------------------------------------------------
 // Where the frame comes from, said once: n rows in host memory; a sageicp_device_frame in the caller's device memory
-// (validated by capi.hip), which the ingest kernel reads into d_in on Prep::stream once that stream has waited for the
+// (validated by caller_mem.hip), which the ingest kernel reads into d_in on Prep::stream once that stream has waited for the
 // caller's; or n records of a sensor_msgs/PointCloud2 payload (sageicp_msg_layout, validated by capi_pipeline.hip) —
 // host bytes are uploaded as they are, device bytes are read in place behind the caller's stream — which k_msg_unpack
 // (msg.hip) turns into rows.  What follows the load does not know which.
