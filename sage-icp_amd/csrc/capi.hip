@@ -12,6 +12,8 @@
 // SAGEICP_ERR_NO_DEVICE.
 #include "capi_internal.h"
 
+#include <mutex>
+
 namespace sageicp {
 thread_local std::string g_err;
 std::atomic<int> g_profiling{0};
@@ -40,23 +42,23 @@ std::atomic<int> g_reference_order{1};
 
 namespace sageicp_impl {
 // RegisterFrame of n points already on `device` (an uploaded frame, or the pipeline's source cloud)
-int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
-                             double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
-                             sageicp_stats *stats) {
-    if (!m || !init || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    if (device != m->device) return fail(SAGEICP_ERR_INVALID, "frame and map live on different devices");
-    if (comm && comm->device != m->device) return fail(SAGEICP_ERR_INVALID, "comm and map live on different devices");
+int register_resident(sageicp_map &m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
+                      double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
+                      sageicp_stats *stats) {
+    if (!init || !pose_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    if (device != m.device) return fail(SAGEICP_ERR_INVALID, "frame and map live on different devices");
+    if (comm && comm->device != m.device) return fail(SAGEICP_ERR_INVALID, "comm and map live on different devices");
     const double t0 = now_us();
-    if (map_is_empty(m)) {
+    if (m.empty()) {
         std::memcpy(pose_out, init, 56);
         if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->n_queries = n; }
         return SAGEICP_OK;
     }
-    if (!m->replicas.empty()) {
+    if (!m.replicas.empty()) {
         if (comm) return fail(SAGEICP_ERR_INVALID, "a map that spans several devices shards the frame itself");
         return register_sharded(m, nullptr, d_frame, n, init, max_dist, kernel, sem_th, pose_out, stats, t0);
     }
-    int rc = sync_mirror(m);
+    int rc = refresh_mirror(m);
     if (rc) return rc;
     const double us_upload = now_us() - t0;
     return run_icp(m, d_frame, n, init, max_dist, kernel, sem_th, comm, pose_out, stats, us_upload, t0);
@@ -157,7 +159,7 @@ sageicp_map *sageicp_map_create(double voxel_size, double max_distance, int basi
 
 int sageicp_map_set_reference_order(sageicp_map *m, int on) {
     if (!m) return fail(SAGEICP_ERR_INVALID, "null map");
-    if (!map_is_empty(m) || m->on_device)
+    if (!m->empty() || m->resident())
         return fail(SAGEICP_ERR_INVALID, "sageicp_map_set_reference_order: the map must be empty (the bucket order "
                                          "records every insertion since construction)");
     m->host.track_order = on != 0;
@@ -180,7 +182,7 @@ int sageicp_map_set_devices(sageicp_map *m, const int *devices, int n) {
     for (int k = 0; k < n; ++k)
         if (count > 0 && (devices[k] < 0 || devices[k] >= count))
             return fail(SAGEICP_ERR_INVALID, "sageicp_map_set_devices: device ordinal out of range");
-    if (int rc = ensure_host(m)) return rc;
+    if (int rc = ensure_host(*m)) return rc;
     for (sageicp_map *r : m->replicas) sageicp_map_destroy(r);
     m->replicas.clear();
     for (sageicp_comm *c : m->ranks) sageicp_comm_destroy(c);
@@ -189,8 +191,7 @@ int sageicp_map_set_devices(sageicp_map *m, const int *devices, int n) {
     for (int k = 1; k < n; ++k) {
         sageicp_map *r = new sageicp_map;
         r->device = devices[k];
-        r->host = m->host;                 // the same map, mirrored on its own device at first use
-        r->mirror_stale_all = true;
+        r->host = m->host;                 // the same map, mirrored on its own device at first use (a new handle: nothing valid in HBM)
         m->replicas.push_back(r);
     }
     return SAGEICP_OK;
@@ -208,8 +209,8 @@ void sageicp_map_destroy(sageicp_map *m) {
 
 // copy of a map whose authority is the HBM copy: device-to-device, the (stale) host side is not
 // touched on either map
-static int clone_on_device(const sageicp_map *src, sageicp_map *m) {
-    const HostMap &h = src->host;
+static int clone_on_device(const sageicp_map &src, sageicp_map *m) {
+    const HostMap &h = src.host;
     m->host.configure(h.voxel_size, h.max_distance, h.basic, h.critical, h.basic_labels.data(),
                       static_cast<int>(h.basic_labels.size()));
     m->host.n_classes = h.n_classes;                    // (the source's size classes, whatever the environment says now)
@@ -220,63 +221,30 @@ static int clone_on_device(const sageicp_map *src, sageicp_map *m) {
     int rc = m->sc.init(m->device);
     if (rc) return rc;
     HIPCHK(hipSetDevice(m->device));
-    hipStream_t s = m->sc.stream.get();
-    HIPCHK(hipStreamSynchronize(src->sc.stream.get()));
-    HIPCHK(m->d_table.reserve(src->d_table.capacity()));
-    HIPCHK(hipMemcpyAsync(m->d_table.data(), src->d_table.data(), src->d_table.capacity() * sizeof(Slot),
-                          hipMemcpyDeviceToDevice, s));
-    m->ctr = src->ctr;
-    if ((rc = grow_device_blocks(m, src->blocks_cap(), 0))) return rc;
-    if ((rc = reserve_device_points(m, src->units_cap(), 0))) return rc;
-    m->on_device = false;       // (reserve_unit_stacks: nothing of this map's to keep yet)
-    if ((rc = reserve_unit_stacks(m, 0))) return rc;
-    HIPCHK(hipMemcpyAsync(m->d_pts.data(), src->d_pts.data(), static_cast<size_t>(m->ctr.units_hi) * kUnitPoints * sizeof(Point4),
-                          hipMemcpyDeviceToDevice, s));
-    for (int k = 0; k < h.n_classes; ++k)
-        if (m->ctr.free_units_count[k] > 0)
-            HIPCHK(hipMemcpyAsync(m->d_free_units[k].data(), src->d_free_units[k].data(),
-                                  static_cast<size_t>(m->ctr.free_units_count[k]) * sizeof(uint32_t),
-                                  hipMemcpyDeviceToDevice, s));
-    if (m->ctr.units_hi)
-        HIPCHK(hipMemcpyAsync(m->d_block_of.data(), src->d_block_of.data(), static_cast<size_t>(m->ctr.units_hi) * sizeof(uint32_t),
-                              hipMemcpyDeviceToDevice, s));
-    if (m->ctr.blocks_hi) {
-        HIPCHK(hipMemcpyAsync(m->d_regions.data(), src->d_regions.data(), m->ctr.blocks_hi * sizeof(uint32_t),
-                              hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(m->d_zeros.data(), src->d_zeros.data(), m->ctr.blocks_hi, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(m->d_slot_of.data(), src->d_slot_of.data(), m->ctr.blocks_hi * sizeof(uint32_t),
-                              hipMemcpyDeviceToDevice, s));
-    }
-    if (m->ctr.free_count)
-        HIPCHK(hipMemcpyAsync(m->d_free.data(), src->d_free.data(), m->ctr.free_count * sizeof(uint32_t),
-                              hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    m->on_device = true;
-    m->mirror_stale_all = false;
-    return SAGEICP_OK;
+    HIPCHK(hipStreamSynchronize(src.sc.stream.get()));
+    return m->dev.copy_from(src.dev, m->host, m->sc.stream.get());
 }
 
-static sageicp_map *clone_one(const sageicp_map *src) {
-    sageicp_map *m = new sageicp_map;
-    m->device = src->device;
-    if (src->on_device) {
+static sageicp_map *clone_one(const sageicp_map &src) {
+    sageicp_map *m = new sageicp_map;       // (nothing valid in HBM: a copy of a host map builds its own mirror on first use)
+    m->device = src.device;
+    if (src.resident()) {
         if (clone_on_device(src, m)) {
             sageicp_map_destroy(m);
             return nullptr;
         }
         return m;
     }
-    m->host = src->host;
-    m->mirror_stale_all = true;   // the clone builds its own mirror on first use
+    m->host = src.host;
     return m;
 }
 
 sageicp_map *sageicp_map_clone(const sageicp_map *src) {
     if (!src) return nullptr;
-    sageicp_map *m = clone_one(src);
+    sageicp_map *m = clone_one(*src);
     if (!m) return nullptr;
     for (const sageicp_map *r : src->replicas) {
-        sageicp_map *c = clone_one(r);
+        sageicp_map *c = clone_one(*r);
         if (!c) {
             sageicp_map_destroy(m);
             return nullptr;
@@ -288,23 +256,15 @@ sageicp_map *sageicp_map_clone(const sageicp_map *src) {
 
 int sageicp_map_clear(sageicp_map *m) {
     if (!m) return fail(SAGEICP_ERR_INVALID, "null map");
-    m->on_device = false;     // whatever the device holds is dropped with the rest
-    m->aux_valid = false;
+    m->dev.invalidate();      // whatever the device holds is dropped with the rest
     m->host.clear();
-    m->mirror_stale_all = true;
     for (sageicp_map *r : m->replicas) sageicp_map_clear(r);
     m->replicas_diverged = false;         // every copy is empty again
     return SAGEICP_OK;
 }
-int sageicp_map_empty(const sageicp_map *m) { return (!m || map_is_empty(m)) ? 1 : 0; }
-uint64_t sageicp_map_size(const sageicp_map *m) {
-    if (!m) return 0;
-    return m->on_device ? m->ctr.total_points : m->host.total_points;
-}
-uint64_t sageicp_map_num_voxels(const sageicp_map *m) {
-    if (!m) return 0;
-    return m->on_device ? m->ctr.num_voxels : m->host.num_voxels;
-}
+int sageicp_map_empty(const sageicp_map *m) { return (!m || m->empty()) ? 1 : 0; }
+uint64_t sageicp_map_size(const sageicp_map *m) { return m ? m->counts().points : 0; }
+uint64_t sageicp_map_num_voxels(const sageicp_map *m) { return m ? m->counts().voxels : 0; }
 
 int sageicp_map_add_points(sageicp_map *m, const double *xyzl, uint64_t n) {
     if (!m || (n && !xyzl)) return fail(SAGEICP_ERR_INVALID, "null argument");
@@ -312,7 +272,7 @@ int sageicp_map_add_points(sageicp_map *m, const double *xyzl, uint64_t n) {
         return fail(SAGEICP_ERR_INVALID, "the copies of this multi-device map diverged in an earlier failed update: Clear() it");
     if (!all_finite(xyzl, n))
         return fail(SAGEICP_ERR_INVALID, "AddPoints: a coordinate or label is not finite (NaN / Inf); nothing was inserted");
-    if (int rc = ensure_host(m)) return rc;
+    if (int rc = ensure_host(*m)) return rc;
     // A voxel index out of range is found by a dry pass: nothing is inserted then (like non-finite input
     // above).  Only the storage limits (2^24 voxels / 2^24 units of 4 points: 67 M point slots, DESIGN.md
     // section 1) can still stop a call part-way — before the point that does not fit, the points before it
@@ -352,7 +312,7 @@ int sageicp_map_add_points(sageicp_map *m, const double *xyzl, uint64_t n) {
 
 int sageicp_map_remove_far(sageicp_map *m, const double origin[3]) {
     if (!m || !origin) return fail(SAGEICP_ERR_INVALID, "null argument");
-    if (int rc = ensure_host(m)) return rc;
+    if (int rc = ensure_host(*m)) return rc;
     m->host.remove_far(origin);
     for (sageicp_map *r : m->replicas)
         if (int rc = sageicp_map_remove_far(r, origin)) return rc;
@@ -380,14 +340,14 @@ int sageicp_map_update_pose(sageicp_map *m, const double *xyzl, uint64_t n, cons
 
 int sageicp_map_update_pose_device(sageicp_map *m, const double *xyzl, uint64_t n, const double pose[7]) {
     if (!m || (n && !xyzl) || !pose) return fail(SAGEICP_ERR_INVALID, "null argument");
-    return device_update_all(m, xyzl, n, pose, nullptr);
+    return device_update_all(*m, xyzl, n, pose, nullptr);
 }
 
-int sageicp_map_resident(const sageicp_map *m) { return (m && m->on_device) ? 1 : 0; }
+int sageicp_map_resident(const sageicp_map *m) { return (m && m->resident()) ? 1 : 0; }
 
 uint64_t sageicp_map_point_slots(const sageicp_map *m) {
     if (!m) return 0;
-    return static_cast<uint64_t>(m->on_device ? m->ctr.units_hi : m->host.units_hi) * kUnitPoints;
+    return static_cast<uint64_t>(m->counts().units_hi) * kUnitPoints;
 }
 
 // ---- for tests: the slot hash, and the state of the authoritative slot table (host-side words only) ----
@@ -395,41 +355,37 @@ uint32_t sageicp_voxel_hash(int32_t x, int32_t y, int32_t z) { return sageicp::v
 
 int sageicp_map_table_stats(const sageicp_map *m, uint64_t out[3]) {
     if (!m || !out) return fail(SAGEICP_ERR_INVALID, "null argument");
-    if (m->on_device) {          // (the counters of the last device pass, kept on the host with the handle)
-        out[0] = m->d_table.capacity();
-        out[1] = m->ctr.used_slots;
-        out[2] = m->ctr.num_voxels;
-    } else {                     // (the host table deletes by backward shift: no tombstones)
-        out[0] = m->host.table.size();
-        out[1] = m->host.num_voxels;
-        out[2] = m->host.num_voxels;
-    }
+    const MapCounts c = m->counts();    // (resident: the counters of the last device pass, kept on the host with the handle)
+    out[0] = c.table_capacity;
+    out[1] = c.used_slots;
+    out[2] = c.voxels;
     return SAGEICP_OK;
 }
 
 int sageicp_map_sync(const sageicp_map *m) {
     if (!m) return fail(SAGEICP_ERR_INVALID, "null map");
-    if (int rc = sync_mirror(m)) return rc;
-    for (const sageicp_map *r : m->replicas)
-        if (int rc = sync_mirror(r)) return rc;
+    if (int rc = refresh_mirror(internal(m))) return rc;
+    for (sageicp_map *r : m->replicas)
+        if (int rc = refresh_mirror(*r)) return rc;
     return SAGEICP_OK;
 }
 
 // ---- search ---------------------------------------------------------------------------------
-int sageicp_get_correspondences(const sageicp_map *m, const double *q, uint64_t n, double max_dist,
+int sageicp_get_correspondences(const sageicp_map *map, const double *q, uint64_t n, double max_dist,
                                 double sem_th, double *src_out, double *tgt_out, uint64_t *n_out,
                                 int64_t *query_idx_out) {
-    if (!m || !n_out || (n && (!q || !src_out || !tgt_out)))
+    if (!map || !n_out || (n && (!q || !src_out || !tgt_out)))
         return fail(SAGEICP_ERR_INVALID, "null argument");
     if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "too many queries (2^26 - 4 max)");
     *n_out = 0;
     if (!all_finite(q, n))
         return fail(SAGEICP_ERR_INVALID, "GetCorrespondences: a coordinate or label of a query is not finite (NaN / Inf)");
+    sageicp_map &m = internal(map);
     int rc = ensure_host(m);      // the returned target points are read from the host copy
     if (rc) return rc;
-    if ((rc = sync_mirror(m))) return rc;
-    if (n == 0 || map_is_empty(m)) return SAGEICP_OK;
-    Scratch &sc = m->sc;
+    if ((rc = refresh_mirror(m))) return rc;
+    if (n == 0 || m.empty()) return SAGEICP_OK;
+    Scratch &sc = m.sc;
     if ((rc = sc.reserve_frame(n))) return rc;
     if ((rc = sc.reserve_nn(n))) return rc;
     if ((rc = sc.reserve_sort(n))) return rc;
@@ -442,10 +398,10 @@ int sageicp_get_correspondences(const sageicp_map *m, const double *q, uint64_t 
     // same pipeline as the ICP loop, pose = identity: sort, rows, search; results are mapped
     // back to the caller's query order through the sort permutation
     HIPCHK(sort_frame(sc.d_frame.data(), sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), false, false,
-                      m->host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(), sc.d_sort_temp.capacity(),
+                      m.host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(), sc.d_sort_temp.capacity(),
                       s));
     const int lw = icp_lw(n, sparse_voxels(m));
-    if ((rc = ensure_cand(m, wants_filter(m, n, sem_th)))) return rc;
+    if ((rc = m.dev.ensure_cand(wants_filter(m, n, sem_th), s))) return rc;
     const IcpParams ip = icp_params(m, sc.d_sorted.data(), n, sem_th, lw, 0);  // identity pose, no loop state
     launch_rows(ip, s);
     launch_icp(ip, lw, false, s);
@@ -462,7 +418,7 @@ int sageicp_get_correspondences(const sageicp_map *m, const double *q, uint64_t 
     for (uint64_t i = 0; i < n; ++i) {     // pairs in query order (VoxelHashMap.cpp:119-127)
         if (by_query[i] < 0) continue;
         // acceptance on the unscaled distance: (nn - point).norm() < max (VoxelHashMap.cpp:111)
-        const Point4 &t = m->host.pts[by_query[i]];
+        const Point4 &t = m.host.pts[by_query[i]];
         const double dx = t.x - q[4 * i], dy = t.y - q[4 * i + 1], dz = t.z - q[4 * i + 2];
         if (!(std::sqrt(SAGE_SQNORM3_ACCEPT(dx * dx, dy * dy, dz * dz)) < max_dist)) continue;
         std::memcpy(src_out + 4 * k, q + 4 * i, 32);
@@ -540,21 +496,22 @@ int sageicp_transform_points(const double pose[7], double *xyzl, uint64_t n, int
 }
 
 // ---- RegisterFrame ----------------------------------------------------------------------------
-int sageicp_register_frame(const sageicp_map *m, const double *frame, uint64_t n,
+int sageicp_register_frame(const sageicp_map *map, const double *frame, uint64_t n,
                            const double init[7], double max_dist, double kernel, double sem_th,
                            double pose_out[7], sageicp_stats *stats) {
-    if (!m || !init || !pose_out || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
+    if (!map || !init || !pose_out || (n && !frame)) return fail(SAGEICP_ERR_INVALID, "null argument");
+    sageicp_map &m = internal(map);
     const double t0 = now_us();
-    if (map_is_empty(m)) {   // Registration.cpp:119
+    if (m.empty()) {   // Registration.cpp:119
         std::memcpy(pose_out, init, 56);
         if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->n_queries = n; }
         return SAGEICP_OK;
     }
-    if (!m->replicas.empty())
+    if (!m.replicas.empty())
         return register_sharded(m, frame, nullptr, n, init, max_dist, kernel, sem_th, pose_out, stats, t0);
-    int rc = sync_mirror(m);
+    int rc = refresh_mirror(m);
     if (rc) return rc;
-    Scratch &sc = m->sc;
+    Scratch &sc = m.sc;
     if ((rc = sc.reserve_frame(n))) return rc;
     if (n) HIPCHK(hipMemcpyAsync(sc.d_frame.data(), frame, n * sizeof(Point4), hipMemcpyHostToDevice,
                                  sc.stream.get()));
@@ -577,11 +534,11 @@ int sageicp_map_loop_status(const sageicp_map *m, sageicp_loop_status *out) {
 }
 
 // a frame of n rows on the map's device, its memory allocated (the first step of both frame entries; nullptr: failed)
-static std::unique_ptr<sageicp_frame> new_frame(const sageicp_map *m, uint64_t n) {
-    if (m->sc.init(m->device)) return nullptr;
-    if (hipSetDevice(m->device) != hipSuccess) { fail(SAGEICP_ERR_HIP, "hipSetDevice"); return nullptr; }
+static std::unique_ptr<sageicp_frame> new_frame(sageicp_map &m, uint64_t n) {
+    if (m.sc.init(m.device)) return nullptr;
+    if (hipSetDevice(m.device) != hipSuccess) { fail(SAGEICP_ERR_HIP, "hipSetDevice"); return nullptr; }
     auto f = std::make_unique<sageicp_frame>();
-    f->device = m->device;
+    f->device = m.device;
     f->n = n;
     if (f->d.reserve(std::max<uint64_t>(n, 1)) != hipSuccess) { fail(SAGEICP_ERR_HIP, "hipMalloc(frame)"); return nullptr; }
     return f;
@@ -589,7 +546,7 @@ static std::unique_ptr<sageicp_frame> new_frame(const sageicp_map *m, uint64_t n
 
 sageicp_frame *sageicp_frame_upload(const sageicp_map *m, const double *frame, uint64_t n) {
     if (!m || (n && !frame)) { fail(SAGEICP_ERR_INVALID, "null argument"); return nullptr; }
-    std::unique_ptr<sageicp_frame> f = new_frame(m, n);
+    std::unique_ptr<sageicp_frame> f = new_frame(internal(m), n);
     if (!f) return nullptr;
     if (n && hipMemcpy(f->d.data(), frame, n * sizeof(Point4), hipMemcpyHostToDevice) != hipSuccess) {
         fail(SAGEICP_ERR_HIP, "hipMemcpy(frame)");
@@ -607,7 +564,7 @@ void sageicp_frame_destroy(sageicp_frame *f) {
 sageicp_frame *sageicp_frame_from_device(const sageicp_map *m, const sageicp_device_frame *fr, void *stream) {
     if (!m) { fail(SAGEICP_ERR_INVALID, "null argument"); return nullptr; }
     if (check_device_frame(fr, nullptr, stream, m->device)) return nullptr;
-    std::unique_ptr<sageicp_frame> f = new_frame(m, fr->n);
+    std::unique_ptr<sageicp_frame> f = new_frame(internal(m), fr->n);
     if (!f) return nullptr;
     // on the caller's stream, behind the work that wrote the buffers; synchronous: afterwards nothing reads them
     const hipStream_t s = static_cast<hipStream_t>(stream);
@@ -625,8 +582,8 @@ int sageicp_register_frame_resident(const sageicp_map *m, const sageicp_frame *f
                                     const double init[7], double max_dist, double kernel,
                                     double sem_th, sageicp_comm *comm, double pose_out[7],
                                     sageicp_stats *stats) {
-    if (!f) return fail(SAGEICP_ERR_INVALID, "null argument");
-    return register_resident(m, f->d.data(), f->n, f->device, init, max_dist, kernel, sem_th, comm, pose_out, stats);
+    if (!f || !m) return fail(SAGEICP_ERR_INVALID, "null argument");
+    return register_resident(internal(m), f->d.data(), f->n, f->device, init, max_dist, kernel, sem_th, comm, pose_out, stats);
 }
 
 // ---- RCCL communicator ------------------------------------------------------------------------

@@ -1,20 +1,18 @@
 // Internals shared by the translation units of libsageicp_hip.so's host side (capi.hip, capi_pipeline.hip,
-// capi_outputs.hip, caller_mem.hip, capi_mirror.hip, capi_run.hip, prep.hip): error channel, tuning knobs, the
+// capi_outputs.hip, caller_mem.hip, map_device.hip, capi_run.hip, prep.hip): error channel, tuning knobs, the
 // per-handle device scratch, the pipeline's frame source and buffers (prep.h) and its prefetch state (prefetch.h), the
-// checks of a caller's device memory (caller_mem.h), the way out (outputs.h), the opaque handles of include/sageicp.h
-// except the pipeline's (capi_pipeline.hip).  Not part of the C ABI.
+// checks of a caller's device memory (caller_mem.h), the HBM copy of a map (map_device.h), the way out (outputs.h), the
+// opaque handles of include/sageicp.h except the pipeline's (capi_pipeline.hip) and the one place where the ABI's
+// `const sageicp_map *` becomes the reference the internals take (internal()).  Not part of the C ABI.
 #pragma once
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
-#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
-#include <functional>
 #include <cstdio>
 #include <cstdlib>
 #include <cfloat>
@@ -22,10 +20,8 @@
 #include <memory>
 #include <cstring>
 #include <map>
-#include <mutex>
 #include <array>
 #include <string>
-#include <thread>
 #include <utility>
 #include <vector>
 
@@ -311,97 +307,6 @@ struct Scratch {
 };
 
 
-// A few parked host threads for the order replays of one Prep (one per label group at most): a
-// replay of a few thousand keys costs no more than starting a thread does, and the replays of a
-// level are the critical path of a streamed frame.  run(count, f) executes f(0..count-1), each index
-// once, on the workers and the calling thread; indices are handed out in order (largest job first
-// if the caller sorted them so).
-class ReplayPool {
-public:
-    ~ReplayPool() {
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto &t : th_) t.join();
-    }
-    void run(size_t count, const std::function<void(size_t)> &f, size_t want_threads) {
-        if (count <= 1 || want_threads <= 1) {
-            for (size_t i = 0; i < count; ++i) f(i);
-            return;
-        }
-        while (th_.size() + 1 < std::min(want_threads, count)) th_.emplace_back([this] { worker(); });
-        {
-            std::lock_guard<std::mutex> lk(mu_);
-            job_ = &f;
-            total_ = count;
-            next_ = 0;
-            pending_ = count;
-            ++epoch_;
-        }
-        cv_.notify_all();
-        drain();
-        std::unique_lock<std::mutex> lk(mu_);
-        done_.wait(lk, [this] { return pending_ == 0; });
-        job_ = nullptr;
-        total_ = next_ = 0;
-    }
-
-private:
-    void drain() {
-        for (;;) {
-            size_t i;
-            const std::function<void(size_t)> *job;
-            {   // (a handful of jobs per level: the lock is not contended, and a worker still between
-                // two jobs when the next run() starts sees that run's state consistently)
-                std::lock_guard<std::mutex> lk(mu_);
-                if (next_ >= total_) return;
-                i = next_++;
-                job = job_;
-            }
-            (*job)(i);
-            std::lock_guard<std::mutex> lk(mu_);
-            if (--pending_ == 0) done_.notify_all();
-        }
-    }
-    void worker() {
-        uint64_t seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> lk(mu_);
-                cv_.wait(lk, [&] { return stop_ || (epoch_ != seen && job_); });
-                if (stop_) return;
-                seen = epoch_;
-            }
-            drain();
-        }
-    }
-    std::vector<std::thread> th_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_;
-    const std::function<void(size_t)> *job_ = nullptr;
-    size_t total_ = 0, pending_ = 0, next_ = 0;
-    uint64_t epoch_ = 0;
-    bool stop_ = false;
-};
-
-// ---- dynamic vehicle filter (dyn_filter.hip; core/Preprocessing.cpp:95-172) -----------------------
-// PCL's cluster order: EuclideanClusterExtraction finds the clusters in order of their smallest index, then
-// std::sort(clusters.rbegin(), clusters.rend(), comparePointClusters) orders them by size, largest first — not stably.
-// std::sort permutes by comparisons only, so the same call on (size, index) records with the same comparator gives
-// PCL's permutation under the same standard library (libstdc++).  order[j] = index of the j-th cluster emitted.
-inline void cluster_emission_order(const uint32_t *sizes, size_t n, uint32_t *order) {
-    struct Rec {
-        uint32_t size, index;
-    };
-    std::vector<Rec> v(n);
-    for (size_t k = 0; k < n; ++k) v[k] = Rec{sizes[k], static_cast<uint32_t>(k)};
-    std::sort(v.rbegin(), v.rend(), [](const Rec &a, const Rec &b) { return a.size < b.size; });
-    for (size_t k = 0; k < n; ++k) order[k] = v[k].index;
-}
-// cluster_is_static (Preprocessing.cpp:141-158): dyn_rules.h
-
 }  // namespace sageicp
 
 // the frame-preparation driver in front of registration (prep.hip): DynFilter, FrameSource, PrepJob, Prep
@@ -410,98 +315,50 @@ inline void cluster_emission_order(const uint32_t *sizes, size_t n, uint32_t *or
 using namespace sageicp;
 
 #include "caller_mem.h"
+#include "map_device.h"
 #include "outputs.h"
 
 // ---- opaque handles -----------------------------------------------------------------------
 struct sageicp_map {
     HostMap host;
     int device = 0;
-    // device mirror + scratch: logically a cache of `host`, refreshed lazily by const searches
-    mutable Scratch sc;
-    mutable DevBuf<Slot> d_table;
-    mutable DevBuf<Point4> d_pts;                // units of 4 points, + one NaN point after them (reserve_device_points)
-    mutable DevBuf<uint32_t> d_regions;          // per block: (class << 28) | first unit of its region
-    mutable DevBuf<uint32_t> d_free_units[kMaxClasses];   // device-side update: per-class stacks of free regions
-    mutable DevBuf<uint32_t> d_freed;            // regions released by one insertion pass
-    mutable DevBuf<uint32_t> d_block_of;         // device-side update: unit -> block (slot words carry units)
-    mutable bool mirror_stale_all = true;
-    // compact copy of d_pts for k_icp's scan (fp32 x, y, z, label), derived on the device whenever
-    // the HBM copy of the map has changed since the last search: a record per point slot, one more, and
-    // kCandSlack records nothing reads (k_icp loads a record's neighbour at a constant offset that the
-    // buffer load's range check does not cover)
-    static constexpr size_t kCandSlack = 64;
-    mutable DevBuf<uint4> d_cand;
-    mutable DevBuf<uint32_t> d_cand_flags;
-    mutable bool cand_stale = true;
-    // pinned staging + device landing buffers for the scattered refresh of changed records
-    mutable PinnedBuf<char> h_stage;
-    mutable DevBuf<char> d_stage;
-    mutable size_t stage_bytes = 0;              // what both hold (0 after a failed reserve)
-    // Device-side Update() (map_update.hip).  After one the HBM copy is the authority
-    // (`on_device`) and `host` is stale until ensure_host() downloads it; `ctr` is the host's
-    // shadow of the device counters.  The auxiliary arrays are valid for the host generation
-    // they were uploaded at.
-    mutable bool on_device = false;
-    // the update's per-block arrays: as many blocks as d_zeros holds (d_regions holds at least as many)
-    mutable DevBuf<uint8_t> d_zeros;
-    mutable DevBuf<uint32_t> d_slot_of;
-    mutable DevBuf<uint32_t> d_free;
-    mutable DevBuf<MapCounters> d_ctr;
-    mutable PinnedBuf<MapCounters> h_ctr;
-    mutable PinnedBuf<uint32_t> h_ctr_aux;       // 16 words: what else a device update hands back (far voxels found)
-    // reference-order maps: the lists a device update exchanges with the host's bucket array (pinned)
-    mutable PinnedBuf<uint2> h_lists;
-    int reserve_lists(size_t n) const {
-        if (n + 2 > h_lists.capacity()) HIPCHK(h_lists.reserve(n + n / 2 + 4096));
-        return SAGEICP_OK;
-    }
-    mutable bool aux_valid = false;
-    mutable uint64_t aux_generation = 0;
-    mutable MapCounters ctr{};
-    // the update's scratch (reserve_update_scratch); map_update.hip gets the view
-    struct UpdateBuffers {
-        DevBuf<Point4> raw, w;
-        DevBuf<unsigned long long> keys, keys_alt;
-        DevBuf<uint32_t> idx, idx_alt, head_slot;
-        DevBuf<UpdateEvents> flag, rank;
-        DevBuf<int8_t> want;
-        DevBuf<uint2> new_list;
-        size_t n = 0;                            // points the buffers above hold (0 after a failed reserve)
-        DevBuf<uint32_t> far_flag, far_sel;
-        DevBuf<uint2> far_list;
-        size_t nb = 0;                           // blocks the three above hold (0 after a failed reserve)
-        DevBuf<uint32_t> n_sel;
-        DevBuf<unsigned char> temp;
-        UpdateScratch view() const {
-            UpdateScratch v{};
-            v.raw = raw.data(); v.w = w.data();
-            v.keys = keys.data(); v.keys_alt = keys_alt.data();
-            v.idx = idx.data(); v.idx_alt = idx_alt.data(); v.head_slot = head_slot.data();
-            v.flag = flag.data(); v.rank = rank.data(); v.want = want.data();
-            v.far_flag = far_flag.data(); v.far_sel = far_sel.data(); v.n_sel = n_sel.data();
-            v.new_list = new_list.data(); v.far_list = far_list.data();
-            v.temp = temp.data(); v.temp_bytes = temp.capacity();
-            return v;
-        }
-    };
-    mutable UpdateBuffers up;
-    mutable sageicp_impl::OutputBuffers out;     // sageicp_map_pointcloud*: the exports work in these (outputs.h)
-    size_t units_cap() const { return d_pts.capacity() / kUnitPoints; }       // units the point array holds
-    size_t blocks_cap() const { return d_zeros.capacity(); }
-    size_t cand_slots() const { return d_cand.capacity() ? d_cand.capacity() - 1 - kCandSlack : 0; }
+    Scratch sc;                                  // the ICP loop's buffers and streams
+    sageicp_impl::MapDevice dev;                            // the copy in HBM, and which of the two copies counts (map_device.h)
+    sageicp_impl::OutputBuffers out;             // sageicp_map_pointcloud*: the exports work in these (outputs.h)
     // Single-process multi-GPU mode (SAGEICP_DEVICES / sageicp_map_set_devices): one more complete
     // copy of the map per extra device.  Every mutation is applied to all of them, RegisterFrame
     // shards the frame over them (one host thread and one stream per device) and the ranks'
     // Gauss-Newton sums meet in peer-mapped exchange blocks.  `this` is rank 0.
     std::vector<sageicp_map *> replicas;
-    mutable std::vector<struct sageicp_comm *> ranks;   // created at the first sharded registration
+    std::vector<struct sageicp_comm *> ranks;    // created at the first sharded registration
     // a mutation reached some copies of the map but not all (a device ran out of memory, ...): the
     // ranks would sum Gauss-Newton terms computed against different maps, so every later entry
     // refuses the handle until Clear() has emptied all copies
     bool replicas_diverged = false;
+
+    bool resident() const { return dev.authority(); }
+    bool empty() const { return counts().voxels == 0; }
+    // what the map holds, read from the copy that counts: the one place that chooses between the two
+    sageicp_impl::MapCounts counts() const {
+        const bool on_device = dev.authority();
+        const MapCounters &c = dev.ctr;
+        sageicp_impl::MapCounts n;
+        n.points = on_device ? c.total_points : host.total_points;
+        n.voxels = on_device ? c.num_voxels : host.num_voxels;
+        n.units_hi = on_device ? c.units_hi : host.units_hi;
+        n.table_capacity = on_device ? dev.d_table.capacity() : host.table.size();
+        n.used_slots = on_device ? c.used_slots : host.num_voxels;
+        return n;
+    }
     // the buffers above are used on sc's streams and go before sc does: the streams are waited for first
     ~sageicp_map() { sc.wait(); }
 };
+
+// The ABI's `const sageicp_map *` says that the map as a set of points is unchanged by the call.  Its representation
+// changes under it — the HBM mirror is refreshed lazily by a search, the host copy is downloaded on demand, the scratch
+// is used — so the extern "C" entries, and only they, turn their pointer into the reference the internals take here.
+// (Handles are created with `new sageicp_map`, never as const objects: the cast is defined.)
+inline sageicp_map &internal(const sageicp_map *m) { return *const_cast<sageicp_map *>(m); }
 
 struct sageicp_frame {
     int device = 0;
@@ -529,7 +386,7 @@ struct sageicp_comm {
 // ---- the library's translation units call each other through these --------------------------------------
 // capi.hip: the C ABI of maps, frames, communicators and the stand-alone entries.  capi_pipeline.hip: the pipeline
 // handle and its entries.  capi_outputs.hip: rows, records and grids out (outputs.h).  caller_mem.hip: the checks of a
-// caller's device memory (caller_mem.h).  capi_mirror.hip: the HBM mirror of a map and Update() on the device.
+// caller's device memory (caller_mem.h).  map_device.hip: the HBM copy of a map (MapDevice): mirror refresh, download, copy, Update() on the device.
 // capi_run.hip: the ICP loop (plan_loop, run_icp and its attempts), the RCCL binding and the single-process multi-GPU
 // mode.
 namespace sageicp_impl {
@@ -547,31 +404,24 @@ struct Rccl {
 extern Rccl g_rccl;
 int load_rccl();
 // capi.hip
-int register_resident(const sageicp_map *m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
+int register_resident(sageicp_map &m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
                       double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
                       sageicp_stats *stats);
-// capi_mirror.hip
-int reserve_device_points(const sageicp_map *m, size_t units, size_t keep);
-int sync_mirror(const sageicp_map *m);
-int ensure_cand(const sageicp_map *m, bool derive = true);
-bool map_is_empty(const sageicp_map *m);
-int ensure_host(const sageicp_map *m);
-int reserve_update_scratch(const sageicp_map *m, size_t n, size_t nb);
-int grow_device_blocks(const sageicp_map *m, size_t blocks, size_t keep);
-int reserve_unit_stacks(const sageicp_map *m, size_t n);
-DevMap dev_map(const sageicp_map *m);
-int device_update(sageicp_map *m, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points = nullptr);
+// map_device.hip: the handle's device made current, its stream and host copy handed to MapDevice
+int refresh_mirror(sageicp_map &m);
+int ensure_host(sageicp_map &m);
+int device_update(sageicp_map &m, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points = nullptr);
 bool all_finite(const double *xyzl, uint64_t n);
 // capi_run.hip
 void identity_pose(double T[7]);
 void fill_state(IcpState *st, const double init[7]);
-bool sparse_voxels(const sageicp_map *m);
-bool wants_filter(const sageicp_map *m, uint64_t n, double sem_th);
-IcpParams icp_params(const sageicp_map *m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift);
-int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const double init[7], double max_dist, double kernel,
+bool sparse_voxels(const sageicp_map &m);
+bool wants_filter(const sageicp_map &m, uint64_t n, double sem_th);
+IcpParams icp_params(const sageicp_map &m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift);
+int run_icp(sageicp_map &m, const Point4 *d_frame, uint64_t n, const double init[7], double max_dist, double kernel,
             double sem_th, sageicp_comm *comm, double out[7], sageicp_stats *stats, double us_upload, double t_begin);
-int device_update_all(sageicp_map *m, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points);
-int register_sharded(const sageicp_map *m, const double *h_frame, const Point4 *d_frame, uint64_t n, const double init[7],
+int device_update_all(sageicp_map &m, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points);
+int register_sharded(sageicp_map &m, const double *h_frame, const Point4 *d_frame, uint64_t n, const double init[7],
                      double max_dist, double kernel, double sem_th, double pose_out[7], sageicp_stats *stats, double t0);
 }  // namespace sageicp_impl
 using namespace sageicp_impl;

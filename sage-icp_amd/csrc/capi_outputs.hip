@@ -5,6 +5,9 @@
 // it.  The map's export entries and the stand-alone occupancy entries are here; the pipeline's are with its handle
 // (capi_pipeline.hip).  The kernels are egress.hip's, msg.hip's, map_update.hip's and keyframe.hip's.  Host code only.
 #include "capi_internal.h"
+#include "replay_pool.h"
+
+#include <mutex>
 
 #include <sys/mman.h>
 
@@ -94,25 +97,24 @@ static void pretouch(void *p, size_t bytes) {
 // The live points of a resident map gathered on stream s in sageicp_map_pointcloud's order into `out`: packed, or
 // straight into a caller's layout (egress.h; the rows at and beyond its cap are not written).  Synchronous only in
 // reference-order mode.
-static int gather_resident(const sageicp_map *m, const RowsOut &out, hipStream_t s) {
-    int rc = reserve_update_scratch(m, 0, static_cast<size_t>(m->ctr.blocks_hi) + 1);
+static int gather_resident(sageicp_map &m, const RowsOut &out, hipStream_t s) {
+    const uint32_t blocks_hi = m.dev.ctr.blocks_hi;
+    MapDevice::GatherScratch g;
+    int rc = m.dev.gather_scratch(static_cast<size_t>(blocks_hi) + 1, &g);
     if (rc) return rc;
-    const DevMap dm = dev_map(m);
-    if (!m->host.track_order) {
-        HIPCHK(map_pointcloud_device(dm, m->ctr.blocks_hi, m->up.far_flag.data(), m->up.far_sel.data(), m->up.temp.data(),
-                                     m->up.temp.capacity(), out, s));
+    const DevMap dm = m.dev.view(m.host);
+    if (!m.host.track_order) {
+        HIPCHK(map_pointcloud_device(dm, blocks_hi, g.flag, g.sel, g.temp, g.temp_bytes, out, s));
         return SAGEICP_OK;
     }
     // reference-order mode: the voxels in the bucket order of the host's array (VoxelHashMap.cpp:132-142), their points
     // gathered on the device in that order
     std::vector<uint32_t> list;
-    list.reserve(m->host.order.size());
-    m->host.order.for_each([&](uint32_t b) { list.push_back(b); });
-    if ((rc = reserve_update_scratch(m, 0, list.size() + 1))) return rc;
-    uint32_t *d_list = reinterpret_cast<uint32_t *>(m->up.far_list.data());        // ([nb] uint2: room for the list)
-    if (!list.empty()) HIPCHK(hipMemcpyAsync(d_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIPCHK(map_pointcloud_listed(dm, d_list, static_cast<uint32_t>(list.size()), m->up.far_flag.data(), m->up.far_sel.data(),
-                                 m->up.temp.data(), m->up.temp.capacity(), out, s));
+    list.reserve(m.host.order.size());
+    m.host.order.for_each([&](uint32_t b) { list.push_back(b); });
+    if ((rc = m.dev.gather_scratch(list.size() + 1, &g))) return rc;
+    if (!list.empty()) HIPCHK(hipMemcpyAsync(g.list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(map_pointcloud_listed(dm, g.list, static_cast<uint32_t>(list.size()), g.flag, g.sel, g.temp, g.temp_bytes, out, s));
     HIPCHK(hipStreamSynchronize(s));                                             // (`list` is pageable and leaves scope)
     return SAGEICP_OK;
 }
@@ -122,11 +124,11 @@ static int gather_resident(const sageicp_map *m, const RowsOut &out, hipStream_t
 static int packed_rows(const RowSource &src, uint64_t n, DevBuf<Point4> &d_pc, std::vector<double> &staged, hipStream_t s,
                        const Point4 **rows) {
     *rows = src.d_rows;
-    const sageicp_map *m = src.map;
+    sageicp_map *m = src.map;
     if (!m) return SAGEICP_OK;
     if (n > d_pc.capacity()) HIPCHK(d_pc.reserve(n + n / 4 + 1024));
     *rows = d_pc.data();
-    if (m->on_device) return gather_resident(m, RowsOut{d_pc.data(), {}}, s);
+    if (m->resident()) return gather_resident(*m, RowsOut{d_pc.data(), {}}, s);
     staged.resize(4 * n);
     m->host.pointcloud(staged.data(), n);
     HIPCHK(hipMemcpyAsync(d_pc.data(), staged.data(), n * sizeof(Point4), hipMemcpyHostToDevice, s));
@@ -148,8 +150,8 @@ static EgressArgs egress_args(const sageicp_device_points &d, int *flags) {
 
 // ---- the driver -------------------------------------------------------------------------------------------------------
 int export_rows(OutputBuffers &ob, int device, const RowSource &src, const RowSink &sink, uint64_t *n_out) {
-    const sageicp_map *m = src.map;
-    const uint64_t n = m ? sageicp_map_size(m) : src.n;
+    sageicp_map *m = src.map;
+    const uint64_t n = m ? m->counts().points : src.n;
     *n_out = n;
     const uint64_t want = std::min(sink.cap, n);
     if (!want) return SAGEICP_OK;
@@ -158,7 +160,7 @@ int export_rows(OutputBuffers &ob, int device, const RowSource &src, const RowSi
     // staged copy moves 63 MB in 1.2 ms into pages that exist — and in 3.4 ms into pages that do not: two thirds of
     // the call were first-touch faults taken one by one inside the copy (profiles/pointcloud_probe.py).  So a map's
     // pages are made to exist first, by a few parked host threads side by side (while the device gathers the rows).
-    if (m && !m->on_device && sink.kind == RowSink::kHostRows) {        // host to host: no device
+    if (m && !m->resident() && sink.kind == RowSink::kHostRows) {        // host to host: no device
         pretouch(sink.out, want * sizeof(Point4));
         m->host.pointcloud(static_cast<double *>(sink.out), sink.cap);
         return SAGEICP_OK;
@@ -189,8 +191,8 @@ int export_rows(OutputBuffers &ob, int device, const RowSource &src, const RowSi
     if (sink.kind == RowSink::kDeviceRows)
         return flagged(ob.d_flag, s, kRowFlags, [&](int *word) -> int {
             const EgressArgs e = egress_args(*sink.dst, word);
-            if (m && m->on_device && !env_int("SAGEICP_EGRESS_TWO_PASS", 0))
-                return gather_resident(m, RowsOut{nullptr, e}, s);      // the gather writes the caller's layout itself
+            if (m && m->resident() && !env_int("SAGEICP_EGRESS_TWO_PASS", 0))
+                return gather_resident(*m, RowsOut{nullptr, e}, s);      // the gather writes the caller's layout itself
             // two passes: the rows packed, then k_egress
             if (int r = packed_rows(src, n, ob.d_pc, staged, s, &rows)) return r;
             launch_egress(e, rows, want, s);
@@ -301,18 +303,22 @@ static int occupancy_on_device(const Point4 *d_pts, uint64_t n, const double *po
 }  // namespace sageicp_impl
 
 // =============================================================================================
+static int export_map(sageicp_map &m, const RowSink &sink, uint64_t *n_out) {
+    return export_rows(m.out, m.device, RowSource::of_map(m), sink, n_out);
+}
+
 extern "C" {
 
 // ---- a map's live points out ---------------------------------------------------------------------------------------
 uint64_t sageicp_map_pointcloud(const sageicp_map *m, double *out, uint64_t cap) {
     uint64_t n = 0;
-    if (!m || export_rows(m->out, m->device, RowSource::of_map(m), RowSink::host_rows(out, cap), &n)) return 0;
+    if (!m || export_map(internal(m), RowSink::host_rows(out, cap), &n)) return 0;
     return n;
 }
 int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_points *dst, void *stream, uint64_t *n_out) {
     if (!m || !n_out) return fail(SAGEICP_ERR_INVALID, "null argument");
     if (int rc = check_device_points(dst, stream, m->device)) return rc;
-    return export_rows(m->out, m->device, RowSource::of_map(m), RowSink::device_rows(dst, stream), n_out);
+    return export_map(internal(m), RowSink::device_rows(dst, stream), n_out);
 }
 static int map_msg(const sageicp_map *m, const sageicp_msg_colors *colors, void *out, uint64_t cap, bool on_device,
                    void *stream, uint64_t *n_out) {
@@ -321,7 +327,7 @@ static int map_msg(const sageicp_map *m, const sageicp_msg_colors *colors, void 
     int rc = color_table(colors, t);
     if (rc) return rc;
     if (on_device && (rc = check_records_out(out, cap, stream, m->device))) return rc;
-    return export_rows(m->out, m->device, RowSource::of_map(m), RowSink::records_out(out, cap, t, on_device, stream), n_out);
+    return export_map(internal(m), RowSink::records_out(out, cap, t, on_device, stream), n_out);
 }
 int sageicp_map_pointcloud_msg(const sageicp_map *m, const sageicp_msg_colors *colors, void *out, uint64_t cap,
                                uint64_t *n_out) {

@@ -202,16 +202,16 @@ static int pipeline_register(sageicp_pipeline *p, const FrameSource &src, double
         int register_source(const double guess[7], double max_dist, double kernel, double sem_th,
                             double pose[7], sageicp_stats *stats) {
             // the source cloud in the Prep buffers
-            return register_resident(p->impl.map, p->prep[p->cur].d_src.data(), p->prep[p->cur].kept_levels[1],
+            return register_resident(*p->impl.map, p->prep[p->cur].d_src.data(), p->prep[p->cur].kept_levels[1],
                                      p->device, guess, max_dist, kernel, sem_th, nullptr, pose, stats);
         }
         int update_map(const double pose[7]) {
             const Prep &pr = p->prep[p->cur];
             const uint64_t n_fd = pr.kept_levels[0];
-            if (src.kind == FrameSource::kMessage && !n_fd && map_is_empty(p->impl.map))
+            if (src.kind == FrameSource::kMessage && !n_fd && p->impl.map->empty())
                 return SAGEICP_OK;               // nothing into nothing
             if (p->impl.map_update_on_device_())
-                return device_update_all(p->impl.map, nullptr, n_fd, pose, pr.d_fd.data());
+                return device_update_all(*p->impl.map, nullptr, n_fd, pose, pr.d_fd.data());
             std::vector<double> fd(4 * n_fd);
             if (n_fd) {
                 HIPCHK(hipSetDevice(p->device));

@@ -3,6 +3,10 @@
 // libsageicp_hip.so's host side: capi_internal.h.
 #include "capi_internal.h"
 
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+
 namespace sageicp_impl {
 
 // ---- RCCL, bound at run time (only multi-GPU runs need it) ------------------------------------
@@ -62,10 +66,9 @@ double accept_threshold(double max_dist) {
 }
 
 // fewer than six points per voxel on average
-bool sparse_voxels(const sageicp_map *m) {
-    const uint64_t mp = m->on_device ? m->ctr.total_points : m->host.total_points;
-    const uint64_t mv = m->on_device ? m->ctr.num_voxels : m->host.num_voxels;
-    return mp < 6 * mv;
+bool sparse_voxels(const sageicp_map &m) {
+    const MapCounts c = m.counts();
+    return c.points < 6 * static_cast<uint64_t>(c.voxels);
 }
 
 // Does the scan of `n` queries read the compact copy behind its fp32 filter?  Worth it where scans
@@ -73,7 +76,7 @@ bool sparse_voxels(const sageicp_map *m) {
 // 6+ points on average (c2: +6 %, c4: +10 %; c1, c5 and the streamed 24k-point frames lose 4-5 %
 // with it; SAGEICP_FILTER=0/1 overrides).  Off for a negative or NaN sem_th, where a larger
 // distance can scale to a smaller one and the filter's thresholds do not exist.
-bool wants_filter(const sageicp_map *m, uint64_t n, double sem_th) {
+bool wants_filter(const sageicp_map &m, uint64_t n, double sem_th) {
     const int want = env_int("SAGEICP_FILTER", (n >= 40000 && !sparse_voxels(m)) ? 1 : 0);
     return sem_th >= 0.0 && want != 0;
 }
@@ -83,33 +86,32 @@ bool wants_filter(const sageicp_map *m, uint64_t n, double sem_th) {
 // restarting in every voxel leaves lanes idle and makes the heaviest query's chain the longer one (c5:
 // +4.6 %, c1 through the launch-per-iteration loop: +13 %); against c2's and c4's ~12 points per voxel the
 // restart is faster by 1.5 and 5 %.  (8 and 16 lanes always stride flat; SAGEICP_FLAT=0/1 overrides.)
-static bool wants_flat(const sageicp_map *m, int lw) {
-    const uint64_t mp = m->on_device ? m->ctr.total_points : m->host.total_points;
-    const uint64_t mv = m->on_device ? m->ctr.num_voxels : m->host.num_voxels;
-    return env_int("SAGEICP_FLAT", mp < (2ull << lw) * mv ? 1 : 0) != 0;
+static bool wants_flat(const sageicp_map &m, int lw) {
+    const MapCounts c = m.counts();
+    return env_int("SAGEICP_FLAT", c.points < (2ull << lw) * c.voxels ? 1 : 0) != 0;
 }
 
 // k_icp's arguments for a search of `n` queries against the HBM copy of `m`; the sums are accumulated at
 // 2^(-24 acc_shift) of their value (run_icp raises the shift for a frame whose sums left the fixed-point range)
-IcpParams icp_params(const sageicp_map *m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift) {
-    const Scratch &sc = m->sc;
+IcpParams icp_params(const sageicp_map &m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift) {
+    const Scratch &sc = m.sc;
+    const SearchView map = m.dev.search_view();
     IcpParams ip{};
     ip.frame = d_queries;
     ip.n = static_cast<int>(n);
     ip.st = sc.d_state.data();
     ip.check_done = 0;
     ip.apply_pose = 0;
-    ip.voxel_size = m->host.voxel_size;
-    ip.inv_voxel_size = env_int("SAGEICP_EXACT_DIVIDE", 0) ? 0.0 : 1.0 / m->host.voxel_size;
+    ip.voxel_size = m.host.voxel_size;
+    ip.inv_voxel_size = env_int("SAGEICP_EXACT_DIVIDE", 0) ? 0.0 : 1.0 / m.host.voxel_size;
     ip.rows = sc.d_rows.data();
-    ip.table = m->d_table.data();
-    ip.mask = static_cast<uint32_t>(m->d_table.capacity() - 1);
-    ip.pts = m->d_pts.data();
-    const uint64_t pts_bytes = (static_cast<uint64_t>(m->units_cap()) * kUnitPoints + 1) * sizeof(Point4);
-    ip.pts_bytes = static_cast<uint32_t>(pts_bytes);        // (< 4 GiB: kMaxUnits units of 128 B)
-    ip.cand = m->d_cand.data();
-    ip.cand_bytes = m->cand_slots() >= m->units_cap() * kUnitPoints ? static_cast<uint32_t>(pts_bytes / 2) : 0u;
-    ip.cand_flags = m->d_cand_flags.data();
+    ip.table = map.table;
+    ip.mask = map.mask;
+    ip.pts = map.pts;
+    ip.pts_bytes = static_cast<uint32_t>(map.pts_bytes);    // (< 4 GiB: kMaxUnits units of 128 B)
+    ip.cand = map.cand;
+    ip.cand_bytes = map.cand_bytes;
+    ip.cand_flags = map.cand_flags;
     // fp32 thresholds of the scan's filter (kernels.hip): off (infinite) for a negative or NaN
     // sem_th, where a larger distance can scale to a smaller one
     {
@@ -183,8 +185,8 @@ static int loop_wgs_per_cu(const Scratch &sc, int lw, bool filter, int nw, size_
     // its ceil(nw / 4) waves on the same SIMD.  Four waves per workgroup, seven workgroups per CU fill the CU.
     return std::min(v, SAGE_LOOP_OCC / ((nw + 3) / 4));
 }
-static bool plan_loop(const sageicp_map *m, uint64_t n, double sem_th, LoopPlan *out) {
-    const Scratch &sc = m->sc;
+static bool plan_loop(const sageicp_map &m, uint64_t n, double sem_th, LoopPlan *out) {
+    const Scratch &sc = m.sc;
     const int mode = env_int("SAGEICP_LOOP", 1);       // 0: never, 1 / 2: wherever the frame fits
     if (mode == 0 || n == 0 || sc.num_cus < 8) return false;
     const bool sparse = sparse_voxels(m);
@@ -314,7 +316,7 @@ struct Attempt {
 
 // What the attempts of a call share: its arguments and what follows from them and the knobs alone.
 struct IcpCall {
-    const sageicp_map *m;
+    sageicp_map &m;
     const Point4 *d_frame;
     uint64_t n;
     const double *init;
@@ -388,7 +390,7 @@ struct IcpCall {
             HIPCHK(check_copy_frame(d_frame, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), comm == nullptr, s));
         else if (n > 0)
             HIPCHK(sort_frame(d_frame, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), true, comm == nullptr,
-                              m->host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(),
+                              m.host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(),
                               sc.d_sort_temp.capacity(), s));
         return SAGEICP_OK;
     }
@@ -787,7 +789,7 @@ static int run_attempt(const IcpCall &c, const Attempt &a, AttemptResult &r) {
     int rc;
     if ((rc = c.start_state())) return rc;
     const AttemptPlan p = plan_attempt(c, a);
-    if ((rc = ensure_cand(c.m, wants_filter(c.m, c.n, c.sem_th)))) return rc;
+    if ((rc = c.m.dev.ensure_cand(wants_filter(c.m, c.n, c.sem_th), c.s))) return rc;
     if ((rc = sc.reserve_sort(c.n))) return rc;
     IcpParams ip = icp_params(c.m, sc.d_sorted.data(), c.n, c.sem_th, p.lw, a.acc_shift);
     ip.check_done = 1; ip.apply_pose = 1;
@@ -840,10 +842,10 @@ static void fill_stats(sageicp_stats *stats, const IcpState &st, uint64_t n, con
     stats->us_wall = now_us() - t_begin;             // (the whole call's, every attempt included)
 }
 
-int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const double init[7],
+int run_icp(sageicp_map &m, const Point4 *d_frame, uint64_t n, const double init[7],
             double max_dist, double kernel, double sem_th, sageicp_comm *comm, double out[7],
             sageicp_stats *stats, double us_upload, double t_begin) {
-    Scratch &sc = m->sc;
+    Scratch &sc = m.sc;
     if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
     int rc;
     IcpCall c{m, d_frame, n, init, max_dist, kernel, sem_th, comm, sc, sc.stream.get(), false, false, false, false, false, 0, P2pParams{}};
@@ -897,22 +899,22 @@ int run_icp(const sageicp_map *m, const Point4 *d_frame, uint64_t n, const doubl
 
 // ---- single-process multi-GPU mode -------------------------------------------------------------
 // Update(points, pose) on every copy of the map.  `d_points` (optional) lives on rank 0's device.
-int device_update_all(sageicp_map *m, const double *xyzl, uint64_t n, const double pose[7],
+int device_update_all(sageicp_map &m, const double *xyzl, uint64_t n, const double pose[7],
                       const Point4 *d_points) {
-    if (m->replicas_diverged)
+    if (m.replicas_diverged)
         return fail(SAGEICP_ERR_INVALID, "the copies of this multi-device map diverged in an earlier failed update: Clear() it");
     int rc = device_update(m, xyzl, n, pose, d_points);
-    if (rc || m->replicas.empty()) return rc;       // (a failed device update changes nothing on its device)
+    if (rc || m.replicas.empty()) return rc;       // (a failed device update changes nothing on its device)
     std::vector<double> host;
     if (d_points) {                               // the other devices take the points from the host
         host.resize(4 * n);
-        HIPCHK(hipSetDevice(m->device));
+        HIPCHK(hipSetDevice(m.device));
         if (n) HIPCHK(hipMemcpy(host.data(), d_points, n * sizeof(Point4), hipMemcpyDeviceToHost));
         xyzl = host.data();
     }
-    for (sageicp_map *r : m->replicas)
-        if ((rc = device_update(r, xyzl, n, pose))) {
-            m->replicas_diverged = true;            // rank 0 (and maybe others) took the update, this copy did not
+    for (sageicp_map *r : m.replicas)
+        if ((rc = device_update(*r, xyzl, n, pose))) {
+            m.replicas_diverged = true;            // rank 0 (and maybe others) took the update, this copy did not
             const std::string why = g_err;
             return fail(rc, "update reached only some devices of the map (" + why + "); the map must be cleared");
         }
@@ -921,18 +923,18 @@ int device_update_all(sageicp_map *m, const double *xyzl, uint64_t n, const doub
 
 // exchange blocks of the ranks of one process: fine-grained device memory, reached by the other
 // devices through peer access (no IPC)
-int create_ranks(const sageicp_map *m) {
-    const int N = 1 + static_cast<int>(m->replicas.size());
-    if (static_cast<int>(m->ranks.size()) == N) {
-        for (sageicp_comm *c : m->ranks)
+int create_ranks(sageicp_map &m) {
+    const int N = 1 + static_cast<int>(m.replicas.size());
+    if (static_cast<int>(m.ranks.size()) == N) {
+        for (sageicp_comm *c : m.ranks)
             if (c->poisoned)
                 return fail(SAGEICP_ERR_RCCL, "an earlier exchange between the devices of this map timed out: "
                                               "call sageicp_map_set_devices again");
         return SAGEICP_OK;
     }
     std::vector<int> dev(N);
-    dev[0] = m->device;
-    for (int k = 1; k < N; ++k) dev[k] = m->replicas[k - 1]->device;
+    dev[0] = m.device;
+    for (int k = 1; k < N; ++k) dev[k] = m.replicas[k - 1]->device;
     for (int a = 0; a < N; ++a)
         for (int b = 0; b < N; ++b) {
             if (dev[a] == dev[b]) continue;
@@ -971,7 +973,7 @@ int create_ranks(const sageicp_map *m) {
         for (int r = 0; r < N; ++r) ranks[k]->blocks[r] = ranks[r]->my_block;
         ranks[k]->p2p = true;
     }
-    m->ranks = ranks;
+    m.ranks = ranks;
     return SAGEICP_OK;
 }
 
@@ -979,17 +981,17 @@ int create_ranks(const sageicp_map *m) {
 // blocks of ceil(n / N) points) against its copy of the map, on its own host thread and
 // stream; the sums meet in k_fin (direct exchange).  Exactly one of h_frame / d_frame is given
 // (d_frame on rank 0's device).
-int register_sharded(const sageicp_map *m, const double *h_frame, const Point4 *d_frame, uint64_t n,
+int register_sharded(sageicp_map &m, const double *h_frame, const Point4 *d_frame, uint64_t n,
                      const double init[7], double max_dist, double kernel, double sem_th,
                      double pose_out[7], sageicp_stats *stats, double t0) {
-    if (m->replicas_diverged)
+    if (m.replicas_diverged)
         return fail(SAGEICP_ERR_INVALID, "the copies of this multi-device map diverged in an earlier failed update: Clear() it");
     int rc = create_ranks(m);
     if (rc) return rc;
-    const int N = 1 + static_cast<int>(m->replicas.size());
-    std::vector<const sageicp_map *> maps(N);
-    maps[0] = m;
-    for (int k = 1; k < N; ++k) maps[k] = m->replicas[k - 1];
+    const int N = 1 + static_cast<int>(m.replicas.size());
+    std::vector<sageicp_map *> maps(N);
+    maps[0] = &m;
+    for (int k = 1; k < N; ++k) maps[k] = m.replicas[k - 1];
     const uint64_t per = (n + N - 1) / N;
     std::vector<int> codes(N, SAGEICP_OK);
     std::vector<std::string> errors(N);
@@ -1003,16 +1005,16 @@ int register_sharded(const sageicp_map *m, const double *h_frame, const Point4 *
     int gate_arrived = 0;
     bool gate_ok = true;
     auto work = [&](int k) {
-        const sageicp_map *mk = maps[k];
+        sageicp_map &mk = *maps[k];
         const uint64_t lo = std::min<uint64_t>(n, k * per), cnt = std::min<uint64_t>(n, lo + per) - lo;
         const Point4 *mine = nullptr;
         auto setup = [&]() -> int {
-            HIPCHK(hipSetDevice(mk->device));
-            int r = sync_mirror(mk);
+            HIPCHK(hipSetDevice(mk.device));
+            int r = refresh_mirror(mk);
             if (r) return r;
-            Scratch &sc = mk->sc;
+            Scratch &sc = mk.sc;
             if ((r = sc.reserve_frame(cnt))) return r;
-            if ((r = ensure_cand(mk, wants_filter(mk, cnt, sem_th)))) return r;
+            if ((r = mk.dev.ensure_cand(wants_filter(mk, cnt, sem_th), sc.stream.get()))) return r;
             if ((r = sc.reserve_sort(cnt))) return r;
             mine = sc.d_frame.data();
             if (cnt) {
@@ -1022,7 +1024,7 @@ int register_sharded(const sageicp_map *m, const double *h_frame, const Point4 *
                 else if (k == 0)
                     mine = d_frame + lo;
                 else
-                    HIPCHK(hipMemcpyPeerAsync(sc.d_frame.data(), mk->device, d_frame + lo, m->device,
+                    HIPCHK(hipMemcpyPeerAsync(sc.d_frame.data(), mk.device, d_frame + lo, m.device,
                                               cnt * sizeof(Point4), sc.stream.get()));
                 HIPCHK(hipStreamSynchronize(sc.stream.get()));     // the shard has arrived (or the copy failed: here, not in the loop)
             }
@@ -1043,7 +1045,7 @@ int register_sharded(const sageicp_map *m, const double *h_frame, const Point4 *
                 return;
             }
         }
-        codes[k] = run_icp(mk, mine, cnt, init, max_dist, kernel, sem_th, m->ranks[k], poses[k].data(),
+        codes[k] = run_icp(mk, mine, cnt, init, max_dist, kernel, sem_th, m.ranks[k], poses[k].data(),
                            &st[k], now_us() - t0, t0);
         if (codes[k]) errors[k] = g_err;
     };
@@ -1051,7 +1053,7 @@ int register_sharded(const sageicp_map *m, const double *h_frame, const Point4 *
     for (int k = 1; k < N; ++k) th.emplace_back(work, k);
     work(0);
     for (auto &t : th) t.join();
-    (void)hipSetDevice(m->device);
+    (void)hipSetDevice(m.device);
     for (int k = 0; k < N; ++k)        // the rank that failed on its own first, then the ones it stopped
         if (codes[k] && errors[k].rfind("not started", 0) != 0)
             return fail(codes[k], "device rank " + std::to_string(k) + ": " + errors[k]);

@@ -18,7 +18,7 @@
 //   k_dyn_count      compress; per point the L neighbours within radius; size and count per root (integer atomics)
 //   k_dyn_records    the components of >= 5 points, in ascending root order = the order PCL finds them
 //   -- round trip 2: the per-component table (root, size, count); the host replays PCL's std::sort of the clusters
-//      (cluster_emission_order, capi_internal.h), applies the static test and uploads each kept cluster's offset --
+//      (cluster_emission_order, dyn_rules.h), applies the static test and uploads each kept cluster's offset --
 //   k_dyn_scatter    the kept clusters' points behind the inliers (points grouped by root with a stable sort)
 //
 // Distances follow FLANN's L2_Simple in fp32 on the float copies PCL makes: d2 = (dx*dx + dy*dy) + dz*dz with

@@ -1,11 +1,13 @@
 // The two scalar conversions of the dynamic vehicle filter (core/Preprocessing.cpp:95-172) whose C++ behaviour is
-// undefined for some inputs, fixed here to what the reference's x86-64 build computes.  Host and
-// device; compiled on its own by tests/test_dynfilter_host.py.
+// undefined for some inputs, fixed here to what the reference's x86-64 build computes, host and device,
+// and the order its clusters are emitted in (host).  Compiled on its own by tests/test_dynfilter_host.py.
 #pragma once
 
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <vector>
 
 #include "sageicp_types.h"
 
@@ -29,6 +31,20 @@ SAGE_HD inline int x86_int_cast(double v) {
 SAGE_HD inline bool cluster_is_static(uint64_t count, uint32_t size, double dy_th) {
     const int th = x86_int_cast(dy_th * static_cast<double>(size));
     return count >= 1 && (th < 0 || count > static_cast<uint64_t>(th));
+}
+
+// PCL's cluster order: EuclideanClusterExtraction finds the clusters in order of their smallest index, then
+// std::sort(clusters.rbegin(), clusters.rend(), comparePointClusters) orders them by size, largest first — not stably.
+// std::sort permutes by comparisons only, so the same call on (size, index) records with the same comparator gives
+// PCL's permutation under the same standard library (libstdc++).  order[j] = index of the j-th cluster emitted.
+inline void cluster_emission_order(const uint32_t *sizes, size_t n, uint32_t *order) {
+    struct Rec {
+        uint32_t size, index;
+    };
+    std::vector<Rec> v(n);
+    for (size_t k = 0; k < n; ++k) v[k] = Rec{sizes[k], static_cast<uint32_t>(k)};
+    std::sort(v.rbegin(), v.rend(), [](const Rec &a, const Rec &b) { return a.size < b.size; });
+    for (size_t k = 0; k < n; ++k) order[k] = v[k].index;
 }
 
 }  // namespace sageicp

@@ -291,29 +291,36 @@ public:
         return k;
     }
 
-    // Take over the state a device-side update left in HBM (capi.hip ensure_host): the device
+    // Take over the state a device-side update left in HBM (map_device.hip, download_into): the device
     // table (any slot layout, tombstones allowed), the first `bhi` point blocks, the per-block
     // unlabelled counts, the free-list stack and the counters.  The host table is rebuilt
     // tombstone-free at the same capacity, so afterwards it must be uploaded as a whole.
-    // `dregions`: the region words of blocks [0, bhi); `dfree_units[k]` / `nfree_units[k]`: the free
-    // regions of class k; units [0, uhi) of the point array are filled by the caller afterwards.
-    void adopt(const std::vector<Slot> &dtab, size_t blocks_cap, uint32_t bhi, const uint8_t *dzeros,
-               const uint32_t *dfree, uint32_t nfree, uint32_t nvox, uint64_t total,
-               const uint32_t *dregions, size_t units_cap, uint32_t uhi,
-               const uint32_t *const dfree_units[kMaxClasses], const uint32_t nfree_units[kMaxClasses]) {
+    // `regions`, `zeros`: of blocks [0, blocks_hi); `free_units[k]`: the free regions of class k;
+    // units [0, units_hi) of the point array are filled by the caller afterwards.
+    struct Adopted {
+        std::vector<Slot> table;
+        std::vector<uint32_t> regions, free_blocks, free_units[kMaxClasses];
+        std::vector<uint8_t> zeros;
+        size_t blocks_cap = 0, units_cap = 0;     // what the device arrays hold: the host's get the same
+        uint32_t blocks_hi = 0, units_hi = 0, num_voxels = 0;
+        uint64_t total_points = 0;
+    };
+    void adopt(const Adopted &a) {
+        const std::vector<Slot> &dtab = a.table;
+        const size_t blocks_cap = a.blocks_cap;
+        const uint32_t bhi = a.blocks_hi;
         reset_table(static_cast<uint32_t>(dtab.size()));
         cnt.assign(blocks_cap, 0);
         zeros.assign(blocks_cap, 0);
         keys.assign(3 * blocks_cap, 0);
         regions.assign(blocks_cap, kNoRegion);
-        if (bhi) std::memcpy(regions.data(), dregions, static_cast<size_t>(bhi) * sizeof(uint32_t));
-        for (int k = 0; k < kMaxClasses; ++k)
-            free_units[k].assign(dfree_units[k], dfree_units[k] + nfree_units[k]);
-        units_hi = uhi;
+        if (bhi) std::memcpy(regions.data(), a.regions.data(), static_cast<size_t>(bhi) * sizeof(uint32_t));
+        for (int k = 0; k < kMaxClasses; ++k) free_units[k] = a.free_units[k];
+        units_hi = a.units_hi;
         regions_all_dirty = false;
         dirty_regions.clear();
-        pts.resize(units_cap * kUnitPoints, static_cast<size_t>(uhi) * kUnitPoints);   // units [0, uhi) filled by the caller
-        block_of.assign(units_cap, 0);
+        pts.resize(a.units_cap * kUnitPoints, static_cast<size_t>(units_hi) * kUnitPoints);   // units [0, units_hi) filled by the caller
+        block_of.assign(a.units_cap, 0);
         for (uint32_t b = 0; b < bhi; ++b)
             if (regions[b] != kNoRegion) block_of[region_unit(regions[b])] = b;
         for (const Slot &e : dtab) {
@@ -323,11 +330,11 @@ public:
             cnt[b] = static_cast<uint8_t>(e.blk & 255u);
             keys[3 * b] = e.x; keys[3 * b + 1] = e.y; keys[3 * b + 2] = e.z;
         }
-        if (bhi) std::memcpy(zeros.data(), dzeros, bhi);
-        free_blocks.assign(dfree, dfree + nfree);
+        if (bhi) std::memcpy(zeros.data(), a.zeros.data(), bhi);
+        free_blocks = a.free_blocks;
         blocks_hi = bhi;
-        num_voxels = nvox;
-        total_points = total;
+        num_voxels = a.num_voxels;
+        total_points = a.total_points;
         dirty_pts.clear();
         dirty_slots.clear();
         table_all_dirty = true;

@@ -29,16 +29,16 @@ struct RowSource {
     // Resident: the gather, fused into a caller's layout or packed into d_pc (SAGEICP_EGRESS_TWO_PASS=1: always
     // packed); in reference-order mode the listed gather, synchronous.  Not resident: the host copy, staged and
     // uploaded — or, for host rows, copied on the host with no device at all.
-    const sageicp_map *map = nullptr;
+    sageicp_map *map = nullptr;
 
     static RowSource packed(const Point4 *d_rows, uint64_t n, hipStream_t stream) {
         RowSource s;
         s.d_rows = d_rows; s.n = n; s.stream = stream;
         return s;
     }
-    static RowSource of_map(const sageicp_map *m) {
+    static RowSource of_map(sageicp_map &m) {
         RowSource s;
-        s.map = m;
+        s.map = &m;
         return s;
     }
 };

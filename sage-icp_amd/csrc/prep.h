@@ -1,8 +1,10 @@
 // The per-frame driver in front of registration: what a frame is prepared from (FrameSource: host rows, a device frame,
 // a message), what it passes through (deskew, the dynamic vehicle filter) and the buffers of one preparation (Prep).
-// Declarations only: Prep's bodies are in prep.hip, DynFilter's in dyn_filter.hip.  Included by capi_internal.h after the
-// helpers the declarations name (ReplayPool); not part of the C ABI.
+// Declarations only: Prep's bodies are in prep.hip, DynFilter's in dyn_filter.hip.  Included by capi_internal.h; not part of
+// the C ABI.
 #pragma once
+
+#include "replay_pool.h"
 
 namespace sageicp {
 

@@ -5,6 +5,7 @@
 #include "capi_internal.h"
 
 #include <cassert>
+#include <thread>
 
 namespace sageicp {
 
