@@ -66,8 +66,8 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * sageicp_pipeline_set_key_frames, sageicp_pipeline_key_frame_reset / _info / _grid / _grid_device,
  * sageicp_occupancy_grid, sageicp_occupancy_grid_device; then PointCloud2 payloads — sageicp_msg_layout, sageicp_msg_colors,
  * SAGEICP_MSG_*, sageicp_pipeline_register_frame_msg / _msg_device, sageicp_pipeline_source_msg / _msg_device,
- * sageicp_map_pointcloud_msg / _msg_device, sageicp_msg_output_fields (additions only: no existing struct or entry
- * changed). */
+ * sageicp_map_pointcloud_msg / _msg_device, sageicp_msg_output_fields; then correspondences of a device frame —
+ * sageicp_get_correspondences_device (additions only: no existing struct or entry changed). */
 #define SAGEICP_ABI_VERSION 4
 
 /* Filled by sageicp_register_frame*.  Times are microseconds. */
@@ -536,6 +536,37 @@ int sageicp_pipeline_source_device(const sageicp_pipeline *p, const sageicp_devi
  * host copy while it is not */
 int sageicp_map_pointcloud_device(const sageicp_map *m, const sageicp_device_points *dst,
                                   void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
+/* VoxelHashMap::GetCorrespondences (core/VoxelHashMap.cpp:48-130) of a frame in device memory, answered into device memory.
+ * Inputs: the frame is read through sageicp_pipeline_register_frame_device's conversion (a plain (double) cast).  With
+ * pose != NULL every row is first moved by the point action of sageicp_transform_points, bit for bit, its label kept:
+ * the moved rows are the queries (Registration.cpp:123,129).  A pose, coordinate or label that is not finite refuses
+ * the whole call (SAGEICP_ERR_INVALID) before anything is written to a destination.
+ * Result: *n_out pairs, in query order, exactly sageicp_get_correspondences': pair k has src = the k-th accepted query
+ * row (with a pose: the moved row), tgt = that query's semantic nearest neighbour, bit for bit the map's row, and
+ * query_idx_out[k] = the query's index in the frame.  A query with no point in its 27 voxels gives no pair; an empty
+ * map or n == 0 gives 0 pairs and reads nothing.
+ * Capacity: any of src_out, tgt_out, query_idx_out may be NULL (all three: a count-only call); the caps of those given
+ * — src_out->cap, tgt_out->cap, idx_cap — must be equal.  The first min(cap, *n_out) pairs are written and nothing
+ * beyond them is touched.  Conversions into src_out / tgt_out are sageicp_device_points' own, the refusal of an integer
+ * label that does not fit included (the destinations' contents are then unspecified).
+ * Checks, before anything is enqueued: the three layouts first (no device is asked); the caps; query_idx_out 8-byte
+ * aligned; destinations that overlap EACH OTHER are refused (their extents are compared on the host); then every extent
+ * must be device memory of the map's device, and the stream one of it.  A destination MAY alias the frame: the frame is
+ * ingested completely into the library's own rows before any destination is written — guaranteed.
+ * Stream and lifetime: as for sageicp_device_frame and sageicp_device_points — the caller's earlier work on `stream` is
+ * ordered before the call's through an event; the call is synchronous: on return the pairs are in place and nothing
+ * reads or writes the caller's memory.
+ * Map state: the target rows come from the HBM copy of the map, as a mirror (refreshed like before any search) or as the
+ * authority: nothing is downloaded, and sageicp_map_resident, sageicp_map_table_stats and sageicp_map_loop_status answer
+ * after the call what they answered before it.  (sageicp_get_correspondences reads the host copy and hands a resident
+ * map back to the host.)  A map that spans several devices answers on the first. */
+int sageicp_get_correspondences_device(const sageicp_map *map, const sageicp_device_frame *frame,
+                                       const double pose[7] /* NULL = identity */,
+                                       double max_correspondence_distance, double sem_th,
+                                       const sageicp_device_points *src_out /* or NULL */,
+                                       const sageicp_device_points *tgt_out /* or NULL */,
+                                       int64_t *query_idx_out /* device, or NULL */, uint64_t idx_cap,
+                                       void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
 int sageicp_pipeline_reinitialize(sageicp_pipeline *p);          /* pipeline/sageICP.hpp:94-99 */
 uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p);  /* poses().size() */
 int sageicp_pipeline_pose(const sageicp_pipeline *p, uint64_t index, double pose_out[7]);

@@ -252,6 +252,9 @@ _SIGNATURES = [
     ("sageicp_map_sync", C.c_int, [C.c_void_p]),
     ("sageicp_get_correspondences", C.c_int,
      [C.c_void_p, _dp, C.c_uint64, C.c_double, C.c_double, _dp, _dp, _u64p, _i64p]),
+    ("sageicp_get_correspondences_device", C.c_int,
+     [C.c_void_p, C.POINTER(DeviceFrame), _dp, C.c_double, C.c_double, C.POINTER(DevicePoints), C.POINTER(DevicePoints),
+      C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
     ("sageicp_align_clouds", C.c_int, [_dp, _dp, C.c_uint64, C.c_double, _dp, _dp, _dp, C.c_int]),
     ("sageicp_transform_points", C.c_int, [_dp, _dp, C.c_uint64, C.c_int]),
     ("sageicp_register_frame", C.c_int,
@@ -955,7 +958,21 @@ class VoxelHashMap:
         _check(lib().sageicp_map_loop_status(self._h, C.byref(st)))
         return st
 
-    def GetCorrespondences(self, pts, max_correspondance_distance, th, with_index=False):
+    def GetCorrespondences(self, pts, max_correspondance_distance, th, with_index=False, labels=None, pose=None,
+                           dtype=None):
+        """GetCorrespondences (core/VoxelHashMap.cpp:48-130): (src, tgt[, idx]), the accepted pairs in query order.
+        `pts` as numpy (n, 4) rows or a CPU tensor: numpy (k, 4) float64 arrays and an int64 idx
+        (sageicp_get_correspondences; the target rows are read from the host copy, so a resident map is handed back to
+        the host).  `pts` as a torch tensor on the map's GPU, in the layouts RegisterFrame takes (`labels` as there):
+        tensors on that GPU — (k, 4) float64, or dtype=torch.float32, and an int64 idx — allocated at n rows and
+        returned as [:k] views (sageicp_get_correspondences_device); with pose= (qx, qy, qz, qw, tx, ty, tz) the rows
+        are first moved as transform_points moves them, and src holds the moved rows.  The map stays where it is: a
+        resident map stays resident.  Ordered on the device's current torch stream; synchronous."""
+        if _is_device_tensor(pts):
+            return self._correspondences_device(pts, max_correspondance_distance, th, with_index, labels, pose, dtype)
+        for name, v in (("labels", labels), ("pose", pose), ("dtype", dtype)):
+            if v is not None:
+                raise ValueError("%s= is for a frame that is a torch tensor on a GPU" % name)
         pts, pp = _d(pts)
         n = pts.reshape(-1, 4).shape[0]
         src = np.empty((n, 4))
@@ -969,6 +986,31 @@ class VoxelHashMap:
         if with_index:
             return src[:k].copy(), tgt[:k].copy(), idx[:k].copy()
         return src[:k].copy(), tgt[:k].copy()
+
+    def _correspondences_device(self, pts, max_dist, th, with_index, labels, pose, dtype):
+        # everything that can be wrong with the arguments raises ValueError before any call into the library
+        f, stream = _device_rows(DeviceFrame, pts, labels, self.device, _FRAME_WORDS)
+        pp = None
+        if pose is not None:
+            pose_a, pp = _d(pose)
+            if pose_a.size != 7:
+                raise ValueError("a pose is (qx, qy, qz, qw, tx, ty, tz)")
+        import torch
+        dt = torch.float64 if dtype is None else dtype
+        if dt not in (torch.float32, torch.float64):
+            raise ValueError("dtype= is torch.float32 or torch.float64, not %s" % (dt,))
+        n = int(f.n)
+        src = torch.empty((n, 4), dtype=dt, device=pts.device)
+        tgt = torch.empty((n, 4), dtype=dt, device=pts.device)
+        idx = torch.empty(n, dtype=torch.int64, device=pts.device) if with_index else None
+        ds, _ = _device_rows(DevicePoints, src, None, self.device, _OUT_WORDS, distinct=True)
+        dg, _ = _device_rows(DevicePoints, tgt, None, self.device, _OUT_WORDS, distinct=True)
+        nout = C.c_uint64(0)
+        _check(lib().sageicp_get_correspondences_device(
+            self._h, C.byref(f), pp, max_dist, th, C.byref(ds), C.byref(dg),
+            (idx.data_ptr() or None) if with_index else None, n, stream, C.byref(nout)))
+        k = nout.value
+        return (src[:k], tgt[:k], idx[:k]) if with_index else (src[:k], tgt[:k])
 
 
 def register_frame(frame, voxel_map, initial_guess, max_correspondence_distance, kernel, sem_th,

@@ -20,5 +20,16 @@ int check_stream(void *stream, int device);
 // stored there.
 int check_device_frame(const sageicp_device_frame *f, const double *ts, void *stream, int device, int *found = nullptr);
 int check_device_points(const sageicp_device_points *d, void *stream, int device);
+// The layout part of the two checks above alone: no device is asked.  An entry that takes several layouts checks them
+// all before it looks at where any of them points (sageicp_get_correspondences_device).
+int check_frame_layout(const sageicp_device_frame *f);
+int check_points_layout(const sageicp_device_points *d);
+// the bytes [lo, hi) a destination of a valid layout spans — its rows and, if apart, its labels: `out` gets that many
+// (0 for cap == 0), for comparing the extents of several destinations on the host
+struct CallerExtent {
+    const char *lo, *hi;
+    bool overlaps(const CallerExtent &o) const { return lo < o.hi && o.lo < hi; }
+};
+int points_extents(const sageicp_device_points &d, CallerExtent out[2]);
 
 }  // namespace sageicp_impl

@@ -74,9 +74,8 @@ static const RowRules kPointsRows{
                        1u << SAGEICP_DTYPE_FLOAT32 | 1u << SAGEICP_DTYPE_FLOAT64,
     "SAGEICP_DTYPE_UINT8, _INT32, _INT64, _FLOAT32 or _FLOAT64", std::numeric_limits<uint64_t>::max()};
 
-// everything about caller rows that can be known before the stream is touched or anything launched (caller_mem.h)
-static int check_rows(const CallerRows &r, const RowRules &k, const double *ts, void *stream, int device,
-                      int *found = nullptr) {
+// the layout of caller rows: what can be known without a device.  *xyz_bytes, *label_bytes: what a row and a label occupy
+static int check_layout(const CallerRows &r, const RowRules &k, size_t *xyz_bytes = nullptr, size_t *label_bytes = nullptr) {
     const std::string pre = k.prefix;
     if (r.rows && !r.xyz) return fail(SAGEICP_ERR_INVALID, pre + "xyz is NULL");
     const size_t ex = r.xyz_dtype == SAGEICP_DTYPE_FLOAT32 || r.xyz_dtype == SAGEICP_DTYPE_FLOAT64 ? dtype_bytes(r.xyz_dtype) : 0;
@@ -95,15 +94,26 @@ static int check_rows(const CallerRows &r, const RowRules &k, const double *ts, 
             return fail(SAGEICP_ERR_INVALID, pre + "label_stride must be a positive multiple of the label's size");
     }
     if (r.rows > k.max_rows) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
-    if (!r.rows) return SAGEICP_OK;
-    int rc = require_device();
+    if (xyz_bytes) *xyz_bytes = cols * ex;
+    if (label_bytes) *label_bytes = el;
+    return SAGEICP_OK;
+}
+
+// everything about caller rows that can be known before the stream is touched or anything launched (caller_mem.h)
+static int check_rows(const CallerRows &r, const RowRules &k, const double *ts, void *stream, int device,
+                      int *found = nullptr) {
+    const std::string pre = k.prefix;
+    size_t row = 0, el = 0;
+    int rc = check_layout(r, k, &row, &el);
     if (rc) return rc;
+    if (!r.rows) return SAGEICP_OK;
+    if ((rc = require_device())) return rc;
     if (found) {                        // (memory that is not device memory is refused just below)
         device = 0;
         (void)device_of(r.xyz, &device);
         *found = device;
     }
-    rc = check_extent(r.xyz, (r.rows - 1) * r.xyz_stride + cols * ex, device, (pre + "xyz").c_str());
+    rc = check_extent(r.xyz, (r.rows - 1) * r.xyz_stride + row, device, (pre + "xyz").c_str());
     if (!rc && r.label) rc = check_extent(r.label, (r.rows - 1) * r.label_stride + el, device, (pre + "label").c_str());
     if (!rc && ts) rc = check_extent(ts, r.rows * sizeof(double), device, "timestamps");
     return rc ? rc : check_stream(stream, device);
@@ -113,6 +123,33 @@ int check_device_frame(const sageicp_device_frame *f, const double *ts, void *st
     if (!f) return fail(SAGEICP_ERR_INVALID, "null device frame");
     return check_rows({f->xyz, f->xyz_stride, f->xyz_dtype, f->label, f->label_stride, f->label_dtype, f->n}, kFrameRows,
                       ts, stream, device, found);
+}
+
+static CallerRows rows_of(const sageicp_device_points &d) {
+    return {d.xyz, d.xyz_stride, d.xyz_dtype, d.label, d.label_stride, d.label_dtype, d.cap};
+}
+
+int check_frame_layout(const sageicp_device_frame *f) {
+    if (!f) return fail(SAGEICP_ERR_INVALID, "null device frame");
+    return check_layout({f->xyz, f->xyz_stride, f->xyz_dtype, f->label, f->label_stride, f->label_dtype, f->n}, kFrameRows);
+}
+
+int check_points_layout(const sageicp_device_points *d) {
+    if (!d) return fail(SAGEICP_ERR_INVALID, "null destination");
+    return check_layout(rows_of(*d), kPointsRows);
+}
+
+int points_extents(const sageicp_device_points &d, CallerExtent out[2]) {
+    size_t row = 0, el = 0;
+    if (check_layout(rows_of(d), kPointsRows, &row, &el) || !d.cap) return 0;
+    const char *xyz = static_cast<const char *>(d.xyz);
+    int k = 0;
+    out[k++] = {xyz, xyz + (d.cap - 1) * d.xyz_stride + row};
+    if (d.label) {
+        const char *l = static_cast<const char *>(d.label);
+        out[k++] = {l, l + (d.cap - 1) * d.label_stride + el};
+    }
+    return k;
 }
 
 int check_device_points(const sageicp_device_points *d, void *stream, int device) {

@@ -6,7 +6,8 @@
 //
 // Reference call sites this file stands in for (cpp/sage_icp/):
 //   core/Registration.cpp:113-141   RegisterFrame        -> run_icp()
-//   core/VoxelHashMap.cpp:48-130    GetCorrespondences   -> sageicp_get_correspondences()
+//   core/VoxelHashMap.cpp:48-130    GetCorrespondences   -> sageicp_get_correspondences(), and on a frame in device
+//                                                           memory sageicp_get_correspondences_device() (correspond.hip)
 //   core/VoxelHashMap.cpp:144-184   Update/AddPoints/... -> HostMap (host_map.hpp)
 // There is no CPU fallback: without a HIP device the compute entries fail with
 // SAGEICP_ERR_NO_DEVICE.
@@ -427,6 +428,147 @@ int sageicp_get_correspondences(const sageicp_map *map, const double *q, uint64_
         ++k;
     }
     *n_out = k;
+    return SAGEICP_OK;
+}
+
+// GetCorrespondences of a frame in device memory, answered into device memory: the same search, and behind it the
+// acceptance, the compaction in query order and the gather of the target rows on the device (correspond.hip).  The
+// target rows come from the HBM copy, which is valid as a mirror and as the authority alike: refresh_mirror() only,
+// never ensure_host() — a resident map stays resident.
+int sageicp_get_correspondences_device(const sageicp_map *map, const sageicp_device_frame *frame, const double pose[7],
+                                       double max_dist, double sem_th, const sageicp_device_points *src_out,
+                                       const sageicp_device_points *tgt_out, int64_t *query_idx_out, uint64_t idx_cap,
+                                       void *stream, uint64_t *n_out) {
+    if (!map || !frame || !n_out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    // what needs no device: the three layouts, the pose, the caps, the index array's alignment, destinations that overlap
+    int rc = check_frame_layout(frame);
+    if (!rc && src_out) rc = check_points_layout(src_out);
+    if (!rc && tgt_out) rc = check_points_layout(tgt_out);
+    if (rc) return rc;
+    if (pose && !finite_n(pose, 7)) return fail(SAGEICP_ERR_INVALID, "GetCorrespondences: the pose is not finite");
+    {
+        const uint64_t caps[3] = {src_out ? src_out->cap : 0, tgt_out ? tgt_out->cap : 0, idx_cap};
+        const bool given[3] = {src_out != nullptr, tgt_out != nullptr, query_idx_out != nullptr};
+        for (int a = 0; a < 3; ++a)
+            for (int b = a + 1; b < 3; ++b)
+                if (given[a] && given[b] && caps[a] != caps[b])
+                    return fail(SAGEICP_ERR_INVALID, "GetCorrespondences: src_out->cap, tgt_out->cap and idx_cap of the "
+                                                     "destinations given must be equal");
+    }
+    if (reinterpret_cast<uintptr_t>(query_idx_out) % 8)
+        return fail(SAGEICP_ERR_INVALID, "GetCorrespondences: query_idx_out must be 8-byte aligned");
+    CallerExtent ext[5];
+    int n_ext = 0;
+    int first_of_tgt = 0, first_of_idx = 0;
+    if (src_out) n_ext += points_extents(*src_out, ext + n_ext);
+    first_of_tgt = n_ext;
+    if (tgt_out) n_ext += points_extents(*tgt_out, ext + n_ext);
+    first_of_idx = n_ext;
+    if (query_idx_out && idx_cap) {
+        const char *p = reinterpret_cast<const char *>(query_idx_out);
+        ext[n_ext++] = {p, p + idx_cap * sizeof(int64_t)};
+    }
+    for (int a = 0; a < n_ext; ++a)
+        for (int b = a + 1; b < n_ext; ++b) {
+            // (a destination's own rows and labels are its caller's business, as everywhere)
+            const bool same = (b < first_of_tgt) || (a >= first_of_tgt && b < first_of_idx);
+            if (!same && ext[a].overlaps(ext[b]))
+                return fail(SAGEICP_ERR_INVALID, "GetCorrespondences: src_out, tgt_out and query_idx_out must not overlap "
+                                                 "each other");
+        }
+    // where the memory lives, and the stream
+    if ((rc = check_device_frame(frame, nullptr, stream, map->device))) return rc;
+    if (src_out && (rc = check_device_points(src_out, stream, map->device))) return rc;
+    if (tgt_out && (rc = check_device_points(tgt_out, stream, map->device))) return rc;
+    if (query_idx_out && idx_cap) {
+        if ((rc = require_device())) return rc;
+        if ((rc = check_extent(query_idx_out, idx_cap * sizeof(int64_t), map->device, "GetCorrespondences: query_idx_out")))
+            return rc;
+    }
+    if ((rc = check_stream(stream, map->device))) return rc;
+    sageicp_map &m = internal(map);
+    const uint64_t n = frame->n;
+    if (n == 0 || m.empty()) {
+        *n_out = 0;
+        return SAGEICP_OK;
+    }
+    if ((rc = refresh_mirror(m))) return rc;          // (makes the device current)
+    Scratch &sc = m.sc;
+    if ((rc = sc.reserve_frame(n))) return rc;
+    if ((rc = sc.reserve_nn(n))) return rc;
+    if ((rc = sc.reserve_sort(n))) return rc;
+    if ((rc = sc.reserve_correspond(n))) return rc;
+    hipStream_t s = sc.stream.get();
+    // the work that wrote the frame and may still use the destinations goes first
+    if ((rc = stream_after_caller(m.out.ev_caller, static_cast<hipStream_t>(stream), s))) return rc;
+    // Whatever a section enqueued is waited for before the call returns, also when it fails part-way: nothing touches
+    // the caller's memory afterwards.
+    auto section = [&](auto &&enqueue) -> int {
+        const int r = enqueue();
+        const hipError_t w = hipStreamSynchronize(s);
+        if (r) return r;
+        HIPCHK(w);
+        return SAGEICP_OK;
+    };
+    // 1. The frame, whole, into the library's rows — from here on the caller's frame is not read again, so a
+    // destination may alias it —, moved by the pose (k_tf: sageicp_transform_points' point action), sorted; the sort's
+    // first pass refuses non-finite rows as it does for every frame, and its verdict is read before anything is searched
+    // or written.
+    rc = section([&]() -> int {
+        launch_ingest(ingest_args(*frame), sc.d_frame.data(), s);
+        double I[7];
+        identity_pose(I);
+        fill_state(sc.h_state.data(), pose ? pose : I);
+        HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
+        if (pose) launch_tf(sc.d_frame.data(), static_cast<int>(n), sc.d_state.data(), s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(sort_frame(sc.d_frame.data(), sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), false, false,
+                          m.host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(),
+                          sc.d_sort_temp.capacity(), s));
+        HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
+        return SAGEICP_OK;
+    });
+    if (rc) return rc;
+    if (sc.h_state.data()->bad_input)
+        return fail(SAGEICP_ERR_INVALID, "GetCorrespondences: a coordinate or label of a query is not finite (NaN / Inf)");
+    // 2. the search (rows, k_icp search-only: the ready-made queries, no pose applied), then correspond.hip
+    unsigned long long *h_words = sc.h_corr_words.data();
+    rc = section([&]() -> int {
+        HIPCHK(hipMemsetAsync(sc.d_corr_words.data(), 0, 2 * sizeof(unsigned long long), s));
+        const int lw = icp_lw(n, sparse_voxels(m));
+        if (int r = m.dev.ensure_cand(wants_filter(m, n, sem_th), s)) return r;
+        const IcpParams ip = icp_params(m, sc.d_sorted.data(), n, sem_th, lw, 0);
+        launch_rows(ip, s);
+        launch_icp(ip, lw, false, s);
+        HIPCHK(hipGetLastError());
+        int *flags = reinterpret_cast<int *>(sc.d_corr_words.data() + 1);
+        CorrespondArgs a{};
+        a.n = static_cast<int>(n);
+        a.frame = sc.d_frame.data();
+        a.sorted = sc.d_sorted.data();
+        a.perm = sc.d_vals.data() + n;
+        a.nn = sc.d_nn.data();
+        a.pts = m.dev.search_view().pts;
+        a.accept_r2 = accept_threshold(max_dist);
+        a.by_query = sc.d_by_query.data();
+        a.counts = sc.d_corr_counts.data();
+        a.total = sc.d_corr_words.data();
+        a.has_src = src_out != nullptr;
+        a.has_tgt = tgt_out != nullptr;
+        if (src_out) a.src = egress_args(*src_out, flags);
+        if (tgt_out) a.tgt = egress_args(*tgt_out, flags);
+        a.idx = reinterpret_cast<long long *>(query_idx_out);
+        a.idx_cap = idx_cap;
+        launch_correspond(a, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_words, sc.d_corr_words.data(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        return SAGEICP_OK;
+    });
+    if (rc) return rc;
+    if (static_cast<int>(h_words[1]) & kEgressLabelRange)
+        return fail(SAGEICP_ERR_INVALID, "GetCorrespondences: a label does not fit the destination's label type "
+                                         "(static_cast<int64_t>(label) out of its range)");
+    *n_out = h_words[0];
     return SAGEICP_OK;
 }
 

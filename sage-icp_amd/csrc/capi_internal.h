@@ -1,7 +1,8 @@
 // Internals shared by the translation units of libsageicp_hip.so's host side (capi.hip, capi_pipeline.hip,
 // capi_outputs.hip, caller_mem.hip, map_device.hip, capi_run.hip, prep.hip): error channel, tuning knobs, the
 // per-handle device scratch, the pipeline's frame source and buffers (prep.h) and its prefetch state (prefetch.h), the
-// checks of a caller's device memory (caller_mem.h), the HBM copy of a map (map_device.h), the way out (outputs.h), the
+// checks of a caller's device memory (caller_mem.h), the HBM copy of a map (map_device.h), the way out (outputs.h), what
+// follows the search of GetCorrespondences on the device (correspond.h), the
 // opaque handles of include/sageicp.h except the pipeline's (capi_pipeline.hip) and the one place where the ABI's
 // `const sageicp_map *` becomes the reference the internals take (internal()).  Not part of the C ABI.
 #pragma once
@@ -31,6 +32,7 @@
 #include "host_map.hpp"
 #include "kernels.h"
 #include "egress.h"
+#include "correspond.h"
 #include "msg.h"
 #include "map_update.h"
 #include "metrics.hpp"
@@ -192,8 +194,14 @@ struct Scratch {
     PinnedBuf<IcpProgress, hipHostMallocMapped | hipHostMallocCoherent> h_prog;   // written by the device every iteration
     IcpProgress *d_prog = nullptr; // its device address
     std::vector<OwnedEvent> events;  // 5 per profiled iteration
+    // GetCorrespondences on the device (correspond.h): every query's accepted answer, the workgroups' counts and their
+    // scan, the words the kernels leave (pairs, refusal flags) and their pinned landing place
+    DevBuf<int32_t> d_by_query;
+    DevBuf<uint32_t> d_corr_counts;
+    DevBuf<unsigned long long> d_corr_words;
+    PinnedBuf<unsigned long long> h_corr_words;
 
-    ~Scratch() { wait(); }          // (then the members go: nothing runs on the streams any more)
+    ~Scratch() { wait(); }         // (then the members go: nothing runs on the streams any more)
     // waits for both streams, with the device current (a scratch that never created a stream calls nothing)
     void wait() const {
         if (!stream) return;
@@ -290,6 +298,14 @@ struct Scratch {
         HIPCHK(d_vals.reserve(2 * cap));
         HIPCHK(d_sort_temp.reserve(sort_temp_bytes(static_cast<int>(cap))));
         sort_cap = cap;
+        return SAGEICP_OK;
+    }
+    int reserve_correspond(size_t n) {
+        if (n > d_by_query.capacity()) HIPCHK(d_by_query.reserve(n + n / 4 + 1024));
+        const size_t words = 2 * static_cast<size_t>(correspond_blocks(static_cast<int>(n)));
+        if (words > d_corr_counts.capacity()) HIPCHK(d_corr_counts.reserve(words + words / 4 + 16));
+        if (!d_corr_words) HIPCHK(d_corr_words.reserve(2));
+        if (!h_corr_words) HIPCHK(h_corr_words.reserve(2));
         return SAGEICP_OK;
     }
     int reserve_partials(size_t blocks) {
@@ -415,6 +431,7 @@ bool all_finite(const double *xyzl, uint64_t n);
 // capi_run.hip
 void identity_pose(double T[7]);
 void fill_state(IcpState *st, const double init[7]);
+double accept_threshold(double max_dist);
 bool sparse_voxels(const sageicp_map &m);
 bool wants_filter(const sageicp_map &m, uint64_t n, double sem_th);
 IcpParams icp_params(const sageicp_map &m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift);

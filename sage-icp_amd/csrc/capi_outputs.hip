@@ -135,7 +135,7 @@ static int packed_rows(const RowSource &src, uint64_t n, DevBuf<Point4> &d_pc, s
     return SAGEICP_OK;
 }
 
-static EgressArgs egress_args(const sageicp_device_points &d, int *flags) {
+EgressArgs egress_args(const sageicp_device_points &d, int *flags) {
     EgressArgs a{};
     a.xyz = static_cast<unsigned char *>(d.xyz);
     a.xyz_stride = d.xyz_stride;

@@ -74,6 +74,9 @@ struct RowSink {
 // cannot hold, or that has no colour, refuses the call (whatever was written below cap stays written).
 int export_rows(OutputBuffers &ob, int device, const RowSource &src, const RowSink &sink, uint64_t *n_out);
 
+// a validated destination as the writers of egress.h take it; flags: the device word a label that does not fit is raised in
+EgressArgs egress_args(const sageicp_device_points &d, int *flags);
+
 // what the record entries check first: the node's color_list as the 256-entry table the label rule leaves room for (keys
 // outside 0..255 can never match), and a caller's destination of cap records in device memory with its stream
 int color_table(const sageicp_msg_colors *c, MsgColorTable &t);
