@@ -340,7 +340,7 @@ struct IcpCall {
             return fail(SAGEICP_ERR_INVALID, "communicator without RCCL needs a connected p2p exchange");
         // (the direct exchange enqueues no collective, so its loop can be polled like the 1-GPU one)
         polled = (!comm || p2p) && env_int("SAGEICP_CHUNKED", 0) == 0;
-        // (probes only: SAGEICP_MAX_ITER stops either loop early — the launch-per-iteration loop then simply runs out of launches)
+        // (probes and tests: SAGEICP_MAX_ITER stops either loop early — the launch-per-iteration loop then simply runs out of launches)
         max_it = std::min(kMaxIterations, std::max(1, env_int("SAGEICP_MAX_ITER", kMaxIterations)));
         // (the counters behind sum_candidates / pairs_evaluated cost ~45 vector instructions per pass, a memset and a
         // launch per frame: a caller that wants the other statistics only — bench.py's timed region — switches them off)
