@@ -567,6 +567,76 @@ int sageicp_get_correspondences_device(const sageicp_map *map, const sageicp_dev
                                        const sageicp_device_points *tgt_out /* or NULL */,
                                        int64_t *query_idx_out /* device, or NULL */, uint64_t idx_cap,
                                        void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
+
+/* ---- registration quality (quality.hip) -------------------------------------------------------------------------------
+ * How good a pose is, from one fused pass on the device behind the search: what Open3D's registration result calls
+ * fitness, inlier_rmse and the information matrix, the Gauss-Newton step still left at the pose, a covariance for
+ * nav_msgs/Odometry, and — for a semantic ICP — which classes produced the pairs and how the pairs split by the label
+ * rule of core/VoxelHashMap.cpp:88.
+ *
+ * Inputs: a map, a frame of n rows, an optional pose applied to the rows exactly as sageicp_get_correspondences_device
+ * applies its pose, max_correspondence_distance, kernel (k) and sem_th.  The accepted pairs are exactly those of
+ * GetCorrespondences for the same arguments: the same search, the same acceptance test, query order.
+ * For an accepted pair with moved query s (label ls) and map point q (label lq):
+ *     r = s - q,   e = |r|^2,   w = k^2 / (k + e)^2,   J = [ I | -hat(s) ]            (core/Registration.cpp:59-94)
+ * Sums over the accepted pairs: n_pairs; sum_r2 = sum e; sum_w = sum w; sum_w_r2 = sum w e; JTJ = sum w J^T J (6x6,
+ * row-major); JTr = sum w J^T r; info = sum J^T J, unweighted (Open3D's information matrix).
+ * Derived on the host in fp64 from the sums:
+ *     fitness = n_pairs / n_queries;   rmse = sqrt(sum_r2 / n_pairs), 0 without pairs;
+ *     step = -JTJ^-1 JTr, the Gauss-Newton step still left at this pose, and step_norm its 2-norm;
+ *     covariance = s2 JTJ^-1 with s2 = sum_w_r2 / (3 n_pairs - 6), in the tangent the loop composes with,
+ *         T <- exp(x) T, x = (upsilon, omega) (Registration.cpp:135);
+ *     covariance_pose = G covariance G^T with G = [[I, -hat(t)], [0, I]], t the pose's translation (0 without a pose):
+ *         the covariance of the pose's own translation and world-axis rotation (dt = upsilon - hat(t) omega,
+ *         dtheta = omega), row-major in the order x, y, z, rot x, rot y, rot z: nav_msgs/Odometry.pose.covariance.
+ * covariance_valid = 1 only if n_pairs >= 3 and the Cholesky factorisation of JTJ has six positive pivots, each above
+ * 2^-26 of its diagonal entry (a pivot far below is the rounding of a zero: collinear pairs; one at the bound keeps half of
+ * fp64's digits — a 30 m scene at UTM coordinates lies below it: register in a local frame for a covariance there);
+ * otherwise step, step_norm and the two covariances are zero and the flag is 0.
+ * Classes: the class of a query is static_cast<int>(ls); classes 0 .. 255 are counted per class (class_queries: every
+ * query; class_pairs, class_sum_r2: the accepted ones), anything else in other_*.  The split of the pairs:
+ * pairs_same_label: (int)lq == (int)ls; pairs_unlabelled: not same and (int)(lq * ls) == 0; pairs_cross_label: the rest.
+ * valid = 0 for an empty map or n == 0: everything else is zero then, and the call returns SAGEICP_OK.
+ * Bits: the results depend on the rows, their order and the arguments, and on nothing else: two calls, the host-rows
+ * entry, the device-frame entry on the same float64 rows and the pipeline's evaluation of the same rows agree bit for
+ * bit.  Sums are fp64 (no fixed-point range: coordinates of any finite size keep their relative accuracy). */
+typedef struct sageicp_quality {
+    double fitness, rmse, step_norm;
+    double sum_r2, sum_w, sum_w_r2;
+    double step[6];
+    double JTr[6];
+    double JTJ[36];
+    double info[36];
+    double covariance[36];
+    double covariance_pose[36];
+    double class_sum_r2[256];
+    double other_sum_r2;
+    uint64_t n_queries, n_pairs;
+    uint64_t pairs_same_label, pairs_unlabelled, pairs_cross_label;
+    uint64_t other_queries, other_pairs;
+    uint32_t class_queries[256];
+    uint32_t class_pairs[256];
+    int32_t valid, covariance_valid;
+} sageicp_quality;                                                 /* 5464 bytes, no padding */
+/* Refused with SAGEICP_ERR_INVALID before any device work: a null map or out; a pose that is not finite; a kernel that is
+ * not finite or not above 0; rows that are not finite (the host scan). */
+int sageicp_registration_quality(const sageicp_map *map, const double *xyzl, uint64_t n,
+                                 const double pose[7] /* NULL = identity */, double max_correspondence_distance,
+                                 double kernel, double sem_th, sageicp_quality *out);
+/* The same on a frame in device memory: every layout and dtype of sageicp_get_correspondences_device, through the same
+ * checks of the caller's memory; non-finite rows are refused by the sort's verdict.  Synchronous.  The map stays where it
+ * is: a resident map stays resident.  A map that spans several devices answers on the first. */
+int sageicp_registration_quality_device(const sageicp_map *map, const sageicp_device_frame *frame,
+                                        const double pose[7] /* NULL = identity */, double max_correspondence_distance,
+                                        double kernel, double sem_th, void *stream /* hipStream_t; NULL = null stream */,
+                                        sageicp_quality *out);
+/* In the pipeline: off by default.  When on, every register call evaluates the report for its source cloud at the NEW
+ * pose, with that frame's 3 sigma and sigma / 3, against the map BEFORE Update() inserts the frame — after the
+ * registration, outside the icp_s and total_s it reports.  The first frame (empty map) and an empty message give
+ * valid = 0; so does a register call that fails, and sageicp_pipeline_reinitialize. */
+int sageicp_pipeline_set_quality(sageicp_pipeline *p, int enable);
+int sageicp_pipeline_quality(const sageicp_pipeline *p, sageicp_quality *out);
+
 int sageicp_pipeline_reinitialize(sageicp_pipeline *p);          /* pipeline/sageICP.hpp:94-99 */
 uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p);  /* poses().size() */
 int sageicp_pipeline_pose(const sageicp_pipeline *p, uint64_t index, double pose_out[7]);

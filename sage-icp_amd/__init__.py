@@ -140,6 +140,40 @@ class MsgField(C.Structure):
 MSG_POINT_STEP = 21      # SAGEICP_MSG_POINT_STEP
 
 
+class Quality(C.Structure):
+    """sageicp_quality: how good a pose is — fitness, rmse, the Gauss-Newton system and the step still left, covariances,
+    and which classes produced the pairs (include/sageicp.h states every field)"""
+    _fields_ = [("fitness", C.c_double), ("rmse", C.c_double), ("step_norm", C.c_double),
+                ("sum_r2", C.c_double), ("sum_w", C.c_double), ("sum_w_r2", C.c_double),
+                ("step", C.c_double * 6), ("JTr", C.c_double * 6),
+                ("JTJ", C.c_double * 36), ("info", C.c_double * 36),
+                ("covariance", C.c_double * 36), ("covariance_pose", C.c_double * 36),
+                ("class_sum_r2", C.c_double * 256), ("other_sum_r2", C.c_double),
+                ("n_queries", C.c_uint64), ("n_pairs", C.c_uint64),
+                ("pairs_same_label", C.c_uint64), ("pairs_unlabelled", C.c_uint64), ("pairs_cross_label", C.c_uint64),
+                ("other_queries", C.c_uint64), ("other_pairs", C.c_uint64),
+                ("class_queries", C.c_uint32 * 256), ("class_pairs", C.c_uint32 * 256),
+                ("valid", C.c_int32), ("covariance_valid", C.c_int32)]
+    _MATRICES = ("JTJ", "info", "covariance", "covariance_pose")
+
+    def as_dict(self):
+        """plain Python numbers; the four matrices as (6, 6) numpy arrays, the other arrays as 1-D numpy arrays"""
+        d = {}
+        for k, ty in self._fields_:
+            v = getattr(self, k)
+            if k in self._MATRICES:
+                v = np.array(v[:], dtype=np.float64).reshape(6, 6)
+            elif hasattr(ty, "_length_"):
+                v = np.array(v[:], dtype=np.uint32 if ty._type_ is C.c_uint32 else np.float64)
+            d[k] = v
+        d["valid"], d["covariance_valid"] = bool(self.valid), bool(self.covariance_valid)
+        return d
+
+
+QUALITY_BYTES = 5464     # sizeof(sageicp_quality)
+assert C.sizeof(Quality) == QUALITY_BYTES
+
+
 class OccupancyParams(C.Structure):
     """sageicp_occupancy_params: the bird's-eye grid of key-frame selection (bounds of x, y, z; H rows, W columns)"""
     _fields_ = [("bounds", (C.c_double * 2) * 3), ("occ_h", C.c_int32), ("occ_w", C.c_int32), ("overlap_th", C.c_double)]
@@ -255,6 +289,12 @@ _SIGNATURES = [
     ("sageicp_get_correspondences_device", C.c_int,
      [C.c_void_p, C.POINTER(DeviceFrame), _dp, C.c_double, C.c_double, C.POINTER(DevicePoints), C.POINTER(DevicePoints),
       C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
+    ("sageicp_registration_quality", C.c_int,
+     [C.c_void_p, _dp, C.c_uint64, _dp, C.c_double, C.c_double, C.c_double, C.POINTER(Quality)]),
+    ("sageicp_registration_quality_device", C.c_int,
+     [C.c_void_p, C.POINTER(DeviceFrame), _dp, C.c_double, C.c_double, C.c_double, C.c_void_p, C.POINTER(Quality)]),
+    ("sageicp_pipeline_set_quality", C.c_int, [C.c_void_p, C.c_int]),
+    ("sageicp_pipeline_quality", C.c_int, [C.c_void_p, C.POINTER(Quality)]),
     ("sageicp_align_clouds", C.c_int, [_dp, _dp, C.c_uint64, C.c_double, _dp, _dp, _dp, C.c_int]),
     ("sageicp_transform_points", C.c_int, [_dp, _dp, C.c_uint64, C.c_int]),
     ("sageicp_register_frame", C.c_int,
@@ -987,6 +1027,31 @@ class VoxelHashMap:
             return src[:k].copy(), tgt[:k].copy(), idx[:k].copy()
         return src[:k].copy(), tgt[:k].copy()
 
+    def RegistrationQuality(self, pts, max_correspondance_distance, kernel, th, pose=None, labels=None):
+        """The quality report (Quality) of `pts` at `pose` against this map: fitness, rmse, the Gauss-Newton system over
+        the pairs GetCorrespondences accepts for the same arguments, the step still left, covariances, class tables.
+        `pts` as numpy (n, 4) rows (sageicp_registration_quality) or a torch tensor on the map's GPU in the layouts
+        RegisterFrame takes, `labels` as there (sageicp_registration_quality_device; ordered on the device's current
+        torch stream).  With pose= (qx, qy, qz, qw, tx, ty, tz) the rows are first moved as transform_points moves
+        them.  Synchronous; a resident map stays resident."""
+        pp = None
+        if pose is not None:
+            pose_a, pp = _d(pose)
+            if pose_a.size != 7:
+                raise ValueError("a pose is (qx, qy, qz, qw, tx, ty, tz)")
+        q = Quality()
+        if _is_device_tensor(pts):
+            f, stream = _device_rows(DeviceFrame, pts, labels, self.device, _FRAME_WORDS)
+            _check(lib().sageicp_registration_quality_device(self._h, C.byref(f), pp, max_correspondance_distance, kernel,
+                                                             th, stream, C.byref(q)))
+            return q
+        if labels is not None:
+            raise ValueError("labels= is for a frame that is a torch tensor on a GPU")
+        pts, fp = _d(pts)
+        _check(lib().sageicp_registration_quality(self._h, fp, pts.reshape(-1, 4).shape[0], pp,
+                                                  max_correspondance_distance, kernel, th, C.byref(q)))
+        return q
+
     def _correspondences_device(self, pts, max_dist, th, with_index, labels, pose, dtype):
         # everything that can be wrong with the arguments raises ValueError before any call into the library
         f, stream = _device_rows(DeviceFrame, pts, labels, self.device, _FRAME_WORDS)
@@ -1114,6 +1179,17 @@ class SageICP:
         lm = (C.c_int * max(len(landmark_labels), 1))(*landmark_labels)
         _check(lib().sageicp_pipeline_set_dynamic_vehicle_filter(self._h, 1 if enable else 0, dy_th, voxid, lm,
                                                                  len(landmark_labels)))
+
+    def set_quality(self, enable=True):
+        """sageicp_pipeline_set_quality: every RegisterFrame evaluates the quality report of its source cloud at the new
+        pose against the map before the update (quality()).  Off by default."""
+        _check(lib().sageicp_pipeline_set_quality(self._h, 1 if enable else 0))
+
+    def quality(self):
+        """the last RegisterFrame's Quality (valid == 0: none — quality off, the first frame, an empty or failed call)"""
+        q = Quality()
+        _check(lib().sageicp_pipeline_quality(self._h, C.byref(q)))
+        return q
 
     def set_key_frames(self, enable=True, bounds=KEY_FRAME_BOUNDS, occ_size=KEY_FRAME_OCC_SIZE, overlap=KEY_FRAME_OVERLAP):
         """Key-frame selection by occupancy overlap for every frame registered (sageicp_pipeline_set_key_frames; the

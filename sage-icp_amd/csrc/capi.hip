@@ -65,6 +65,181 @@ int register_resident(sageicp_map &m, const Point4 *d_frame, uint64_t n, int dev
     return run_icp(m, d_frame, n, init, max_dist, kernel, sem_th, comm, pose_out, stats, us_upload, t0);
 }
 
+// ---- registration quality (quality.h) ---------------------------------------------------------------------------------
+static_assert(sizeof(sageicp_quality) == 5464, "sageicp_quality: doubles first, no padding (include/sageicp.h)");
+static_assert(kQualClasses == 256, "the class tables of sageicp_quality");
+
+// A pivot of the Cholesky factorisation counts as positive above this share of its diagonal entry.  Its rounding error
+// is a few u of that entry: at the bound it keeps about half of fp64's digits, far below it is the rounding of a zero
+// (collinear pairs).  A 30 m scene at UTM coordinates (|s| ~ 5.5e6 m) has pivots of ~2^-40: no covariance there.
+constexpr double kQualPivotBound = 1.0 / 67108864.0;                // 2^-26
+
+// the report from what the kernels left: everything derived, on the host in fp64 (include/sageicp.h)
+static void quality_finish(const QualityRaw &r, uint64_t n, const double *pose, sageicp_quality *q) {
+    std::memset(q, 0, sizeof(*q));
+    q->valid = 1;
+    q->n_queries = n;
+    q->n_pairs = r.counts[kQPairs];
+    q->pairs_same_label = r.counts[kQSame];
+    q->pairs_unlabelled = r.counts[kQUnlabelled];
+    q->pairs_cross_label = r.counts[kQCross];
+    q->other_queries = r.counts[kQOtherQueries];
+    q->other_pairs = r.counts[kQOtherPairs];
+    for (int c = 0; c < kQualClasses; ++c) {
+        q->class_queries[c] = static_cast<uint32_t>(r.class_queries[c]);
+        q->class_pairs[c] = static_cast<uint32_t>(r.class_pairs[c]);
+        q->class_sum_r2[c] = r.class_r2[c];
+    }
+    q->other_sum_r2 = r.class_r2[kQualClasses];
+    q->sum_r2 = r.real[kQR2];
+    q->sum_w = r.real[kW];
+    q->sum_w_r2 = r.real[kQWR2];
+    assemble_normal_equations(r.real, q->JTJ, q->JTr);
+    {
+        // sum J^T J without weights: the same assembly over n_pairs, sum s, sum s s^T
+        double S[kNumSums] = {}, unused[6];
+        S[kW] = static_cast<double>(q->n_pairs);
+        S[kWsx] = r.real[kQSx]; S[kWsy] = r.real[kQSy]; S[kWsz] = r.real[kQSz];
+        S[kWxx] = r.real[kQSxx]; S[kWxy] = r.real[kQSxy]; S[kWxz] = r.real[kQSxz];
+        S[kWyy] = r.real[kQSyy]; S[kWyz] = r.real[kQSyz]; S[kWzz] = r.real[kQSzz];
+        assemble_normal_equations(S, q->info, unused);
+    }
+    const double np = static_cast<double>(q->n_pairs);
+    q->fitness = np / static_cast<double>(n);
+    q->rmse = q->n_pairs ? std::sqrt(q->sum_r2 / np) : 0.0;
+    if (q->n_pairs < 3) return;
+    // JTJ = L L^T; the pivots are the squares of L's diagonal
+    double L[6][6] = {};
+    for (int j = 0; j < 6; ++j) {
+        double d = q->JTJ[j * 6 + j];
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        if (!(d > kQualPivotBound * q->JTJ[j * 6 + j]) || !std::isfinite(d)) return;
+        L[j][j] = std::sqrt(d);
+        for (int i = j + 1; i < 6; ++i) {
+            double v = q->JTJ[i * 6 + j];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / L[j][j];
+        }
+    }
+    double Li[6][6] = {};                     // L^-1, lower triangular
+    for (int j = 0; j < 6; ++j) {
+        Li[j][j] = 1.0 / L[j][j];
+        for (int i = j + 1; i < 6; ++i) {
+            double v = 0.0;
+            for (int k = j; k < i; ++k) v -= L[i][k] * Li[k][j];
+            Li[i][j] = v / L[i][i];
+        }
+    }
+    double inv[6][6];                         // JTJ^-1 = L^-T L^-1
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j <= i; ++j) {
+            double v = 0.0;
+            for (int k = i; k < 6; ++k) v += Li[k][i] * Li[k][j];
+            inv[i][j] = inv[j][i] = v;
+        }
+    double y[6], x[6], norm2 = 0.0;           // step = -L^-T (L^-1 JTr)
+    for (int i = 0; i < 6; ++i) {
+        double v = -q->JTr[i];
+        for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+        y[i] = v / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {
+        double v = y[i];
+        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
+        x[i] = v / L[i][i];
+    }
+    const double s2 = q->sum_w_r2 / (3.0 * np - 6.0);
+    bool finite = std::isfinite(s2);
+    for (int i = 0; i < 6; ++i) {
+        finite = finite && std::isfinite(x[i]);
+        for (int j = 0; j < 6; ++j) finite = finite && std::isfinite(inv[i][j]);
+    }
+    if (!finite) return;
+    for (int i = 0; i < 6; ++i) {
+        q->step[i] = x[i];
+        norm2 += x[i] * x[i];
+        for (int j = 0; j < 6; ++j) q->covariance[i * 6 + j] = s2 * inv[i][j];
+    }
+    q->step_norm = std::sqrt(norm2);
+    // G C G^T, G = [[I, -hat(t)], [0, I]]: rows 0..2 of G hold two more entries each, rows 3..5 none
+    const double t[3] = {pose ? pose[4] : 0.0, pose ? pose[5] : 0.0, pose ? pose[6] : 0.0};
+    const double G[3][3] = {{0.0, t[2], -t[1]}, {-t[2], 0.0, t[0]}, {t[1], -t[0], 0.0}};      // -hat(t)
+    double M[6][6];                           // G C
+    for (int a = 0; a < 6; ++a)
+        for (int j = 0; j < 6; ++j) {
+            double v = q->covariance[a * 6 + j];
+            if (a < 3)
+                for (int k = 0; k < 3; ++k)
+                    if (k != a) v += G[a][k] * q->covariance[(3 + k) * 6 + j];
+            M[a][j] = v;
+        }
+    for (int a = 0; a < 6; ++a)
+        for (int b = 0; b < 6; ++b) {
+            double v = M[a][b];
+            if (b < 3)
+                for (int k = 0; k < 3; ++k)
+                    if (k != b) v += M[a][3 + k] * G[b][k];
+            q->covariance_pose[a * 6 + b] = v;
+        }
+    q->covariance_valid = 1;
+}
+
+int quality_of_scratch_rows(sageicp_map &m, uint64_t n, const double *pose, double max_dist, double kernel, double sem_th,
+                            sageicp_quality *out) {
+    Scratch &sc = m.sc;
+    int rc;
+    if ((rc = sc.reserve_nn(n))) return rc;
+    if ((rc = sc.reserve_sort(n))) return rc;
+    if ((rc = sc.reserve_quality(n))) return rc;
+    hipStream_t s = sc.stream.get();
+    // the rows moved by the pose (k_tf: sageicp_transform_points' point action) and sorted, as
+    // sageicp_get_correspondences_device prepares them; the sort's first pass refuses non-finite rows
+    double I[7];
+    identity_pose(I);
+    fill_state(sc.h_state.data(), pose ? pose : I);
+    HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
+    if (pose) launch_tf(sc.d_frame.data(), static_cast<int>(n), sc.d_state.data(), s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(sort_frame(sc.d_frame.data(), sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), false, false,
+                      m.host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(),
+                      sc.d_sort_temp.capacity(), s));
+    HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (sc.h_state.data()->bad_input)
+        return fail(SAGEICP_ERR_INVALID, "RegistrationQuality: a coordinate or label of a row is not finite (NaN / Inf)");
+    // the search (rows, k_icp search-only), the acceptance by query (k_corr_flag), the pass
+    HIPCHK(hipMemsetAsync(sc.d_qual_raw.data(), 0, sizeof(QualityRaw), s));
+    const int lw = icp_lw(n, sparse_voxels(m));
+    if ((rc = m.dev.ensure_cand(wants_filter(m, n, sem_th), s))) return rc;
+    const IcpParams ip = icp_params(m, sc.d_sorted.data(), n, sem_th, lw, 0);
+    launch_rows(ip, s);
+    launch_icp(ip, lw, false, s);
+    HIPCHK(hipGetLastError());
+    CorrespondArgs c{};
+    c.n = static_cast<int>(n);
+    c.sorted = sc.d_sorted.data();
+    c.perm = sc.d_vals.data() + n;
+    c.nn = sc.d_nn.data();
+    c.pts = m.dev.search_view().pts;
+    c.accept_r2 = accept_threshold(max_dist);
+    c.by_query = sc.d_by_query.data();
+    launch_corr_flag(c, s);
+    QualityArgs a{};
+    a.n = static_cast<int>(n);
+    a.frame = sc.d_frame.data();
+    a.by_query = sc.d_by_query.data();
+    a.pts = c.pts;
+    a.kernel = kernel;
+    a.slabs = sc.d_qual_slabs.data();
+    a.out = sc.d_qual_raw.data();
+    launch_quality(a, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sc.h_qual_raw.data(), sc.d_qual_raw.data(), sizeof(QualityRaw), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    quality_finish(*sc.h_qual_raw.data(), n, pose, out);
+    return SAGEICP_OK;
+}
+
 }  // namespace sageicp_impl
 
 // =============================================================================================
@@ -570,6 +745,63 @@ int sageicp_get_correspondences_device(const sageicp_map *map, const sageicp_dev
                                          "(static_cast<int64_t>(label) out of its range)");
     *n_out = h_words[0];
     return SAGEICP_OK;
+}
+
+// ---- registration quality (quality.hip) --------------------------------------------------------------------------------
+// what both entries refuse before they look at the rows
+static int check_quality_args(const sageicp_map *map, const double *pose, double kernel, const sageicp_quality *out) {
+    if (!map) return fail(SAGEICP_ERR_INVALID, "RegistrationQuality: map is NULL");
+    if (!out) return fail(SAGEICP_ERR_INVALID, "RegistrationQuality: out is NULL");
+    if (pose && !finite_n(pose, 7)) return fail(SAGEICP_ERR_INVALID, "RegistrationQuality: the pose is not finite");
+    if (!(std::isfinite(kernel) && kernel > 0.0))
+        return fail(SAGEICP_ERR_INVALID, "RegistrationQuality: kernel must be finite and above 0");
+    return SAGEICP_OK;
+}
+
+int sageicp_registration_quality(const sageicp_map *map, const double *xyzl, uint64_t n, const double pose[7],
+                                 double max_dist, double kernel, double sem_th, sageicp_quality *out) {
+    int rc = check_quality_args(map, pose, kernel, out);
+    if (rc) return rc;
+    if (n && !xyzl) return fail(SAGEICP_ERR_INVALID, "RegistrationQuality: xyzl is NULL");
+    if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "RegistrationQuality: too many rows (2^26 - 4 max)");
+    if (!all_finite(xyzl, n))
+        return fail(SAGEICP_ERR_INVALID, "RegistrationQuality: a coordinate or label of a row is not finite (NaN / Inf)");
+    std::memset(out, 0, sizeof(*out));
+    sageicp_map &m = internal(map);
+    if (n == 0 || m.empty()) return SAGEICP_OK;
+    if ((rc = refresh_mirror(m))) return rc;          // (makes the device current; a resident map stays resident)
+    Scratch &sc = m.sc;
+    if ((rc = sc.reserve_frame(n))) return rc;
+    HIPCHK(hipMemcpyAsync(sc.d_frame.data(), xyzl, n * sizeof(Point4), hipMemcpyHostToDevice, sc.stream.get()));
+    return quality_of_scratch_rows(m, n, pose, max_dist, kernel, sem_th, out);
+}
+
+int sageicp_registration_quality_device(const sageicp_map *map, const sageicp_device_frame *frame, const double pose[7],
+                                        double max_dist, double kernel, double sem_th, void *stream,
+                                        sageicp_quality *out) {
+    int rc = check_quality_args(map, pose, kernel, out);
+    if (rc) return rc;
+    if (!frame) return fail(SAGEICP_ERR_INVALID, "RegistrationQuality: frame is NULL");
+    if ((rc = check_frame_layout(frame))) return rc;
+    // where the memory lives, and the stream
+    if ((rc = check_device_frame(frame, nullptr, stream, map->device))) return rc;
+    if ((rc = check_stream(stream, map->device))) return rc;
+    std::memset(out, 0, sizeof(*out));
+    sageicp_map &m = internal(map);
+    const uint64_t n = frame->n;
+    if (n == 0 || m.empty()) return SAGEICP_OK;
+    if ((rc = refresh_mirror(m))) return rc;          // (makes the device current)
+    Scratch &sc = m.sc;
+    if ((rc = sc.reserve_frame(n))) return rc;
+    hipStream_t s = sc.stream.get();
+    // the work that wrote the frame goes first; the frame, whole, into the library's rows, and waited for also when
+    // the enqueue failed: from here on nothing reads the caller's memory
+    if ((rc = stream_after_caller(m.out.ev_caller, static_cast<hipStream_t>(stream), s))) return rc;
+    launch_ingest(ingest_args(*frame), sc.d_frame.data(), s);
+    const hipError_t launched = hipGetLastError(), waited = hipStreamSynchronize(s);
+    HIPCHK(launched);
+    HIPCHK(waited);
+    return quality_of_scratch_rows(m, n, pose, max_dist, kernel, sem_th, out);
 }
 
 // ---- AlignClouds ------------------------------------------------------------------------------

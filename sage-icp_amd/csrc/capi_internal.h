@@ -2,7 +2,7 @@
 // capi_outputs.hip, caller_mem.hip, map_device.hip, capi_run.hip, prep.hip): error channel, tuning knobs, the
 // per-handle device scratch, the pipeline's frame source and buffers (prep.h) and its prefetch state (prefetch.h), the
 // checks of a caller's device memory (caller_mem.h), the HBM copy of a map (map_device.h), the way out (outputs.h), what
-// follows the search of GetCorrespondences on the device (correspond.h), the
+// follows the search of GetCorrespondences on the device (correspond.h), the registration quality pass (quality.h), the
 // opaque handles of include/sageicp.h except the pipeline's (capi_pipeline.hip) and the one place where the ABI's
 // `const sageicp_map *` becomes the reference the internals take (internal()).  Not part of the C ABI.
 #pragma once
@@ -33,6 +33,7 @@
 #include "kernels.h"
 #include "egress.h"
 #include "correspond.h"
+#include "quality.h"
 #include "msg.h"
 #include "map_update.h"
 #include "metrics.hpp"
@@ -200,6 +201,10 @@ struct Scratch {
     DevBuf<uint32_t> d_corr_counts;
     DevBuf<unsigned long long> d_corr_words;
     PinnedBuf<unsigned long long> h_corr_words;
+    // registration quality (quality.h): the workgroups' slabs, what the kernels leave and its pinned landing place
+    DevBuf<double> d_qual_slabs;
+    DevBuf<QualityRaw> d_qual_raw;
+    PinnedBuf<QualityRaw> h_qual_raw;
 
     ~Scratch() { wait(); }         // (then the members go: nothing runs on the streams any more)
     // waits for both streams, with the device current (a scratch that never created a stream calls nothing)
@@ -306,6 +311,13 @@ struct Scratch {
         if (words > d_corr_counts.capacity()) HIPCHK(d_corr_counts.reserve(words + words / 4 + 16));
         if (!d_corr_words) HIPCHK(d_corr_words.reserve(2));
         if (!h_corr_words) HIPCHK(h_corr_words.reserve(2));
+        return SAGEICP_OK;
+    }
+    int reserve_quality(size_t n) {
+        if (n > d_by_query.capacity()) HIPCHK(d_by_query.reserve(n + n / 4 + 1024));
+        if (!d_qual_slabs) HIPCHK(d_qual_slabs.reserve(kQualSlabDoubles));
+        if (!d_qual_raw) HIPCHK(d_qual_raw.reserve(1));
+        if (!h_qual_raw) HIPCHK(h_qual_raw.reserve(1));
         return SAGEICP_OK;
     }
     int reserve_partials(size_t blocks) {
@@ -423,6 +435,9 @@ int load_rccl();
 int register_resident(sageicp_map &m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
                       double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
                       sageicp_stats *stats);
+// capi.hip: the quality report of the n rows in m.sc.d_frame (not yet moved by `pose`; written on m.sc's stream)
+int quality_of_scratch_rows(sageicp_map &m, uint64_t n, const double *pose, double max_dist, double kernel, double sem_th,
+                            sageicp_quality *out);
 // map_device.hip: the handle's device made current, its stream and host copy handed to MapDevice
 int refresh_mirror(sageicp_map &m);
 int ensure_host(sageicp_map &m);

@@ -52,6 +52,10 @@ struct sageicp_pipeline {
         }
         KeyFrames() { clear(); }
     } kf;
+    // the registration quality report (sageicp_pipeline_set_quality, quality.hip): off by default; `quality` is the last
+    // register call's, valid = 0 when there is none
+    bool quality_on = false;
+    sageicp_quality quality{};
     // (after the buffers that work on their streams touches — out, kf's: the Preps wait and go first)
     Prep prep[2];
     // (after the Preps: its worker runs voxelize_into on prep[cur ^ 1], and is joined before either goes)
@@ -205,6 +209,24 @@ static int pipeline_register(sageicp_pipeline *p, const FrameSource &src, double
             return register_resident(*p->impl.map, p->prep[p->cur].d_src.data(), p->prep[p->cur].kept_levels[1],
                                      p->device, guess, max_dist, kernel, sem_th, nullptr, pose, stats);
         }
+        // the quality of the new pose against the map before Update(): the source rows copied into the map handle's
+        // frame buffer (on a multi-device map: rank 0's) and evaluated there as the stand-alone entry evaluates them
+        int evaluate_quality(const double pose[7], double max_dist, double kernel, double sem_th) {
+            if (!p->quality_on) return SAGEICP_OK;
+            sageicp_map &m = *p->impl.map;
+            const uint64_t n = p->prep[p->cur].kept_levels[1];
+            if (n == 0 || m.empty()) return SAGEICP_OK;            // (valid stays 0)
+            if (!(std::isfinite(kernel) && kernel > 0.0) || !finite_n(pose, 7)) return SAGEICP_OK;
+            int rc = refresh_mirror(m);
+            if (rc) return rc;
+            if ((rc = m.sc.reserve_frame(n))) return rc;
+            HIPCHK(hipMemcpyAsync(m.sc.d_frame.data(), p->prep[p->cur].d_src.data(), n * sizeof(Point4),
+                                  hipMemcpyDeviceToDevice, m.sc.stream.get()));
+            sageicp_quality q;
+            if ((rc = quality_of_scratch_rows(m, n, pose, max_dist, kernel, sem_th, &q))) return rc;
+            p->quality = q;
+            return SAGEICP_OK;
+        }
         int update_map(const double pose[7]) {
             const Prep &pr = p->prep[p->cur];
             const uint64_t n_fd = pr.kept_levels[0];
@@ -231,7 +253,9 @@ static int pipeline_register(sageicp_pipeline *p, const FrameSource &src, double
 // Every register entry drops the last source first: a call that is refused before it reaches pipeline_register (a bad
 // argument, a device frame or timestamps that fail their checks) leaves 0 rows, as one that fails later does.
 static void drop_source(sageicp_pipeline *p) {
-    if (p) p->src_n = 0;
+    if (!p) return;
+    p->src_n = 0;
+    p->quality = sageicp_quality{};          // ... and no report
 }
 int sageicp_pipeline_register_frame(sageicp_pipeline *p, const double *frame, uint64_t n,
                                     double pose_out[7], double *icp_s, double *total_s,
@@ -413,6 +437,7 @@ int sageicp_pipeline_reinitialize(sageicp_pipeline *p) {
     if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
     p->impl.reinitialize();
     p->src_n = 0;
+    p->quality = sageicp_quality{};
     return SAGEICP_OK;
 }
 uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p) { return p ? p->impl.poses.size() : 0; }
@@ -423,6 +448,18 @@ int sageicp_pipeline_pose(const sageicp_pipeline *p, uint64_t i, double out[7]) 
 }
 const sageicp_map *sageicp_pipeline_local_map(const sageicp_pipeline *p) {
     return p ? p->impl.map : nullptr;
+}
+
+int sageicp_pipeline_set_quality(sageicp_pipeline *p, int enable) {
+    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
+    p->quality_on = enable != 0;
+    p->quality = sageicp_quality{};
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_quality(const sageicp_pipeline *p, sageicp_quality *out) {
+    if (!p || !out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    *out = p->quality;
+    return SAGEICP_OK;
 }
 
 int sageicp_pipeline_set_key_frames(sageicp_pipeline *p, int enable, const sageicp_occupancy_params *params) {

@@ -41,5 +41,7 @@ struct CorrespondArgs {
 inline uint32_t correspond_blocks(int n) { return static_cast<uint32_t>((n + kCorrBlock - 1) / kCorrBlock); }
 // flag, count, scan, write: enqueued on s (n > 0)
 void launch_correspond(const CorrespondArgs &a, hipStream_t s);
+// the flag alone: by_query for a pass that needs no compaction (quality.h); reads n, sorted, perm, nn, pts, accept_r2
+void launch_corr_flag(const CorrespondArgs &a, hipStream_t s);
 
 }  // namespace sageicp

@@ -103,6 +103,11 @@ __global__ __launch_bounds__(256) void k_corr_write(CorrespondArgs a, W w) {
     }
 }
 
+void launch_corr_flag(const CorrespondArgs &a, hipStream_t s) {
+    if (a.n <= 0) return;
+    hipLaunchKernelGGL(k_corr_flag, dim3(correspond_blocks(a.n)), dim3(256), 0, s, a);
+}
+
 void launch_correspond(const CorrespondArgs &a, hipStream_t s) {
     if (a.n <= 0) return;
     const uint32_t blocks = correspond_blocks(a.n);

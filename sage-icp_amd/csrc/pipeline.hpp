@@ -75,6 +75,8 @@ public:
     //                                        pipeline/sageICP.cpp:57-67,97-101); both clouds stay
     //                                        on the device
     //   be.register_source(guess, max_corr, kernel, sem_th, pose, stats)    RegisterFrame(source, ...)
+    //   be.evaluate_quality(pose, max_corr, kernel, sem_th)    the registration quality report of the source at the new
+    //                                        pose, against the map before the update (quality.hip; a no-op when off)
     //   be.update_map(pose)                  local_map_.Update(frame_downsample, pose)
     // deskew: RegisterFrame(frame, timestamps) with config_.deskew (the source's read_stamps); false: the one-argument
     // RegisterFrame(frame), which never deskews.
@@ -116,6 +118,9 @@ public:
         Pose7 ginv;
         se3_inv(guess.v, ginv.v);
         se3_mul(ginv.v, new_pose.v, model_deviation.v);       // UpdateModelDeviation
+        // the quality of new_pose against the map as the registration saw it (outside the times reported below)
+        rc = be.evaluate_quality(new_pose.v, 3.0 * sigma, sigma / 3.0, sem_th);
+        if (rc) return rc;
         rc = be.update_map(new_pose.v);
         if (rc) return rc;
         poses.push_back(new_pose);
