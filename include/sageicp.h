@@ -67,7 +67,11 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * sageicp_occupancy_grid, sageicp_occupancy_grid_device; then PointCloud2 payloads — sageicp_msg_layout, sageicp_msg_colors,
  * SAGEICP_MSG_*, sageicp_pipeline_register_frame_msg / _msg_device, sageicp_pipeline_source_msg / _msg_device,
  * sageicp_map_pointcloud_msg / _msg_device, sageicp_msg_output_fields; then correspondences of a device frame —
- * sageicp_get_correspondences_device (additions only: no existing struct or entry changed). */
+ * sageicp_get_correspondences_device; then the registration quality report — sageicp_quality,
+ * sageicp_registration_quality / _device, sageicp_pipeline_set_quality, sageicp_pipeline_quality; then a batch of
+ * candidate poses and relocalisation — sageicp_pose_score, sageicp_score_poses / _device, sageicp_relocalize_params,
+ * sageicp_relocalize_info, sageicp_relocalize_candidates, sageicp_relocalize / _device (additions only: no existing
+ * struct or entry changed). */
 #define SAGEICP_ABI_VERSION 4
 
 /* Filled by sageicp_register_frame*.  Times are microseconds. */
@@ -636,6 +640,82 @@ int sageicp_registration_quality_device(const sageicp_map *map, const sageicp_de
  * valid = 0; so does a register call that fails, and sageicp_pipeline_reinitialize. */
 int sageicp_pipeline_set_quality(sageicp_pipeline *p, int enable);
 int sageicp_pipeline_quality(const sageicp_pipeline *p, sageicp_quality *out);
+
+/* ---- a batch of candidate poses scored in one pass; relocalisation (score.hip) ----------------------------------------
+ * Moved by k poses, a frame of n rows is k * n independent queries against the same map: one search answers all of them,
+ * and one pass forms every candidate's sums.  out[c] holds, bit for bit, the same-named fields of
+ * sageicp_registration_quality(map, xyzl, n, poses[c], ...) — fitness, rmse, step_norm, sum_r2, sum_w, sum_w_r2, step,
+ * JTr, JTJ, n_queries, n_pairs, the three splits of the pairs, valid —, step_valid is that report's covariance_valid and
+ * score, the ranking key, is sum_w.  This holds whatever k is, whatever the other candidates are and in whatever order,
+ * and however the batch was cut into chunks.  The class tables, `info` and the covariances are not formed in the batch:
+ * ask sageicp_registration_quality at the pose that won.
+ * Chunks: the candidates are taken max(1, chunk_rows / n) at a time, chunk_rows from SAGEICP_SCORE_CHUNK_ROWS (default
+ * 2^20 rows; about 250 B of device memory per row, which stays reserved on the map handle like its other work buffers);
+ * per chunk the sort's verdict on non-finite rows is read once and the results are downloaded once.
+ * k == 0: SAGEICP_OK, nothing read or written.  An empty map or n == 0: every out[c] is zero (valid = 0), SAGEICP_OK.
+ * Refused with SAGEICP_ERR_INVALID before any device is asked (k > 0): a null map, out or poses; null rows with n > 0;
+ * k > 2^20; n > 2^26 - 4; a kernel that is not finite or not above 0; a pose entry that is not finite (the message
+ * names the candidate).  The host entry scans its rows; in both entries the sort's verdict refuses rows that are not
+ * finite once moved.  On every error nothing has been written to out.
+ * The map stays where it is: a resident map stays resident, and sageicp_map_table_stats and sageicp_map_loop_status
+ * answer after the call what they answered before it.  A map that spans several devices answers on the first. */
+typedef struct sageicp_pose_score {
+    double score;                            /* the ranking key: sum_w */
+    double fitness, rmse, step_norm;
+    double sum_r2, sum_w, sum_w_r2;
+    double step[6], JTr[6], JTJ[36];
+    uint64_t n_queries, n_pairs, pairs_same_label, pairs_unlabelled, pairs_cross_label;
+    int32_t valid, step_valid;
+} sageicp_pose_score;                                              /* 488 bytes, doubles first, no padding */
+int sageicp_score_poses(const sageicp_map *map, const double *xyzl, uint64_t n,
+                        const double *poses /* [k][7] */, uint64_t k,
+                        double max_correspondence_distance, double kernel, double sem_th,
+                        sageicp_pose_score *out /* [k] */);
+/* The same on a frame in device memory: the layout and caller-memory checks of sageicp_registration_quality_device.
+ * Synchronous. */
+int sageicp_score_poses_device(const sageicp_map *map, const sageicp_device_frame *frame,
+                               const double *poses /* host, [k][7] */, uint64_t k,
+                               double max_correspondence_distance, double kernel, double sem_th,
+                               void *stream /* hipStream_t; NULL = null stream */, sageicp_pose_score *out);
+
+/* Relocalisation: a grid of candidates around a prior, scored in one batch, the best few refined by RegisterFrame.
+ * Candidates (host code, no device needed).  Per axis, m is the largest integer >= 0 with m * step <= extent in fp64,
+ * and 0 when step <= 0 or extent < step; the indices run from -m to +m.  Candidate (a, i, j, l) is the sensor turned in
+ * place about the vertical through its own position, then shifted along the world axes:
+ *     q = q_z(a * yaw_step) (x) q_prior  (Hamilton product, not renormalised; q_z(th) = (0, 0, sin(th / 2), cos(th / 2)));
+ *     t = t_prior + (i * xy_step, j * xy_step, l * z_step);
+ * an index of 0 leaves the prior's own bits.  Order: yaw outermost, then x, then y, z innermost, each ascending.
+ * k_out always tells K; the first min(cap, K) poses are written (poses_out may be NULL with cap == 0).
+ * SAGEICP_ERR_INVALID: K > 2^20, a prior or a parameter that is not finite, refine_top > 16.
+ * sageicp_relocalize is a composition of public entries: (1) the candidates; (2) sageicp_score_poses; (3) the ranking by
+ * score, descending, ties to the lower index; (4) for the first min(refine_top, K) of them RegisterFrame from the
+ * candidate — the bits of sageicp_register_frame(map, xyzl, n, candidate, max_correspondence_distance, kernel, sem_th)
+ * — and sageicp_registration_quality at its result; the winner is the largest sum_w, ties to the better rank; (5) with
+ * refine_top == 0 the best candidate itself is returned.  quality_out is the full report at pose_out.  The frame is
+ * uploaded (ingested) once and stays on the device through all steps.  An empty map or n == 0 returns the prior,
+ * valid = 0 and refined = 0.  The ranking key cannot tell two poses apart that explain the scan equally well (the two
+ * directions of a symmetric street): keep the extents as small as the prior allows. */
+typedef struct sageicp_relocalize_params {
+    double xy_extent, xy_step, z_extent, z_step;   /* metres, world axes */
+    double yaw_extent, yaw_step;                   /* radians about world z */
+    uint32_t refine_top, reserved;                 /* 0 .. 16 */
+    double max_correspondence_distance, kernel, sem_th;
+} sageicp_relocalize_params;                                       /* 80 bytes */
+typedef struct sageicp_relocalize_info {
+    uint64_t candidates, best_candidate;   /* best_candidate: index of the candidate the returned pose came from */
+    double best_candidate_score;           /* its score before refinement */
+    uint32_t refined, winner_rank;         /* registrations run; rank (0 = best score) of the winner among them */
+    int32_t iterations, converged;         /* of the winner's registration (0, 0 with refine_top == 0) */
+    double us_score, us_refine, us_wall;
+} sageicp_relocalize_info;                                         /* 64 bytes */
+int sageicp_relocalize_candidates(const double prior[7], const sageicp_relocalize_params *params,
+                                  double *poses_out /* [cap][7] */, uint64_t cap, uint64_t *k_out);
+int sageicp_relocalize(const sageicp_map *map, const double *xyzl, uint64_t n, const double prior[7],
+                       const sageicp_relocalize_params *params, double pose_out[7],
+                       sageicp_quality *quality_out /* optional */, sageicp_relocalize_info *info /* optional */);
+int sageicp_relocalize_device(const sageicp_map *map, const sageicp_device_frame *frame, const double prior[7],
+                              const sageicp_relocalize_params *params, void *stream, double pose_out[7],
+                              sageicp_quality *quality_out, sageicp_relocalize_info *info);
 
 int sageicp_pipeline_reinitialize(sageicp_pipeline *p);          /* pipeline/sageICP.hpp:94-99 */
 uint64_t sageicp_pipeline_num_poses(const sageicp_pipeline *p);  /* poses().size() */

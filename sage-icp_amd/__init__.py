@@ -174,6 +174,48 @@ QUALITY_BYTES = 5464     # sizeof(sageicp_quality)
 assert C.sizeof(Quality) == QUALITY_BYTES
 
 
+class PoseScore(C.Structure):
+    """sageicp_pose_score: one candidate pose of a batch — bit for bit the same-named fields of the Quality of that pose
+    alone; step_valid is its covariance_valid, score (the ranking key) its sum_w"""
+    _fields_ = [("score", C.c_double), ("fitness", C.c_double), ("rmse", C.c_double), ("step_norm", C.c_double),
+                ("sum_r2", C.c_double), ("sum_w", C.c_double), ("sum_w_r2", C.c_double),
+                ("step", C.c_double * 6), ("JTr", C.c_double * 6), ("JTJ", C.c_double * 36),
+                ("n_queries", C.c_uint64), ("n_pairs", C.c_uint64),
+                ("pairs_same_label", C.c_uint64), ("pairs_unlabelled", C.c_uint64), ("pairs_cross_label", C.c_uint64),
+                ("valid", C.c_int32), ("step_valid", C.c_int32)]
+
+
+POSE_SCORE_BYTES = 488   # sizeof(sageicp_pose_score)
+assert C.sizeof(PoseScore) == POSE_SCORE_BYTES
+# the structs of ScorePoses as a numpy record array
+POSE_SCORE_DTYPE = np.dtype([("score", "<f8"), ("fitness", "<f8"), ("rmse", "<f8"), ("step_norm", "<f8"),
+                             ("sum_r2", "<f8"), ("sum_w", "<f8"), ("sum_w_r2", "<f8"),
+                             ("step", "<f8", (6,)), ("JTr", "<f8", (6,)), ("JTJ", "<f8", (6, 6)),
+                             ("n_queries", "<u8"), ("n_pairs", "<u8"),
+                             ("pairs_same_label", "<u8"), ("pairs_unlabelled", "<u8"), ("pairs_cross_label", "<u8"),
+                             ("valid", "<i4"), ("step_valid", "<i4")])
+assert POSE_SCORE_DTYPE.itemsize == POSE_SCORE_BYTES
+
+
+class RelocalizeParams(C.Structure):
+    """sageicp_relocalize_params: the candidate grid around a prior, how many of the best to refine, the registration's
+    parameters"""
+    _fields_ = [("xy_extent", C.c_double), ("xy_step", C.c_double), ("z_extent", C.c_double), ("z_step", C.c_double),
+                ("yaw_extent", C.c_double), ("yaw_step", C.c_double),
+                ("refine_top", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_correspondence_distance", C.c_double), ("kernel", C.c_double), ("sem_th", C.c_double)]
+
+
+class RelocalizeInfo(C.Structure):
+    """sageicp_relocalize_info: what Relocalize did"""
+    _fields_ = [("candidates", C.c_uint64), ("best_candidate", C.c_uint64), ("best_candidate_score", C.c_double),
+                ("refined", C.c_uint32), ("winner_rank", C.c_uint32), ("iterations", C.c_int32), ("converged", C.c_int32),
+                ("us_score", C.c_double), ("us_refine", C.c_double), ("us_wall", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class OccupancyParams(C.Structure):
     """sageicp_occupancy_params: the bird's-eye grid of key-frame selection (bounds of x, y, z; H rows, W columns)"""
     _fields_ = [("bounds", (C.c_double * 2) * 3), ("occ_h", C.c_int32), ("occ_w", C.c_int32), ("overlap_th", C.c_double)]
@@ -295,6 +337,16 @@ _SIGNATURES = [
      [C.c_void_p, C.POINTER(DeviceFrame), _dp, C.c_double, C.c_double, C.c_double, C.c_void_p, C.POINTER(Quality)]),
     ("sageicp_pipeline_set_quality", C.c_int, [C.c_void_p, C.c_int]),
     ("sageicp_pipeline_quality", C.c_int, [C.c_void_p, C.POINTER(Quality)]),
+    ("sageicp_score_poses", C.c_int,
+     [C.c_void_p, _dp, C.c_uint64, _dp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    ("sageicp_score_poses_device", C.c_int,
+     [C.c_void_p, C.POINTER(DeviceFrame), _dp, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    ("sageicp_relocalize_candidates", C.c_int, [_dp, C.POINTER(RelocalizeParams), _dp, C.c_uint64, _u64p]),
+    ("sageicp_relocalize", C.c_int,
+     [C.c_void_p, _dp, C.c_uint64, _dp, C.POINTER(RelocalizeParams), _dp, C.POINTER(Quality), C.POINTER(RelocalizeInfo)]),
+    ("sageicp_relocalize_device", C.c_int,
+     [C.c_void_p, C.POINTER(DeviceFrame), _dp, C.POINTER(RelocalizeParams), C.c_void_p, _dp, C.POINTER(Quality),
+      C.POINTER(RelocalizeInfo)]),
     ("sageicp_align_clouds", C.c_int, [_dp, _dp, C.c_uint64, C.c_double, _dp, _dp, _dp, C.c_int]),
     ("sageicp_transform_points", C.c_int, [_dp, _dp, C.c_uint64, C.c_int]),
     ("sageicp_register_frame", C.c_int,
@@ -1052,6 +1104,53 @@ class VoxelHashMap:
                                                   max_correspondance_distance, kernel, th, C.byref(q)))
         return q
 
+    def ScorePoses(self, pts, poses, max_correspondance_distance, kernel, th, labels=None):
+        """A batch of candidate poses scored in one pass (sageicp_score_poses[_device]): a numpy record array
+        (POSE_SCORE_DTYPE) with one PoseScore per row of `poses` ((k, 7): qx, qy, qz, qw, tx, ty, tz), each bit for bit
+        the same-named fields of RegistrationQuality(pts, ..., pose=poses[c]).  `pts` as numpy (n, 4) rows or a torch
+        tensor on the map's GPU in the layouts RegisterFrame takes, `labels` as there.  Synchronous; a resident map
+        stays resident.  The work buffers stay reserved on the map (SAGEICP_SCORE_CHUNK_ROWS rows at most per chunk)."""
+        poses_a, pp = _d(poses)
+        if poses_a.size % 7:
+            raise ValueError("poses is (k, 7): qx, qy, qz, qw, tx, ty, tz per row")
+        k = poses_a.size // 7
+        out = np.zeros(k, dtype=POSE_SCORE_DTYPE)
+        if _is_device_tensor(pts):
+            f, stream = _device_rows(DeviceFrame, pts, labels, self.device, _FRAME_WORDS)
+            _check(lib().sageicp_score_poses_device(self._h, C.byref(f), pp, k, max_correspondance_distance, kernel, th,
+                                                    stream, out.ctypes.data))
+            return out
+        if labels is not None:
+            raise ValueError("labels= is for a frame that is a torch tensor on a GPU")
+        pts, fp = _d(pts)
+        _check(lib().sageicp_score_poses(self._h, fp, pts.reshape(-1, 4).shape[0], pp, k, max_correspondance_distance,
+                                         kernel, th, out.ctypes.data))
+        return out
+
+    def Relocalize(self, pts, prior, max_correspondance_distance, kernel, th, xy=(0, 0), z=(0, 0), yaw=(0, 0),
+                   refine_top=3, labels=None):
+        """Recover a frame whose guess lies outside the basin of the ICP (sageicp_relocalize[_device]): the grid of
+        relocalize_candidates(prior, xy, z, yaw) scored in one batch, the best `refine_top` refined by RegisterFrame, the
+        result with the largest sum_w returned as (pose, Quality at that pose, info dict).  Each of xy, z, yaw is
+        (extent, step): metres along the world axes, radians about world z.  The map is kept, unlike the node's
+        reinit."""
+        prior_a, pr = _d(prior)
+        if prior_a.size != 7:
+            raise ValueError("a pose is (qx, qy, qz, qw, tx, ty, tz)")
+        params = _relocalize_params(xy, z, yaw, refine_top, max_correspondance_distance, kernel, th)
+        pose, q, info = np.empty(7), Quality(), RelocalizeInfo()
+        if _is_device_tensor(pts):
+            f, stream = _device_rows(DeviceFrame, pts, labels, self.device, _FRAME_WORDS)
+            _check(lib().sageicp_relocalize_device(self._h, C.byref(f), pr, C.byref(params), stream,
+                                                   pose.ctypes.data_as(_dp), C.byref(q), C.byref(info)))
+            return pose, q, info.as_dict()
+        if labels is not None:
+            raise ValueError("labels= is for a frame that is a torch tensor on a GPU")
+        pts, fp = _d(pts)
+        _check(lib().sageicp_relocalize(self._h, fp, pts.reshape(-1, 4).shape[0], pr, C.byref(params),
+                                        pose.ctypes.data_as(_dp), C.byref(q), C.byref(info)))
+        return pose, q, info.as_dict()
+
     def _correspondences_device(self, pts, max_dist, th, with_index, labels, pose, dtype):
         # everything that can be wrong with the arguments raises ValueError before any call into the library
         f, stream = _device_rows(DeviceFrame, pts, labels, self.device, _FRAME_WORDS)
@@ -1076,6 +1175,31 @@ class VoxelHashMap:
             (idx.data_ptr() or None) if with_index else None, n, stream, C.byref(nout)))
         k = nout.value
         return (src[:k], tgt[:k], idx[:k]) if with_index else (src[:k], tgt[:k])
+
+
+def _relocalize_params(xy, z, yaw, refine_top=0, max_correspondence_distance=0.0, kernel=1.0, sem_th=0.0):
+    p = RelocalizeParams()
+    (p.xy_extent, p.xy_step), (p.z_extent, p.z_step), (p.yaw_extent, p.yaw_step) = xy, z, yaw
+    p.refine_top = refine_top
+    p.max_correspondence_distance, p.kernel, p.sem_th = max_correspondence_distance, kernel, sem_th
+    return p
+
+
+def relocalize_candidates(prior, xy=(0, 0), z=(0, 0), yaw=(0, 0), cap=None):
+    """The candidate poses of Relocalize around `prior` (sageicp_relocalize_candidates; the bits are the library's): a
+    (K, 7) array, yaw outermost, then x, then y, z innermost, each index ascending from -m to +m.  Each of xy, z, yaw is
+    (extent, step).  cap=: at most that many rows are written and (rows, K) is returned."""
+    prior_a, pr = _d(prior)
+    if prior_a.size != 7:
+        raise ValueError("a pose is (qx, qy, qz, qw, tx, ty, tz)")
+    params = _relocalize_params(xy, z, yaw)
+    k = C.c_uint64(0)
+    if cap is None:
+        _check(lib().sageicp_relocalize_candidates(pr, C.byref(params), None, 0, C.byref(k)))
+    rows = k.value if cap is None else int(cap)
+    out = np.empty((rows, 7))
+    _check(lib().sageicp_relocalize_candidates(pr, C.byref(params), out.ctypes.data_as(_dp), rows, C.byref(k)))
+    return out if cap is None else (out[:min(rows, k.value)], k.value)
 
 
 def register_frame(frame, voxel_map, initial_guess, max_correspondence_distance, kernel, sem_th,

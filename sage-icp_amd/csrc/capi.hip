@@ -74,6 +74,66 @@ static_assert(kQualClasses == 256, "the class tables of sageicp_quality");
 // (collinear pairs).  A 30 m scene at UTM coordinates (|s| ~ 5.5e6 m) has pivots of ~2^-40: no covariance there.
 constexpr double kQualPivotBound = 1.0 / 67108864.0;                // 2^-26
 
+// The Gauss-Newton step still left and JTJ^-1 from the assembled system, by Cholesky: false — nothing written that
+// counts — with fewer than three pairs, a pivot at or below the bound, or a result that is not finite.  The one solve
+// behind sageicp_quality and sageicp_pose_score (capi_relocalize.hip): the same operations in the same order.
+bool quality_solve(const double JTJ[36], const double JTr[6], double sum_w_r2, uint64_t n_pairs, QualitySolve *o) {
+    if (n_pairs < 3) return false;
+    const double np = static_cast<double>(n_pairs);
+    // JTJ = L L^T; the pivots are the squares of L's diagonal
+    double L[6][6] = {};
+    for (int j = 0; j < 6; ++j) {
+        double d = JTJ[j * 6 + j];
+        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+        if (!(d > kQualPivotBound * JTJ[j * 6 + j]) || !std::isfinite(d)) return false;
+        L[j][j] = std::sqrt(d);
+        for (int i = j + 1; i < 6; ++i) {
+            double v = JTJ[i * 6 + j];
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / L[j][j];
+        }
+    }
+    double Li[6][6] = {};                     // L^-1, lower triangular
+    for (int j = 0; j < 6; ++j) {
+        Li[j][j] = 1.0 / L[j][j];
+        for (int i = j + 1; i < 6; ++i) {
+            double v = 0.0;
+            for (int k = j; k < i; ++k) v -= L[i][k] * Li[k][j];
+            Li[i][j] = v / L[i][i];
+        }
+    }
+    for (int i = 0; i < 6; ++i)               // JTJ^-1 = L^-T L^-1
+        for (int j = 0; j <= i; ++j) {
+            double v = 0.0;
+            for (int k = i; k < 6; ++k) v += Li[k][i] * Li[k][j];
+            o->inv[i][j] = o->inv[j][i] = v;
+        }
+    double y[6], x[6], norm2 = 0.0;           // step = -L^-T (L^-1 JTr)
+    for (int i = 0; i < 6; ++i) {
+        double v = -JTr[i];
+        for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+        y[i] = v / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {
+        double v = y[i];
+        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
+        x[i] = v / L[i][i];
+    }
+    o->s2 = sum_w_r2 / (3.0 * np - 6.0);
+    bool finite = std::isfinite(o->s2);
+    for (int i = 0; i < 6; ++i) {
+        finite = finite && std::isfinite(x[i]);
+        for (int j = 0; j < 6; ++j) finite = finite && std::isfinite(o->inv[i][j]);
+    }
+    if (!finite) return false;
+    for (int i = 0; i < 6; ++i) {
+        o->step[i] = x[i];
+        norm2 += x[i] * x[i];
+    }
+    o->step_norm = std::sqrt(norm2);
+    return true;
+}
+
 // the report from what the kernels left: everything derived, on the host in fp64 (include/sageicp.h)
 static void quality_finish(const QualityRaw &r, uint64_t n, const double *pose, sageicp_quality *q) {
     std::memset(q, 0, sizeof(*q));
@@ -107,60 +167,13 @@ static void quality_finish(const QualityRaw &r, uint64_t n, const double *pose, 
     const double np = static_cast<double>(q->n_pairs);
     q->fitness = np / static_cast<double>(n);
     q->rmse = q->n_pairs ? std::sqrt(q->sum_r2 / np) : 0.0;
-    if (q->n_pairs < 3) return;
-    // JTJ = L L^T; the pivots are the squares of L's diagonal
-    double L[6][6] = {};
-    for (int j = 0; j < 6; ++j) {
-        double d = q->JTJ[j * 6 + j];
-        for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
-        if (!(d > kQualPivotBound * q->JTJ[j * 6 + j]) || !std::isfinite(d)) return;
-        L[j][j] = std::sqrt(d);
-        for (int i = j + 1; i < 6; ++i) {
-            double v = q->JTJ[i * 6 + j];
-            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-            L[i][j] = v / L[j][j];
-        }
-    }
-    double Li[6][6] = {};                     // L^-1, lower triangular
-    for (int j = 0; j < 6; ++j) {
-        Li[j][j] = 1.0 / L[j][j];
-        for (int i = j + 1; i < 6; ++i) {
-            double v = 0.0;
-            for (int k = j; k < i; ++k) v -= L[i][k] * Li[k][j];
-            Li[i][j] = v / L[i][i];
-        }
-    }
-    double inv[6][6];                         // JTJ^-1 = L^-T L^-1
-    for (int i = 0; i < 6; ++i)
-        for (int j = 0; j <= i; ++j) {
-            double v = 0.0;
-            for (int k = i; k < 6; ++k) v += Li[k][i] * Li[k][j];
-            inv[i][j] = inv[j][i] = v;
-        }
-    double y[6], x[6], norm2 = 0.0;           // step = -L^-T (L^-1 JTr)
+    QualitySolve sol;
+    if (!quality_solve(q->JTJ, q->JTr, q->sum_w_r2, q->n_pairs, &sol)) return;
     for (int i = 0; i < 6; ++i) {
-        double v = -q->JTr[i];
-        for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-        y[i] = v / L[i][i];
+        q->step[i] = sol.step[i];
+        for (int j = 0; j < 6; ++j) q->covariance[i * 6 + j] = sol.s2 * sol.inv[i][j];
     }
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
-        x[i] = v / L[i][i];
-    }
-    const double s2 = q->sum_w_r2 / (3.0 * np - 6.0);
-    bool finite = std::isfinite(s2);
-    for (int i = 0; i < 6; ++i) {
-        finite = finite && std::isfinite(x[i]);
-        for (int j = 0; j < 6; ++j) finite = finite && std::isfinite(inv[i][j]);
-    }
-    if (!finite) return;
-    for (int i = 0; i < 6; ++i) {
-        q->step[i] = x[i];
-        norm2 += x[i] * x[i];
-        for (int j = 0; j < 6; ++j) q->covariance[i * 6 + j] = s2 * inv[i][j];
-    }
-    q->step_norm = std::sqrt(norm2);
+    q->step_norm = sol.step_norm;
     // G C G^T, G = [[I, -hat(t)], [0, I]]: rows 0..2 of G hold two more entries each, rows 3..5 none
     const double t[3] = {pose ? pose[4] : 0.0, pose ? pose[5] : 0.0, pose ? pose[6] : 0.0};
     const double G[3][3] = {{0.0, t[2], -t[1]}, {-t[2], 0.0, t[0]}, {t[1], -t[0], 0.0}};      // -hat(t)
@@ -184,33 +197,23 @@ static void quality_finish(const QualityRaw &r, uint64_t n, const double *pose, 
     q->covariance_valid = 1;
 }
 
-int quality_of_scratch_rows(sageicp_map &m, uint64_t n, const double *pose, double max_dist, double kernel, double sem_th,
-                            sageicp_quality *out) {
+// The search behind the quality report and the batch score alike: the n rows at d_rows (already moved, in the caller's
+// order; the identity state uploaded on the stream before) sorted — the sort's first pass refuses non-finite rows, and
+// its verdict is read before anything is searched —, the search (rows, k_icp search-only) and the acceptance by query
+// (k_corr_flag) into d_by_query.  Needs reserve_nn(n) and reserve_sort(n).
+int search_rows_by_query(sageicp_map &m, const Point4 *d_rows, uint64_t n, double max_dist, double sem_th,
+                         int32_t *d_by_query, const char *who) {
     Scratch &sc = m.sc;
-    int rc;
-    if ((rc = sc.reserve_nn(n))) return rc;
-    if ((rc = sc.reserve_sort(n))) return rc;
-    if ((rc = sc.reserve_quality(n))) return rc;
     hipStream_t s = sc.stream.get();
-    // the rows moved by the pose (k_tf: sageicp_transform_points' point action) and sorted, as
-    // sageicp_get_correspondences_device prepares them; the sort's first pass refuses non-finite rows
-    double I[7];
-    identity_pose(I);
-    fill_state(sc.h_state.data(), pose ? pose : I);
-    HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
-    if (pose) launch_tf(sc.d_frame.data(), static_cast<int>(n), sc.d_state.data(), s);
-    HIPCHK(hipGetLastError());
-    HIPCHK(sort_frame(sc.d_frame.data(), sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), false, false,
+    HIPCHK(sort_frame(d_rows, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), false, false,
                       m.host.voxel_size, sc.d_keys.data(), sc.d_vals.data(), sc.d_sort_temp.data(),
                       sc.d_sort_temp.capacity(), s));
     HIPCHK(hipMemcpyAsync(sc.h_state.data(), sc.d_state.data(), sizeof(IcpState), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (sc.h_state.data()->bad_input)
-        return fail(SAGEICP_ERR_INVALID, "RegistrationQuality: a coordinate or label of a row is not finite (NaN / Inf)");
-    // the search (rows, k_icp search-only), the acceptance by query (k_corr_flag), the pass
-    HIPCHK(hipMemsetAsync(sc.d_qual_raw.data(), 0, sizeof(QualityRaw), s));
+        return fail(SAGEICP_ERR_INVALID, std::string(who) + ": a coordinate or label of a row is not finite (NaN / Inf)");
     const int lw = icp_lw(n, sparse_voxels(m));
-    if ((rc = m.dev.ensure_cand(wants_filter(m, n, sem_th), s))) return rc;
+    if (int rc = m.dev.ensure_cand(wants_filter(m, n, sem_th), s)) return rc;
     const IcpParams ip = icp_params(m, sc.d_sorted.data(), n, sem_th, lw, 0);
     launch_rows(ip, s);
     launch_icp(ip, lw, false, s);
@@ -222,13 +225,37 @@ int quality_of_scratch_rows(sageicp_map &m, uint64_t n, const double *pose, doub
     c.nn = sc.d_nn.data();
     c.pts = m.dev.search_view().pts;
     c.accept_r2 = accept_threshold(max_dist);
-    c.by_query = sc.d_by_query.data();
+    c.by_query = d_by_query;
     launch_corr_flag(c, s);
+    HIPCHK(hipGetLastError());
+    return SAGEICP_OK;
+}
+
+int quality_of_scratch_rows(sageicp_map &m, uint64_t n, const double *pose, double max_dist, double kernel, double sem_th,
+                            sageicp_quality *out) {
+    Scratch &sc = m.sc;
+    int rc;
+    if ((rc = sc.reserve_nn(n))) return rc;
+    if ((rc = sc.reserve_sort(n))) return rc;
+    if ((rc = sc.reserve_quality(n))) return rc;
+    hipStream_t s = sc.stream.get();
+    // the rows moved by the pose (k_tf: sageicp_transform_points' point action), as
+    // sageicp_get_correspondences_device prepares them
+    double I[7];
+    identity_pose(I);
+    fill_state(sc.h_state.data(), pose ? pose : I);
+    HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
+    if (pose) launch_tf(sc.d_frame.data(), static_cast<int>(n), sc.d_state.data(), s);
+    HIPCHK(hipGetLastError());
+    if ((rc = search_rows_by_query(m, sc.d_frame.data(), n, max_dist, sem_th, sc.d_by_query.data(), "RegistrationQuality")))
+        return rc;
+    // the pass
+    HIPCHK(hipMemsetAsync(sc.d_qual_raw.data(), 0, sizeof(QualityRaw), s));
     QualityArgs a{};
     a.n = static_cast<int>(n);
     a.frame = sc.d_frame.data();
     a.by_query = sc.d_by_query.data();
-    a.pts = c.pts;
+    a.pts = m.dev.search_view().pts;
     a.kernel = kernel;
     a.slabs = sc.d_qual_slabs.data();
     a.out = sc.d_qual_raw.data();

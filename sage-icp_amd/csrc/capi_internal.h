@@ -3,7 +3,7 @@
 // per-handle device scratch, the pipeline's frame source and buffers (prep.h) and its prefetch state (prefetch.h), the
 // checks of a caller's device memory (caller_mem.h), the HBM copy of a map (map_device.h), the way out (outputs.h), what
 // follows the search of GetCorrespondences on the device (correspond.h), the registration quality pass (quality.h), the
-// opaque handles of include/sageicp.h except the pipeline's (capi_pipeline.hip) and the one place where the ABI's
+// batch score of candidate poses (score.h), the opaque handles of include/sageicp.h except the pipeline's (capi_pipeline.hip) and the one place where the ABI's
 // `const sageicp_map *` becomes the reference the internals take (internal()).  Not part of the C ABI.
 #pragma once
 
@@ -34,6 +34,7 @@
 #include "egress.h"
 #include "correspond.h"
 #include "quality.h"
+#include "score.h"
 #include "msg.h"
 #include "map_update.h"
 #include "metrics.hpp"
@@ -205,6 +206,17 @@ struct Scratch {
     DevBuf<double> d_qual_slabs;
     DevBuf<QualityRaw> d_qual_raw;
     PinnedBuf<QualityRaw> h_qual_raw;
+    // the batch score of candidate poses (score.h): the frame's pristine rows, and per chunk the candidates as the
+    // device applies them, the moved rows, their accepted answers, the workgroups' slabs, what the kernels leave and its
+    // pinned landing place.  They grow to the largest chunk a call needed (SAGEICP_SCORE_CHUNK_ROWS rows) and stay
+    // reserved on the handle, like every buffer here.
+    DevBuf<Point4> d_score_frame, d_score_rows;
+    DevBuf<int32_t> d_score_by_query;
+    DevBuf<double> d_score_slabs;
+    DevBuf<ScorePose> d_score_poses;
+    PinnedBuf<ScorePose> h_score_poses;
+    DevBuf<ScoreRaw> d_score_raw;
+    PinnedBuf<ScoreRaw> h_score_raw;
 
     ~Scratch() { wait(); }         // (then the members go: nothing runs on the streams any more)
     // waits for both streams, with the device current (a scratch that never created a stream calls nothing)
@@ -320,6 +332,22 @@ struct Scratch {
         if (!h_qual_raw) HIPCHK(h_qual_raw.reserve(1));
         return SAGEICP_OK;
     }
+    int reserve_score_frame(size_t n) {
+        if (n > d_score_frame.capacity()) HIPCHK(d_score_frame.reserve(n + n / 4 + 1024));
+        return SAGEICP_OK;
+    }
+    // a chunk of kc candidates of a frame of n rows
+    int reserve_score(size_t n, size_t kc) {
+        const size_t rows = n * kc, slabs = score_slab_doubles(static_cast<int>(n), static_cast<uint32_t>(kc));
+        if (rows > d_score_rows.capacity()) HIPCHK(d_score_rows.reserve(rows + rows / 4 + 1024));
+        if (rows > d_score_by_query.capacity()) HIPCHK(d_score_by_query.reserve(rows + rows / 4 + 1024));
+        if (slabs > d_score_slabs.capacity()) HIPCHK(d_score_slabs.reserve(slabs + slabs / 4 + 1024));
+        if (kc > d_score_poses.capacity()) HIPCHK(d_score_poses.reserve(kc + kc / 4 + 16));
+        if (kc > h_score_poses.capacity()) HIPCHK(h_score_poses.reserve(kc + kc / 4 + 16));
+        if (kc > d_score_raw.capacity()) HIPCHK(d_score_raw.reserve(kc + kc / 4 + 16));
+        if (kc > h_score_raw.capacity()) HIPCHK(h_score_raw.reserve(kc + kc / 4 + 16));
+        return SAGEICP_OK;
+    }
     int reserve_partials(size_t blocks) {
         if (blocks > d_partials.capacity() / kNumSums) HIPCHK(d_partials.reserve((blocks + blocks / 4 + 256) * kNumSums));
         return SAGEICP_OK;
@@ -415,6 +443,7 @@ struct sageicp_comm {
 // capi.hip: the C ABI of maps, frames, communicators and the stand-alone entries.  capi_pipeline.hip: the pipeline
 // handle and its entries.  capi_outputs.hip: rows, records and grids out (outputs.h).  caller_mem.hip: the checks of a
 // caller's device memory (caller_mem.h).  map_device.hip: the HBM copy of a map (MapDevice): mirror refresh, download, copy, Update() on the device.
+// capi_relocalize.hip: the batch score of candidate poses and Relocalize.
 // capi_run.hip: the ICP loop (plan_loop, run_icp and its attempts), the RCCL binding and the single-process multi-GPU
 // mode.
 namespace sageicp_impl {
@@ -438,6 +467,15 @@ int register_resident(sageicp_map &m, const Point4 *d_frame, uint64_t n, int dev
 // capi.hip: the quality report of the n rows in m.sc.d_frame (not yet moved by `pose`; written on m.sc's stream)
 int quality_of_scratch_rows(sageicp_map &m, uint64_t n, const double *pose, double max_dist, double kernel, double sem_th,
                             sageicp_quality *out);
+// capi.hip: the search behind the quality report and the batch score — the n moved rows at d_rows sorted (the verdict on
+// non-finite rows read first), searched, the accepted answer of every query into d_by_query
+int search_rows_by_query(sageicp_map &m, const Point4 *d_rows, uint64_t n, double max_dist, double sem_th,
+                         int32_t *d_by_query, const char *who);
+// capi.hip: the Gauss-Newton step still left and JTJ^-1 (false: none — too few pairs, a pivot below the bound, not finite)
+struct QualitySolve {
+    double step[6], step_norm, inv[6][6], s2;
+};
+bool quality_solve(const double JTJ[36], const double JTr[6], double sum_w_r2, uint64_t n_pairs, QualitySolve *o);
 // map_device.hip: the handle's device made current, its stream and host copy handed to MapDevice
 int refresh_mirror(sageicp_map &m);
 int ensure_host(sageicp_map &m);

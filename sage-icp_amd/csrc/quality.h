@@ -58,6 +58,62 @@ struct QualityArgs {
     double *slabs;                      // scratch [(kQualReals + kQualBins) * kQualGroups], number-major
     QualityRaw *out;
 };
+// ---- what k_quality and the batch's k_score (score.hip) share: one pair's terms, the lanes' tree ----------------------
+// v of every lane of the wave, added in a fixed tree; every lane gets the same bits (a + b == b + a)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// the split of the pairs a lane has seen, by the label rule of VoxelHashMap.cpp:88
+struct QualPairCounts {
+    uint32_t pairs = 0, same = 0, unlabelled = 0, cross = 0;
+};
+
+// One accepted pair — moved query s, map point g — added to a lane's running sums: acc[0 .. kQWR2] always, the nine
+// unweighted moments acc[kQSx .. kQSzz] with kMoments (acc then holds kQualReals numbers, else kQWR2 + 1).  Returns
+// e = |r|^2.  The plain IEEE sequence of k_gn (kernels.hip); k2 = k * k.
+template <bool kMoments>
+__device__ __forceinline__ double quality_pair_term(const Point4 &s, const Point4 &g, double k, double k2, double *acc,
+                                                    QualPairCounts &n) {
+    const double sx = s.x, sy = s.y, sz = s.z;
+    const double rx = sx - g.x, ry = sy - g.y, rz = sz - g.z;
+    const double e = SAGE_SQNORM3_RESID(rx * rx, ry * ry, rz * rz);
+    const double den = k + e;
+    const double w = k2 / (den * den);   // square(th) / square(th + residual2), Registration.cpp:79-81
+    const double wsx = w * sx, wsy = w * sy, wsz = w * sz;
+    acc[kW] += w;
+    acc[kWsx] += wsx; acc[kWsy] += wsy; acc[kWsz] += wsz;
+    acc[kWxx] += wsx * sx; acc[kWxy] += wsx * sy; acc[kWxz] += wsx * sz;
+    acc[kWyy] += wsy * sy; acc[kWyz] += wsy * sz; acc[kWzz] += wsz * sz;
+    acc[kWrx] += w * rx; acc[kWry] += w * ry; acc[kWrz] += w * rz;
+    acc[kWcx] += w * (sy * rz - sz * ry);
+    acc[kWcy] += w * (sz * rx - sx * rz);
+    acc[kWcz] += w * (sx * ry - sy * rx);
+    acc[kQR2] += e;
+    acc[kQWR2] += w * e;
+    if constexpr (kMoments) {
+        acc[kQSx] += sx; acc[kQSy] += sy; acc[kQSz] += sz;
+        acc[kQSxx] += sx * sx; acc[kQSxy] += sx * sy; acc[kQSxz] += sx * sz;
+        acc[kQSyy] += sy * sy; acc[kQSyz] += sy * sz; acc[kQSzz] += sz * sz;
+    }
+    // the label rule of VoxelHashMap.cpp:88, on the truncated labels
+    const double lq = trunc(g.l), ls = trunc(s.l);
+    const bool eq = lq == ls;
+    const bool un = !eq && trunc(g.l * s.l) == 0.0;
+    ++n.pairs;
+    n.same += eq ? 1u : 0u;
+    n.unlabelled += un ? 1u : 0u;
+    n.cross += (!eq && !un) ? 1u : 0u;
+    return e;
+}
+
 inline uint32_t quality_tiles(int n) { return static_cast<uint32_t>((n + kQualTile - 1) / kQualTile); }
 inline uint32_t quality_groups(int n) { return quality_tiles(n) < kQualGroups ? quality_tiles(n) : kQualGroups; }
 constexpr size_t kQualSlabDoubles = static_cast<size_t>(kQualReals + kQualBins) * kQualGroups;

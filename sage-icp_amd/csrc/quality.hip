@@ -23,18 +23,6 @@ static_assert(kQualTile == 256 && kQualGroups == 256 && kQualClasses == 256, "fo
 // the class a label is counted in: static_cast<int>(l) where that lies in 0 .. 255, else the bin of the others
 __device__ __forceinline__ int quality_class(double l) { return (l > -1.0 && l < 256.0) ? static_cast<int>(l) : kQualClasses; }
 
-// v of every lane of the wave, added in a fixed tree; every lane gets the same bits (a + b == b + a)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_quality(QualityArgs a) {
     __shared__ uint32_t cls_queries[kQualBins], cls_pairs[kQualBins];
     __shared__ int stage_c[kQualTile];
@@ -48,7 +36,7 @@ __global__ __launch_bounds__(256) void k_quality(QualityArgs a) {
     double acc[kQualReals];
 #pragma unroll
     for (int c = 0; c < kQualReals; ++c) acc[c] = 0.0;
-    uint32_t pairs = 0, same = 0, unlabelled = 0, cross = 0;
+    QualPairCounts cnt;
     double cls_r2 = 0.0, other_r2 = 0.0;         // class t's; thread 0: also the other classes'
     const double k = a.kernel, k2 = k * k;
     const uint32_t tiles = (static_cast<uint32_t>(a.n) + 255u) / 256u;
@@ -63,34 +51,7 @@ __global__ __launch_bounds__(256) void k_quality(QualityArgs a) {
             const int c = quality_class(s.l);
             atomicAdd(&cls_queries[c], 1u);
             if (nn >= 0) {
-                const Point4 g = a.pts[nn];
-                const double sx = s.x, sy = s.y, sz = s.z;
-                const double rx = sx - g.x, ry = sy - g.y, rz = sz - g.z;
-                e = SAGE_SQNORM3_RESID(rx * rx, ry * ry, rz * rz);
-                const double den = k + e;
-                const double w = k2 / (den * den);   // square(th) / square(th + residual2), Registration.cpp:79-81
-                const double wsx = w * sx, wsy = w * sy, wsz = w * sz;
-                acc[kW] += w;
-                acc[kWsx] += wsx; acc[kWsy] += wsy; acc[kWsz] += wsz;
-                acc[kWxx] += wsx * sx; acc[kWxy] += wsx * sy; acc[kWxz] += wsx * sz;
-                acc[kWyy] += wsy * sy; acc[kWyz] += wsy * sz; acc[kWzz] += wsz * sz;
-                acc[kWrx] += w * rx; acc[kWry] += w * ry; acc[kWrz] += w * rz;
-                acc[kWcx] += w * (sy * rz - sz * ry);
-                acc[kWcy] += w * (sz * rx - sx * rz);
-                acc[kWcz] += w * (sx * ry - sy * rx);
-                acc[kQR2] += e;
-                acc[kQWR2] += w * e;
-                acc[kQSx] += sx; acc[kQSy] += sy; acc[kQSz] += sz;
-                acc[kQSxx] += sx * sx; acc[kQSxy] += sx * sy; acc[kQSxz] += sx * sz;
-                acc[kQSyy] += sy * sy; acc[kQSyz] += sy * sz; acc[kQSzz] += sz * sz;
-                // the label rule of VoxelHashMap.cpp:88, on the truncated labels
-                const double lq = trunc(g.l), ls = trunc(s.l);
-                const bool eq = lq == ls;
-                const bool un = !eq && trunc(g.l * s.l) == 0.0;
-                ++pairs;
-                same += eq ? 1u : 0u;
-                unlabelled += un ? 1u : 0u;
-                cross += (!eq && !un) ? 1u : 0u;
+                e = quality_pair_term<true>(s, a.pts[nn], k, k2, acc, cnt);
                 atomicAdd(&cls_pairs[c], 1u);
                 pair_class = c;
             }
@@ -116,7 +77,7 @@ __global__ __launch_bounds__(256) void k_quality(QualityArgs a) {
         if (lane == 0) wave_real[wv][c] = v;
     }
     {
-        const uint32_t p = wave_sum_u32(pairs), q = wave_sum_u32(same), u = wave_sum_u32(unlabelled), x = wave_sum_u32(cross);
+        const uint32_t p = wave_sum_u32(cnt.pairs), q = wave_sum_u32(cnt.same), u = wave_sum_u32(cnt.unlabelled), x = wave_sum_u32(cnt.cross);
         if (lane == 0) {
             wave_cnt[wv][0] = p; wave_cnt[wv][1] = q; wave_cnt[wv][2] = u; wave_cnt[wv][3] = x;
         }
