@@ -2,6 +2,7 @@
 // one launch wherever the frame fits), run_icp, the RCCL binding, and the single-process multi-GPU mode.  Part of
 // libsageicp_hip.so's host side: capi_internal.h.
 #include "capi_internal.h"
+#include "accept.h"     // accept_threshold: the definition (declared in capi_internal.h)
 
 #include <condition_variable>
 #include <mutex>
@@ -48,21 +49,6 @@ void fill_state(IcpState *st, const double init[7]) {
     for (int i = 0; i < 7; ++i) st->T[i] = init[i];
     quat_to_mat(init, st->R);
     identity_pose(st->T_icp);
-}
-
-// largest r2 with sqrt(r2) < max_dist: the acceptance test (nn - p).norm() < max_dist
-// (VoxelHashMap.cpp:111) without a device square root, exact for the IEEE sqrt the CPU evaluates
-double accept_threshold(double max_dist) {
-    if (!(max_dist > 0.0)) return -1.0;                       // nothing passes (also NaN)
-    double x = max_dist * max_dist;
-    if (std::isinf(x)) x = std::numeric_limits<double>::max();
-    while (x > 0.0 && !(std::sqrt(x) < max_dist)) x = std::nextafter(x, 0.0);
-    for (;;) {
-        const double up = std::nextafter(x, std::numeric_limits<double>::infinity());
-        if (std::isinf(up) || !(std::sqrt(up) < max_dist)) break;
-        x = up;
-    }
-    return std::sqrt(x) < max_dist ? x : -1.0;
 }
 
 // fewer than six points per voxel on average
@@ -765,7 +751,7 @@ struct Iterations {
         const IcpState &st = *sc.h_state.data();
         int rc, launched = 0, chunk = 4;
         for (;;) {
-            const int todo = std::min(chunk, kMaxIterations - launched);
+            const int todo = std::min(chunk, c.max_it - launched);
             for (int k = 0; k < todo; ++k)
                 if ((rc = enqueue(k, launched + k))) return rc;
             if ((rc = c.fetch_state(ip.nwaves))) return rc;
@@ -775,7 +761,7 @@ struct Iterations {
                     if (sampled(launched + k)) harvest(k);
             }
             launched += todo;
-            if (st.done || launched >= kMaxIterations) return SAGEICP_OK;
+            if (st.done || launched >= c.max_it) return SAGEICP_OK;
             chunk = std::min(kChunkMax, chunk * 2);   // 4, 8, 16, 16, ... : few syncs, bounded no-op tail
         }
     }

@@ -23,8 +23,10 @@ def _run(args, timeout):
 @pytest.mark.skipif(os.environ.get("SAGE_SQNORM3_ORDER", "2") == "0", reason="already the variant run")
 def test_oracle_suite_on_the_other_association():
     """golden vectors (indices exact, sums within rounding) and the known-answer tests of the oracle
-    built with x^2 + (y^2 + z^2) everywhere"""
-    r = _run(["tests/test_golden_oracle.py", "tests/test_oracle_kat.py", "-m", "not gpu"], 900)
+    built with x^2 + (y^2 + z^2) everywhere; the scenes on the acceptance radius, whose deciders change sides with the
+    association (tests/acceptscenes.py)"""
+    r = _run(["tests/test_golden_oracle.py", "tests/test_oracle_kat.py", "tests/test_accept_threshold_host.py",
+              "-m", "not gpu"], 900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
 
@@ -33,9 +35,11 @@ def test_oracle_suite_on_the_other_association():
 @pytest.mark.skipif(os.environ.get("SAGE_SQNORM3_ORDER", "2") == "0", reason="already the variant run")
 def test_gpu_parity_on_the_other_association():
     """the product built with the same switch against the oracle built with it: index-exact
-    correspondences (golden vectors, random scenes, near-ties), pose parity on c2 scaled"""
-    r = _run(["tests/test_gpu_parity.py", "-m", "gpu", "-k",
-              "golden_vectors or correspondences_index_exact or near_ties or parity_c2_scaled or edge_cases"],
+    correspondences (golden vectors, random scenes, near-ties), pose parity on c2 scaled; the pairs on the acceptance
+    radius at every site that decides them (tests/test_accept_boundary_gpu.py)"""
+    r = _run(["tests/test_gpu_parity.py", "tests/test_accept_boundary_gpu.py", "-m", "gpu", "-k",
+              "golden_vectors or correspondences_index_exact or near_ties or parity_c2_scaled or edge_cases"
+              " or accept_boundary"],
              1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout
