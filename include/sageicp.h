@@ -70,8 +70,10 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * sageicp_get_correspondences_device; then the registration quality report — sageicp_quality,
  * sageicp_registration_quality / _device, sageicp_pipeline_set_quality, sageicp_pipeline_quality; then a batch of
  * candidate poses and relocalisation — sageicp_pose_score, sageicp_score_poses / _device, sageicp_relocalize_params,
- * sageicp_relocalize_info, sageicp_relocalize_candidates, sageicp_relocalize / _device (additions only: no existing
- * struct or entry changed). */
+ * sageicp_relocalize_info, sageicp_relocalize_candidates, sageicp_relocalize / _device; then the archive of a map —
+ * sageicp_archive_info, sageicp_archive_voxel, SAGEICP_ARCHIVE_* / SAGEICP_SESSION, sageicp_map_set_archive,
+ * sageicp_map_archive_info / _clear / _voxels / _rows / _rows_device / _msg / _msg_device, sageicp_pipeline_set_archive
+ * (additions only: no existing struct or entry changed). */
 #define SAGEICP_ABI_VERSION 4
 
 /* Filled by sageicp_register_frame*.  Times are microseconds. */
@@ -863,6 +865,65 @@ int sageicp_map_pointcloud_msg(const sageicp_map *map, const sageicp_msg_colors 
 int sageicp_map_pointcloud_msg_device(const sageicp_map *map, const sageicp_msg_colors *colors, void *out,
                                       uint64_t cap_points, void *stream /* hipStream_t; NULL = null stream */,
                                       uint64_t *n_out);
+
+/* ---- the archive of a map: what the local map evicts, and the session's map --------------------------
+ * A per-handle, append-only log of the voxels RemovePointsFarFromLocation evicts; off by default, and with it off no
+ * call does anything it did not do before.  While it is on, every voxel that sageicp_map_remove_far, sageicp_map_update,
+ * sageicp_map_update_pose, sageicp_map_update_pose_device or the pipeline's per-frame update evicts is appended before
+ * its block is freed — on the device for an update that runs there (new kernels between the search for the far voxels
+ * and their eviction, no atomic deciding a position, no added host synchronisation), on the host otherwise.
+ * Order: calls in the order they were made; within a call the voxels in the order of their eviction (ascending block
+ * index; in reference-order mode the order the erase-while-iterating sweep erases them); within a voxel its rows in
+ * their stored order, bit for bit.  A refused update (non-finite input, a voxel index beyond +-2^20, storage overflow)
+ * leaves what the archive holds unchanged and takes no serial (where its rows are kept may change: a device-side update
+ * first moves rows that host-side evictions left on the host behind the device part and reserves room, which can
+ * re-allocate the device buffers and then waits for the stream; an update that does neither adds no synchronisation).
+ * Limit: max_rows (0: none).  A voxel is archived only while all its rows still fit; the first that does not makes the
+ * archive `full` until sageicp_map_archive_clear, and evictions are only counted from then on (dropped_rows /
+ * dropped_voxels): a limited archive is the longest prefix of whole voxels of the unlimited one.
+ * Lifetime: sageicp_map_clear and sageicp_pipeline_reinitialize leave the archive alone (it belongs to the session, not
+ * to the window); sageicp_map_archive_clear empties it, releases its device memory, resets full, the dropped counts and
+ * the serial, and keeps the setting; sageicp_map_clone copies setting and contents; of a multi-device map only the first
+ * copy archives.  Environment (for callers behind the header shim): SAGEICP_MAP_ARCHIVE=1 switches it on for every map
+ * the process creates, SAGEICP_MAP_ARCHIVE_MAX_ROWS sets the limit (a 64-bit decimal count of rows).
+ * Exports — `which`: SAGEICP_ARCHIVE_ALL the log as recorded (a voxel the sensor came back to and left again appears once
+ * per generation); SAGEICP_ARCHIVE_LATEST record i iff no later record has its key and the live map holds no voxel with
+ * that key, in log order; SAGEICP_SESSION the LATEST rows followed by sageicp_map_pointcloud's rows in its order: every
+ * voxel key the session has seen exactly once, with its most recent content.  `first` skips rows of the selection;
+ * *n_out = the rows the selection has; rows [first, first + min(cap, *n_out - first)) are written and nothing beyond
+ * them; first > *n_out writes nothing and is SAGEICP_OK.  Exports are synchronous, work whether the archive is on or
+ * off, and follow sageicp_map_pointcloud_device's stream and lifetime rules and sageicp_map_pointcloud_msg's colour and
+ * label rules.  ALL into host rows needs no device while no row of the archive is in device memory; every other export
+ * is device work (SAGEICP_ERR_NO_DEVICE without one) and leaves a resident map resident. */
+#define SAGEICP_ARCHIVE_ALL 0
+#define SAGEICP_ARCHIVE_LATEST 1
+#define SAGEICP_SESSION 2
+typedef struct sageicp_archive_info {
+    int32_t enabled, full;
+    uint64_t rows, voxels, dropped_rows, dropped_voxels, max_rows, updates;
+    uint64_t device_rows, host_rows, device_bytes;   /* where the rows are; what the archive holds in device memory */
+} sageicp_archive_info;
+typedef struct sageicp_archive_voxel {
+    int32_t x, y, z;       /* the voxel key */
+    uint32_t count;
+    uint64_t first_row;    /* index of its first row in the log */
+    uint64_t update;       /* serial of the call that evicted it: the eviction-capable calls that succeeded before it
+                              while the archive was on, counted since the map was created or the archive cleared (a call
+                              that evicts nothing takes one too; calls made while it is off take none, and switching it
+                              off and on again goes on counting where it stopped) */
+} sageicp_archive_voxel;
+int sageicp_map_set_archive(sageicp_map *m, int enable, uint64_t max_rows);   /* a max_rows below the rows held: SAGEICP_ERR_INVALID */
+int sageicp_map_archive_info(const sageicp_map *m, sageicp_archive_info *out);
+int sageicp_map_archive_clear(sageicp_map *m);
+int sageicp_map_archive_voxels(const sageicp_map *m, uint64_t first, sageicp_archive_voxel *out, uint64_t cap, uint64_t *n_out);
+int sageicp_map_archive_rows(const sageicp_map *m, int which, uint64_t first, double *out_xyzl, uint64_t cap, uint64_t *n_out);
+int sageicp_map_archive_rows_device(const sageicp_map *m, int which, uint64_t first, const sageicp_device_points *dst,
+                                    void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
+int sageicp_map_archive_msg(const sageicp_map *m, int which, uint64_t first, const sageicp_msg_colors *colors, void *out,
+                            uint64_t cap_points, uint64_t *n_out);
+int sageicp_map_archive_msg_device(const sageicp_map *m, int which, uint64_t first, const sageicp_msg_colors *colors, void *out,
+                                   uint64_t cap_points, void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
+int sageicp_pipeline_set_archive(sageicp_pipeline *p, int enable, uint64_t max_rows);   /* its map's */
 
 /* ---- KITTI trajectory metrics: sage_icp::metrics (metrics/Metrics.hpp:33-37) ----------------------
  * Host-only (the reference's are CPU code too).  Poses are 4x4 homogeneous matrices, ROW-major

@@ -216,6 +216,22 @@ class RelocalizeInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ArchiveInfo(C.Structure):
+    """sageicp_archive_info"""
+    _fields_ = [("enabled", C.c_int32), ("full", C.c_int32), ("rows", C.c_uint64), ("voxels", C.c_uint64),
+                ("dropped_rows", C.c_uint64), ("dropped_voxels", C.c_uint64), ("max_rows", C.c_uint64), ("updates", C.c_uint64),
+                ("device_rows", C.c_uint64), ("host_rows", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+ARCHIVE_ALL, ARCHIVE_LATEST, SESSION = 0, 1, 2          # SAGEICP_ARCHIVE_ALL / _LATEST, SAGEICP_SESSION
+ARCHIVE_WHICH = {"all": ARCHIVE_ALL, "latest": ARCHIVE_LATEST, "session": SESSION}
+# sageicp_archive_voxel
+ARCHIVE_VOXEL_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("count", "<u4"), ("first_row", "<u8"), ("update", "<u8")])
+
+
 class OccupancyParams(C.Structure):
     """sageicp_occupancy_params: the bird's-eye grid of key-frame selection (bounds of x, y, z; H rows, W columns)"""
     _fields_ = [("bounds", (C.c_double * 2) * 3), ("occ_h", C.c_int32), ("occ_w", C.c_int32), ("overlap_th", C.c_double)]
@@ -409,6 +425,16 @@ _SIGNATURES = [
     ("sageicp_map_pointcloud_msg", C.c_int, [C.c_void_p, C.POINTER(MsgColors), C.c_void_p, C.c_uint64, _u64p]),
     ("sageicp_map_pointcloud_msg_device", C.c_int,
      [C.c_void_p, C.POINTER(MsgColors), C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
+    ("sageicp_map_set_archive", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
+    ("sageicp_map_archive_info", C.c_int, [C.c_void_p, C.POINTER(ArchiveInfo)]),
+    ("sageicp_map_archive_clear", C.c_int, [C.c_void_p]),
+    ("sageicp_map_archive_voxels", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _u64p]),
+    ("sageicp_map_archive_rows", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _dp, C.c_uint64, _u64p]),
+    ("sageicp_map_archive_rows_device", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(DevicePoints), C.c_void_p, _u64p]),
+    ("sageicp_map_archive_msg", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(MsgColors), C.c_void_p, C.c_uint64, _u64p]),
+    ("sageicp_map_archive_msg_device", C.c_int,
+     [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(MsgColors), C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
+    ("sageicp_pipeline_set_archive", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
     ("sageicp_pipeline_create", C.c_void_p, [C.POINTER(PipelineConfig)]),
     ("sageicp_pipeline_destroy", None, [C.c_void_p]),
     ("sageicp_pipeline_register_frame", C.c_int,
@@ -602,7 +628,7 @@ def _device_rows(struct, pts, labels, device, words, distinct=False):
     return r, _current_stream(pts.device)
 
 
-def _rows_out(device_index, count, host_rows, device_call, device, dtype, out, labels_out):
+def _rows_out(device_index, count, host_rows, device_call, device, dtype, out, labels_out, first=0):
     """SageICP.source / SageICP.LocalMap / VoxelHashMap.Pointcloud: numpy (n, 4) float64 host rows (host_rows(n)); with
     device=True a fresh (n, 4) tensor on the GPU (float64, or dtype=torch.float32); with out= (and labels_out=) the
     caller's tensors, returned as the filled views out[:n] (and labels_out[:n]); an out= of fewer rows than there are
@@ -630,7 +656,7 @@ def _rows_out(device_index, count, host_rows, device_call, device, dtype, out, l
     d, stream = _device_rows(DevicePoints, out, labels_out, device_index, _OUT_WORDS, distinct=True)
     n = C.c_uint64(0)
     _check(device_call(C.byref(d), stream, C.byref(n)))
-    k = min(n.value, out.shape[0])
+    k = min(max(0, n.value - first), out.shape[0])      # (first: the entry skipped that many of the n rows there are)
     return out[:k] if labels_out is None else (out[:k], labels_out[:k])
 
 
@@ -767,7 +793,7 @@ def _msg_colors(colors):
     return c
 
 
-def _records_out(device_index, count, host_call, device_call, colors, device, out):
+def _records_out(device_index, count, host_call, device_call, colors, device, out, first=0):
     """source_msg / LocalMapMsg / PointcloudMsg: the rows as (n, 21) uint8 records — numpy, with device=True a fresh
     tensor on the GPU, with out= the caller's buffer (a C-contiguous uint8 numpy array or a contiguous uint8 tensor on
     the GPU, 1-D or (k, 21), any base alignment): its first min(rows that fit, n) records are written and returned as a
@@ -777,7 +803,7 @@ def _records_out(device_index, count, host_call, device_call, colors, device, ou
     if out is None and not device:
         a = np.empty((count(), MSG_POINT_STEP), dtype=np.uint8)
         _check(host_call(C.byref(c), a.ctypes.data_as(C.c_void_p) if a.size else None, a.shape[0], C.byref(n)))
-        return a[:min(n.value, a.shape[0])]
+        return a[:min(max(0, n.value - first), a.shape[0])]
     if out is None:
         import torch
         _check_one_hip_runtime()
@@ -789,7 +815,7 @@ def _records_out(device_index, count, host_call, device_call, colors, device, ou
             raise ValueError("out= is 1-D or (k, %d)" % MSG_POINT_STEP)
         cap = out.size // MSG_POINT_STEP
         _check(host_call(C.byref(c), out.ctypes.data_as(C.c_void_p) if cap else None, cap, C.byref(n)))
-        k = min(n.value, cap)
+        k = min(max(0, n.value - first), cap)
         return out.reshape(-1)[:k * MSG_POINT_STEP].reshape(k, MSG_POINT_STEP)
     if not _is_device_tensor(out):
         raise ValueError("out= is a uint8 numpy array or a uint8 torch tensor on the GPU")
@@ -801,7 +827,7 @@ def _records_out(device_index, count, host_call, device_call, colors, device, ou
     _check_one_hip_runtime()
     cap = out.numel() // MSG_POINT_STEP
     _check(device_call(C.byref(c), (out.data_ptr() or None) if cap else None, cap, _current_stream(out.device), C.byref(n)))
-    k = min(n.value, cap)
+    k = min(max(0, n.value - first), cap)
     return out.reshape(-1)[:k * MSG_POINT_STEP].view(k, MSG_POINT_STEP)
 
 
@@ -1026,6 +1052,31 @@ class VoxelHashMap:
                             lambda c, o, cap, n: lib().sageicp_map_pointcloud_msg(self._h, c, o, cap, n),
                             lambda c, o, cap, s, n: lib().sageicp_map_pointcloud_msg_device(self._h, c, o, cap, s, n),
                             colors, device, out)
+
+    # ---- the archive: what the map evicts, and the session's map (include/sageicp.h) ----
+    def set_archive(self, enable=True, max_rows=0):
+        """Keep every voxel the map evicts from now on (off by default); max_rows bounds the log (0: no limit)"""
+        _check(lib().sageicp_map_set_archive(self._h, 1 if enable else 0, int(max_rows)))
+        return self
+
+    def archive_info(self):
+        return _archive_info(self._h)
+
+    def archive_voxels(self):
+        """the log's records, one per evicted voxel: a numpy record array (ARCHIVE_VOXEL_DTYPE)"""
+        return _archive_voxels(self._h)
+
+    def archive_clear(self):
+        _check(lib().sageicp_map_archive_clear(self._h))
+
+    def ArchivedPointcloud(self, which="all", first=0, device=False, dtype=None, out=None, labels_out=None):
+        """The rows of a selection from row `first` on: "all" the log as recorded, "latest" the last generation of every
+        key the live map does not hold, "session" those followed by Pointcloud().  The keywords as Pointcloud()."""
+        return _archive_rows(lambda: self._h, self.device, which, first, device, dtype, out, labels_out)
+
+    def ArchivedPointcloudMsg(self, colors, which="all", first=0, device=False, out=None):
+        """ArchivedPointcloud()'s rows as (n, 21) uint8 records; the arguments as PointcloudMsg"""
+        return _archive_msg(lambda: self._h, self.device, colors, which, first, device, out)
 
     def resident(self):
         """True while the HBM copy of the map is the authority (after a device-side update)"""
@@ -1508,6 +1559,27 @@ class SageICP:
                             lambda c, o, cap, s, n: lib().sageicp_map_pointcloud_msg_device(h(), c, o, cap, s, n),
                             colors, device, out)
 
+    def set_archive(self, enable=True, max_rows=0):
+        """the local map's archive (VoxelHashMap.set_archive): keep what the per-frame update evicts"""
+        _check(lib().sageicp_pipeline_set_archive(self._h, 1 if enable else 0, int(max_rows)))
+        return self
+
+    def archive_info(self):
+        return _archive_info(lib().sageicp_pipeline_local_map(self._h))
+
+    def archive_voxels(self):
+        return _archive_voxels(lib().sageicp_pipeline_local_map(self._h))
+
+    def SessionMap(self, which="session", first=0, device=False, dtype=None, out=None, labels_out=None):
+        """The map of what the session drove through: the latest generation of every evicted voxel the local map does
+        not hold, then LocalMap() (VoxelHashMap.ArchivedPointcloud; which= "all" / "latest" give the log alone)"""
+        return _archive_rows(lambda: lib().sageicp_pipeline_local_map(self._h), self.config.device, which, first, device, dtype,
+                             out, labels_out)
+
+    def SessionMapMsg(self, colors, which="session", first=0, device=False, out=None):
+        return _archive_msg(lambda: lib().sageicp_pipeline_local_map(self._h), self.config.device, colors, which, first, device,
+                            out)
+
     def source_size(self):
         """rows of source(): n_source of the last successful RegisterFrame, 0 if there is none"""
         n = C.c_uint64(0)
@@ -1523,6 +1595,56 @@ class SageICP:
         k = C.c_uint64(0)
         _check(lib().sageicp_pipeline_source(self._h, a.ctypes.data_as(_dp), n, C.byref(k)))
         return a
+
+
+def _archive_info(h):
+    i = ArchiveInfo()
+    _check(lib().sageicp_map_archive_info(h, C.byref(i)))
+    return i.as_dict()
+
+
+def _archive_voxels(h):
+    n = C.c_uint64(0)
+    _check(lib().sageicp_map_archive_voxels(h, 0, None, 0, C.byref(n)))
+    a = np.zeros(n.value, dtype=ARCHIVE_VOXEL_DTYPE)
+    if n.value:
+        _check(lib().sageicp_map_archive_voxels(h, 0, a.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+    return a.view(np.recarray)
+
+
+def _archive_which(which):
+    return ARCHIVE_WHICH[which] if isinstance(which, str) else int(which)
+
+
+def _archive_room(handle, w, first):
+    """rows to make room for: what selection w has from row `first` on ("all"), or an upper bound of it that costs no
+    device work ("latest": every archived row; "session": those and the map's) — the selection itself is then computed
+    once, by the call that writes the rows, and the result trimmed to what it reported"""
+    i = _archive_info(handle())
+    n = i["rows"] + (int(lib().sageicp_map_size(handle())) if w == SESSION else 0)
+    return max(0, n - first)
+
+
+def _archive_rows(handle, device_index, which, first, device, dtype, out, labels_out):
+    w, first = _archive_which(which), int(first)
+
+    def host_rows(n):
+        a = np.empty((n, 4))
+        k = C.c_uint64(0)
+        _check(lib().sageicp_map_archive_rows(handle(), w, first, a.ctypes.data_as(_dp) if n else None, n, C.byref(k)))
+        return a[:min(max(0, k.value - first), n)]
+
+    return _rows_out(device_index, lambda: _archive_room(handle, w, first), host_rows,
+                     lambda d, s, n: lib().sageicp_map_archive_rows_device(handle(), w, first, d, s, n),
+                     device, dtype, out, labels_out, first=first)
+
+
+def _archive_msg(handle, device_index, colors, which, first, device, out):
+    w, first = _archive_which(which), int(first)
+    return _records_out(device_index, lambda: _archive_room(handle, w, first),
+                        lambda c, o, cap, n: lib().sageicp_map_archive_msg(handle(), w, first, c, o, cap, n),
+                        lambda c, o, cap, s, n: lib().sageicp_map_archive_msg_device(handle(), w, first, c, o, cap, s, n),
+                        colors, device, out, first=first)
 
 
 def _map_rows(handle, device_index, device, dtype, out, labels_out):

@@ -357,6 +357,12 @@ sageicp_map *sageicp_map_create(double voxel_size, double max_distance, int basi
     // SAGEICP_MAP_REFERENCE_ORDER=1: every map of this process is created in reference-order mode (the
     // knob for callers behind the header shim; sageicp_map_set_reference_order for everyone else)
     if (env_int("SAGEICP_MAP_REFERENCE_ORDER", 0)) (void)sageicp_map_set_reference_order(m, 1);
+    // SAGEICP_MAP_ARCHIVE=1: every map of this process keeps what it evicts (sageicp_map_set_archive), at most
+    // SAGEICP_MAP_ARCHIVE_MAX_ROWS rows of it (0 / unset: no limit)
+    if (env_int("SAGEICP_MAP_ARCHIVE", 0)) {
+        const char *lim = env_cached("SAGEICP_MAP_ARCHIVE_MAX_ROWS");      // (64 bits: 2^31 rows are only 64 GiB)
+        (void)sageicp_map_set_archive(m, 1, (lim && lim[0] != '-') ? std::strtoull(lim, nullptr, 10) : 0);
+    }
     return m;
 }
 
@@ -442,10 +448,24 @@ static sageicp_map *clone_one(const sageicp_map &src) {
     return m;
 }
 
+// the archive's setting and contents (a deep copy: the device part device to device)
+static int clone_archive(const sageicp_map &src, sageicp_map *m) {
+    if (src.arc.dev_vox) {
+        if (int rc = m->sc.init(m->device)) return rc;
+        HIPCHK(hipSetDevice(m->device));
+        HIPCHK(hipStreamSynchronize(src.sc.stream.get()));
+    }
+    return m->arc.copy_from(src.arc, m->sc.stream.get());
+}
+
 sageicp_map *sageicp_map_clone(const sageicp_map *src) {
     if (!src) return nullptr;
     sageicp_map *m = clone_one(*src);
     if (!m) return nullptr;
+    if (clone_archive(*src, m)) {
+        sageicp_map_destroy(m);
+        return nullptr;
+    }
     for (const sageicp_map *r : src->replicas) {
         sageicp_map *c = clone_one(*r);
         if (!c) {
@@ -516,7 +536,7 @@ int sageicp_map_add_points(sageicp_map *m, const double *xyzl, uint64_t n) {
 int sageicp_map_remove_far(sageicp_map *m, const double origin[3]) {
     if (!m || !origin) return fail(SAGEICP_ERR_INVALID, "null argument");
     if (int rc = ensure_host(*m)) return rc;
-    m->host.remove_far(origin);
+    host_remove_far(*m, origin);          // (the evicted voxels into the handle's archive while it is on)
     for (sageicp_map *r : m->replicas)
         if (int rc = sageicp_map_remove_far(r, origin)) return rc;
     return SAGEICP_OK;

@@ -372,6 +372,7 @@ using namespace sageicp;
 
 #include "caller_mem.h"
 #include "map_device.h"
+#include "archive.h"
 #include "outputs.h"
 
 // ---- opaque handles -----------------------------------------------------------------------
@@ -381,6 +382,7 @@ struct sageicp_map {
     Scratch sc;                                  // the ICP loop's buffers and streams
     sageicp_impl::MapDevice dev;                            // the copy in HBM, and which of the two copies counts (map_device.h)
     sageicp_impl::OutputBuffers out;             // sageicp_map_pointcloud*: the exports work in these (outputs.h)
+    sageicp_impl::MapArchive arc;                // the log of evicted voxels (archive.h): off by default; replicas never archive
     // Single-process multi-GPU mode (SAGEICP_DEVICES / sageicp_map_set_devices): one more complete
     // copy of the map per extra device.  Every mutation is applied to all of them, RegisterFrame
     // shards the frame over them (one host thread and one stream per device) and the ranks'
@@ -481,6 +483,8 @@ int refresh_mirror(sageicp_map &m);
 int ensure_host(sageicp_map &m);
 int device_update(sageicp_map &m, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points = nullptr);
 bool all_finite(const double *xyzl, uint64_t n);
+// capi_archive.hip: RemovePointsFarFromLocation on the host copy of one handle, the evicted voxels into its archive while on
+void host_remove_far(sageicp_map &m, const double origin[3]);
 // capi_run.hip
 void identity_pose(double T[7]);
 void fill_state(IcpState *st, const double init[7]);

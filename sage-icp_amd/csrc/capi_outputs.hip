@@ -135,6 +135,10 @@ static int packed_rows(const RowSource &src, uint64_t n, DevBuf<Point4> &d_pc, s
     return SAGEICP_OK;
 }
 
+int map_packed_rows(sageicp_map &m, hipStream_t s, std::vector<double> &staged, const Point4 **rows) {
+    return packed_rows(RowSource::of_map(m), m.counts().points, m.out.d_pc, staged, s, rows);
+}
+
 EgressArgs egress_args(const sageicp_device_points &d, int *flags) {
     EgressArgs a{};
     a.xyz = static_cast<unsigned char *>(d.xyz);

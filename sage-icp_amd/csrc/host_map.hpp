@@ -246,6 +246,11 @@ public:
     }
 
     void remove_far(const double origin[3]) {
+        remove_far(origin, [](uint32_t) {});
+    }
+    // on_evict(b): block b is about to go (its key, count and points still in place), in the order of eviction
+    template <typename OnEvict>
+    void remove_far(const double origin[3], OnEvict &&on_evict) {
         const double max2 = max_distance * max_distance;
         bool any = false;
         if (track_order) {
@@ -257,6 +262,7 @@ public:
                     return SAGE_SQNORM3_FAR(dx * dx, dy * dy, dz * dz) > max2;
                 },
                 [&](uint32_t b) {
+                    on_evict(b);
                     erase_block(b);
                     any = true;
                 });
@@ -268,6 +274,7 @@ public:
             const Point4 &p = pts[first_point(b)];
             const double dx = p.x - origin[0], dy = p.y - origin[1], dz = p.z - origin[2];
             if (SAGE_SQNORM3_FAR(dx * dx, dy * dy, dz * dz) > max2) {
+                on_evict(b);
                 erase_block(b);
                 any = true;
             }

@@ -26,6 +26,8 @@
 namespace sageicp_impl {
 using namespace sageicp;
 
+struct MapArchive;      // archive.h: the log of evicted voxels a handle may keep
+
 // what the authoritative copy holds (sageicp_map::counts())
 struct MapCounts {
     uint64_t points = 0;
@@ -158,7 +160,9 @@ struct MapDevice {
     int refresh_from(HostMap &h, hipStream_t s);             // no-op while the HBM copy is the authority
     int ensure_cand(bool derive, hipStream_t s);
     int download_into(HostMap &h, hipStream_t s);            // no-op unless the HBM copy is the authority
-    int update(HostMap &h, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points, hipStream_t s);
+    // `arc`: the handle's archive while it is on (the evicted voxels are appended to it before their blocks are freed), else nullptr
+    int update(HostMap &h, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points, hipStream_t s,
+               MapArchive *arc = nullptr);
     int copy_from(const MapDevice &src, const HostMap &h, hipStream_t s);   // src: an authority; `h`: this map's configuration
     DevMap view(const HostMap &h) const;                     // map_update.hip's view of the arrays
     SearchView search_view() const;

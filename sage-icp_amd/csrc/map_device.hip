@@ -106,7 +106,8 @@ int MapDevice::reserve_update_scratch(size_t n, size_t nb) {
         u.nb = c;
     }
     if (!u.n_sel) HIPCHK(u.n_sel.reserve(1));
-    const size_t tb = map_update_temp_bytes(static_cast<int>(u.n), static_cast<int>(u.nb));
+    // (the archive's scan of nb + 1 counts works in the same storage)
+    const size_t tb = std::max(map_update_temp_bytes(static_cast<int>(u.n), static_cast<int>(u.nb)), archive_temp_bytes(u.nb));
     if (tb > u.temp.capacity()) HIPCHK(u.temp.reserve(tb));
     return SAGEICP_OK;
 }
@@ -384,6 +385,9 @@ struct UpdateJob {
     UpdateNeeds needs{};
     DevMap dm{};
     UpdateScratch us{};
+    MapArchive *arc = nullptr;   // the handle's archive while it is on
+    ArchiveDev ad{};
+    ArchiveCtr &arc_back() const { return *reinterpret_cast<ArchiveCtr *>(d.h_ctr_aux.data() + kArchiveAuxWord); }
     MapCounters &back() const { return *d.h_ctr.data(); }      // the counters as the device last handed them back
 };
 
@@ -401,6 +405,16 @@ int seed_counters(UpdateJob &j) {
     c.units_hi = h.units_hi;
     for (int k = 0; k < h.n_classes; ++k) c.free_units_count[k] = static_cast<int32_t>(h.free_units[k].size());
     return SAGEICP_OK;
+}
+
+// the archive before the pass: its pending tail behind its device part, and room for whatever this update can evict —
+// the live points and the frame bound it, numbers the host holds.  (Where the log's rows are kept may change here even
+// if the pass then refuses the update — the tail moves to the device, a buffer is re-allocated, the stream waited for —
+// what the log holds does not.)
+int reserve_archive(UpdateJob &j) {
+    MapArchive &a = *j.arc;
+    if (int rc = a.flush_pending(j.s)) return rc;
+    return a.reserve(j.d.ctr.total_points + j.n, static_cast<uint64_t>(j.d.ctr.num_voxels) + j.n, j.s);
 }
 
 int reserve(UpdateJob &j) {
@@ -467,7 +481,8 @@ int run_pass(UpdateJob &j) {
     const HostMap &h = j.h;
     hipStream_t s = j.s;
     const uint32_t bound = static_cast<uint32_t>(j.needs.need_blocks);
-    if (int rc = d.reserve_update_scratch(j.n, bound)) return rc;
+    // (the archive's append scans bound + 1 counts in far_flag: k_arc_counts writes counts[bound], the scan's total)
+    if (int rc = d.reserve_update_scratch(j.n, static_cast<size_t>(bound) + (j.arc ? 1 : 0))) return rc;
     UpdateScratch &us = j.us;
     us = d.up.view();
     if (j.d_points) us.raw = const_cast<Point4 *>(j.d_points);
@@ -479,10 +494,36 @@ int run_pass(UpdateJob &j) {
     pol.critical = h.critical;
     pol.n_labels = static_cast<int>(h.basic_labels.size());
     for (int i = 0; i < pol.n_labels; ++i) pol.labels[i] = h.basic_labels[i];
+    if (j.arc) {
+        // the archive's counters go out as the host has them and come back with the pass's (arc_back: words of h_ctr_aux);
+        // its scratch is what the search for far voxels has finished with
+        MapArchive &a = *j.arc;
+        j.arc_back() = a.counters();
+        HIPCHK(hipMemcpyAsync(a.d_ctr.data(), &j.arc_back(), sizeof(ArchiveCtr), hipMemcpyHostToDevice, s));
+        ArchiveDev &ad = j.ad;
+        ad.rows = a.d_rows.data();
+        ad.vox = a.d_vox.data();
+        ad.ctr = a.d_ctr.data();
+        ad.cap_rows = a.d_rows.capacity();
+        ad.cap_vox = a.d_vox.capacity();
+        ad.limit_rows = a.max_rows ? a.max_rows : ~0ull;
+        ad.serial = a.updates;
+        ad.counts = d.up.far_flag.data();
+        ad.offsets = reinterpret_cast<uint32_t *>(d.up.far_list.data());
+        ad.temp = d.up.temp.data();
+        ad.temp_bytes = d.up.temp.capacity();
+    }
     if (!h.track_order) {
         us.new_list = nullptr;
         us.far_list = nullptr;
-        HIPCHK(map_update_device(j.dm, pol, us, static_cast<int>(j.n), j.pose, bound, s));
+        if (!j.arc) {
+            HIPCHK(map_update_device(j.dm, pol, us, static_cast<int>(j.n), j.pose, bound, s));
+        } else {
+            // map_update_device's launches with the append between the search for the far voxels and their eviction
+            HIPCHK(map_update_insert_find_far(j.dm, pol, us, static_cast<int>(j.n), j.pose, bound, s));
+            HIPCHK(archive_append(j.dm, j.ad, us.far_sel, us.n_sel, bound, s));
+            HIPCHK(map_evict_listed(j.dm, us.far_sel, us.n_sel, bound, s));
+        }
     } else {
         // A map in reference-order mode: the bucket array of the reference's robin_map lives on the host (host_map.hpp,
         // RobinTable); the device inserts and FINDS the far voxels, the host replays the new voxels (arrival order) and the
@@ -492,6 +533,7 @@ int run_pass(UpdateJob &j) {
     }
     HIPCHK(hipMemcpyAsync(d.h_ctr.data(), d.d_ctr.data(), sizeof(MapCounters), hipMemcpyDeviceToHost, s));
     if (h.track_order) HIPCHK(hipMemcpyAsync(d.h_ctr_aux.data(), us.n_sel, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    else if (j.arc) HIPCHK(hipMemcpyAsync(&j.arc_back(), j.arc->d_ctr.data(), sizeof(ArchiveCtr), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return SAGEICP_OK;
 }
@@ -542,8 +584,10 @@ int replay_reference_order(UpdateJob &j) {
         // far_sel <- the erased blocks in the order of their erasure (the order they go onto the free list), n_sel <- their number
         HIPCHK(hipMemcpyAsync(us.n_sel, erased, sizeof(uint32_t), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(us.far_sel, erased + 1, n_er * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        if (j.arc) HIPCHK(archive_append(j.dm, j.ad, us.far_sel, us.n_sel, n_er, s));      // in the order of their erasure
         HIPCHK(map_evict_listed(j.dm, us.far_sel, us.n_sel, n_er, s));
         HIPCHK(hipMemcpyAsync(d.h_ctr.data(), d.d_ctr.data(), sizeof(MapCounters), hipMemcpyDeviceToHost, s));
+        if (j.arc) HIPCHK(hipMemcpyAsync(&j.arc_back(), j.arc->d_ctr.data(), sizeof(ArchiveCtr), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
     } else {
         j.back().n_far = 0;
@@ -555,12 +599,14 @@ int replay_reference_order(UpdateJob &j) {
 // VoxelHashMap::Update(points, pose) on the device.
 // `d_points`: the points are already in HBM (the pipeline's down-sampled frame); else `xyzl` (host).
 int MapDevice::update(HostMap &h, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points,
-                      hipStream_t s) {
+                      hipStream_t s, MapArchive *arc) {
     UpdateJob j{*this, h, xyzl, d_points, n, pose, s};
+    j.arc = arc;
     int rc;
     if (!authority() && (rc = seed_counters(j))) return rc;
     j.needs = update_needs(ctr, n, h, blocks_cap(), units_cap(), d_table.capacity());
     if (j.needs.too_many_voxels) return fail(SAGEICP_ERR_CAPACITY, "more than 2^24 voxels");
+    if (arc && (rc = reserve_archive(j))) return rc;       // (refused here, neither the map nor the log has changed)
     if ((rc = reserve(j))) return rc;
     if (!authority() && !aux_current_for(h) && (rc = upload_aux(j))) return rc;
     if ((rc = send_counters(j))) return rc;
@@ -571,6 +617,10 @@ int MapDevice::update(HostMap &h, const double *xyzl, uint64_t n, const double p
     if (h.track_order && (rc = replay_reference_order(j))) return rc;
     h.clear_dirty();
     became_authority(j.back());
+    if (arc) {                  // the call took its serial; the tail is where the device left it
+        arc->adopt(j.arc_back());
+        ++arc->updates;
+    }
     return SAGEICP_OK;
 }
 
@@ -595,7 +645,7 @@ int device_update(sageicp_map &m, const double *xyzl, uint64_t n, const double p
     int rc = m.sc.init(m.device);
     if (rc) return rc;
     HIPCHK(hipSetDevice(m.device));
-    return m.dev.update(m.host, xyzl, n, pose, d_points, m.sc.stream.get());
+    return m.dev.update(m.host, xyzl, n, pose, d_points, m.sc.stream.get(), m.arc.enabled ? &m.arc : nullptr);
 }
 
 // Non-finite input (NaN / Inf coordinates or labels).  The reference turns such values into voxel

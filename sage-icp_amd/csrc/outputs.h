@@ -74,6 +74,10 @@ struct RowSink {
 // cannot hold, or that has no colour, refuses the call (whatever was written below cap stays written).
 int export_rows(OutputBuffers &ob, int device, const RowSource &src, const RowSink &sink, uint64_t *n_out);
 
+// A map's rows in sageicp_map_pointcloud's order, packed in its d_pc on s (source (b) above, for an export that puts them
+// behind other rows: the session's map, capi_archive.hip).  `staged` lives until s has been waited for.
+int map_packed_rows(sageicp_map &m, hipStream_t s, std::vector<double> &staged, const Point4 **rows);
+
 // a validated destination as the writers of egress.h take it; flags: the device word a label that does not fit is raised in
 EgressArgs egress_args(const sageicp_device_points &d, int *flags);
 

@@ -126,6 +126,11 @@ struct VoxelHashMap {
 
     // ---- not part of the reference surface -------------------------------------------------
     const sageicp_map *handle() const { return map_; }     // used by the Registration.hpp shim
+    // The archive (include/sageicp.h; SAGEICP_MAP_ARCHIVE=1 switches it on for a caller that cannot be changed): every
+    // voxel the map evicted, as recorded, and the session's map — the latest generation of every evicted voxel the map
+    // does not hold, then Pointcloud().
+    Vector4dVector ArchivedPointcloud() const { return ArchiveRows(SAGEICP_ARCHIVE_ALL, "ArchivedPointcloud"); }
+    Vector4dVector SessionPointcloud() const { return ArchiveRows(SAGEICP_SESSION, "SessionPointcloud"); }
     // HIP device ordinal for maps created by this process (one process per GPU); set it before
     // the first map is constructed, e.g. from LOCAL_RANK.
     static int &Device() {
@@ -151,6 +156,13 @@ private:
         if (rc != SAGEICP_OK)
             throw std::runtime_error(std::string("sage_icp::VoxelHashMap::") + what + ": " +
                                      sageicp_last_error());
+    }
+    Vector4dVector ArchiveRows(int which, const char *what) const {
+        uint64_t n = 0;
+        Check(sageicp_map_archive_rows(map_, which, 0, nullptr, 0, &n), what);
+        Vector4dVector out(n);
+        Check(sageicp_map_archive_rows(map_, which, 0, Data(out), out.size(), &n), what);
+        return out;
     }
     void swap(VoxelHashMap &o) noexcept {
         std::swap(voxel_size_, o.voxel_size_);
