@@ -1,5 +1,5 @@
 // Internals shared by the translation units of libsageicp_hip.so's host side (capi.hip, capi_pipeline.hip,
-// capi_outputs.hip, caller_mem.hip, map_device.hip, capi_run.hip, prep.hip): error channel, tuning knobs, the
+// capi_outputs.hip, capi_query.hip, capi_relocalize.hip, caller_mem.hip, map_device.hip, capi_run.hip, prep.hip): error channel, tuning knobs, the
 // per-handle device scratch, the pipeline's frame source and buffers (prep.h) and its prefetch state (prefetch.h), the
 // checks of a caller's device memory (caller_mem.h), the HBM copy of a map (map_device.h), the way out (outputs.h), what
 // follows the search of GetCorrespondences on the device (correspond.h), the registration quality pass (quality.h), the
@@ -442,10 +442,13 @@ struct sageicp_comm {
 };
 
 // ---- the library's translation units call each other through these --------------------------------------
-// capi.hip: the C ABI of maps, frames, communicators and the stand-alone entries.  capi_pipeline.hip: the pipeline
-// handle and its entries.  capi_outputs.hip: rows, records and grids out (outputs.h).  caller_mem.hip: the checks of a
-// caller's device memory (caller_mem.h).  map_device.hip: the HBM copy of a map (MapDevice): mirror refresh, download, copy, Update() on the device.
-// capi_relocalize.hip: the batch score of candidate poses and Relocalize.
+// capi.hip: the C ABI of maps, frames, communicators and the stand-alone entries that ask a map nothing.
+// capi_pipeline.hip: the pipeline handle and its entries.  capi_outputs.hip: rows, records and grids out (outputs.h).
+// caller_mem.hip: the checks of a caller's device memory (caller_mem.h).  map_device.hip: the HBM copy of a map
+// (MapDevice): mirror refresh, download, copy, Update() on the device.
+// capi_query.hip: the one path of the entries that ask a map about a frame — stage, move, sort and search, accept
+// (query.h) — with GetCorrespondences, RegistrationQuality and the host side of the quality report.
+// capi_relocalize.hip: the candidate grid, the chunked batch score of candidate poses and Relocalize, on that path.
 // capi_run.hip: the ICP loop (plan_loop, run_icp and its attempts), the RCCL binding and the single-process multi-GPU
 // mode.
 namespace sageicp_impl {
@@ -466,18 +469,7 @@ int load_rccl();
 int register_resident(sageicp_map &m, const Point4 *d_frame, uint64_t n, int device, const double init[7],
                       double max_dist, double kernel, double sem_th, sageicp_comm *comm, double pose_out[7],
                       sageicp_stats *stats);
-// capi.hip: the quality report of the n rows in m.sc.d_frame (not yet moved by `pose`; written on m.sc's stream)
-int quality_of_scratch_rows(sageicp_map &m, uint64_t n, const double *pose, double max_dist, double kernel, double sem_th,
-                            sageicp_quality *out);
-// capi.hip: the search behind the quality report and the batch score — the n moved rows at d_rows sorted (the verdict on
-// non-finite rows read first), searched, the accepted answer of every query into d_by_query
-int search_rows_by_query(sageicp_map &m, const Point4 *d_rows, uint64_t n, double max_dist, double sem_th,
-                         int32_t *d_by_query, const char *who);
-// capi.hip: the Gauss-Newton step still left and JTJ^-1 (false: none — too few pairs, a pivot below the bound, not finite)
-struct QualitySolve {
-    double step[6], step_norm, inv[6][6], s2;
-};
-bool quality_solve(const double JTJ[36], const double JTr[6], double sum_w_r2, uint64_t n_pairs, QualitySolve *o);
+// (capi_query.hip: query.h)
 // map_device.hip: the handle's device made current, its stream and host copy handed to MapDevice
 int refresh_mirror(sageicp_map &m);
 int ensure_host(sageicp_map &m);

@@ -5,6 +5,7 @@
 // registration and the map update are capi.hip's and capi_run.hip's.  Then the key-frame step, the exported source
 // cloud (through outputs.h's driver) and the switches.  Host code only.  Part of libsageicp_hip.so's host side: capi_internal.h.
 #include "capi_internal.h"
+#include "query.h"
 
 extern "C" {
 
@@ -219,11 +220,9 @@ static int pipeline_register(sageicp_pipeline *p, const FrameSource &src, double
             if (!(std::isfinite(kernel) && kernel > 0.0) || !finite_n(pose, 7)) return SAGEICP_OK;
             int rc = refresh_mirror(m);
             if (rc) return rc;
-            if ((rc = m.sc.reserve_frame(n))) return rc;
-            HIPCHK(hipMemcpyAsync(m.sc.d_frame.data(), p->prep[p->cur].d_src.data(), n * sizeof(Point4),
-                                  hipMemcpyDeviceToDevice, m.sc.stream.get()));
             sageicp_quality q;
-            if ((rc = quality_of_scratch_rows(m, n, pose, max_dist, kernel, sem_th, &q))) return rc;
+            if ((rc = quality_of_device_rows(m, p->prep[p->cur].d_src.data(), n, pose, max_dist, kernel, sem_th, &q)))
+                return rc;
             p->quality = q;
             return SAGEICP_OK;
         }

@@ -1,9 +1,9 @@
 // A batch of candidate poses scored in one pass, and Relocalize on top of it (include/sageicp.h; score.h; DESIGN.md
 // D14): the host side.  The frame's pristine rows live in Scratch::d_score_frame for the whole call — uploaded or
 // ingested once —; the candidates are taken in chunks of max(1, chunk_rows / n), each chunk moved (k_score_move),
-// searched by the sequence the quality report uses (search_rows_by_query, capi.hip) and summed (k_score,
-// k_score_reduce); score_finish derives what sageicp_registration_quality derives, through the same solve.
-#include "capi_internal.h"
+// searched and accepted by the steps the quality report uses (QueryCall, query.h) and summed (k_score,
+// k_score_reduce); score_finish derives what sageicp_registration_quality derives, through the same code.
+#include "query.h"
 
 #include <algorithm>
 
@@ -15,30 +15,11 @@ static_assert(sizeof(sageicp_relocalize_params) == 80 && sizeof(sageicp_relocali
 constexpr uint64_t kMaxCandidates = 1ull << 20;
 constexpr uint32_t kMaxRefine = 16;
 
-// one candidate's fields from what the kernels left: quality_finish's formulas on the same sums (capi.hip)
+// one candidate's fields from what the kernels left
 static void score_finish(const ScoreRaw &r, uint64_t n, sageicp_pose_score *q) {
-    std::memset(q, 0, sizeof(*q));
-    q->valid = 1;
-    q->n_queries = n;
-    q->n_pairs = r.counts[kQPairs];
-    q->pairs_same_label = r.counts[kQSame];
-    q->pairs_unlabelled = r.counts[kQUnlabelled];
-    q->pairs_cross_label = r.counts[kQCross];
-    q->sum_r2 = r.real[kQR2];
-    q->sum_w = r.real[kW];
-    q->sum_w_r2 = r.real[kQWR2];
-    q->score = q->sum_w;
-    double sums[kNumSums] = {};
-    for (int c = 0; c < kCount; ++c) sums[c] = r.real[c];
-    assemble_normal_equations(sums, q->JTJ, q->JTr);
-    const double np = static_cast<double>(q->n_pairs);
-    q->fitness = np / static_cast<double>(n);
-    q->rmse = q->n_pairs ? std::sqrt(q->sum_r2 / np) : 0.0;
     QualitySolve sol;
-    if (!quality_solve(q->JTJ, q->JTr, q->sum_w_r2, q->n_pairs, &sol)) return;
-    for (int i = 0; i < 6; ++i) q->step[i] = sol.step[i];
-    q->step_norm = sol.step_norm;
-    q->step_valid = 1;
+    q->step_valid = derive_shared(r, n, q, &sol) ? 1 : 0;
+    q->score = q->sum_w;
 }
 
 // what every scoring entry refuses before any device is asked (k > 0)
@@ -58,10 +39,9 @@ static int check_score_args(const char *who, const sageicp_map *map, const doubl
 
 // The scores of k candidates for the n pristine rows in m.sc.d_score_frame (n > 0, a map that is not empty, the mirror
 // current): staged in `out`, which the caller copies out once everything has succeeded.
-static int score_resident(sageicp_map &m, uint64_t n, const double *poses, uint64_t k, double max_dist, double kernel,
-                          double sem_th, sageicp_pose_score *out, const char *who) {
-    Scratch &sc = m.sc;
-    hipStream_t s = sc.stream.get();
+static int score_staged(QueryCall &c, uint64_t n, const double *poses, uint64_t k, double max_dist, double kernel,
+                        double sem_th, sageicp_pose_score *out) {
+    Scratch &sc = c.sc;
     uint64_t chunk_rows = static_cast<uint64_t>(std::max(1, env_int("SAGEICP_SCORE_CHUNK_ROWS", 1 << 20)));
     chunk_rows = std::min<uint64_t>(chunk_rows, kMaxQueries);
     const uint64_t per_chunk = std::max<uint64_t>(1, chunk_rows / n);
@@ -72,17 +52,15 @@ static int score_resident(sageicp_map &m, uint64_t n, const double *poses, uint6
         if ((rc = sc.reserve_sort(rows))) return rc;
         if ((rc = sc.reserve_score(n, kc))) return rc;
         ScorePose *hp = sc.h_score_poses.data();
-        for (uint64_t c = 0; c < kc; ++c) {
-            const double *p = poses + 7 * (c0 + c);
-            quat_to_mat(p, hp[c].R);
-            hp[c].t[0] = p[4]; hp[c].t[1] = p[5]; hp[c].t[2] = p[6];
+        for (uint64_t i = 0; i < kc; ++i) {
+            const double *p = poses + 7 * (c0 + i);
+            quat_to_mat(p, hp[i].R);
+            hp[i].t[0] = p[4]; hp[i].t[1] = p[5]; hp[i].t[2] = p[6];
         }
-        HIPCHK(hipMemcpyAsync(sc.d_score_poses.data(), hp, kc * sizeof(ScorePose), hipMemcpyHostToDevice, s));
-        double I[7];
-        identity_pose(I);
-        fill_state(sc.h_state.data(), I);
-        HIPCHK(hipMemcpyAsync(sc.d_state.data(), sc.h_state.data(), sizeof(IcpState), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemsetAsync(sc.d_score_raw.data(), 0, kc * sizeof(ScoreRaw), s));
+        HIPCHK(hipMemcpyAsync(sc.d_score_poses.data(), hp, kc * sizeof(ScorePose), hipMemcpyHostToDevice, c.stream()));
+        // (the search's state: the rows are moved by their candidates, k_score_move, not by it)
+        if ((rc = c.move(sc.d_score_rows.data(), rows, nullptr))) return rc;
+        HIPCHK(hipMemsetAsync(sc.d_score_raw.data(), 0, kc * sizeof(ScoreRaw), c.stream()));
         ScoreArgs a{};
         a.n = static_cast<int>(n);
         a.kc = static_cast<uint32_t>(kc);
@@ -93,44 +71,26 @@ static int score_resident(sageicp_map &m, uint64_t n, const double *poses, uint6
         a.kernel = kernel;
         a.slabs = sc.d_score_slabs.data();
         a.out = sc.d_score_raw.data();
-        launch_score_move(a, s);
+        launch_score_move(a, c.stream());
         HIPCHK(hipGetLastError());
-        // one search over the chunk's rows: whatever fails in it, the stream is idle when it returns
-        rc = search_rows_by_query(m, sc.d_score_rows.data(), rows, max_dist, sem_th, sc.d_score_by_query.data(), who);
-        if (rc) {
-            (void)hipStreamSynchronize(s);
-            return rc;
-        }
-        a.pts = m.dev.search_view().pts;
-        launch_score(a, s);
+        // one search over the chunk's rows
+        if ((rc = c.sort_and_search(sc.d_score_rows.data(), rows, sem_th))) return rc;
+        if ((rc = c.accept(rows, max_dist, sc.d_score_by_query.data()))) return rc;
+        a.pts = c.m.dev.search_view().pts;
+        launch_score(a, c.stream());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(sc.h_score_raw.data(), sc.d_score_raw.data(), kc * sizeof(ScoreRaw), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        for (uint64_t c = 0; c < kc; ++c) score_finish(sc.h_score_raw.data()[c], n, out + c0 + c);
+        HIPCHK(hipMemcpyAsync(sc.h_score_raw.data(), sc.d_score_raw.data(), kc * sizeof(ScoreRaw), hipMemcpyDeviceToHost,
+                              c.stream()));
+        if ((rc = c.wait())) return rc;
+        for (uint64_t i = 0; i < kc; ++i) score_finish(sc.h_score_raw.data()[i], n, out + c0 + i);
     }
     return SAGEICP_OK;
 }
 
-// the frame of a host entry into d_score_frame (enqueued; the next synchronisation of the stream covers it)
-static int upload_score_frame(sageicp_map &m, const double *xyzl, uint64_t n) {
-    Scratch &sc = m.sc;
-    if (int rc = sc.reserve_score_frame(n)) return rc;
-    HIPCHK(hipMemcpyAsync(sc.d_score_frame.data(), xyzl, n * sizeof(Point4), hipMemcpyHostToDevice, sc.stream.get()));
-    return SAGEICP_OK;
-}
-
-// the frame of a device entry, whole, into d_score_frame, behind the work that wrote it; waited for also when the
-// enqueue failed: afterwards nothing reads the caller's memory
-static int ingest_score_frame(sageicp_map &m, const sageicp_device_frame &frame, void *stream) {
-    Scratch &sc = m.sc;
-    if (int rc = sc.reserve_score_frame(frame.n)) return rc;
-    hipStream_t s = sc.stream.get();
-    if (int rc = stream_after_caller(m.out.ev_caller, static_cast<hipStream_t>(stream), s)) return rc;
-    launch_ingest(ingest_args(frame), sc.d_score_frame.data(), s);
-    const hipError_t launched = hipGetLastError(), waited = hipStreamSynchronize(s);
-    HIPCHK(launched);
-    HIPCHK(waited);
-    return SAGEICP_OK;
+// the frame of a scoring entry, whole, into d_score_frame, where it stays pristine for the whole call
+static int stage_score_frame(QueryCall &c, const FrameSource &src) {
+    if (int rc = c.sc.reserve_score_frame(src.n)) return rc;
+    return c.stage(src, c.sc.d_score_frame.data());
 }
 
 // ---- candidates ---------------------------------------------------------------------------------------------------------
@@ -199,25 +159,20 @@ static void write_candidates(const double prior[7], const sageicp_relocalize_par
 }
 
 // ---- Relocalize ---------------------------------------------------------------------------------------------------------
-// the quality report of the pristine rows at `pose`: the rows copied into d_frame, where the report moves them
-static int quality_of_score_frame(sageicp_map &m, uint64_t n, const double *pose, const sageicp_relocalize_params &p,
-                                  sageicp_quality *out) {
-    Scratch &sc = m.sc;
-    if (int rc = sc.reserve_frame(n)) return rc;
-    HIPCHK(hipMemcpyAsync(sc.d_frame.data(), sc.d_score_frame.data(), n * sizeof(Point4), hipMemcpyDeviceToDevice,
-                          sc.stream.get()));
-    return quality_of_scratch_rows(m, n, pose, p.max_correspondence_distance, p.kernel, p.sem_th, out);
-}
-
 // steps 2-5 of sageicp_relocalize on the n rows in m.sc.d_score_frame (n > 0, a map that is not empty, mirror current)
-static int relocalize_resident(sageicp_map &m, uint64_t n, const std::vector<double> &cands,
-                               const sageicp_relocalize_params &p, double pose_out[7], sageicp_quality *quality_out,
-                               sageicp_relocalize_info *info) {
+static int relocalize_staged(QueryCall &c, uint64_t n, const std::vector<double> &cands,
+                             const sageicp_relocalize_params &p, double pose_out[7], sageicp_quality *quality_out,
+                             sageicp_relocalize_info *info) {
+    sageicp_map &m = c.m;
+    const Point4 *d_rows = m.sc.d_score_frame.data();
+    // the quality report of the pristine rows at `pose`
+    auto quality_at = [&](const double *pose, sageicp_quality *q) {
+        return quality_of_device_rows(m, d_rows, n, pose, p.max_correspondence_distance, p.kernel, p.sem_th, q);
+    };
     const uint64_t K = cands.size() / 7;
     const double t0 = now_us();
     std::vector<sageicp_pose_score> scores(K);
-    int rc = score_resident(m, n, cands.data(), K, p.max_correspondence_distance, p.kernel, p.sem_th, scores.data(),
-                            "Relocalize");
+    int rc = score_staged(c, n, cands.data(), K, p.max_correspondence_distance, p.kernel, p.sem_th, scores.data());
     if (rc) return rc;
     const double t1 = now_us();
     // the ranking: score descending, ties to the lower index; only the first few are needed
@@ -226,8 +181,8 @@ static int relocalize_resident(sageicp_map &m, uint64_t n, const std::vector<dou
     std::vector<char> taken(K, 0);
     for (uint32_t r = 0; r < top; ++r) {
         uint64_t best = K;
-        for (uint64_t c = 0; c < K; ++c)
-            if (!taken[c] && (best == K || scores[c].score > scores[best].score)) best = c;
+        for (uint64_t i = 0; i < K; ++i)
+            if (!taken[i] && (best == K || scores[i].score > scores[best].score)) best = i;
         taken[best] = 1;
         ranked.push_back(best);
     }
@@ -237,7 +192,7 @@ static int relocalize_resident(sageicp_map &m, uint64_t n, const std::vector<dou
     I.candidates = K;
     if (p.refine_top == 0) {
         std::memcpy(pose, cands.data() + 7 * ranked[0], 56);
-        if ((rc = quality_of_score_frame(m, n, pose, p, &quality))) return rc;
+        if ((rc = quality_at(pose, &quality))) return rc;
         I.best_candidate = ranked[0];
         I.best_candidate_score = scores[ranked[0]].score;
     } else {
@@ -246,10 +201,12 @@ static int relocalize_resident(sageicp_map &m, uint64_t n, const std::vector<dou
             double refined[7];
             sageicp_stats st;
             sageicp_quality q;
-            if ((rc = register_resident(m, m.sc.d_score_frame.data(), n, m.device, cands.data() + 7 * ranked[r],
-                                        p.max_correspondence_distance, p.kernel, p.sem_th, nullptr, refined, &st)))
+            if ((rc = register_resident(m, d_rows, n, m.device, cands.data() + 7 * ranked[r],
+                                        p.max_correspondence_distance, p.kernel, p.sem_th, nullptr, refined, &st))) {
+                (void)c.stream();              // (an ICP loop that failed may have left work on it)
                 return rc;
-            if ((rc = quality_of_score_frame(m, n, refined, p, &q))) return rc;
+            }
+            if ((rc = quality_at(refined, &q))) return rc;
             ++I.refined;
             if (!have || q.sum_w > quality.sum_w) {
                 have = true;
@@ -285,6 +242,39 @@ static int relocalize_nothing(const double prior[7], uint64_t K, double pose_out
     return SAGEICP_OK;
 }
 
+// both ScorePoses entries behind their argument checks
+static int score_poses(const sageicp_map *map, const FrameSource &src, const double *poses, uint64_t k, double max_dist,
+                       double kernel, double sem_th, sageicp_pose_score *out) {
+    sageicp_map &m = internal(map);
+    if (src.n == 0 || m.empty()) {
+        std::memset(out, 0, k * sizeof(*out));
+        return SAGEICP_OK;
+    }
+    int rc = refresh_mirror(m);          // (makes the device current; a resident map stays resident)
+    if (rc) return rc;
+    QueryCall c(m, "ScorePoses");
+    if ((rc = stage_score_frame(c, src))) return rc;
+    std::vector<sageicp_pose_score> staged(k);
+    if ((rc = score_staged(c, src.n, poses, k, max_dist, kernel, sem_th, staged.data()))) return rc;
+    std::memcpy(out, staged.data(), k * sizeof(*out));
+    return SAGEICP_OK;
+}
+
+// both Relocalize entries behind their argument checks
+static int relocalize(const sageicp_map *map, const FrameSource &src, const double prior[7],
+                      const sageicp_relocalize_params &p, const CandidateGrid &g, double pose_out[7],
+                      sageicp_quality *quality_out, sageicp_relocalize_info *info) {
+    sageicp_map &m = internal(map);
+    if (src.n == 0 || m.empty()) return relocalize_nothing(prior, g.count, pose_out, quality_out, info);
+    std::vector<double> cands(7 * g.count);
+    write_candidates(prior, p, g, cands.data(), g.count);
+    int rc = refresh_mirror(m);
+    if (rc) return rc;
+    QueryCall c(m, "Relocalize");
+    if ((rc = stage_score_frame(c, src))) return rc;
+    return relocalize_staged(c, src.n, cands, p, pose_out, quality_out, info);
+}
+
 }  // namespace sageicp_impl
 
 extern "C" {
@@ -294,25 +284,8 @@ int sageicp_score_poses(const sageicp_map *map, const double *xyzl, uint64_t n, 
     if (k == 0) return SAGEICP_OK;
     int rc = check_score_args("ScorePoses", map, poses, k, kernel, out);
     if (rc) return rc;
-    if (n && !xyzl) return fail(SAGEICP_ERR_INVALID, "ScorePoses: xyzl is NULL");
-    if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "ScorePoses: too many rows (2^26 - 4 max)");
-    if (!all_finite(xyzl, n))
-        return fail(SAGEICP_ERR_INVALID, "ScorePoses: a coordinate or label of a row is not finite (NaN / Inf)");
-    sageicp_map &m = internal(map);
-    if (n == 0 || m.empty()) {
-        std::memset(out, 0, k * sizeof(*out));
-        return SAGEICP_OK;
-    }
-    if ((rc = refresh_mirror(m))) return rc;          // (makes the device current; a resident map stays resident)
-    if ((rc = upload_score_frame(m, xyzl, n))) return rc;
-    std::vector<sageicp_pose_score> staged(k);
-    rc = score_resident(m, n, poses, k, max_dist, kernel, sem_th, staged.data(), "ScorePoses");
-    if (rc) {
-        (void)hipStreamSynchronize(m.sc.stream.get());       // (the upload reads the caller's rows)
-        return rc;
-    }
-    std::memcpy(out, staged.data(), k * sizeof(*out));
-    return SAGEICP_OK;
+    if ((rc = check_host_rows("ScorePoses", xyzl, n))) return rc;
+    return score_poses(map, FrameSource::host_rows(xyzl, n), poses, k, max_dist, kernel, sem_th, out);
 }
 
 int sageicp_score_poses_device(const sageicp_map *map, const sageicp_device_frame *frame, const double *poses, uint64_t k,
@@ -320,23 +293,9 @@ int sageicp_score_poses_device(const sageicp_map *map, const sageicp_device_fram
     if (k == 0) return SAGEICP_OK;
     int rc = check_score_args("ScorePoses", map, poses, k, kernel, out);
     if (rc) return rc;
-    if (!frame) return fail(SAGEICP_ERR_INVALID, "ScorePoses: frame is NULL");
-    if ((rc = check_frame_layout(frame))) return rc;
-    // where the memory lives, and the stream
-    if ((rc = check_device_frame(frame, nullptr, stream, map->device))) return rc;
-    if ((rc = check_stream(stream, map->device))) return rc;
-    sageicp_map &m = internal(map);
-    const uint64_t n = frame->n;
-    if (n == 0 || m.empty()) {
-        std::memset(out, 0, k * sizeof(*out));
-        return SAGEICP_OK;
-    }
-    if ((rc = refresh_mirror(m))) return rc;          // (makes the device current)
-    if ((rc = ingest_score_frame(m, *frame, stream))) return rc;
-    std::vector<sageicp_pose_score> staged(k);
-    if ((rc = score_resident(m, n, poses, k, max_dist, kernel, sem_th, staged.data(), "ScorePoses"))) return rc;
-    std::memcpy(out, staged.data(), k * sizeof(*out));
-    return SAGEICP_OK;
+    if ((rc = check_device_source("ScorePoses", map, frame, stream))) return rc;
+    return score_poses(map, FrameSource::device_frame(frame, nullptr, static_cast<hipStream_t>(stream)), poses, k,
+                       max_dist, kernel, sem_th, out);
 }
 
 int sageicp_relocalize_candidates(const double prior[7], const sageicp_relocalize_params *params, double *poses_out,
@@ -358,17 +317,8 @@ int sageicp_relocalize(const sageicp_map *map, const double *xyzl, uint64_t n, c
     if (rc) return rc;
     if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "Relocalize: too many rows (2^26 - 4 max)");
     if (!(params->kernel > 0.0)) return fail(SAGEICP_ERR_INVALID, "Relocalize: kernel must be finite and above 0");
-    if (!all_finite(xyzl, n))
-        return fail(SAGEICP_ERR_INVALID, "Relocalize: a coordinate or label of a row is not finite (NaN / Inf)");
-    sageicp_map &m = internal(map);
-    if (n == 0 || m.empty()) return relocalize_nothing(prior, g.count, pose_out, quality_out, info);
-    std::vector<double> cands(7 * g.count);
-    write_candidates(prior, *params, g, cands.data(), g.count);
-    if ((rc = refresh_mirror(m))) return rc;
-    if ((rc = upload_score_frame(m, xyzl, n))) return rc;
-    rc = relocalize_resident(m, n, cands, *params, pose_out, quality_out, info);
-    if (rc) (void)hipStreamSynchronize(m.sc.stream.get());
-    return rc;
+    if (!all_finite(xyzl, n)) return refuse_non_finite("Relocalize", "row");
+    return relocalize(map, FrameSource::host_rows(xyzl, n), prior, *params, g, pose_out, quality_out, info);
 }
 
 int sageicp_relocalize_device(const sageicp_map *map, const sageicp_device_frame *frame, const double prior[7],
@@ -379,17 +329,9 @@ int sageicp_relocalize_device(const sageicp_map *map, const sageicp_device_frame
     int rc = candidate_grid(prior, params, &g);
     if (rc) return rc;
     if (!(params->kernel > 0.0)) return fail(SAGEICP_ERR_INVALID, "Relocalize: kernel must be finite and above 0");
-    if ((rc = check_frame_layout(frame))) return rc;
-    if ((rc = check_device_frame(frame, nullptr, stream, map->device))) return rc;
-    if ((rc = check_stream(stream, map->device))) return rc;
-    sageicp_map &m = internal(map);
-    const uint64_t n = frame->n;
-    if (n == 0 || m.empty()) return relocalize_nothing(prior, g.count, pose_out, quality_out, info);
-    std::vector<double> cands(7 * g.count);
-    write_candidates(prior, *params, g, cands.data(), g.count);
-    if ((rc = refresh_mirror(m))) return rc;
-    if ((rc = ingest_score_frame(m, *frame, stream))) return rc;
-    return relocalize_resident(m, n, cands, *params, pose_out, quality_out, info);
+    if ((rc = check_device_source("Relocalize", map, frame, stream))) return rc;
+    return relocalize(map, FrameSource::device_frame(frame, nullptr, static_cast<hipStream_t>(stream)), prior, *params, g,
+                      pose_out, quality_out, info);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // What follows the search of GetCorrespondences on the device (correspond.hip): the acceptance test, the ordered
 // compaction of the accepted pairs into the reference's order (VoxelHashMap.cpp:119-127: query order), the gather of the
 // target rows from the HBM copy of the map and the write into a caller's layouts (egress.h).  Launch interface between
-// capi.hip (host side) and correspond.hip; the search itself is kernels.hip's, unchanged.
+// capi_query.hip (host side) and correspond.hip; the search itself is kernels.hip's, unchanged.
 //
 // Positions come from a scan and from nothing else: a workgroup of kCorrBlock consecutive queries counts its accepted
 // ones (wave ballot + popcount), ONE workgroup scans the counts in tiles of kCorrScanTile with a running carry, and a

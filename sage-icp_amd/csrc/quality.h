@@ -2,7 +2,7 @@
 // (correspond.hip), that forms every sum of sageicp_quality (include/sageicp.h) over the accepted pairs — the
 // Gauss-Newton sums of AlignClouds (Registration.cpp:59-94), the squared residuals, the unweighted moments of the moved
 // queries, the counts, the split of the pairs by the label rule of VoxelHashMap.cpp:88 and the per-class tables.  Launch
-// interface between capi.hip (host side: quality_finish turns the sums into fitness, rmse, step and covariances) and
+// interface between capi_query.hip (host side: quality_finish turns the sums into fitness, rmse, step and covariances) and
 // quality.hip; the search itself is kernels.hip's, unchanged.
 //
 // Reduction.  No floating-point atomic anywhere.  At most kQualGroups workgroups take the tiles of

@@ -1,7 +1,7 @@
 """Pairs ON the acceptance radius (tests/acceptscenes.py): every site that evaluates (nn - p).norm() < max_dist — the fused
 epilogue of the search (csrc/icp_body.h: k_icp, the chained launches, k_loop, at every lane width and in both scan forms),
 k_corr_flag (csrc/correspond.hip: GetCorrespondences on device frames, the quality report, ScorePoses) and the host entry's
-own sqrt form (csrc/capi.hip) — against the oracle, which follows the same build switch.  Every comparison is for equality.
+own sqrt form (csrc/capi_query.hip) — against the oracle, which follows the same build switch.  Every comparison is for equality.
 
 Rows lie within 4 ulps of T = accept_threshold(max_dist) on either side, many exactly on it and on its successor, and
 hundreds of them change sides with the association of the three squares: a threshold one ulp off, `<` for `<=`, the other
