@@ -1,7 +1,9 @@
 """Where does an iteration of the one-launch loop wait?  Timeline per workgroup from a -DSAGE_LOOP_TIMING build
 (sage-icp_amd/_probe/libsageicp_looptiming.so): when it held the pose, when one of its waves took a unit beyond one
 per wave and when it finished it, when the workgroup counted itself in — split by units owned and by CU population.
-    python profiles/loop_tail.py [divisor 1] [cold|steady] [workload c2]"""
+    python profiles/loop_tail.py [divisor 1] [cold|steady] [workload c2 | ring]
+(ring: the ring-geometry family of ring_probe.py, every divisor-th point of its scan.)  The last lines give what a unit
+cost by its rank in the workgroup's order and one `deal-input:` line of JSON: the input of profiles/deal_table.py."""
 import ctypes as C
 import os
 import sys
@@ -16,13 +18,21 @@ from sage_icp_amd import synthetic as syn  # noqa: E402
 div = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 p = syn.PARAMS[sys.argv[2] if len(sys.argv) > 2 else "cold"]
 name = sys.argv[3] if len(sys.argv) > 3 else "c2"
-w = syn.make_workload(name, lambda: sage.VoxelHashMap(syn.WORKLOADS[name]["voxel"], 100.0))
-n = len(w["scan"]) // div
-f = sage.Frame(w["map"], w["scan"][:n])
+guess = sage.IDENTITY
+if name == "ring":
+    w = syn.make_ring_workload(lambda: sage.VoxelHashMap(1.0, 100.0), n_map_scans=40)
+    scan = np.ascontiguousarray(w["scan"][::div])
+    guess = w["T_gt"].copy()
+    guess[4] -= 0.5
+else:
+    w = syn.make_workload(name, lambda: sage.VoxelHashMap(syn.WORKLOADS[name]["voxel"], 100.0))
+    scan = w["scan"][:len(w["scan"]) // div]
+n = len(scan)
+f = sage.Frame(w["map"], scan)
 os.environ["SAGEICP_LOOP"] = "2"
 sage.set_counting(False)
 for _ in range(3):
-    pose, st = sage.register_frame(f, w["map"], sage.IDENTITY, p["max_dist"], p["kernel"], p["sem_th"], return_stats=True)
+    pose, st = sage.register_frame(f, w["map"], guess, p["max_dist"], p["kernel"], p["sem_th"], return_stats=True)
 assert st.single_launch == 1
 IT, WG = 32, 2048
 wg = np.zeros((IT, WG, 4), dtype=np.uint64)
@@ -134,3 +144,57 @@ if hasattr(sage.lib(), "sageicp_debug_loop_waves"):
         print("   %d SIMDs: waves per SIMD histogram %s; heaviest units (unit 0) per SIMD histogram %s" % (len(keys), np.bincount(cnt.astype(int)).tolist(), np.bincount(heavy.astype(int)).tolist()))
         for h in sorted(set(heavy.astype(int))):
             print("      SIMDs with %d heaviest units: %d, last first-unit ends mean %.2f max %.2f" % (h, (heavy == h).sum(), last[heavy == h].mean(), last[heavy == h].max()))
+        # the same by the SIMD's index within its CU, CUs of six and of seven workgroups apart: what the deal's rows for
+        # a CU's fifth to seventh workgroup (csrc/loop_deal.h) are about
+        cuk, cui = np.unique(key[:, 0] >> 2, return_inverse=True)
+        pop_of_cu = dict(zip(cuk.tolist(), np.bincount(cui).tolist()))
+        spop = np.array([pop_of_cu[int(k) >> 2] for k in keys])
+        sidx = (keys & 3).astype(int)
+        for k in sorted(set(spop.tolist())):
+            if (spop == k).sum() < 16:
+                continue
+            print("      CUs of %d workgroups, last first-unit ends by SIMD index, mean (max): " % k + "  ".join(
+                "SIMD %d %.2f (%.2f)" % (s, last[(spop == k) & (sidx == s)].mean(), last[(spop == k) & (sidx == s)].max()) for s in range(4))
+                + "  | gap between the SIMD means %.2f" % (max(last[(spop == k) & (sidx == s)].mean() for s in range(4))
+                                                          - min(last[(spop == k) & (sidx == s)].mean() for s in range(4))))
+
+# ---- per unit: what it cost by the kernel's own measure (the heaviest query's points), by rank in the workgroup's order
+if hasattr(sage.lib(), "sageicp_debug_loop_unit_work") and hasattr(sage.lib(), "sageicp_debug_loop_waves"):
+    import json
+    uw = np.zeros((IT, WG, 8), dtype=np.uint32)
+    sage.lib().sageicp_debug_loop_unit_work(uw.ctypes.data_as(C.c_void_p))
+    its = [i for i in range(4, min(IT, st.iterations))]
+    work = uw[its][:, used].astype(np.float64)                       # [iteration][workgroup][unit]
+    nwv = int((wv[its[0]][used][0, :, 0] > 0).sum())
+    has5 = work[:, :, nwv] > 0
+    rec = {"input": "%s-%s-%d" % (name, sys.argv[2] if len(sys.argv) > 2 else "cold", n), "queries": n, "lanes_per_query": int(st.lanes_per_query),
+           "waves": nwv, "workgroups": nwg, "iterations_used": len(its), "fifth_share": float(has5.mean()),
+           "deal": os.environ.get("SAGEICP_LOOP_DEAL", "1")}
+    print("unit work (the most points one of the unit's queries was handed), iterations %d-%d, by rank:" % (its[0], its[-1]))
+    rec["work_mean"], rec["work_sd"] = [], []
+    for u in range(nwv + 1):
+        x = work[:, :, u][has5] if u == nwv else work[:, :, u].ravel()
+        x = x[x > 0]
+        rec["work_mean"].append(float(x.mean()) if len(x) else 0.0)
+        rec["work_sd"].append(float(x.std()) if len(x) else 0.0)
+        print("   %s: %d units, mean %.1f sd %.1f p10 %.0f p50 %.0f p90 %.0f" % ("rank %d" % u if u < nwv else "the unit beyond one per wave", len(x),
+              rec["work_mean"][-1], rec["work_sd"][-1], q(x, .1), q(x, .5), q(x, .9)))
+    # the units beyond one per wave run at one priority (3) and start when the SIMDs have emptied a little: how long one
+    # lasts against its work, in bins of 20 points — profiles/deal_table.py fits the cost model to these
+    s2a, e2a = wg[its][:, used, 2], wg[its][:, used, 3]
+    ok = has5 & (s2a > 0) & (e2a > s2a)
+    lasts, w5 = (e2a - s2a)[ok], work[:, :, nwv][ok]
+    rec["extra_bins"] = []
+    for lo in range(0, 400, 20):
+        sel = (w5 >= lo) & (w5 < lo + 20)
+        if sel.sum() >= 20:
+            rec["extra_bins"].append([int(sel.sum()), float(w5[sel].mean()), float(lasts[sel].mean())])
+    print("   units beyond one per wave, lasts by work: " + "; ".join("%.0f pts: %.2f us (%d)" % (b[1], b[2], b[0]) for b in rec["extra_bins"]))
+    # which wave of a workgroup takes the unit beyond one per wave: the one whose first unit ended first (by its rank)
+    recs = wv[its][:, used][:, :, :nwv]
+    ends = recs[..., 0].astype(np.float64)
+    ranks = ((recs[..., 1] >> np.uint64(16)) & np.uint64(0xFF)).astype(int)
+    first = np.take_along_axis(ranks, np.argmin(np.where(ends > 0, ends, np.inf), axis=2)[..., None], axis=2)[..., 0]
+    rec["first_done_by_rank"] = [float((first[has5] == r).mean()) if has5.any() else 0.0 for r in range(nwv)]
+    print("   the wave that ends its first unit first holds rank: " + " ".join("%d: %.2f" % (r, p_) for r, p_ in enumerate(rec["first_done_by_rank"])))
+    print("deal-input: " + json.dumps(rec))

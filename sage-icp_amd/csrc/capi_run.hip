@@ -472,7 +472,7 @@ static LoopParams solver_params(const IcpCall &c, const AttemptPlan &p, double a
             if (L.contiguous == 1 && (L.xcd_first[x + 1] - L.xcd_first[x] + nwg - 1) / nwg > static_cast<uint64_t>(p.loop.gpw)) L.contiguous = 0;
         L.count_timeout_ticks = L.timeout_ticks;       // (the solving wave's wait for its own workgroups: local, short)
         L.prio = std::min(3, std::max(0, env_int("SAGEICP_LOOP_PRIO", 3)));
-        L.deal = env_int("SAGEICP_LOOP_DEAL", 1) ? 1 : 0;
+        L.deal = std::min(2, std::max(0, env_int("SAGEICP_LOOP_DEAL", 1)));       // 1: loop_deal.h's table | 2: the formula alone | 0: no deal
     }
     if (c.comm) {
         // (under a communicator the workgroups — or a chained launch — wait for a pose that waits for the peers' sums:

@@ -215,8 +215,9 @@ struct LoopParams {
                                    // this rank's loop on its own (the ranks must keep exchanging in step)
     int prio;                      // wave priorities by the work of a wave's unit (kernels.hip, k_loop): 0 off | 1..3: on, the
                                    // priority of a unit beyond one per wave
-    int deal;                      // 1: a wave's FIRST unit of an iteration is fixed by where the wave sits — unit (SIMD +
-                                   // the workgroup's slot on the CU) mod waves — instead of first come first served (k_loop)
+    int deal;                      // 1, 2: a wave's FIRST unit of an iteration is fixed by where the wave sits instead of first
+                                   // come first served (k_loop) — 2: unit (SIMD + the workgroup's slot on the CU) mod waves; 1:
+                                   // the same for slots 0-3, loop_deal.h's table for the slots of a CU's fifth workgroup on
     int copies;                    // accumulator copies the workgroups add into: kLoopReplicas (k_loop: LoopShared::acc) or
                                    // kChainReplicas (chained k_icp launches: LoopShared::acc32)
     int pose_map;                  // which copy of the pose workgroup b polls (loop_pose_copy): 0: b & 7 | 1: copy 0 | 2: (b + 3) & 7

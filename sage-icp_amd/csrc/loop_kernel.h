@@ -3,6 +3,8 @@
 // words of the LDS header, LoopLds — is defined in kernels.hip ahead of both).
 #pragma once
 
+#include "loop_deal.h"
+
 namespace sageicp {
 
 // ------------------------------------------------------------------------------------ k_loop
@@ -447,9 +449,14 @@ void k_loop(LoopArgs A) {
         // other workgroups of its CU on one SIMD: a workgroup's four waves sit on the four SIMDs, one wave of every
         // workgroup of the CU per SIMD, and a SIMD's issue slots are what its waves share.  Workgroup r of the CU
         // (its waves' slot number) hands unit (s + r) mod waves to its wave on SIMD s: every SIMD gets the same mix.
+        // That holds for the first four workgroups of a CU; the rows of the fifth to the seventh come from a table that
+        // levels what goes WITH the second heaviest unit two or three SIMDs then hold (loop_deal.h; L.deal == 2: the
+        // formula for every row).
         unsigned hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        smem[kLpFirst + static_cast<unsigned>(wv)] = (((hw >> 4) & 3u) + (hw & 15u)) % static_cast<unsigned>(nw);
+        const unsigned simd = (hw >> 4) & 3u, slot = hw & 15u;
+        smem[kLpFirst + static_cast<unsigned>(wv)] = L.deal == 2 ? loopdeal::formula(simd, slot, static_cast<unsigned>(nw))
+                                                                 : loopdeal::loop_deal_unit(simd, slot, static_cast<unsigned>(nw));
     }
     for (unsigned i = threadIdx.x; i < 2u * kWgAccWords; i += blockDim.x) smem[kLpAcc + i] = 0u;
     for (unsigned i = threadIdx.x; i < nblk_max; i += blockDim.x) {
@@ -622,6 +629,7 @@ void k_loop(LoopArgs A) {
                 PROBE_LOOP_PASS_BEGIN(lp, G);
                 icp_body<LW, true, FILT, true, false, 2>(B.P, smem, &G, reinterpret_cast<const double *>(smem + kLpPose), &S);
                 PROBE_LOOP_UNIT_END(lp, G, it, gi, B.L.nw, static_cast<int>(opaque_s(who) & 7u), lane_now(), t_unit);
+                PROBE_LOOP_UNIT_WORK(G, it, gi, BPW, lane_now());
             }
             gi = 0u;
             if (lane_now() == 0)

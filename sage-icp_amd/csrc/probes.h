@@ -145,6 +145,7 @@ __device__ unsigned long long g_loop_solver[kLoopTimedIters][4];
 __device__ unsigned long long g_loop_solver2[kLoopTimedIters][4];      // inside the solve: after the solve | the exponential (and the sqrt of the step norm) | the composition | the norm test
 __device__ unsigned long long g_loop_wave[kLoopTimedIters][kLoopTimedWgs][8][2];      // per wave: its FIRST unit of the iteration: end stamp | start stamp (low 32) << 32 ... see PROBE_LOOP_UNIT_END
 __device__ unsigned long long g_loop_wave_pose[kLoopTimedIters][kLoopTimedWgs][8];    // ... and when that pass first used the pose (PROBE_LOOP_POSE_USE)
+__device__ unsigned g_loop_unit_work[kLoopTimedIters][kLoopTimedWgs][8];       // per unit of a workgroup, in the iteration's order (0 = heaviest by the iteration before): see PROBE_LOOP_UNIT_WORK
 __device__ unsigned long long g_loop_phase[16];     // [0..7] cycles per body phase, [8] wait for the pose, [9] closing a workgroup, [10] group passes
 #define LOOP_STAMP_SOLVER(it, k) do { if ((it) < kLoopTimedIters && (threadIdx.x & 63u) == 0u) g_loop_solver[it][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #define LOOP_STAMP_SOLVER2(it, k) do { if ((it) < kLoopTimedIters && (threadIdx.x & 63u) == 0u) g_loop_solver2[it][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -179,6 +180,17 @@ __device__ unsigned long long g_loop_phase[16];     // [0..7] cycles per body ph
             g_loop_wave_pose[it][blockIdx.x][wv] = (G).tpose;                                                              \
         }                                                                                                                  \
         for (int i = 0; i < 8; ++i) lp##_ph[i] += (G).ph[i];                                                               \
+    }
+// ... and what the unit cost by the kernel's own measure: the most points one of its queries was handed (+ 48 for a stale
+// row), the maximum of LoopGroup::work over the unit's blocks of four queries — for the first units and the ones beyond
+#define PROBE_LOOP_UNIT_WORK(G, it, gi, bpw, lane)                                                                         \
+    {                                                                                                                      \
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                                                             \
+        if ((it) < kLoopTimedIters && blockIdx.x < kLoopTimedWgs && (lane) == 0 && (gi) < 8u) {                            \
+            unsigned mx = 0u;                                                                                              \
+            for (unsigned b = 0; b < (bpw); ++b) mx = max(mx, (G).work[(G).perm[(gi) * (bpw) + b]]);                       \
+            g_loop_unit_work[it][blockIdx.x][gi] = mx;                                                                     \
+        }                                                                                                                  \
     }
 // a stamp in shader cycles under the name given
 #define PROBE_LOOP_MARK(t) const unsigned long long t = __builtin_amdgcn_s_memtime()
@@ -226,6 +238,9 @@ extern "C" void sageicp_debug_loop_waves(unsigned long long *out) {
 extern "C" void sageicp_debug_loop_wave_pose(unsigned long long *out) {
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_loop_wave_pose), sizeof(unsigned long long) * kLoopTimedIters * kLoopTimedWgs * 8);
 }
+extern "C" void sageicp_debug_loop_unit_work(unsigned *out) {
+    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_loop_unit_work), sizeof(unsigned) * kLoopTimedIters * kLoopTimedWgs * 8);
+}
 extern "C" void sageicp_debug_loop_info(unsigned *info) {
     (void)hipMemcpyFromSymbol(info, HIP_SYMBOL(g_loop_wginfo), sizeof(unsigned) * kLoopTimedIters * kLoopTimedWgs * 4);
 }
@@ -247,6 +262,7 @@ extern "C" void sageicp_debug_loop_times(unsigned long long *wg, unsigned long l
 #define PROBE_LOOP_UNIT_BEGIN(it, gi, nw, t_unit) ((void)0)
 #define PROBE_LOOP_PASS_BEGIN(lp, G) ((void)0)
 #define PROBE_LOOP_UNIT_END(lp, G, it, gi, nw, wv, lane, t_unit) ((void)0)
+#define PROBE_LOOP_UNIT_WORK(G, it, gi, bpw, lane) ((void)0)
 #define PROBE_LOOP_MARK(t) ((void)0)
 #define PROBE_LOOP_WG_INFO(smem, it, lane) ((void)0)
 #define PROBE_LOOP_CLOSED(lp, last, t_a) ((void)0)
