@@ -925,6 +925,118 @@ int sageicp_map_archive_msg_device(const sageicp_map *m, int which, uint64_t fir
                                    uint64_t cap_points, void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
 int sageicp_pipeline_set_archive(sageicp_pipeline *p, int enable, uint64_t max_rows);   /* its map's */
 
+/* ---- place recognition: the semantic scan context of key frames (place.hip) -------------------------------------------
+ * Additions only; the ABI version stays.  A descriptor says where the sensor stood: a polar grid of R rings by S sectors
+ * around it that holds, per cell, the highest return (a byte) and the most important class.  Descriptors of one
+ * parameter set are kept in a database on the device, and a new one is matched against all of them under all S
+ * rotations by counting the cells that agree.  Everything that decides a byte or a rank is an integer or a plain fp64
+ * comparison against two tables made once on the host, so the same input gives the same bytes and the same matches on
+ * every run.
+ *
+ * Parameters.  Refused with SAGEICP_ERR_INVALID (before any device is asked): a double that is not finite,
+ * min_range <= 0 or min_range >= max_range, z_lo >= z_hi, rings outside [1, 64], sectors outside [3, 360],
+ * rings * sectors > 16384 (two u32 planes of that many cells are what one workgroup's LDS holds).
+ * Tables (sageicp_place_tables, host code, no device):
+ *     edge2[k] = e * e,  e = min_range + k * ((max_range - min_range) / rings),  k = 0 .. rings    (fp64, this association)
+ *     dir[s]   = (cos(a), sin(a)),  a = (2.0 * M_PI * s) / sectors,  s = 0 .. sectors - 1           (the host's libm)
+ * A row (x, y, z, l), all fp64 without contraction:
+ *   class   c = l truncated toward zero; the row is ignored unless -1 < l < 256 (so c is 0 .. 255; -0.5 is class 0) and
+ *           rank[c] != 0 — a rank of 0 is how the caller drops moving classes and unlabelled points.
+ *   ring    r2 = x * x + y * y; ignored when r2 < edge2[0] or r2 >= edge2[rings]; otherwise the ring is the number of
+ *           k in 1 .. rings - 1 with r2 >= edge2[k].  No square root is taken.
+ *   sector  f(s) = (dir[s].x * y - dir[s].y * x >= 0); the sector is the s with f(s) true and f((s + 1) % sectors)
+ *           false.  No atan2 decides anything (the kernel guesses with one in fp32, then steps with f).
+ *   height  t = (z - z_lo) / (z_hi - z_lo); v = t > 0 ? (t < 1 ? t : 1) : 0; h = 1 + (int)floor(v * 254.0): 1 .. 255,
+ *           0 means empty.
+ *   key     rank[c] << 8 | c.
+ * Per cell the descriptor keeps the maximum h and the low byte of the maximum key (the class of highest rank, ties to
+ * the higher class number); the two planes are independent.  It leaves as 2 * rings * sectors bytes: the height plane
+ * [rings][sectors], then the class plane [rings][sectors].  n == 0: all zeros.  A coordinate that is not finite refuses
+ * the call (labels are not checked: a label that is not finite is a row ignored). */
+typedef struct sageicp_place_params {
+    double min_range, max_range;       /* metres in the sensor's xy plane: min_range <= r < max_range */
+    double z_lo, z_hi;                 /* the heights mapped to bytes 1 and 255 */
+    int32_t rings, sectors;            /* R in [1, 64], S in [3, 360], R * S <= 16384 */
+    uint8_t rank[256];                 /* per class: 0 = ignored, otherwise its importance */
+} sageicp_place_params;                                            /* 296 bytes, doubles first, no padding */
+int sageicp_place_tables(const sageicp_place_params *params, double *edge2_out /* [rings + 1] */,
+                         double *dir_out /* [sectors][2] */);
+int sageicp_place_describe(const double *xyzl, uint64_t n, const sageicp_place_params *params,
+                           uint8_t *desc_out /* 2 * rings * sectors bytes */, int device);
+/* the same of a frame in device memory: the layout and caller-memory checks of sageicp_occupancy_grid_device, on the
+ * device the frame lives on and behind the work on `stream`; the bytes go to host memory.  Synchronous. */
+int sageicp_place_describe_device(const sageicp_device_frame *frame, const sageicp_place_params *params,
+                                  uint8_t *desc_out /* host */, void *stream /* hipStream_t; NULL = null stream */);
+
+/* The database: descriptors of one parameter set as [N][2][rings][sectors] bytes in device memory (it grows by
+ * doubling, from 64 entries, on the handle's stream; N <= 2^20, beyond: SAGEICP_ERR_CAPACITY), each with a tag and a
+ * pose (qx qy qz qw tx ty tz) kept on the host.  Every entry is synchronous.  _read returns what _add was given, byte for
+ * byte (any of its three outputs may be NULL), so a database is saved by _read and loaded by _add.
+ *
+ * sageicp_place_db_match(db, desc, query, out, n_out).  For entry e and shift k in 0 .. S - 1, agree(k) is the number of
+ * cells (r, s) with: the query's height at (r, s) > 0, the entry's height at (r, (s + k) % S) > 0, the two class bytes
+ * equal, and the absolute height difference <= h_tol.  shift is the smallest k of maximal agree and agree that
+ * maximum; n_query and n_entry are the occupied-cell counts, m = max(n_query, n_entry), and
+ * similarity = m ? (double)agree / (double)m : 0.0 (one division).  Only entries with index < size - exclude_last are
+ * considered (exclude_last >= size: *n_out = 0).  Ranking: a precedes b when agree_a * m_b > agree_b * m_a, exact in
+ * u64; an entry with m == 0 ranks as 0; ties go to the lower index.  The first top_k are taken, then those with
+ * similarity < min_similarity are dropped; *n_out tells how many were written.  Brute force: every considered entry is
+ * scored under every shift, so the answer is exact.  Refused (SAGEICP_ERR_INVALID): top_k outside [1, 16], h_tol > 255,
+ * a min_similarity that is not finite.
+ * Convention.  A query sensor turned by +yaw about z relative to the entry's sensor sees the entry's sector s + k in its
+ * own sector s, so T_world_query ~ T_world_entry o R_z(yaw): with w = 2.0 * M_PI / S, yaw = shift * w when
+ * shift <= S / 2 (integer division) and (shift - S) * w otherwise (both integer to double, then one product), and
+ * prior = (q_entry (x) q_z(yaw), t_entry) — the Hamilton product, not renormalised, q_z as at
+ * sageicp_relocalize_candidates; a shift of 0 leaves the entry's bits.  prior goes straight into sageicp_relocalize.
+ * sageicp_place_prior is that rule alone (host code, no device; SAGEICP_ERR_INVALID for a shift >= sectors). */
+typedef struct sageicp_place_db sageicp_place_db;
+typedef struct sageicp_place_query {
+    double min_similarity;
+    uint64_t exclude_last;             /* the newest entries are not considered (a typical value: some tens) */
+    uint32_t top_k, h_tol;             /* 1 .. 16; 0 .. 255 */
+} sageicp_place_query;                                             /* 24 bytes */
+typedef struct sageicp_place_match {
+    double similarity, yaw;
+    double pose[7], prior[7];          /* the entry's pose; the prior for sageicp_relocalize */
+    uint64_t index, tag;
+    uint32_t agree, n_query, n_entry, shift;
+} sageicp_place_match;                                             /* 160 bytes, doubles first, no padding */
+sageicp_place_db *sageicp_place_db_create(const sageicp_place_params *params, int device);
+void sageicp_place_db_destroy(sageicp_place_db *db);
+uint64_t sageicp_place_db_size(const sageicp_place_db *db);
+int sageicp_place_db_clear(sageicp_place_db *db);
+int sageicp_place_db_add(sageicp_place_db *db, const uint8_t *desc /* host bytes */, uint64_t tag,
+                         const double pose[7] /* NULL = identity */, uint64_t *index_out /* optional */);
+int sageicp_place_db_read(const sageicp_place_db *db, uint64_t first, uint64_t count, uint8_t *desc_out,
+                          uint64_t *tags_out, double *poses_out /* [count][7] */);
+int sageicp_place_db_match(const sageicp_place_db *db, const uint8_t *desc /* host bytes */,
+                           const sageicp_place_query *query, sageicp_place_match *out /* [top_k] */, uint32_t *n_out);
+int sageicp_place_prior(const double pose[7], uint32_t shift, int32_t sectors, double *yaw_out, double prior_out[7]);
+
+/* In the pipeline (off by default; off, no kernel, launch or result changes).  For every frame that becomes a key frame
+ * the pipeline, after the key-frame decision and outside the times the register calls report, (1) describes the RAW
+ * frame (the copy key-frame selection sets aside), (2) matches the descriptor against the database BEFORE adding it,
+ * with the given query, and (3) appends it device to device with tag = key_frame_index and pose = key_pose.  Other
+ * frames leave described = 0 and n_matches = 0.  The only host synchronisation added is the one download of the match
+ * records.  sageicp_pipeline_set_places is refused with SAGEICP_ERR_INVALID while key-frame selection is off;
+ * switching key frames off (or setting them anew) switches places off.  Switching places on starts an empty database.
+ * sageicp_pipeline_reinitialize keeps the database, as it keeps the key-frame state: tags then refer to the earlier
+ * trajectory.  sageicp_pipeline_place_reset and sageicp_pipeline_key_frame_reset clear it.  A register call that fails
+ * changes nothing in the database.  sageicp_pipeline_place_db returns the pipeline's database, borrowed (NULL while
+ * places are off): valid until places are switched off or the pipeline goes. */
+typedef struct sageicp_place_info {
+    sageicp_place_match matches[16];
+    uint64_t entries;                  /* the database's size */
+    int32_t enabled;
+    int32_t described;                 /* the last frame registered was a key frame and was described */
+    uint32_t n_matches, reserved;
+} sageicp_place_info;                                              /* 2584 bytes */
+int sageicp_pipeline_set_places(sageicp_pipeline *p, int enable, const sageicp_place_params *params,
+                                const sageicp_place_query *query);
+int sageicp_pipeline_place_info(const sageicp_pipeline *p, sageicp_place_info *out);
+const sageicp_place_db *sageicp_pipeline_place_db(const sageicp_pipeline *p);
+int sageicp_pipeline_place_reset(sageicp_pipeline *p);
+
 /* ---- KITTI trajectory metrics: sage_icp::metrics (metrics/Metrics.hpp:33-37) ----------------------
  * Host-only (the reference's are CPU code too).  Poses are 4x4 homogeneous matrices, ROW-major
  * (a KITTI poses.txt row padded with 0 0 0 1), n of them, 16 doubles each.

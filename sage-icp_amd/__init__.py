@@ -269,6 +269,69 @@ def occupancy_params(bounds=KEY_FRAME_BOUNDS, occ_size=KEY_FRAME_OCC_SIZE, overl
     return p
 
 
+class PlaceParams(C.Structure):
+    """sageicp_place_params: the polar grid of a place descriptor (rings R, sectors S), the heights mapped to bytes 1 and
+    255, and the rank of every class (0: ignored)"""
+    _fields_ = [("min_range", C.c_double), ("max_range", C.c_double), ("z_lo", C.c_double), ("z_hi", C.c_double),
+                ("rings", C.c_int32), ("sectors", C.c_int32), ("rank", C.c_uint8 * 256)]
+
+
+class PlaceQuery(C.Structure):
+    """sageicp_place_query"""
+    _fields_ = [("min_similarity", C.c_double), ("exclude_last", C.c_uint64), ("top_k", C.c_uint32), ("h_tol", C.c_uint32)]
+
+
+class PlaceMatch(C.Structure):
+    """sageicp_place_match"""
+    _fields_ = [("similarity", C.c_double), ("yaw", C.c_double), ("pose", C.c_double * 7), ("prior", C.c_double * 7),
+                ("index", C.c_uint64), ("tag", C.c_uint64),
+                ("agree", C.c_uint32), ("n_query", C.c_uint32), ("n_entry", C.c_uint32), ("shift", C.c_uint32)]
+
+
+class PlaceInfo(C.Structure):
+    """sageicp_place_info: what place recognition did for the last frame registered"""
+    _fields_ = [("matches", PlaceMatch * 16), ("entries", C.c_uint64), ("enabled", C.c_int32), ("described", C.c_int32),
+                ("n_matches", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PLACE_PARAMS_BYTES, PLACE_QUERY_BYTES, PLACE_MATCH_BYTES, PLACE_INFO_BYTES = 296, 24, 160, 2584
+assert (C.sizeof(PlaceParams), C.sizeof(PlaceQuery), C.sizeof(PlaceMatch), C.sizeof(PlaceInfo)) == \
+    (PLACE_PARAMS_BYTES, PLACE_QUERY_BYTES, PLACE_MATCH_BYTES, PLACE_INFO_BYTES)
+# the structs of PlaceDB.match as a numpy record array
+PLACE_MATCH_DTYPE = np.dtype([("similarity", "<f8"), ("yaw", "<f8"), ("pose", "<f8", (7,)), ("prior", "<f8", (7,)),
+                              ("index", "<u8"), ("tag", "<u8"),
+                              ("agree", "<u4"), ("n_query", "<u4"), ("n_entry", "<u4"), ("shift", "<u4")])
+assert PLACE_MATCH_DTYPE.itemsize == PLACE_MATCH_BYTES
+PLACE_MAX_CELLS = 16384  # rings * sectors at most: two u32 planes of that many cells are one workgroup's LDS
+
+
+def place_params(min_range=3.0, max_range=50.0, z_lo=-3.0, z_hi=7.0, rings=20, sectors=60, rank=None):
+    """PlaceParams.  rank: a dict {class: rank} (the classes it does not name get 0: ignored), a sequence of 256 ranks,
+    or None for rank 1 for every class but 0"""
+    p = PlaceParams()
+    p.min_range, p.max_range, p.z_lo, p.z_hi = float(min_range), float(max_range), float(z_lo), float(z_hi)
+    p.rings, p.sectors = int(rings), int(sectors)
+    if rank is None:
+        table = [0] + [1] * 255
+    elif isinstance(rank, dict):
+        table = [0] * 256
+        for c, r in rank.items():
+            table[int(c)] = int(r)
+    else:
+        table = [int(r) for r in rank]
+        if len(table) != 256:
+            raise ValueError("rank holds one entry per class 0 .. 255")
+    for c, r in enumerate(table):
+        p.rank[c] = r
+    return p
+
+
+def place_query(top_k=1, h_tol=0, exclude_last=0, min_similarity=0.0):
+    q = PlaceQuery()
+    q.top_k, q.h_tol, q.exclude_last, q.min_similarity = int(top_k), int(h_tol), int(exclude_last), float(min_similarity)
+    return q
+
+
 # the SemanticKITTI parameter sets of ros/launch/odometry*.launch.py
 KITTI_VOXEL_LABELS = [[40, 44, 48, 49], [50, 51, 52], [70, 72], [60, 71, 80, 81, 99], [0],
                       [10, 11, 13, 15, 16, 18, 20]]
@@ -435,6 +498,21 @@ _SIGNATURES = [
     ("sageicp_map_archive_msg_device", C.c_int,
      [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(MsgColors), C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
     ("sageicp_pipeline_set_archive", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
+    ("sageicp_place_tables", C.c_int, [C.POINTER(PlaceParams), _dp, _dp]),
+    ("sageicp_place_describe", C.c_int, [_dp, C.c_uint64, C.POINTER(PlaceParams), C.c_void_p, C.c_int]),
+    ("sageicp_place_describe_device", C.c_int, [C.POINTER(DeviceFrame), C.POINTER(PlaceParams), C.c_void_p, C.c_void_p]),
+    ("sageicp_place_db_create", C.c_void_p, [C.POINTER(PlaceParams), C.c_int]),
+    ("sageicp_place_db_destroy", None, [C.c_void_p]),
+    ("sageicp_place_db_size", C.c_uint64, [C.c_void_p]),
+    ("sageicp_place_db_clear", C.c_int, [C.c_void_p]),
+    ("sageicp_place_db_add", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _dp, _u64p]),
+    ("sageicp_place_db_read", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("sageicp_place_db_match", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PlaceQuery), C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("sageicp_place_prior", C.c_int, [_dp, C.c_uint32, C.c_int32, _dp, _dp]),
+    ("sageicp_pipeline_set_places", C.c_int, [C.c_void_p, C.c_int, C.POINTER(PlaceParams), C.POINTER(PlaceQuery)]),
+    ("sageicp_pipeline_place_info", C.c_int, [C.c_void_p, C.POINTER(PlaceInfo)]),
+    ("sageicp_pipeline_place_db", C.c_void_p, [C.c_void_p]),
+    ("sageicp_pipeline_place_reset", C.c_int, [C.c_void_p]),
     ("sageicp_pipeline_create", C.c_void_p, [C.POINTER(PipelineConfig)]),
     ("sageicp_pipeline_destroy", None, [C.c_void_p]),
     ("sageicp_pipeline_register_frame", C.c_int,
@@ -1306,6 +1384,114 @@ def occupancy_grid(frame, bounds=KEY_FRAME_BOUNDS, occ_size=KEY_FRAME_OCC_SIZE, 
     return out
 
 
+def place_tables(params):
+    """(edge2[R + 1], dir[S, 2]): the two host-made tables every decision of a place descriptor reads
+    (sageicp_place_tables) — the squared ring edges and the sectors' directions (cos, sin)"""
+    edge2 = np.empty(max(int(params.rings), 0) + 1)
+    dirs = np.empty((max(int(params.sectors), 0), 2))
+    _check(lib().sageicp_place_tables(C.byref(params), edge2.ctypes.data_as(_dp), dirs.ctypes.data_as(_dp)))
+    return edge2, dirs
+
+
+def place_prior(pose, shift, sectors):
+    """(yaw, prior[7]) of a match at `shift` with an entry at `pose` (sageicp_place_prior; host code)"""
+    pose_a, pp = _d(pose)
+    if pose_a.size != 7:
+        raise ValueError("a pose is (qx, qy, qz, qw, tx, ty, tz)")
+    yaw, prior = C.c_double(0), np.empty(7)
+    _check(lib().sageicp_place_prior(pp, int(shift), int(sectors), C.byref(yaw), prior.ctypes.data_as(_dp)))
+    return yaw.value, prior
+
+
+def _place_bytes(params, device=0, labels=None, frame=None):
+    out = np.zeros(2 * max(int(params.rings), 0) * max(int(params.sectors), 0), dtype=np.uint8)
+    if _is_device_tensor(frame):
+        f, stream = _device_rows(DeviceFrame, frame, labels, frame.device.index, _FRAME_WORDS)
+        _check(lib().sageicp_place_describe_device(C.byref(f), C.byref(params), out.ctypes.data_as(C.c_void_p), stream))
+        return out
+    if labels is not None:
+        raise ValueError("labels= is for a frame that is a torch tensor on a GPU")
+    pts, fp = _d(frame)
+    _check(lib().sageicp_place_describe(fp, pts.reshape(-1, 4).shape[0], C.byref(params), out.ctypes.data_as(C.c_void_p),
+                                        device))
+    return out
+
+
+def place_describe(frame, params, device=0, labels=None):
+    """The place descriptor of a frame (sageicp_place_describe[_device]): (heights, classes), two (R, S) uint8 arrays —
+    per cell of the polar grid the highest return as a byte (0: empty) and the class of highest rank.  `frame` is numpy
+    (n, 4) rows (on GPU `device`) or a torch tensor on a GPU in the layouts RegisterFrame takes (`labels` as there)."""
+    out = _place_bytes(params, device, labels, frame).reshape(2, params.rings, params.sectors)
+    return out[0], out[1]
+
+
+def _place_desc(desc, params):
+    """a descriptor in any of its forms — (heights, classes), (2, R, S), flat bytes — as 2 * R * S contiguous bytes"""
+    a = np.ascontiguousarray(np.stack(desc) if isinstance(desc, tuple) else desc, dtype=np.uint8).reshape(-1)
+    if a.size != 2 * params.rings * params.sectors:
+        raise ValueError("a descriptor of these params holds 2 * %d * %d bytes" % (params.rings, params.sectors))
+    return a
+
+
+def _place_match(handle, desc, query):
+    out = np.zeros(16, dtype=PLACE_MATCH_DTYPE)
+    n = C.c_uint32(0)
+    _check(lib().sageicp_place_db_match(handle, desc.ctypes.data_as(C.c_void_p), C.byref(query),
+                                        out.ctypes.data_as(C.c_void_p), C.byref(n)))
+    return out[:n.value].copy()
+
+
+class PlaceDB:
+    """sageicp_place_db: place descriptors of one parameter set on GPU `device`, each with a tag and a pose, and the
+    brute-force matcher over them.  PlaceDB(params) owns a new database; a pipeline's (SageICP.places()) is borrowed."""
+
+    def __init__(self, params, device=0, _borrowed=None, _owner=None):
+        self.params = params
+        self._owner = _owner
+        self._own = _borrowed is None
+        self._h = _borrowed if _borrowed is not None else lib().sageicp_place_db_create(C.byref(params), device)
+        if not self._h:
+            raise SageIcpError(ERR_INVALID, (lib().sageicp_last_error() or b"").decode())
+
+    def __del__(self):
+        if getattr(self, "_h", None) and getattr(self, "_own", False) and lib is not None:
+            lib().sageicp_place_db_destroy(self._h)
+            self._h = None
+
+    def __len__(self):
+        return int(lib().sageicp_place_db_size(self._h))
+
+    def clear(self):
+        _check(lib().sageicp_place_db_clear(self._h))
+
+    def add(self, desc, tag=0, pose=None):
+        """appends a descriptor ((heights, classes), (2, R, S) or flat bytes); returns its index"""
+        a = _place_desc(desc, self.params)
+        pp = None
+        if pose is not None:
+            pose_a, pp = _d(pose)
+            if pose_a.size != 7:
+                raise ValueError("a pose is (qx, qy, qz, qw, tx, ty, tz)")
+        idx = C.c_uint64(0)
+        _check(lib().sageicp_place_db_add(self._h, a.ctypes.data_as(C.c_void_p), int(tag), pp, C.byref(idx)))
+        return idx.value
+
+    def match(self, desc, top_k=1, h_tol=0, exclude_last=0, min_similarity=0.0, query=None):
+        """the best entries for `desc` as a numpy record array (PLACE_MATCH_DTYPE), best first (sageicp_place_db_match)"""
+        q = query if query is not None else place_query(top_k, h_tol, exclude_last, min_similarity)
+        return _place_match(self._h, _place_desc(desc, self.params), q)
+
+    def read(self, first=0, count=None):
+        """(descriptors (count, 2, R, S) uint8, tags (count,) uint64, poses (count, 7)) as they were added"""
+        count = len(self) - first if count is None else count
+        desc = np.zeros((max(count, 0), 2, self.params.rings, self.params.sectors), dtype=np.uint8)
+        tags = np.zeros(max(count, 0), dtype=np.uint64)
+        poses = np.zeros((max(count, 0), 7))
+        _check(lib().sageicp_place_db_read(self._h, first, count, desc.ctypes.data_as(C.c_void_p),
+                                           tags.ctypes.data_as(C.c_void_p), poses.ctypes.data_as(C.c_void_p)))
+        return desc, tags, poses
+
+
 def align_clouds(src, tgt, kernel, device=0):
     src, sp = _d(src)
     tgt, gp = _d(tgt)
@@ -1375,6 +1561,7 @@ class SageICP:
         _check(lib().sageicp_pipeline_set_key_frames(self._h, 1 if enable else 0,
                                                      C.byref(params) if params is not None else None))
         self._occ_size = (params.occ_h, params.occ_w) if enable else None
+        self._place_params = None          # (a new selection starts with places off)
 
     def key_frame_info(self):
         """dict: enabled, is_key_frame (of the last frame), overlap (NaN on a first key frame or an empty key grid),
@@ -1403,6 +1590,38 @@ class SageICP:
         stream = _current_stream(dev)
         _check(lib().sageicp_pipeline_key_frame_grid_device(self._h, out.data_ptr() or None, out.numel(), stream))
         return out
+
+    def set_places(self, enable=True, params=None, top_k=1, h_tol=0, exclude_last=0, min_similarity=0.0, query=None):
+        """Place recognition for every key frame (sageicp_pipeline_set_places): the raw frame described, matched against
+        the places before it (place_info()), then added with tag = its index in poses() and its pose.  Needs key-frame
+        selection on; starts from an empty database.  Off by default."""
+        self._place_params = None
+        if not enable:
+            _check(lib().sageicp_pipeline_set_places(self._h, 0, None, None))
+            return
+        params = params if params is not None else place_params()
+        q = query if query is not None else place_query(top_k, h_tol, exclude_last, min_similarity)
+        _check(lib().sageicp_pipeline_set_places(self._h, 1, C.byref(params), C.byref(q)))
+        self._place_params = params
+
+    def place_info(self):
+        """dict: enabled, described (the last frame registered was a key frame and was described), entries, matches (a
+        numpy record array, PLACE_MATCH_DTYPE, best first)"""
+        info = PlaceInfo()
+        _check(lib().sageicp_pipeline_place_info(self._h, C.byref(info)))
+        matches = np.frombuffer(bytes(info)[:16 * PLACE_MATCH_BYTES], dtype=PLACE_MATCH_DTYPE)[:info.n_matches].copy()
+        return {"enabled": bool(info.enabled), "described": bool(info.described), "entries": int(info.entries),
+                "matches": matches}
+
+    def places(self):
+        """the pipeline's place database (a borrowed PlaceDB: valid while places stay on), or None"""
+        h = lib().sageicp_pipeline_place_db(self._h)
+        params = getattr(self, "_place_params", None)
+        return PlaceDB(params, _borrowed=h, _owner=self) if h and params is not None else None
+
+    def place_reset(self):
+        """empties the place database (key_frame_reset() does too; reinitialize() keeps it)"""
+        _check(lib().sageicp_pipeline_place_reset(self._h))
 
     def dynamic_filter_info(self):
         """dict: what the filter did to the last frame registered (zeros when it was off)"""

@@ -35,6 +35,7 @@
 #include "correspond.h"
 #include "quality.h"
 #include "score.h"
+#include "place.h"
 #include "msg.h"
 #include "map_update.h"
 #include "metrics.hpp"
@@ -475,6 +476,14 @@ int refresh_mirror(sageicp_map &m);
 int ensure_host(sageicp_map &m);
 int device_update(sageicp_map &m, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points = nullptr);
 bool all_finite(const double *xyzl, uint64_t n);
+// capi_place.hip: place recognition (place.h) — the checks of its parameter structs, a database for the pipeline, and the
+// pipeline's step for a key frame: describe the n raw rows at d_rows, match against the database as it is, append
+int place_check_params(const sageicp_place_params *p);
+int place_check_query(const sageicp_place_query *q);
+sageicp_place_db *place_db_new(const sageicp_place_params &p, int device);
+void place_db_clear(sageicp_place_db &db);
+int place_db_step(sageicp_place_db &db, const Point4 *d_rows, uint64_t n, const sageicp_place_query &q, uint64_t tag,
+                  const double pose[7], hipStream_t s, sageicp_place_match *out, uint32_t *n_out);
 // capi_archive.hip: RemovePointsFarFromLocation on the host copy of one handle, the evicted voxels into its archive while on
 void host_remove_far(sageicp_map &m, const double origin[3]);
 // capi_run.hip

@@ -53,6 +53,32 @@ struct sageicp_pipeline {
         }
         KeyFrames() { clear(); }
     } kf;
+    // place recognition (sageicp_pipeline_set_places, place.hip): off by default.  The database of the key frames'
+    // descriptors (capi_place.hip) and what the last frame's step found in it.
+    struct Places {
+        struct Destroy {
+            void operator()(sageicp_place_db *d) const { sageicp_place_db_destroy(d); }
+        };
+        bool on = false;
+        sageicp_place_query query{};
+        std::unique_ptr<sageicp_place_db, Destroy> db;
+        sageicp_place_info info{};
+        // what every register call starts from
+        void no_frame() {
+            info.described = 0;
+            info.n_matches = 0;
+        }
+        void clear() {
+            if (db) place_db_clear(*db);
+            info = sageicp_place_info{};
+            info.enabled = on ? 1 : 0;
+        }
+        void off() {
+            on = false;
+            db.reset();
+            clear();
+        }
+    } places;
     // the registration quality report (sageicp_pipeline_set_quality, quality.hip): off by default; `quality` is the last
     // register call's, valid = 0 when there is none
     bool quality_on = false;
@@ -152,6 +178,15 @@ static int key_frame_step(sageicp_pipeline *p, uint64_t n) {
         info.key_frame_index = p->impl.poses.size() - 1;
         ++info.key_frames;
         for (int i = 0; i < 7; ++i) info.key_pose[i] = pose.v[i];
+        // the key frame's place: described from the raw rows, matched against the places before it, then added
+        auto &pl = p->places;
+        if (pl.on) {
+            if (int rc = place_db_step(*pl.db, pr.d_raw.data(), n, pl.query, info.key_frame_index, pose.v, s,
+                                       pl.info.matches, &pl.info.n_matches))
+                return rc;
+            pl.info.described = 1;
+            pl.info.entries = sageicp_place_db_size(pl.db.get());
+        }
     }
     return SAGEICP_OK;
 }
@@ -255,6 +290,7 @@ static void drop_source(sageicp_pipeline *p) {
     if (!p) return;
     p->src_n = 0;
     p->quality = sageicp_quality{};          // ... and no report
+    p->places.no_frame();
 }
 int sageicp_pipeline_register_frame(sageicp_pipeline *p, const double *frame, uint64_t n,
                                     double pose_out[7], double *icp_s, double *total_s,
@@ -487,11 +523,47 @@ int sageicp_pipeline_set_key_frames(sageicp_pipeline *p, int enable, const sagei
         p->prep[1].d_raw.reset();
     }
     k.clear();
+    (void)hipSetDevice(p->device);
+    p->places.off();                    // (places describe key frames: a new selection starts without them)
     return SAGEICP_OK;
 }
 int sageicp_pipeline_key_frame_reset(sageicp_pipeline *p) {
     if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
     p->kf.clear();
+    p->places.clear();
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_set_places(sageicp_pipeline *p, int enable, const sageicp_place_params *params,
+                                const sageicp_place_query *query) {
+    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
+    auto &pl = p->places;
+    if (!enable) {
+        (void)hipSetDevice(p->device);
+        pl.off();
+        return SAGEICP_OK;
+    }
+    if (!p->kf.on) return fail(SAGEICP_ERR_INVALID, "sageicp_pipeline_set_places: key-frame selection is off");
+    if (int rc = place_check_params(params)) return rc;
+    if (int rc = place_check_query(query)) return rc;
+    if (int rc = require_device(p->device)) return rc;
+    sageicp_place_db *db = place_db_new(*params, p->device);
+    if (!db) return SAGEICP_ERR_HIP;    // (the message is the failing call's)
+    pl.off();
+    pl.db.reset(db);
+    pl.on = true;
+    pl.query = *query;
+    pl.clear();
+    return SAGEICP_OK;
+}
+int sageicp_pipeline_place_info(const sageicp_pipeline *p, sageicp_place_info *out) {
+    if (!p || !out) return fail(SAGEICP_ERR_INVALID, "null argument");
+    *out = p->places.info;
+    return SAGEICP_OK;
+}
+const sageicp_place_db *sageicp_pipeline_place_db(const sageicp_pipeline *p) { return p ? p->places.db.get() : nullptr; }
+int sageicp_pipeline_place_reset(sageicp_pipeline *p) {
+    if (!p) return fail(SAGEICP_ERR_INVALID, "null pipeline");
+    p->places.clear();
     return SAGEICP_OK;
 }
 int sageicp_pipeline_key_frame_info(const sageicp_pipeline *p, sageicp_key_frame_info *info) {
