@@ -109,8 +109,9 @@ int sageicp_device_count(void);               /* number of visible HIP devices (
 void sageicp_set_profiling(int level);        /* 0 off; 1 HIP events around k_icp in one iteration
                                                * out of 8; 2 around every kernel of every iteration */
 void sageicp_reload_env(void);                /* the SAGEICP_* tuning knobs are read from the environment once per process (at
-                                               * first use); this makes the next calls read them again.  Not while calls of
-                                               * other threads are in flight. */
+                                               * first use, all together); this reads them again for the calls that begin
+                                               * afterwards: a call in flight keeps the values it began with.  Not while
+                                               * another thread changes the environment. */
 void sageicp_set_counting(int on);            /* 1 (default): a call given a sageicp_stats counts C_q and the pairs it
                                                * evaluates (sum_candidates, pairs_evaluated: ~3 % of the search);
                                                * 0: those two fields stay zero, the others are filled as before.

@@ -11,31 +11,10 @@
 // SAGEICP_ERR_NO_DEVICE.
 #include "capi_internal.h"
 
-#include <mutex>
-
 namespace sageicp {
 thread_local std::string g_err;
 std::atomic<int> g_profiling{0};
 std::atomic<int> g_counting{1};
-std::atomic<unsigned> g_env_epoch{0};
-const char *env_cached(const char *name) {
-    // (text knobs — SAGEICP_DEVICES, SAGEICP_CU_SHARE — are asked for when a handle or its streams are created, not per call)
-    static std::mutex mu;
-    static unsigned epoch = 0xFFFFFFFFu;
-    static std::map<std::string, std::pair<bool, std::string>> vals;
-    std::lock_guard<std::mutex> lk(mu);
-    const unsigned e = g_env_epoch.load();
-    if (epoch != e) {
-        vals.clear();
-        epoch = e;
-    }
-    auto it = vals.find(name);
-    if (it == vals.end()) {
-        const char *v = std::getenv(name);
-        it = vals.emplace(name, std::make_pair(v != nullptr, std::string(v ? v : ""))).first;
-    }
-    return it->second.first ? it->second.second.c_str() : nullptr;
-}
 std::atomic<int> g_reference_order{1};
 }  // namespace sageicp
 
@@ -77,7 +56,7 @@ int sageicp_device_count(void) {
 }
 void sageicp_set_profiling(int level) { g_profiling = level; }
 void sageicp_set_counting(int on) { g_counting = on ? 1 : 0; }
-void sageicp_reload_env(void) { sageicp::g_env_epoch.fetch_add(1u); }
+void sageicp_reload_env(void) { (void)sageicp::reload_knobs(); }
 void sageicp_set_downsample_order(int reference_order) { g_reference_order = reference_order ? 1 : 0; }
 int sageicp_robin_iteration_order(const int32_t *vox_xyz, uint64_t n, uint32_t *order_out) {
     if (n && (!vox_xyz || !order_out)) return fail(SAGEICP_ERR_INVALID, "null argument");
@@ -131,34 +110,22 @@ sageicp_map *sageicp_map_create(double voxel_size, double max_distance, int basi
                                   "1 <= basic+critical <= 255)");
         return nullptr;
     }
+    const Knobs &kn = knobs();               // (the knobs of a map's creation: read here, not per call)
     sageicp_map *m = new sageicp_map;
-    m->host.configure(voxel_size, max_distance, basic, critical, labels, n_labels);
+    m->host.configure(voxel_size, max_distance, basic, critical, labels, n_labels, kn.size_classes);
     m->device = device;
     // SAGEICP_DEVICES=0,1,2,3: every map of this process spans these devices (the knob for callers
     // that cannot be changed, e.g. the ROS node behind the header shim); the first is rank 0
-    if (const char *list = env_cached("SAGEICP_DEVICES")) {
-        std::vector<int> devs;
-        for (const char *q = list; *q;) {
-            char *end = nullptr;
-            const long v = std::strtol(q, &end, 10);
-            if (end == q) break;
-            devs.push_back(static_cast<int>(v));
-            q = (*end == ',') ? end + 1 : end;
-        }
-        if (devs.size() > 1 && sageicp_map_set_devices(m, devs.data(), static_cast<int>(devs.size()))) {
-            sageicp_map_destroy(m);
-            return nullptr;
-        }
+    if (kn.n_devices > 1 && sageicp_map_set_devices(m, kn.devices, kn.n_devices)) {
+        sageicp_map_destroy(m);
+        return nullptr;
     }
     // SAGEICP_MAP_REFERENCE_ORDER=1: every map of this process is created in reference-order mode (the
     // knob for callers behind the header shim; sageicp_map_set_reference_order for everyone else)
-    if (env_int("SAGEICP_MAP_REFERENCE_ORDER", 0)) (void)sageicp_map_set_reference_order(m, 1);
+    if (kn.map_reference_order.get()) (void)sageicp_map_set_reference_order(m, 1);
     // SAGEICP_MAP_ARCHIVE=1: every map of this process keeps what it evicts (sageicp_map_set_archive), at most
     // SAGEICP_MAP_ARCHIVE_MAX_ROWS rows of it (0 / unset: no limit)
-    if (env_int("SAGEICP_MAP_ARCHIVE", 0)) {
-        const char *lim = env_cached("SAGEICP_MAP_ARCHIVE_MAX_ROWS");      // (64 bits: 2^31 rows are only 64 GiB)
-        (void)sageicp_map_set_archive(m, 1, (lim && lim[0] != '-') ? std::strtoull(lim, nullptr, 10) : 0);
-    }
+    if (kn.map_archive.get()) (void)sageicp_map_set_archive(m, 1, kn.map_archive_max_rows);      // (64 bits: 2^31 rows are only 64 GiB)
     return m;
 }
 
@@ -217,8 +184,8 @@ void sageicp_map_destroy(sageicp_map *m) {
 static int clone_on_device(const sageicp_map &src, sageicp_map *m) {
     const HostMap &h = src.host;
     m->host.configure(h.voxel_size, h.max_distance, h.basic, h.critical, h.basic_labels.data(),
-                      static_cast<int>(h.basic_labels.size()));
-    m->host.n_classes = h.n_classes;                    // (the source's size classes, whatever the environment says now)
+                      static_cast<int>(h.basic_labels.size()), true);
+    m->host.n_classes = h.n_classes;                    // (the source's size classes, whatever the knob says now)
     for (int k = 0; k < kMaxClasses; ++k) m->host.class_points[k] = h.class_points[k];
     // (a map in reference-order mode: the bucket array lives on the host whoever holds the points — "a copy has the same array")
     m->host.track_order = h.track_order;

@@ -31,7 +31,7 @@ void MapArchive::clear() {
 }
 
 // the first capacity of the device part (SAGEICP_ARCHIVE_INITIAL_ROWS: a test forces re-allocations with it)
-static uint64_t initial_rows() { return static_cast<uint64_t>(std::max(1, env_int("SAGEICP_ARCHIVE_INITIAL_ROWS", 1 << 16))); }
+static uint64_t initial_rows() { return static_cast<uint64_t>(knobs().archive_initial_rows.get()); }
 
 static int grow_to(MapArchive &a, uint64_t need_rows, uint64_t need_vox, hipStream_t s) {
     if (need_rows > a.d_rows.capacity()) {

@@ -1,5 +1,5 @@
 // Internals shared by the translation units of libsageicp_hip.so's host side (capi.hip, capi_pipeline.hip,
-// capi_outputs.hip, capi_query.hip, capi_relocalize.hip, caller_mem.hip, map_device.hip, capi_run.hip, prep.hip): error channel, tuning knobs, the
+// capi_outputs.hip, capi_query.hip, capi_relocalize.hip, caller_mem.hip, map_device.hip, capi_run.hip, prep.hip): error channel, tuning knobs (knobs.h), the
 // per-handle device scratch, the pipeline's frame source and buffers (prep.h) and its prefetch state (prefetch.h), the
 // checks of a caller's device memory (caller_mem.h), the HBM copy of a map (map_device.h), the way out (outputs.h), what
 // follows the search of GetCorrespondences on the device (correspond.h), the registration quality pass (quality.h), the
@@ -31,6 +31,7 @@
 #include "dyn_rules.h"
 #include "host_map.hpp"
 #include "kernels.h"
+#include "knobs.h"
 #include "egress.h"
 #include "correspond.h"
 #include "quality.h"
@@ -56,58 +57,8 @@ extern std::atomic<int> g_counting;                // sageicp_set_counting: the 
 // tsl::robin_map, replayed on the host: robin_order.hpp) unless switched to arrival order
 extern std::atomic<int> g_reference_order;
 
-// tuning knobs (defaults chosen by measurement on MI355X; the environment overrides are for
-// experiments only)
-// The process environment is read ONCE per knob and call site (the first time it is asked for) and again only after
-// sageicp_reload_env(): a registration asks for ~35 knobs, and a ROS node's environment does not change under it.
-// (Tests and probes that flip knobs between calls go through the Python binding, which calls sageicp_reload_env()
-// whenever the SAGEICP_* part of os.environ changed.)
-extern std::atomic<unsigned> g_env_epoch;          // bumped by sageicp_reload_env()
-struct EnvKnob {
-    const char *name;
-    std::atomic<unsigned> epoch{0xFFFFFFFFu};
-    std::atomic<int> has{0}, val{0};
-};
-inline int env_knob(EnvKnob &k, int dflt) {
-    const unsigned e = g_env_epoch.load(std::memory_order_relaxed);
-    if (k.epoch.load(std::memory_order_acquire) != e) {
-        const char *v = std::getenv(k.name);
-        k.val.store(v ? std::atoi(v) : 0, std::memory_order_relaxed);
-        k.has.store(v ? 1 : 0, std::memory_order_relaxed);
-        k.epoch.store(e, std::memory_order_release);
-    }
-    return k.has.load(std::memory_order_relaxed) ? k.val.load(std::memory_order_relaxed) : dflt;
-}
-#define env_int(name, dflt) ([&]() -> int { static ::sageicp::EnvKnob _knob{name}; return ::sageicp::env_knob(_knob, (dflt)); }())
-// a knob that is text: the value at the last (re)load (capi.hip), or nullptr
-const char *env_cached(const char *name);
-// Lanes per query in k_icp (log2).  One lane per query needs the fewest instructions per query
-// but gives a frame of n points only n / 64 waves with long dependent chains; small frames and
-// shards spread each query over more lanes.  Thresholds measured on MI355X (profiles/README.md);
-// SAGEICP_LW overrides for experiments.
-inline int icp_lw(uint64_t n, bool sparse_voxels) {
-    const int e = env_int("SAGEICP_LW", -1);
-    if (e >= 0) return e > 4 ? 4 : e;
-    // (all of this re-measured after the flat-order scan, profiles/r04/lanes_probe2.txt (dense voxels) and
-    // lanes_probe3.txt (sparse ones); us per iteration)
-    // the biggest frames are bound by instruction issue, not by the length of a wave's chain: two
-    // lanes per query halve the per-query share of the fixed work (prologue, bounds, epilogue) — against
-    // dense voxels only at c4's size (500k: 90.7 against 92.9 with four, 400k a tie), against sparse ones
-    // from ~150k (c5, 200k: 42.8 / 43.2; 100k: 33.3 / 31.6)
-    if (n >= (sparse_voxels ? 150000u : 400000u)) return 1;
-    // eight lanes stride through a query's voxels in flat order (kernels.hip) and hold against dense voxels
-    // up to ~110k queries (50k: 25.7 against 31.1 with four; 60k: 28.0 / 31.5; 80k: 32.3 / 34.5; 100k: 36.2 /
-    // 37.1; 120k: 40.8 / 40.6), against sparse ones up to ~60k (25k: 19.8 / 22.9; 50k: 24.7 / 25.1; 100k:
-    // 34.9 / 31.6); until late round 4 the switch to four sat at 50k and, for sparse voxels, at 4k
-    if (n >= (sparse_voxels ? 60000u : 110000u)) return 2;
-    // sixteen lanes only for small frames against dense voxels (in flat order they hold up to ~20k queries:
-    // 10k 17.8 against 18.9 with eight, 15k 19.1 / 20.0, 30k 24.7 / 22.6 — lanes_probe4.txt; the switch used
-    // to sit at 10k): a scan against sparse ones is a handful of points whatever the split (c1, 10k: 17.6
-    // with eight, 20.7 with four)
-    if (n >= (sparse_voxels ? 4096u : 20000u)) return 3;
-    return 4;
-}
-
+// tuning knobs (defaults chosen by measurement on MI355X; the environment overrides are for experiments only): knobs.h —
+// knobs() is the snapshot of the last (re)load, and an entry that reads more than one knob takes it once
 
 inline int fail(int code, const std::string &msg) {
     g_err = msg;
@@ -237,14 +188,9 @@ struct Scratch {
             int cus = 0;
             if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess) num_cus = cus;
         }
-        if (cu_share_k <= 1) {
-            if (const char *e = env_cached("SAGEICP_CU_SHARE")) {
-                int i = 0, k = 1;
-                if (std::sscanf(e, "%d/%d", &i, &k) == 2 && k >= 1 && k <= 16 && i >= 0 && i < k) {
-                    cu_share_i = i;
-                    cu_share_k = k;
-                }
-            }
+        if (const Knobs &k = knobs(); cu_share_k <= 1 && k.cu_share_set) {
+            cu_share_i = k.cu_share_i;
+            cu_share_k = k.cu_share_k;
         }
         if (cu_share_k > 1 && num_cus >= 8 * cu_share_k) {
             // this handle's kernels run on CUs [i, i + 1) * num_cus / k only: the persistent grids of k ranks
@@ -491,8 +437,9 @@ void identity_pose(double T[7]);
 void fill_state(IcpState *st, const double init[7]);
 double accept_threshold(double max_dist);
 bool sparse_voxels(const sageicp_map &m);
-bool wants_filter(const sageicp_map &m, uint64_t n, double sem_th);
-IcpParams icp_params(const sageicp_map &m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift);
+int icp_lw(const Knobs &k, uint64_t n, bool sparse_voxels);
+bool wants_filter(const Knobs &k, const sageicp_map &m, uint64_t n, double sem_th);
+IcpParams icp_params(const Knobs &k, const sageicp_map &m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift);
 int run_icp(sageicp_map &m, const Point4 *d_frame, uint64_t n, const double init[7], double max_dist, double kernel,
             double sem_th, sageicp_comm *comm, double out[7], sageicp_stats *stats, double us_upload, double t_begin);
 int device_update_all(sageicp_map &m, const double *xyzl, uint64_t n, const double pose[7], const Point4 *d_points);

@@ -52,7 +52,8 @@ static int flagged(DevBuf<int> &flag, hipStream_t s, const FlagText (&texts)[N],
 // into every page.  (Measured and not kept: asking for huge pages first — no better; the copy cut
 // in pieces running behind the populating threads — slower than populate-then-copy, 3.1 vs 2.2 ms.)
 static void pretouch(void *p, size_t bytes) {
-    static const int threads = env_int("SAGEICP_TOUCH_THREADS", 4);
+    const Knobs &kn = knobs();
+    const int threads = std::min(kn.touch_threads.get(), ReplayPool::kMaxThreads);
     constexpr size_t kPage = 4096;
     if (threads <= 0 || bytes < (size_t{4} << 20)) return;
     static ReplayPool pool;
@@ -69,8 +70,7 @@ static void pretouch(void *p, size_t bytes) {
     // where the kernel hands out transparent huge pages on request (.../transparent_hugepage/enabled = madvise, the
     // usual setting), the 2-MB-aligned inside of the range is faulted in as ~20 huge pages instead of ~11,000 small
     // ones: 2.95 against 3.11 ms per LocalMap() of 46 MB (SAGEICP_HUGEPAGES=0: off)
-    static const int huge = env_int("SAGEICP_HUGEPAGES", 1);
-    if (huge) {
+    if (kn.hugepages.get()) {
         constexpr uintptr_t kHuge = uintptr_t{2} << 20;
         const uintptr_t h0 = (reinterpret_cast<uintptr_t>(lo_al) + kHuge - 1) & ~(kHuge - 1);
         const uintptr_t h1 = reinterpret_cast<uintptr_t>(hi_al) & ~(kHuge - 1);
@@ -195,7 +195,7 @@ int export_rows(OutputBuffers &ob, int device, const RowSource &src, const RowSi
     if (sink.kind == RowSink::kDeviceRows)
         return flagged(ob.d_flag, s, kRowFlags, [&](int *word) -> int {
             const EgressArgs e = egress_args(*sink.dst, word);
-            if (m && m->resident() && !env_int("SAGEICP_EGRESS_TWO_PASS", 0))
+            if (m && m->resident() && !knobs().egress_two_pass.get())
                 return gather_resident(*m, RowsOut{nullptr, e}, s);      // the gather writes the caller's layout itself
             // two passes: the rows packed, then k_egress
             if (int r = packed_rows(src, n, ob.d_pc, staged, s, &rows)) return r;
@@ -295,7 +295,7 @@ static int occupancy_on_device(const Point4 *d_pts, uint64_t n, const double *po
         HIPCHK(hipMemsetAsync(d_bits.data(), 0, words * sizeof(uint32_t), s));
         const OccTransform tf = pose ? occ_transform(pose) : OccTransform{};
         launch_occ_draw(d_pts, static_cast<int>(n), g, pose ? &tf : nullptr, pose ? nullptr : d_bits.data(),
-                        pose ? d_bits.data() : nullptr, word, env_int("SAGEICP_OCC_GLOBAL", 0) != 0, s);
+                        pose ? d_bits.data() : nullptr, word, knobs().occ_global.get() != 0, s);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(bits.data(), d_bits.data(), words * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         return SAGEICP_OK;

@@ -104,7 +104,7 @@ struct sageicp_pipeline {
         job.dyn = dyn_on ? &dyn_cfg : nullptr; job.deskew = deskew;
         // level 0 (frame_downsample: it goes into the map, AddPoints depends on arrival order)
         // keeps the reference's emission order; level 1 (the registered source) does not need it
-        pr.arrival_order_levels = env_int("SAGEICP_SOURCE_REFERENCE_ORDER", 0) ? 0u : 2u;
+        pr.arrival_order_levels = knobs().source_reference_order.get() ? 0u : 2u;
         pr.keep_raw = kf.on;
         return pr.run(src, job);
     }
@@ -157,7 +157,7 @@ static int key_frame_step(sageicp_pipeline *p, uint64_t n) {
     HIPCHK(hipMemsetAsync(k.d_cand.data(), 0, words * sizeof(uint32_t), s));
     if (k.has_key) HIPCHK(hipMemsetAsync(k.d_cur.data(), 0, words * sizeof(uint32_t), s));
     launch_occ_draw(pr.d_raw.data(), static_cast<int>(n), k.g, k.has_key ? &tf : nullptr, k.d_cand.data(), k.d_cur.data(),
-                    nullptr, env_int("SAGEICP_OCC_GLOBAL", 0) != 0, s);
+                    nullptr, knobs().occ_global.get() != 0, s);
     HIPCHK(hipGetLastError());
     launch_occ_decide(k.d_key.data(), k.d_cand.data(), k.d_cur.data(), words, k.has_key ? 0 : 1, k.prm.overlap_th,
                       k.d_dec.data(), s);

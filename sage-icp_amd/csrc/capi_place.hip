@@ -177,7 +177,7 @@ struct sageicp_place_db {
         launch_place_compile(d_query.data(), pd.prm.rings, pd.prm.sectors, q.h_tol, d_cells.data(), d_nq.data(), s);
         HIPCHK(hipGetLastError());
         launch_place_score(d_desc.data(), static_cast<uint32_t>(considered), pd.prm.rings, pd.prm.sectors, d_cells.data(),
-                           d_nq.data(), d_scores.data(), env_int("SAGEICP_PLACE_DOUBLED", 0) == 0, s);
+                           d_nq.data(), d_scores.data(), knobs().place_doubled.get() == 0, s);
         HIPCHK(hipGetLastError());
         launch_place_select(d_scores.data(), static_cast<uint32_t>(considered), d_nq.data(), q.top_k, d_top.data(), s);
         HIPCHK(hipGetLastError());

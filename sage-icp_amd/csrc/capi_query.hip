@@ -51,9 +51,10 @@ int QueryCall::sort_and_search(const Point4 *d_rows, uint64_t n, double sem_th, 
         if (int rc = wait()) return rc;
         if (sc.h_state.data()->bad_input) return refuse_non_finite(who_, noun_);
     }
-    const int lw = icp_lw(n, sparse_voxels(m));
-    if (int rc = m.dev.ensure_cand(wants_filter(m, n, sem_th), stream())) return rc;
-    const IcpParams ip = icp_params(m, sc.d_sorted.data(), n, sem_th, lw, 0);      // identity pose, no loop state
+    const Knobs &kn = knobs();
+    const int lw = icp_lw(kn, n, sparse_voxels(m));
+    if (int rc = m.dev.ensure_cand(wants_filter(kn, m, n, sem_th), stream())) return rc;
+    const IcpParams ip = icp_params(kn, m, sc.d_sorted.data(), n, sem_th, lw, 0);      // identity pose, no loop state
     launch_rows(ip, stream());
     launch_icp(ip, lw, false, stream());
     HIPCHK(hipGetLastError());

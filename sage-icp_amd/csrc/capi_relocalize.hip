@@ -42,7 +42,7 @@ static int check_score_args(const char *who, const sageicp_map *map, const doubl
 static int score_staged(QueryCall &c, uint64_t n, const double *poses, uint64_t k, double max_dist, double kernel,
                         double sem_th, sageicp_pose_score *out) {
     Scratch &sc = c.sc;
-    uint64_t chunk_rows = static_cast<uint64_t>(std::max(1, env_int("SAGEICP_SCORE_CHUNK_ROWS", 1 << 20)));
+    uint64_t chunk_rows = static_cast<uint64_t>(knobs().score_chunk_rows.get());
     chunk_rows = std::min<uint64_t>(chunk_rows, kMaxQueries);
     const uint64_t per_chunk = std::max<uint64_t>(1, chunk_rows / n);
     int rc;

@@ -62,8 +62,8 @@ bool sparse_voxels(const sageicp_map &m) {
 // 6+ points on average (c2: +6 %, c4: +10 %; c1, c5 and the streamed 24k-point frames lose 4-5 %
 // with it; SAGEICP_FILTER=0/1 overrides).  Off for a negative or NaN sem_th, where a larger
 // distance can scale to a smaller one and the filter's thresholds do not exist.
-bool wants_filter(const sageicp_map &m, uint64_t n, double sem_th) {
-    const int want = env_int("SAGEICP_FILTER", (n >= 40000 && !sparse_voxels(m)) ? 1 : 0);
+bool wants_filter(const Knobs &kn, const sageicp_map &m, uint64_t n, double sem_th) {
+    const int want = kn.filter.get((n >= 40000 && !sparse_voxels(m)) ? 1 : 0);
     return sem_th >= 0.0 && want != 0;
 }
 
@@ -72,14 +72,40 @@ bool wants_filter(const sageicp_map &m, uint64_t n, double sem_th) {
 // restarting in every voxel leaves lanes idle and makes the heaviest query's chain the longer one (c5:
 // +4.6 %, c1 through the launch-per-iteration loop: +13 %); against c2's and c4's ~12 points per voxel the
 // restart is faster by 1.5 and 5 %.  (8 and 16 lanes always stride flat; SAGEICP_FLAT=0/1 overrides.)
-static bool wants_flat(const sageicp_map &m, int lw) {
+static bool wants_flat(const Knobs &kn, const sageicp_map &m, int lw) {
     const MapCounts c = m.counts();
-    return env_int("SAGEICP_FLAT", c.points < (2ull << lw) * c.voxels ? 1 : 0) != 0;
+    return kn.flat.get(c.points < (2ull << lw) * c.voxels ? 1 : 0) != 0;
+}
+
+// Lanes per query in k_icp (log2).  One lane per query needs the fewest instructions per query
+// but gives a frame of n points only n / 64 waves with long dependent chains; small frames and
+// shards spread each query over more lanes.  Thresholds measured on MI355X (profiles/README.md);
+// SAGEICP_LW overrides for experiments.
+int icp_lw(const Knobs &kn, uint64_t n, bool sparse_voxels) {
+    if (kn.lw.get() >= 0) return kn.lw.get();
+    // (all of this re-measured after the flat-order scan, profiles/r04/lanes_probe2.txt (dense voxels) and
+    // lanes_probe3.txt (sparse ones); us per iteration)
+    // the biggest frames are bound by instruction issue, not by the length of a wave's chain: two
+    // lanes per query halve the per-query share of the fixed work (prologue, bounds, epilogue) — against
+    // dense voxels only at c4's size (500k: 90.7 against 92.9 with four, 400k a tie), against sparse ones
+    // from ~150k (c5, 200k: 42.8 / 43.2; 100k: 33.3 / 31.6)
+    if (n >= (sparse_voxels ? 150000u : 400000u)) return 1;
+    // eight lanes stride through a query's voxels in flat order (kernels.hip) and hold against dense voxels
+    // up to ~110k queries (50k: 25.7 against 31.1 with four; 60k: 28.0 / 31.5; 80k: 32.3 / 34.5; 100k: 36.2 /
+    // 37.1; 120k: 40.8 / 40.6), against sparse ones up to ~60k (25k: 19.8 / 22.9; 50k: 24.7 / 25.1; 100k:
+    // 34.9 / 31.6); until late round 4 the switch to four sat at 50k and, for sparse voxels, at 4k
+    if (n >= (sparse_voxels ? 60000u : 110000u)) return 2;
+    // sixteen lanes only for small frames against dense voxels (in flat order they hold up to ~20k queries:
+    // 10k 17.8 against 18.9 with eight, 15k 19.1 / 20.0, 30k 24.7 / 22.6 — lanes_probe4.txt; the switch used
+    // to sit at 10k): a scan against sparse ones is a handful of points whatever the split (c1, 10k: 17.6
+    // with eight, 20.7 with four)
+    if (n >= (sparse_voxels ? 4096u : 20000u)) return 3;
+    return 4;
 }
 
 // k_icp's arguments for a search of `n` queries against the HBM copy of `m`; the sums are accumulated at
 // 2^(-24 acc_shift) of their value (run_icp raises the shift for a frame whose sums left the fixed-point range)
-IcpParams icp_params(const sageicp_map &m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift) {
+IcpParams icp_params(const Knobs &kn, const sageicp_map &m, const Point4 *d_queries, uint64_t n, double sem_th, int lw, int acc_shift) {
     const Scratch &sc = m.sc;
     const SearchView map = m.dev.search_view();
     IcpParams ip{};
@@ -89,7 +115,7 @@ IcpParams icp_params(const sageicp_map &m, const Point4 *d_queries, uint64_t n, 
     ip.check_done = 0;
     ip.apply_pose = 0;
     ip.voxel_size = m.host.voxel_size;
-    ip.inv_voxel_size = env_int("SAGEICP_EXACT_DIVIDE", 0) ? 0.0 : 1.0 / m.host.voxel_size;
+    ip.inv_voxel_size = kn.exact_divide.get() ? 0.0 : 1.0 / m.host.voxel_size;
     ip.rows = sc.d_rows.data();
     ip.table = map.table;
     ip.mask = map.mask;
@@ -103,9 +129,9 @@ IcpParams icp_params(const sageicp_map &m, const Point4 *d_queries, uint64_t n, 
     {
         const double k1 = (1.0 + 1.0 / 1024.0) * (1.0 + 1e-6);
         const double inf = std::numeric_limits<double>::infinity();
-        const bool filt = wants_filter(m, n, sem_th) && env_int("SAGEICP_NO_FILTER", 0) == 0;
-        ip.filter = wants_filter(m, n, sem_th) ? 1 : 0;
-        ip.flat = wants_flat(m, lw) ? 1 : 0;
+        const bool filt = wants_filter(kn, m, n, sem_th) && kn.no_filter.get() == 0;
+        ip.filter = wants_filter(kn, m, n, sem_th) ? 1 : 0;
+        ip.flat = wants_flat(kn, m, lw) ? 1 : 0;
         ip.filt_inv_diff = filt ? k1 : inf;
         ip.filt_inv_same = filt ? (sem_th > 0.0 ? k1 / sem_th : inf) : inf;
         ip.filt_slack = std::ldexp(1.0, -44) * 1025.0 * (1.0 + 1e-6);
@@ -114,7 +140,7 @@ IcpParams icp_params(const sageicp_map &m, const Point4 *d_queries, uint64_t n, 
     ip.dist_init = DBL_MAX;
     // scaled distance = d2 * sem_th for matching labels, d2 otherwise: >= min(sem_th, 1) * d2.
     // A negative or NaN sem_th gives no usable bound: every occupied voxel is visited.
-    const bool prune = sem_th >= 0.0 && env_int("SAGEICP_NO_PRUNE", 0) == 0;
+    const bool prune = sem_th >= 0.0 && kn.no_prune.get() == 0;
     ip.prune_scale = prune ? std::min(sem_th, 1.0) * (1.0 - 1e-9) : 0.0;
     ip.keep_all = prune ? 0u : 0x7FFFFFFu;
     ip.nn_idx = sc.d_nn.data();
@@ -122,7 +148,7 @@ IcpParams icp_params(const sageicp_map &m, const Point4 *d_queries, uint64_t n, 
     ip.accept_r2 = -1.0;
     ip.nn_prev = sc.d_prev.data();
     ip.work = sc.d_work.data();
-    ip.acc_scale = std::ldexp(1.0, -24 * std::max(acc_shift, std::min(2, std::max(0, env_int("SAGEICP_ACC_SHIFT", 0)))));
+    ip.acc_scale = std::ldexp(1.0, -24 * std::max(acc_shift, kn.acc_shift.get()));
     {
         // k_fin adds the accumulator copies in 64-bit integers: blocks x limit < 2^62 (kernels.hip, kDigitLimitCounted)
         const uint64_t blocks = std::max<uint64_t>(1, (n + 3) / 4);
@@ -136,8 +162,8 @@ IcpParams icp_params(const sageicp_map &m, const Point4 *d_queries, uint64_t n, 
     const uint64_t qw = 64u >> lw;
     ip.nwaves = static_cast<unsigned>((n + qw - 1) / qw);
 #ifdef SAGE_ICP_DELAY_PROBE
-    ip.dbg_delay = static_cast<unsigned>(env_int("SAGEICP_DBG_DELAY", 0));
-    ip.dbg_repeat = static_cast<unsigned>(env_int("SAGEICP_DBG_REPEAT", 0));
+    ip.dbg_delay = static_cast<unsigned>(kn.dbg_delay.get());
+    ip.dbg_repeat = static_cast<unsigned>(kn.dbg_repeat.get());
 #endif
     return ip;
 }
@@ -171,15 +197,15 @@ static int loop_wgs_per_cu(const Scratch &sc, int lw, bool filter, int nw, size_
     // its ceil(nw / 4) waves on the same SIMD.  Four waves per workgroup, seven workgroups per CU fill the CU.
     return std::min(v, SAGE_LOOP_OCC / ((nw + 3) / 4));
 }
-static bool plan_loop(const sageicp_map &m, uint64_t n, double sem_th, LoopPlan *out) {
+static bool plan_loop(const Knobs &kn, const sageicp_map &m, uint64_t n, double sem_th, LoopPlan *out) {
     const Scratch &sc = m.sc;
-    const int mode = env_int("SAGEICP_LOOP", 1);       // 0: never, 1 / 2: wherever the frame fits
+    const int mode = kn.loop.get();                     // 0: never, 1 / 2: wherever the frame fits
     if (mode == 0 || n == 0 || sc.num_cus < 8) return false;
     const bool sparse = sparse_voxels(m);
-    const bool filter = wants_filter(m, n, sem_th);
+    const bool filter = wants_filter(kn, m, n, sem_th);
     const uint64_t cus = static_cast<uint64_t>(sc.num_cus);
-    const int env_nw = std::min(kLoopMaxWavesHost, std::max(0, env_int("SAGEICP_LOOP_WAVES", 0)));
-    const int env_gpw = std::max(0, env_int("SAGEICP_LOOP_GPW", 0));
+    const int env_nw = std::min(kLoopMaxWavesHost, kn.loop_waves.get());
+    const int env_gpw = kn.loop_gpw.get();
     auto groups_at = [n](int l) { return (n + (64u >> l) - 1) / (64u >> l); };
     // the workgroup slots a launch may count on: k per CU less a sixteenth (below) — and behind a CU mask (SAGEICP_CU_SHARE:
     // ranks sharing one GPU) one per CU fewer for every halving of the device: on half of the CUs six of seven workgroups per
@@ -222,7 +248,7 @@ static bool plan_loop(const sageicp_map &m, uint64_t n, double sem_th, LoopPlan 
                 uint64_t cap = slots(k) / 32 * 32;
                 cap = cap > 32ull * static_cast<uint64_t>(sc.loop_derate) ? cap - 32ull * static_cast<uint64_t>(sc.loop_derate) : 0;
                 if (cap < 32) continue;
-                if (const int e = env_int("SAGEICP_LOOP_MAX_WGS", 0)) cap = std::min<uint64_t>(cap, static_cast<uint64_t>(e) / 32 * 32);   // (probes)
+                if (const int e = kn.loop_max_wgs.get()) cap = std::min<uint64_t>(cap, static_cast<uint64_t>(e) / 32 * 32);   // (probes)
                 // (every resident workgroup slot is used: the groups are dealt out evenly over the workgroups,
                 // so more workgroups mean fewer waves that have to make a second pass)
                 uint64_t gpw = env_gpw ? static_cast<uint64_t>(env_gpw) : (groups + cap - 1) / cap;
@@ -241,8 +267,8 @@ static bool plan_loop(const sageicp_map &m, uint64_t n, double sem_th, LoopPlan 
         }
         return best > 0;
     };
-    const int forced = env_int("SAGEICP_LW", -1);
-    int lw = forced >= 0 ? std::min(forced, 4) : icp_lw(n, sparse);
+    const int forced = kn.lw.get();
+    int lw = icp_lw(kn, n, sparse);
     if (lw < 1) return false;                          // (k_loop is built for 2..16 lanes per query)
     if (forced < 0 && !env_gpw) {
         // An iteration of k_loop ends with its slowest wave, and with eight or more lanes per query the
@@ -262,7 +288,7 @@ static bool plan_loop(const sageicp_map &m, uint64_t n, double sem_th, LoopPlan 
         const uint64_t resident_waves = 4ull * SAGE_LOOP_OCC * cus * 15 / 16;
         while (lw > 2 && groups_at(lw) > resident_waves * 4 / 5) --lw;
     }
-    const bool dbg = env_int("SAGEICP_LOOP_DEBUG", 0) != 0;
+    const bool dbg = kn.loop_debug.get() != 0;
     bool ok = !env_gpw && one_pass(lw, env_nw ? env_nw : 4, out);
     if (!ok) ok = multi_pass(lw, out);
     if (dbg) {
@@ -302,6 +328,7 @@ struct Attempt {
 
 // What the attempts of a call share: its arguments and what follows from them and the knobs alone.
 struct IcpCall {
+    const Knobs &kn;            // the one snapshot of the knobs every attempt of the call reads
     sageicp_map &m;
     const Point4 *d_frame;
     uint64_t n;
@@ -325,9 +352,9 @@ struct IcpCall {
         if (comm && !p2p && !comm->comm)
             return fail(SAGEICP_ERR_INVALID, "communicator without RCCL needs a connected p2p exchange");
         // (the direct exchange enqueues no collective, so its loop can be polled like the 1-GPU one)
-        polled = (!comm || p2p) && env_int("SAGEICP_CHUNKED", 0) == 0;
+        polled = (!comm || p2p) && kn.chunked.get() == 0;
         // (probes and tests: SAGEICP_MAX_ITER stops either loop early — the launch-per-iteration loop then simply runs out of launches)
-        max_it = std::min(kMaxIterations, std::max(1, env_int("SAGEICP_MAX_ITER", kMaxIterations)));
+        max_it = std::min(kMaxIterations, kn.max_iter.get(kMaxIterations));
         // (the counters behind sum_candidates / pairs_evaluated cost ~45 vector instructions per pass, a memset and a
         // launch per frame: a caller that wants the other statistics only — bench.py's timed region — switches them off)
         counting = want_stats && g_counting != 0;
@@ -340,8 +367,8 @@ struct IcpCall {
         // a peer's sums normally arrive within microseconds, but its FIRST launches of a process (code
         // object loading) or a GPU shared with other work can take a second: five seconds of in-kernel
         // waiting is a failure (SAGEICP_P2P_TIMEOUT_S overrides, e.g. under a debugger)
-        xp.timeout_ticks = 100000000ull * static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_P2P_TIMEOUT_S", 5)));
-        if (const int ticks = env_int("SAGEICP_P2P_TIMEOUT_TICKS", 0))      // tests: provoke a timeout
+        xp.timeout_ticks = 100000000ull * static_cast<unsigned long long>(kn.p2p_timeout_s.get());
+        if (const int ticks = kn.p2p_timeout_ticks.get())      // tests: provoke a timeout
             xp.timeout_ticks = static_cast<unsigned long long>(ticks);
         return SAGEICP_OK;
     }
@@ -372,7 +399,7 @@ struct IcpCall {
     // c2 cold start, profiles/README.md.)
     int order_frame() const {
         // ... from kSortFrameFrom points on (kernels.h); SAGEICP_SORT_FROM overrides the size (0: always sorted)
-        if (n > 0 && n < static_cast<uint64_t>(std::max(0, env_int("SAGEICP_SORT_FROM", kSortFrameFrom))))
+        if (n > 0 && n < static_cast<uint64_t>(kn.sort_from.get(kSortFrameFrom)))
             HIPCHK(check_copy_frame(d_frame, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), comm == nullptr, s));
         else if (n > 0)
             HIPCHK(sort_frame(d_frame, sc.d_sorted.data(), static_cast<int>(n), sc.d_state.data(), true, comm == nullptr,
@@ -400,9 +427,9 @@ static AttemptPlan plan_attempt(const IcpCall &c, const Attempt &a) {
     // out, the calls of the cool-down after it) — the fixed-point sums are rounded once per group of queries,
     // so their bits depend on the lanes per query and on nothing else, and a call repeated gives the same bits.
     // (SAGEICP_CHUNKED=1 asks for the chunked launch-per-iteration loop by name)
-    p.loop_shape = (!comm || (c.p2p && !comm->device_shared && env_int("SAGEICP_CHUNKED", 0) == 0)) &&
-                   plan_loop(c.m, n, c.sem_th, &p.loop);
-    p.lw = p.loop_shape ? p.loop.lw : icp_lw(n, sparse_voxels(c.m));
+    p.loop_shape = (!comm || (c.p2p && !comm->device_shared && c.kn.chunked.get() == 0)) &&
+                   plan_loop(c.kn, c.m, n, c.sem_th, &p.loop);
+    p.lw = p.loop_shape ? p.loop.lw : icp_lw(c.kn, n, sparse_voxels(c.m));
     // a launch that timed out (its grid was not resident as a whole: the GPU is shared with other work)
     // cost 50 ms before the frame went through the other loop: the next calls do not try again
     p.use_loop = p.loop_shape && !a.no_loop;
@@ -425,9 +452,9 @@ static AttemptPlan plan_attempt(const IcpCall &c, const Attempt &a) {
     // SAGEICP_CHAIN_COMM=1: the only place it could be measured, two processes sharing one GPU, runs c4 twice as slowly
     // with it (42.7 against 21.0 ms per frame: the waiting launches of two processes on one device's queues,
     // profiles/r06/run63.sh); on a GPU per rank it has never run.  Never for several ranks of one process on one device.)
-    const bool chain_comm = comm && c.p2p && !comm->device_shared && env_int("SAGEICP_CHAIN_COMM", 0) != 0;
+    const bool chain_comm = comm && c.p2p && !comm->device_shared && c.kn.chain_comm.get() != 0;
     p.chain = !p.loop_shape && (!comm || chain_comm) && c.polled && n > 0 &&
-              p.chain_grid / kChainReplicas <= 255 && !a.no_chain && !c.prof2 && env_int("SAGEICP_CHAIN", 1) != 0;
+              p.chain_grid / kChainReplicas <= 255 && !a.no_chain && !c.prof2 && c.kn.chain.get() != 0;
     return p;
 }
 
@@ -444,13 +471,14 @@ static bool solver_is_own_launch(const AttemptPlan &p) {
 // The solving wave's arguments, for the one-launch loop or for the chained launches (p.use_loop or p.chain).  Every
 // call takes a new epoch of the handle's shared block.
 static LoopParams solver_params(const IcpCall &c, const AttemptPlan &p, double acc_unscale) {
+    const Knobs &kn = c.kn;
     LoopParams L{};
     L.sh = c.sc.d_loop.data();
     L.st = c.sc.d_state.data();
     // a wait inside the launch normally takes microseconds; 50 ms of it means the grid is not
     // resident as a whole (SAGEICP_LOOP_TIMEOUT_MS overrides, e.g. under a debugger)
-    L.timeout_ticks = 100000ull * static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_LOOP_TIMEOUT_MS", 50)));
-    const int test_ticks = env_int("SAGEICP_LOOP_TIMEOUT_TICKS", 0);      // tests: provoke a timeout
+    L.timeout_ticks = 100000ull * static_cast<unsigned long long>(kn.loop_timeout_ms.get());
+    const int test_ticks = kn.loop_timeout_ticks.get();      // tests: provoke a timeout
     if (test_ticks) L.timeout_ticks = static_cast<unsigned long long>(test_ticks);
     if (p.chain) {
         L.wgs = p.chain_grid;                     // every workgroup of a launch sends its sums, also the ones past the frame's end
@@ -463,7 +491,7 @@ static LoopParams solver_params(const IcpCall &c, const AttemptPlan &p, double a
         L.nw = p.loop.nw; L.gpw = p.loop.gpw; L.wgs = p.loop.wgs;
         L.copies = kLoopReplicas;
         L.progress = nullptr;
-        L.contiguous = env_int("SAGEICP_LOOP_CONTIGUOUS", 0) ? 1 : 0;
+        L.contiguous = kn.loop_contiguous.get() ? 1 : 0;
         const uint64_t qw = 64u >> p.loop.lw, groups = (c.n + qw - 1) / qw;
         for (int x = 0; x <= 8; ++x) L.xcd_first[x] = static_cast<uint32_t>(groups * x / 8);
         // (an XCD's workgroups must be able to hold its range)
@@ -471,8 +499,8 @@ static LoopParams solver_params(const IcpCall &c, const AttemptPlan &p, double a
         for (int x = 0; x < 8; ++x)
             if (L.contiguous == 1 && (L.xcd_first[x + 1] - L.xcd_first[x] + nwg - 1) / nwg > static_cast<uint64_t>(p.loop.gpw)) L.contiguous = 0;
         L.count_timeout_ticks = L.timeout_ticks;       // (the solving wave's wait for its own workgroups: local, short)
-        L.prio = std::min(3, std::max(0, env_int("SAGEICP_LOOP_PRIO", 3)));
-        L.deal = std::min(2, std::max(0, env_int("SAGEICP_LOOP_DEAL", 1)));       // 1: loop_deal.h's table | 2: the formula alone | 0: no deal
+        L.prio = kn.loop_prio.get();
+        L.deal = kn.loop_deal.get();       // 1: loop_deal.h's table | 2: the formula alone | 0: no deal
     }
     if (c.comm) {
         // (under a communicator the workgroups — or a chained launch — wait for a pose that waits for the peers' sums:
@@ -481,11 +509,11 @@ static LoopParams solver_params(const IcpCall &c, const AttemptPlan &p, double a
         L.shared_loop = 1;
         if (test_ticks == 0) L.timeout_ticks = std::max(L.timeout_ticks, c.xp.timeout_ticks + 100000000ull);
         // (tests: ONE rank of a communicator loses its grid or its launches — the others must follow it out of the exchange)
-        if (env_int("SAGEICP_LOOP_COUNT_TIMEOUT_RANK", -1) == c.comm->rank)
-            L.count_timeout_ticks = static_cast<unsigned long long>(std::max(1, env_int("SAGEICP_LOOP_COUNT_TIMEOUT_TICKS", 1)));
+        if (kn.loop_count_timeout_rank.get() == c.comm->rank)
+            L.count_timeout_ticks = static_cast<unsigned long long>(kn.loop_count_timeout_ticks.get());
     }
     // (tests: the workgroups on other copies of the pose than their XCD's — any copy is the pose; kernels.h, kLoopPoseCopies)
-    L.pose_map = std::min(2, std::max(0, env_int("SAGEICP_LOOP_POSE_MAP", 0)));
+    L.pose_map = kn.loop_pose_map.get();
     L.max_iterations = c.max_it;
     L.epoch = ++c.sc.loop_epoch;
     for (int i = 0; i < 7; ++i) L.T0[i] = c.init[i];
@@ -579,13 +607,13 @@ static int run_one_launch(const IcpCall &c, const AttemptPlan &p, const IcpParam
         // (sageicp_types.h, P2pBlock::abort_tag) — this frame goes through the other form on every rank, in step; no cool-down here
         sc.last_fallback = SAGEICP_LOOP_FALLBACK_PEER;
     } else {
-        sc.loop_cooldown = std::max(0, env_int("SAGEICP_LOOP_COOLDOWN", 256));
-        if (env_int("SAGEICP_LOOP_TIMEOUT_TICKS", 0) == 0 && env_int("SAGEICP_LOOP_COUNT_TIMEOUT_RANK", -1) < 0 && sc.loop_derate < 16) ++sc.loop_derate;
+        sc.loop_cooldown = c.kn.loop_cooldown.get();
+        if (c.kn.loop_timeout_ticks.get() == 0 && c.kn.loop_count_timeout_rank.get() < 0 && sc.loop_derate < 16) ++sc.loop_derate;
         ++sc.loop_timeouts;
         sc.last_fallback = SAGEICP_LOOP_FALLBACK_TIMEOUT;
         // (said out loud once per process: the fast path was lost, and what it cost)
         static std::atomic<int> told{0};
-        if (told.exchange(1) == 0 && env_int("SAGEICP_QUIET", 0) == 0)
+        if (told.exchange(1) == 0 && c.kn.quiet.get() == 0)
             std::fprintf(stderr, "sageicp: a wait inside the one-launch ICP loop timed out (the GPU is shared with other work, or "
                                  "fewer workgroups are resident than planned): this frame goes through the launch-per-iteration "
                                  "loop, the next %d calls of this map too, later plans take %d workgroups fewer "
@@ -646,7 +674,7 @@ struct Iterations {
         stripes = c.n > 0 ? static_cast<unsigned>(icp_stripes_for(static_cast<int>(c.n), lw)) : 0u;
         // (three small sorts per frame: worth it from ~40k points on — c1 through this loop: +4.5 % with them)
         lpt = stripes >= 16 && stripes <= sc.sort_cap && stripe_sort_temp_bytes(stripes) <= sc.d_sort_temp.capacity() &&
-              env_int("SAGEICP_LPT", c.n >= 40000 ? 1 : 0) != 0;
+              c.kn.lpt.get(c.n >= 40000 ? 1 : 0) != 0;
         st_work = sc.d_keys.data(); st_sorted = sc.d_keys.data() + stripes; st_iota = sc.d_vals.data(); st_order = sc.d_vals.data() + stripes;
         if (lpt) stripe_order_init(st_work, st_iota, stripes, s);
         return SAGEICP_OK;
@@ -692,7 +720,7 @@ struct Iterations {
     // of the chained launches timed out, and the frame has to be registered again without the chain.
     int run_polled() {
         int rc;
-        const int depth = std::min(8, std::max(1, env_int("SAGEICP_DEPTH", 4)));
+        const int depth = c.kn.depth.get();
         volatile unsigned long long *word = &sc.h_prog.data()->word;
         int enq = 0;
         unsigned spins = 0;
@@ -735,7 +763,7 @@ struct Iterations {
             // a wait timed out (the solving wave was not resident beside the launches, or a launch took longer than its
             // patience): the frame again with k_fin between the launches — same lanes per query, same bits
             static std::atomic<int> told{0};
-            if (told.exchange(1) == 0 && env_int("SAGEICP_QUIET", 0) == 0)
+            if (told.exchange(1) == 0 && c.kn.quiet.get() == 0)
                 std::fprintf(stderr, "sageicp: a wait inside the chained ICP launches timed out: this frame is registered again with "
                                      "k_fin between the launches\n");
             r.chain_gave_up = true;
@@ -775,9 +803,9 @@ static int run_attempt(const IcpCall &c, const Attempt &a, AttemptResult &r) {
     int rc;
     if ((rc = c.start_state())) return rc;
     const AttemptPlan p = plan_attempt(c, a);
-    if ((rc = c.m.dev.ensure_cand(wants_filter(c.m, c.n, c.sem_th), c.s))) return rc;
+    if ((rc = c.m.dev.ensure_cand(wants_filter(c.kn, c.m, c.n, c.sem_th), c.s))) return rc;
     if ((rc = sc.reserve_sort(c.n))) return rc;
-    IcpParams ip = icp_params(c.m, sc.d_sorted.data(), c.n, c.sem_th, p.lw, a.acc_shift);
+    IcpParams ip = icp_params(c.kn, c.m, sc.d_sorted.data(), c.n, c.sem_th, p.lw, a.acc_shift);
     ip.check_done = 1; ip.apply_pose = 1;
     ip.kernel = c.kernel;
     ip.accept_r2 = accept_threshold(c.max_dist);
@@ -834,7 +862,7 @@ int run_icp(sageicp_map &m, const Point4 *d_frame, uint64_t n, const double init
     Scratch &sc = m.sc;
     if (n > kMaxQueries) return fail(SAGEICP_ERR_INVALID, "frame too large (2^26 - 4 points max)");
     int rc;
-    IcpCall c{m, d_frame, n, init, max_dist, kernel, sem_th, comm, sc, sc.stream.get(), false, false, false, false, false, 0, P2pParams{}};
+    IcpCall c{knobs(), m, d_frame, n, init, max_dist, kernel, sem_th, comm, sc, sc.stream.get(), false, false, false, false, false, 0, P2pParams{}};
     if ((rc = c.constants(stats != nullptr))) return rc;
     if (c.prof && (rc = sc.reserve_events(c.polled ? kMaxIterations : kChunkMax))) return rc;
     Attempt a;
@@ -1000,7 +1028,7 @@ int register_sharded(sageicp_map &m, const double *h_frame, const Point4 *d_fram
             if (r) return r;
             Scratch &sc = mk.sc;
             if ((r = sc.reserve_frame(cnt))) return r;
-            if ((r = mk.dev.ensure_cand(wants_filter(mk, cnt, sem_th), sc.stream.get()))) return r;
+            if ((r = mk.dev.ensure_cand(wants_filter(knobs(), mk, cnt, sem_th), sc.stream.get()))) return r;
             if ((r = sc.reserve_sort(cnt))) return r;
             mine = sc.d_frame.data();
             if (cnt) {

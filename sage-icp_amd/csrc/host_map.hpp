@@ -34,7 +34,6 @@
 
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <initializer_list>
 #include <new>
@@ -159,7 +158,7 @@ public:
 
     HostMap() { reset_table(1024); }
 
-    void configure(double vs, double md, int b, int c, const int *labels, int nl) {
+    void configure(double vs, double md, int b, int c, const int *labels, int nl, bool classed) {
         voxel_size = vs;
         max_distance = md;
         basic = b;
@@ -167,9 +166,7 @@ public:
         cap = b + c;
         basic_labels.assign(labels, labels + nl);
         // size classes 4 / 8 / 16 below the capacity, then the capacity (rounded up to whole units);
-        // SAGEICP_SIZE_CLASSES=0 (read when the map is created) keeps the single full-size class
-        const char *e = std::getenv("SAGEICP_SIZE_CLASSES");
-        const bool classed = !(e && e[0] == '0');
+        // `classed` false (SAGEICP_SIZE_CLASSES=0 when the map is created) keeps the single full-size class
         n_classes = 0;
         if (classed)
             for (uint32_t sz : {4u, 8u, 16u})

@@ -283,7 +283,7 @@ int Prep::restore_reference_order(int level, Point4 *dst, uint32_t kept) {
         if (!pool) pool.reset(new ReplayPool);
         const size_t hw = std::max(1u, std::thread::hardware_concurrency());
         pool->run(runs.size(), [&](size_t k) { replay(by_size[k]); },
-                  std::min<size_t>(hw, static_cast<size_t>(std::max(1, env_int("SAGEICP_REPLAY_THREADS", 8)))));
+                  std::min<size_t>(hw, static_cast<size_t>(knobs().replay_threads.get())));
     } else {
         for (size_t r = 0; r < runs.size(); ++r) replay(r);
     }
@@ -291,7 +291,7 @@ int Prep::restore_reference_order(int level, Point4 *dst, uint32_t kept) {
     HIPCHK(hipMemcpyAsync(d_perm.data(), h_perm.data(), kept * sizeof(uint32_t), hipMemcpyHostToDevice, stream.get()));
     launch_vds_permute(dst, d_perm.data(), kept, d_tmp.data(), stream.get());
     HIPCHK(hipMemcpyAsync(dst, d_tmp.data(), kept * sizeof(Point4), hipMemcpyDeviceToDevice, stream.get()));
-    if (env_int("SAGEICP_DEBUG_ORDER", 0)) {
+    if (knobs().debug_order.get()) {
         std::string rs;
         for (auto &r : runs) rs += " " + std::to_string(r.second - r.first);
         std::fprintf(stderr, "order level %d: kept %u, fetch keys %.0f us, replay %.0f us (runs:%s), rest %.0f us\n",

@@ -19,6 +19,7 @@ namespace sageicp {
 // if the caller sorted them so).
 class ReplayPool {
 public:
+    static constexpr int kMaxThreads = 64;     // what a caller that takes the count from outside asks for at most
     ~ReplayPool() {
         {
             std::lock_guard<std::mutex> lk(mu_);

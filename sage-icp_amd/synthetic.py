@@ -300,7 +300,7 @@ def make_stream(seed, n_frames, points_per_frame=30000, half=120.0, step=(1.0, 0
 # sensor, so the density of a scan falls with range ring by ring, surfaces are occluded, and a map built from such scans
 # is dense near the driven path and thin far from it.  (sample_surfaces / make_scan draw points on the surfaces directly,
 # thinned by a range rule: every surface is seen from everywhere.)  Used to check that the library's break-points (lanes per
-# query, compact-scan filter, flat order: capi_internal.h::icp_lw, capi_run.hip::wants_filter / wants_flat) — measured on
+# query, compact-scan filter, flat order: capi_run.hip::icp_lw / wants_filter / wants_flat) — measured on
 # the first family — hold on scans of LiDAR geometry: profiles/README.md, tests/test_gpu_parity.py.
 def _blob_cells(lo, hi):
     """the vegetation blobs of sample_surfaces whose 16-m grid cells intersect [lo, hi]^2: (cx, cy) arrays"""

@@ -195,6 +195,30 @@ def test_initial_guess_and_repeated_calls(gpu_sage, oracle):
             assert np.array_equal(b, c)
 
 
+def test_a_knob_flipped_between_calls_reaches_each_call_whole(gpu_sage, oracle):
+    """one frame registered three times in one process, SAGEICP_LOOP = 1, 0, 1 with four lanes per query pinned: every
+    call takes the form its own environment asks for — in its statistics and in the handle's counts — and the three
+    poses are one pose to the bit"""
+    from sage_icp_amd import synthetic as syn
+    w, om = _workload(gpu_sage, oracle, "c2", 0.05)
+    assert len(w["scan"]) >= 512
+    p = syn.PARAMS["cold"]
+    poses, seen = [], []
+    for loop in (1, 0, 1):
+        s0 = w["map"].loop_status()
+        with Env(SAGEICP_LW=2, SAGEICP_LOOP=loop):
+            a, sa = gpu_sage.register_frame(w["scan"], w["map"], gpu_sage.IDENTITY, p["max_dist"], p["kernel"], p["sem_th"],
+                                            return_stats=True)
+        s1 = w["map"].loop_status()
+        poses.append(a)
+        seen.append((sa.single_launch, sa.lanes_per_query, s1.calls_single_launch - s0.calls_single_launch,
+                     s1.calls_per_iteration - s0.calls_per_iteration))
+    print(seen)
+    assert seen == [(1, 4, 1, 0), (0, 4, 0, 1), (1, 4, 1, 0)]
+    assert np.array_equal(poses[0], poses[1]) and np.array_equal(poses[0], poses[2])
+    assert poses[0].tobytes() == poses[1].tobytes() == poses[2].tobytes()
+
+
 def test_frame_that_does_not_fit_uses_the_launch_per_iteration_loop(gpu_sage, oracle):
     """rows and per-query state of every query have to fit the LDS of the machine (232 B per query, 160 KB per
     CU: ~170k queries on 256 CUs)"""
