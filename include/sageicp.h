@@ -72,7 +72,8 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * candidate poses and relocalisation — sageicp_pose_score, sageicp_score_poses / _device, sageicp_relocalize_params,
  * sageicp_relocalize_info, sageicp_relocalize_candidates, sageicp_relocalize / _device; then the archive of a map —
  * sageicp_archive_info, sageicp_archive_voxel, SAGEICP_ARCHIVE_* / SAGEICP_SESSION, sageicp_map_set_archive,
- * sageicp_map_archive_info / _clear / _voxels / _rows / _rows_device / _msg / _msg_device, sageicp_pipeline_set_archive
+ * sageicp_map_archive_info / _clear / _voxels / _rows / _rows_device / _msg / _msg_device, sageicp_pipeline_set_archive;
+ * then recall — sageicp_recall_info, sageicp_map_recall, sageicp_pipeline_recall
  * (additions only: no existing struct or entry changed). */
 #define SAGEICP_ABI_VERSION 4
 
@@ -925,6 +926,40 @@ int sageicp_map_archive_msg(const sageicp_map *m, int which, uint64_t first, con
 int sageicp_map_archive_msg_device(const sageicp_map *m, int which, uint64_t first, const sageicp_msg_colors *colors, void *out,
                                    uint64_t cap_points, void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
 int sageicp_pipeline_set_archive(sageicp_pipeline *p, int enable, uint64_t max_rows);   /* its map's */
+
+/* ---- recall: a place of the session's map back into a map that can be searched -------------------------
+ * Additions only; the ABI version stays.  The session's voxels of `src` are the SAGEICP_ARCHIVE_LATEST records of its
+ * archive in log order followed by its live voxels in sageicp_map_pointcloud's order (what SAGEICP_SESSION exports; with
+ * the archive off or empty, the live map).  sageicp_map_recall keeps voxel v iff its FIRST stored row p is not far from
+ * `center` — far as RemovePointsFarFromLocation decides it, (p - center).squaredNorm() > radius * radius, radius * radius
+ * formed once; a voxel is kept or dropped whole, by its first row alone — and puts the kept voxels into `dst` in session
+ * order, each with its rows bit for bit in stored order: what a local map of max_distance = radius standing at `center`
+ * would still hold of the session.
+ * dst: cleared first, as by sageicp_map_clear (its own archive is left alone and nothing is logged into it); afterwards
+ * it holds the kept voxels and nothing else, blocks handed out in arrival order (sageicp_map_pointcloud: the kept rows in
+ * session order), and it is resident: filled on the device, nothing downloaded.  From then on an ordinary map — search,
+ * updates on either side, archive, exports, download.  Its rows, their order and its counters equal those of a fresh map
+ * of the same voxel size and policy after sageicp_map_add_points(SESSION rows) and sageicp_map_remove_far(center) at
+ * max_distance = radius; where a region lies in the point array and a slot in the table may differ (no result depends on
+ * either), and so may the block a LATER update gives a new voxel: here every block below num_voxels is taken, there the
+ * evicted ones are free and handed out first.
+ * SAGEICP_ERR_INVALID, dst untouched: a null handle; dst == src; a non-finite centre; a radius that is negative or NaN
+ * (+inf recalls the whole session); a dst whose voxel size, points per voxel (basic, critical) or basic labels differ
+ * from src's; a dst in reference-order mode, spanning several devices, or on another device than src's first.  src may be
+ * in either mode and span several devices (its first copy is the one that archives).  Device work: SAGEICP_ERR_NO_DEVICE
+ * without one.  SAGEICP_ERR_CAPACITY: more than 2^32 - 2 records, or more voxels / storage units than a map holds.  After
+ * any failure past the argument checks dst is left cleared, never partly filled.  src: a pending host tail of its archive
+ * is moved to the device first, as by an export; a resident src stays resident.  Synchronous. */
+typedef struct sageicp_recall_info {
+    uint64_t voxels, rows;                    /* what dst holds now */
+    uint64_t archive_voxels, archive_rows;    /* of them, from the archive (LATEST) */
+    uint64_t map_voxels, map_rows;            /* of them, from src's live map */
+    uint64_t session_voxels, session_rows;    /* what was considered */
+} sageicp_recall_info;
+int sageicp_map_recall(const sageicp_map *src, const double center[3], double radius, sageicp_map *dst,
+                       sageicp_recall_info *info /* may be NULL */);
+int sageicp_pipeline_recall(const sageicp_pipeline *p, const double center[3], double radius, sageicp_map *dst,
+                            sageicp_recall_info *info /* may be NULL */);   /* its local map's */
 
 /* ---- place recognition: the semantic scan context of key frames (place.hip) -------------------------------------------
  * Additions only; the ABI version stays.  A descriptor says where the sensor stood: a polar grid of R rings by S sectors

@@ -226,6 +226,15 @@ class ArchiveInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class RecallInfo(C.Structure):
+    """sageicp_recall_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("voxels", "rows", "archive_voxels", "archive_rows", "map_voxels", "map_rows",
+                                          "session_voxels", "session_rows")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 ARCHIVE_ALL, ARCHIVE_LATEST, SESSION = 0, 1, 2          # SAGEICP_ARCHIVE_ALL / _LATEST, SAGEICP_SESSION
 ARCHIVE_WHICH = {"all": ARCHIVE_ALL, "latest": ARCHIVE_LATEST, "session": SESSION}
 # sageicp_archive_voxel
@@ -498,6 +507,8 @@ _SIGNATURES = [
     ("sageicp_map_archive_msg_device", C.c_int,
      [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(MsgColors), C.c_void_p, C.c_uint64, C.c_void_p, _u64p]),
     ("sageicp_pipeline_set_archive", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
+    ("sageicp_map_recall", C.c_int, [C.c_void_p, _dp, C.c_double, C.c_void_p, C.POINTER(RecallInfo)]),
+    ("sageicp_pipeline_recall", C.c_int, [C.c_void_p, _dp, C.c_double, C.c_void_p, C.POINTER(RecallInfo)]),
     ("sageicp_place_tables", C.c_int, [C.POINTER(PlaceParams), _dp, _dp]),
     ("sageicp_place_describe", C.c_int, [_dp, C.c_uint64, C.POINTER(PlaceParams), C.c_void_p, C.c_int]),
     ("sageicp_place_describe_device", C.c_int, [C.POINTER(DeviceFrame), C.POINTER(PlaceParams), C.c_void_p, C.c_void_p]),
@@ -1156,6 +1167,13 @@ class VoxelHashMap:
         """ArchivedPointcloud()'s rows as (n, 21) uint8 records; the arguments as PointcloudMsg"""
         return _archive_msg(lambda: self._h, self.device, colors, which, first, device, out)
 
+    def Recall(self, center, radius, into=None):
+        """The voxels of the session's map (the archive's latest generations, then the live map: what
+        ArchivedPointcloud("session") exports) whose first row lies within `radius` of `center`, put into the map `into`
+        on the device (sageicp_map_recall).  `into` is cleared first and ends resident; None: a new map
+        with this map's parameters on its device, max_distance = radius.  Returns (into, info dict)."""
+        return _recall(lib().sageicp_map_recall, self._h, self, center, radius, into)
+
     def resident(self):
         """True while the HBM copy of the map is the authority (after a device-side update)"""
         return bool(lib().sageicp_map_resident(self._h))
@@ -1786,6 +1804,13 @@ class SageICP:
     def archive_info(self):
         return _archive_info(lib().sageicp_pipeline_local_map(self._h))
 
+    def Recall(self, center, radius, into=None):
+        """VoxelHashMap.Recall on the pipeline's local map (sageicp_pipeline_recall): returns (into, info dict)"""
+        c = self.config
+        like = VoxelHashMap(c.voxel_size_map, float(radius), c.basic_points_per_voxel, c.critical_points_per_voxel,
+                            [c.basic_parts_labels[i] for i in range(c.n_basic_parts_labels)], device=c.device, _handle=0)
+        return _recall(lib().sageicp_pipeline_recall, self._h, like, center, radius, into)
+
     def archive_voxels(self):
         return _archive_voxels(lib().sageicp_pipeline_local_map(self._h))
 
@@ -1814,6 +1839,19 @@ class SageICP:
         k = C.c_uint64(0)
         _check(lib().sageicp_pipeline_source(self._h, a.ctypes.data_as(_dp), n, C.byref(k)))
         return a
+
+
+def _recall(entry, handle, like, center, radius, into):
+    """`like`: the VoxelHashMap (or its parameters) a fresh destination is created from"""
+    c = np.ascontiguousarray(center, dtype=np.float64).reshape(-1)
+    if c.size != 3:
+        raise ValueError("Recall takes a centre[3]")
+    if into is None:
+        into = VoxelHashMap(like.voxel_size_, float(radius), like.basic_points_per_voxel_, like.critical_points_per_voxel_,
+                            like.basic_parts_labels_, device=like.device)
+    info = RecallInfo()
+    _check(entry(handle, c.ctypes.data_as(_dp), float(radius), into._h, C.byref(info)))
+    return into, info.as_dict()
 
 
 def _archive_info(h):

@@ -397,7 +397,7 @@ struct sageicp_comm {
 // (query.h) — with GetCorrespondences, RegistrationQuality and the host side of the quality report.
 // capi_relocalize.hip: the candidate grid, the chunked batch score of candidate poses and Relocalize, on that path.
 // capi_run.hip: the ICP loop (plan_loop, run_icp and its attempts), the RCCL binding and the single-process multi-GPU
-// mode.
+// mode.  capi_recall.hip: recall (recall.h) — a place of a session's map into a second handle, on the device.
 namespace sageicp_impl {
 struct Rccl {
     void *h = nullptr;

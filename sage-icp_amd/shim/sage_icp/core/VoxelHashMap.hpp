@@ -131,6 +131,23 @@ struct VoxelHashMap {
     // does not hold, then Pointcloud().
     Vector4dVector ArchivedPointcloud() const { return ArchiveRows(SAGEICP_ARCHIVE_ALL, "ArchivedPointcloud"); }
     Vector4dVector SessionPointcloud() const { return ArchiveRows(SAGEICP_SESSION, "SessionPointcloud"); }
+    // Recall (include/sageicp.h): the voxels of the session's map whose first point lies within `radius` of
+    // `center`, as a map of max_distance = radius that can be searched — what Relocalize takes when a place was
+    // recognised after the local map evicted it.  The returned map is filled on the device and is in block-pool order
+    // (a recall's destination is never in reference-order mode).
+    VoxelHashMap Recall(const Eigen::Vector3d &center, double radius) const {
+        sageicp_map *dst = sageicp_map_create(voxel_size_, radius, basic_points_per_voxel_, critical_points_per_voxel_,
+                                              basic_parts_labels_.data(), static_cast<int>(basic_parts_labels_.size()), Device());
+        if (!dst) throw std::runtime_error(std::string("sageicp_map_create: ") + sageicp_last_error());
+        int rc = sageicp_map_set_reference_order(dst, 0);      // (SAGEICP_MAP_REFERENCE_ORDER=1 would have switched it on)
+        if (rc == SAGEICP_OK) rc = sageicp_map_recall(map_, center.data(), radius, dst, nullptr);
+        if (rc != SAGEICP_OK) {
+            const std::string why = sageicp_last_error();
+            sageicp_map_destroy(dst);
+            throw std::runtime_error("sage_icp::VoxelHashMap::Recall: " + why);
+        }
+        return VoxelHashMap(*this, radius, dst);
+    }
     // HIP device ordinal for maps created by this process (one process per GPU); set it before
     // the first map is constructed, e.g. from LOCAL_RANK.
     static int &Device() {
@@ -149,6 +166,14 @@ struct VoxelHashMap {
     }
 
 private:
+    // a handle that already exists, with the parameters of `like` (Recall)
+    VoxelHashMap(const VoxelHashMap &like, double max_distance, sageicp_map *handle)
+        : voxel_size_(like.voxel_size_),
+          max_distance_(max_distance),
+          basic_points_per_voxel_(like.basic_points_per_voxel_),
+          critical_points_per_voxel_(like.critical_points_per_voxel_),
+          basic_parts_labels_(like.basic_parts_labels_),
+          map_(handle) {}
     // Eigen::Vector4d is four contiguous doubles, so a vector of them is the ABI's double[n][4]
     static const double *Data(const Vector4dVector &v) { return v.empty() ? nullptr : v.front().data(); }
     static double *Data(Vector4dVector &v) { return v.empty() ? nullptr : v.front().data(); }
