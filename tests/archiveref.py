@@ -156,6 +156,50 @@ def walk(seed=3):
     return steps
 
 
+# ---- a sheet beyond one stride of the row gathers ---------------------------------------------------------------------------
+# archive.hip's gathers and recall.hip's fill launch at most 2048 workgroups of 256 lanes, a lane per row, and stride
+# over what lies beyond.  116 x 116 voxels of 40 rows are 538,240 rows: 13,952 of them are written on a second trip.
+GATHER_STRIDE = 2048 * 256
+BIG_SIDE, BIG_COUNT, BIG_AGAIN = 116, 40, 300
+BIG_MAX_DISTANCE = 100.0                                            # holds the sheet from BIG_ORIGIN (its corners: 82 m)
+BIG_ORIGIN, BIG_AWAY = (58.0, 58.0, 0.5), (5000.0, 58.0, 0.5)
+
+
+def big_sheet(seed=17):
+    """(rows, again): BIG_SIDE^2 voxels of 1 m, each offered BIG_COUNT rows of label 71 (a critical one: all 40 are kept,
+    in the order offered) at multiples of 1/64, shuffled; and BIG_COUNT other rows for BIG_AGAIN of the voxels, spread
+    over the sheet, shuffled"""
+    rng = np.random.default_rng(seed)
+
+    def rows_of_voxels(ix, iy):
+        n = len(ix) * BIG_COUNT
+        p = np.empty((n, 4))
+        p[:, 0] = np.repeat(ix, BIG_COUNT) + rng.integers(4, 60, size=n) / 64.0
+        p[:, 1] = np.repeat(iy, BIG_COUNT) + rng.integers(4, 60, size=n) / 64.0
+        p[:, 2] = rng.integers(4, 60, size=n) / 64.0
+        p[:, 3] = 71.0
+        return p[rng.permutation(n)]
+
+    ix, iy = (a.reshape(-1) for a in np.meshgrid(np.arange(BIG_SIDE), np.arange(BIG_SIDE), indexing="ij"))
+    rows = rows_of_voxels(ix, iy)
+    pick = np.sort(rng.choice(BIG_SIDE * BIG_SIDE, size=BIG_AGAIN, replace=False))
+    return rows, rows_of_voxels(ix[pick], iy[pick])
+
+
+def big_sheet_steps():
+    """the sheet inserted and evicted whole by one empty update far away, then BIG_AGAIN of its voxels born again with
+    other rows and evicted again: a second generation, so LATEST is not the log"""
+    rows, again = big_sheet()
+    none = np.zeros((0, 4))
+    return [(rows, BIG_ORIGIN), (none, BIG_AWAY), (again, BIG_ORIGIN), (none, BIG_AWAY)]
+
+
+def by_voxel(rows, voxel_size=1.0):
+    """the rows in ascending voxel key, each voxel's rows in the order they had (a stable sort)"""
+    k = np.trunc(np.asarray(rows)[:, :3] / voxel_size).astype(np.int64)
+    return rows[np.lexsort((k[:, 2], k[:, 1], k[:, 0]))]
+
+
 IDENTITY_ROT = (0.0, 0.0, 0.0, 1.0)
 
 

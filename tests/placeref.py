@@ -7,6 +7,8 @@ libm that may differ; everything after them is plain fp64 (numpy ufuncs: no cont
         assertion that every kept row has exactly one s with f(s) and not f(s + 1); the cells by np.maximum.at
     match(db, desc, ...) -> list of dicts: three nested loops over entries, shifts and cells (the cells vectorised per
         shift), ranked with Python integers
+    scores(entries, desc, h_tol) -> ((agree, shift, n_entry), n_query) of every entry: the same rules with one numpy pass
+        over all entries per shift, for databases of thousands of entries; match(..., scores=) ranks them
     prior(pose, shift, S) -> (yaw, prior[7])
 """
 import functools
@@ -64,6 +66,27 @@ def score(qh, qc, eh, ec, h_tol):
     return best, shift, int((qh > 0).sum()), int((eh > 0).sum())
 
 
+def scores(entries, desc, h_tol):
+    """((agree, shift, n_entry), n_query): int64 arrays over all entries, shift the smallest of maximal agree.  One pass
+    over the entries per shift: an entry cell (r, s + k) agrees with the query cell (r, s) when both are occupied, the
+    classes are equal and the heights differ by at most h_tol"""
+    e = np.asarray(entries)
+    assert e.ndim == 4 and e.shape[1] == 2, "entries: (N, 2, R, S), or a sequence of (heights, classes)"
+    qh, qc = (np.asarray(a).astype(np.int16) for a in desc)
+    N, S = len(e), qh.shape[1]
+    assert e.shape[2:] == qh.shape == qc.shape
+    e = e.astype(np.int16)
+    e = np.concatenate([e, e], axis=3)                   # e[..., s + k] without a wrap
+    agree, shift = np.full(N, -1, dtype=np.int64), np.zeros(N, dtype=np.int64)
+    for k in range(S):
+        sh, sc = e[:, 0, :, k:k + S], e[:, 1, :, k:k + S]
+        a = ((qh > 0) & (sh > 0) & (qc == sc) & (np.abs(qh - sh) <= h_tol)).sum(axis=(1, 2), dtype=np.int64)
+        better = a > agree                               # (strictly: a later shift of equal agreement does not replace)
+        agree[better], shift[better] = a[better], k
+    n_entry = (e[:, 0, :, :S] > 0).sum(axis=(1, 2), dtype=np.int64)
+    return (agree, shift, n_entry), int((qh > 0).sum())
+
+
 def prior(pose, shift, S):
     w = 2.0 * math.pi / S
     yaw = shift * w if shift <= S // 2 else (shift - S) * w
@@ -75,8 +98,9 @@ def prior(pose, shift, S):
     return yaw, np.array(p)
 
 
-def match(entries, desc, top_k=1, h_tol=0, exclude_last=0, min_similarity=0.0, tags=None, poses=None):
-    """entries: a sequence of (heights, classes); desc: (heights, classes).  The matches as dicts, best first."""
+def match(entries, desc, top_k=1, h_tol=0, exclude_last=0, min_similarity=0.0, tags=None, poses=None, scores=None):
+    """entries: a sequence of (heights, classes); desc: (heights, classes).  The matches as dicts, best first.
+    scores: what scores(entries, desc, h_tol) returned, in place of the loop over score(); the ranking is the same code"""
     size = len(entries)
     if exclude_last >= size:
         return []
@@ -84,7 +108,10 @@ def match(entries, desc, top_k=1, h_tol=0, exclude_last=0, min_similarity=0.0, t
     S = np.asarray(qh).shape[1]
     recs = []
     for i in range(size - exclude_last):
-        agree, shift, nq, ne = score(qh, qc, entries[i][0], entries[i][1], h_tol)
+        if scores is not None:
+            (agree, shift, ne), nq = (int(a[i]) for a in scores[0]), int(scores[1])
+        else:
+            agree, shift, nq, ne = score(qh, qc, entries[i][0], entries[i][1], h_tol)
         m = max(nq, ne)
         recs.append(dict(index=i, agree=agree, shift=shift, n_query=nq, n_entry=ne, m=m))
 

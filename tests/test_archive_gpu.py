@@ -286,6 +286,49 @@ def test_257_keys_and_257_generations_of_one_key(gpu_sage):
     assert len(latest) == 257 + 2 and m.archive_info()["voxels"] == 514
 
 
+def test_latest_and_session_exports_beyond_one_stride_of_the_gather(gpu_sage):
+    """The gathers launch 2048 x 256 lanes, a lane per row, and stride over the rest: an export of 538,240 rows takes a
+    second trip for its last 13,952.  ALL is a plain copy of the log, so LATEST is built from it with numpy: the log without
+    the superseded records, in log order.  300 voxels have a second generation, so the selection is not the identity."""
+    sage = gpu_sage
+    rows, again = ar.big_sheet()
+    voxels = ar.BIG_SIDE * ar.BIG_SIDE
+    assert len(rows) == voxels * ar.BIG_COUNT == 538240 > ar.GATHER_STRIDE == 524288 and len(again) == 300 * 40
+    m = _map(sage, max_distance=ar.BIG_MAX_DISTANCE).set_archive(True)
+    for pts, origin in ar.big_sheet_steps():
+        ar.apply_step(m, "device", pts, origin)
+    info = m.archive_info()
+    assert m.resident() and m.num_voxels() == 0 and info["full"] == 0
+    assert info["device_rows"] == info["rows"] == len(rows) + len(again) and info["voxels"] == voxels + ar.BIG_AGAIN
+    log = m.ArchivedPointcloud("all")
+    rec = np.asarray(m.archive_voxels())
+    assert (rec["count"] == ar.BIG_COUNT).all() and np.array_equal(rec["first_row"], ar.BIG_COUNT * np.arange(len(rec)))
+    assert (rec["update"][:voxels] == 1).all() and (rec["update"][voxels:] == 3).all()
+    # the log itself (one update evicted 538,240 rows: the append's gather strides too): per voxel the rows offered, the
+    # first generation before the second
+    assert ar.by_voxel(log).tobytes() == ar.by_voxel(np.concatenate([rows, again])).tobytes()
+    key = (rec["x"].astype(np.int64) * ar.BIG_SIDE + rec["y"]) * 2 + rec["z"]
+    assert rec["z"].min() == rec["z"].max() == 0 and len(np.unique(key)) == voxels
+    kept = np.ones(len(rec), dtype=bool)
+    kept[:voxels] = ~np.isin(key[:voxels], key[voxels:])             # superseded: a later record has the key (nothing is live)
+    assert (~kept).sum() == ar.BIG_AGAIN and np.flatnonzero(~kept)[0] < voxels // 10
+    want = log[np.repeat(kept, rec["count"])]
+    got = m.ArchivedPointcloud("latest")
+    assert len(got) == len(want) == len(rows)
+    assert got.tobytes() == want.tobytes()
+    tail = len(got) - ar.GATHER_STRIDE
+    assert tail == 13952 and got[-tail:].tobytes() == want[-tail:].tobytes()         # what the second trip writes
+    assert want[-tail:].tobytes() != log[ar.GATHER_STRIDE:len(got)].tobytes()        # ... and not from the same log position
+    # per voxel, the rows offered last
+    born_again = np.isin(ar.by_voxel(rows)[:, :2].astype(np.int64) @ [ar.BIG_SIDE, 1], (key[voxels:] // 2))
+    final = np.concatenate([ar.by_voxel(rows)[~born_again], again])
+    assert len(final) == len(rows) and ar.by_voxel(got).tobytes() == ar.by_voxel(final).tobytes()
+    # SESSION: nothing is live, so it is LATEST; through the device sink the same bytes
+    assert m.Pointcloud().shape == (0, 4) and m.ArchivedPointcloud("session").tobytes() == want.tobytes()
+    assert m.ArchivedPointcloud("latest", device=True).cpu().numpy().tobytes() == want.tobytes()
+    assert m.ArchivedPointcloud("latest", first=ar.GATHER_STRIDE - 5).tobytes() == want[ar.GATHER_STRIDE - 5:].tobytes()
+
+
 # ---- sinks ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("which", ["all", "latest", "session"])
 def test_sinks_of_an_export(gpu_sage, which):

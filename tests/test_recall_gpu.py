@@ -334,6 +334,37 @@ def test_the_same_recall_twice_gives_the_same_bytes(gpu_sage):
     assert (a.size(), a.num_voxels(), a.point_slots(), a.table_stats()) == (b.size(), b.num_voxels(), b.point_slots(), b.table_stats())
 
 
+# ---- 5b. parts beyond one stride of the fill ---------------------------------------------------------------------------
+# k_rc_fill launches at most 2048 x 256 lanes per part, a lane per row, and strides over the rest (as archive.hip's
+# gathers do).  The sheet of archiveref.big_sheet holds 538,240 rows: 13,952 of a part are written on a second trip.
+def test_an_archive_part_beyond_one_stride_of_the_fill(gpu_sage):
+    sage = gpu_sage
+    src = _map(sage, max_distance=ar.BIG_MAX_DISTANCE).set_archive(True)
+    for pts, origin in ar.big_sheet_steps():                    # archived whole, 300 voxels in a second generation
+        ar.apply_step(src, "device", pts, origin)
+    assert src.num_voxels() == 0 and src.archive_info()["voxels"] == ar.BIG_SIDE ** 2 + ar.BIG_AGAIN
+    dst, _, info = _recall_and_check(sage, src, ar.BIG_ORIGIN, math.inf, what="archive part")
+    assert info["archive_rows"] == ar.BIG_SIDE ** 2 * ar.BIG_COUNT == 538240 and info["archive_rows"] > 524288 == ar.GATHER_STRIDE
+    assert info["archive_voxels"] == ar.BIG_SIDE ** 2 and info["map_rows"] == 0
+    # per voxel the rows offered last: the born-again voxels hold their second generation
+    rows, again = ar.big_sheet()
+    cloud = dst.Pointcloud()
+    assert ar.by_voxel(cloud[-len(again):]).tobytes() == ar.by_voxel(again).tobytes()
+
+
+def test_a_map_part_beyond_one_stride_of_the_fill(gpu_sage):
+    sage = gpu_sage
+    rows, _ = ar.big_sheet()
+    token = np.array([[3000.5, 58.5, 0.5, 71.0], [3000.25, 58.5, 0.5, 71.0]])          # born out of range: archived at once
+    src = _map(sage, max_distance=ar.BIG_MAX_DISTANCE).set_archive(True)
+    ar.apply_step(src, "device", np.concatenate([token, rows]), ar.BIG_ORIGIN)
+    assert src.resident() and src.num_voxels() == ar.BIG_SIDE ** 2 and src.archive_info()["rows"] == len(token)
+    dst, _, info = _recall_and_check(sage, src, ar.BIG_ORIGIN, math.inf, what="map part")
+    assert info["map_rows"] == len(rows) == 538240 and info["map_rows"] > 524288 == ar.GATHER_STRIDE
+    assert info["archive_rows"] == len(token) and info["archive_voxels"] == 1
+    assert ar.by_voxel(dst.Pointcloud()[len(token):]).tobytes() == ar.by_voxel(rows).tobytes()
+
+
 # ---- 6. the loop closed ------------------------------------------------------------------------------------------------
 # The street scene of tests/test_place_gpu.py driven through a map that forgets: 17 scans of 8000 points at their poses,
 # 8 m apart, into a map of 1 m voxels and max_distance LOOP_MAX_DISTANCE with the archive on.  Place 9 lies 56 m behind
