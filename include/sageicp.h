@@ -73,7 +73,9 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * sageicp_relocalize_info, sageicp_relocalize_candidates, sageicp_relocalize / _device; then the archive of a map —
  * sageicp_archive_info, sageicp_archive_voxel, SAGEICP_ARCHIVE_* / SAGEICP_SESSION, sageicp_map_set_archive,
  * sageicp_map_archive_info / _clear / _voxels / _rows / _rows_device / _msg / _msg_device, sageicp_pipeline_set_archive;
- * then recall — sageicp_recall_info, sageicp_map_recall, sageicp_pipeline_recall
+ * then recall — sageicp_recall_info, sageicp_map_recall, sageicp_pipeline_recall; then loop closure —
+ * sageicp_closure_info, sageicp_closure_corrections, sageicp_map_session_stays, sageicp_map_session_corrected / _device,
+ * sageicp_pipeline_closure, sageicp_pipeline_session_corrected / _device
  * (additions only: no existing struct or entry changed). */
 #define SAGEICP_ABI_VERSION 4
 
@@ -960,6 +962,75 @@ int sageicp_map_recall(const sageicp_map *src, const double center[3], double ra
                        sageicp_recall_info *info /* may be NULL */);
 int sageicp_pipeline_recall(const sageicp_pipeline *p, const double center[3], double radius, sageicp_map *dst,
                             sageicp_recall_info *info /* may be NULL */);   /* its local map's */
+
+/* ---- loop closure: a closure spread over the trajectory, the session's map re-posed -------------------
+ * Additions only; the ABI version stays; off unless called: no other entry does anything it did not do before, and a
+ * pipeline's own state (its poses, its local map) is never touched — it keeps running in its odometry frame.
+ *
+ * Corrections (host, fp64, no device).  poses: n rows T_world_k, (qx, qy, qz, qw, tx, ty, tz).  closed: where pose j really
+ * is, in pose i's frame of the world — what sageicp_relocalize returns against a map recalled around pose i.
+ *     delta = closed * poses[j]^-1          (se3_mul, se3_inv; REP-105's map->odom transform after the closure)
+ *     c     = t_j, the translation of poses[j]: the pivot
+ *     alpha_k = 0 for k <= i, 1 for k >= j, between them the share of path length
+ *               sum_{m=i+1..k} |t_m - t_{m-1}| / sum_{m=i+1..j} |t_m - t_{m-1}|  ((k - i) / (j - i) if the whole path is 0)
+ *     C_k   = Tr(c) * exp(alpha_k * log(Tr(-c) * delta * Tr(c))) * Tr(-c)          (se3_log, se3_exp)
+ *     poses_out[k] = C_k * poses[k]
+ * Interpolating about t_j makes the result move with the trajectory when the trajectory is translated.  The two ends do
+ * not pass through log or exp: for k <= i, C_k is (0,0,0,1,0,0,0) and poses_out[k] is poses[k], bit for bit; for k >= j,
+ * C_k is delta's own bytes.  info: delta, its rotation angle (rad), shift = how far pose j moves (|closed.t - t_j|), path =
+ * the path length from pose i to pose j.  SAGEICP_ERR_INVALID, nothing written: a null pointer that is not optional;
+ * n == 0, i >= j, j >= n; a non-finite input; a quaternion of norm 0; a delta that turns by more than pi - 1e-6 (that is
+ * not drift, and the logarithm is not to be trusted there).  Several closures are applied one after another
+ * (poses_out of one is poses of the next, and the corrections compose: C'_k * C_k); a pose graph with many simultaneous
+ * constraints is out of scope.
+ *
+ * Stays (device).  The session's voxels of `which` are enumerated as recall enumerates them: SAGEICP_ARCHIVE_ALL every
+ * record in log order; SAGEICP_ARCHIVE_LATEST the LATEST records in log order; SAGEICP_SESSION those, then the live
+ * voxels in sageicp_map_pointcloud's order.  positions: n >= 1 rows (x, y, z), the sensor position of the call with serial
+ * s (sageicp_archive_voxel.update).  A voxel is evicted by its FIRST row p alone, so between its insertion and its
+ * eviction no position was far from p — far as RemovePointsFarFromLocation decides it, (p - position).squaredNorm() >
+ * max_distance * max_distance.  With hi = min(update, n) - 1 for a record and n - 1 for a live voxel, walk k = hi, hi - 1,
+ * ... while k >= 0 and positions[k] is not far from p: stay = the walked k of smallest squared distance, the larger k on
+ * a tie; max(hi, 0) if nothing was walked.  This is not the nearest pose over all poses: on an out-and-back drive that is
+ * often one of the old pass, whose correction is the wrong one.  One uint32 per voxel of the selection, in selection
+ * order; `first` skips voxels, *n_out = the voxels of the selection, [first, first + min(cap, *n_out - first)) written.
+ *
+ * The re-posed export (device).  The rows of the selection, in the order of sageicp_map_archive_rows(which), each moved
+ * by corrections[stay of its voxel] — the point action of sageicp_transform_points, bit for bit; the label untouched —
+ * and then converted to the caller's layout; first, cap, *n_out, stream and lifetime rules, refusals, and "leaves a
+ * resident map resident" as sageicp_map_archive_rows[_device].  With every correction the identity the bytes are those
+ * of the plain export (a coordinate that is -0.0 leaves as +0.0, as it does through sageicp_transform_points).
+ * SAGEICP_ERR_INVALID: a null argument, a `which` that is none of the three, n == 0 or beyond 2^32 - 1, a non-finite
+ * position or correction.  SAGEICP_ERR_NO_DEVICE without a device; SAGEICP_ERR_CAPACITY beyond 2^32 - 2 records or rows.
+ *
+ * The pipeline's entries take the poses and the positions from the pipeline (j: its last pose; n must be its number of
+ * poses) and return SAGEICP_ERR_INVALID unless the archive's `updates` equals sageicp_pipeline_num_poses — the archive on
+ * from the first frame and nothing interrupting the count: only then is serial s pose s. */
+typedef struct sageicp_closure_info {
+    double delta[7];
+    double angle;
+    double shift;
+    double path;
+    uint64_t i, j;
+} sageicp_closure_info;
+int sageicp_closure_corrections(const double *poses /* n x 7 */, uint64_t n, uint64_t i, uint64_t j, const double closed[7],
+                                double *corrections_out /* n x 7 */, double *poses_out /* n x 7, may be NULL */,
+                                sageicp_closure_info *info /* may be NULL */);
+int sageicp_map_session_stays(const sageicp_map *m, int which, uint64_t first, const double *positions /* n x 3 */, uint64_t n,
+                              uint32_t *stay_out, uint64_t cap, uint64_t *n_out);
+int sageicp_map_session_corrected(const sageicp_map *m, int which, uint64_t first, const double *positions /* n x 3 */,
+                                  const double *corrections /* n x 7 */, uint64_t n, double *out_xyzl, uint64_t cap,
+                                  uint64_t *n_out);
+int sageicp_map_session_corrected_device(const sageicp_map *m, int which, uint64_t first, const double *positions,
+                                         const double *corrections, uint64_t n, const sageicp_device_points *dst,
+                                         void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
+int sageicp_pipeline_closure(const sageicp_pipeline *p, uint64_t i, const double closed[7], double *corrections_out,
+                             double *poses_out /* may be NULL */, sageicp_closure_info *info /* may be NULL */);
+int sageicp_pipeline_session_corrected(const sageicp_pipeline *p, int which, uint64_t first, const double *corrections,
+                                       uint64_t n, double *out_xyzl, uint64_t cap, uint64_t *n_out);
+int sageicp_pipeline_session_corrected_device(const sageicp_pipeline *p, int which, uint64_t first, const double *corrections,
+                                              uint64_t n, const sageicp_device_points *dst,
+                                              void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
 
 /* ---- place recognition: the semantic scan context of key frames (place.hip) -------------------------------------------
  * Additions only; the ABI version stays.  A descriptor says where the sensor stood: a polar grid of R rings by S sectors

@@ -241,6 +241,15 @@ ARCHIVE_WHICH = {"all": ARCHIVE_ALL, "latest": ARCHIVE_LATEST, "session": SESSIO
 ARCHIVE_VOXEL_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("z", "<i4"), ("count", "<u4"), ("first_row", "<u8"), ("update", "<u8")])
 
 
+class ClosureInfo(C.Structure):
+    """sageicp_closure_info"""
+    _fields_ = [("delta", C.c_double * 7), ("angle", C.c_double), ("shift", C.c_double), ("path", C.c_double),
+                ("i", C.c_uint64), ("j", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(delta=np.array(self.delta[:]), angle=self.angle, shift=self.shift, path=self.path, i=int(self.i), j=int(self.j))
+
+
 class OccupancyParams(C.Structure):
     """sageicp_occupancy_params: the bird's-eye grid of key-frame selection (bounds of x, y, z; H rows, W columns)"""
     _fields_ = [("bounds", (C.c_double * 2) * 3), ("occ_h", C.c_int32), ("occ_w", C.c_int32), ("overlap_th", C.c_double)]
@@ -509,6 +518,15 @@ _SIGNATURES = [
     ("sageicp_pipeline_set_archive", C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
     ("sageicp_map_recall", C.c_int, [C.c_void_p, _dp, C.c_double, C.c_void_p, C.POINTER(RecallInfo)]),
     ("sageicp_pipeline_recall", C.c_int, [C.c_void_p, _dp, C.c_double, C.c_void_p, C.POINTER(RecallInfo)]),
+    ("sageicp_closure_corrections", C.c_int, [_dp, C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, _dp, C.POINTER(ClosureInfo)]),
+    ("sageicp_map_session_stays", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _dp, C.c_uint64, C.POINTER(C.c_uint32), C.c_uint64, _u64p]),
+    ("sageicp_map_session_corrected", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _dp, _dp, C.c_uint64, _dp, C.c_uint64, _u64p]),
+    ("sageicp_map_session_corrected_device", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _dp, _dp, C.c_uint64,
+                                                       C.POINTER(DevicePoints), C.c_void_p, _u64p]),
+    ("sageicp_pipeline_closure", C.c_int, [C.c_void_p, C.c_uint64, _dp, _dp, _dp, C.POINTER(ClosureInfo)]),
+    ("sageicp_pipeline_session_corrected", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _dp, C.c_uint64, _dp, C.c_uint64, _u64p]),
+    ("sageicp_pipeline_session_corrected_device", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _dp, C.c_uint64,
+                                                            C.POINTER(DevicePoints), C.c_void_p, _u64p]),
     ("sageicp_place_tables", C.c_int, [C.POINTER(PlaceParams), _dp, _dp]),
     ("sageicp_place_describe", C.c_int, [_dp, C.c_uint64, C.POINTER(PlaceParams), C.c_void_p, C.c_int]),
     ("sageicp_place_describe_device", C.c_int, [C.POINTER(DeviceFrame), C.POINTER(PlaceParams), C.c_void_p, C.c_void_p]),
@@ -1174,6 +1192,34 @@ class VoxelHashMap:
         with this map's parameters on its device, max_distance = radius.  Returns (into, info dict)."""
         return _recall(lib().sageicp_map_recall, self._h, self, center, radius, into)
 
+    # ---- loop closure: the pose every voxel belongs to, the session's map re-posed (DESIGN.md D18) ----
+    def SessionStays(self, positions, which="session", first=0):
+        """One uint32 per voxel of the selection, in its order (the records of "all" / "latest", then for "session" the
+        live voxels in Pointcloud() order): the index into `positions` (n, 3) — the sensor position of the call with
+        serial s — of the pose the voxel is tied to (sageicp_map_session_stays)."""
+        w, first = _archive_which(which), int(first)
+        pos = _positions(positions)
+        # room for an upper bound that costs no device work (every record, and for "session" every live voxel): the
+        # selection is then computed once, by the call that writes, and the result trimmed to what it reported
+        room = max(0, self.archive_info()["voxels"] + (self.num_voxels() if w == SESSION else 0) - first)
+        out = np.zeros(room, dtype=np.uint32)
+        n = C.c_uint64(0)
+        _check(lib().sageicp_map_session_stays(self._h, w, first, _p(pos), pos.shape[0],
+                                               out.ctypes.data_as(C.POINTER(C.c_uint32)) if room else None, room, C.byref(n)))
+        return out[:min(max(0, n.value - first), room)]
+
+    def CorrectedPointcloud(self, which="session", positions=None, corrections=None, first=0, device=False, dtype=None, out=None,
+                            labels_out=None):
+        """ArchivedPointcloud(which)'s rows, each moved by corrections[stay of its voxel] (closure_corrections; the stays
+        as SessionStays takes them against `positions`), label untouched (sageicp_map_session_corrected[_device]).  The
+        other keywords as Pointcloud()."""
+        pos, corr = _positions(positions), _corrections(corrections, positions)
+        w, first, n = _archive_which(which), int(first), pos.shape[0]
+        return _corrected_rows(lambda: self._h, self.device, w, first, device, dtype, out, labels_out,
+                               lambda a, cap, k: lib().sageicp_map_session_corrected(self._h, w, first, _p(pos), _p(corr), n, a, cap, k),
+                               lambda d, st, k: lib().sageicp_map_session_corrected_device(self._h, w, first, _p(pos), _p(corr), n,
+                                                                                           d, st, k))
+
     def resident(self):
         """True while the HBM copy of the map is the authority (after a device-side update)"""
         return bool(lib().sageicp_map_resident(self._h))
@@ -1820,6 +1866,31 @@ class SageICP:
         return _archive_rows(lambda: lib().sageicp_pipeline_local_map(self._h), self.config.device, which, first, device, dtype,
                              out, labels_out)
 
+    def Closure(self, i, closed):
+        """A loop closure between pose i and the last pose: `closed` is where the last pose really is in pose i's frame
+        of the world (what Relocalize returns against a map recalled around pose i).  Returns (corrections (n, 7),
+        corrected poses (n, 7), info dict) — info["delta"] is the map->odom transform (sageicp_pipeline_closure).  The
+        pipeline itself is not touched.  Needs the archive on from the first frame."""
+        n = int(lib().sageicp_pipeline_num_poses(self._h))
+        corr, poses, info = np.empty((n, 7)), np.empty((n, 7)), ClosureInfo()
+        c = np.ascontiguousarray(closed, dtype=np.float64).reshape(-1)
+        if c.size != 7:
+            raise ValueError("Closure takes closed[7]")
+        _check(lib().sageicp_pipeline_closure(self._h, int(i), _p(c), _p(corr), _p(poses), C.byref(info)))
+        return corr, poses, info.as_dict()
+
+    def CorrectedSessionMap(self, corrections, which="session", first=0, device=False, dtype=None, out=None, labels_out=None):
+        """SessionMap(which)'s rows re-posed by `corrections` (n, 7), one per pose of the pipeline, as Closure returns
+        them (sageicp_pipeline_session_corrected[_device]; VoxelHashMap.CorrectedPointcloud)"""
+        corr = np.ascontiguousarray(corrections, dtype=np.float64)
+        if corr.ndim != 2 or corr.shape[1] != 7:
+            raise ValueError("corrections is (n, 7)")
+        w, first, n = _archive_which(which), int(first), corr.shape[0]
+        handle = lambda: lib().sageicp_pipeline_local_map(self._h)
+        return _corrected_rows(handle, self.config.device, w, first, device, dtype, out, labels_out,
+                               lambda a, cap, k: lib().sageicp_pipeline_session_corrected(self._h, w, first, _p(corr), n, a, cap, k),
+                               lambda d, st, k: lib().sageicp_pipeline_session_corrected_device(self._h, w, first, _p(corr), n, d, st, k))
+
     def SessionMapMsg(self, colors, which="session", first=0, device=False, out=None):
         return _archive_msg(lambda: lib().sageicp_pipeline_local_map(self._h), self.config.device, colors, which, first, device,
                             out)
@@ -1894,6 +1965,50 @@ def _archive_rows(handle, device_index, which, first, device, dtype, out, labels
     return _rows_out(device_index, lambda: _archive_room(handle, w, first), host_rows,
                      lambda d, s, n: lib().sageicp_map_archive_rows_device(handle(), w, first, d, s, n),
                      device, dtype, out, labels_out, first=first)
+
+
+def _p(a):
+    """the address of a C-contiguous float64 array (the caller keeps it alive)"""
+    return a.ctypes.data_as(_dp)
+
+
+def _positions(positions):
+    pos = np.ascontiguousarray(positions, dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != 3 or pos.shape[0] == 0:
+        raise ValueError("positions is (n, 3), n >= 1")
+    return pos
+
+
+def _corrections(corrections, positions):
+    corr = np.ascontiguousarray(corrections, dtype=np.float64)
+    if corr.ndim != 2 or corr.shape[1] != 7 or corr.shape[0] != len(positions):
+        raise ValueError("corrections is (n, 7), one per position")
+    return corr
+
+
+def _corrected_rows(handle, device_index, w, first, device, dtype, out, labels_out, host_call, device_call):
+    """the re-posed export of a selection: host_call(rows, cap, n_out) / device_call(DevicePoints, stream, n_out)"""
+    def host_rows(n):
+        a = np.empty((n, 4))
+        k = C.c_uint64(0)
+        _check(host_call(a.ctypes.data_as(_dp) if n else None, n, C.byref(k)))
+        return a[:min(max(0, k.value - first), n)]
+
+    return _rows_out(device_index, lambda: _archive_room(handle, w, first), host_rows, device_call, device, dtype, out, labels_out,
+                     first=first)
+
+
+def closure_corrections(poses, i, j, closed, return_info=False):
+    """The corrections C_k (n, 7) that spread the closure "pose j really is at `closed`, in pose i's frame of the world"
+    over poses i..j by path length, and the corrected poses C_k * poses[k] (sageicp_closure_corrections).
+    Host arithmetic, no device.  return_info=True adds the info dict (delta, angle, shift, path, i, j)."""
+    P = np.ascontiguousarray(poses, dtype=np.float64)
+    c = np.ascontiguousarray(closed, dtype=np.float64).reshape(-1)
+    if P.ndim != 2 or P.shape[1] != 7 or c.size != 7:
+        raise ValueError("closure_corrections takes poses (n, 7) and closed[7]")
+    corr, out, info = np.empty_like(P), np.empty_like(P), ClosureInfo()
+    _check(lib().sageicp_closure_corrections(_p(P), P.shape[0], int(i), int(j), _p(c), _p(corr), _p(out), C.byref(info)))
+    return (corr, out, info.as_dict()) if return_info else (corr, out)
 
 
 def _archive_msg(handle, device_index, colors, which, first, device, out):

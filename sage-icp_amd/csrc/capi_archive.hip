@@ -106,24 +106,6 @@ void host_remove_far(sageicp_map &m, const double origin[3]) {
 // ---- exports -----------------------------------------------------------------------------------------------------------
 namespace {
 
-// what LATEST works in: for one call (nothing is cached between calls)
-struct LatestBuffers {
-    DevBuf<unsigned long long> keys, keys_alt;
-    DevBuf<uint32_t> idx, idx_alt, flag, sel, counts, offsets, n_sel;
-    DevBuf<unsigned char> temp;
-    LatestScratch view() const {
-        return LatestScratch{keys.data(), keys_alt.data(), idx.data(), idx_alt.data(), flag.data(), sel.data(), counts.data(),
-                             offsets.data(), n_sel.data(), temp.data(), temp.capacity()};
-    }
-    int reserve(size_t nv) {
-        HIPCHK(keys.reserve(nv)); HIPCHK(keys_alt.reserve(nv));
-        HIPCHK(idx.reserve(nv)); HIPCHK(idx_alt.reserve(nv)); HIPCHK(flag.reserve(nv)); HIPCHK(sel.reserve(nv));
-        HIPCHK(counts.reserve(nv + 1)); HIPCHK(offsets.reserve(nv + 1)); HIPCHK(n_sel.reserve(1));
-        HIPCHK(temp.reserve(archive_latest_temp_bytes(nv)));
-        return SAGEICP_OK;
-    }
-};
-
 // ALL into host rows: the device part copied down, the pending tail copied over; no device while no row is in HBM
 int all_to_host(sageicp_map &m, uint64_t first, double *out, uint64_t cap, uint64_t *n_out) {
     const MapArchive &a = m.arc;

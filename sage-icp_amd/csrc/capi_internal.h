@@ -320,6 +320,7 @@ using namespace sageicp;
 #include "caller_mem.h"
 #include "map_device.h"
 #include "archive.h"
+#include "recall.h"
 #include "outputs.h"
 
 // ---- opaque handles -----------------------------------------------------------------------
@@ -398,6 +399,7 @@ struct sageicp_comm {
 // capi_relocalize.hip: the candidate grid, the chunked batch score of candidate poses and Relocalize, on that path.
 // capi_run.hip: the ICP loop (plan_loop, run_icp and its attempts), the RCCL binding and the single-process multi-GPU
 // mode.  capi_recall.hip: recall (recall.h) — a place of a session's map into a second handle, on the device.
+// capi_closure.hip: loop closure (closure.h) — the corrections of a trajectory, the stays, the session's map re-posed.
 namespace sageicp_impl {
 struct Rccl {
     void *h = nullptr;
@@ -430,6 +432,37 @@ sageicp_place_db *place_db_new(const sageicp_place_params &p, int device);
 void place_db_clear(sageicp_place_db &db);
 int place_db_step(sageicp_place_db &db, const Point4 *d_rows, uint64_t n, const sageicp_place_query &q, uint64_t tag,
                   const double pose[7], hipStream_t s, sageicp_place_match *out, uint32_t *n_out);
+// capi_recall.hip: a session's map as two RecallParts (recall.h) — the records of a handle's archive in log order, its live
+// voxels in Pointcloud() order — and what they point into, for one call (nothing is cached between calls): what recall
+// selects from and the closure entries (capi_closure.hip) enumerate
+struct LatestBuffers {               // what archive_latest works in
+    DevBuf<unsigned long long> keys, keys_alt;
+    DevBuf<uint32_t> idx, idx_alt, flag, sel, counts, offsets, n_sel;
+    DevBuf<unsigned char> temp;
+    LatestScratch view() const {
+        return LatestScratch{keys.data(), keys_alt.data(), idx.data(), idx_alt.data(), flag.data(), sel.data(), counts.data(),
+                             offsets.data(), n_sel.data(), temp.data(), temp.capacity()};
+    }
+    int reserve(size_t nv) {
+        HIPCHK(keys.reserve(nv)); HIPCHK(keys_alt.reserve(nv));
+        HIPCHK(idx.reserve(nv)); HIPCHK(idx_alt.reserve(nv)); HIPCHK(flag.reserve(nv)); HIPCHK(sel.reserve(nv));
+        HIPCHK(counts.reserve(nv + 1)); HIPCHK(offsets.reserve(nv + 1)); HIPCHK(n_sel.reserve(1));
+        HIPCHK(temp.reserve(archive_latest_temp_bytes(nv)));
+        return SAGEICP_OK;
+    }
+};
+struct SessionParts {
+    LatestBuffers lb;
+    RecallPart part[2]{};            // the records, the live voxels (scratch pointers: the user's)
+    DevBuf<Slot> d_cand;             // the live voxels of a host-authoritative source
+    DevBuf<uint32_t> d_list;         // the bucket order of a resident source in reference-order mode
+    std::vector<Slot> h_cand;        // (pageable: they live until the stream has been waited for)
+    std::vector<uint32_t> h_list;
+};
+// on s, the map's stream; a pending host tail of the archive is moved to the device first.  latest_only: the LATEST
+// verdicts decide (the mirror refreshed for them, as before any search); otherwise every record is a candidate
+int session_archive_part(sageicp_map &src, hipStream_t s, bool latest_only, SessionParts &sp);
+int session_live_part(sageicp_map &src, hipStream_t s, SessionParts &sp);   // (after session_archive_part(.., true, ..): it reads the mirror)
 // capi_archive.hip: RemovePointsFarFromLocation on the host copy of one handle, the evicted voxels into its archive while on
 void host_remove_far(sageicp_map &m, const double origin[3]);
 // capi_run.hip

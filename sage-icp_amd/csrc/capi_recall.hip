@@ -5,25 +5,76 @@
 #include "recall.h"
 
 namespace sageicp_impl {
-namespace {
 
-// what archive_latest works in (for one call: nothing is cached between calls)
-struct LatestBuffers {
-    DevBuf<unsigned long long> keys, keys_alt;
-    DevBuf<uint32_t> idx, idx_alt, flag, sel, counts, offsets, n_sel;
-    DevBuf<unsigned char> temp;
-    LatestScratch view() const {
-        return LatestScratch{keys.data(), keys_alt.data(), idx.data(), idx_alt.data(), flag.data(), sel.data(), counts.data(),
-                             offsets.data(), n_sel.data(), temp.data(), temp.capacity()};
-    }
-    int reserve(size_t nv) {
-        HIPCHK(keys.reserve(nv)); HIPCHK(keys_alt.reserve(nv));
-        HIPCHK(idx.reserve(nv)); HIPCHK(idx_alt.reserve(nv)); HIPCHK(flag.reserve(nv)); HIPCHK(sel.reserve(nv));
-        HIPCHK(counts.reserve(nv + 1)); HIPCHK(offsets.reserve(nv + 1)); HIPCHK(n_sel.reserve(1));
-        HIPCHK(temp.reserve(archive_latest_temp_bytes(nv)));
+// ---- the two parts of a session's map (capi_internal.h: SessionParts) --------------------------------------------------
+// the records of src's archive: the whole log on the device, the LATEST verdicts (latest_only == false: every record kept)
+int session_archive_part(sageicp_map &src, hipStream_t s, bool latest_only, SessionParts &sp) {
+    MapArchive &a = src.arc;
+    if (int rc = a.flush_pending(s)) return rc;
+    if (a.dev_vox >= 0xFFFFFFFFull) return fail(SAGEICP_ERR_CAPACITY, "recall: more than 2^32 - 2 records");
+    // the slot table and the points in HBM: the authority's, or the mirror refreshed as before any search
+    if (latest_only)
+        if (int rc = refresh_mirror(src)) return rc;
+    RecallPart &p = sp.part[0];
+    p.n_cand = static_cast<uint32_t>(a.dev_vox);
+    if (!p.n_cand) return SAGEICP_OK;
+    p.rows = a.d_rows.data();
+    p.vox = a.d_vox.data();
+    if (!latest_only) {              // (any non-zero word keeps a record)
+        HIPCHK(sp.lb.flag.reserve(a.dev_vox));
+        HIPCHK(hipMemsetAsync(sp.lb.flag.data(), 0xFF, a.dev_vox * sizeof(uint32_t), s));
+        p.latest = sp.lb.flag.data();
         return SAGEICP_OK;
     }
-};
+    if (int rc = sp.lb.reserve(a.dev_vox)) return rc;
+    const LatestScratch ls = sp.lb.view();
+    const MapDevice &d = src.dev;
+    HIPCHK(archive_latest(a.d_vox.data(), p.n_cand, d.d_table.data(), static_cast<uint32_t>(d.d_table.capacity() - 1), ls, s));
+    p.latest = ls.flag;
+    return SAGEICP_OK;
+}
+
+// src's live voxels in Pointcloud() order
+int session_live_part(sageicp_map &m, hipStream_t s, SessionParts &sp) {
+    const HostMap &h = m.host;
+    RecallPart &p = sp.part[1];
+    p.rows = m.dev.d_pts.data();
+    if (m.resident()) {
+        p.table = m.dev.d_table.data();
+        p.slot_of = m.dev.d_slot_of.data();
+        p.n_cand = m.dev.ctr.blocks_hi;
+        if (h.track_order) {         // the bucket order of the host's array (VoxelHashMap.cpp:132-142)
+            sp.h_list.reserve(h.order.size());
+            h.order.for_each([&](uint32_t b) { sp.h_list.push_back(b); });
+            p.n_cand = static_cast<uint32_t>(sp.h_list.size());
+            if (p.n_cand) {
+                HIPCHK(sp.d_list.reserve(p.n_cand));
+                HIPCHK(hipMemcpyAsync(sp.d_list.data(), sp.h_list.data(), p.n_cand * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+                p.list = sp.d_list.data();
+            }
+        }
+        return SAGEICP_OK;
+    }
+    // the host copy is the map and HBM mirrors its points: the voxels' slot words as the host lists them
+    auto emit = [&](uint32_t b) {
+        sp.h_cand.push_back(Slot{h.keys[3 * b], h.keys[3 * b + 1], h.keys[3 * b + 2],
+                                 (region_unit(h.regions[b]) << 8) | static_cast<uint32_t>(h.cnt[b])});
+    };
+    sp.h_cand.reserve(h.num_voxels);
+    if (h.track_order) h.order.for_each(emit);
+    else
+        for (uint32_t b = 0; b < h.blocks_hi; ++b)
+            if (h.cnt[b]) emit(b);
+    p.n_cand = static_cast<uint32_t>(sp.h_cand.size());
+    if (p.n_cand) {
+        HIPCHK(sp.d_cand.reserve(p.n_cand));
+        HIPCHK(hipMemcpyAsync(sp.d_cand.data(), sp.h_cand.data(), p.n_cand * sizeof(Slot), hipMemcpyHostToDevice, s));
+        p.cand = sp.d_cand.data();
+    }
+    return SAGEICP_OK;
+}
+
+namespace {
 
 // the scratch of one part's selection
 struct PartBuffers {
@@ -51,92 +102,26 @@ struct RecallJob {
     const double *center;
     double radius;
     hipStream_t s;               // src's: its archive and its HBM copy are used on it
-    LatestBuffers lb;
+    SessionParts sp;             // the records and the live voxels of src
     PartBuffers pb[2];
-    RecallPart part[2]{};
-    DevBuf<Slot> d_cand;         // the live voxels of a host-authoritative source
-    DevBuf<uint32_t> d_list;     // the bucket order of a resident source in reference-order mode
-    std::vector<Slot> h_cand;    // (pageable: they live until the wait)
-    std::vector<uint32_t> h_list;
     DevBuf<RecallTotals> d_totals;
     DevBuf<unsigned char> temp;
     Totals t{};
 };
 
-// the records of src's archive: the whole log on the device, the LATEST verdicts
-int archive_part(RecallJob &j) {
-    MapArchive &a = j.src.arc;
-    if (int rc = a.flush_pending(j.s)) return rc;
-    if (a.dev_vox >= 0xFFFFFFFFull) return fail(SAGEICP_ERR_CAPACITY, "recall: more than 2^32 - 2 records");
-    // the slot table and the points in HBM: the authority's, or the mirror refreshed as before any search
-    if (int rc = refresh_mirror(j.src)) return rc;
-    RecallPart &p = j.part[0];
-    p.n_cand = static_cast<uint32_t>(a.dev_vox);
-    if (!p.n_cand) return SAGEICP_OK;
-    if (int rc = j.lb.reserve(a.dev_vox)) return rc;
-    const LatestScratch ls = j.lb.view();
-    const MapDevice &d = j.src.dev;
-    HIPCHK(archive_latest(a.d_vox.data(), p.n_cand, d.d_table.data(), static_cast<uint32_t>(d.d_table.capacity() - 1), ls, j.s));
-    p.rows = a.d_rows.data();
-    p.vox = a.d_vox.data();
-    p.latest = ls.flag;
-    return SAGEICP_OK;
-}
-
-// src's live voxels in Pointcloud() order
-int live_part(RecallJob &j) {
-    sageicp_map &m = j.src;
-    const HostMap &h = m.host;
-    RecallPart &p = j.part[1];
-    p.rows = m.dev.d_pts.data();
-    if (m.resident()) {
-        p.table = m.dev.d_table.data();
-        p.slot_of = m.dev.d_slot_of.data();
-        p.n_cand = m.dev.ctr.blocks_hi;
-        if (h.track_order) {         // the bucket order of the host's array (VoxelHashMap.cpp:132-142)
-            j.h_list.reserve(h.order.size());
-            h.order.for_each([&](uint32_t b) { j.h_list.push_back(b); });
-            p.n_cand = static_cast<uint32_t>(j.h_list.size());
-            if (p.n_cand) {
-                HIPCHK(j.d_list.reserve(p.n_cand));
-                HIPCHK(hipMemcpyAsync(j.d_list.data(), j.h_list.data(), p.n_cand * sizeof(uint32_t), hipMemcpyHostToDevice, j.s));
-                p.list = j.d_list.data();
-            }
-        }
-        return SAGEICP_OK;
-    }
-    // the host copy is the map and HBM mirrors its points: the voxels' slot words as the host lists them
-    auto emit = [&](uint32_t b) {
-        j.h_cand.push_back(Slot{h.keys[3 * b], h.keys[3 * b + 1], h.keys[3 * b + 2],
-                                (region_unit(h.regions[b]) << 8) | static_cast<uint32_t>(h.cnt[b])});
-    };
-    j.h_cand.reserve(h.num_voxels);
-    if (h.track_order) h.order.for_each(emit);
-    else
-        for (uint32_t b = 0; b < h.blocks_hi; ++b)
-            if (h.cnt[b]) emit(b);
-    p.n_cand = static_cast<uint32_t>(j.h_cand.size());
-    if (p.n_cand) {
-        HIPCHK(j.d_cand.reserve(p.n_cand));
-        HIPCHK(hipMemcpyAsync(j.d_cand.data(), j.h_cand.data(), p.n_cand * sizeof(Slot), hipMemcpyHostToDevice, j.s));
-        p.cand = j.d_cand.data();
-    }
-    return SAGEICP_OK;
-}
-
 // both selections, then the one wait for their totals
 int select(RecallJob &j) {
     const double radius2 = j.radius * j.radius;         // formed once, as max_dist2 is
     HIPCHK(j.d_totals.reserve(2));
-    HIPCHK(j.temp.reserve(std::max(recall_temp_bytes(j.part[0].n_cand), recall_temp_bytes(j.part[1].n_cand))));
+    HIPCHK(j.temp.reserve(std::max(recall_temp_bytes(j.sp.part[0].n_cand), recall_temp_bytes(j.sp.part[1].n_cand))));
     const DevMap dm = j.dst.dev.view(j.dst.host);       // (the destination's size classes)
     for (int k = 0; k < 2; ++k) {
-        if (int rc = j.pb[k].reserve(j.part[k])) return rc;
-        HIPCHK(recall_select(j.part[k], dm, j.center, radius2, j.temp.data(), j.temp.capacity(), j.d_totals.data() + k, j.s));
+        if (int rc = j.pb[k].reserve(j.sp.part[k])) return rc;
+        HIPCHK(recall_select(j.sp.part[k], dm, j.center, radius2, j.temp.data(), j.temp.capacity(), j.d_totals.data() + k, j.s));
     }
     HIPCHK(hipMemcpyAsync(j.t.part, j.d_totals.data(), 2 * sizeof(RecallTotals), hipMemcpyDeviceToHost, j.s));
-    if (const uint32_t nv = j.part[0].n_cand) {         // what LATEST holds: the session's records
-        const LatestScratch ls = j.lb.view();
+    if (const uint32_t nv = j.sp.part[0].n_cand) {         // what LATEST holds: the session's records
+        const LatestScratch ls = j.sp.lb.view();
         HIPCHK(hipMemcpyAsync(&j.t.latest_voxels, ls.n_sel, sizeof(uint32_t), hipMemcpyDeviceToHost, j.s));
         HIPCHK(hipMemcpyAsync(&j.t.latest_rows, ls.offsets + nv, sizeof(uint32_t), hipMemcpyDeviceToHost, j.s));
     }
@@ -173,8 +158,8 @@ int fill(RecallJob &j, sageicp_recall_info *info) {
     MapDevice &d = j.dst.dev;
     const DevMap dm = d.view(j.dst.host);
     const uint32_t n32 = static_cast<uint32_t>(n), u32 = static_cast<uint32_t>(units);
-    HIPCHK(recall_fill(j.part[0], dm, 0u, 0u, n32, u32, ta.rows, j.s));
-    HIPCHK(recall_fill(j.part[1], dm, ta.voxels, ta.units, n32, u32, tm.rows, j.s));
+    HIPCHK(recall_fill(j.sp.part[0], dm, 0u, 0u, n32, u32, ta.rows, j.s));
+    HIPCHK(recall_fill(j.sp.part[1], dm, ta.voxels, ta.units, n32, u32, tm.rows, j.s));
     HIPCHK(recall_finish(dm, n32, rows, u32, static_cast<uint32_t>(d.units_cap()), j.s));
     HIPCHK(hipMemcpyAsync(d.h_ctr.data(), d.d_ctr.data(), sizeof(MapCounters), hipMemcpyDeviceToHost, j.s));
     HIPCHK(hipStreamSynchronize(j.s));
@@ -204,8 +189,8 @@ int recall(sageicp_map &src, const double center[3], double radius, sageicp_map 
     HIPCHK(hipSetDevice(src.device));
     dst.sc.wait();                       // nothing of the destination's runs any more: its arrays are filled on src's stream
     sageicp_map_clear(&dst);             // (its archive stays as it is)
-    RecallJob j{src, dst, center, radius, src.sc.stream.get(), {}, {}, {}, {}, {}, {}, {}, {}, {}, {}};
-    if (!(rc = archive_part(j)) && !(rc = live_part(j)) && !(rc = select(j))) rc = fill(j, info);
+    RecallJob j{src, dst, center, radius, src.sc.stream.get(), {}, {}, {}, {}, {}};
+    if (!(rc = session_archive_part(src, j.s, true, j.sp)) && !(rc = session_live_part(src, j.s, j.sp)) && !(rc = select(j))) rc = fill(j, info);
     if (rc) {                            // the destination stays cleared; nothing is left running on its arrays
         (void)hipStreamSynchronize(j.s);
         dst.dev.invalidate();

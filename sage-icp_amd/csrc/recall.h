@@ -48,6 +48,37 @@ struct RecallPart {
     RecallNeed *need, *off;      // [n_cand + 1]; off[n_cand]: the totals
 };
 
+// a candidate as the kernels read it (recall.hip; closure.hip enumerates the session through the same function)
+struct Cand {
+    int32_t x, y, z;
+    uint32_t count;
+    uint64_t first;              // its first row in P.rows
+};
+
+// candidate i of a part; false: not a voxel of the session (an older generation of its key, a free block)
+__device__ __forceinline__ bool cand_of(const RecallPart &P, uint32_t i, Cand &c) {
+    if (P.vox) {
+        if (!P.latest[i]) return false;
+        const ArchiveVoxel v = P.vox[i];
+        c.x = v.x; c.y = v.y; c.z = v.z;
+        c.count = v.count;
+        c.first = v.first_row;
+        return true;
+    }
+    Slot e;
+    if (P.cand) {
+        e = P.cand[i];
+    } else {
+        const uint32_t s = P.slot_of[P.list ? P.list[i] : i];
+        if (s == kNoSlot) return false;
+        e = P.table[s];
+    }
+    c.x = e.x; c.y = e.y; c.z = e.z;
+    c.count = e.blk & 255u;
+    c.first = static_cast<uint64_t>(e.blk >> 8) * kDevUnitPoints;
+    return true;
+}
+
 struct RecallTotals {            // what the host waits for, per part
     uint32_t voxels, rows, units;
 };

@@ -14,6 +14,7 @@
 
 #include <Eigen/Core>
 #include <sophus/se3.hpp>
+#include <array>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -131,6 +132,22 @@ struct VoxelHashMap {
     // does not hold, then Pointcloud().
     Vector4dVector ArchivedPointcloud() const { return ArchiveRows(SAGEICP_ARCHIVE_ALL, "ArchivedPointcloud"); }
     Vector4dVector SessionPointcloud() const { return ArchiveRows(SAGEICP_SESSION, "SessionPointcloud"); }
+    // The session's map after a loop closure (include/sageicp.h "loop closure"): SessionPointcloud()'s rows,
+    // each moved by the correction of the pose its voxel belongs to.  positions[s]: the sensor position of the update with
+    // serial s; corrections[s]: C_s of sageicp_closure_corrections as (qx, qy, qz, qw, tx, ty, tz), one per position.
+    Vector4dVector CorrectedPointcloud(const std::vector<Eigen::Vector3d> &positions,
+                                       const std::vector<std::array<double, 7>> &corrections) const {
+        if (positions.empty() || positions.size() != corrections.size())
+            throw std::runtime_error("sage_icp::VoxelHashMap::CorrectedPointcloud: one correction per position, at least one");
+        const double *pos = positions.front().data(), *corr = corrections.front().data();
+        uint64_t n = 0;
+        Check(sageicp_map_session_corrected(map_, SAGEICP_SESSION, 0, pos, corr, positions.size(), nullptr, 0, &n),
+              "CorrectedPointcloud");
+        Vector4dVector out(n);
+        Check(sageicp_map_session_corrected(map_, SAGEICP_SESSION, 0, pos, corr, positions.size(), Data(out), out.size(), &n),
+              "CorrectedPointcloud");
+        return out;
+    }
     // Recall (include/sageicp.h): the voxels of the session's map whose first point lies within `radius` of
     // `center`, as a map of max_distance = radius that can be searched — what Relocalize takes when a place was
     // recognised after the local map evicted it.  The returned map is filled on the device and is in block-pool order
