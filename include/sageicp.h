@@ -1032,6 +1032,76 @@ int sageicp_pipeline_session_corrected_device(const sageicp_pipeline *p, int whi
                                               uint64_t n, const sageicp_device_points *dst,
                                               void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
 
+/* ---- pose graph: several loop closures at once -------------------------------------------------------------
+ * Additions only; the ABI version stays; off unless called.  sageicp_closure_corrections spreads ONE closure; applied one
+ * after another, a later closure reopens the seam of an earlier one.  This is the optimiser between Relocalize's relative
+ * poses and sageicp_map_session_corrected*: a chain of odometry edges plus c <= 256 closures, minimised together.
+ *
+ * The problem.  poses: n >= 2 rows x_k = T_world_k, (qx, qy, qz, qw, tx, ty, tz), unit quaternions.  The tangent is
+ * (upsilon, omega), translation first.  Odometry edges are implicit: for k < n - 1, Z_k = poses[k]^-1 * poses[k + 1], with
+ * information odom_info, a row-major symmetric positive definite 6x6 — one for all edges (odom_info_stride 0) or one per
+ * edge (36).  Closure edges are explicit, in any order, several on one pair allowed: z = T_a_b (pose b in pose a's frame),
+ * a != b.  With
+ *     r_e(x) = log(Z_e^-1 * x_a^-1 * x_b)          F(x) = sum_e r_e^T info_e r_e
+ * F is minimised over the poses but `anchor`, by Gauss-Newton with the exact Jacobians (d r / d delta_b = Jr^-1(r),
+ * d r / d delta_a = -Jr^-1(r) Ad((x_a^-1 x_b)^-1)) under the update x_k <- x_k * exp(delta_k) (quaternion renormalised), from
+ * `initial` (NULL: poses).  Every term is a function of relative transforms (x_a^-1 x_b is formed from t_b - t_a), so the
+ * problem moves with the trajectory at UTM coordinates.  The step solves H delta = -g, H = sum J^T info J, exactly (a block
+ * tridiagonal factor plus a rank-6c correction); it is tried at s = 1, 1/2, ... (max_halvings halvings) and taken only if F
+ * decreases.  status: 0 an accepted step with |s delta|_inf <= step_tol; 1 no trial decreased F (the floating-point floor);
+ * 2 max_iterations reached.  The anchor's output is its input bit for bit and its correction (0,0,0,1,0,0,0).
+ *     corrections_out[k] = poses_out[k] * poses[k]^-1       (sageicp_closure_corrections' convention: it goes straight
+ *                                                            into sageicp_map_session_corrected*)
+ * info: F at the start and at poses_out, grad_max = |dF/d delta|_inf at poses_out, step_last = |s delta|_inf of the last
+ * accepted step, max_shift = the largest |t_out - t_poses|, accepted iterations, halvings in all, status, where it ran.
+ * where: 1 the host (sequential block Thomas), 2 the device (block cyclic reduction; the same bytes on
+ * every run; SAGEICP_ERR_NO_DEVICE without one), 0 the device from SAGEICP_GRAPH_AUTO_POSES poses on if there is one.
+ * Host and device agree to tolerance, not to bits.  The device path takes the current device and works in buffers of
+ * its own for the call: per pose about 2.6 KB, plus at most 512 MiB (or one column, if that is more) for the
+ * right-hand sides, which are solved in chunks of columns.
+ * SAGEICP_ERR_INVALID, nothing written: a null pointer that is not optional; n < 2; a == b or an index >= n; anchor >= n;
+ * a non-finite input; a quaternion of norm 0; an info that is not symmetric to the bit or not positive definite by an
+ * unpivoted Cholesky; a stride that is neither 0 nor 36; where > 2; a step_tol that is negative or NaN; a chain whose
+ * normal matrix the factor finds not positive definite to fp64 (hundreds of thousands of metre steps with few closures).
+ * SAGEICP_ERR_CAPACITY: c > 256, or n beyond 2^31.
+ * sageicp_graph_edge_from_closed: the edge of "pose j really is at `closed`, in pose i's frame of the world"
+ * (sageicp_closure_corrections' argument; what Relocalize returns against a map recalled around pose i): z = poses[i]^-1 *
+ * closed, a = i, b = j.  sageicp_graph_cost: F at `at` (host, fp64), and each edge's term (odometry first).
+ * The pipeline's entry takes the pipeline's poses; the pipeline itself is not touched. */
+#define SAGEICP_GRAPH_AUTO_POSES 4000
+typedef struct sageicp_graph_edge {
+    uint64_t a, b;
+    double z[7];
+    double info[36];
+} sageicp_graph_edge;
+typedef struct sageicp_graph_params {
+    uint64_t anchor;            /* default 0 */
+    uint32_t max_iterations;    /* default 50 */
+    uint32_t max_halvings;      /* default 10 */
+    double step_tol;            /* default 1e-9 */
+    uint32_t where;             /* 0 auto, 1 host, 2 device */
+    uint32_t reserved;
+} sageicp_graph_params;
+typedef struct sageicp_graph_info {
+    double cost_initial, cost_final, grad_max, step_last, max_shift;
+    uint32_t iterations, halvings, status, where;
+} sageicp_graph_info;
+void sageicp_graph_params_default(sageicp_graph_params *p);
+int sageicp_graph_edge_from_closed(const double *poses /* n x 7 */, uint64_t n, uint64_t i, uint64_t j, const double closed[7],
+                                   const double info[36], sageicp_graph_edge *out);
+int sageicp_graph_cost(const double *poses /* n x 7 */, uint64_t n, const double *odom_info, uint32_t odom_info_stride,
+                       const sageicp_graph_edge *closures, uint32_t c, const double *at /* n x 7 */, double *cost,
+                       double *per_edge /* n - 1 + c, may be NULL */);
+int sageicp_graph_optimize(const double *poses /* n x 7 */, uint64_t n, const double *odom_info, uint32_t odom_info_stride,
+                           const sageicp_graph_edge *closures /* may be NULL if c == 0 */, uint32_t c,
+                           const double *initial /* n x 7; NULL = poses */, const sageicp_graph_params *params /* NULL = defaults */,
+                           double *poses_out /* n x 7 */, double *corrections_out /* n x 7, may be NULL */,
+                           sageicp_graph_info *info /* may be NULL */);
+int sageicp_pipeline_graph_optimize(const sageicp_pipeline *p, const double *odom_info, uint32_t odom_info_stride,
+                                    const sageicp_graph_edge *closures, uint32_t c, const sageicp_graph_params *params,
+                                    double *corrections_out /* n x 7 */, double *poses_out /* may be NULL */,
+                                    sageicp_graph_info *info /* may be NULL */);
+
 /* ---- place recognition: the semantic scan context of key frames (place.hip) -------------------------------------------
  * Additions only; the ABI version stays.  A descriptor says where the sensor stood: a polar grid of R rings by S sectors
  * around it that holds, per cell, the highest return (a byte) and the most important class.  Descriptors of one

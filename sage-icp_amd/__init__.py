@@ -250,6 +250,30 @@ class ClosureInfo(C.Structure):
         return dict(delta=np.array(self.delta[:]), angle=self.angle, shift=self.shift, path=self.path, i=int(self.i), j=int(self.j))
 
 
+class GraphEdge(C.Structure):
+    """sageicp_graph_edge: a closure of the pose graph, z = T_a_b with its 6x6 information"""
+    _fields_ = [("a", C.c_uint64), ("b", C.c_uint64), ("z", C.c_double * 7), ("info", C.c_double * 36)]
+
+
+class GraphParams(C.Structure):
+    """sageicp_graph_params"""
+    _fields_ = [("anchor", C.c_uint64), ("max_iterations", C.c_uint32), ("max_halvings", C.c_uint32), ("step_tol", C.c_double),
+                ("where", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GraphInfo(C.Structure):
+    """sageicp_graph_info"""
+    _fields_ = [("cost_initial", C.c_double), ("cost_final", C.c_double), ("grad_max", C.c_double), ("step_last", C.c_double),
+                ("max_shift", C.c_double), ("iterations", C.c_uint32), ("halvings", C.c_uint32), ("status", C.c_uint32),
+                ("where", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+GRAPH_WHERE = {"auto": 0, "host": 1, "device": 2}
+
+
 class OccupancyParams(C.Structure):
     """sageicp_occupancy_params: the bird's-eye grid of key-frame selection (bounds of x, y, z; H rows, W columns)"""
     _fields_ = [("bounds", (C.c_double * 2) * 3), ("occ_h", C.c_int32), ("occ_w", C.c_int32), ("overlap_th", C.c_double)]
@@ -527,6 +551,13 @@ _SIGNATURES = [
     ("sageicp_pipeline_session_corrected", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _dp, C.c_uint64, _dp, C.c_uint64, _u64p]),
     ("sageicp_pipeline_session_corrected_device", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _dp, C.c_uint64,
                                                             C.POINTER(DevicePoints), C.c_void_p, _u64p]),
+    ("sageicp_graph_params_default", None, [C.POINTER(GraphParams)]),
+    ("sageicp_graph_edge_from_closed", C.c_int, [_dp, C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, C.POINTER(GraphEdge)]),
+    ("sageicp_graph_cost", C.c_int, [_dp, C.c_uint64, _dp, C.c_uint32, C.POINTER(GraphEdge), C.c_uint32, _dp, _dp, _dp]),
+    ("sageicp_graph_optimize", C.c_int, [_dp, C.c_uint64, _dp, C.c_uint32, C.POINTER(GraphEdge), C.c_uint32, _dp,
+                                         C.POINTER(GraphParams), _dp, _dp, C.POINTER(GraphInfo)]),
+    ("sageicp_pipeline_graph_optimize", C.c_int, [C.c_void_p, _dp, C.c_uint32, C.POINTER(GraphEdge), C.c_uint32,
+                                                  C.POINTER(GraphParams), _dp, _dp, C.POINTER(GraphInfo)]),
     ("sageicp_place_tables", C.c_int, [C.POINTER(PlaceParams), _dp, _dp]),
     ("sageicp_place_describe", C.c_int, [_dp, C.c_uint64, C.POINTER(PlaceParams), C.c_void_p, C.c_int]),
     ("sageicp_place_describe_device", C.c_int, [C.POINTER(DeviceFrame), C.POINTER(PlaceParams), C.c_void_p, C.c_void_p]),
@@ -1879,6 +1910,18 @@ class SageICP:
         _check(lib().sageicp_pipeline_closure(self._h, int(i), _p(c), _p(corr), _p(poses), C.byref(info)))
         return corr, poses, info.as_dict()
 
+    def OptimizeGraph(self, closures, odom_info, anchor=0, max_iterations=None, max_halvings=None, step_tol=None, where="auto"):
+        """The pipeline's poses optimised under all `closures` at once (graph_edge() records; sageicp_pipeline_graph_optimize,
+        DESIGN.md D19).  Returns (corrections (n, 7), corrected poses (n, 7), info dict), as Closure does; the corrections go
+        into CorrectedSessionMap.  The pipeline itself is not touched."""
+        n = int(lib().sageicp_pipeline_num_poses(self._h))
+        corr, poses, info = np.empty((n, 7)), np.empty((n, 7)), GraphInfo()
+        arr, c = _graph_edges(closures)
+        O, stride = _graph_odom_info(odom_info, n)
+        prm = _graph_params(anchor, max_iterations, max_halvings, step_tol, where)
+        _check(lib().sageicp_pipeline_graph_optimize(self._h, _p(O), stride, arr, c, C.byref(prm), _p(corr), _p(poses), C.byref(info)))
+        return corr, poses, info.as_dict()
+
     def CorrectedSessionMap(self, corrections, which="session", first=0, device=False, dtype=None, out=None, labels_out=None):
         """SessionMap(which)'s rows re-posed by `corrections` (n, 7), one per pose of the pipeline, as Closure returns
         them (sageicp_pipeline_session_corrected[_device]; VoxelHashMap.CorrectedPointcloud)"""
@@ -2008,6 +2051,91 @@ def closure_corrections(poses, i, j, closed, return_info=False):
         raise ValueError("closure_corrections takes poses (n, 7) and closed[7]")
     corr, out, info = np.empty_like(P), np.empty_like(P), ClosureInfo()
     _check(lib().sageicp_closure_corrections(_p(P), P.shape[0], int(i), int(j), _p(c), _p(corr), _p(out), C.byref(info)))
+    return (corr, out, info.as_dict()) if return_info else (corr, out)
+
+
+def _graph_edges(closures):
+    closures = list(closures) if closures is not None else []
+    arr = (GraphEdge * max(1, len(closures)))()
+    for k, e in enumerate(closures):
+        if not isinstance(e, GraphEdge):
+            raise ValueError("closures are GraphEdge records (graph_edge())")
+        arr[k] = e
+    return arr, len(closures)
+
+
+def _graph_odom_info(odom_info, n):
+    """(array, stride): one 6x6 for all odometry edges, or (n - 1, 6, 6) / (n - 1, 36), one per edge"""
+    O = np.ascontiguousarray(odom_info, dtype=np.float64)
+    if O.size == 36:
+        return O.reshape(36), 0
+    if n >= 2 and O.size == 36 * (n - 1):
+        return O.reshape(-1), 36
+    raise ValueError("odom_info is one 6x6, or one per odometry edge (n - 1 of them)")
+
+
+def _graph_params(anchor, max_iterations, max_halvings, step_tol, where):
+    prm = GraphParams()
+    lib().sageicp_graph_params_default(C.byref(prm))
+    prm.anchor = int(anchor)
+    if max_iterations is not None:
+        prm.max_iterations = int(max_iterations)
+    if max_halvings is not None:
+        prm.max_halvings = int(max_halvings)
+    if step_tol is not None:
+        prm.step_tol = float(step_tol)
+    prm.where = GRAPH_WHERE[where] if isinstance(where, str) else int(where)
+    return prm
+
+
+def graph_edge(poses, i, j, closed, info):
+    """The closure edge of "pose j really is at `closed`, in pose i's frame of the world" (closure_corrections' argument):
+    a GraphEdge with a = i, b = j, z = poses[i]^-1 * closed and the 6x6 information `info` (sageicp_graph_edge_from_closed)"""
+    P = np.ascontiguousarray(poses, dtype=np.float64)
+    c = np.ascontiguousarray(closed, dtype=np.float64).reshape(-1)
+    O = np.ascontiguousarray(info, dtype=np.float64).reshape(-1)
+    if P.ndim != 2 or P.shape[1] != 7 or c.size != 7 or O.size != 36:
+        raise ValueError("graph_edge takes poses (n, 7), closed[7] and info 6x6")
+    e = GraphEdge()
+    _check(lib().sageicp_graph_edge_from_closed(_p(P), P.shape[0], int(i), int(j), _p(c), _p(O), C.byref(e)))
+    return e
+
+
+def graph_cost(poses, closures, odom_info, at=None, per_edge=False):
+    """F(at) of the pose graph of `poses` and `closures` (at=None: at poses), host fp64 (sageicp_graph_cost);
+    per_edge=True adds each edge's term, odometry edges first"""
+    P = np.ascontiguousarray(poses, dtype=np.float64)
+    if P.ndim != 2 or P.shape[1] != 7:
+        raise ValueError("graph_cost takes poses (n, 7)")
+    A = P if at is None else np.ascontiguousarray(at, dtype=np.float64)
+    if A.shape != P.shape:
+        raise ValueError("at has the shape of poses")
+    arr, c = _graph_edges(closures)
+    O, stride = _graph_odom_info(odom_info, P.shape[0])
+    cost, pe = C.c_double(0.0), np.empty(max(0, P.shape[0] - 1) + c)
+    _check(lib().sageicp_graph_cost(_p(P), P.shape[0], _p(O), stride, arr, c, _p(A), C.byref(cost), _p(pe)))
+    return (cost.value, pe) if per_edge else cost.value
+
+
+def graph_optimize(poses, closures, odom_info, initial=None, anchor=0, max_iterations=None, max_halvings=None, step_tol=None,
+                   where="auto", return_info=False):
+    """`poses` (n, 7) optimised under its own odometry (information `odom_info`) and all `closures` (graph_edge()) at once:
+    Gauss-Newton on SE(3) with exact Jacobians, pose `anchor` fixed (sageicp_graph_optimize).  Returns
+    (corrections (n, 7), optimised poses (n, 7)); the corrections are closure_corrections' kind.  where: "auto", "host" or
+    "device".  return_info=True adds the info dict (cost_initial, cost_final, grad_max, step_last, max_shift, iterations,
+    halvings, status, where)."""
+    P = np.ascontiguousarray(poses, dtype=np.float64)
+    if P.ndim != 2 or P.shape[1] != 7:
+        raise ValueError("graph_optimize takes poses (n, 7)")
+    X0 = None if initial is None else np.ascontiguousarray(initial, dtype=np.float64)
+    if X0 is not None and X0.shape != P.shape:
+        raise ValueError("initial has the shape of poses")
+    arr, c = _graph_edges(closures)
+    O, stride = _graph_odom_info(odom_info, P.shape[0])
+    prm = _graph_params(anchor, max_iterations, max_halvings, step_tol, where)
+    corr, out, info = np.empty_like(P), np.empty_like(P), GraphInfo()
+    _check(lib().sageicp_graph_optimize(_p(P), P.shape[0], _p(O), stride, arr, c, None if X0 is None else _p(X0), C.byref(prm),
+                                        _p(out), _p(corr), C.byref(info)))
     return (corr, out, info.as_dict()) if return_info else (corr, out)
 
 
