@@ -1047,8 +1047,9 @@ int sageicp_pipeline_session_corrected_device(const sageicp_pipeline *p, int whi
  * d r / d delta_a = -Jr^-1(r) Ad((x_a^-1 x_b)^-1)) under the update x_k <- x_k * exp(delta_k) (quaternion renormalised), from
  * `initial` (NULL: poses).  Every term is a function of relative transforms (x_a^-1 x_b is formed from t_b - t_a), so the
  * problem moves with the trajectory at UTM coordinates.  The step solves H delta = -g, H = sum J^T info J, exactly (a block
- * tridiagonal factor plus a rank-6c correction); it is tried at s = 1, 1/2, ... (max_halvings halvings) and taken only if F
- * decreases.  status: 0 an accepted step with |s delta|_inf <= step_tol; 1 no trial decreased F (the floating-point floor);
+ * tridiagonal factor plus a rank-6c correction, refined twice against the edges' own blocks); it is tried at s = 1, 1/2, ...
+ * (max_halvings halvings) and taken only if F decreases — the full step also where F cannot tell, within (edges + 64) 2^-52 F
+ * of no change, what two evaluations of F at one point may differ by, and never above F at the start.  status: 0 an accepted step with |s delta|_inf <= step_tol; 1 no trial decreased F (the floating-point floor);
  * 2 max_iterations reached.  The anchor's output is its input bit for bit and its correction (0,0,0,1,0,0,0).
  *     corrections_out[k] = poses_out[k] * poses[k]^-1       (sageicp_closure_corrections' convention: it goes straight
  *                                                            into sageicp_map_session_corrected*)

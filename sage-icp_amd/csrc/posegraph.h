@@ -40,6 +40,7 @@ namespace sageicp {
 
 constexpr uint32_t kPgMaxClosures = 256;
 constexpr double kPgSeriesAngle = 0.25;
+constexpr int kPgRefineRounds = 2;           // rounds of delta += H^-1 (-g - H delta) after the Woodbury solve (capi_posegraph.hip)
 
 // ---- 6x6 blocks ------------------------------------------------------------------------------------------------------------
 SAGE_HD inline void pg_zero(double (&M)[6][6]) {
@@ -337,6 +338,14 @@ SAGE_HD inline void pg_linearize(const double Zinv[7], const double xa[7], const
         }
 }
 
+// t = A d_a + B d_b + w: the edge's linear model of its whitened residual under the steps of its two poses
+SAGE_HD inline void pg_edge_model(const PgEdgeLin &l, const double (&da)[6], const double (&db)[6], double (&t)[6]) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) t[i] = l.w[i];
+    pg_add_av(l.A, da, 1.0, t);
+    pg_add_av(l.B, db, 1.0, t);
+}
+
 // x <- x * se3_exp(s * d), the quaternion renormalised (se3_mul)
 SAGE_HD inline void pg_retract(const double x[7], const double d[6], double s, double o[7]) {
     double sd[6], E[7];
@@ -406,6 +415,21 @@ struct PgHostChain {
     }
 };
 
+// z = C^-1 b for the factor pg_solve_capacitance left in C; b[i * stride]
+inline void pg_resolve_capacitance(const std::vector<double> &C, uint32_t r, const double *b, size_t stride, double *z) {
+    for (uint32_t i = 0; i < r; ++i) {
+        const double *ci = C.data() + static_cast<size_t>(i) * r;
+        double v = b[i * stride];
+        for (uint32_t k = 0; k < i; ++k) v -= ci[k] * z[k];
+        z[i] = v / ci[i];
+    }
+    for (uint32_t i = r; i-- > 0;) {
+        double v = z[i];
+        for (uint32_t k = i + 1; k < r; ++k) v -= C[static_cast<size_t>(k) * r + i] * z[k];
+        z[i] = v / C[static_cast<size_t>(i) * r + i];
+    }
+}
+
 // z = (I + Gm[:, 1:])^-1 Gm[:, 0]: dense Cholesky of the capacitance matrix (its lower triangle), r = 6c, ld = 1 + r
 inline bool pg_solve_capacitance(const double *Gm, uint32_t r, std::vector<double> &C, double *z) {
     const size_t ld = 1 + static_cast<size_t>(r);
@@ -426,20 +450,9 @@ inline bool pg_solve_capacitance(const double *Gm, uint32_t r, std::vector<doubl
             ci[j] = v / s;
         }
     }
-    for (uint32_t i = 0; i < r; ++i) {
-        const double *ci = C.data() + static_cast<size_t>(i) * r;
-        double v = Gm[i * ld];
-        for (uint32_t k = 0; k < i; ++k) v -= ci[k] * z[k];
-        z[i] = v / ci[i];
-    }
-    for (uint32_t i = r; i-- > 0;) {
-        double v = z[i];
-        for (uint32_t k = i + 1; k < r; ++k) v -= C[static_cast<size_t>(k) * r + i] * z[k];
-        z[i] = v / C[static_cast<size_t>(i) * r + i];
-    }
+    pg_resolve_capacitance(C, r, Gm, ld, z);
     return true;
 }
-
 
 // ---- the device side (posegraph.hip) -----------------------------------------------------------------------------------------
 // Layouts.  E = n - 1 + c edges: odometry edge k = (k, k + 1) first, then the closures in the caller's order.  m = n - 1
@@ -499,7 +512,11 @@ hipError_t pg_rhs_final(const PgGraph &G, const PgSystem &S, const double *z, do
 hipError_t pg_apply(const PgSystem &S, const PgLevels &lv, uint32_t K, double *X, hipStream_t s);
 // Gm[(6 e + s) * ld + col0 + col] = (U^T X)[6 e + s][col], ld = 1 + 6 c
 hipError_t pg_capacitance(const PgGraph &G, const PgSystem &S, const double *X, uint32_t col0, uint32_t K, double *Gm, hipStream_t s);
-// out = x * exp(step * delta), the anchor's bytes copied; delta = X level 0 with K = 1
+// q = g + H delta (field-major, as g), summed from the edges' blocks; X level 0 (K = 1) <- -q
+hipError_t pg_residual(const PgGraph &G, const PgSystem &S, const double *delta, double *q, double *X, hipStream_t s);
+// delta += X level 0 (K = 1)
+hipError_t pg_accumulate(const PgGraph &G, const double *X, double *delta, hipStream_t s);
+// out = x * exp(step * delta), the anchor's bytes copied; delta: 6 per free vertex, as X level 0 with K = 1
 hipError_t pg_update(const PgGraph &G, const double *x, const double *delta, double step, double *out, hipStream_t s);
 hipError_t pg_cost(const PgGraph &G, const double *x, double *edge_cost, hipStream_t s);
 // *out = the sum (max of |.| if absmax) of v[0 .. count) by a fixed tree: slabs (kPgBlocks doubles), then one workgroup

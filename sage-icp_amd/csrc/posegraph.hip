@@ -5,6 +5,7 @@
 //   factor      k_pg_inv, k_pg_red    per level of the block cyclic reduction: invert the even diagonals, reduce onto the odd
 //   apply       k_pg_fwd, k_pg_bwd    per level, a lane per (node, column) of a chunk of right-hand sides
 //   low rank    k_pg_rhs_cols, k_pg_cap, k_pg_rhs_final     columns of [-g | U] in, U^T T^-1 [-g | U] out, -g - U z in
+//   refine      k_pg_resid, k_pg_acc          g + H delta per free vertex from its edges' blocks; delta += the correction
 //   step        k_pg_update, k_pg_cost, k_pg_red1 -> k_pg_red2
 //
 // Phases are kernel boundaries on one stream.  No atomic, no barrier across workgroups, no wait inside a kernel; every
@@ -309,6 +310,51 @@ __global__ __launch_bounds__(256) void k_pg_cap(PgGraph G, PgSystem S, const dou
     }
 }
 
+// ---- the refinement --------------------------------------------------------------------------------------------------------
+// acc += J^T (A d_a + B d_b + w) of edge e = (a, b), J its A (at_a) or B block; delta: 6 per free vertex, the anchor's zero
+__device__ __forceinline__ void add_edge_model(const PgGraph &G, const PgSystem &S, const double *__restrict__ delta, uint32_t e,
+                                               uint32_t a, uint32_t b, bool at_a, double (&acc)[6]) {
+    PgEdgeLin l;
+    ld36(S.lin, G.E, e, l.A);
+    ld36(S.lin + static_cast<size_t>(36) * G.E, G.E, e, l.B);
+    ld6(S.lin + static_cast<size_t>(72) * G.E, G.E, e, l.w);
+    double da[6], db[6], t[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        da[i] = a == G.anchor ? 0.0 : delta[static_cast<size_t>(pg_free_of(a, G.anchor)) * 6 + i];
+        db[i] = b == G.anchor ? 0.0 : delta[static_cast<size_t>(pg_free_of(b, G.anchor)) * 6 + i];
+    }
+    pg_edge_model(l, da, db, t);
+    if (at_a) pg_add_atv(l.A, t, 1.0, acc);
+    else pg_add_atv(l.B, t, 1.0, acc);
+}
+
+// a lane per free vertex, its edges in k_pg_asm's order
+__global__ __launch_bounds__(256) void k_pg_resid(PgGraph G, PgSystem S, const double *__restrict__ delta, double *__restrict__ q,
+                                                  double *__restrict__ X) {
+    PG_STRIDE(f64, G.m) {
+        const uint32_t f = static_cast<uint32_t>(f64), k = pg_vertex_of(f, G.anchor);
+        double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (k >= 1u) add_edge_model(G, S, delta, k - 1u, k - 1u, k, false, acc);
+        if (k + 1u < G.n) add_edge_model(G, S, delta, k, k, k + 1u, true, acc);
+        for (uint32_t ce = 0; ce < G.c; ++ce) {
+            const uint32_t a = G.ca[ce], b = G.cb[ce];
+            if (a == k || b == k) add_edge_model(G, S, delta, G.n - 1u + ce, a, b, a == k, acc);
+        }
+        double v[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            q[static_cast<size_t>(i) * G.m + f] = acc[i];
+            v[i] = -acc[i];
+        }
+        stx(X, f, 1u, 0u, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pg_acc(uint64_t count, const double *__restrict__ X, double *__restrict__ delta) {
+    PG_STRIDE(i, count) delta[i] += X[i];
+}
+
 // ---- the step --------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pg_update(PgGraph G, const double *__restrict__ x, const double *__restrict__ delta,
                                                    double step, double *__restrict__ out) {
@@ -428,6 +474,19 @@ hipError_t pg_apply(const PgSystem &S, const PgLevels &lv, uint32_t K, double *X
 hipError_t pg_capacitance(const PgGraph &G, const PgSystem &S, const double *X, uint32_t col0, uint32_t K, double *Gm, hipStream_t s) {
     if (!G.c || !K) return hipSuccess;
     hipLaunchKernelGGL(k_pg_cap, dim3(grid_for(static_cast<uint64_t>(6u * G.c) * K)), dim3(256), 0, s, G, S, X, col0, K, Gm);
+    return hipGetLastError();
+}
+
+hipError_t pg_residual(const PgGraph &G, const PgSystem &S, const double *delta, double *q, double *X, hipStream_t s) {
+    if (!G.m) return hipSuccess;
+    hipLaunchKernelGGL(k_pg_resid, dim3(grid_for(G.m)), dim3(256), 0, s, G, S, delta, q, X);
+    return hipGetLastError();
+}
+
+hipError_t pg_accumulate(const PgGraph &G, const double *X, double *delta, hipStream_t s) {
+    if (!G.m) return hipSuccess;
+    const uint64_t count = 6 * static_cast<uint64_t>(G.m);
+    hipLaunchKernelGGL(k_pg_acc, dim3(grid_for(count)), dim3(256), 0, s, count, X, delta);
     return hipGetLastError();
 }
 

@@ -126,6 +126,54 @@ def chain(n, c, seed, how="spread", anchor=0):
     return dict(poses=poses, truth=truth, odom_info=ODOM_INFO.copy(), closures=closures)
 
 
+ODOM_ANGLES = (1e-3, 0.2499, 0.2501, 0.6)
+CLOSURE_ANGLES = (0.01, 0.2499, 0.2501, 1.5, 3.0)
+
+
+def _unit(rng):
+    v = rng.normal(size=3)
+    return v / np.linalg.norm(v)
+
+
+def stepped(n, c, seed, anchor=0, how="edges", angles=CLOSURE_ANGLES, odom_angles=ODOM_ANGLES, trans=0.02, base=None):
+    """chain(n, c, seed, how, anchor) with a start whose first linearisation decides (tests/graphsteps.py): scene["initial"]
+    = poses * exp(e_k), the tangents e_k drawn once.  Poses of even k keep their rotation and poses of odd k turn by
+    odom_angles[(k // 2) % 4] about an axis of their own, so the residuals of the two odometry edges at an odd pose have
+    exactly that angle (to rounding): no odometry residual is zero, and the angles lie on either side of posegraph.h's
+    kPgSeriesAngle = 0.25 rad.  An odd pose at which a closure ends turns by odom_angles[0] only: the closure is taken from
+    the start, and a pose turned by 0.6 rad would swing a closure of 100 m by 60 m against the odometry, a start from
+    which no step within three halvings decreases F on the long chains.  Every pose is also shifted by `trans` metres
+    (normal).  Each closure's measurement is
+    turned by the exp(.) that makes its residual at initial (u, angles[k % len] * axis) to rounding.  Every fifth start
+    pose and every other closure carry the other sign of their quaternion (the same rotation; se3_log then meets
+    qw < 0).  Translations of poses and of initial lie on the 2^-10 m grid.  base: another drive (poses, truth, odom_info,
+    closures) in place of chain's."""
+    s = chain(n, c, seed, how=how, anchor=anchor) if base is None else dict(base)
+    rng = np.random.default_rng(seed + 7919)
+    poses = s["poses"]
+    n = len(poses)
+    e = np.zeros((n, 6))
+    e[:, :3] = trans * rng.normal(size=(n, 3))
+    axes = rng.normal(size=(n, 3))
+    theta = np.array(odom_angles)[(np.arange(n) // 2) % len(odom_angles)] * (np.arange(n) % 2)
+    for a, b, _, _ in s["closures"]:                             # (a closure's ends: see above)
+        theta[[a, b]] = np.minimum(theta[[a, b]], odom_angles[0])
+    e[:, 3:] = theta[:, None] * axes / np.linalg.norm(axes, axis=1)[:, None]
+    initial = pg.vmul(poses, pg.vexp(e))
+    initial[:, 4:] = np.round(initial[:, 4:] * 1024.0) / 1024.0
+    initial[3::5, :4] *= -1.0
+    closures = []
+    for k, (a, b, z, info) in enumerate(s["closures"]):
+        r = np.concatenate([trans * rng.normal(size=3), angles[k % len(angles)] * _unit(rng)])
+        # z exp(t) with t = log(z^-1 D exp(-r)), D = initial_a^-1 initial_b: the product itself, not through the logarithm
+        z2 = pg.vmul(pg.vbetween(initial[a][None], initial[b][None]), pg.vexp(-r[None]))[0]
+        if k % 2:
+            z2[:4] *= -1.0
+        closures.append((a, b, z2, info))
+    s["closures"], s["initial"] = closures, initial
+    return s
+
+
 def edges(sage, scene):
     """the scene's closures as the library's records"""
     out = []

@@ -9,7 +9,14 @@ written from the definitions:
     does not move the fixed point, which is where the gradient of the chosen type vanishes); mode "identity" replaces
     Jr^-1 by I — the approximation the library must NOT be;
   * measured(): for a scene, the longdouble optimum, d_ref = the distance between the fp64 and the longdouble runs, both
-    run to a stall, and the contraction ratio of the late steps — asserted <= 0.8 here, on the restatement's own."""
+    run to a stall, and the contraction ratio of the late steps — asserted <= 0.8 here, on the restatement's own;
+  * step_exact(): ONE Gauss-Newton step to the precision of the graph's type (the dense system assembled from the edges'
+    blocks in that type, an fp64 factorisation refined with residuals of that type); residual(): what a given step leaves
+    of H d + g, edge by edge with no dense matrix, relative to the size of its terms; step_measured(): for a scene and a
+    start, the longdouble step, the halvings the longdouble run takes, the pose after it, and how far the fp64
+    restatement's own step is from all of that — what tests/graphsteps.py holds one step of the library to."""
+import copy
+
 import numpy as np
 
 import closureref as cr
@@ -206,6 +213,64 @@ class Graph:
         d[keep] = np.linalg.solve(H, -g)
         return d.reshape(self.n, 6), H
 
+    def step_exact(self, x, rounds=4):
+        """the Gauss-Newton step (n, 6) and H, both in the graph's type: H and g summed from the edges' 6x6 blocks in that
+        type (the Jacobians are step()'s), the solve by an fp64 factorisation refined `rounds` times with residuals of the
+        graph's type (each round gains cond(H) 2^-53: four reach 1e-19 at cond 5e8)"""
+        assert self.n <= 130
+        w, Ja, Jb = self.jacobians(x)
+        N = self.n
+        H = np.zeros((N, N, 6, 6), dtype=self.dtype)
+        g = np.zeros((N, 6), dtype=self.dtype)
+        np.add.at(H, (self.a, self.a), np.einsum("eki,ekj->eij", Ja, Ja))
+        np.add.at(H, (self.b, self.b), np.einsum("eki,ekj->eij", Jb, Jb))
+        np.add.at(H, (self.a, self.b), np.einsum("eki,ekj->eij", Ja, Jb))
+        np.add.at(H, (self.b, self.a), np.einsum("eki,ekj->eij", Jb, Ja))
+        np.add.at(g, self.a, np.einsum("eki,ek->ei", Ja, w))
+        np.add.at(g, self.b, np.einsum("eki,ek->ei", Jb, w))
+        keep = np.ones(6 * N, dtype=bool)
+        keep[6 * self.anchor:6 * self.anchor + 6] = False
+        H = H.transpose(0, 2, 1, 3).reshape(6 * N, 6 * N)[np.ix_(keep, keep)]
+        rhs = -g.reshape(-1)[keep]
+        H64 = H.astype(np.float64)
+        dk = np.linalg.solve(H64, rhs.astype(np.float64)).astype(self.dtype)
+        for _ in range(rounds):
+            r = rhs - np.array([(row * dk).sum() for row in H])
+            dk = dk + np.linalg.solve(H64, r.astype(np.float64)).astype(self.dtype)
+        d = np.zeros(6 * N, dtype=self.dtype)
+        d[keep] = dk
+        return d.reshape(N, 6), H
+
+    def residual(self, x, d, sample=None):
+        """rho = max |r| / max S of the step d (n, 6) at x: per free vertex i, r_i = sum J_i^T (Ja d_a + Jb d_b + w) over its
+        edges and S_i = sum |J_i^T| (|Ja| |d_a| + |Jb| |d_b| + |w|), the size of the terms r_i is summed from.  Edge by
+        edge, no dense matrix.  sample: these vertices only, from their incident edges (rows of d beyond the sample and
+        its neighbours are not read)"""
+        G = self
+        if sample is not None:
+            keep = np.zeros(self.n, dtype=bool)
+            keep[sample] = True
+            sel = np.nonzero(keep[self.a] | keep[self.b])[0]
+            G = copy.copy(self)
+            G.a, G.b, G.zinv, G.L, G.E = self.a[sel], self.b[sel], self.zinv[sel], self.L[sel], len(sel)
+        w, Ja, Jb = G.jacobians(x)
+        d = np.array(d, dtype=self.dtype)
+        d[self.anchor] = 0
+        da, db = d[G.a], d[G.b]
+        lin = np.einsum("eki,ei->ek", Ja, da) + np.einsum("eki,ei->ek", Jb, db) + w
+        mag = np.einsum("eki,ei->ek", np.abs(Ja), np.abs(da)) + np.einsum("eki,ei->ek", np.abs(Jb), np.abs(db)) + np.abs(w)
+        r = np.zeros((self.n, 6), dtype=self.dtype)
+        S = np.zeros((self.n, 6), dtype=self.dtype)
+        np.add.at(r, G.a, np.einsum("eki,ek->ei", Ja, lin))
+        np.add.at(r, G.b, np.einsum("eki,ek->ei", Jb, lin))
+        np.add.at(S, G.a, np.einsum("eki,ek->ei", np.abs(Ja), mag))
+        np.add.at(S, G.b, np.einsum("eki,ek->ei", np.abs(Jb), mag))
+        r[self.anchor] = 0
+        S[self.anchor] = 0
+        if sample is not None:
+            r, S = r[sample], S[sample]
+        return float(np.abs(r).max() / S.max())
+
     def retract(self, x, d):
         x = np.asarray(x).astype(self.dtype)
         out = vmul(x, vexp(np.asarray(d).astype(self.dtype)))
@@ -271,3 +336,47 @@ def measured(key, poses, odom_info, closures, anchor=0, initial=None, identity=T
         _MEASURED[key] = dict(opt=xl, opt64=x64, F=float(Fl), d_ref=distance(x64, xl), ratio=ratio, steps=steps, fixed_identity=xi,
                               cond=float(np.linalg.cond(H)), F0=float(Gl.cost(x0)))
     return _MEASURED[key]
+
+
+def angles(G, x):
+    """the rotation angle of every edge's residual at x, and the real part of the quaternion se3_log is handed"""
+    x = np.asarray(x).astype(G.dtype)
+    T = vmul(G.zinv, vbetween(x[G.a], x[G.b]))
+    return np.linalg.norm(vlog(T)[:, 3:].astype(np.float64), axis=1), T[:, 3].astype(np.float64)
+
+
+_STEPPED = {}
+
+
+def step_measured(key, poses, odom_info, closures, anchor, initial, max_halvings):
+    """One Gauss-Newton iteration from `initial`, in np.longdouble, and the fp64 restatement's distance from it — computed
+    once per key.  dict(d: the longdouble step (n, 6); h: the halvings the longdouble run takes, the first s = 2^-h with
+    F(x0 exp(s d)) < F(x0); s; x1 = retract(x0, s d); F0, F1; d_ref = distance(x1, the fp64 graph's own x1 at the same h);
+    rho_ref: the residual of the fp64 graph's step under the longdouble graph; rho: the longdouble step's own; cond of H;
+    grad0, grad1: the longdouble gradients at x0 and x1; theta, qw: angles(); deg: the most edges at one vertex).
+    Asserted here, on the restatement alone, as conditions on the scene: h <= max_halvings, and at every trial up to and
+    including the accepted one |F_trial - F0| > 1e-6 F0, so that no path's rounding decides h."""
+    if key not in _STEPPED:
+        Gl = Graph(poses, odom_info, closures, np.longdouble, anchor)
+        G64 = Graph(poses, odom_info, closures, np.float64, anchor)
+        x0 = np.asarray(initial, dtype=np.float64)
+        d, H = Gl.step_exact(x0)
+        F0 = Gl.cost(x0)
+        h, s, x1, F1 = None, np.longdouble(1), None, None
+        for k in range(max_halvings + 1):
+            xt = Gl.retract(x0, s * d)
+            Ft = Gl.cost(xt)
+            assert abs(Ft - F0) > 1e-6 * F0, (key, k, float(Ft), float(F0))
+            if Ft < F0:
+                h, x1, F1 = k, xt, Ft
+                break
+            s = s / 2
+        assert h is not None, (key, "no trial up to max_halvings = %d decreases F" % max_halvings)
+        d64, _ = G64.step(x0)
+        x1_64 = G64.retract(x0, float(s) * d64)
+        theta, qw = angles(Gl, x0)
+        _STEPPED[key] = dict(d=d, h=h, s=float(s), x1=x1, F0=F0, F1=F1, d_ref=distance(x1_64, x1),
+                             rho_ref=Gl.residual(x0, d64), rho=Gl.residual(x0, d), cond=float(np.linalg.cond(H.astype(np.float64))),
+                             grad0=Gl.gradient(x0), grad1=Gl.gradient(x1), theta=theta, qw=qw,
+                             deg=int(np.bincount(np.concatenate([Gl.a, Gl.b])).max()))
+    return _STEPPED[key]
