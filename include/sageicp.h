@@ -1103,6 +1103,66 @@ int sageicp_pipeline_graph_optimize(const sageicp_pipeline *p, const double *odo
                                     double *corrections_out /* n x 7 */, double *poses_out /* may be NULL */,
                                     sageicp_graph_info *info /* may be NULL */);
 
+/* ---- robust pose graph: false closures down-weighted; an edge's information from a quality report --------
+ * Additions only; the ABI version stays.  One false place match among the closures wrecks a least-squares optimum.  With a
+ * robust kernel every CLOSURE's term s = r^T info r enters F as rho(s) (odometry edges stay quadratic), c = scale:
+ *     HUBER   rho = s if s <= c^2, else 2 c sqrt(s) - c^2      weight rho' = 1 if s <= c^2, else c / sqrt(s)
+ *     CAUCHY  rho = c^2 log1p(s / c^2)                          weight 1 / (1 + s / c^2)
+ *     GM      rho = c^2 s / (c^2 + s)                           weight (c^2 / (c^2 + s))^2
+ * Huber bounds a false closure's pull, it does not reject it; Cauchy and Geman-McClure redescend.  The step is Gauss-Newton
+ * on the re-weighted edges (each closure's linearisation scaled by sqrt(rho')): g is the exact gradient of F, H stays
+ * positive definite.  Backtracking, the (edges + 64) 2^-52 F rule and the stop rule are sageicp_graph_optimize's, applied to
+ * the robust F, on the host and on the device alike.  scale is a chi-square threshold in the edge's own information, which
+ * therefore has to be a real one: sageicp_graph_info_from_quality below.
+ * anneal = 1: from a drifted start the TRUE closures lie far outside c^2 too and a redescending kernel would give them up.
+ * With s0 the largest closure term at the start (evaluated on the host), the call runs the stages c^2 f^m, ..., c^2 f, c^2
+ * (f = anneal_factor; m the smallest count with c^2 f^m >= s0, so one stage if s0 <= c^2; more than 1024 stages:
+ * SAGEICP_ERR_CAPACITY), each but the last for at most stage_iterations iterations (fewer on status 0 or 1), the last under
+ * max_iterations; its status is the call's.  iterations and halvings count all stages.
+ * cost_initial and cost_final are the FINAL kernel's F (scale c) at the start and at poses_out; cost_final <= cost_initial is
+ * promised only with anneal == 0.  grad_max is the gradient of that F.  closure_chi2_out[k] is the raw s of closure k at
+ * poses_out (sageicp_graph_cost's term), closure_weight_out[k] its rho' at c^2; outliers counts weights below 0.5: drop
+ * those matches.  robust == NULL or kernel NONE: sageicp_graph_optimize itself, bit for bit, weights 1, stages 1.
+ * SAGEICP_ERR_INVALID, nothing written, besides sageicp_graph_optimize's: kernel > 3; anneal > 1; a scale or anneal_factor
+ * that is not finite; scale <= 0; anneal_factor <= 1; stage_iterations == 0.
+ *
+ * sageicp_graph_info_from_quality: the information of the edge sageicp_graph_edge_from_closed makes of `closed`, from the
+ * quality report AT closed (what sageicp_relocalize returns).  The report's tangent is the left perturbation closed <-
+ * exp(xi) closed, an edge's the right one z <- z exp(eta), z = poses[i]^-1 closed: xi = Ad(closed) eta whatever poses[i], so
+ *     info = gain * Ad(closed)^T (JTJ / s2) Ad(closed),  Ad(T) = [[R, hat(t) R], [0, R]],  s2 = sum_w_r2 / (3 n_pairs - 6),
+ * symmetrised as (M + M^T) / 2.  gain > 0 is the caller's noise model: ICP covariances are overconfident (they know the
+ * pairs' noise, not the wrong pairs), so a gain well below 1 is usual.  SAGEICP_ERR_INVALID, nothing written: a null
+ * argument; covariance_valid == 0; s2 not above 0; an input that is not finite; a quaternion of norm 0; gain not above 0; a
+ * result that is not positive definite by the optimiser's own test (UTM coordinates: register in a local frame). */
+#define SAGEICP_GRAPH_KERNEL_NONE 0
+#define SAGEICP_GRAPH_KERNEL_HUBER 1
+#define SAGEICP_GRAPH_KERNEL_CAUCHY 2
+#define SAGEICP_GRAPH_KERNEL_GM 3
+typedef struct sageicp_graph_robust {
+    uint32_t kernel, anneal;          /* anneal: 0 / 1 */
+    double scale;                     /* c > 0; default sqrt(16.81): chi-square, 6 dof, 99 % */
+    double anneal_factor;             /* > 1, default 2 */
+    uint32_t stage_iterations;        /* >= 1, default 3 */
+    uint32_t reserved;
+} sageicp_graph_robust;
+typedef struct sageicp_graph_robust_info {
+    double scale2_first;              /* c^2 of the first stage */
+    uint32_t stages, outliers;        /* outliers: closures with weight < 0.5 at poses_out */
+} sageicp_graph_robust_info;
+void sageicp_graph_robust_default(sageicp_graph_robust *r);
+int sageicp_graph_optimize_robust(const double *poses /* n x 7 */, uint64_t n, const double *odom_info, uint32_t odom_info_stride,
+                                  const sageicp_graph_edge *closures, uint32_t c, const double *initial,
+                                  const sageicp_graph_params *params, double *poses_out, double *corrections_out,
+                                  sageicp_graph_info *info, const sageicp_graph_robust *robust /* NULL = none */,
+                                  double *closure_chi2_out /* c, may be NULL */, double *closure_weight_out /* c, may be NULL */,
+                                  sageicp_graph_robust_info *rinfo /* may be NULL */);
+int sageicp_pipeline_graph_optimize_robust(const sageicp_pipeline *p, const double *odom_info, uint32_t odom_info_stride,
+                                           const sageicp_graph_edge *closures, uint32_t c, const sageicp_graph_params *params,
+                                           double *corrections_out /* n x 7 */, double *poses_out /* may be NULL */,
+                                           sageicp_graph_info *info /* may be NULL */, const sageicp_graph_robust *robust,
+                                           double *closure_chi2_out, double *closure_weight_out, sageicp_graph_robust_info *rinfo);
+int sageicp_graph_info_from_quality(const sageicp_quality *q, const double closed[7], double gain, double info_out[36]);
+
 /* ---- place recognition: the semantic scan context of key frames (place.hip) -------------------------------------------
  * Additions only; the ABI version stays.  A descriptor says where the sensor stood: a polar grid of R rings by S sectors
  * around it that holds, per cell, the highest return (a byte) and the most important class.  Descriptors of one

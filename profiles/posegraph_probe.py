@@ -5,6 +5,12 @@
                                                      medians and ranges of `calls` (30) calls; one JSON line per size
   python profiles/posegraph_probe.py trace           a few device calls of two sizes, to be run under
                                                      rocprofv3 --kernel-trace --stats (a run of its own)
+  python profiles/posegraph_probe.py --robust [calls] [plain]   DESIGN.md D20 (results in profiles/r41/): 4 000 poses with c = 1
+                                                     and 36 000 with c = 64, device, ITER iterations per call, 3 warm-up calls,
+                                                     medians and ranges of `calls` (30): the plain entry, Cauchy without
+                                                     anneal, and a Geman-McClure call with anneal run to its end (its total;
+                                                     more iterations by design).  `plain`: the plain entry alone — what the
+                                                     parent commit can run, for the comparison across commits
 
 The scene: two laps of a ring driven in steps of 1 m, odometry that wanders (1 cm, 0.2 mrad per step), c closures that
 join a place of lap one to the same place of lap two, spread over the lap.  At 360 000 poses the steps are 1 cm (and the
@@ -91,9 +97,31 @@ def cmd_trace():
     print(json.dumps(dict(traced=[[36000, 8], [360000, 64]], calls_of_each=3, iterations=ITER)))
 
 
+def cmd_robust(calls, plain_only):
+    for n, c in ((4000, 1), (36000, 64)):
+        s, E = drive(n, c)
+        fixed = dict(max_iterations=ITER, step_tol=0.0)
+        run = lambda **kw: sage.graph_optimize(s["poses"], E, s["odom_info"], where="device", return_info=True, **kw)
+        plain = timed(lambda: run(**fixed), calls, 3)
+        line = dict(n=n, c=len(E), iterations_timed=ITER, plain=stats(plain), plain_per_iteration_ms=round(float(np.median(plain)) / ITER, 3))
+        if not plain_only:
+            cauchy = timed(lambda: run(robust=dict(kernel="cauchy"), **fixed), calls, 3)
+            again = timed(lambda: run(**fixed), calls, 0)        # the plain entry once more, after: the run's own drift
+            anneal = timed(lambda: run(robust=dict(kernel="gm", anneal=1)), calls, 3)
+            info = run(robust=dict(kernel="gm", anneal=1))[2]
+            line.update(cauchy=stats(cauchy), cauchy_per_iteration_ms=round(float(np.median(cauchy)) / ITER, 3), plain_again=stats(again),
+                        cauchy_info=run(robust=dict(kernel="cauchy"), **fixed)[2]["iterations"],
+                        gm_anneal_to_the_end=stats(anneal), gm_anneal_iterations=info["iterations"], gm_anneal_stages=info["stages"],
+                        gm_anneal_status=info["status"], gm_anneal_outliers=info["outliers"])
+        print(json.dumps(line), flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "sizes"
-    if what == "sizes":
+    if what == "--robust":
+        rest = sys.argv[2:]
+        cmd_robust(int(next((a for a in rest if a.isdigit()), 30)), "plain" in rest)
+    elif what == "sizes":
         cmd_sizes(int(sys.argv[2]) if len(sys.argv) > 2 else 30)
     elif what == "trace":
         cmd_trace()

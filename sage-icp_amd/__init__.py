@@ -272,6 +272,18 @@ class GraphInfo(C.Structure):
 
 
 GRAPH_WHERE = {"auto": 0, "host": 1, "device": 2}
+GRAPH_KERNEL = {"none": 0, "huber": 1, "cauchy": 2, "gm": 3}
+
+
+class GraphRobust(C.Structure):
+    """sageicp_graph_robust: the robust kernel on the closures of a pose graph"""
+    _fields_ = [("kernel", C.c_uint32), ("anneal", C.c_uint32), ("scale", C.c_double), ("anneal_factor", C.c_double),
+                ("stage_iterations", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class GraphRobustInfo(C.Structure):
+    """sageicp_graph_robust_info"""
+    _fields_ = [("scale2_first", C.c_double), ("stages", C.c_uint32), ("outliers", C.c_uint32)]
 
 
 class OccupancyParams(C.Structure):
@@ -558,6 +570,14 @@ _SIGNATURES = [
                                          C.POINTER(GraphParams), _dp, _dp, C.POINTER(GraphInfo)]),
     ("sageicp_pipeline_graph_optimize", C.c_int, [C.c_void_p, _dp, C.c_uint32, C.POINTER(GraphEdge), C.c_uint32,
                                                   C.POINTER(GraphParams), _dp, _dp, C.POINTER(GraphInfo)]),
+    ("sageicp_graph_robust_default", None, [C.POINTER(GraphRobust)]),
+    ("sageicp_graph_optimize_robust", C.c_int, [_dp, C.c_uint64, _dp, C.c_uint32, C.POINTER(GraphEdge), C.c_uint32, _dp,
+                                                C.POINTER(GraphParams), _dp, _dp, C.POINTER(GraphInfo), C.POINTER(GraphRobust),
+                                                _dp, _dp, C.POINTER(GraphRobustInfo)]),
+    ("sageicp_pipeline_graph_optimize_robust", C.c_int, [C.c_void_p, _dp, C.c_uint32, C.POINTER(GraphEdge), C.c_uint32,
+                                                         C.POINTER(GraphParams), _dp, _dp, C.POINTER(GraphInfo),
+                                                         C.POINTER(GraphRobust), _dp, _dp, C.POINTER(GraphRobustInfo)]),
+    ("sageicp_graph_info_from_quality", C.c_int, [C.POINTER(Quality), _dp, C.c_double, _dp]),
     ("sageicp_place_tables", C.c_int, [C.POINTER(PlaceParams), _dp, _dp]),
     ("sageicp_place_describe", C.c_int, [_dp, C.c_uint64, C.POINTER(PlaceParams), C.c_void_p, C.c_int]),
     ("sageicp_place_describe_device", C.c_int, [C.POINTER(DeviceFrame), C.POINTER(PlaceParams), C.c_void_p, C.c_void_p]),
@@ -1910,17 +1930,23 @@ class SageICP:
         _check(lib().sageicp_pipeline_closure(self._h, int(i), _p(c), _p(corr), _p(poses), C.byref(info)))
         return corr, poses, info.as_dict()
 
-    def OptimizeGraph(self, closures, odom_info, anchor=0, max_iterations=None, max_halvings=None, step_tol=None, where="auto"):
+    def OptimizeGraph(self, closures, odom_info, anchor=0, max_iterations=None, max_halvings=None, step_tol=None, where="auto",
+                      robust=None):
         """The pipeline's poses optimised under all `closures` at once (graph_edge() records; sageicp_pipeline_graph_optimize,
         DESIGN.md D19).  Returns (corrections (n, 7), corrected poses (n, 7), info dict), as Closure does; the corrections go
-        into CorrectedSessionMap.  The pipeline itself is not touched."""
+        into CorrectedSessionMap.  The pipeline itself is not touched.  robust: as graph_optimize's."""
         n = int(lib().sageicp_pipeline_num_poses(self._h))
         corr, poses, info = np.empty((n, 7)), np.empty((n, 7)), GraphInfo()
         arr, c = _graph_edges(closures)
         O, stride = _graph_odom_info(odom_info, n)
         prm = _graph_params(anchor, max_iterations, max_halvings, step_tol, where)
-        _check(lib().sageicp_pipeline_graph_optimize(self._h, _p(O), stride, arr, c, C.byref(prm), _p(corr), _p(poses), C.byref(info)))
-        return corr, poses, info.as_dict()
+        if robust is None:
+            _check(lib().sageicp_pipeline_graph_optimize(self._h, _p(O), stride, arr, c, C.byref(prm), _p(corr), _p(poses), C.byref(info)))
+            return corr, poses, info.as_dict()
+        rb, chi2, weight, ri = _graph_robust(robust), np.empty(c), np.empty(c), GraphRobustInfo()
+        _check(lib().sageicp_pipeline_graph_optimize_robust(self._h, _p(O), stride, arr, c, C.byref(prm), _p(corr), _p(poses), C.byref(info),
+                                                            C.byref(rb), _p(chi2), _p(weight), C.byref(ri)))
+        return corr, poses, _graph_robust_dict(info, chi2, weight, ri)
 
     def CorrectedSessionMap(self, corrections, which="session", first=0, device=False, dtype=None, out=None, labels_out=None):
         """SessionMap(which)'s rows re-posed by `corrections` (n, 7), one per pose of the pipeline, as Closure returns
@@ -2088,6 +2114,53 @@ def _graph_params(anchor, max_iterations, max_halvings, step_tol, where):
     return prm
 
 
+def _graph_robust(robust):
+    """sageicp_graph_robust from a dict or a tuple (kernel, scale, anneal, anneal_factor, stage_iterations); absent: the defaults"""
+    names = ("kernel", "scale", "anneal", "anneal_factor", "stage_iterations")
+    if isinstance(robust, str):
+        robust = dict(kernel=robust)
+    elif not isinstance(robust, dict):
+        robust = dict(zip(names, tuple(robust)))
+    unknown = set(robust) - set(names)
+    if unknown or "kernel" not in robust:
+        raise ValueError("robust takes kernel, scale, anneal, anneal_factor, stage_iterations")
+    rb = GraphRobust()
+    lib().sageicp_graph_robust_default(C.byref(rb))
+    k = robust["kernel"]
+    if isinstance(k, str) and k not in GRAPH_KERNEL:
+        raise ValueError('robust kernel is "huber", "cauchy" or "gm"')
+    rb.kernel = GRAPH_KERNEL[k] if isinstance(k, str) else int(k)
+    if robust.get("scale") is not None:
+        rb.scale = float(robust["scale"])
+    if robust.get("anneal") is not None:
+        rb.anneal = int(robust["anneal"])
+    if robust.get("anneal_factor") is not None:
+        rb.anneal_factor = float(robust["anneal_factor"])
+    if robust.get("stage_iterations") is not None:
+        rb.stage_iterations = int(robust["stage_iterations"])
+    return rb
+
+
+def _graph_robust_dict(info, chi2, weight, ri):
+    d = info.as_dict()
+    d.update(closure_chi2=chi2, closure_weight=weight, stages=int(ri.stages), outliers=int(ri.outliers), scale2_first=ri.scale2_first)
+    return d
+
+
+def graph_edge_info(quality, closed, gain=1.0):
+    """The 6x6 information of the closure edge graph_edge() makes of `closed`, from the Quality report at `closed` (what
+    Relocalize returns): gain * Ad(closed)^T (JTJ / s2) Ad(closed), symmetric to the bit (sageicp_graph_info_from_quality;
+    DESIGN.md D20).  gain is the caller's noise model: ICP covariances are overconfident."""
+    if not isinstance(quality, Quality):
+        raise ValueError("graph_edge_info takes the Quality record of Relocalize / registration_quality")
+    c = np.ascontiguousarray(closed, dtype=np.float64).reshape(-1)
+    if c.size != 7:
+        raise ValueError("closed is (qx, qy, qz, qw, tx, ty, tz)")
+    out = np.empty((6, 6))
+    _check(lib().sageicp_graph_info_from_quality(C.byref(quality), _p(c), float(gain), _p(out)))
+    return out
+
+
 def graph_edge(poses, i, j, closed, info):
     """The closure edge of "pose j really is at `closed`, in pose i's frame of the world" (closure_corrections' argument):
     a GraphEdge with a = i, b = j, z = poses[i]^-1 * closed and the 6x6 information `info` (sageicp_graph_edge_from_closed)"""
@@ -2118,12 +2191,14 @@ def graph_cost(poses, closures, odom_info, at=None, per_edge=False):
 
 
 def graph_optimize(poses, closures, odom_info, initial=None, anchor=0, max_iterations=None, max_halvings=None, step_tol=None,
-                   where="auto", return_info=False):
+                   where="auto", return_info=False, robust=None):
     """`poses` (n, 7) optimised under its own odometry (information `odom_info`) and all `closures` (graph_edge()) at once:
     Gauss-Newton on SE(3) with exact Jacobians, pose `anchor` fixed (sageicp_graph_optimize).  Returns
     (corrections (n, 7), optimised poses (n, 7)); the corrections are closure_corrections' kind.  where: "auto", "host" or
     "device".  return_info=True adds the info dict (cost_initial, cost_final, grad_max, step_last, max_shift, iterations,
-    halvings, status, where)."""
+    halvings, status, where).  robust: a robust kernel on the closures (sageicp_graph_optimize_robust), a
+    dict or tuple of kernel="huber"|"cauchy"|"gm", scale, anneal, anneal_factor, stage_iterations; the info dict then gains
+    closure_chi2, closure_weight (below 0.5: drop the match), stages, outliers and scale2_first."""
     P = np.ascontiguousarray(poses, dtype=np.float64)
     if P.ndim != 2 or P.shape[1] != 7:
         raise ValueError("graph_optimize takes poses (n, 7)")
@@ -2134,6 +2209,11 @@ def graph_optimize(poses, closures, odom_info, initial=None, anchor=0, max_itera
     O, stride = _graph_odom_info(odom_info, P.shape[0])
     prm = _graph_params(anchor, max_iterations, max_halvings, step_tol, where)
     corr, out, info = np.empty_like(P), np.empty_like(P), GraphInfo()
+    if robust is not None:
+        rb, chi2, weight, ri = _graph_robust(robust), np.empty(c), np.empty(c), GraphRobustInfo()
+        _check(lib().sageicp_graph_optimize_robust(_p(P), P.shape[0], _p(O), stride, arr, c, None if X0 is None else _p(X0), C.byref(prm),
+                                                   _p(out), _p(corr), C.byref(info), C.byref(rb), _p(chi2), _p(weight), C.byref(ri)))
+        return (corr, out, _graph_robust_dict(info, chi2, weight, ri)) if return_info else (corr, out)
     _check(lib().sageicp_graph_optimize(_p(P), P.shape[0], _p(O), stride, arr, c, None if X0 is None else _p(X0), C.byref(prm),
                                         _p(out), _p(corr), C.byref(info)))
     return (corr, out, info.as_dict()) if return_info else (corr, out)

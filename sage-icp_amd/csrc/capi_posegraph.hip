@@ -9,6 +9,12 @@
 // summed edge by edge.  Waits of the device path: one per outer iteration (Gm and, at the first, F), with closures one per
 // refinement round (U^T T^-1 of the residual, for C^-1 on the host), one per backtracking trial (F and |delta|_inf), one
 // at the end (the gradient and the poses).
+//
+// Robust kernels on the closures: Problem::kernel and the solver's scale make linearize() / k_pg_lin<true>
+// scale a closure's A, B, w by sqrt(rho') and the costs take rho(s); everything after the linearisation is unchanged.
+// The scale continuation runs gn_stage() once per stage; its schedule comes from the closures' terms at the start,
+// evaluated here on the host, so neither path waits for it.  An annealed device call waits once more, for the final
+// kernel's F at the start.
 #include "capi_internal.h"
 #include "posegraph.h"
 
@@ -21,6 +27,7 @@ struct Problem {
     std::vector<double> zinv;        // E x 7
     std::vector<double> L;           // odometry (1 or n - 1), then the closures: 36 each, row-major lower
     std::vector<uint32_t> ca, cb;
+    uint32_t kernel = 0;             // the closures' robust kernel (posegraph.h pg_rho); its scale is the solver's, per stage
     const double *l_of(uint32_t e) const {
         if (e < n - 1u) return L.data() + static_cast<size_t>(l_stride) * e;
         return L.data() + (l_stride ? size_t(36) * (n - 1u) : size_t(36)) + size_t(36) * (e - (n - 1u));
@@ -98,13 +105,15 @@ int make_problem(const double *poses, uint64_t n, const double *odom_info, uint3
     return SAGEICP_OK;
 }
 
-double cost_at(const Problem &P, const double *x, double *per_edge) {
+// kernel 0: the plain F; otherwise the closures' terms under pg_rho(kernel, c2, .)
+double cost_at(const Problem &P, const double *x, double *per_edge, uint32_t kernel = 0, double c2 = 0.0) {
     double F = 0.0;
     for (uint32_t e = 0; e < P.E; ++e) {
         uint32_t a, b;
         P.ends(e, a, b);
-        const double v = pg_edge_cost(P.zinv.data() + 7 * static_cast<size_t>(e), x + 7 * static_cast<size_t>(a),
-                                      x + 7 * static_cast<size_t>(b), P.l_of(e));
+        double v = pg_edge_cost(P.zinv.data() + 7 * static_cast<size_t>(e), x + 7 * static_cast<size_t>(a),
+                                x + 7 * static_cast<size_t>(b), P.l_of(e));
+        if (kernel && e >= P.n - 1u) v = pg_rho(kernel, c2, v);
         if (per_edge) per_edge[e] = v;
         F += v;
     }
@@ -183,10 +192,16 @@ public:
             if (k == P.anchor) std::memcpy(o, xk, 7 * sizeof(double));
             else pg_retract(xk, delta.data() + 6 * static_cast<size_t>(pg_free_of(k, P.anchor)), s, o);
         }
-        F = cost_at(P, xt.data(), nullptr);
+        F = cost_at(P, xt.data(), nullptr, P.kernel, c2);
         return SAGEICP_OK;
     }
     void accept() { x.swap(xt); }
+    void set_scale2(double v) { c2 = v; }
+    // F at x under the current scale, nothing else touched
+    int cost_here(double &F) {
+        F = cost_at(P, x.data(), nullptr, P.kernel, c2);
+        return SAGEICP_OK;
+    }
     int finish(double &grad_max, double *poses_out) {
         linearize();
         assemble();
@@ -208,7 +223,8 @@ private:
             P.ends(e, a, b);
             pg_linearize(P.zinv.data() + 7 * static_cast<size_t>(e), x.data() + 7 * static_cast<size_t>(a),
                          x.data() + 7 * static_cast<size_t>(b), P.l_of(e), lin[e]);
-            F += pg_dot6(lin[e].w, lin[e].w);
+            if (P.kernel && e >= P.n - 1u) F += pg_robustify(P.kernel, c2, lin[e]);
+            else F += pg_dot6(lin[e].w, lin[e].w);
         }
         return F;
     }
@@ -328,6 +344,7 @@ private:
     }
 
     const Problem &P;
+    double c2 = 0.0;
     std::vector<double> x, xt, g, delta, rhs, X, Gm, Cm, z;
     std::vector<PgEdgeLin> lin;
     PgHostChain T;
@@ -365,7 +382,7 @@ public:
         }
         // the reduced levels' D and E, and the unused halves of DP and Q, are written before they are read; X's levels
         // likewise (posegraph.hip)
-        G = PgGraph{P.n, P.c, P.anchor, P.m, P.E, d_zinv.data(), d_L.data(), P.l_stride, d_ca.data(), d_cb.data()};
+        G = PgGraph{P.n, P.c, P.anchor, P.m, P.E, d_zinv.data(), d_L.data(), P.l_stride, d_ca.data(), d_cb.data(), P.kernel, 0.0};
         HIPCHK(hipMemsetAsync(d_bad.data(), 0, sizeof(uint32_t), s));
         S = PgSystem{d_lin.data(), d_g.data(), d_D.data(), d_E.data(), d_DP.data(), d_Q.data(), lv.nodes, d_bad.data()};
         return SAGEICP_OK;
@@ -429,6 +446,16 @@ public:
         return SAGEICP_OK;
     }
     void accept() { std::swap(d_x, d_xt); }
+    void set_scale2(double v) { G.c2 = v; }
+    // F at x under the current scale: one wait, once per annealed call
+    int cost_here(double &F) {
+        HIPCHK(pg_cost(G, d_x.data(), d_ecost.data(), s));
+        HIPCHK(pg_reduce(d_ecost.data(), P.E, false, d_slabs.data(), d_out.data(), s));
+        HIPCHK(hipMemcpyAsync(h_out.data(), d_out.data(), sizeof(double), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        F = h_out.data()[0];
+        return SAGEICP_OK;
+    }
     int finish(double &grad_max, double *poses_out) {
         HIPCHK(pg_linearize_all(G, d_x.data(), S, d_ecost.data(), s));
         HIPCHK(pg_assemble(G, S, s));
@@ -457,16 +484,19 @@ private:
 };
 
 // ---- Gauss-Newton with backtracking, over either path -------------------------------------------------------------------------
+// One stage: at most max_iterations iterations at the solver's current scale.  iterations, halvings and step_last of `info`
+// go on counting; F_first is F where the stage began, F the cost where it ended, status as sageicp_graph_info's.
 template <class Solver>
-int gauss_newton(Solver &sv, uint32_t edges, const sageicp_graph_params &prm, sageicp_graph_info &info, double *poses_tmp) {
-    double F = 0.0;
-    info.status = 2;
-    for (uint32_t it = 0; it < prm.max_iterations; ++it) {
+int gn_stage(Solver &sv, uint32_t edges, uint32_t max_iterations, const sageicp_graph_params &prm, sageicp_graph_info &info,
+             double &F_first, double &F, uint32_t &status) {
+    F = 0.0;
+    status = 2;
+    for (uint32_t it = 0; it < max_iterations; ++it) {
         double F_lin = 0.0;
         if (int rc = sv.direction(F_lin)) return rc;
         if (it == 0) {
             if (!std::isfinite(F_lin)) return fail(SAGEICP_ERR_INVALID, "graph: the cost at the start is not finite");
-            F = info.cost_initial = F_lin;
+            F = F_first = F_lin;
         }
         bool accepted = false;
         double step = 1.0, dmax = 0.0;
@@ -480,7 +510,7 @@ int gauss_newton(Solver &sv, uint32_t edges, const sageicp_graph_params &prm, sa
             // alone, whether such a step was taken, halved or refused (status 1) was decided by rounding.  (Never above the
             // start: cost_final <= cost_initial stays a property of every return.)
             const double noise = (static_cast<double>(edges) + 64.0) * 0x1p-52 * F;
-            if (F_try < F || (h == 0 && F_try < F + noise && F_try <= info.cost_initial)) {
+            if (F_try < F || (h == 0 && F_try < F + noise && F_try <= F_first)) {
                 sv.accept();
                 F = F_try;
                 accepted = true;
@@ -489,31 +519,89 @@ int gauss_newton(Solver &sv, uint32_t edges, const sageicp_graph_params &prm, sa
             ++info.halvings;
         }
         if (!accepted) {
-            info.status = 1;
+            status = 1;
             break;
         }
         ++info.iterations;
         info.step_last = step * dmax;
         if (info.step_last <= prm.step_tol) {
-            info.status = 0;
+            status = 0;
             break;
         }
     }
-    if (prm.max_iterations == 0) {                       // (nothing linearised: F is asked for on its own)
+    if (max_iterations == 0) {                           // (nothing linearised: F is asked for on its own)
         double F_lin = 0.0;
         if (int rc = sv.direction(F_lin)) return rc;
-        F = info.cost_initial = F_lin;
+        F = F_first = F_lin;
     }
+    return SAGEICP_OK;
+}
+
+// What a robust call adds to the problem (sageicp_graph_robust, checked) and what it reports
+struct Robust {
+    uint32_t kernel = 0;
+    bool anneal = false;
+    double c2 = 0.0, factor = 2.0;
+    uint32_t stage_iterations = 3;
+    double s0 = 0.0;                 // the largest closure term at the start (host, fp64): it alone fixes the schedule
+    double c2_first = 0.0;
+    uint32_t stages = 1;
+};
+constexpr uint32_t kPgMaxStages = 1024;
+
+// The stages c2 f^m, ..., c2 f, c2 (m the smallest count with c2 f^m >= s0; one stage without anneal), each but the last
+// under stage_iterations, the last under max_iterations.  cost_initial and cost_final are the final scale's F.
+template <class Solver>
+int gauss_newton(Solver &sv, uint32_t edges, const sageicp_graph_params &prm, Robust &rb, sageicp_graph_info &info, double *poses_tmp) {
+    double F_first = 0.0, F = 0.0;
+    if (!rb.kernel) {
+        if (int rc = gn_stage(sv, edges, prm.max_iterations, prm, info, F_first, F, info.status)) return rc;
+        info.cost_initial = F_first;
+        info.cost_final = F;
+        return sv.finish(info.grad_max, poses_tmp);
+    }
+    std::vector<double> scale2(1, rb.c2);
+    if (rb.anneal)
+        while (scale2.back() < rb.s0) scale2.push_back(scale2.back() * rb.factor);
+    rb.stages = static_cast<uint32_t>(scale2.size());
+    rb.c2_first = scale2.back();
+    if (rb.stages > 1u) {
+        sv.set_scale2(rb.c2);
+        if (int rc = sv.cost_here(info.cost_initial)) return rc;
+        if (!std::isfinite(info.cost_initial)) return fail(SAGEICP_ERR_INVALID, "graph: the cost at the start is not finite");
+    }
+    for (uint32_t st = rb.stages; st-- > 0;) {
+        sv.set_scale2(scale2[st]);
+        if (int rc = gn_stage(sv, edges, st ? rb.stage_iterations : prm.max_iterations, prm, info, F_first, F, info.status)) return rc;
+    }
+    if (rb.stages == 1u) info.cost_initial = F_first;
     info.cost_final = F;
     return sv.finish(info.grad_max, poses_tmp);
 }
 
 int optimize(const double *poses, uint64_t n, const double *odom_info, uint32_t stride, const sageicp_graph_edge *cl, uint32_t c,
-             const double *initial, const sageicp_graph_params *params, double *poses_out, double *corr_out, sageicp_graph_info *info_out) {
+             const double *initial, const sageicp_graph_params *params, double *poses_out, double *corr_out, sageicp_graph_info *info_out,
+             const sageicp_graph_robust *robust = nullptr, double *chi2_out = nullptr, double *weight_out = nullptr,
+             sageicp_graph_robust_info *rinfo_out = nullptr) {
     sageicp_graph_params prm;
     sageicp_graph_params_default(&prm);
     if (params) prm = *params;
     if (!poses_out) return fail(SAGEICP_ERR_INVALID, "graph: null argument");
+    Robust rb;
+    if (robust) {
+        if (robust->kernel > 3u) return fail(SAGEICP_ERR_INVALID, "graph: robust kernel is 0 (none), 1 (Huber), 2 (Cauchy) or 3 (Geman-McClure)");
+        if (robust->anneal > 1u) return fail(SAGEICP_ERR_INVALID, "graph: robust anneal is 0 or 1");
+        if (!std::isfinite(robust->scale) || !(robust->scale > 0.0)) return fail(SAGEICP_ERR_INVALID, "graph: robust scale is not finite and above 0");
+        if (!std::isfinite(robust->anneal_factor) || !(robust->anneal_factor > 1.0))
+            return fail(SAGEICP_ERR_INVALID, "graph: robust anneal_factor is not finite and above 1");
+        if (robust->stage_iterations == 0u) return fail(SAGEICP_ERR_INVALID, "graph: robust stage_iterations is 0");
+        rb.kernel = robust->kernel;
+        rb.anneal = robust->anneal == 1u;
+        rb.c2 = rb.c2_first = robust->scale * robust->scale;
+        rb.factor = robust->anneal_factor;
+        rb.stage_iterations = robust->stage_iterations;
+        if (!std::isfinite(rb.c2) || !(rb.c2 > 0.0)) return fail(SAGEICP_ERR_INVALID, "graph: the square of robust scale is not finite and above 0");
+    }
     if (prm.where > 2u) return fail(SAGEICP_ERR_INVALID, "graph: where is 0 (auto), 1 (host) or 2 (device)");
     if (!(prm.step_tol >= 0.0)) return fail(SAGEICP_ERR_INVALID, "graph: step_tol is negative or not a number");
     Problem P;
@@ -521,6 +609,17 @@ int optimize(const double *poses, uint64_t n, const double *odom_info, uint32_t 
     if (initial)
         if (int rc = check_poses(initial, n, "initial")) return rc;
     const double *start = initial ? initial : poses;
+    P.kernel = rb.kernel;
+    if (rb.kernel && rb.anneal) {
+        for (uint32_t e = P.n - 1u; e < P.E; ++e)
+            rb.s0 = std::max(rb.s0, pg_edge_cost(P.zinv.data() + 7 * static_cast<size_t>(e), start + 7 * static_cast<size_t>(P.ca[e - (P.n - 1u)]),
+                                                 start + 7 * static_cast<size_t>(P.cb[e - (P.n - 1u)]), P.l_of(e)));
+        if (!std::isfinite(rb.s0)) return fail(SAGEICP_ERR_INVALID, "graph: the cost at the start is not finite");
+        double v = rb.c2;
+        uint32_t m = 1;
+        for (; v < rb.s0; v *= rb.factor)
+            if (++m > kPgMaxStages) return fail(SAGEICP_ERR_CAPACITY, "graph: the anneal needs more than 1024 stages");
+    }
     uint32_t where = prm.where;
     if (where == 2u) {
         if (int rc = require_device()) return rc;
@@ -535,11 +634,11 @@ int optimize(const double *poses, uint64_t n, const double *odom_info, uint32_t 
     if (where == 2u) {
         DeviceSolver sv(P);
         rc = sv.init(start);
-        if (!rc) rc = gauss_newton(sv, P.E, prm, info, out.data());
+        if (!rc) rc = gauss_newton(sv, P.E, prm, rb, info, out.data());
     } else {
         HostSolver sv(P);
         rc = sv.init(start);
-        if (!rc) rc = gauss_newton(sv, P.E, prm, info, out.data());
+        if (!rc) rc = gauss_newton(sv, P.E, prm, rb, info, out.data());
     }
     if (rc) return rc;
     if (!finite_n(out.data(), out.size())) return fail(SAGEICP_ERR_INVALID, "graph: the optimum is not finite");
@@ -565,8 +664,22 @@ int optimize(const double *poses, uint64_t n, const double *odom_info, uint32_t 
         }
     }
     info.max_shift = shift;
+    // the closures' raw terms at poses_out and their weights under the final scale (host, fp64: sageicp_graph_cost's terms)
+    sageicp_graph_robust_info ri{};
+    ri.scale2_first = rb.c2_first;
+    ri.stages = rb.stages;
+    for (uint32_t ce = 0; ce < P.c; ++ce) {
+        const uint32_t e = P.n - 1u + ce;
+        const double sv = pg_edge_cost(P.zinv.data() + 7 * static_cast<size_t>(e), out.data() + 7 * static_cast<size_t>(P.ca[ce]),
+                                       out.data() + 7 * static_cast<size_t>(P.cb[ce]), P.l_of(e));
+        const double w = pg_rho_weight(rb.kernel, rb.c2, sv);
+        if (w < 0.5) ++ri.outliers;
+        if (chi2_out) chi2_out[ce] = sv;
+        if (weight_out) weight_out[ce] = w;
+    }
     std::memmove(poses_out, out.data(), out.size() * sizeof(double));
     if (info_out) *info_out = info;
+    if (rinfo_out) *rinfo_out = ri;
     return SAGEICP_OK;
 }
 
@@ -626,14 +739,87 @@ int sageicp_graph_optimize(const double *poses, uint64_t n, const double *odom_i
 int sageicp_pipeline_graph_optimize(const sageicp_pipeline *p, const double *odom_info, uint32_t odom_info_stride,
                                     const sageicp_graph_edge *closures, uint32_t c, const sageicp_graph_params *params,
                                     double *corrections_out, double *poses_out, sageicp_graph_info *info) {
+    return sageicp_pipeline_graph_optimize_robust(p, odom_info, odom_info_stride, closures, c, params, corrections_out, poses_out, info,
+                                                  nullptr, nullptr, nullptr, nullptr);
+}
+
+void sageicp_graph_robust_default(sageicp_graph_robust *r) {
+    if (!r) return;
+    sageicp_graph_robust d{};
+    d.kernel = SAGEICP_GRAPH_KERNEL_NONE;
+    d.anneal = 0;
+    d.scale = std::sqrt(16.81);
+    d.anneal_factor = 2.0;
+    d.stage_iterations = 3;
+    *r = d;
+}
+
+int sageicp_graph_optimize_robust(const double *poses, uint64_t n, const double *odom_info, uint32_t odom_info_stride,
+                                  const sageicp_graph_edge *closures, uint32_t c, const double *initial, const sageicp_graph_params *params,
+                                  double *poses_out, double *corrections_out, sageicp_graph_info *info, const sageicp_graph_robust *robust,
+                                  double *closure_chi2_out, double *closure_weight_out, sageicp_graph_robust_info *rinfo) {
+    return optimize(poses, n, odom_info, odom_info_stride, closures, c, initial, params, poses_out, corrections_out, info, robust,
+                    closure_chi2_out, closure_weight_out, rinfo);
+}
+
+int sageicp_pipeline_graph_optimize_robust(const sageicp_pipeline *p, const double *odom_info, uint32_t odom_info_stride,
+                                           const sageicp_graph_edge *closures, uint32_t c, const sageicp_graph_params *params,
+                                           double *corrections_out, double *poses_out, sageicp_graph_info *info,
+                                           const sageicp_graph_robust *robust, double *closure_chi2_out, double *closure_weight_out,
+                                           sageicp_graph_robust_info *rinfo) {
     if (!p || !corrections_out) return fail(SAGEICP_ERR_INVALID, "sageicp_pipeline_graph_optimize: null argument");
     const uint64_t n = sageicp_pipeline_num_poses(p);
     std::vector<double> poses(7 * static_cast<size_t>(n)), out(7 * static_cast<size_t>(n));
     for (uint64_t k = 0; k < n; ++k)
         if (int rc = sageicp_pipeline_pose(p, k, poses.data() + 7 * k)) return rc;
-    if (int rc = optimize(poses.data(), n, odom_info, odom_info_stride, closures, c, nullptr, params, out.data(), corrections_out, info))
+    if (int rc = optimize(poses.data(), n, odom_info, odom_info_stride, closures, c, nullptr, params, out.data(), corrections_out, info,
+                          robust, closure_chi2_out, closure_weight_out, rinfo))
         return rc;
     if (poses_out) std::memcpy(poses_out, out.data(), out.size() * sizeof(double));
+    return SAGEICP_OK;
+}
+
+// ---- an edge's information from a quality report (host, fp64) -------------------------------------------------
+int sageicp_graph_info_from_quality(const sageicp_quality *q, const double closed[7], double gain, double info_out[36]) {
+    if (!q || !closed || !info_out) return fail(SAGEICP_ERR_INVALID, "graph info: null argument");
+    if (!q->covariance_valid) return fail(SAGEICP_ERR_INVALID, "graph info: the report has no valid covariance");
+    if (!finite_n(q->JTJ, 36) || !std::isfinite(q->sum_w_r2) || !finite_n(closed, 7) || !std::isfinite(gain))
+        return fail(SAGEICP_ERR_INVALID, "graph info: an input is not finite");
+    if (zero_quat(closed)) return fail(SAGEICP_ERR_INVALID, "graph info: the quaternion of closed is 0");
+    if (!(gain > 0.0)) return fail(SAGEICP_ERR_INVALID, "graph info: gain is not above 0");
+    const double s2 = q->sum_w_r2 / (3.0 * static_cast<double>(q->n_pairs) - 6.0);
+    if (!(s2 > 0.0) || !std::isfinite(s2)) return fail(SAGEICP_ERR_INVALID, "graph info: s2 = sum_w_r2 / (3 n_pairs - 6) is not above 0");
+    // Ad(closed) = [[R, hat(t) R], [0, R]] in (upsilon, omega): the report's left tangent xi from the edge's right one, xi = Ad eta
+    const double qn = std::sqrt((closed[0] * closed[0] + closed[1] * closed[1]) + (closed[2] * closed[2] + closed[3] * closed[3]));
+    const double qu[4] = {closed[0] / qn, closed[1] / qn, closed[2] / qn, closed[3] / qn};
+    double Rf[9], R[3][3], T[3][3], TR[3][3], Ad[6][6], M[6][6], W[6][6], O[6][6];
+    quat_to_mat(qu, Rf);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) R[i][j] = Rf[3 * i + j];
+    const double t[3] = {closed[4], closed[5], closed[6]};
+    pg_hat(t, T);
+    pg_mul3(T, R, TR);
+    pg_zero(Ad);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            Ad[i][j] = R[i][j];
+            Ad[i][j + 3] = TR[i][j];
+            Ad[i + 3][j + 3] = R[i][j];
+        }
+    const double k = gain / s2;
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) M[i][j] = k * q->JTJ[6 * i + j];
+    pg_zero(W);
+    pg_zero(O);
+    pg_add_ab(M, Ad, 1.0, W);
+    pg_add_atb(Ad, W, 1.0, O);
+    double sym[36], L[36];
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) sym[6 * i + j] = i <= j ? 0.5 * (O[i][j] + O[j][i]) : 0.0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < i; ++j) sym[6 * i + j] = sym[6 * j + i];
+    if (!info_factor(sym, L)) return fail(SAGEICP_ERR_INVALID, "graph info: the result is not finite and positive definite (register in a local frame)");
+    std::memcpy(info_out, sym, sizeof(sym));
     return SAGEICP_OK;
 }
 

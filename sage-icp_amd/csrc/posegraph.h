@@ -286,6 +286,26 @@ SAGE_HD inline double pg_edge_cost(const double Zinv[7], const double xa[7], con
     return pg_dot6(w, w);
 }
 
+// ---- robust kernels on closure edges -----------------------------------------------------------------------
+// s = r^T Omega r of a closure, c2 = scale^2.  rho(s) replaces s in F; rho'(s) is the edge's IRLS weight: A, B, w scaled
+// by sqrt(rho') make g the exact gradient of F and H = sum rho' J^T J positive definite (no second-order term).
+// 0 none, 1 Huber, 2 Cauchy, 3 Geman-McClure (sageicp.h's SAGEICP_GRAPH_KERNEL_*).
+SAGE_HD inline double pg_rho(uint32_t kernel, double c2, double s) {
+    if (kernel == 1u) return s <= c2 ? s : 2.0 * sqrt(c2 * s) - c2;
+    if (kernel == 2u) return c2 * log1p(s / c2);
+    if (kernel == 3u) return c2 * s / (c2 + s);
+    return s;
+}
+SAGE_HD inline double pg_rho_weight(uint32_t kernel, double c2, double s) {
+    if (kernel == 1u) return s <= c2 ? 1.0 : sqrt(c2 / s);
+    if (kernel == 2u) return 1.0 / (1.0 + s / c2);
+    if (kernel == 3u) {
+        const double t = c2 / (c2 + s);
+        return t * t;
+    }
+    return 1.0;
+}
+
 // The whitened linearisation of an edge: A = L^T dr/d delta_a, B = L^T dr/d delta_b, w = L^T r.  Its terms of
 // H = sum J^T Omega J and g = sum J^T Omega r are then A^T A, A^T B, B^T B and A^T w, B^T w.
 struct PgEdgeLin {
@@ -336,6 +356,22 @@ SAGE_HD inline void pg_linearize(const double Zinv[7], const double xa[7], const
             o.A[i][j] = va;
             o.B[i][j] = vb;
         }
+}
+
+// a closure's linearisation under the kernel: scaled by sqrt(rho'(s)), s = |w|^2 before; returns rho(s)
+SAGE_HD inline double pg_robustify(uint32_t kernel, double c2, PgEdgeLin &o) {
+    const double s = pg_dot6(o.w, o.w);
+    const double sw = sqrt(pg_rho_weight(kernel, c2, s));
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            o.A[i][j] *= sw;
+            o.B[i][j] *= sw;
+        }
+        o.w[i] *= sw;
+    }
+    return pg_rho(kernel, c2, s);
 }
 
 // t = A d_a + B d_b + w: the edge's linear model of its whitened residual under the steps of its two poses
@@ -494,6 +530,8 @@ struct PgGraph {
     const double *L;                 // Cholesky factors: odometry (1 or n - 1, by l_stride) then the closures
     uint32_t l_stride;               // 0 or 36
     const uint32_t *ca, *cb;         // c: the closures' vertices
+    uint32_t kernel;                 // the closures' robust kernel (pg_rho); 0: the plain kernels are launched
+    double c2;                       // its scale^2 at the current stage
 };
 struct PgSystem {
     double *lin;                     // 78 x E

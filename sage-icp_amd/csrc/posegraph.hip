@@ -1,6 +1,6 @@
 // The device side of the pose-graph optimiser (gfx950) — see posegraph.h and DESIGN.md D19.
 //
-//   linearise   k_pg_lin      a lane per edge: A, B, w and the edge's cost
+//   linearise   k_pg_lin      a lane per edge: A, B, w and the edge's cost; <true>: the closures under a robust kernel (D20)
 //   assemble    k_pg_asm      a lane per free vertex gathers its two odometry edges and, in the caller's order, its closures
 //   factor      k_pg_inv, k_pg_red    per level of the block cyclic reduction: invert the even diagonals, reduce onto the odd
 //   apply       k_pg_fwd, k_pg_bwd    per level, a lane per (node, column) of a chunk of right-hand sides
@@ -65,6 +65,8 @@ __device__ __forceinline__ void edge_of(const PgGraph &G, uint32_t e, uint32_t &
     for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x; i < (count);            \
          i += static_cast<uint64_t>(gridDim.x) * 256)
 
+// Robust: the closures (e >= n - 1) under G.kernel at G.c2 (posegraph.h pg_robustify); the plain kernels hold none of it
+template <bool Robust>
 __global__ __launch_bounds__(256) void k_pg_lin(PgGraph G, const double *__restrict__ x, double *__restrict__ lin,
                                                 double *__restrict__ edge_cost) {
     PG_STRIDE(e64, G.E) {
@@ -74,22 +76,27 @@ __global__ __launch_bounds__(256) void k_pg_lin(PgGraph G, const double *__restr
         edge_of(G, e, a, b, L);
         PgEdgeLin o;
         pg_linearize(G.zinv + 7 * static_cast<size_t>(e), x + 7 * static_cast<size_t>(a), x + 7 * static_cast<size_t>(b), L, o);
+        double cost;
+        if (Robust && e >= G.n - 1u) cost = pg_robustify(G.kernel, G.c2, o);
+        else cost = pg_dot6(o.w, o.w);
         st36(lin, G.E, e, o.A);
         st36(lin + static_cast<size_t>(36) * G.E, G.E, e, o.B);
 #pragma unroll
         for (int i = 0; i < 6; ++i) lin[static_cast<size_t>(72 + i) * G.E + e] = o.w[i];
-        edge_cost[e] = pg_dot6(o.w, o.w);
+        edge_cost[e] = cost;
     }
 }
 
+template <bool Robust>
 __global__ __launch_bounds__(256) void k_pg_cost(PgGraph G, const double *__restrict__ x, double *__restrict__ edge_cost) {
     PG_STRIDE(e64, G.E) {
         const uint32_t e = static_cast<uint32_t>(e64);
         uint32_t a, b;
         const double *L;
         edge_of(G, e, a, b, L);
-        edge_cost[e] = pg_edge_cost(G.zinv + 7 * static_cast<size_t>(e), x + 7 * static_cast<size_t>(a),
-                                    x + 7 * static_cast<size_t>(b), L);
+        const double cost = pg_edge_cost(G.zinv + 7 * static_cast<size_t>(e), x + 7 * static_cast<size_t>(a),
+                                         x + 7 * static_cast<size_t>(b), L);
+        edge_cost[e] = (Robust && e >= G.n - 1u) ? pg_rho(G.kernel, G.c2, cost) : cost;
     }
 }
 
@@ -421,13 +428,15 @@ inline unsigned grid_for(uint64_t items) {
 
 hipError_t pg_linearize_all(const PgGraph &G, const double *x, const PgSystem &S, double *edge_cost, hipStream_t s) {
     if (!G.E) return hipSuccess;
-    hipLaunchKernelGGL(k_pg_lin, dim3(grid_for(G.E)), dim3(256), 0, s, G, x, S.lin, edge_cost);
+    if (G.kernel) hipLaunchKernelGGL(k_pg_lin<true>, dim3(grid_for(G.E)), dim3(256), 0, s, G, x, S.lin, edge_cost);
+    else hipLaunchKernelGGL(k_pg_lin<false>, dim3(grid_for(G.E)), dim3(256), 0, s, G, x, S.lin, edge_cost);
     return hipGetLastError();
 }
 
 hipError_t pg_cost(const PgGraph &G, const double *x, double *edge_cost, hipStream_t s) {
     if (!G.E) return hipSuccess;
-    hipLaunchKernelGGL(k_pg_cost, dim3(grid_for(G.E)), dim3(256), 0, s, G, x, edge_cost);
+    if (G.kernel) hipLaunchKernelGGL(k_pg_cost<true>, dim3(grid_for(G.E)), dim3(256), 0, s, G, x, edge_cost);
+    else hipLaunchKernelGGL(k_pg_cost<false>, dim3(grid_for(G.E)), dim3(256), 0, s, G, x, edge_cost);
     return hipGetLastError();
 }
 
