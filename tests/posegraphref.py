@@ -348,17 +348,23 @@ def angles(G, x):
 _STEPPED = {}
 
 
-def step_measured(key, poses, odom_info, closures, anchor, initial, max_halvings):
+def step_measured(key, poses, odom_info, closures, anchor, initial, max_halvings, kernel=None, c2=None):
     """One Gauss-Newton iteration from `initial`, in np.longdouble, and the fp64 restatement's distance from it — computed
-    once per key.  dict(d: the longdouble step (n, 6); h: the halvings the longdouble run takes, the first s = 2^-h with
+    once per key.  kernel, c2: the graph at both precisions is robustref.RobustGraph under that kernel at that c^2 (the key
+    then holds both); everything below follows from its per_edge() and jacobians().  dict(d: the longdouble step (n, 6); h: the halvings the longdouble run takes, the first s = 2^-h with
     F(x0 exp(s d)) < F(x0); s; x1 = retract(x0, s d); F0, F1; d_ref = distance(x1, the fp64 graph's own x1 at the same h);
     rho_ref: the residual of the fp64 graph's step under the longdouble graph; rho: the longdouble step's own; cond of H;
     grad0, grad1: the longdouble gradients at x0 and x1; theta, qw: angles(); deg: the most edges at one vertex).
     Asserted here, on the restatement alone, as conditions on the scene: h <= max_halvings, and at every trial up to and
     including the accepted one |F_trial - F0| > 1e-6 F0, so that no path's rounding decides h."""
+    make = Graph
+    if kernel is not None:
+        import robustref                                             # (it imports this module)
+        key = (key, kernel, float(c2))
+        make = lambda *a: robustref.RobustGraph(*a, kernel=kernel, c2=float(c2))
     if key not in _STEPPED:
-        Gl = Graph(poses, odom_info, closures, np.longdouble, anchor)
-        G64 = Graph(poses, odom_info, closures, np.float64, anchor)
+        Gl = make(poses, odom_info, closures, np.longdouble, anchor)
+        G64 = make(poses, odom_info, closures, np.float64, anchor)
         x0 = np.asarray(initial, dtype=np.float64)
         d, H = Gl.step_exact(x0)
         F0 = Gl.cost(x0)

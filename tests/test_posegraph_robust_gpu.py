@@ -139,6 +139,15 @@ def test_kernel_none_is_the_plain_device_path(gpu_sage):
         assert (none[2]["closure_weight"] == 1.0).all() and none[2]["stages"] == 1 and none[2]["outliers"] == 0
 
 
+def test_the_verdict_at_a_weight_of_exactly_a_half(gpu_sage):
+    """the decision is the host's on either path, from the same numbers (test_posegraph_robust_host.py)"""
+    rs.check_the_verdict_at_a_weight_of_a_half(gpu_sage, "device")
+
+
+def test_the_schedule_at_a_power_of_the_factor(gpu_sage):
+    rs.check_the_schedule_at_a_power_of_the_factor(gpu_sage, "device")
+
+
 def test_the_same_bytes_on_two_runs(gpu_sage):
     s = rs.scene("hard")
     a, b = rs.optimize(gpu_sage, s, "gm", True, where="device"), rs.optimize(gpu_sage, s, "gm", True, where="device")

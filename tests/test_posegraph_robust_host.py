@@ -217,17 +217,7 @@ def test_a_closure_met_exactly_under_huber(sage):
 def test_a_closure_exactly_at_the_scale_under_huber(sage):
     """max_iterations = 0: the call stops where it starts, and the closure's s there is made c^2 to the bit (an information
     scaled until sqrt(s)^2 == s in fp64)"""
-    base = gs.chain(17, 1, seed=11, how="spread")
-    a, b, z, info0 = base["closures"][0]
-    for j in range(64):
-        s = dict(base, closures=[(a, b, z, info0 * (1.0 + j / 64.0))])
-        E = gs.edges(sage, s)
-        _, per = sage.graph_cost(s["poses"], E, s["odom_info"], per_edge=True)
-        scale = float(np.sqrt(per[-1]))
-        if scale * scale == per[-1] and per[-1] > 0.0:
-            break
-    else:
-        raise AssertionError("no information among 64 gives sqrt(s)^2 == s")
+    s, E, scale, _ = rs.exactly_at_a_scale(sage)
     _, out, info = sage.graph_optimize(s["poses"], E, s["odom_info"], where="host", return_info=True, max_iterations=0,
                                        robust=dict(kernel="huber", scale=scale))
     assert _bits(out) == _bits(s["poses"])
@@ -236,6 +226,14 @@ def test_a_closure_exactly_at_the_scale_under_huber(sage):
     _, _, info = sage.graph_optimize(s["poses"], E, s["odom_info"], where="host", return_info=True, max_iterations=0,
                                      robust=dict(kernel="huber", scale=float(np.nextafter(scale, 0.0))))
     assert info["closure_weight"][0] < 1.0
+
+
+def test_the_verdict_at_a_weight_of_exactly_a_half(sage):
+    rs.check_the_verdict_at_a_weight_of_a_half(sage, "host")
+
+
+def test_the_schedule_at_a_power_of_the_factor(sage):
+    rs.check_the_schedule_at_a_power_of_the_factor(sage, "host")
 
 
 def test_a_closure_of_1e12_under_gm(sage):
