@@ -75,7 +75,8 @@ typedef struct sageicp_comm sageicp_comm;     /* opaque: RCCL communicator for q
  * sageicp_map_archive_info / _clear / _voxels / _rows / _rows_device / _msg / _msg_device, sageicp_pipeline_set_archive;
  * then recall — sageicp_recall_info, sageicp_map_recall, sageicp_pipeline_recall; then loop closure —
  * sageicp_closure_info, sageicp_closure_corrections, sageicp_map_session_stays, sageicp_map_session_corrected / _device,
- * sageicp_pipeline_closure, sageicp_pipeline_session_corrected / _device
+ * sageicp_pipeline_closure, sageicp_pipeline_session_corrected / _device; then the session rebuild —
+ * sageicp_rebuild_info, sageicp_map_session_rebuild, sageicp_pipeline_session_rebuild
  * (additions only: no existing struct or entry changed). */
 #define SAGEICP_ABI_VERSION 4
 
@@ -1031,6 +1032,52 @@ int sageicp_pipeline_session_corrected(const sageicp_pipeline *p, int which, uin
 int sageicp_pipeline_session_corrected_device(const sageicp_pipeline *p, int which, uint64_t first, const double *corrections,
                                               uint64_t n, const sageicp_device_points *dst,
                                               void *stream /* hipStream_t; NULL = null stream */, uint64_t *n_out);
+
+/* ---- session rebuild: the corrected session voxelised again, into a map that can be searched ---------------
+ * Additions only; the ABI version stays; off unless called.  sageicp_map_session_corrected* returns rows: a street driven
+ * twice is in them twice, and rows cannot be searched.  sageicp_map_session_rebuild puts them through the map's own
+ * retention policy on the device and leaves a map.  Afterwards dst equals a fresh map of dst's voxel size and policy after
+ *   1. sageicp_map_add_points of the rows sageicp_map_session_corrected(src, which, 0, positions, corrections, n, ..)
+ *      returns, in that order, and
+ *   2. if `center` is given, sageicp_map_remove_far(center) at max_distance = radius — far as RemovePointsFarFromLocation
+ *      decides it, (p - center).squaredNorm() > radius * radius on the voxel's first stored row p, radius * radius formed once:
+ * the bytes and the order of sageicp_map_pointcloud (kept voxels in the order of their first arrival), sageicp_map_size and
+ * sageicp_map_num_voxels are the same, every later search gives the same answer and every later update behaves the same —
+ * where a region lies in the point array and a slot in the table may differ (no result depends on either), and so may
+ * the block a LATER update gives a new voxel: here every block below num_voxels is taken, there the evicted ones are free
+ * and handed out first (recall's caveat).  Unlike recall's, the voxels are new ones: a moved row is keyed by
+ * static_cast<int>(coordinate / voxel_size) of its MOVED coordinates, so the rows of one source voxel may land in several
+ * destination voxels; rows of source voxels of different passes and generations (SAGEICP_ARCHIVE_ALL) land in one, where
+ * they go through VoxelBlock::AddPoint in arrival order; and the crop is decided by the destination voxel's FINAL first
+ * stored row, which may be a later arrival that replaced an unlabelled first one.
+ * dst: cleared first, as by sageicp_map_clear (its own archive is left alone and nothing is logged into it; its own
+ * max_distance is unchanged), and it ends resident: filled on the device, nothing downloaded; from then on an ordinary map.
+ * info: what dst holds; the selection (what was moved and keyed); what the retention policy kept of it, before the crop;
+ * and built - held.
+ * SAGEICP_ERR_INVALID, dst untouched: dst's refusals are recall's (a null handle, dst == src, a dst whose voxel size,
+ * points per voxel or basic labels differ from src's, a dst in reference-order mode, spanning several devices or on
+ * another device than src's first) and more than 32 basic labels; src, which, positions, corrections and n have the
+ * refusals of sageicp_map_session_corrected; with a centre, a non-finite centre and a radius that is negative or NaN
+ * (center == NULL: everything is kept and radius is not looked at).  Device work: SAGEICP_ERR_NO_DEVICE without one.
+ * Found on the device: SAGEICP_ERR_INVALID, a moved coordinate that is not finite; SAGEICP_ERR_CAPACITY, a moved row's voxel
+ * index beyond +-2^20, more than 2^32 - 2 records or rows, more voxels / storage units than a map holds.  After any failure
+ * past the argument checks dst is left cleared and usable, never partly filled.  src is read as by the corrected export: a
+ * pending host tail of its archive is moved to the device first, a resident src stays resident.  Synchronous; the same
+ * bytes on every run.  The pipeline's entry takes the positions from the pipeline (n must be its number of poses) and
+ * returns SAGEICP_ERR_INVALID unless the archive's `updates` equals sageicp_pipeline_num_poses, as the closure entries do. */
+typedef struct sageicp_rebuild_info {
+    uint64_t voxels, rows;                  /* what dst holds now */
+    uint64_t session_voxels, session_rows;  /* the selection: what was moved and keyed */
+    uint64_t built_voxels, built_rows;      /* after the retention policy, before the crop */
+    uint64_t cropped_voxels, cropped_rows;  /* built - held */
+} sageicp_rebuild_info;
+int sageicp_map_session_rebuild(const sageicp_map *src, int which, const double *positions /* n x 3 */,
+                                const double *corrections /* n x 7 */, uint64_t n,
+                                const double center[3] /* NULL: keep everything, radius ignored */, double radius,
+                                sageicp_map *dst, sageicp_rebuild_info *info /* may be NULL */);
+int sageicp_pipeline_session_rebuild(const sageicp_pipeline *p, int which, const double *corrections /* n x 7 */, uint64_t n,
+                                     const double center[3] /* NULL: keep everything */, double radius, sageicp_map *dst,
+                                     sageicp_rebuild_info *info /* may be NULL */);
 
 /* ---- pose graph: several loop closures at once -------------------------------------------------------------
  * Additions only; the ABI version stays; off unless called.  sageicp_closure_corrections spreads ONE closure; applied one

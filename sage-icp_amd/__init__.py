@@ -15,6 +15,7 @@ The directory is named `sage-icp_amd`; import it as `sage_icp_amd` through the l
 /sage_icp_amd.py at the repo root.
 """
 import ctypes as C
+import math
 import os
 import sys
 
@@ -230,6 +231,15 @@ class RecallInfo(C.Structure):
     """sageicp_recall_info"""
     _fields_ = [(k, C.c_uint64) for k in ("voxels", "rows", "archive_voxels", "archive_rows", "map_voxels", "map_rows",
                                           "session_voxels", "session_rows")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class RebuildInfo(C.Structure):
+    """sageicp_rebuild_info"""
+    _fields_ = [(k, C.c_uint64) for k in ("voxels", "rows", "session_voxels", "session_rows", "built_voxels", "built_rows",
+                                          "cropped_voxels", "cropped_rows")]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -563,6 +573,10 @@ _SIGNATURES = [
     ("sageicp_pipeline_session_corrected", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _dp, C.c_uint64, _dp, C.c_uint64, _u64p]),
     ("sageicp_pipeline_session_corrected_device", C.c_int, [C.c_void_p, C.c_int, C.c_uint64, _dp, C.c_uint64,
                                                             C.POINTER(DevicePoints), C.c_void_p, _u64p]),
+    ("sageicp_map_session_rebuild", C.c_int, [C.c_void_p, C.c_int, _dp, _dp, C.c_uint64, _dp, C.c_double, C.c_void_p,
+                                              C.POINTER(RebuildInfo)]),
+    ("sageicp_pipeline_session_rebuild", C.c_int, [C.c_void_p, C.c_int, _dp, C.c_uint64, _dp, C.c_double, C.c_void_p,
+                                                   C.POINTER(RebuildInfo)]),
     ("sageicp_graph_params_default", None, [C.POINTER(GraphParams)]),
     ("sageicp_graph_edge_from_closed", C.c_int, [_dp, C.c_uint64, C.c_uint64, C.c_uint64, _dp, _dp, C.POINTER(GraphEdge)]),
     ("sageicp_graph_cost", C.c_int, [_dp, C.c_uint64, _dp, C.c_uint32, C.POINTER(GraphEdge), C.c_uint32, _dp, _dp, _dp]),
@@ -1271,6 +1285,16 @@ class VoxelHashMap:
                                lambda d, st, k: lib().sageicp_map_session_corrected_device(self._h, w, first, _p(pos), _p(corr), n,
                                                                                            d, st, k))
 
+    def RebuildSession(self, positions, corrections, which="session", center=None, radius=math.inf, into=None):
+        """CorrectedPointcloud(which)'s rows voxelised again under the map's retention policy, on the device, into the map
+        `into`: what a fresh map holds after AddPoints of those rows and, with a `center`, RemovePointsFarFromLocation
+        at max_distance = radius (sageicp_map_session_rebuild).  `into` is cleared first and ends
+        resident; None: a new map with this map's parameters on its device.  Returns (into, info dict)."""
+        pos, corr = _positions(positions), _corrections(corrections, positions)
+        w, n = _archive_which(which), pos.shape[0]
+        return _rebuild(lambda c, r, h, i: lib().sageicp_map_session_rebuild(self._h, w, _p(pos), _p(corr), n, c, r, h, i),
+                        self, center, radius, into)
+
     def resident(self):
         """True while the HBM copy of the map is the authority (after a device-side update)"""
         return bool(lib().sageicp_map_resident(self._h))
@@ -1960,6 +1984,19 @@ class SageICP:
                                lambda a, cap, k: lib().sageicp_pipeline_session_corrected(self._h, w, first, _p(corr), n, a, cap, k),
                                lambda d, st, k: lib().sageicp_pipeline_session_corrected_device(self._h, w, first, _p(corr), n, d, st, k))
 
+    def RebuildSessionMap(self, corrections, which="session", center=None, radius=math.inf, into=None):
+        """CorrectedSessionMap(corrections, which)'s rows voxelised again into the map `into` (None: a new map with the
+        local map's parameters): VoxelHashMap.RebuildSession with the pipeline's positions
+        (sageicp_pipeline_session_rebuild).  Returns (into, info dict).  The pipeline itself is not touched."""
+        corr = np.ascontiguousarray(corrections, dtype=np.float64)
+        if corr.ndim != 2 or corr.shape[1] != 7:
+            raise ValueError("corrections is (n, 7)")
+        w, n, c = _archive_which(which), corr.shape[0], self.config
+        like = VoxelHashMap(c.voxel_size_map, c.local_map_range, c.basic_points_per_voxel, c.critical_points_per_voxel,
+                            [c.basic_parts_labels[i] for i in range(c.n_basic_parts_labels)], device=c.device, _handle=0)
+        return _rebuild(lambda ctr, r, h, i: lib().sageicp_pipeline_session_rebuild(self._h, w, _p(corr), n, ctr, r, h, i),
+                        like, center, radius, into)
+
     def SessionMapMsg(self, colors, which="session", first=0, device=False, out=None):
         return _archive_msg(lambda: lib().sageicp_pipeline_local_map(self._h), self.config.device, colors, which, first, device,
                             out)
@@ -1991,6 +2028,21 @@ def _recall(entry, handle, like, center, radius, into):
                             like.basic_parts_labels_, device=like.device)
     info = RecallInfo()
     _check(entry(handle, c.ctypes.data_as(_dp), float(radius), into._h, C.byref(info)))
+    return into, info.as_dict()
+
+
+def _rebuild(entry, like, center, radius, into):
+    """`like`: the VoxelHashMap (or its parameters) a fresh destination is created from; entry(center, radius, dst, info)"""
+    c = None
+    if center is not None:
+        c = np.ascontiguousarray(center, dtype=np.float64).reshape(-1)
+        if c.size != 3:
+            raise ValueError("RebuildSession takes a centre[3]")
+    if into is None:
+        into = VoxelHashMap(like.voxel_size_, like.max_distance_, like.basic_points_per_voxel_, like.critical_points_per_voxel_,
+                            like.basic_parts_labels_, device=like.device)
+    info = RebuildInfo()
+    _check(entry(c.ctypes.data_as(_dp) if c is not None else None, float(radius), into._h, C.byref(info)))
     return into, info.as_dict()
 
 

@@ -15,8 +15,9 @@ SOURCES = ["csrc/kernels.hip", "csrc/sort.hip", "csrc/preprocess.hip", "csrc/dyn
            "csrc/capi_outputs.hip", "csrc/caller_mem.hip", "csrc/correspond.hip", "csrc/quality.hip", "csrc/score.hip",
            "csrc/capi_query.hip", "csrc/capi_relocalize.hip", "csrc/archive.hip", "csrc/capi_archive.hip",
            "csrc/place.hip", "csrc/capi_place.hip", "csrc/recall.hip", "csrc/capi_recall.hip",
-           "csrc/closure.hip", "csrc/capi_closure.hip", "csrc/posegraph.hip", "csrc/capi_posegraph.hip"]
-HEADERS = ["csrc/kernels.h", "csrc/dev_buffer.h", "csrc/sageicp_types.h", "csrc/se3_math.h", "csrc/host_map.hpp", "csrc/pipeline.hpp", "csrc/map_update.h", "csrc/egress.h", "csrc/msg.h", "csrc/metrics.hpp", "csrc/robin_order.hpp", "csrc/capi_internal.h", "csrc/knobs.h", "csrc/prep.h", "csrc/prefetch.h", "csrc/dyn_rules.h", "csrc/probes.h", "csrc/icp_body.h", "csrc/row_shift.h", "csrc/fin_kernel.h", "csrc/loop_kernel.h", "csrc/loop_deal.h", "csrc/caller_mem.h", "csrc/outputs.h", "csrc/map_device.h", "csrc/replay_pool.h", "csrc/correspond.h", "csrc/quality.h", "csrc/score.h", "csrc/accept.h", "csrc/archive.h", "csrc/query.h", "csrc/place.h", "csrc/recall.h", "csrc/closure.h", "csrc/posegraph.h",
+           "csrc/closure.hip", "csrc/capi_closure.hip", "csrc/posegraph.hip", "csrc/capi_posegraph.hip",
+           "csrc/rebuild.hip", "csrc/capi_rebuild.hip"]
+HEADERS = ["csrc/kernels.h", "csrc/dev_buffer.h", "csrc/sageicp_types.h", "csrc/se3_math.h", "csrc/host_map.hpp", "csrc/pipeline.hpp", "csrc/map_update.h", "csrc/egress.h", "csrc/msg.h", "csrc/metrics.hpp", "csrc/robin_order.hpp", "csrc/capi_internal.h", "csrc/knobs.h", "csrc/prep.h", "csrc/prefetch.h", "csrc/dyn_rules.h", "csrc/probes.h", "csrc/icp_body.h", "csrc/row_shift.h", "csrc/fin_kernel.h", "csrc/loop_kernel.h", "csrc/loop_deal.h", "csrc/caller_mem.h", "csrc/outputs.h", "csrc/map_device.h", "csrc/replay_pool.h", "csrc/correspond.h", "csrc/quality.h", "csrc/score.h", "csrc/accept.h", "csrc/archive.h", "csrc/query.h", "csrc/place.h", "csrc/recall.h", "csrc/closure.h", "csrc/posegraph.h", "csrc/rebuild.h", "csrc/rebuild_rule.h",
            "../include/sageicp.h"]
 OUT = os.path.join(HERE, "libsageicp_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")

@@ -113,6 +113,9 @@ struct ClosureJob {
     uint32_t voxels[2] = {0, 0}, rows[2] = {0, 0};   // what the one wait brings back
 };
 
+}  // namespace
+
+// (capi_internal.h: the rebuild's entries make the same checks)
 int check_selection(const sageicp_map *m, int which, const double *positions, uint64_t n, const uint64_t *n_out, const char *who) {
     const std::string w(who);
     if (!m || !positions || !n_out) return fail(SAGEICP_ERR_INVALID, w + ": null argument");
@@ -122,6 +125,8 @@ int check_selection(const sageicp_map *m, int which, const double *positions, ui
     if (!finite_n(positions, 3 * n)) return fail(SAGEICP_ERR_INVALID, w + ": a position is not finite");
     return SAGEICP_OK;
 }
+
+namespace {
 
 // the selection of `which`, every voxel's stay, and the one wait for the totals
 int stays(ClosureJob &j, const double *positions, uint64_t n) {
@@ -209,6 +214,8 @@ int session_corrected(sageicp_map &m, int which, uint64_t first, const double *p
     return rc;
 }
 
+}  // namespace
+
 int check_corrections(const double *corr, uint64_t n, const char *who) {
     if (!corr) return fail(SAGEICP_ERR_INVALID, std::string(who) + ": null argument");
     if (!finite_n(corr, 7 * n)) return fail(SAGEICP_ERR_INVALID, std::string(who) + ": a correction is not finite");
@@ -235,7 +242,6 @@ int pipeline_positions(const sageicp_pipeline *p, const char *who, std::vector<d
     return SAGEICP_OK;
 }
 
-}  // namespace
 }  // namespace sageicp_impl
 
 extern "C" {

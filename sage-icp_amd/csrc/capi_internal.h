@@ -463,6 +463,12 @@ struct SessionParts {
 // verdicts decide (the mirror refreshed for them, as before any search); otherwise every record is a candidate
 int session_archive_part(sageicp_map &src, hipStream_t s, bool latest_only, SessionParts &sp);
 int session_live_part(sageicp_map &src, hipStream_t s, SessionParts &sp);   // (after session_archive_part(.., true, ..): it reads the mirror)
+bool same_policy(const HostMap &a, const HostMap &b);      // capi_recall.hip: voxel size, points per voxel, basic labels
+// capi_closure.hip: the argument checks of the closure entries (`who`: the entry, for the message), and a pipeline's
+// positions (and poses) where serial s of its archive is pose s — shared with the rebuild's entries (capi_rebuild.hip)
+int check_selection(const sageicp_map *m, int which, const double *positions, uint64_t n, const uint64_t *n_out, const char *who);
+int check_corrections(const double *corr, uint64_t n, const char *who);
+int pipeline_positions(const sageicp_pipeline *p, const char *who, std::vector<double> &pos, std::vector<double> *poses);
 // capi_archive.hip: RemovePointsFarFromLocation on the host copy of one handle, the evicted voxels into its archive while on
 void host_remove_far(sageicp_map &m, const double origin[3]);
 // capi_run.hip

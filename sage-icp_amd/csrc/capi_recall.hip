@@ -198,11 +198,12 @@ int recall(sageicp_map &src, const double center[3], double radius, sageicp_map 
     return rc;
 }
 
+}  // namespace
+
 bool same_policy(const HostMap &a, const HostMap &b) {
     return a.voxel_size == b.voxel_size && a.basic == b.basic && a.critical == b.critical && a.basic_labels == b.basic_labels;
 }
 
-}  // namespace
 }  // namespace sageicp_impl
 
 extern "C" {

@@ -165,6 +165,17 @@ struct VoxelHashMap {
         }
         return VoxelHashMap(*this, radius, dst);
     }
+    // The session rebuilt (include/sageicp.h "session rebuild"): CorrectedPointcloud()'s rows voxelised
+    // again under this map's retention policy, on the device, as a map that can be searched — a street driven twice is in
+    // it once.  With (center, radius): only the voxels whose first point lies within `radius` of `center`, as a map of
+    // max_distance = radius; without: everything, max_distance as this map's.  Block-pool order, like Recall's.
+    VoxelHashMap RebuiltMap(const std::vector<Eigen::Vector3d> &positions, const std::vector<std::array<double, 7>> &corrections) const {
+        return Rebuilt(positions, corrections, nullptr, max_distance_);
+    }
+    VoxelHashMap RebuiltMap(const std::vector<Eigen::Vector3d> &positions, const std::vector<std::array<double, 7>> &corrections,
+                            const Eigen::Vector3d &center, double radius) const {
+        return Rebuilt(positions, corrections, center.data(), radius);
+    }
     // HIP device ordinal for maps created by this process (one process per GPU); set it before
     // the first map is constructed, e.g. from LOCAL_RANK.
     static int &Device() {
@@ -198,6 +209,22 @@ private:
         if (rc != SAGEICP_OK)
             throw std::runtime_error(std::string("sage_icp::VoxelHashMap::") + what + ": " +
                                      sageicp_last_error());
+    }
+    VoxelHashMap Rebuilt(const std::vector<Eigen::Vector3d> &positions, const std::vector<std::array<double, 7>> &corrections,
+                         const double *center, double radius) const {
+        if (positions.empty() || positions.size() != corrections.size())
+            throw std::runtime_error("sage_icp::VoxelHashMap::RebuiltMap: one correction per position, at least one");
+        sageicp_map *dst = sageicp_map_create(voxel_size_, radius, basic_points_per_voxel_, critical_points_per_voxel_,
+                                              basic_parts_labels_.data(), static_cast<int>(basic_parts_labels_.size()), Device());
+        if (!dst) throw std::runtime_error(std::string("sageicp_map_create: ") + sageicp_last_error());
+        const int rc = sageicp_map_session_rebuild(map_, SAGEICP_SESSION, positions.front().data(), corrections.front().data(),
+                                                   positions.size(), center, radius, dst, nullptr);
+        if (rc != SAGEICP_OK) {
+            const std::string why = sageicp_last_error();
+            sageicp_map_destroy(dst);
+            throw std::runtime_error("sage_icp::VoxelHashMap::RebuiltMap: " + why);
+        }
+        return VoxelHashMap(*this, radius, dst);
     }
     Vector4dVector ArchiveRows(int which, const char *what) const {
         uint64_t n = 0;
